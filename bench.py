@@ -7,7 +7,7 @@ scene, no external data), and for N > 1 the ranks' packed colour tiles (1 / N of
 collective over xGMI and scattered into the frame there.
 Scene, BVH and all buffers are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080 --spp 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080 --spp 256] [--dump-outputs DIR]
     N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
             or plainly `python bench.py --gpus N ...`: without WORLD_SIZE in the environment bench.py starts that launcher itself as a
@@ -28,6 +28,12 @@ instantiation next to it.  Plus
                   construction, both reported under `counters`).
                   SURVEY.md section 8d's algorithmic-bytes figure stays as a side field (it counts reads that LDS serves).
   "cpu_baseline": the CPU oracle (a from-scratch port; the reference has no CPU path) timed on the host cores
+
+--dump-outputs DIR writes what the headline's last timed step computed, the float32 H x W x RGBA AOVs a caller of render_device
+receives, as DIR/color.npy, DIR/albedo.npy and DIR/normal.npy (N > 1: rank 0's gathered colour frame only).  Frames of more than
+2^20 pixels are cut to one fixed sample of 2^20 pixels, the same in every file (numpy default_rng(0), sorted row-major pixel indices;
+shape (2^20, 4)), which keeps the three files under 64 MB.  The inputs depend only on the arguments, so two builds run with the same
+arguments can be compared file for file.
 """
 import argparse
 import json
@@ -150,6 +156,25 @@ def stress_secondary(lib_path, spheres, segments, env=None):
                          "definition": "(FETCH_SIZE x 2 + WRITE_SIZE) counter bytes per launch / kernel time: fabric-side traffic, the scene (~70 MB) is Infinity-Cache resident"}}
 
 
+DUMP_SAMPLE_PIXELS = 1 << 20  # 3 AOVs x 2^20 pixels x 16 B = 48 MiB: under the 64 MB cap of --dump-outputs
+
+
+def dump_outputs(out_dir, aovs):
+    """--dump-outputs: saves each (H, W, 4) float32 device tensor of `aovs` as out_dir/<name>.npy, frames of more than
+    DUMP_SAMPLE_PIXELS pixels as the same seeded pixel sample of every AOV (module docstring)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, ch = next(iter(aovs.values())).shape
+    idx = None
+    if h * w > DUMP_SAMPLE_PIXELS:
+        pick = np.sort(np.random.default_rng(0).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+        idx = torch.from_numpy(pick).to(next(iter(aovs.values())).device)
+    for name, t in aovs.items():
+        a = t if idx is None else t.reshape(h * w, ch).index_select(0, idx)
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -169,7 +194,11 @@ def main():
     ap.add_argument("--cpu-spp", type=int, default=1024, help="spp of the bounded CPU-baseline sample (the metric's RMSE is quoted at 1024 spp)")
     ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("HJR_CPU_THREADS", "16")),
                     help="oracle threads for the CPU baseline (a 1-GPU box's CPU share is 16 cores)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the AOVs of the headline's last timed step to DIR/<name>.npy (float32, at most 64 MB; module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- started plainly with --gpus N > 1: become the launcher.  One rank process per GPU through torch.distributed.run, as a CHILD
     #      process (never an exec of this one), before torch is imported or the GPU is touched; rank 0 of the child prints the JSON line
@@ -336,6 +365,8 @@ def main():
         fast_frame = fb.clone()
         params = params_exact
     elapsed, kernel_ms, pipe_full = timed(step_full)  # the headline: EXACTLY args.steps steps between the fences
+    if args.dump_outputs and rank == 0:  # before the counting and CPU-baseline launches below reuse fb
+        dump_outputs(args.dump_outputs, {"color": fb} if world > 1 else {"color": fb, "albedo": fb_albedo, "normal": fb_normal})
     if world == 1:
         d2 = (fast_frame[..., :3].double() - fb[..., :3].double()) ** 2
         fast_block = {"value": round(float(W) * H * SPP * args.steps / elapsed_fast / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(elapsed_fast / args.steps * 1e3, 3),

@@ -7,7 +7,7 @@ import sys
 
 import pytest
 
-from scene_util import ROOT
+from scene_util import ROOT, hjr
 
 pytestmark = pytest.mark.gpu
 REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -43,6 +43,40 @@ def test_bench_single_gpu_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == "Msamples/s"
     assert c["rmse_gpu_vs_cpu"]["value"] < 1e-3 * 50  # 2 spp here: a smoke value; the 1024-spp bar is checked in test_gpu_parity.py
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the AOVs of the headline's last timed step as float32 DIR/<name>.npy, equal to a direct render of the same
+    frame through the package whatever --steps is; a 1920x1080 frame is cut to the fixed 2^20-pixel sample, under 64 MB in all."""
+    import numpy as np
+    quick = ["--warmup", "1", "--no-pmc", "--no-cpu-baseline", "--no-secondary"]
+    for d, steps in (("a", 1), ("b", 3)):
+        r = run([sys.executable, "bench.py", "--width", "320", "--height", "200", "--spp", "8", "--steps", str(steps),
+                 "--dump-outputs", str(tmp_path / d)] + quick)
+        assert r["steps"] == steps
+    cwd = os.getcwd()
+    os.chdir(hjr.ASSETS)
+    try:
+        rd = hjr.Renderer(0)
+        rd.loadRenderOption("render_option_c2.json")
+        rd.render_option.image_width, rd.render_option.image_height, rd.render_option.max_spp = 320, 200, 8
+        rd.render_option.integrator = hjr.INTEGRATOR_NEE
+        rd.loadGLTFfile(rd.render_option.gltf_path.decode(), rd.render_option.gltf_name.decode())
+        rd.build()
+    finally:
+        os.chdir(cwd)
+    want = dict(zip(("color", "albedo", "normal"), rd.render_frame(rd.render_option.start_frame)))
+    assert np.any(want["color"][..., :3] > 0)
+    for name, ref in want.items():
+        for d in ("a", "b"):
+            got = np.load(str(tmp_path / d / (name + ".npy")))
+            assert got.dtype == np.float32 and got.shape == (200, 320, 4), (name, got.dtype, got.shape)
+            assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (name, d)
+    run([sys.executable, "bench.py", "--width", "1920", "--height", "1080", "--spp", "1", "--steps", "1", "--dump-outputs", str(tmp_path / "c")] + quick)
+    files = sorted(os.listdir(str(tmp_path / "c")))
+    assert files == ["albedo.npy", "color.npy", "normal.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "c" / f)) for f in files) <= 64e6
+    assert all(np.load(str(tmp_path / "c" / f)).shape == (1 << 20, 4) for f in files)
 
 
 def test_bench_two_rank_rehearsal():
