@@ -97,9 +97,7 @@ extern "C" void hjr_destroy(hjr_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (DevBuf* b : { &c->d_nodes, &c->d_tri_geom, &c->d_tri_shade, &c->d_tri_inst, &c->d_materials, &c->d_lights, &c->d_lut, &c->d_spill, &c->d_wf_ctx, &c->d_tiles, &c->d_tile_cost, &c->d_dn_a, &c->d_dn_b, &c->d_dn_out,
-                       &c->d_texels, &c->d_tex_desc, &c->d_srgb_lut, &c->d_sky, &c->d_work, &c->d_color, &c->d_albedo, &c->d_normal, &c->d_part_color, &c->d_part_albedo, &c->d_part_normal })
-        b->release();
+    c->release_buffers();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -224,9 +222,6 @@ extern "C" int hjr_set_lut(hjr_ctx* c, const uint8_t* rgba, int w, int h)
     return HJR_OK;
 }
 
-
-// persistent grid = resident workgroups only: CUs x (workgroups the kernel's VGPR/LDS budget admits per CU), capped by the
-// number of wavefront-sized batches of work; HJR_BLOCKS_PER_CU overrides the occupancy query
 extern "C" int hjr_set_sky(hjr_ctx* c, const float* rgba, int w, int h)
 {
     if (!c) { set_error("hjr_set_sky: null context"); return HJR_ERR_ARG; }
@@ -240,23 +235,22 @@ extern "C" int hjr_set_sky(hjr_ctx* c, const float* rgba, int w, int h)
 
 // the render kernels live in their own translation units (hjr_launch.hip.h)
 #ifndef HJR_LEAN_VARIANT
-extern template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
-extern template int hjr_launch<HJR_INTEGRATOR_NEE, true>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
-extern template int hjr_launch<HJR_INTEGRATOR_PT, false>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
-extern template int hjr_launch<HJR_INTEGRATOR_PT, true>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
-extern template int hjr_launch<HJR_INTEGRATOR_MIS, false>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
-extern template int hjr_launch<HJR_INTEGRATOR_MIS, true>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
+extern template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+extern template int hjr_launch<HJR_INTEGRATOR_NEE, true>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+extern template int hjr_launch<HJR_INTEGRATOR_PT, false>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+extern template int hjr_launch<HJR_INTEGRATOR_PT, true>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+extern template int hjr_launch<HJR_INTEGRATOR_MIS, false>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+extern template int hjr_launch<HJR_INTEGRATOR_MIS, true>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
 #endif
 #if !defined(HJR_LEAN_VARIANT) && !defined(HJR_UNITY)
-template <int I> int hjr_launch_fast(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t); // hjr_launch_fast_*.hip (HJR_FLAG_FAST_MATH)
-extern template int hjr_launch_fast<HJR_INTEGRATOR_NEE>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
-extern template int hjr_launch_fast<HJR_INTEGRATOR_PT>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
+template <int I> int hjr_launch_fast(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t); // hjr_launch_fast_*.hip (HJR_FLAG_FAST_MATH)
+extern template int hjr_launch_fast<HJR_INTEGRATOR_NEE>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+extern template int hjr_launch_fast<HJR_INTEGRATOR_PT>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
 #define HJR_HAVE_FAST 1
 #endif
 #ifdef HJR_UNITY /* diagnostic variants (make variant): one translation unit, so that the __device__ diagnostic counters are one symbol */
 #ifdef HJR_LEAN_VARIANT /* NEE without the statistics counters only; every other launch runs that kernel too (timing experiments, not pictures) */
-#include "hjr_launch.hip.h"
-template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
+template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
 #else
 #include "hjr_launch_nee.hip"
 #include "hjr_launch_pt.hip"
@@ -264,63 +258,151 @@ template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const KParams&, uin
 #endif
 #endif
 
-static int render_impl(hjr_ctx* c, const hjr_params* p, void* d_color, void* d_albedo, void* d_normal, hipStream_t st)
+// descent loops of the fused traversals (hjr_traverse.hip.h): lanes still descending below which a pass moves on to the leaves
+#ifndef HJR_NODE_MIN_LDS
+#define HJR_NODE_MIN_LDS 6     /* megakernel, LDS-resident scenes (round 2, with AOVs, 1 / 4 / 8 / 12 / 16: 139.8 / 128.9 / 129.8 / 135.2 / 140.4 ms; round 3 with a carry-over of 14 lanes, 4 / 5 / 6 / 7 / 8: 110.1 / 109.6 / 109.15 / 109.05 / 109.3) */
+#endif
+#ifndef HJR_NODE_MIN_LDS_WF
+#define HJR_NODE_MIN_LDS_WF 8  /* wavefront kernel, LDS-resident scenes (1 / 4 / 8 / 12 / 16: 132.4 / 125.4 / 124.8 / 125.7 / 126.4 ms) */
+#endif
+#ifndef HJR_NODE_MIN_MEM
+#define HJR_NODE_MIN_MEM 24    /* scenes read from memory (1 M triangles, 1 / 8 / 16 / 24 / 32: megakernel 280 / 197 / 180 / 179 / 190 ms, wavefront 255 / 213 / 194 / 189 / 192) */
+#endif
+#ifndef HJR_TOP_NODES
+#define HJR_TOP_NODES 85 /* memory layouts, BVH4: nodes of the top of the tree (levels 0 - 3) staged in LDS per workgroup (option "top_nodes"; 1 M triangles, 0 / 21 / 85 / 140 / 200 / 341: 166.9 / 165.9 / 164.6 / 164.5 / 164.6 / 273.7 ms — the last one loses a workgroup per CU) */
+#endif
+#ifndef HJR_HOLD_MIN
+#define HJR_HOLD_MIN 8 /* megakernel: lanes of the rare material class (multiple-scattering GGX) a wave collects before it shades them (0: never hold; C2 with AOVs, 0 / 4 / 8 / 16 / 32: 129.0 / 126.5 / 126.2 / 127.9 / 144.2 ms) */
+#endif
+#ifndef HJR_HOLD_AGE
+#define HJR_HOLD_AGE 2 /* ... or rounds the oldest of them has waited */
+#endif
+
+// Kernel family, layout, variant, grid shape, LDS split and traversal tuning of one render launch.  `fast`: an approximate-arithmetic
+// launch (hjr_launch_fast_*.hip hold the megakernel family only).
+static LaunchPlan plan_launch(const hjr_ctx* c, const KParams& kp, uint64_t n_items, int lds_mode, int integrator, bool fast)
+{
+    LaunchPlan pl;
+    pl.kp = kp; pl.lds_mode = lds_mode;
+    // the albedo / normal AOV sums cost 6 VGPRs per lane: a separate variant for callers that only want aov_color
+    pl.var = (kp.tex_desc || kp.sky_tex) ? 2 : ((kp.aov_albedo || kp.aov_normal) ? 1 : 0);
+    const bool lds_layout = lds_mode == 1 || lds_mode == 2;
+    const size_t scene_bytes = ((size_t)kp.n_node_f4 + kp.n_tri_f4 + kp.n_mat_f4 + kp.n_light_f4) * 16;
+    const uint32_t short_stack = (uint32_t)c->opt.get(hjr::OPT_SHORT_STACK, HJR_SHORT_STACK); // tests force the overflow path with 2
+    // Two kernel families produce the same bits (hjr_kernel.hip.h / hjr_wavefront.hip.h); which one is faster depends on the launch
+    // (MI355X, profiles/r02_experiments.md §4).  Bundled scene (LDS-resident), 1080p x 256 spp: MIS 193 ms wavefront vs 234 ms megakernel
+    // (the NEE shadow ray and the next closest-hit ray of its bounce are traced by sorted, full waves), NEE colour-only 126.7 vs 126.6,
+    // NEE with albedo / normal AOVs 145.7 vs 128.9, Pathtrace 104.7 vs 91.2.  Scenes read from memory (1 M triangles, 1080p x 64 spp):
+    // MIS 416 vs 635 ms, NEE 188 vs 179.  So: MIS -> wavefront kernel, everything else -> megakernel.  option "pipeline" overrides.
+    const int pe = c->opt.get(hjr::OPT_PIPELINE, 0); // option "pipeline": 1 megakernel, 2 wavefront kernel
+    bool wf = integrator == HJR_INTEGRATOR_MIS;
+    if (pe) wf = pe == 2;
+    // the wavefront kernel's queue positions are free-running 32-bit counters per workgroup (hjr_wavefront.hip.h::WfShared): a context is
+    // queued at most ~12 times per sample; frames that could bring one workgroup near 2^32 pushes (4x its even share) stay with the megakernel
+    if ((double)n_items * kp.chunk_spp * 12.0 * 4.0 / (double)(c->n_cus > 0 ? c->n_cus : 1) >= 4.0e9) wf = false;
+#ifdef HJR_LEAN_VARIANT /* kernel experiments (make variant X="-DHJR_LEAN_VARIANT ..."): only the megakernel is instantiated: builds in seconds */
+    wf = false;
+#endif
+    if (wf && !fast) {
+        // Workgroup-local wavefront kernel (hjr_wavefront.hip.h): one 1024-thread workgroup per CU for every layout.  LDS holds the top of
+        // the traversal stacks, the scene tables (LDS layouts), the queue header, the hit slots and the id rings; what is left after the
+        // fixed parts decides how many stack entries per lane stay in LDS (the rest overflows to HBM).
+        uint32_t cap = lds_layout ? 2048 : 4096; // contexts per workgroup: more of them in flight pay when every node comes from memory (1 M triangles: 272 -> 259 ms)
+        { const int v = c->opt.get(hjr::OPT_WF_CAP, (int)cap); if ((v & (v - 1)) == 0) cap = (uint32_t)v; }
+        const size_t fixed = (lds_layout ? scene_bytes : 0) + 96 + (size_t)HJR_WF_QUEUES * cap * 2;
+        const size_t lds_max = 160u * 1024u;
+        if (fixed + (size_t)HJR_BLOCK_LDS * 4 * 4 <= lds_max) { // at least four stack entries per lane fit; otherwise: megakernel
+            uint32_t lds_entries = std::min<uint32_t>((uint32_t)((lds_max - fixed) / ((size_t)HJR_BLOCK_LDS * 4)), kp.stack_depth);
+            if ((!lds_layout || c->opt.is_set(hjr::OPT_SHORT_STACK)) && lds_entries > short_stack) lds_entries = short_stack;
+            pl.wf = true; pl.block = HJR_BLOCK_LDS;
+            pl.wf_spill = !(lds_layout && lds_entries >= kp.stack_depth); // false: whole stacks in LDS
+            pl.smem = (size_t)HJR_BLOCK_LDS * lds_entries * 4 + fixed;
+            pl.kp.wf_cap = cap; pl.kp.stack_lds_entries = lds_entries;
+            pl.kp.wf_refill = (uint32_t)c->opt.get(hjr::OPT_WF_REFILL, HJR_WF_REFILL); // tuning options
+            pl.kp.wf_trace_min = (uint32_t)c->opt.get(hjr::OPT_WF_TRACE_MIN, HJR_WF_TRACE_MIN); pl.kp.wf_prefetch_min = (uint32_t)c->opt.get(hjr::OPT_WF_PREFETCH_MIN, HJR_WF_PREFETCH_MIN);
+        }
+    }
+    pl.kp.hold_min = (uint32_t)c->opt.get(hjr::OPT_HOLD_MIN, HJR_HOLD_MIN); pl.kp.hold_age = (uint32_t)c->opt.get(hjr::OPT_HOLD_AGE, HJR_HOLD_AGE); // tuning options
+    const uint32_t nm_forced = (uint32_t)c->opt.get(hjr::OPT_NODE_MIN, 0); // option "node_min"
+    pl.kp.node_min = nm_forced ? nm_forced : (lds_layout ? (pl.wf ? HJR_NODE_MIN_LDS_WF : HJR_NODE_MIN_LDS) : HJR_NODE_MIN_MEM);
+    if (pl.wf) return pl;
+    if (lds_layout) { // megakernel, BVH2 + tables staged in LDS: one workgroup per CU, whole stacks in LDS
+        pl.block = HJR_BLOCK_LDS; pl.spill_buf = false;
+        pl.smem = (((size_t)HJR_BLOCK_LDS * kp.stack_depth * (lds_mode == 2 ? 2 : 4) + 15) / 16) * 16 + scene_bytes;
+        return pl;
+    }
+    // megakernel, scene read from memory: short stacks in LDS, BVH4 with the top of the tree (breadth-first ids: the first nodes) next to
+    // them, sized so that four workgroups still share a CU
+    const uint32_t lds_entries = std::min<uint32_t>(kp.stack_depth, short_stack);
+    const uint32_t n_top = lds_mode == 0 ? std::min<uint32_t>((uint32_t)c->opt.get(hjr::OPT_TOP_NODES, HJR_TOP_NODES), kp.n_node_f4 / HJR_NODE4_F4) : 0u;
+    pl.smem = (((size_t)HJR_BLOCK * lds_entries * 4 + 15) / 16) * 16 + (size_t)n_top * HJR_NODE4_F4 * 16;
+    pl.set_smem = pl.smem > 48 * 1024;
+    pl.per_cu = c->opt.is_set(hjr::OPT_BLOCKS_PER_CU) ? c->opt.get(hjr::OPT_BLOCKS_PER_CU, 0) : 0;
+    pl.kp.stack_lds_entries = lds_entries; pl.kp.n_top_nodes = n_top;
+    return pl;
+}
+
+// this rank's share of a frame
+struct FrameGeom {
+    uint32_t world, tiles_x, chunk_spp, n_chunks;
+    uint64_t owned, n_items;
+    int lds_mode; // LaunchPlan::lds_mode of the frame data
+};
+
+// argument checks and tile geometry
+static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_color, FrameGeom& g)
 {
     if (!c || !p || !d_color) { set_error("hjr_render: null argument"); return HJR_ERR_ARG; }
     if (!c->have_scene || !c->have_frame) { set_error("hjr_render: upload a scene and set transforms first"); return HJR_ERR_STATE; }
     if (p->width == 0 || p->height == 0 || p->spp == 0) { set_error("hjr_render: width, height and spp must be positive"); return HJR_ERR_ARG; }
     if (p->width > 8192 || p->height > 8192) { set_error("hjr_render: frames larger than 8192 x 8192 are not supported"); return HJR_ERR_ARG; }
     if (p->integrator > HJR_INTEGRATOR_MIS) { set_error("hjr_render: unknown integrator"); return HJR_ERR_ARG; }
-    const uint32_t world = p->world_size ? p->world_size : 1u;
-    if (p->rank >= world) { set_error("hjr_render: rank >= world_size"); return HJR_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-
-    const uint32_t tiles_x = (p->width + HJR_TILE - 1) / HJR_TILE, tiles_y = (p->height + HJR_TILE - 1) / HJR_TILE;
-    const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
-    const uint64_t owned = (n_tiles > p->rank) ? (n_tiles - p->rank + world - 1) / world : 0;
-    const uint32_t chunk_spp = hjr_chunk_spp(p->spp), n_chunks = hjr_n_chunks(p->spp);
-    const uint64_t n_items = owned * n_chunks * 64;
+    g.world = p->world_size ? p->world_size : 1u;
+    if (p->rank >= g.world) { set_error("hjr_render: rank >= world_size"); return HJR_ERR_ARG; }
+    g.tiles_x = (p->width + HJR_TILE - 1) / HJR_TILE;
+    const uint64_t n_tiles = (uint64_t)g.tiles_x * ((p->height + HJR_TILE - 1) / HJR_TILE);
+    g.owned = (n_tiles > p->rank) ? (n_tiles - p->rank + g.world - 1) / g.world : 0;
+    g.chunk_spp = hjr_chunk_spp(p->spp); g.n_chunks = hjr_n_chunks(p->spp);
+    g.n_items = g.owned * g.n_chunks * 64;
     // the 32-bit queue head overshoots n_items by at most 64 per wave of the persistent grid (every wave stops fetching once it
     // has seen the queue dry, hjr_kernel.hip.h); 2^24 covers 262 144 waves, far more than any resident grid
-    if (n_items >= 0xffffffffull - (1ull << 24)) { set_error("hjr_render: image too large (more than 2^32 - 2^24 work items per launch)"); return HJR_ERR_ARG; }
+    if (g.n_items >= 0xffffffffull - (1ull << 24)) { set_error("hjr_render: image too large (more than 2^32 - 2^24 work items per launch)"); return HJR_ERR_ARG; }
+    // node format / LDS staging were decided by the host builder for this frame (host/frame.cpp)
+    g.lds_mode = c->frame.lds_mode;
+    if (g.lds_mode == 0 && c->frame.width == 2) g.lds_mode = 3;
+    return HJR_OK;
+}
 
-    // work area: [0] queue head, [16..] HJR_NSTAT uint64 counters
-    const size_t nan_list_at = 16 + (HJR_NSTAT + 20) * 8 + 32 + 512;
-    const size_t work_bytes = nan_list_at + (1 + HJR_NAN_LIST) * 8; // +20: phase clocks / lane-occupancy sums of the HJR_TIMING diagnostic build; +32: tile-class counters
-    if (c->d_work.cap < work_bytes) {
-        std::vector<unsigned char> z(work_bytes, 0);
-        if (!c->d_work.upload(z.data(), work_bytes, st)) { set_error("hjr_render: work buffer allocation failed"); return HJR_ERR_DEVICE; }
+// work area, output zeroing, chunk-sum buffers, and the kernel parameters of scene, frame and outputs
+static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void* d_color, void* d_albedo, void* d_normal, hipStream_t st, KParams& kp)
+{
+    if (c->d_work.cap < WorkArea::BYTES) {
+        std::vector<unsigned char> z(WorkArea::BYTES, 0);
+        if (!c->d_work.upload(z.data(), WorkArea::BYTES, st)) { set_error("hjr_render: work buffer allocation failed"); return HJR_ERR_DEVICE; }
     }
-    HIPCHK(hipMemsetAsync(c->d_work.p, 0, work_bytes, st));
+    HIPCHK(hipMemsetAsync(c->d_work.p, 0, WorkArea::BYTES, st));
     const size_t img_bytes = (size_t)p->width * p->height * 16;
     const bool packed = (p->flags & HJR_FLAG_PACKED) != 0;
-    if (!packed && world > 1 && (p->flags & HJR_FLAG_ZERO_UNOWNED)) {
+    if (!packed && g.world > 1 && (p->flags & HJR_FLAG_ZERO_UNOWNED)) {
         HIPCHK(hipMemsetAsync(d_color, 0, img_bytes, st));
         if (d_albedo) HIPCHK(hipMemsetAsync(d_albedo, 0, img_bytes, st));
         if (d_normal) HIPCHK(hipMemsetAsync(d_normal, 0, img_bytes, st));
     }
 
-    KParams kp;
     memset(&kp, 0, sizeof(kp));
-    kp.n_owned_tiles = (uint32_t)owned;
-    if (n_chunks > 1) {
+    kp.n_owned_tiles = (uint32_t)g.owned;
+    if (g.n_chunks > 1) {
         // chunk sums of THIS rank's tiles only: [chunk][owned tile][64] float4 (1/world of the frame; allocated once per size)
-        const size_t part_bytes = (size_t)owned * 64u * 16u * n_chunks;
+        const size_t part_bytes = (size_t)g.owned * 64u * 16u * g.n_chunks;
         DevBuf* pb[3] = { &c->d_part_color, &c->d_part_albedo, &c->d_part_normal };
         void* want[3] = { d_color, d_albedo, d_normal };
-        for (int i = 0; i < 3; i++) {
-            if (!want[i]) continue;
-            if (pb[i]->cap < part_bytes) {
-                pb[i]->release();
-                if (hipMalloc(&pb[i]->p, part_bytes) != hipSuccess) { set_error("hjr_render: chunk-sum buffer allocation failed"); return HJR_ERR_DEVICE; }
-                pb[i]->cap = part_bytes;
-            }
-        }
+        for (int i = 0; i < 3; i++)
+            if (want[i] && !pb[i]->reserve(part_bytes)) { set_error("hjr_render: chunk-sum buffer allocation failed"); return HJR_ERR_DEVICE; }
         kp.part_color = (float4*)c->d_part_color.p;
         kp.part_albedo = d_albedo ? (float4*)c->d_part_albedo.p : nullptr;
         kp.part_normal = d_normal ? (float4*)c->d_part_normal.p : nullptr;
     }
-    kp.chunk_spp = chunk_spp; kp.n_chunks = n_chunks;
+    kp.chunk_spp = g.chunk_spp; kp.n_chunks = g.n_chunks;
     kp.nodes = (const float4*)c->d_nodes.p;
     kp.tri_geom = (const float4*)c->d_tri_geom.p;
     kp.tri_shade = (const float4*)c->d_tri_shade.p;
@@ -333,13 +415,14 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, void* d_color, void* d_a
     if (c->sky_w > 0) { kp.sky_tex = (const float4*)c->d_sky.p; kp.sky_w = c->sky_w; kp.sky_h = c->sky_h; }
     kp.ibl_intensity = p->ibl_intensity;
     kp.aov_color = (float4*)d_color; kp.aov_albedo = (float4*)d_albedo; kp.aov_normal = (float4*)d_normal;
-    kp.queue_head = (unsigned int*)c->d_work.p;
-    kp.stats = (unsigned long long*)((char*)c->d_work.p + 16);
-    kp.nan_list = (unsigned long long*)((char*)c->d_work.p + nan_list_at);
+    char* const work = (char*)c->d_work.p;
+    kp.queue_head = (unsigned int*)(work + WorkArea::QUEUE_HEAD);
+    kp.stats = (unsigned long long*)(work + WorkArea::STATS);
+    kp.nan_list = (unsigned long long*)(work + WorkArea::NAN_LIST);
     kp.n_lights = c->frame.n_lights;
     kp.width = p->width; kp.height = p->height; kp.spp = p->spp; kp.frame = p->frame; kp.seed = p->seed; kp.integrator = p->integrator;
-    kp.tiles_x = tiles_x; kp.n_owned_items = (uint32_t)n_items;
-    kp.rank = p->rank; kp.world = world;
+    kp.tiles_x = g.tiles_x; kp.n_owned_items = (uint32_t)g.n_items;
+    kp.rank = p->rank; kp.world = g.world;
     kp.packed = packed ? 1u : 0u;
     for (int k = 0; k < 3; k++) {
         kp.cam_pos[k] = p->camera.pos[k]; kp.cam_dir[k] = p->camera.dir[k];
@@ -348,100 +431,114 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, void* d_color, void* d_a
     }
     kp.cam_f = p->camera.f;
 
-    const bool stats = (p->flags & HJR_FLAG_STATS) != 0;
     kp.n_node_f4 = c->frame.n_nodes * (c->frame.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4);
     kp.n_tri_f4 = (c->frame.n_tris ? c->frame.n_tris : 1u) * HJR_TRI_F4;
     kp.stack_depth = c->frame.stack_need; // exact worst case for this tree (host/frame.cpp)
     kp.n_mat_f4 = (uint32_t)c->scene.materials.size() * HJR_MAT_F4;
     kp.n_light_f4 = c->frame.n_lights * HJR_LIGHT_F4;
-    // node format / LDS staging were decided by the host builder for this frame (host/frame.cpp)
-    int lds_mode = c->frame.lds_mode;
-    if (lds_mode == 0 && c->frame.width == 2) lds_mode = 3;
-    c->stats.lds_mode = (uint32_t)lds_mode;
-    c->stats.stack_need = c->frame.stack_need;
-    c->stats.stack_lds_entries = 0; // set by the memory-path launch
-    HIPCHK(hipEventRecord(c->ev0, st));
-    // cost-ordered tile list (hjr_classify_tiles_kernel): HJR_TILE_ORDER=0 keeps the plain round-robin order
+    c->stats.lds_mode = (uint32_t)g.lds_mode; c->stats.stack_need = c->frame.stack_need;
+    return HJR_OK;
+}
+
+// cost-ordered tile list (hjr_classify_tiles_kernel): option "tile_order" = 0 keeps the plain round-robin order
+static int order_tiles(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KParams& kp, hipStream_t st)
+{
     const int order_knob = c->opt.get(hjr::OPT_TILE_ORDER, -1); // option "tile_order"
-    const bool tile_order_on = order_knob != 0;
-    if (tile_order_on && owned > 0) {
-        const size_t tb = (size_t)owned * 4;
-        if (c->d_tiles.cap < 3 * tb) {
-            c->d_tiles.release();
-            if (hipMalloc(&c->d_tiles.p, 3 * tb) != hipSuccess) { set_error("hjr_render: tile list allocation failed"); return HJR_ERR_DEVICE; }
-            c->d_tiles.cap = 3 * tb;
-            c->cost_tag = 0; // the classes of the previous frames went with the buffer
-        }
-        kp.tile_order_w = (uint32_t*)c->d_tiles.p;
-        kp.tile_class = (uint32_t*)((char*)c->d_tiles.p + tb);
-        kp.tile_bucket = (uint32_t*)((char*)c->d_tiles.p + 2 * tb);
-        kp.tile_count = (uint32_t*)((char*)c->d_work.p + 16 + (HJR_NSTAT + 20) * 8);
-        // Inside a class the tiles can also be ordered by what they cost in the previous frame of the same configuration.  That
-        // shortens the tail of a launch further (an 8-GPU share of C2: 19.0 -> 18.4 ms) but gives up the scanline order inside a
-        // class, which costs 1.6 % when the launch is long (N = 1: 134.6 -> 136.8 ms): used when the frame is split over several
-        // GPUs.  Pure scheduling: no pixel depends on it.  Option "tile_order" = 1 / 2 forces it off / on.
-        const bool cost_feedback = order_knob == 2 || (order_knob != 1 && world > 1);
-        const uint64_t tag = ((uint64_t)p->width << 48) ^ ((uint64_t)p->height << 32) ^ ((uint64_t)p->spp << 12) ^ ((uint64_t)world << 8) ^
-                             ((uint64_t)p->rank << 2) ^ (uint64_t)p->integrator ^ 0x8000000000000000ull;
-        bool have_cost = false;
-        if (cost_feedback) {
-            if (c->d_tile_cost.cap < tb) {
-                c->d_tile_cost.release();
-                if (hipMalloc(&c->d_tile_cost.p, tb) != hipSuccess) { set_error("hjr_render: tile cost allocation failed"); return HJR_ERR_DEVICE; }
-                c->d_tile_cost.cap = tb;
-                c->cost_tag = 0;
-            }
-            have_cost = c->cost_tag == tag;
-            if (!have_cost) HIPCHK(hipMemsetAsync(c->d_tile_cost.p, 0, tb, st));
-            c->cost_tag = tag;
-            kp.tile_cost = (uint32_t*)c->d_tile_cost.p;
-            kp.cost_hist = (uint32_t*)((char*)c->d_work.p + 16 + (HJR_NSTAT + 20) * 8 + 32);
-            kp.cost_div = 64u * p->spp;
-        }
-        const unsigned tg = (unsigned)((owned + 255) / 256);
-        if (have_cost) {
-            hipLaunchKernelGGL(hjr_cost_hist_kernel, dim3(tg), dim3(256), 0, st, kp);
-            hipLaunchKernelGGL(hjr_cost_scatter_kernel, dim3(tg), dim3(256), 0, st, kp);
-        } else {
-            const unsigned cg = (unsigned)std::min<uint64_t>(owned, (uint64_t)c->n_cus * 16);
-            const size_t csm = (size_t)64 * kp.stack_depth * 4;
-            if (c->frame.width == 2) hipLaunchKernelGGL(hjr_classify_tiles_kernel<2>, dim3(cg), dim3(64), csm, st, kp);
-            else hipLaunchKernelGGL(hjr_classify_tiles_kernel<4>, dim3(cg), dim3(64), csm, st, kp);
-            hipLaunchKernelGGL(hjr_order_tiles_kernel, dim3(tg), dim3(256), 0, st, kp);
-        }
-        HIPCHK(hipGetLastError());
-        kp.tile_order = (const uint32_t*)c->d_tiles.p;
+    if (order_knob == 0 || g.owned == 0) return HJR_OK;
+    const size_t tb = (size_t)g.owned * 4;
+    bool grown = false;
+    if (!c->d_tiles.reserve(3 * tb, &grown)) { set_error("hjr_render: tile list allocation failed"); return HJR_ERR_DEVICE; }
+    if (grown) c->cost_tag = 0; // the classes of the previous frames went with the buffer
+    char* const work = (char*)c->d_work.p;
+    kp.tile_order_w = (uint32_t*)c->d_tiles.p;
+    kp.tile_class = (uint32_t*)((char*)c->d_tiles.p + tb);
+    kp.tile_bucket = (uint32_t*)((char*)c->d_tiles.p + 2 * tb);
+    kp.tile_count = (uint32_t*)(work + WorkArea::TILE_COUNT);
+    // Inside a class the tiles can also be ordered by what they cost in the previous frame of the same configuration.  That
+    // shortens the tail of a launch further (an 8-GPU share of C2: 19.0 -> 18.4 ms) but gives up the scanline order inside a
+    // class, which costs 1.6 % when the launch is long (N = 1: 134.6 -> 136.8 ms): used when the frame is split over several
+    // GPUs.  Pure scheduling: no pixel depends on it.  Option "tile_order" = 1 / 2 forces it off / on.
+    const bool cost_feedback = order_knob == 2 || (order_knob != 1 && g.world > 1);
+    const uint64_t tag = ((uint64_t)p->width << 48) ^ ((uint64_t)p->height << 32) ^ ((uint64_t)p->spp << 12) ^ ((uint64_t)g.world << 8) ^
+                         ((uint64_t)p->rank << 2) ^ (uint64_t)p->integrator ^ 0x8000000000000000ull;
+    bool have_cost = false;
+    if (cost_feedback) {
+        if (!c->d_tile_cost.reserve(tb, &grown)) { set_error("hjr_render: tile cost allocation failed"); return HJR_ERR_DEVICE; }
+        if (grown) c->cost_tag = 0;
+        have_cost = c->cost_tag == tag;
+        if (!have_cost) HIPCHK(hipMemsetAsync(c->d_tile_cost.p, 0, tb, st));
+        c->cost_tag = tag;
+        kp.tile_cost = (uint32_t*)c->d_tile_cost.p;
+        kp.cost_hist = (uint32_t*)(work + WorkArea::COST_HIST);
+        kp.cost_div = 64u * p->spp;
     }
-    int lrc = 0;
-    c->stats.fast_math = 0u;
-#ifdef HJR_LEAN_VARIANT
-    lrc = hjr_launch<HJR_INTEGRATOR_NEE, false>(c, kp, n_items, lds_mode, st);
-#else
+    const unsigned tg = (unsigned)((g.owned + 255) / 256);
+    if (have_cost) {
+        hipLaunchKernelGGL(hjr_cost_hist_kernel, dim3(tg), dim3(256), 0, st, kp);
+        hipLaunchKernelGGL(hjr_cost_scatter_kernel, dim3(tg), dim3(256), 0, st, kp);
+    } else {
+        const unsigned cg = (unsigned)std::min<uint64_t>(g.owned, (uint64_t)c->n_cus * 16);
+        const size_t csm = (size_t)64 * kp.stack_depth * 4;
+        if (c->frame.width == 2) hipLaunchKernelGGL(hjr_classify_tiles_kernel<2>, dim3(cg), dim3(64), csm, st, kp);
+        else hipLaunchKernelGGL(hjr_classify_tiles_kernel<4>, dim3(cg), dim3(64), csm, st, kp);
+        hipLaunchKernelGGL(hjr_order_tiles_kernel, dim3(tg), dim3(256), 0, st, kp);
+    }
+    HIPCHK(hipGetLastError());
+    kp.tile_order = (const uint32_t*)c->d_tiles.p;
+    return HJR_OK;
+}
+
+// the render kernel
+static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, const KParams& kp, hipStream_t st)
+{
+    const bool stats = (p->flags & HJR_FLAG_STATS) != 0;
+    bool fast = false;
 #ifdef HJR_HAVE_FAST
     // approximate-arithmetic kernels (megakernel family).  A counting launch stays exact, and so does MIS: its exact launch runs on the
     // wavefront kernels, which beat the approximate megakernel (C2: 175 vs 185 ms), so the flag would only make it slower
-    if ((p->flags & HJR_FLAG_FAST_MATH) && !stats && p->integrator != HJR_INTEGRATOR_MIS) {
-        c->stats.fast_math = 1u;
-        lrc = p->integrator == HJR_INTEGRATOR_NEE ? hjr_launch_fast<HJR_INTEGRATOR_NEE>(c, kp, n_items, lds_mode, st) : hjr_launch_fast<HJR_INTEGRATOR_PT>(c, kp, n_items, lds_mode, st);
-    } else
+    fast = (p->flags & HJR_FLAG_FAST_MATH) && !stats && p->integrator != HJR_INTEGRATOR_MIS;
 #endif
-    switch (p->integrator * 2 + (stats ? 1 : 0)) {
-    case 0: lrc = hjr_launch<HJR_INTEGRATOR_NEE, false>(c, kp, n_items, lds_mode, st); break;
-    case 1: lrc = hjr_launch<HJR_INTEGRATOR_NEE, true>(c, kp, n_items, lds_mode, st); break;
-    case 2: lrc = hjr_launch<HJR_INTEGRATOR_PT, false>(c, kp, n_items, lds_mode, st); break;
-    case 3: lrc = hjr_launch<HJR_INTEGRATOR_PT, true>(c, kp, n_items, lds_mode, st); break;
-    case 4: lrc = hjr_launch<HJR_INTEGRATOR_MIS, false>(c, kp, n_items, lds_mode, st); break;
-    default: lrc = hjr_launch<HJR_INTEGRATOR_MIS, true>(c, kp, n_items, lds_mode, st); break;
-    }
+    const LaunchPlan pl = plan_launch(c, kp, g.n_items, g.lds_mode, p->integrator, fast);
+    c->stats.pipeline = pl.wf ? 1u : 0u; c->stats.fast_math = fast ? 1u : 0u; c->stats.stack_lds_entries = pl.kp.stack_lds_entries;
+    using LaunchFn = int (*)(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+#ifdef HJR_LEAN_VARIANT
+    LaunchFn fn = hjr_launch<HJR_INTEGRATOR_NEE, false>;
+#else
+    static const LaunchFn exact[6] = { hjr_launch<HJR_INTEGRATOR_NEE, false>, hjr_launch<HJR_INTEGRATOR_NEE, true>, hjr_launch<HJR_INTEGRATOR_PT, false>,
+                                       hjr_launch<HJR_INTEGRATOR_PT, true>, hjr_launch<HJR_INTEGRATOR_MIS, false>, hjr_launch<HJR_INTEGRATOR_MIS, true> };
+    LaunchFn fn = exact[p->integrator * 2 + (stats ? 1 : 0)];
+#ifdef HJR_HAVE_FAST
+    if (fast) fn = p->integrator == HJR_INTEGRATOR_NEE ? hjr_launch_fast<HJR_INTEGRATOR_NEE> : hjr_launch_fast<HJR_INTEGRATOR_PT>;
 #endif
-    if (lrc != 0) { set_error("hjr_render: could not reserve dynamic LDS for the BVH"); return HJR_ERR_DEVICE; }
+#endif
+    if (const int rc = fn(c, pl, g.n_items, st)) return rc;
     HIPCHK(hipGetLastError());
-    if (n_chunks > 1) {
-        const size_t n_slots = (size_t)owned * 64u;
-        unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
-        hipLaunchKernelGGL(hjr_finalize_kernel, dim3(fb), dim3(256), 0, st, kp);
-        HIPCHK(hipGetLastError());
-    }
+    return HJR_OK;
+}
+
+// sums of the sample chunks -> pixel means
+static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, const KParams& kp, hipStream_t st)
+{
+    if (g.n_chunks <= 1) return HJR_OK;
+    const size_t n_slots = (size_t)g.owned * 64u;
+    unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
+    hipLaunchKernelGGL(hjr_finalize_kernel, dim3(fb), dim3(256), 0, st, kp);
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+
+static int render_impl(hjr_ctx* c, const hjr_params* p, void* d_color, void* d_albedo, void* d_normal, hipStream_t st)
+{
+    FrameGeom g;
+    KParams kp;
+    int rc;
+    if ((rc = frame_geometry(c, p, d_color, g)) != HJR_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = bind_params(c, p, g, d_color, d_albedo, d_normal, st, kp)) != HJR_OK) return rc;
+    HIPCHK(hipEventRecord(c->ev0, st));
+    if ((rc = order_tiles(c, p, g, kp, st)) != HJR_OK) return rc;
+    if ((rc = launch_render(c, p, g, kp, st)) != HJR_OK) return rc;
+    if ((rc = finalize_chunks(c, g, kp, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
     return HJR_OK;
@@ -450,14 +547,14 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, void* d_color, void* d_a
 static int fetch_stats(hjr_ctx* c, hipStream_t st)
 {
     unsigned long long h[HJR_NSTAT];
-    HIPCHK(hipMemcpyAsync(h, (char*)c->d_work.p + 16, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h, (char*)c->d_work.p + WorkArea::STATS, sizeof(h), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     uint64_t* dst = &c->stats.samples;
     for (int i = 0; i < 10; i++) dst[i] = h[i];
     c->stats.stack_overflow_pushes = h[10];
     {
         unsigned long long nl[1 + HJR_NAN_LIST];
-        HIPCHK(hipMemcpy(nl, (char*)c->d_work.p + 16 + (HJR_NSTAT + 20) * 8 + 32 + 512, sizeof(nl), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nl, (char*)c->d_work.p + WorkArea::NAN_LIST, sizeof(nl), hipMemcpyDeviceToHost));
         const uint32_t n = (uint32_t)std::min<unsigned long long>(nl[0], HJR_NAN_LIST);
         c->stats.nan_located = n;
         for (uint32_t i = 0; i < HJR_NAN_LIST; i++) {
@@ -485,7 +582,7 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
 #ifdef HJR_WF_WATCHDOG
     { // diagnostic build only: did the wavefront kernel run into its deadline, and where?
         unsigned long long wd[19];
-        HIPCHK(hipMemcpy(wd, (char*)c->d_work.p + 16 + HJR_NSTAT * 8, sizeof(wd), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(wd, (char*)c->d_work.p + WorkArea::DIAG, sizeof(wd), hipMemcpyDeviceToHost));
         unsigned int where[8] = { 0 };
         (void)hipMemcpyFromSymbol(where, HIP_SYMBOL(wf_where), sizeof(where));
         if (where[1] | where[2] | where[3] | where[4] | where[5] | where[6]) {
@@ -500,7 +597,7 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
 #ifdef HJR_TIMING
     { // diagnostic build only: wave-clock shares of the megakernel's loop phases and lane occupancies
         unsigned long long tk[18];
-        HIPCHK(hipMemcpy(tk, (char*)c->d_work.p + 16 + HJR_NSTAT * 8, sizeof(tk), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(tk, (char*)c->d_work.p + WorkArea::DIAG, sizeof(tk), hipMemcpyDeviceToHost));
         const double tot = (double)tk[0] + (double)tk[1] + (double)tk[2];
         if (tot > 0) fprintf(stderr, "[hjr timing] roulette/refill/regeneration %.1f%%  fused trace %.1f%%  resolve + hit program + shading %.1f%%  (%.3g wave-clocks)\n",
                              100 * tk[0] / tot, 100 * tk[1] / tot, 100 * tk[2] / tot, tot);
@@ -520,18 +617,8 @@ extern "C" int hjr_render_device(hjr_ctx* c, const hjr_params* p_user, void* d_c
     hjr_params params; // sized struct
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_device")) { if (!c) set_error("hjr_render_device: null context"); return HJR_ERR_ARG; }
     const hjr_params* p = &params;
-    if (!c) { set_error("hjr_render_device: null context"); return HJR_ERR_ARG; }
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     return render_impl(c, p, d_color, d_albedo, d_normal, st);
-}
-
-static bool ensure(DevBuf& b, size_t bytes)
-{
-    if (b.cap >= bytes) return true;
-    b.release();
-    if (hipMalloc(&b.p, bytes) != hipSuccess) return false;
-    b.cap = bytes;
-    return true;
 }
 
 // OptixDenoiserManager::denoise() replacement (csrc/hjr_denoise.hip.h), device buffers, asynchronous on `hip_stream`
@@ -552,7 +639,7 @@ extern "C" int hjr_denoise_device(hjr_ctx* c, int render_mode, uint32_t in_w, ui
         if (d_out != d_color) HIPCHK(hipMemcpyAsync(d_out, d_color, in_bytes, hipMemcpyDeviceToDevice, st));
         return HJR_OK;
     }
-    if (!ensure(c->d_dn_a, in_bytes) || !ensure(c->d_dn_b, in_bytes)) { set_error("hjr_denoise: allocation failed"); return HJR_ERR_DEVICE; }
+    if (!c->d_dn_a.reserve(in_bytes) || !c->d_dn_b.reserve(in_bytes)) { set_error("hjr_denoise: allocation failed"); return HJR_ERR_DEVICE; }
     const dim3 block(256), grid((in_w + 63) / 64, (in_h + 3) / 4);
     const float4* src = (const float4*)d_color;
     float4* pp[2] = { (float4*)c->d_dn_a.p, (float4*)c->d_dn_b.p };
@@ -578,7 +665,7 @@ extern "C" int hjr_denoise(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t 
     if (in_w == 0 || in_h == 0 || out_w == 0 || out_h == 0) { set_error("hjr_denoise: empty image"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     const size_t in_bytes = (size_t)in_w * in_h * 16, out_bytes = (size_t)out_w * out_h * 16;
-    if (!ensure(c->d_color, in_bytes) || !ensure(c->d_albedo, in_bytes) || !ensure(c->d_normal, in_bytes) || !ensure(c->d_dn_out, out_bytes)) {
+    if (!c->d_color.reserve(in_bytes) || !c->d_albedo.reserve(in_bytes) || !c->d_normal.reserve(in_bytes) || !c->d_dn_out.reserve(out_bytes)) {
         set_error("hjr_denoise: allocation failed");
         return HJR_ERR_DEVICE;
     }
@@ -605,7 +692,7 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     const size_t in_bytes = (size_t)p->width * p->height * 16, out_bytes = (size_t)out_w * out_h * 16;
     if (in_bytes == 0 || out_bytes == 0) { set_error("hjr_render_denoised: empty image"); return HJR_ERR_ARG; }
     const bool guides = render_mode != HJR_MODE_DEFAULT;
-    if (!ensure(c->d_color, in_bytes) || (guides && (!ensure(c->d_albedo, in_bytes) || !ensure(c->d_normal, in_bytes))) || !ensure(c->d_dn_out, out_bytes)) {
+    if (!c->d_color.reserve(in_bytes) || (guides && (!c->d_albedo.reserve(in_bytes) || !c->d_normal.reserve(in_bytes))) || !c->d_dn_out.reserve(out_bytes)) {
         set_error("hjr_render_denoised: allocation failed");
         return HJR_ERR_DEVICE;
     }
@@ -712,11 +799,7 @@ extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, fl
     float* host[3] = { color, albedo, normal };
     for (int i = 0; i < 3; i++) {
         if (!host[i]) continue;
-        if (bufs[i]->cap < bytes) {
-            bufs[i]->release();
-            if (hipMalloc(&bufs[i]->p, bytes) != hipSuccess) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
-            bufs[i]->cap = bytes;
-        }
+        if (!bufs[i]->reserve(bytes)) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
         if (!packed_out) HIPCHK(hipMemsetAsync(bufs[i]->p, 0, bytes, c->stream));
     }
     int rc = render_impl(c, p, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr, c->stream);

@@ -4,4 +4,4 @@
 #error "compile this unit with -DHJR_FAST_MATH (Makefile: build/hjr_launch_fast_%.o)"
 #endif
 #include "hjr_launch.hip.h"
-template int hjr_launch_fast<HJR_INTEGRATOR_PT>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
+template int hjr_launch_fast<HJR_INTEGRATOR_PT>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);

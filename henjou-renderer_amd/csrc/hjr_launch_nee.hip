@@ -1,4 +1,4 @@
 // Render kernels of the NEE integrator (every layout, variant and both kernel families; with and without the statistics counters).
 #include "hjr_launch.hip.h"
-template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
-template int hjr_launch<HJR_INTEGRATOR_NEE, true>(hjr_ctx*, const KParams&, uint64_t, int, hipStream_t);
+template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
+template int hjr_launch<HJR_INTEGRATOR_NEE, true>(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
