@@ -20,6 +20,7 @@ ASSETS = os.path.join(PKG_DIR, "assets")
 INTEGRATOR_NEE, INTEGRATOR_PT, INTEGRATOR_MIS = 0, 1, 2
 MODE_DEFAULT, MODE_DENOISE, MODE_DENOISE_UPSCALE2X, MODE_DEBUG = 0, 1, 2, 3  # render_option.h:38-43
 FLAG_STATS, FLAG_ZERO_UNOWNED, FLAG_PACKED, FLAG_FAST_MATH = 1, 2, 4, 8
+FRAME_NODES, FRAME_TRI_GEOM, FRAME_TRI_SHADE, FRAME_LIGHTS = 0, 1, 2, 3  # hjr_copy_frame_data
 
 
 class HjrError(RuntimeError):
@@ -76,7 +77,8 @@ class RenderOption(_Sized):
                 ("use_IBL", C.c_int32), ("IBL_path", C.c_char * 512), ("IBL_intensity", C.c_float),
                 ("scene_sky_default", C.c_float * 3), ("use_date", C.c_int32), ("save_renderOption", C.c_int32),
                 ("LUT_path", C.c_char * 512), ("seed", C.c_uint32), ("integrator", C.c_int32),
-                ("devices", C.c_uint32), ("tile", C.c_uint32), ("serial_io", C.c_int32), ("fast_math", C.c_int32), ("force_rebuild", C.c_int32)]
+                ("devices", C.c_uint32), ("tile", C.c_uint32), ("serial_io", C.c_int32), ("fast_math", C.c_int32), ("force_rebuild", C.c_int32),
+                ("device_bvh", C.c_int32)]
 
 
 class Camera(C.Structure):
@@ -105,10 +107,17 @@ class Stats(_Sized):
                 ("nan_located", C.c_uint32), ("fast_math", C.c_uint32), ("nan_where", (C.c_uint32 * 3) * 8)]
 
     def as_dict(self):
-        d = {n: (float(getattr(self, n)) if n == "last_kernel_ms" else int(getattr(self, n)))
-             for n, _ in self._fields_ if n not in ("struct_size", "_pad0", "nan_where")}
+        names = [n for k in reversed(type(self).__mro__) for n, _ in getattr(k, "_fields_", [])]
+        d = {n: (float(getattr(self, n)) if n in ("last_kernel_ms", "frame_build_ms") else int(getattr(self, n)))
+             for n in names if n not in ("struct_size", "_pad0", "nan_where")}
         d["nan_where"] = [tuple(int(v) for v in self.nan_where[i]) for i in range(int(self.nan_located))]  # (x, y, sample)
         return d
+
+
+class StatsV2(Stats):
+    """hjr_stats with the fields appended after `Stats` (the layout up to nan_where).  Both are valid callers under the sized-struct
+    rule: the library writes min(struct_size, its sizeof) bytes.  Device.stats() uses this one."""
+    _fields_ = [("bvh_builder", C.c_uint32), ("frame_build_ms", C.c_float)]
 
 
 _lib = None
@@ -150,6 +159,7 @@ def lib():
             "hjr_preview_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
             "hjr_set_option": [C.c_void_p, C.c_char_p, C.c_int],
             "hjr_get_option": [C.c_void_p, C.c_char_p, C.c_void_p],
+            "hjr_copy_frame_data": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
             "hjr_float4_to_srgb8": [C.c_void_p, C.c_void_p, C.c_uint32],
             "hjr_tonemap_to_srgb8": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int],
             "hjr_write_png": [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int],
@@ -434,8 +444,18 @@ class Device:
         _check(lib().hjr_get_option(self._h, key.encode(), C.byref(v)), "hjr_get_option")
         return v.value
 
+    def copy_frame_data(self, what):
+        """hjr_copy_frame_data: the current frame data as float32 [records, 4] (what = FRAME_NODES / FRAME_TRI_GEOM / FRAME_TRI_SHADE /
+        FRAME_LIGHTS; layouts in csrc/hjr_layout.h; child refs and ids are uint32 bits: .view(np.uint32))."""
+        n = C.c_size_t()
+        _check(lib().hjr_copy_frame_data(self._h, what, None, 0, C.byref(n)), "hjr_copy_frame_data")
+        out = np.zeros(n.value // 4, dtype=np.float32)
+        if n.value:
+            _check(lib().hjr_copy_frame_data(self._h, what, out.ctypes.data, n.value, C.byref(n)), "hjr_copy_frame_data")
+        return out.reshape(-1, 4)
+
     def stats(self):
-        st = Stats()
+        st = StatsV2()
         _check(lib().hjr_get_stats(self._h, C.byref(st)), "hjr_get_stats")
         return st.as_dict()
 

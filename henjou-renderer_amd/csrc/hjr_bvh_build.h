@@ -1,0 +1,62 @@
+// Device buffers of a context and the per-frame device BVH4 builder (option "device_bvh", csrc/hjr_bvh_build.hip).
+// Kept free of the kernel headers so that hjr_bvh_build.hip compiles on its own.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <utility>
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    // grow without copying to exactly `bytes` (the old contents are lost); *grown tells whether the buffer was reallocated
+    bool reserve(size_t bytes, bool* grown = nullptr)
+    {
+        if (grown) *grown = cap < bytes;
+        if (cap >= bytes) return true;
+        release();
+        if (hipMalloc(&p, bytes) != hipSuccess) return false;
+        cap = bytes;
+        return true;
+    }
+    bool upload(const void* src, size_t bytes, hipStream_t st) // grows with 25 % slack
+    {
+        if (bytes > cap && !reserve(bytes + bytes / 4 + 256)) return false;
+        return !bytes || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+};
+
+namespace hjr {
+struct SceneCopy;
+
+// Traversal-stack entries a device-built tree may need: the tile classifier takes 64 * stack_need * 4 bytes of dynamic LDS without
+// raising the kernel's limit (hjr_device.hip::order_tiles), which stays at 32 KB with this cap.
+constexpr uint32_t DEVICE_BVH_MAX_STACK = 128;
+
+struct DeviceBvh {
+    // object-space scene, uploaded at the first device build after hjr_upload_scene (have_scene = false drops it)
+    DevBuf vert, norm, uv, idx, mat, prim_off;
+    bool have_scene = false;
+    DevBuf xf;  // per instance: 12 floats of the transform, then 12 of the inverse
+    // scratch of one build
+    DevBuf wv, box, cent, keys[2], vals[2], hist, part, leaf_box, inner_box, inner_child, inner_range, parent, counter, frontier[2], wide, hdr;
+    // the frame data a build writes; hjr_commit_transforms swaps them with the context's current buffers when the build succeeds
+    DevBuf nodes, tri_geom, tri_shade, tri_inst, lights;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    void release();
+};
+
+struct DeviceBvhResult {
+    uint32_t n_nodes = 0, stack_need = 0, depth = 0;
+    float build_ms = 0.0f; // HIP-event time of the build's kernels
+};
+
+// Enqueues the whole build on `st` behind whatever is already there, waits for it and reads back its header.  HJR_ERR_ARG with `err`
+// set for a scene the host builder rejects too (non-finite vertex, tree deeper than the traversal stack allows), HJR_ERR_DEVICE for a
+// runtime failure.  The lights are the host's table (build_lights), copied into `b.lights`.
+int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, const float* lights,
+                     size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+} // namespace hjr

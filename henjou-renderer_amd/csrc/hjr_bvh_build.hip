@@ -1,0 +1,615 @@
+// Per-frame BVH4 build on the device (option "device_bvh" = 1): the same frame data host/frame.cpp::build_frame
+// emits for the memory layout (lds_mode 0, HJR_NODE4_F4 nodes), from a Morton-order tree instead of binned SAH.
+//   flatten      one lane per triangle: world vertices, shading record, instance id, padded box inputs (frame.cpp's expressions)
+//   morton       padding from the exact maximum |coordinate|, 63-bit codes over the centroid bounds
+//   radix sort   stable LSD over (code, prim id), 8 bits per pass, reduce-then-scan in separate launches
+//   hierarchy    Karras 2012: every inner node finds its range and split on its own (ties by index)
+//   boxes        bottom-up, one agent-scope acq_rel counter per inner node: the second lane to arrive takes the union
+//   collapse     BVH4 level by level with emit_bvh4's rules; ids from a scan of each level (breadth-first, same bytes every run)
+// No workgroup ever waits for another one; every cross-launch size the host does not know is read by the kernels from `hdr`.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/henjou_hip.h"
+#include "../host/frame.hpp"
+#include "hjr_bvh_build.h"
+#include "hjr_layout.h"
+
+namespace {
+
+constexpr int NT = 256;         // threads per workgroup of every kernel here (4 waves)
+constexpr int SCAN_G = 256;     // workgroups of the scan passes (== NT: the top pass scans their sums in one workgroup)
+constexpr int SORT_TILE = 2048; // keys per workgroup of a radix pass (8 rounds of NT)
+constexpr int LEVEL_BATCH = 8;  // collapse levels enqueued between two reads of the frontier size
+
+// header words (uint32)
+enum Hdr {
+    H_SMAX = 0,      // bits of max |coordinate| over the unpadded triangle boxes (non-negative floats order as their bits)
+    H_CMIN = 1,      // 3 ordered-uint centroid minima, then 3 maxima
+    H_CMAX = 4,
+    H_WORST = 7,     // max pending traversal-stack entries over the wide nodes
+    H_DEPTH = 8,     // max BVH2 depth of a wide-node slot
+    H_BASE = 9,      // first wide id of the current level
+    H_F = 10,        // nodes of the current level
+    H_NEXT = 11,     // nodes of the next level (scan total)
+    H_WORDS = 16
+};
+
+__device__ __forceinline__ uint32_t f2o(float f) // order-preserving float -> uint
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float o2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+// std::min / std::max of frame.cpp's Box::grow (a NaN operand on the right is dropped, as there)
+__device__ __forceinline__ float smin(float a, float b) { return b < a ? b : a; }
+__device__ __forceinline__ float smax(float a, float b) { return a < b ? b : a; }
+
+// exclusive scan over a 256-thread workgroup; `s` holds 4 words of LDS
+__device__ uint32_t block_scan(uint32_t v, uint32_t& total, uint32_t* s)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) s[w] = x;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+    for (int k = 0; k < NT / 64; k++) { if (k < w) pre += s[k]; tot += s[k]; }
+    __syncthreads();
+    total = tot;
+    return pre + x - v;
+}
+
+// ---- generic exclusive scan of n uint32 (n from the host or from a header word), in place allowed: three launches -----------------
+__device__ __forceinline__ void scan_range(uint32_t n, uint32_t& b0, uint32_t& b1)
+{
+    const uint32_t chunk = (n + SCAN_G - 1) / SCAN_G;
+    b0 = min(n, blockIdx.x * chunk);
+    b1 = min(n, b0 + chunk);
+}
+__global__ void __launch_bounds__(NT) scan_reduce_kernel(const uint32_t* in, const uint32_t* n_ptr, uint32_t n_const, uint32_t* part)
+{
+    __shared__ uint32_t s[4];
+    const uint32_t n = n_ptr ? *n_ptr : n_const;
+    uint32_t b0, b1, acc = 0, tot;
+    scan_range(n, b0, b1);
+    for (uint32_t i = b0 + threadIdx.x; i < b1; i += NT) acc += in[i];
+    block_scan(acc, tot, s);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(NT) scan_top_kernel(uint32_t* part, uint32_t* total)
+{
+    __shared__ uint32_t s[4];
+    uint32_t tot;
+    const uint32_t ex = block_scan(part[threadIdx.x], tot, s);
+    part[threadIdx.x] = ex;
+    if (threadIdx.x == 0 && total) *total = tot;
+}
+__global__ void __launch_bounds__(NT) scan_down_kernel(const uint32_t* in, uint32_t* out, const uint32_t* n_ptr, uint32_t n_const, const uint32_t* part)
+{
+    __shared__ uint32_t s[4];
+    const uint32_t n = n_ptr ? *n_ptr : n_const;
+    uint32_t b0, b1, tot;
+    scan_range(n, b0, b1);
+    uint32_t run = part[blockIdx.x];
+    for (uint32_t base = b0; base < b1; base += NT) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < b1 ? in[i] : 0u;
+        const uint32_t ex = block_scan(v, tot, s);
+        if (i < b1) out[i] = run + ex;
+        run += tot;
+    }
+}
+
+// ---- flatten: frame.cpp:520-543 (world vertices, shading record, instance) and :586-600 (box, centroid, max |coordinate|) ----------
+__device__ __forceinline__ void xform_pos(const float* m, float px, float py, float pz, float* o)
+{
+    o[0] = m[0] * px + m[1] * py + m[2] * pz + m[3] * 1.0f;
+    o[1] = m[4] * px + m[5] * py + m[6] * pz + m[7] * 1.0f;
+    o[2] = m[8] * px + m[9] * py + m[10] * pz + m[11] * 1.0f;
+}
+__device__ __forceinline__ void xform_nrm(const float* m, float nx, float ny, float nz, float* o)
+{
+    o[0] = m[0] * nx + m[4] * ny + m[8] * nz + 0.0f * 0.0f;
+    o[1] = m[1] * nx + m[5] * ny + m[9] * nz + 0.0f * 0.0f;
+    o[2] = m[2] * nx + m[6] * ny + m[10] * nz + 0.0f * 0.0f;
+}
+
+struct FlattenArgs {
+    const float *vert, *norm, *uv, *xf;
+    const uint32_t *idx, *mat, *prim_off;
+    uint32_t n, n_inst;
+    float *wv, *shade, *box, *cent; // wv 9 / shade 16 / box 8 (lo xyz -, hi xyz -) / cent 4 floats per triangle
+    uint32_t *inst, *hdr;
+};
+
+__global__ void __launch_bounds__(NT) flatten_kernel(FlattenArgs a)
+{
+    __shared__ uint32_t s_red[7];
+    if (threadIdx.x < 7) s_red[threadIdx.x] = threadIdx.x >= 1 && threadIdx.x < 4 ? 0xffffffffu : 0u;
+    __syncthreads();
+    const uint32_t t = blockIdx.x * NT + threadIdx.x;
+    if (t < a.n) {
+        uint32_t lo = 0, hi = a.n_inst; // last prim_offset <= t (prim_offset[0] == 0)
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.prim_off[mid] <= t) lo = mid; else hi = mid; }
+        const float* m = a.xf + 24 * (size_t)lo;
+        const float* mi = m + 12;
+        float v[9], s[16], uv[6];
+        for (int k = 0; k < 3; k++) {
+            const uint32_t ix = a.idx[3 * (size_t)t + k];
+            xform_pos(m, a.vert[3 * (size_t)ix], a.vert[3 * (size_t)ix + 1], a.vert[3 * (size_t)ix + 2], &v[3 * k]);
+            float nn[3];
+            xform_nrm(mi, a.norm[3 * (size_t)ix], a.norm[3 * (size_t)ix + 1], a.norm[3 * (size_t)ix + 2], nn);
+            const float inv = 1.0f / sqrtf(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
+            s[4 * k + 0] = nn[0] * inv; s[4 * k + 1] = nn[1] * inv; s[4 * k + 2] = nn[2] * inv;
+            uv[2 * k] = a.uv[2 * (size_t)ix]; uv[2 * k + 1] = a.uv[2 * (size_t)ix + 1];
+        }
+        s[3] = uv[0]; s[7] = uv[1]; s[11] = uv[2];
+        s[12] = uv[3]; s[13] = uv[4]; s[14] = uv[5];
+        s[15] = __uint_as_float(a.mat[t]);
+        float4* sd = reinterpret_cast<float4*>(a.shade) + 4 * (size_t)t;
+        for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+        for (int k = 0; k < 9; k++) a.wv[9 * (size_t)t + k] = v[k];
+        a.inst[t] = lo;
+        float bl[3], bh[3], c[3], mx = 0.0f;
+        for (int ax = 0; ax < 3; ax++) {
+            bl[ax] = 3.402823466e+38f; bh[ax] = -3.402823466e+38f;
+            for (int k = 0; k < 3; k++) { bl[ax] = smin(bl[ax], v[3 * k + ax]); bh[ax] = smax(bh[ax], v[3 * k + ax]); }
+        }
+        for (int ax = 0; ax < 3; ax++) {
+            c[ax] = 0.5f * (bl[ax] + bh[ax]);
+            mx = smax(mx, smax(fabsf(bl[ax]), fabsf(bh[ax])));
+        }
+        float4* bd = reinterpret_cast<float4*>(a.box) + 2 * (size_t)t;
+        bd[0] = make_float4(bl[0], bl[1], bl[2], 0.0f);
+        bd[1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
+        reinterpret_cast<float4*>(a.cent)[t] = make_float4(c[0], c[1], c[2], 0.0f);
+        // exact, order-independent reductions: max of non-negative float bits, min / max of order-preserving encodings
+        atomicMax(&s_red[0], __float_as_uint(mx));
+        for (int ax = 0; ax < 3; ax++) { atomicMin(&s_red[1 + ax], f2o(c[ax])); atomicMax(&s_red[4 + ax], f2o(c[ax])); }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) atomicMax(&a.hdr[H_SMAX], s_red[0]);
+    else if (threadIdx.x < 4) atomicMin(&a.hdr[H_CMIN + threadIdx.x - 1], s_red[threadIdx.x]);
+    else if (threadIdx.x < 7) atomicMax(&a.hdr[H_CMAX + threadIdx.x - 4], s_red[threadIdx.x]);
+}
+
+// ---- padding (frame.cpp:603-609) and Morton codes --------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t spread21(uint32_t x) // 21 bits -> every third bit of 63
+{
+    uint64_t v = x & 0x1fffffull;
+    v = (v | (v << 32)) & 0x1f00000000ffffull;
+    v = (v | (v << 16)) & 0x1f0000ff0000ffull;
+    v = (v | (v << 8)) & 0x100f00f00f00f00full;
+    v = (v | (v << 4)) & 0x10c30c30c30c30c3ull;
+    v = (v | (v << 2)) & 0x1249249249249249ull;
+    return v;
+}
+__device__ __forceinline__ uint32_t quantize21(float c, float lo, float scale)
+{
+    const float f = (c - lo) * scale;
+    return f >= 2097151.0f ? 2097151u : (f > 0.0f ? (uint32_t)f : 0u); // NaN -> 0
+}
+__global__ void __launch_bounds__(NT) morton_kernel(uint32_t n, float* box, const float* cent, const uint32_t* hdr, uint64_t* keys, uint32_t* vals)
+{
+    const uint32_t t = blockIdx.x * NT + threadIdx.x;
+    if (t >= n) return;
+    const float pad = __uint_as_float(hdr[H_SMAX]) * (1.0f / 32768.0f);
+    float4* b = reinterpret_cast<float4*>(box) + 2 * (size_t)t;
+    float4 lo = b[0], hi = b[1];
+    lo.x -= pad; lo.y -= pad; lo.z -= pad;
+    hi.x += pad; hi.y += pad; hi.z += pad;
+    b[0] = lo; b[1] = hi;
+    const float4 c = reinterpret_cast<const float4*>(cent)[t];
+    uint64_t key = 0;
+    const float cc[3] = { c.x, c.y, c.z };
+    for (int ax = 0; ax < 3; ax++) {
+        const float l = o2f(hdr[H_CMIN + ax]), h = o2f(hdr[H_CMAX + ax]);
+        const float ext = h - l;
+        const float scale = ext > 0.0f ? 2097152.0f / ext : 0.0f;
+        key |= spread21(quantize21(cc[ax], l, scale)) << (2 - ax);
+    }
+    keys[t] = key;
+    vals[t] = t; // seeded in prim order: the stable sort leaves equal codes in prim-id order
+}
+
+// ---- stable LSD radix sort, 8 bits per pass ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(NT) radix_hist_kernel(const uint64_t* keys, uint32_t n, int shift, uint32_t* hist, uint32_t nb)
+{
+    __shared__ uint32_t s_h[256];
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    for (int r = 0; r < SORT_TILE / NT; r++) {
+        const uint32_t i = blockIdx.x * SORT_TILE + r * NT + threadIdx.x;
+        if (i < n) atomicAdd(&s_h[(uint32_t)(keys[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * nb + blockIdx.x] = s_h[threadIdx.x];
+}
+// hist: exclusive offsets, digit-major ([digit][workgroup]).  Rounds of NT keys in index order; inside a round a wave ranks its lanes
+// among equal digits with eight ballots, the waves are ordered through LDS: the scatter keeps the input order of equal digits.
+__global__ void __launch_bounds__(NT) radix_scatter_kernel(const uint64_t* keys, const uint32_t* vals, uint32_t n, int shift, const uint32_t* hist,
+                                                           uint32_t nb, uint64_t* keys_out, uint32_t* vals_out)
+{
+    __shared__ uint32_t s_base[256], s_wc[4][256], s_tot[256];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    s_base[threadIdx.x] = hist[(size_t)threadIdx.x * nb + blockIdx.x];
+    for (int r = 0; r < SORT_TILE / NT; r++) {
+        for (int k = 0; k < 4; k++) s_wc[k][threadIdx.x] = 0;
+        __syncthreads();
+        const uint32_t i = blockIdx.x * SORT_TILE + r * NT + threadIdx.x;
+        const bool valid = i < n;
+        const uint64_t key = valid ? keys[i] : 0ull;
+        const uint32_t val = valid ? vals[i] : 0u;
+        const uint32_t d = (uint32_t)(key >> shift) & 255u;
+        uint64_t m = __ballot(valid);
+        for (int bit = 0; bit < 8; bit++) {
+            const uint64_t bb = __ballot((d >> bit) & 1u);
+            m &= ((d >> bit) & 1u) ? bb : ~bb;
+        }
+        const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (valid && (m >> lane) == 1ull) s_wc[w][d] = (uint32_t)__popcll(m); // the last lane of its digit in this wave
+        __syncthreads();
+        { // per digit: the waves' prefix (in place) and the round's total
+            uint32_t acc = 0;
+            for (int k = 0; k < 4; k++) { const uint32_t c = s_wc[k][threadIdx.x]; s_wc[k][threadIdx.x] = acc; acc += c; }
+            s_tot[threadIdx.x] = acc;
+        }
+        __syncthreads();
+        const uint32_t dst = s_base[d] + s_wc[w][d] + rank;
+        if (valid && dst < n) { // (always: the offsets are a permutation of [0, n))
+            keys_out[dst] = key;
+            vals_out[dst] = val;
+        }
+        __syncthreads();
+        s_base[threadIdx.x] += s_tot[threadIdx.x];
+    }
+}
+
+// ---- leaves in sorted order: tri_geom (frame.cpp:652-660) and the leaf boxes ----------------------------------------------------
+__global__ void __launch_bounds__(NT) gather_kernel(uint32_t n, const uint32_t* order, const float* wv, const uint32_t* mat, const float* box, float* tri_geom, float* leaf_box)
+{
+    const uint32_t k = blockIdx.x * NT + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t t = order[k];
+    const float* v = wv + 9 * (size_t)t;
+    float4* g = reinterpret_cast<float4*>(tri_geom) + 3 * (size_t)k;
+    g[0] = make_float4(v[0], v[1], v[2], v[3]);
+    g[1] = make_float4(v[4], v[5], v[6], v[7]);
+    g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(mat[t]), 0.0f);
+    const float4* b = reinterpret_cast<const float4*>(box) + 2 * (size_t)t;
+    float4* lb = reinterpret_cast<float4*>(leaf_box) + 2 * (size_t)k;
+    lb[0] = b[0];
+    lb[1] = b[1];
+}
+
+// ---- hierarchy (Karras 2012) ----------------------------------------------------------------------------------------------------
+// BVH2 refs: inner node i -> i, sorted leaf k -> k | REF_LEAF.  Inner node 0 is the root.
+constexpr uint32_t REF_LEAF = 0x80000000u;
+
+__device__ __forceinline__ int delta(const uint64_t* keys, int n, int i, int j)
+{
+    if (j < 0 || j >= n) return -1;
+    const uint64_t a = keys[i], b = keys[j];
+    return a == b ? 64 + __clz((uint32_t)(i ^ j)) : __clzll((long long)(a ^ b));
+}
+// parent: [0, n - 1) inner nodes, then [n - 1, 2n - 1) leaves
+__global__ void __launch_bounds__(NT) karras_kernel(int n, const uint64_t* keys, uint2* child, uint2* range, uint32_t* parent)
+{
+    const int i = (int)(blockIdx.x * NT + threadIdx.x);
+    if (i >= n - 1) return;
+    const int d = delta(keys, n, i, i + 1) - delta(keys, n, i, i - 1) >= 0 ? 1 : -1;
+    const int dmin = delta(keys, n, i, i - d);
+    int lmax = 2;
+    while (delta(keys, n, i, i + lmax * d) > dmin) lmax <<= 1;
+    int l = 0;
+    for (int t = lmax >> 1; t >= 1; t >>= 1)
+        if (delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
+    const int j = i + l * d;
+    const int dnode = delta(keys, n, i, j);
+    int s = 0, t = l;
+    do {
+        t = (t + 1) >> 1;
+        if (delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
+    } while (t > 1);
+    const int gamma = i + s * d + min(d, 0);
+    const int first = min(i, j), last = max(i, j);
+    const uint32_t left = first == gamma ? ((uint32_t)gamma | REF_LEAF) : (uint32_t)gamma;
+    const uint32_t right = last == gamma + 1 ? ((uint32_t)(gamma + 1) | REF_LEAF) : (uint32_t)(gamma + 1);
+    child[i] = make_uint2(left, right);
+    range[i] = make_uint2((uint32_t)first, (uint32_t)(last - first + 1));
+    const size_t pl = (left & REF_LEAF) ? (size_t)(n - 1) + (left & ~REF_LEAF) : left, pr = (right & REF_LEAF) ? (size_t)(n - 1) + (right & ~REF_LEAF) : right;
+    if (pl < (size_t)(2 * n - 1)) parent[pl] = (uint32_t)i; // (always: gamma + 1 <= n - 1)
+    if (pr < (size_t)(2 * n - 1)) parent[pr] = (uint32_t)i;
+}
+
+// ---- boxes, bottom-up ---------------------------------------------------------------------------------------------------------------
+// One lane per leaf climbs while it is the second to reach a node.  Cross-workgroup hand-off (MI355X_MICROARCH.md, inter-workgroup
+// visibility): the lane stores the box of the node it completed, then its agent-scope acq_rel add on the parent's counter releases
+// that store (L2 write-back) and, for the second lane, acquires the sibling's (L1 invalidate) before it reads both boxes.
+__device__ __forceinline__ void box_of(uint32_t ref, const float4* leaf_box, const float4* inner_box, float4& lo, float4& hi)
+{
+    const float4* b = (ref & REF_LEAF) ? leaf_box + 2 * (size_t)(ref & ~REF_LEAF) : inner_box + 2 * (size_t)ref;
+    lo = b[0];
+    hi = b[1];
+}
+__global__ void __launch_bounds__(NT) boxes_kernel(int n, const uint2* child, const uint32_t* parent, uint32_t* counter, const float4* leaf_box, float4* inner_box)
+{
+    const int k = (int)(blockIdx.x * NT + threadIdx.x);
+    if (k >= n) return;
+    uint32_t p = parent[(size_t)(n - 1) + k];
+    for (;;) {
+        const uint32_t before = __hip_atomic_fetch_add(&counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == 0) return; // the sibling's lane finishes this node
+        const uint2 c = child[p];
+        float4 l0, h0, l1, h1;
+        box_of(c.x, leaf_box, inner_box, l0, h0);
+        box_of(c.y, leaf_box, inner_box, l1, h1);
+        inner_box[2 * (size_t)p] = make_float4(smin(l0.x, l1.x), smin(l0.y, l1.y), smin(l0.z, l1.z), 0.0f);
+        inner_box[2 * (size_t)p + 1] = make_float4(smax(h0.x, h1.x), smax(h0.y, h1.y), smax(h0.z, h1.z), 0.0f);
+        if (p == 0) return;
+        p = parent[p];
+    }
+}
+
+// ---- collapse to BVH4 (frame.cpp::emit_bvh4) ------------------------------------------------------------------------------------
+struct Front { uint32_t ref, pend, depth, pad; };     // a wide node of the current level: its BVH2 node, pending entries above it, its depth
+struct Wide { uint32_t child[4], depth[4], n, pend, pad[2]; }; // children in emit_bvh4's slot order
+
+struct CollapseArgs {
+    const uint2 *child, *range;
+    const float4 *leaf_box, *inner_box;
+    uint32_t leaf_max;
+    uint32_t cap; // wide nodes the buffers hold (>= the wide nodes of any tree over these triangles)
+    uint32_t* hdr;
+};
+// a BVH2 node that becomes a wide node: inner, and the root or more than leaf_max triangles (frame.cpp:166)
+__device__ __forceinline__ bool is_inner(const CollapseArgs& a, uint32_t ref)
+{
+    return !(ref & REF_LEAF) && (ref == 0 || a.range[ref].y > a.leaf_max);
+}
+__device__ __forceinline__ float area_of(const CollapseArgs& a, uint32_t ref)
+{
+    float4 lo, hi;
+    box_of(ref, a.leaf_box, a.inner_box, lo, hi);
+    const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
+    return (dx < 0) ? 0.0f : 2.0f * (dx * dy + dy * dz + dz * dx);
+}
+__global__ void __launch_bounds__(NT) wide_expand_kernel(CollapseArgs a, const Front* fr, Wide* wide, uint32_t* n_inner)
+{
+    const uint32_t F = a.hdr[H_F];
+    for (uint32_t i = blockIdx.x * NT + threadIdx.x; i < F && i < a.cap; i += gridDim.x * NT) {
+        const Front f = fr[i];
+        Wide w;
+        w.n = 0;
+        if (!is_inner(a, f.ref)) { w.child[0] = f.ref; w.depth[0] = f.depth; w.n = 1; } // a single leaf: wide root with one leaf child
+        else {
+            const uint2 c = a.child[f.ref];
+            w.child[0] = c.x; w.child[1] = c.y; w.depth[0] = w.depth[1] = f.depth + 1; w.n = 2;
+        }
+        while (w.n < 4) { // replace the largest-area inner child by its two children
+            int best = -1;
+            float barea = -1.0f;
+            for (uint32_t k = 0; k < w.n; k++)
+                if (is_inner(a, w.child[k])) { const float ar = area_of(a, w.child[k]); if (ar > barea) { barea = ar; best = (int)k; } }
+            if (best < 0) break;
+            const uint2 c = a.child[w.child[best]];
+            const uint32_t dd = w.depth[best] + 1;
+            w.child[best] = c.x; w.depth[best] = dd;
+            w.child[w.n] = c.y; w.depth[w.n] = dd; w.n++;
+        }
+        uint32_t ni = 0;
+        for (uint32_t k = 0; k < w.n; k++) ni += is_inner(a, w.child[k]) ? 1u : 0u;
+        w.pend = f.pend;
+        wide[i] = w;
+        n_inner[i] = ni;
+    }
+}
+// writes the level's nodes (ids H_BASE + i) and the next level's frontier (ids H_BASE + F + off[i] + k)
+__global__ void __launch_bounds__(NT) wide_emit_kernel(CollapseArgs a, const Wide* wide, const uint32_t* off, Front* next, float4* nodes)
+{
+    const uint32_t F = a.hdr[H_F], base = a.hdr[H_BASE];
+    uint32_t worst = 0, depth = 0;
+    for (uint32_t i = blockIdx.x * NT + threadIdx.x; i < F && base + i < a.cap; i += gridDim.x * NT) {
+        const Wide w = wide[i];
+        float q[28];
+        uint32_t k_in = 0;
+        // emit_bvh4's stack bound: a visited wide node leaves (children - 1) entries pending above those of its parent
+        const uint32_t h = w.pend + (w.n > 0 ? w.n - 1 : 0);
+        worst = max(worst, h);
+        for (int c = 0; c < 4; c++) {
+            if ((uint32_t)c < w.n) {
+                const uint32_t r = w.child[c];
+                float4 lo, hi;
+                box_of(r, a.leaf_box, a.inner_box, lo, hi);
+                q[c] = lo.x; q[4 + c] = hi.x; q[8 + c] = lo.y; q[12 + c] = hi.y; q[16 + c] = lo.z; q[20 + c] = hi.z;
+                uint32_t ref;
+                if (is_inner(a, r)) {
+                    const uint32_t j = off[i] + k_in++;
+                    ref = base + F + j;
+                    if (j < a.cap) next[j] = Front{ r, h, w.depth[c], 0u };
+                } else {
+                    ref = (r & REF_LEAF) ? (HJR_LEAF_FLAG | (1u << 27) | (r & ~REF_LEAF)) : (HJR_LEAF_FLAG | (a.range[r].y << 27) | a.range[r].x);
+                    depth = max(depth, w.depth[c]);
+                }
+                q[24 + c] = __uint_as_float(ref);
+            } else { // unused slot: inverted box, empty leaf
+                q[c] = 1e30f; q[4 + c] = -1e30f; q[8 + c] = 1e30f; q[12 + c] = -1e30f; q[16 + c] = 1e30f; q[20 + c] = -1e30f;
+                q[24 + c] = __uint_as_float(HJR_LEAF_FLAG);
+            }
+        }
+        float4* o = nodes + (size_t)(base + i) * HJR_NODE4_F4;
+        for (int v = 0; v < HJR_NODE4_F4; v++) o[v] = make_float4(q[4 * v], q[4 * v + 1], q[4 * v + 2], q[4 * v + 3]);
+    }
+    if (worst) atomicMax(&a.hdr[H_WORST], worst);
+    if (depth) atomicMax(&a.hdr[H_DEPTH], depth);
+}
+__global__ void level_advance_kernel(uint32_t* hdr)
+{
+    hdr[H_BASE] += hdr[H_F];
+    hdr[H_F] = hdr[H_NEXT];
+}
+__global__ void collapse_init_kernel(uint32_t n, Front* fr, uint32_t* hdr)
+{
+    fr[0] = Front{ n == 1 ? REF_LEAF : 0u, 0u, 0u, 0u };
+    hdr[H_BASE] = 0;
+    hdr[H_F] = 1;
+}
+__global__ void hdr_init_kernel(uint32_t* hdr)
+{
+    if (threadIdx.x < H_WORDS) hdr[threadIdx.x] = threadIdx.x >= H_CMIN && threadIdx.x < H_CMAX ? 0xffffffffu : 0u;
+}
+
+inline unsigned blocks_for(size_t n) { return (unsigned)std::max<size_t>(1, (n + NT - 1) / NT); }
+
+} // namespace
+
+namespace hjr {
+
+void DeviceBvh::release()
+{
+    for (DevBuf* x : { &vert, &norm, &uv, &idx, &mat, &prim_off, &xf, &wv, &box, &cent, &keys[0], &keys[1], &vals[0], &vals[1], &hist, &part, &leaf_box,
+                       &inner_box, &inner_child, &inner_range, &parent, &counter, &frontier[0], &frontier[1], &wide, &hdr, &nodes, &tri_geom, &tri_shade,
+                       &tri_inst, &lights })
+        x->release();
+    have_scene = false;
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    ev0 = ev1 = nullptr;
+}
+
+#define DCHK(call)                                                                                           \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) { err = std::string(#call) + " failed: " + hipGetErrorString(e_); return HJR_ERR_DEVICE; } \
+    } while (0)
+
+static int scan(uint32_t* in_out, const uint32_t* n_ptr, uint32_t n_const, uint32_t* part, uint32_t* total, hipStream_t st, std::string& err)
+{
+    hipLaunchKernelGGL(scan_reduce_kernel, dim3(SCAN_G), dim3(NT), 0, st, in_out, n_ptr, n_const, part);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(NT), 0, st, part, total);
+    hipLaunchKernelGGL(scan_down_kernel, dim3(SCAN_G), dim3(NT), 0, st, in_out, in_out, n_ptr, n_const, part);
+    DCHK(hipGetLastError());
+    return HJR_OK;
+}
+
+int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, const float* lights,
+                     size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+{
+    const uint32_t n = sc.n_triangles;
+    r = DeviceBvhResult();
+    if (!b.ev0) DCHK(hipEventCreate(&b.ev0));
+    if (!b.ev1) DCHK(hipEventCreate(&b.ev1));
+    auto fail_alloc = [&] { err = "device BVH: allocation or upload failed"; return HJR_ERR_DEVICE; };
+    // object-space scene, once per hjr_upload_scene
+    if (!b.have_scene) {
+        if (!b.vert.upload(sc.vertices.data(), sc.vertices.size() * 4, st) || !b.norm.upload(sc.normals.data(), sc.normals.size() * 4, st) ||
+            !b.uv.upload(sc.texcoords.data(), sc.texcoords.size() * 4, st) || !b.idx.upload(sc.indices.data(), sc.indices.size() * 4, st) ||
+            !b.mat.upload(sc.material_ids.data(), sc.material_ids.size() * 4, st) || !b.prim_off.upload(sc.prim_offset.data(), sc.prim_offset.size() * 4, st))
+            return fail_alloc();
+        b.have_scene = true;
+    }
+    std::vector<float> xf((size_t)n_inst * 24);
+    for (uint32_t i = 0; i < n_inst; i++) {
+        memcpy(&xf[24 * (size_t)i], M + 12 * (size_t)i, 48);
+        memcpy(&xf[24 * (size_t)i + 12], Mi + 12 * (size_t)i, 48);
+    }
+    const size_t nn = std::max<uint32_t>(n, 1u);            // node / frontier capacity: a wide node takes at least one BVH2 inner node
+    const uint32_t nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+    if (!b.xf.upload(xf.data(), xf.size() * 4, st) || !b.lights.upload(lights, light_floats * 4, st) || !b.hdr.reserve(H_WORDS * 4) ||
+        !b.nodes.reserve(nn * HJR_NODE4_F4 * 16) || !b.tri_geom.reserve(nn * HJR_TRI_F4 * 16) || !b.tri_shade.reserve(nn * HJR_SHADE_F4 * 16) ||
+        !b.tri_inst.reserve(nn * 4) || !b.wv.reserve(nn * 36) || !b.box.reserve(nn * 32) || !b.cent.reserve(nn * 16) || !b.keys[0].reserve(nn * 8) ||
+        !b.keys[1].reserve(nn * 8) || !b.vals[0].reserve(nn * 4) || !b.vals[1].reserve(nn * 4) || !b.hist.reserve(std::max<size_t>(1, (size_t)nb * 256 * 4)) ||
+        !b.part.reserve(SCAN_G * 4) || !b.leaf_box.reserve(nn * 32) || !b.inner_box.reserve(nn * 32) || !b.inner_child.reserve(nn * 8) ||
+        !b.inner_range.reserve(nn * 8) || !b.parent.reserve(2 * nn * 4) || !b.counter.reserve(nn * 4) || !b.frontier[0].reserve(nn * sizeof(Front)) ||
+        !b.frontier[1].reserve(nn * sizeof(Front)) || !b.wide.reserve(nn * (sizeof(Wide) + 4)))
+        return fail_alloc();
+    uint32_t* hdr = (uint32_t*)b.hdr.p;
+    DCHK(hipEventRecord(b.ev0, st));
+    hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
+    if (n == 0) { // empty scene: one root with four empty slots (frame.cpp:614-624), one zero triangle record
+        float q[28];
+        for (int c = 0; c < 4; c++) {
+            for (int ax = 0; ax < 3; ax++) { q[8 * ax + c] = 1e30f; q[8 * ax + 4 + c] = -1e30f; }
+            const uint32_t e = HJR_LEAF_FLAG;
+            memcpy(&q[24 + c], &e, 4);
+        }
+        DCHK(hipMemcpyAsync(b.nodes.p, q, sizeof(q), hipMemcpyHostToDevice, st));
+        DCHK(hipMemsetAsync(b.tri_geom.p, 0, HJR_TRI_F4 * 16, st));
+        DCHK(hipEventRecord(b.ev1, st));
+        DCHK(hipStreamSynchronize(st));
+        r.n_nodes = 1; r.stack_need = 2; r.depth = 0;
+        DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
+        return HJR_OK;
+    }
+    FlattenArgs fa;
+    fa.vert = (const float*)b.vert.p; fa.norm = (const float*)b.norm.p; fa.uv = (const float*)b.uv.p; fa.xf = (const float*)b.xf.p;
+    fa.idx = (const uint32_t*)b.idx.p; fa.mat = (const uint32_t*)b.mat.p; fa.prim_off = (const uint32_t*)b.prim_off.p;
+    fa.n = n; fa.n_inst = n_inst;
+    fa.wv = (float*)b.wv.p; fa.shade = (float*)b.tri_shade.p; fa.box = (float*)b.box.p; fa.cent = (float*)b.cent.p;
+    fa.inst = (uint32_t*)b.tri_inst.p; fa.hdr = hdr;
+    hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, fa);
+    uint64_t* keys[2] = { (uint64_t*)b.keys[0].p, (uint64_t*)b.keys[1].p };
+    uint32_t* vals[2] = { (uint32_t*)b.vals[0].p, (uint32_t*)b.vals[1].p };
+    hipLaunchKernelGGL(morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (float*)b.box.p, (const float*)b.cent.p, (const uint32_t*)hdr, keys[0], vals[0]);
+    for (int pass = 0; pass < 8; pass++) { // 8 x 8 bits: the result is back in keys[0] / vals[0]
+        const int s = pass & 1;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], n, 8 * pass, (uint32_t*)b.hist.p, nb);
+        if (const int rc = scan((uint32_t*)b.hist.p, nullptr, nb * 256u, (uint32_t*)b.part.p, nullptr, st, err)) return rc;
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], (const uint32_t*)vals[s], n, 8 * pass,
+                           (const uint32_t*)b.hist.p, nb, keys[s ^ 1], vals[s ^ 1]);
+    }
+    hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals[0], (const float*)b.wv.p, (const uint32_t*)b.mat.p,
+                       (const float*)b.box.p, (float*)b.tri_geom.p, (float*)b.leaf_box.p);
+    if (n >= 2) {
+        hipLaunchKernelGGL(karras_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint64_t*)keys[0], (uint2*)b.inner_child.p,
+                           (uint2*)b.inner_range.p, (uint32_t*)b.parent.p);
+        DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+        hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)b.inner_child.p, (const uint32_t*)b.parent.p,
+                           (uint32_t*)b.counter.p, (const float4*)b.leaf_box.p, (float4*)b.inner_box.p);
+    }
+    DCHK(hipGetLastError());
+    CollapseArgs ca;
+    ca.child = (const uint2*)b.inner_child.p; ca.range = (const uint2*)b.inner_range.p;
+    ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
+    ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
+    Front* fr[2] = { (Front*)b.frontier[0].p, (Front*)b.frontier[1].p };
+    Wide* wide = (Wide*)b.wide.p;
+    uint32_t* n_inner = (uint32_t*)((char*)b.wide.p + nn * sizeof(Wide));
+    hipLaunchKernelGGL(collapse_init_kernel, dim3(1), dim3(1), 0, st, n, fr[0], hdr);
+    const unsigned grid = (unsigned)std::min<size_t>(blocks_for(nn), 1024);
+    uint32_t level = 0, F = 1;
+    while (F > 0 && level < DEVICE_BVH_MAX_STACK) {
+        for (int k = 0; k < LEVEL_BATCH; k++, level++) {
+            Front* cur = fr[level & 1];
+            hipLaunchKernelGGL(wide_expand_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Front*)cur, wide, n_inner);
+            if (const int rc = scan(n_inner, hdr + H_F, 0u, (uint32_t*)b.part.p, hdr + H_NEXT, st, err)) return rc;
+            hipLaunchKernelGGL(wide_emit_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Wide*)wide, (const uint32_t*)n_inner, fr[(level + 1) & 1],
+                               (float4*)b.nodes.p);
+            hipLaunchKernelGGL(level_advance_kernel, dim3(1), dim3(1), 0, st, hdr);
+        }
+        DCHK(hipGetLastError());
+        DCHK(hipMemcpyAsync(&F, hdr + H_F, 4, hipMemcpyDeviceToHost, st));
+        DCHK(hipStreamSynchronize(st));
+    }
+    DCHK(hipEventRecord(b.ev1, st));
+    uint32_t h[H_WORDS];
+    DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
+    const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
+    if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
+    r.n_nodes = h[H_BASE];
+    r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
+    r.depth = h[H_DEPTH];
+    if (F > 0 || r.stack_need > DEVICE_BVH_MAX_STACK) { err = "BVH deeper than the traversal stack"; return HJR_ERR_ARG; }
+    return HJR_OK;
+}
+
+} // namespace hjr

@@ -137,6 +137,7 @@ extern "C" int hjr_upload_scene(hjr_ctx* c, const hjr_scene_view* v)
     HIPCHK(hipStreamSynchronize(c->stream));
     c->have_scene = true;
     c->have_frame = false;
+    c->dbvh.have_scene = false; // the device builder uploads the new scene at its next build
     return HJR_OK;
 }
 
@@ -157,7 +158,12 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
     bo.leaf_max = c->opt.get(hjr::OPT_LEAF_MAX, -1);
     bo.refine = c->opt.get(hjr::OPT_BVH_REFINE, -1);
     bo.timing = c->opt.get(hjr::OPT_VERBOSE, 0) != 0;
-    const uint32_t build_tag = (bo.allow_lds ? 1u : 0u) | (bo.prefer_stack16 ? 2u : 0u) | ((uint32_t)(bo.bvh_width + 1) << 2) | ((uint32_t)(bo.leaf_max + 1) << 6) | ((uint32_t)(bo.refine + 1) << 10);
+    const bool device = c->opt.get(hjr::OPT_DEVICE_BVH, 0) != 0; // option "device_bvh": the build runs at hjr_commit_transforms
+    if (device && (bo.bvh_width == 2 || c->opt.get(hjr::OPT_LDS_BVH, -1) == 1)) {
+        set_error("hjr_set_transforms: \"device_bvh\" builds the BVH4 memory layout only; it cannot be combined with \"bvh_width\" 2 or \"lds_bvh\" 1");
+        return HJR_ERR_ARG;
+    }
+    const uint32_t build_tag = (bo.allow_lds ? 1u : 0u) | (bo.prefer_stack16 ? 2u : 0u) | ((uint32_t)(bo.bvh_width + 1) << 2) | ((uint32_t)(bo.leaf_max + 1) << 6) | ((uint32_t)(bo.refine + 1) << 10) | (device ? 1u << 16 : 0u);
     c->pending_valid = false;
     c->pending_same = false;
     // unchanged instance transforms (static geometry, e.g. a camera-only animation): the world-space arrays and the BVH of the
@@ -170,10 +176,37 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
         return HJR_OK;
     }
     const auto t_build0 = std::chrono::steady_clock::now();
-    if (!hjr::build_frame(c->scene, m, inv, n, bo, c->pending, err)) { set_error("hjr_set_transforms: " + err); return HJR_ERR_ARG; }
+    if (device) { // validation and the light table here; flatten + BVH at the commit, on the device
+        if (n != c->scene.n_instances) { set_error("hjr_set_transforms: instance count does not match the uploaded scene"); return HJR_ERR_ARG; }
+        c->pending = hjr::FrameData();
+        c->pending.n_tris = c->scene.n_triangles;
+        c->pending.width = 4;
+        c->pending.lds_mode = 0;
+        hjr::build_lights(c->scene, m, inv, c->pending);
+    } else if (!hjr::build_frame(c->scene, m, inv, n, bo, c->pending, err)) { set_error("hjr_set_transforms: " + err); return HJR_ERR_ARG; }
     c->pending_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
+    c->pending_device = device;
     c->pending_m.assign(m, m + (size_t)n * 12); c->pending_inv.assign(inv, inv + (size_t)n * 12); c->pending_build_tag = build_tag;
     c->pending_valid = true;
+    return HJR_OK;
+}
+
+// option "device_bvh": the build of the prepared transforms as kernels on the context's stream, behind what is already queued there.
+// It writes the builder's own buffers; they become current (swapped with d_nodes, d_tri_*, d_lights) only when it succeeds, so a
+// failed build leaves the previous frame current.
+static int commit_device(hjr_ctx* c)
+{
+    const int leaf_max = c->opt.get(hjr::OPT_LEAF_MAX, (int)HJR_LEAF_DEFAULT);
+    hjr::DeviceBvhResult r;
+    std::string err;
+    hjr::FrameData& f = c->pending;
+    const int rc = hjr::device_bvh_build(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), (uint32_t)(c->pending_m.size() / 12), (uint32_t)leaf_max,
+                                         f.lights.data(), f.lights.size(), c->stream, r, err);
+    if (rc != HJR_OK) { set_error("hjr_set_transforms: " + err); return rc; }
+    c->d_nodes.swap(c->dbvh.nodes); c->d_tri_geom.swap(c->dbvh.tri_geom); c->d_tri_shade.swap(c->dbvh.tri_shade);
+    c->d_tri_inst.swap(c->dbvh.tri_inst); c->d_lights.swap(c->dbvh.lights);
+    f.n_nodes = r.n_nodes; f.stack_need = r.stack_need; f.depth = r.depth;
+    c->pending_build_ms = r.build_ms;
     return HJR_OK;
 }
 
@@ -187,21 +220,56 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
         return HJR_OK;
     }
     HIPCHK(hipSetDevice(c->device));
-    std::swap(c->frame, c->pending);
+    if (c->pending_device) {
+        if (const int rc = commit_device(c)) return rc;
+        std::swap(c->frame, c->pending);
+    } else {
+        std::swap(c->frame, c->pending);
+        const hjr::FrameData& f = c->frame;
+        bool ok = c->d_nodes.upload(f.nodes.data(), f.nodes.size() * 4, c->stream) &&
+                  c->d_tri_geom.upload(f.tri_geom.data(), f.tri_geom.size() * 4, c->stream) &&
+                  c->d_tri_shade.upload(f.tri_shade.data(), f.tri_shade.size() * 4, c->stream) &&
+                  c->d_tri_inst.upload(f.tri_inst.data(), f.tri_inst.size() * 4, c->stream) &&
+                  c->d_lights.upload(f.lights.data(), f.lights.size() * 4, c->stream);
+        if (!ok) { c->have_frame = false; set_error("hjr_set_transforms: device upload failed"); return HJR_ERR_DEVICE; }
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     const hjr::FrameData& f = c->frame;
-    bool ok = c->d_nodes.upload(f.nodes.data(), f.nodes.size() * 4, c->stream) &&
-              c->d_tri_geom.upload(f.tri_geom.data(), f.tri_geom.size() * 4, c->stream) &&
-              c->d_tri_shade.upload(f.tri_shade.data(), f.tri_shade.size() * 4, c->stream) &&
-              c->d_tri_inst.upload(f.tri_inst.data(), f.tri_inst.size() * 4, c->stream) &&
-              c->d_lights.upload(f.lights.data(), f.lights.size() * 4, c->stream);
-    if (!ok) { c->have_frame = false; set_error("hjr_set_transforms: device upload failed"); return HJR_ERR_DEVICE; }
-    HIPCHK(hipStreamSynchronize(c->stream));
     c->have_frame = true;
     c->last_m.swap(c->pending_m); c->last_inv.swap(c->pending_inv); c->last_build_tag = c->pending_build_tag;
     c->stats.bvh_nodes = f.n_nodes;
     c->stats.bvh_depth = f.depth;
-    if (c->opt.get(hjr::OPT_VERBOSE, 0)) fprintf(stderr, "[hjr] BVH%u (lds_mode %d): %u nodes (%zu KB), %u triangles (%zu KB), stack %u entries/lane, host build %.1f ms\n", f.width, f.lds_mode, f.n_nodes, f.nodes.size() * 4 / 1024, f.n_tris, f.tri_geom.size() * 4 / 1024, f.stack_need, c->pending_build_ms);
+    c->stats.bvh_builder = c->pending_device ? 1u : 0u;
+    c->stats.frame_build_ms = (float)c->pending_build_ms;
+    if (c->opt.get(hjr::OPT_VERBOSE, 0))
+        fprintf(stderr, "[hjr] BVH%u (lds_mode %d): %u nodes (%zu KB), %u triangles (%zu KB), stack %u entries/lane, %s build %.1f ms\n", f.width, f.lds_mode, f.n_nodes,
+                (size_t)f.n_nodes * (f.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4) * 16 / 1024, f.n_tris, (size_t)std::max(f.n_tris, 1u) * HJR_TRI_F4 * 16 / 1024,
+                f.stack_need, c->pending_device ? "device" : "host", c->pending_build_ms);
     c->stats.n_triangles = f.n_tris;
+    return HJR_OK;
+}
+
+// inspection copy of the current frame data (tests): synchronous, from the device buffers the kernels read
+extern "C" int hjr_copy_frame_data(hjr_ctx* c, int what, void* dst, size_t dst_bytes, size_t* bytes)
+{
+    if (!c || !bytes) { set_error("hjr_copy_frame_data: null argument"); return HJR_ERR_ARG; }
+    if (!c->have_frame) { set_error("hjr_copy_frame_data: no frame data (set transforms first)"); return HJR_ERR_STATE; }
+    const hjr::FrameData& f = c->frame;
+    const DevBuf* src = nullptr;
+    size_t n = 0;
+    switch (what) {
+    case HJR_FRAME_NODES: src = &c->d_nodes; n = (size_t)f.n_nodes * (f.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4) * 16; break;
+    case HJR_FRAME_TRI_GEOM: src = &c->d_tri_geom; n = (size_t)std::max(f.n_tris, 1u) * HJR_TRI_F4 * 16; break;
+    case HJR_FRAME_TRI_SHADE: src = &c->d_tri_shade; n = (size_t)f.n_tris * HJR_SHADE_F4 * 16; break;
+    case HJR_FRAME_LIGHTS: src = &c->d_lights; n = (size_t)f.n_lights * HJR_LIGHT_F4 * 16; break;
+    default: set_error("hjr_copy_frame_data: unknown HJR_FRAME_* value"); return HJR_ERR_ARG;
+    }
+    *bytes = n;
+    if (!dst || n == 0) return HJR_OK;
+    if (dst_bytes < n) { set_error("hjr_copy_frame_data: destination too small"); return HJR_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(dst, src->p, n, hipMemcpyDeviceToHost));
     return HJR_OK;
 }
 

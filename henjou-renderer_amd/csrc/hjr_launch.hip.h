@@ -14,32 +14,12 @@
 #include "../host/frame.hpp"
 #include "hjr_kernel.hip.h"
 #include "hjr_wavefront.hip.h"
+#include "hjr_bvh_build.h"
 
 namespace hjr {
 void set_error(const std::string& s);
 }
 using hjr::set_error;
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    // grow without copying to exactly `bytes` (the old contents are lost); *grown tells whether the buffer was reallocated
-    bool reserve(size_t bytes, bool* grown = nullptr)
-    {
-        if (grown) *grown = cap < bytes;
-        if (cap >= bytes) return true;
-        release();
-        if (hipMalloc(&p, bytes) != hipSuccess) return false;
-        cap = bytes;
-        return true;
-    }
-    bool upload(const void* src, size_t bytes, hipStream_t st) // grows with 25 % slack
-    {
-        if (bytes > cap && !reserve(bytes + bytes / 4 + 256)) return false;
-        return !bytes || hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 // Work area (d_work, zeroed before every launch), byte offsets.  The diagnostic builds (HJR_TIMING, HJR_WF_WATCHDOG) write their slots
 // as P.stats[HJR_NSTAT + i], so those follow the counters directly.
@@ -67,7 +47,9 @@ struct hjr_ctx {
     bool pending_valid = false, pending_same = false;
     uint32_t pending_build_tag = 0;
     double pending_build_ms = 0.0;
-    hjr::FrameData frame;
+    bool pending_device = false; // option "device_bvh": hjr_commit_transforms runs the build (pending.lights is the host-built light table)
+    hjr::FrameData frame; // device-built frame data: the counts, format and lights only (the arrays live in d_nodes, d_tri_*)
+    hjr::DeviceBvh dbvh;  // the device builder's scene copy, scratch and pending output buffers
     DevBuf d_nodes, d_tri_geom, d_tri_shade, d_tri_inst, d_materials, d_lights, d_lut, d_work;
     DevBuf d_texels, d_tex_desc, d_srgb_lut, d_sky;
     int sky_w = 0, sky_h = 0;
@@ -90,6 +72,7 @@ struct hjr_ctx {
         for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
                            &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out })
             b->release();
+        dbvh.release();
     }
 };
 

@@ -496,6 +496,41 @@ void emit_bvh4(const Builder& B, FrameData& out)
 
 } // namespace
 
+// light table (light_sample.h:22-58, 69-72); both builders use it (the device path keeps it on the host: O(lights), double arithmetic)
+void build_lights(const SceneCopy& sc, const float* M, const float* Mi, FrameData& out)
+{
+    const uint32_t nl = (uint32_t)sc.light_prim_ids.size();
+    out.n_lights = nl;
+    out.lights.assign((size_t)nl * HJR_LIGHT_F4 * 4, 0.0f);
+    for (uint32_t l = 0; l < nl; l++) {
+        uint32_t prim = sc.light_prim_ids[l];
+        // the reference's binary search over prim_offsets (light_sample.h:26-38) == last offset <= prim
+        uint32_t inst = (uint32_t)(std::upper_bound(sc.prim_offset.begin(), sc.prim_offset.end(), prim) - sc.prim_offset.begin()) - 1;
+        const float* m = M + 12 * inst;
+        const float* mi = Mi + 12 * inst;
+        V3 v[3], nn[3];
+        for (int k = 0; k < 3; k++) {
+            uint32_t idx = sc.indices[3 * prim + k];
+            v[k] = transform_position(m, { sc.vertices[3 * idx], sc.vertices[3 * idx + 1], sc.vertices[3 * idx + 2] });
+            nn[k] = transform_normal(mi, { sc.normals[3 * idx], sc.normals[3 * idx + 1], sc.normals[3 * idx + 2] });
+        }
+        V3 c = cross(sub(v[1], v[0]), sub(v[2], v[0]));
+        float area = sqrtf(dot(c, c)) * 0.5f;
+        float select_pdf = 1.0f / nl;
+        float pdf = (float)(1.0 / (double)area); // `pdf = 1.0 / light_area;` is a double division (light_sample.h:69)
+        pdf *= select_pdf;
+        float* L = &out.lights[(size_t)l * 24];
+        for (int k = 0; k < 3; k++) {
+            L[4 * k + 0] = v[k].x; L[4 * k + 1] = v[k].y; L[4 * k + 2] = v[k].z;
+            L[12 + 4 * k + 0] = nn[k].x; L[12 + 4 * k + 1] = nn[k].y; L[12 + 4 * k + 2] = nn[k].z;
+        }
+        L[3] = pdf;
+        L[23] = 1.0f / pdf; // l5.w: float3 / pdf is float3 * (1.0f / pdf) (vec_math.h), the same IEEE division here as on the device
+        L[19] = u2f(prim); // l4.w: global prim id (MIS looks the emissive triangle up by it)
+        L[7] = sc.light_prim_emission[3 * l]; L[11] = sc.light_prim_emission[3 * l + 1]; L[15] = sc.light_prim_emission[3 * l + 2];
+    }
+}
+
 void set_host_threads(int n) { g_host_threads.store(n > 0 ? n : 0, std::memory_order_relaxed); }
 
 bool build_frame(const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const BuildOptions& bo, FrameData& out, std::string& err)
@@ -543,37 +578,7 @@ bool build_frame(const SceneCopy& sc, const float* M, const float* Mi, uint32_t 
     });
 
     lap("flatten");
-    // light table (light_sample.h:22-58, 69-72)
-    const uint32_t nl = (uint32_t)sc.light_prim_ids.size();
-    out.n_lights = nl;
-    out.lights.assign((size_t)nl * HJR_LIGHT_F4 * 4, 0.0f);
-    for (uint32_t l = 0; l < nl; l++) {
-        uint32_t prim = sc.light_prim_ids[l];
-        // the reference's binary search over prim_offsets (light_sample.h:26-38) == last offset <= prim
-        uint32_t inst = (uint32_t)(std::upper_bound(sc.prim_offset.begin(), sc.prim_offset.end(), prim) - sc.prim_offset.begin()) - 1;
-        const float* m = M + 12 * inst;
-        const float* mi = Mi + 12 * inst;
-        V3 v[3], nn[3];
-        for (int k = 0; k < 3; k++) {
-            uint32_t idx = sc.indices[3 * prim + k];
-            v[k] = transform_position(m, { sc.vertices[3 * idx], sc.vertices[3 * idx + 1], sc.vertices[3 * idx + 2] });
-            nn[k] = transform_normal(mi, { sc.normals[3 * idx], sc.normals[3 * idx + 1], sc.normals[3 * idx + 2] });
-        }
-        V3 c = cross(sub(v[1], v[0]), sub(v[2], v[0]));
-        float area = sqrtf(dot(c, c)) * 0.5f;
-        float select_pdf = 1.0f / nl;
-        float pdf = (float)(1.0 / (double)area); // `pdf = 1.0 / light_area;` is a double division (light_sample.h:69)
-        pdf *= select_pdf;
-        float* L = &out.lights[(size_t)l * 24];
-        for (int k = 0; k < 3; k++) {
-            L[4 * k + 0] = v[k].x; L[4 * k + 1] = v[k].y; L[4 * k + 2] = v[k].z;
-            L[12 + 4 * k + 0] = nn[k].x; L[12 + 4 * k + 1] = nn[k].y; L[12 + 4 * k + 2] = nn[k].z;
-        }
-        L[3] = pdf;
-        L[23] = 1.0f / pdf; // l5.w: float3 / pdf is float3 * (1.0f / pdf) (vec_math.h), the same IEEE division here as on the device
-        L[19] = u2f(prim); // l4.w: global prim id (MIS looks the emissive triangle up by it)
-        L[7] = sc.light_prim_emission[3 * l]; L[11] = sc.light_prim_emission[3 * l + 1]; L[15] = sc.light_prim_emission[3 * l + 2];
-    }
+    build_lights(sc, M, Mi, out);
 
     // BVH over padded triangle boxes
     Builder B;

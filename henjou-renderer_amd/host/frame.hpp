@@ -41,4 +41,7 @@ struct SceneCopy {
 bool build_frame(const SceneCopy& sc, const float* transforms12, const float* inv12, uint32_t n_instances, const BuildOptions& bo,
                  FrameData& out, std::string& err);
 
+// the light table of build_frame alone (out.lights, out.n_lights)
+void build_lights(const SceneCopy& sc, const float* transforms12, const float* inv12, FrameData& out);
+
 } // namespace hjr

@@ -131,6 +131,7 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             o.serial_io = flag("serial_io") ? 1 : 0;
             o.fast_math = flag("fast_math") ? 1 : 0;
             o.force_rebuild = flag("force_rebuild") ? 1 : 0;
+            o.device_bvh = flag("device_bvh") ? 1 : 0; // the frame data built on the device (option "device_bvh")
         }
     } catch (std::exception& e) { // :222-225
         err = std::string("Caught exception: ") + e.what();

@@ -15,6 +15,7 @@
  */
 #ifndef HENJOU_HIP_H
 #define HENJOU_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -136,6 +137,7 @@ typedef struct hjr_render_option {
     int32_t serial_io;           /* default 0; 1: hjr_render_file renders, writes and prepares the next frame one after the other (no overlap) */
     int32_t fast_math;           /* default 0; 1: hjr_render_file / henjou_cli launch with HJR_FLAG_FAST_MATH */
     int32_t force_rebuild;       /* default 0; 1: hjr_render_file rebuilds the frame data every frame even when nothing moved (benchmarking) */
+    int32_t device_bvh;          /* default 0; 1: hjr_render_file / henjou_cli build the frame data on the device (option "device_bvh") */
 } hjr_render_option;
 
 typedef struct hjr_camera {      /* Params.camera_* (renderer/renderer.h:1187-1191) */
@@ -189,6 +191,8 @@ typedef struct hjr_stats {
     uint32_t nan_located;
     uint32_t fast_math;          /* 1: the last launch ran the HJR_FLAG_FAST_MATH kernels */
     uint32_t nan_where[8][3];
+    uint32_t bvh_builder;        /* who built the current frame data: 0 = host threads, 1 = device kernels (option "device_bvh") */
+    float    frame_build_ms;     /* its build time: host wall time of flatten + BVH build, or HIP-event time of the device build */
 } hjr_stats;
 
 typedef struct hjr_scene hjr_scene; /* owning, host side (SceneData + animations) */
@@ -294,10 +298,19 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *   "host_threads"    1..256      worker threads of the per-frame host preparation, process-wide (min(hardware threads, 16))
  *   "verbose"         0 1         BVH format, sizes, host build stages per frame on stderr (0)
  *   "force_rebuild"   0 1         rebuild the frame data even when the transforms did not change (0)
+ *   "device_bvh"      0 1         0: flatten + BVH build on host threads (default); 1: on the device, as kernels on the context's stream
+ *                                 (Morton-order tree collapsed to BVH4, always the memory layout: lds_mode 0).  hjr_prepare_transforms then
+ *                                 only validates and builds the light table; hjr_commit_transforms runs the build and makes its result
+ *                                 current only if it succeeds.  Rejected together with a forced "bvh_width" 2 or "lds_bvh" 1;
+ *                                 "bvh_refine" does not apply                                                                  [*]
  *   [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
+/* Synchronous copy of the current frame data (either builder) for inspection: `what` is one of HJR_FRAME_*; dst NULL asks for the size
+ * only (*bytes), otherwise dst_bytes must hold it.  Layouts: csrc/hjr_layout.h.  No reference counterpart (OptiX keeps its GAS opaque). */
+enum { HJR_FRAME_NODES = 0, HJR_FRAME_TRI_GEOM = 1, HJR_FRAME_TRI_SHADE = 2, HJR_FRAME_LIGHTS = 3 };
+int hjr_copy_frame_data(hjr_ctx*, int what, void* dst, size_t dst_bytes, size_t* bytes);
 /* Host-only self-test of the 16-bit traversal-stack encoding (csrc/hjr_traverse.hip.h): 0 when every child ref of a tree the
  * builder admits to that layout survives encode + decode.  No reference counterpart (OptiX owns its traversal stack). */
 int hjr_selftest_stack16(void);
