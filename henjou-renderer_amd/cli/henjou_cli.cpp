@@ -62,6 +62,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     hjr_ctx* ctx = nullptr;
     HJRX(hjr_create(rank, &ctx));
     if (opt.device_bvh) HJRX(hjr_set_option(ctx, "device_bvh", 1));
+    if (opt.device_bvh_opt) HJRX(hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt));
     HJRX(hjr_upload_scene(ctx, &view));
     {
         uint8_t* lut = nullptr; int lw = 0, lh = 0;

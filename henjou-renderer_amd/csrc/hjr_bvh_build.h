@@ -43,6 +43,7 @@ struct DeviceBvh {
     DevBuf xf;  // per instance: 12 floats of the transform, then 12 of the inverse
     // scratch of one build
     DevBuf wv, box, cent, keys[2], vals[2], hist, part, leaf_box, inner_box, inner_child, inner_range, parent, counter, frontier[2], wide, hdr;
+    DevBuf node_count, node_cost, leaf_pos; // scratch of the treelet restructuring ("device_bvh_opt")
     // the frame data a build writes; hjr_commit_transforms swaps them with the context's current buffers when the build succeeds
     DevBuf nodes, tri_geom, tri_shade, tri_inst, lights;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -57,6 +58,7 @@ struct DeviceBvhResult {
 // Enqueues the whole build on `st` behind whatever is already there, waits for it and reads back its header.  HJR_ERR_ARG with `err`
 // set for a scene the host builder rejects too (non-finite vertex, tree deeper than the traversal stack allows), HJR_ERR_DEVICE for a
 // runtime failure.  The lights are the host's table (build_lights), copied into `b.lights`.
-int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, const float* lights,
-                     size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+// `opt_rounds` (option "device_bvh_opt", 0..3) treelet-restructuring rounds run over the BVH2 before the collapse; 0 leaves the build as it was.
+int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
+                     const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
 } // namespace hjr

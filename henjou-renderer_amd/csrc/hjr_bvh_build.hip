@@ -5,6 +5,8 @@
 //   radix sort   stable LSD over (code, prim id), 8 bits per pass, reduce-then-scan in separate launches
 //   hierarchy    Karras 2012: every inner node finds its range and split on its own (ties by index)
 //   boxes        bottom-up, one agent-scope acq_rel counter per inner node: the second lane to arrive takes the union
+//   treelets     ("device_bvh_opt" rounds) Karras & Aila 2013: bottom-up climbs with the same hand-off, a wave per 7-leaf treelet
+//                finds its SAH-optimal topology; then leaf positions and inner ranges are recomputed and tri_geom is gathered in the new order
 //   collapse     BVH4 level by level with emit_bvh4's rules; ids from a scan of each level (breadth-first, same bytes every run)
 // No workgroup ever waits for another one; every cross-launch size the host does not know is read by the kernels from `hdr`.
 #include <hip/hip_runtime.h>
@@ -35,6 +37,7 @@ enum Hdr {
     H_BASE = 9,      // first wide id of the current level
     H_F = 10,        // nodes of the current level
     H_NEXT = 11,     // nodes of the next level (scan total)
+    H_ERR = 12,      // non-zero: the restructured BVH2 failed a structural bound (a bug, reported as HJR_ERR_DEVICE)
     H_WORDS = 16
 };
 
@@ -273,20 +276,27 @@ __global__ void __launch_bounds__(NT) radix_scatter_kernel(const uint64_t* keys,
 }
 
 // ---- leaves in sorted order: tri_geom (frame.cpp:652-660) and the leaf boxes ----------------------------------------------------
-__global__ void __launch_bounds__(NT) gather_kernel(uint32_t n, const uint32_t* order, const float* wv, const uint32_t* mat, const float* box, float* tri_geom, float* leaf_box)
+// Either output may be null.  `pos` (null: the sorted order itself) is the tri_geom row of sorted leaf k after a restructuring.
+__global__ void __launch_bounds__(NT) gather_kernel(uint32_t n, const uint32_t* order, const uint32_t* pos, const float* wv, const uint32_t* mat,
+                                                    const float* box, float* tri_geom, float* leaf_box)
 {
     const uint32_t k = blockIdx.x * NT + threadIdx.x;
     if (k >= n) return;
     const uint32_t t = order[k];
-    const float* v = wv + 9 * (size_t)t;
-    float4* g = reinterpret_cast<float4*>(tri_geom) + 3 * (size_t)k;
-    g[0] = make_float4(v[0], v[1], v[2], v[3]);
-    g[1] = make_float4(v[4], v[5], v[6], v[7]);
-    g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(mat[t]), 0.0f);
-    const float4* b = reinterpret_cast<const float4*>(box) + 2 * (size_t)t;
-    float4* lb = reinterpret_cast<float4*>(leaf_box) + 2 * (size_t)k;
-    lb[0] = b[0];
-    lb[1] = b[1];
+    const uint32_t d = pos ? pos[k] : k;
+    if (tri_geom && d < n) {
+        const float* v = wv + 9 * (size_t)t;
+        float4* g = reinterpret_cast<float4*>(tri_geom) + 3 * (size_t)d;
+        g[0] = make_float4(v[0], v[1], v[2], v[3]);
+        g[1] = make_float4(v[4], v[5], v[6], v[7]);
+        g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(mat[t]), 0.0f);
+    }
+    if (leaf_box) {
+        const float4* b = reinterpret_cast<const float4*>(box) + 2 * (size_t)t;
+        float4* lb = reinterpret_cast<float4*>(leaf_box) + 2 * (size_t)k;
+        lb[0] = b[0];
+        lb[1] = b[1];
+    }
 }
 
 // ---- hierarchy (Karras 2012) ----------------------------------------------------------------------------------------------------
@@ -358,6 +368,285 @@ __global__ void __launch_bounds__(NT) boxes_kernel(int n, const uint2* child, co
     }
 }
 
+// ---- treelet restructuring (option "device_bvh_opt"; Karras & Aila, HPG 2013) ------------------------------------------------------
+// Collapse-aware SAH of a BVH2 node: a node of at most leaf_max triangles becomes a BVH4 leaf (is_inner), so it costs Ct * A * N;
+// any other node costs Ci * A plus its children.  The constants of the cost model live here only.
+constexpr float SAH_CI = 1.2f, SAH_CT = 1.0f;
+constexpr uint32_t TREELET = 7;                      // leaves of a treelet: 127 subsets in the dynamic programme, 6 inner nodes
+// A topology replaces the treelet only when its cost times this is still below the current cost: strictly lower by more than float
+// rounding of the two sums (<= 13 terms) can explain, so that equal-cost alternatives (all boxes equal) never replace the tree.
+constexpr float SAH_ACCEPT = 1.0f + 1.0f / 65536.0f;
+// subsets of the 7 treelet leaves by size, then value; size k starts at c_size_start[k]
+__constant__ uint8_t c_subsets[127] = {
+    1, 2, 4, 8, 16, 32, 64, 3, 5, 6, 9, 10, 12, 17, 18, 20, 24, 33, 34, 36, 40, 48, 65, 66, 68, 72, 80, 96, 7, 11, 13, 14, 19, 21, 22, 25, 26, 28,
+    35, 37, 38, 41, 42, 44, 49, 50, 52, 56, 67, 69, 70, 73, 74, 76, 81, 82, 84, 88, 97, 98, 100, 104, 112, 15, 23, 27, 29, 30, 39, 43, 45, 46, 51,
+    53, 54, 57, 58, 60, 71, 75, 77, 78, 83, 85, 86, 89, 90, 92, 99, 101, 102, 105, 106, 108, 113, 114, 116, 120, 31, 47, 55, 59, 61, 62, 79, 87, 91,
+    93, 94, 103, 107, 109, 110, 115, 117, 118, 121, 122, 124, 63, 95, 111, 119, 123, 125, 126, 127 };
+__constant__ uint8_t c_size_start[9] = { 0, 0, 7, 28, 63, 98, 119, 126, 127 };
+
+__device__ __forceinline__ float sah_area(const float4& lo, const float4& hi)
+{
+    const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
+    return (dx < 0) ? 0.0f : 2.0f * (dx * dy + dy * dz + dz * dx);
+}
+__device__ __forceinline__ float sah_cost(float area, uint32_t cnt, uint32_t leaf_max, float children)
+{
+    return cnt <= leaf_max ? SAH_CT * area * (float)cnt : fmaf(SAH_CI, area, children);
+}
+// index of a node in `parent`: inner nodes first, then the leaves
+__device__ __forceinline__ size_t parent_slot(int n, uint32_t ref) { return (ref & REF_LEAF) ? (size_t)(n - 1) + (ref & ~REF_LEAF) : ref; }
+// the i-th (1-based, increasing) non-empty subset of `mask`: the bits of i deposited into its set bits
+__device__ __forceinline__ uint32_t deposit(uint32_t i, uint32_t mask)
+{
+    uint32_t q = 0;
+    for (; mask; mask &= mask - 1, i >>= 1)
+        if (i & 1u) q |= mask & (0u - mask);
+    return q;
+}
+// orders this wave's LDS accesses across its lanes (the wave runs one treelet while its other waves climb on their own)
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct TreeletArgs {
+    int n;
+    uint32_t leaf_max, gamma; // treelet roots: nodes of at least gamma triangles
+    uint2* child;
+    uint32_t *parent, *counter, *count; // count: triangles under each inner node
+    float* cost;                        // collapse-aware SAH of each inner node
+    const float4* leaf_box;
+    float4* inner_box;
+};
+__device__ __forceinline__ void node_sah(const TreeletArgs& a, uint32_t ref, uint32_t& cnt, float& cost)
+{
+    if (ref & REF_LEAF) {
+        float4 lo, hi;
+        box_of(ref, a.leaf_box, a.inner_box, lo, hi);
+        cnt = 1;
+        cost = sah_cost(sah_area(lo, hi), 1u, a.leaf_max, 0.0f);
+    } else {
+        cnt = a.count[ref];
+        cost = a.cost[ref];
+    }
+}
+
+struct TreeletLds {                 // one per wave
+    float area[128], cost[128];     // per subset of the treelet's leaves: box area, optimal cost
+    uint32_t cnt[128], part[128];   // triangles, best split (the part without the subset's lowest leaf)
+    float4 lo[8], hi[8];            // treelet leaves: boxes, refs
+    uint32_t ref[8];
+    uint32_t inner[8], sub[8];      // treelet inner node ids ([0] the root) and the subset each one takes in the new topology
+    uint2 kids[8];
+};
+
+// One wave restructures the treelet under R; every lane calls it with the same R and the root's current cost, and every lane gets
+// the root's cost back.  Nodes under R are complete: their writers' releases reached R's counter before the climbing lane's acquire,
+// whose L1 invalidate covers the whole wave.  The stores here drain with the wave's next agent-scope release (s_waitcnt vmcnt is per
+// wave), the climbing lane's add on the parent's counter.
+__device__ float treelet(const TreeletArgs& a, TreeletLds& L, uint32_t R, float old_cost, int lane)
+{
+    wave_sync(); // the previous treelet's reads of L are done
+    // formation: lane i < 7 holds treelet leaf i, lane j < 6 inner node j; expand the leaf of largest area (ties: lowest slot)
+    const uint2 c0 = a.child[R];
+    uint32_t ref = lane == 0 ? c0.x : c0.y, inner = R;
+    float4 lo, hi;
+    box_of(ref, a.leaf_box, a.inner_box, lo, hi);
+    float area = sah_area(lo, hi);
+    for (int nl = 2; nl < (int)TREELET; nl++) {
+        const bool cand = lane < nl && !(ref & REF_LEAF);
+        const uint64_t cm = __ballot(cand);
+        if (!cm) return old_cost; // (never: R holds at least gamma >= 7 triangles)
+        float m = cand ? area : -INFINITY;
+        for (int o = 1; o < 8; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+        m = __shfl(m, 0);
+        const uint64_t bm = __ballot(cand && area == m);
+        const int b = __ffsll((unsigned long long)(bm ? bm : cm)) - 1;
+        const uint32_t rb = __shfl(ref, b);
+        const uint2 cb = a.child[rb];
+        if (lane == nl - 1) inner = rb;
+        if (lane == b || lane == nl) {
+            ref = lane == b ? cb.x : cb.y;
+            box_of(ref, a.leaf_box, a.inner_box, lo, hi);
+            area = sah_area(lo, hi);
+        }
+    }
+    if (lane < (int)TREELET) {
+        uint32_t cnt;
+        float cost;
+        node_sah(a, ref, cnt, cost);
+        L.lo[lane] = lo; L.hi[lane] = hi; L.ref[lane] = ref;
+        L.cnt[1u << lane] = cnt;
+        L.cost[1u << lane] = cost;
+    }
+    if (lane < (int)TREELET - 1) L.inner[lane] = inner;
+    wave_sync();
+    // subset boxes (exact min / max) and triangle counts
+    for (uint32_t s = (uint32_t)lane; s < 128; s += 64) {
+        if (!s) continue;
+        const int i0 = __ffs(s) - 1;
+        float4 bl = L.lo[i0], bh = L.hi[i0];
+        uint32_t c = L.cnt[1u << i0];
+        for (uint32_t m = s & (s - 1); m; m &= m - 1) {
+            const int i = __ffs(m) - 1;
+            const float4 l1 = L.lo[i], h1 = L.hi[i];
+            bl = make_float4(smin(bl.x, l1.x), smin(bl.y, l1.y), smin(bl.z, l1.z), 0.0f);
+            bh = make_float4(smax(bh.x, h1.x), smax(bh.y, h1.y), smax(bh.z, h1.z), 0.0f);
+            c += L.cnt[1u << i];
+        }
+        L.area[s] = sah_area(bl, bh);
+        if (s & (s - 1)) L.cnt[s] = c;
+    }
+    wave_sync();
+    // dynamic programme by subset size; g lanes share a subset's 2^(k-1) - 1 splits and reduce (cost, lowest split index)
+    for (uint32_t k = 2; k <= TREELET; k++) {
+        const uint32_t g = k == 7 ? 64u : (k == 6 ? 8u : (k == 5 ? 2u : 1u));
+        const uint32_t first = c_size_start[k], m = c_size_start[k + 1] - first, P = (1u << (k - 1)) - 1u;
+        const uint32_t mi = (uint32_t)lane / g, j = (uint32_t)lane % g;
+        float best = INFINITY;
+        uint32_t bi = 0xffffffffu, s = 0, delta = 0;
+        if (mi < m) {
+            s = c_subsets[first + mi];
+            delta = s & (s - 1); // the split's part without the lowest leaf is a non-empty subset of delta
+            for (uint32_t i = 1 + j; i <= P; i += g) {
+                const uint32_t q = deposit(i, delta);
+                const float c = L.cost[s ^ q] + L.cost[q];
+                if (bi == 0xffffffffu || c < best) { best = c; bi = i; }
+            }
+        }
+        for (uint32_t o = 1; o < g; o <<= 1) {
+            const float ob = __shfl_xor(best, (int)o);
+            const uint32_t oi = __shfl_xor(bi, (int)o);
+            if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        if (mi < m && j == 0) {
+            L.part[s] = deposit(bi, delta);
+            L.cost[s] = sah_cost(L.area[s], L.cnt[s], a.leaf_max, best);
+        }
+        wave_sync();
+    }
+    const float new_cost = L.cost[127];
+    if (!(new_cost * SAH_ACCEPT < old_cost)) return old_cost;
+    // the new topology breadth-first from the root: inner node h takes id inner[h] and subset sub[h]
+    if (lane == 0) {
+        L.sub[0] = 127;
+        uint32_t tail = 1;
+        for (uint32_t h = 0; h < TREELET - 1; h++) {
+            const uint32_t s = L.sub[h], r = L.part[s], l = s ^ r;
+            uint32_t kl, kr;
+            if (!(l & (l - 1))) kl = L.ref[__ffs(l) - 1];
+            else { kl = L.inner[tail]; L.sub[tail] = l; tail = min(tail + 1, TREELET - 1); }
+            if (!(r & (r - 1))) kr = L.ref[__ffs(r) - 1];
+            else { kr = L.inner[tail]; L.sub[tail] = r; tail = min(tail + 1, TREELET - 1); }
+            L.kids[h] = make_uint2(kl, kr);
+        }
+    }
+    wave_sync();
+    if (lane < (int)TREELET - 1) {
+        const uint32_t id = L.inner[lane], s = L.sub[lane];
+        const uint2 kd = L.kids[lane];
+        const size_t px = parent_slot(a.n, kd.x), py = parent_slot(a.n, kd.y), slots = 2 * (size_t)a.n - 1;
+        a.child[id] = kd;
+        if (px < slots) a.parent[px] = id; // (always: the refs are the treelet's own)
+        if (py < slots) a.parent[py] = id;
+        if (lane > 0) { // the root keeps its box and count; its cost goes back to the climbing lane
+            const int i0 = __ffs(s) - 1;
+            float4 bl = L.lo[i0], bh = L.hi[i0];
+            for (uint32_t m = s & (s - 1); m; m &= m - 1) {
+                const int i = __ffs(m) - 1;
+                const float4 l1 = L.lo[i], h1 = L.hi[i];
+                bl = make_float4(smin(bl.x, l1.x), smin(bl.y, l1.y), smin(bl.z, l1.z), 0.0f);
+                bh = make_float4(smax(bh.x, h1.x), smax(bh.y, h1.y), smax(bh.z, h1.z), 0.0f);
+            }
+            a.inner_box[2 * (size_t)id] = bl;
+            a.inner_box[2 * (size_t)id + 1] = bh;
+            a.count[id] = L.cnt[s];
+            a.cost[id] = L.cost[s];
+        }
+    }
+    return new_cost;
+}
+
+// One restructuring round: boxes_kernel's climb (one lane per leaf, the second lane to reach a node continues; nothing waits) computes
+// every inner node's count and cost, and a node of at least gamma triangles is a treelet root.  The wave takes its lanes' roots one
+// after the other, all 64 lanes in each, and no lane leaves the loop before the wave is done.  A treelet only rewires nodes under its
+// root, which are complete, so the result is the same whatever order the lanes run in.
+__global__ void __launch_bounds__(NT) treelet_kernel(TreeletArgs a)
+{
+    __shared__ TreeletLds s_tl[NT / 64];
+    TreeletLds& L = s_tl[threadIdx.x >> 6];
+    const int lane = threadIdx.x & 63;
+    const int k = (int)(blockIdx.x * NT + threadIdx.x);
+    bool active = k < a.n;
+    uint32_t p = active ? a.parent[(size_t)(a.n - 1) + k] : 0u;
+    while (__ballot(active)) {
+        bool done = false; // this lane completed node p
+        uint32_t cnt = 0;
+        float cost = 0.0f;
+        if (active) {
+            const uint32_t before = __hip_atomic_fetch_add(&a.counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            if (before == 0) active = false; // the sibling's lane finishes this node
+            else {
+                const uint2 c = a.child[p];
+                uint32_t n0, n1;
+                float c0, c1;
+                node_sah(a, c.x, n0, c0);
+                node_sah(a, c.y, n1, c1);
+                float4 lo, hi;
+                box_of(p, a.leaf_box, a.inner_box, lo, hi);
+                cnt = n0 + n1;
+                cost = sah_cost(sah_area(lo, hi), cnt, a.leaf_max, c0 + c1);
+                done = true;
+            }
+        }
+        for (uint64_t roots = __ballot(done && cnt >= a.gamma); roots; roots &= roots - 1) {
+            const int src = __ffsll((unsigned long long)roots) - 1;
+            const float nc = treelet(a, L, __shfl(p, src), __shfl(cost, src), lane);
+            if (lane == src) cost = nc;
+        }
+        if (done) {
+            a.count[p] = cnt;
+            a.cost[p] = cost;
+            if (p == 0) active = false;
+            else p = a.parent[p];
+        }
+    }
+}
+
+// ---- re-layout after restructuring: subtrees are no longer ranges of the sorted order ------------------------------------------
+// Leaf k's tri_geom row: the triangles left of it in a depth-first, left-before-right walk (the counts of the left siblings on its
+// path to the root).  Bounded by n steps; a longer path or an out-of-range parent sets H_ERR.
+__global__ void __launch_bounds__(NT) leaf_pos_kernel(int n, const uint2* child, const uint32_t* parent, const uint32_t* count, uint32_t* pos, uint32_t* hdr)
+{
+    const int k = (int)(blockIdx.x * NT + threadIdx.x);
+    if (k >= n) return;
+    uint32_t ref = (uint32_t)k | REF_LEAF, at = 0;
+    for (int steps = 0; ref != 0; steps++) { // inner node 0 is the root
+        const uint32_t p = parent[parent_slot(n, ref)];
+        if (steps >= n || p >= (uint32_t)(n - 1)) { atomicOr(&hdr[H_ERR], 1u); at = 0; break; }
+        const uint2 c = child[p];
+        if (c.y == ref) at += (c.x & REF_LEAF) ? 1u : (c.x < (uint32_t)(n - 1) ? count[c.x] : 0u);
+        ref = p;
+    }
+    pos[k] = at;
+}
+// (first, count) of every inner node: the row of its leftmost leaf and its triangle count, what is_inner and wide_emit_kernel read
+__global__ void __launch_bounds__(NT) inner_range_kernel(int n, const uint2* child, const uint32_t* count, const uint32_t* pos, uint2* range, uint32_t* hdr)
+{
+    const int i = (int)(blockIdx.x * NT + threadIdx.x);
+    if (i >= n - 1) return;
+    uint32_t r = (uint32_t)i;
+    for (int steps = 0; !(r & REF_LEAF); steps++) {
+        if (steps >= n || r >= (uint32_t)(n - 1)) { atomicOr(&hdr[H_ERR], 2u); r = REF_LEAF; break; }
+        r = child[r].x;
+    }
+    const uint32_t leaf = r & ~REF_LEAF;
+    if (leaf >= (uint32_t)n) atomicOr(&hdr[H_ERR], 2u);
+    range[i] = make_uint2(leaf < (uint32_t)n ? pos[leaf] : 0u, count[i]);
+}
+
 // ---- collapse to BVH4 (frame.cpp::emit_bvh4) ------------------------------------------------------------------------------------
 struct Front { uint32_t ref, pend, depth, pad; };     // a wide node of the current level: its BVH2 node, pending entries above it, its depth
 struct Wide { uint32_t child[4], depth[4], n, pend, pad[2]; }; // children in emit_bvh4's slot order
@@ -365,6 +654,7 @@ struct Wide { uint32_t child[4], depth[4], n, pend, pad[2]; }; // children in em
 struct CollapseArgs {
     const uint2 *child, *range;
     const float4 *leaf_box, *inner_box;
+    const uint32_t* leaf_pos; // tri_geom row of each sorted leaf after a restructuring (null: the sorted order)
     uint32_t leaf_max;
     uint32_t cap; // wide nodes the buffers hold (>= the wide nodes of any tree over these triangles)
     uint32_t* hdr;
@@ -435,7 +725,7 @@ __global__ void __launch_bounds__(NT) wide_emit_kernel(CollapseArgs a, const Wid
                     ref = base + F + j;
                     if (j < a.cap) next[j] = Front{ r, h, w.depth[c], 0u };
                 } else {
-                    ref = (r & REF_LEAF) ? (HJR_LEAF_FLAG | (1u << 27) | (r & ~REF_LEAF)) : (HJR_LEAF_FLAG | (a.range[r].y << 27) | a.range[r].x);
+                    ref = (r & REF_LEAF) ? (HJR_LEAF_FLAG | (1u << 27) | (a.leaf_pos ? a.leaf_pos[r & ~REF_LEAF] : (r & ~REF_LEAF))) : (HJR_LEAF_FLAG | (a.range[r].y << 27) | a.range[r].x);
                     depth = max(depth, w.depth[c]);
                 }
                 q[24 + c] = __uint_as_float(ref);
@@ -475,8 +765,8 @@ namespace hjr {
 void DeviceBvh::release()
 {
     for (DevBuf* x : { &vert, &norm, &uv, &idx, &mat, &prim_off, &xf, &wv, &box, &cent, &keys[0], &keys[1], &vals[0], &vals[1], &hist, &part, &leaf_box,
-                       &inner_box, &inner_child, &inner_range, &parent, &counter, &frontier[0], &frontier[1], &wide, &hdr, &nodes, &tri_geom, &tri_shade,
-                       &tri_inst, &lights })
+                       &inner_box, &inner_child, &inner_range, &parent, &counter, &frontier[0], &frontier[1], &wide, &hdr, &node_count, &node_cost, &leaf_pos,
+                       &nodes, &tri_geom, &tri_shade, &tri_inst, &lights })
         x->release();
     have_scene = false;
     if (ev0) (void)hipEventDestroy(ev0);
@@ -499,8 +789,8 @@ static int scan(uint32_t* in_out, const uint32_t* n_ptr, uint32_t n_const, uint3
     return HJR_OK;
 }
 
-int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, const float* lights,
-                     size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
+                     const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
 {
     const uint32_t n = sc.n_triangles;
     r = DeviceBvhResult();
@@ -529,6 +819,9 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         !b.part.reserve(SCAN_G * 4) || !b.leaf_box.reserve(nn * 32) || !b.inner_box.reserve(nn * 32) || !b.inner_child.reserve(nn * 8) ||
         !b.inner_range.reserve(nn * 8) || !b.parent.reserve(2 * nn * 4) || !b.counter.reserve(nn * 4) || !b.frontier[0].reserve(nn * sizeof(Front)) ||
         !b.frontier[1].reserve(nn * sizeof(Front)) || !b.wide.reserve(nn * (sizeof(Wide) + 4)))
+        return fail_alloc();
+    const bool restructure = opt_rounds > 0 && n >= 2;
+    if (restructure && (!b.node_count.reserve(nn * 4) || !b.node_cost.reserve(nn * 4) || !b.leaf_pos.reserve(nn * 4)))
         return fail_alloc();
     uint32_t* hdr = (uint32_t*)b.hdr.p;
     DCHK(hipEventRecord(b.ev0, st));
@@ -565,8 +858,9 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], (const uint32_t*)vals[s], n, 8 * pass,
                            (const uint32_t*)b.hist.p, nb, keys[s ^ 1], vals[s ^ 1]);
     }
-    hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals[0], (const float*)b.wv.p, (const uint32_t*)b.mat.p,
-                       (const float*)b.box.p, (float*)b.tri_geom.p, (float*)b.leaf_box.p);
+    // with a restructuring, tri_geom waits for the leaves' new positions
+    hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals[0], (const uint32_t*)nullptr, (const float*)b.wv.p,
+                       (const uint32_t*)b.mat.p, (const float*)b.box.p, restructure ? (float*)nullptr : (float*)b.tri_geom.p, (float*)b.leaf_box.p);
     if (n >= 2) {
         hipLaunchKernelGGL(karras_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint64_t*)keys[0], (uint2*)b.inner_child.p,
                            (uint2*)b.inner_range.p, (uint32_t*)b.parent.p);
@@ -574,10 +868,29 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)b.inner_child.p, (const uint32_t*)b.parent.p,
                            (uint32_t*)b.counter.p, (const float4*)b.leaf_box.p, (float4*)b.inner_box.p);
     }
+    if (restructure) { // option "device_bvh_opt"
+        TreeletArgs ta;
+        ta.n = (int)n; ta.leaf_max = leaf_max;
+        ta.child = (uint2*)b.inner_child.p; ta.parent = (uint32_t*)b.parent.p; ta.counter = (uint32_t*)b.counter.p;
+        ta.count = (uint32_t*)b.node_count.p; ta.cost = (float*)b.node_cost.p;
+        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p;
+        for (uint32_t round = 0; round < opt_rounds; round++) {
+            ta.gamma = TREELET << round; // the paper's schedule: the treelet size, doubled every round
+            DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+            hipLaunchKernelGGL(treelet_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, ta);
+        }
+        hipLaunchKernelGGL(leaf_pos_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)b.inner_child.p, (const uint32_t*)b.parent.p,
+                           (const uint32_t*)b.node_count.p, (uint32_t*)b.leaf_pos.p, hdr);
+        hipLaunchKernelGGL(inner_range_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint2*)b.inner_child.p,
+                           (const uint32_t*)b.node_count.p, (const uint32_t*)b.leaf_pos.p, (uint2*)b.inner_range.p, hdr);
+        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals[0], (const uint32_t*)b.leaf_pos.p,
+                           (const float*)b.wv.p, (const uint32_t*)b.mat.p, (const float*)b.box.p, (float*)b.tri_geom.p, (float*)nullptr);
+    }
     DCHK(hipGetLastError());
     CollapseArgs ca;
     ca.child = (const uint2*)b.inner_child.p; ca.range = (const uint2*)b.inner_range.p;
     ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
+    ca.leaf_pos = restructure ? (const uint32_t*)b.leaf_pos.p : nullptr;
     ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
     Front* fr[2] = { (Front*)b.frontier[0].p, (Front*)b.frontier[1].p };
     Wide* wide = (Wide*)b.wide.p;
@@ -605,6 +918,7 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
     const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
     if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
+    if (h[H_ERR]) { err = "device BVH: the restructured tree failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
     r.n_nodes = h[H_BASE];
     r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
     r.depth = h[H_DEPTH];

@@ -163,7 +163,8 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
         set_error("hjr_set_transforms: \"device_bvh\" builds the BVH4 memory layout only; it cannot be combined with \"bvh_width\" 2 or \"lds_bvh\" 1");
         return HJR_ERR_ARG;
     }
-    const uint32_t build_tag = (bo.allow_lds ? 1u : 0u) | (bo.prefer_stack16 ? 2u : 0u) | ((uint32_t)(bo.bvh_width + 1) << 2) | ((uint32_t)(bo.leaf_max + 1) << 6) | ((uint32_t)(bo.refine + 1) << 10) | (device ? 1u << 16 : 0u);
+    const uint32_t build_tag = (bo.allow_lds ? 1u : 0u) | (bo.prefer_stack16 ? 2u : 0u) | ((uint32_t)(bo.bvh_width + 1) << 2) | ((uint32_t)(bo.leaf_max + 1) << 6) | ((uint32_t)(bo.refine + 1) << 10) | (device ? 1u << 16 : 0u) |
+                               (device ? (uint32_t)c->opt.get(hjr::OPT_DEVICE_BVH_OPT, 0) << 17 : 0u);
     c->pending_valid = false;
     c->pending_same = false;
     // unchanged instance transforms (static geometry, e.g. a camera-only animation): the world-space arrays and the BVH of the
@@ -197,11 +198,12 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
 static int commit_device(hjr_ctx* c)
 {
     const int leaf_max = c->opt.get(hjr::OPT_LEAF_MAX, (int)HJR_LEAF_DEFAULT);
+    const int opt_rounds = c->opt.get(hjr::OPT_DEVICE_BVH_OPT, 0); // option "device_bvh_opt": treelet-restructuring rounds
     hjr::DeviceBvhResult r;
     std::string err;
     hjr::FrameData& f = c->pending;
     const int rc = hjr::device_bvh_build(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), (uint32_t)(c->pending_m.size() / 12), (uint32_t)leaf_max,
-                                         f.lights.data(), f.lights.size(), c->stream, r, err);
+                                         (uint32_t)opt_rounds, f.lights.data(), f.lights.size(), c->stream, r, err);
     if (rc != HJR_OK) { set_error("hjr_set_transforms: " + err); return rc; }
     c->d_nodes.swap(c->dbvh.nodes); c->d_tri_geom.swap(c->dbvh.tri_geom); c->d_tri_shade.swap(c->dbvh.tri_shade);
     c->d_tri_inst.swap(c->dbvh.tri_inst); c->d_lights.swap(c->dbvh.lights);

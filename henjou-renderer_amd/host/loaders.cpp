@@ -132,6 +132,12 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             o.fast_math = flag("fast_math") ? 1 : 0;
             o.force_rebuild = flag("force_rebuild") ? 1 : 0;
             o.device_bvh = flag("device_bvh") ? 1 : 0; // the frame data built on the device (option "device_bvh")
+            // device_bvh_opt: treelet-restructuring rounds of the device build (option "device_bvh_opt")
+            if (const Json* v = h->find("device_bvh_opt")) {
+                const double r = v->is_number() ? v->as_number() : -1.0;
+                if (!(r >= 0 && r <= 3) || r != (double)(uint32_t)r) throw JsonError("Henjou_HIP.device_bvh_opt must be an integer in [0, 3]");
+                o.device_bvh_opt = (int32_t)r;
+            }
         }
     } catch (std::exception& e) { // :222-225
         err = std::string("Caught exception: ") + e.what();
