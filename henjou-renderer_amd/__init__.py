@@ -78,7 +78,7 @@ class RenderOption(_Sized):
                 ("scene_sky_default", C.c_float * 3), ("use_date", C.c_int32), ("save_renderOption", C.c_int32),
                 ("LUT_path", C.c_char * 512), ("seed", C.c_uint32), ("integrator", C.c_int32),
                 ("devices", C.c_uint32), ("tile", C.c_uint32), ("serial_io", C.c_int32), ("fast_math", C.c_int32), ("force_rebuild", C.c_int32),
-                ("device_bvh", C.c_int32), ("device_bvh_opt", C.c_int32)]
+                ("device_bvh", C.c_int32), ("device_bvh_opt", C.c_int32), ("passes", C.c_uint32)]
 
 
 class Camera(C.Structure):
@@ -95,6 +95,12 @@ class Params(_Sized):
                 ("seed", C.c_uint32), ("integrator", C.c_uint32), ("camera", Camera), ("sky", C.c_float * 3),
                 ("ibl_intensity", C.c_float), ("rank", C.c_uint32), ("world_size", C.c_uint32),
                 ("flags", C.c_uint32)]
+
+
+class ParamsV2(Params):
+    """hjr_params with the fields appended after `Params` (the layout up to flags): the sample pass of a progressive frame
+    (include/henjou_hip.h; sample_end 0 = the whole frame).  Both are valid callers under the sized-struct rule; make_params returns this one."""
+    _fields_ = [("sample_begin", C.c_uint32), ("sample_end", C.c_uint32)]
 
 
 class Stats(_Sized):
@@ -180,6 +186,8 @@ def lib():
             fn.argtypes = args
         L.hjr_owned_tiles.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.hjr_owned_tiles.restype = C.c_uint32
+        L.hjr_sample_granule.argtypes = [C.c_uint32]
+        L.hjr_sample_granule.restype = C.c_uint32
         L.hjr_scene_free.argtypes = [C.c_void_p]
         L.hjr_scene_free.restype = None
         L.hjr_destroy.argtypes = [C.c_void_p]
@@ -401,6 +409,18 @@ class Device:
                                 albedo.ctypes.data if want_aovs else None, normal.ctypes.data if want_aovs else None), "hjr_render")
         return color, albedo, normal
 
+    def render_progressive(self, params, passes, want_aovs=True):
+        """Renders the frame of `params` in `passes` sample passes (hjr_params.sample_begin / sample_end, split by pass_bounds) and yields
+        (sample_end, color, albedo, normal) after each: the running mean over samples [0, sample_end).  The last one is the one-shot frame,
+        bit for bit.  `params` itself is not modified."""
+        for begin, end in pass_bounds(params.spp, passes):
+            p = ParamsV2()
+            C.memmove(C.addressof(p), C.addressof(params), min(C.sizeof(params), C.sizeof(p)))
+            p.struct_size = C.sizeof(p)
+            p.sample_begin, p.sample_end = begin, end
+            color, albedo, normal = self.render(p, want_aovs)
+            yield end, color, albedo, normal
+
     def render_device(self, params, d_color, d_albedo=None, d_normal=None, stream=None):
         """Asynchronous render into device pointers (ints, e.g. torch tensor .data_ptr()) on a hipStream_t (int)."""
         _check(lib().hjr_render_device(self._h, C.byref(params), C.c_void_p(d_color),
@@ -461,8 +481,8 @@ class Device:
 
 
 def make_params(width, height, spp, camera, frame=1, seed=1, integrator=INTEGRATOR_NEE, sky=(0.8, 0.8, 0.8),
-                ibl_intensity=1.0, rank=0, world_size=1, flags=0):
-    p = Params()
+                ibl_intensity=1.0, rank=0, world_size=1, flags=0, sample_begin=0, sample_end=0):
+    p = ParamsV2()
     p.width, p.height, p.spp, p.frame, p.seed, p.integrator = width, height, spp, frame, seed, integrator
     if isinstance(camera, Camera):
         p.camera = camera
@@ -475,6 +495,7 @@ def make_params(width, height, spp, camera, frame=1, seed=1, integrator=INTEGRAT
     p.sky = (C.c_float * 3)(*sky)
     p.ibl_intensity = ibl_intensity
     p.rank, p.world_size, p.flags = rank, world_size, flags
+    p.sample_begin, p.sample_end = sample_begin, sample_end
     return p
 
 
@@ -496,6 +517,27 @@ def exchange_framebuffer(fb, dst=0):
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dist.reduce(fb, dst=dst, op=dist.ReduceOp.SUM)
     return fb
+
+
+def sample_granule(spp):
+    """hjr_sample_granule: the boundary granule of a frame's sample passes (one work-item chunk; spp itself for a single-chunk frame)."""
+    return int(lib().hjr_sample_granule(spp))
+
+
+def pass_bounds(spp, passes, granule=None):
+    """The sample passes [(begin, end), ...] of a frame of `spp` samples split into `passes` (1..64): pass k ends at k * spp // passes rounded
+    down to the granule (sample_granule(spp) unless given), the last at spp; passes that come out empty are dropped.  The same split as
+    "Henjou_HIP": {"passes": N} in hjr_render_file / henjou_cli."""
+    if not 1 <= passes <= 64:
+        raise ValueError("passes must be in [1, 64]")
+    g = sample_granule(spp) if granule is None else granule
+    ends = []
+    for k in range(1, passes):
+        e = (k * spp // passes) // g * g if g else 0
+        if e > (ends[-1] if ends else 0):
+            ends.append(e)
+    ends.append(spp)
+    return list(zip([0] + ends[:-1], ends))
 
 
 def owned_tiles(width, height, rank, world_size):

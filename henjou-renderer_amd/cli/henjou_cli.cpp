@@ -110,7 +110,18 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
         p.ibl_intensity = opt.IBL_intensity;
         p.rank = (uint32_t)rank; p.world_size = (uint32_t)world; p.flags = HJR_FLAG_PACKED | (opt.fast_math ? HJR_FLAG_FAST_MATH : 0u);
         const auto t0 = std::chrono::steady_clock::now();
-        HJRX(hjr_render_device(ctx, &p, d_packed, nullptr, nullptr, st));
+        // "passes": the frame in sample passes split as hjr_render_file splits it (k * spp / passes rounded down to the granule, empty
+        // passes dropped); the last pass leaves the frame's tiles in d_packed
+        const uint32_t n_pass = opt.passes ? opt.passes : 1u, g = hjr_sample_granule(p.spp);
+        uint32_t n_done = 0;
+        for (uint32_t k = 1, begin = 0; k <= n_pass; k++) {
+            const uint32_t end = k == n_pass ? p.spp : (g ? (uint32_t)((uint64_t)k * p.spp / n_pass) / g * g : 0u);
+            if (end <= begin) continue;
+            if (n_pass > 1) { p.sample_begin = begin; p.sample_end = end; }
+            HJRX(hjr_render_device(ctx, &p, d_packed, nullptr, nullptr, st));
+            begin = end;
+            n_done++;
+        }
         NCCLX(ncclGather(d_packed, d_all, block * 4, ncclFloat, 0, comm, st)); // the one data-path collective of a frame
         if (rank == 0) {
             for (int r = 0; r < world; r++) HJRX(hjr_unpack_tiles_device(ctx, d_all + (size_t)r * block * 4, W, H, (uint32_t)r, (uint32_t)world, d_frame, st));
@@ -121,7 +132,8 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
         hjr_stats s;
         HJR_INIT(s);
         if (hjr_get_stats(ctx, &s) == HJR_OK)
-            fprintf(stderr, "[henjou %d/%d] frame %u: kernel %.3f ms, render + gather + assemble %.3f ms\n", rank, world, f, s.last_kernel_ms, ms);
+            fprintf(stderr, "[henjou %d/%d] frame %u: kernel %.3f ms, render + gather + assemble %.3f ms%s\n", rank, world, f, s.last_kernel_ms, ms,
+                    n_done > 1 ? (", " + std::to_string(n_done) + " sample passes").c_str() : "");
         if (rank == 0) {
             std::vector<uint8_t> rgba8((size_t)W * H * 4);
             HJRX(hjr_float4_to_srgb8(frame.data(), rgba8.data(), W * H));

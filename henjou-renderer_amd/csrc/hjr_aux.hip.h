@@ -135,6 +135,44 @@ __global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P)
     }
 }
 
+// A sample pass (hjr_params.sample_begin / sample_end) instead of hjr_finalize_kernel: a = the running sum of the frame's
+// earlier passes (+0.0f on its first pass), then this pass's chunk sums added in chunk order with the finalize kernel's expressions; a goes
+// back unless this is the frame's last pass, and the AOV gets a * (1 / sample_end).  Chunk by chunk this is the finalize kernel's summation,
+// so the last pass writes the one-shot frame's bits.  Same streaming shape: one lane per owned pixel, coalesced float4 loads and stores.
+__global__ void __launch_bounds__(256) hjr_accumulate_kernel(const KParams P)
+{
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    const float inv_end = 1.0f / (float)P.sample_end;
+    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
+        uint32_t tx, ty;
+        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
+        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+        if (x >= P.width || y >= P.height) continue;
+        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
+        if (P.run_load) {
+            a = P.run_color[sl];
+            if (P.aov_albedo) b = P.run_albedo[sl];
+            if (P.aov_normal) c = P.run_normal[sl];
+        }
+        for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
+            const float4 v = P.part_color[(size_t)k * n_slots + sl];
+            a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
+            if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
+            if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
+        }
+        if (P.run_store) {
+            P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
+            if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
+            if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
+        }
+        P.aov_color[pix] = make_float4(a.x * inv_end, a.y * inv_end, a.z * inv_end, 1.0f);
+        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv_end, b.y * inv_end, b.z * inv_end, 1.0f);
+        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv_end, c.y * inv_end, c.z * inv_end, 1.0f);
+    }
+}
+
 // ---- tile pack / unpack: the multi-GPU exchange moves only owned tiles ([owned tile][64] float4)
 __global__ void __launch_bounds__(256) hjr_pack_tiles_kernel(const float4* frame, float4* packed, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_owned, uint32_t rank, uint32_t world)
 {

@@ -135,6 +135,7 @@ extern "C" int hjr_upload_scene(hjr_ctx* c, const hjr_scene_view* v)
         }
     }
     HIPCHK(hipStreamSynchronize(c->stream));
+    c->frame_gen++;
     c->have_scene = true;
     c->have_frame = false;
     c->dbvh.have_scene = false; // the device builder uploads the new scene at its next build
@@ -222,6 +223,7 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
         return HJR_OK;
     }
     HIPCHK(hipSetDevice(c->device));
+    c->frame_gen++; // the frame data is replaced (a progressive frame cannot continue on it, even if the build below fails)
     if (c->pending_device) {
         if (const int rc = commit_device(c)) return rc;
         std::swap(c->frame, c->pending);
@@ -285,6 +287,7 @@ extern "C" int hjr_set_lut(hjr_ctx* c, const uint8_t* rgba, int w, int h)
 {
     if (!c) { set_error("hjr_set_lut: null context"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
+    c->frame_gen++;
     if (!rgba || w <= 0 || h <= 0) { c->lut_w = c->lut_h = 0; return HJR_OK; }
     if (!c->d_lut.upload(rgba, (size_t)w * (size_t)h * 4, c->stream)) { set_error("hjr_set_lut: upload failed"); return HJR_ERR_DEVICE; }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -296,6 +299,7 @@ extern "C" int hjr_set_sky(hjr_ctx* c, const float* rgba, int w, int h)
 {
     if (!c) { set_error("hjr_set_sky: null context"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
+    c->frame_gen++;
     if (!rgba || w <= 0 || h <= 0) { c->sky_w = c->sky_h = 0; return HJR_OK; }
     if (!c->d_sky.upload(rgba, (size_t)w * (size_t)h * 16, c->stream)) { set_error("hjr_set_sky: upload failed"); return HJR_ERR_DEVICE; }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -412,15 +416,77 @@ static LaunchPlan plan_launch(const hjr_ctx* c, const KParams& kp, uint64_t n_it
     return pl;
 }
 
+// The samples one render call covers: the whole frame, or a sample pass of a progressive frame (include/henjou_hip.h)
+struct PassRange {
+    bool pass = false;         // a sample pass (else the whole frame, the one-shot launch sequence)
+    uint32_t begin = 0, end = 0;
+    uint32_t aovs = 0;         // AOVs requested: bit 0 colour, 1 albedo, 2 normal
+};
+static const uint32_t PASS_FLAGS = HJR_FLAG_PACKED | HJR_FLAG_ZERO_UNOWNED | HJR_FLAG_FAST_MATH; // the flags that change pixels
+
+// The pass rules, checked before a call enqueues or writes anything: HJR_ERR_ARG for a bad range, HJR_ERR_STATE for a pass that does not
+// continue the context's progressive frame.  Changes nothing; end_pass records a launch once it is enqueued.
+static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, PassRange& r)
+{
+    r = PassRange();
+    r.aovs = aovs;
+    if (p->sample_end == 0) {
+        if (p->sample_begin != 0) { set_error("hjr_render: sample_begin without sample_end (sample_end 0 renders the whole frame)"); return HJR_ERR_ARG; }
+        return HJR_OK;
+    }
+    if (p->spp == 0) { set_error("hjr_render: width, height and spp must be positive"); return HJR_ERR_ARG; }
+    if (p->sample_begin == 0 && p->sample_end == p->spp) return HJR_OK; // the whole frame, through the same path
+    const uint32_t g = hjr_chunk_spp(p->spp);
+    if (p->sample_begin >= p->sample_end || p->sample_end > p->spp) {
+        set_error("hjr_render: sample pass [" + std::to_string(p->sample_begin) + ", " + std::to_string(p->sample_end) + ") is not a range inside [0, spp = " + std::to_string(p->spp) + "]");
+        return HJR_ERR_ARG;
+    }
+    if (hjr_n_chunks(p->spp) == 1) { set_error("hjr_render: a frame of " + std::to_string(p->spp) + " spp is a single chunk: only the whole range [0, spp) is a pass"); return HJR_ERR_ARG; }
+    if (p->sample_begin % g || (p->sample_end % g && p->sample_end != p->spp)) {
+        set_error("hjr_render: sample pass boundaries must be multiples of hjr_sample_granule(" + std::to_string(p->spp) + ") = " + std::to_string(g) + " or equal spp");
+        return HJR_ERR_ARG;
+    }
+    r.pass = true; r.begin = p->sample_begin; r.end = p->sample_end;
+    if (r.begin == 0) return HJR_OK; // starts a progressive frame (replacing an unfinished one)
+    const hjr_ctx::PassSession& s = c->pass;
+    std::string bad;
+    if (!s.active) bad = "no progressive frame is open (its first pass starts at sample 0)";
+    else if (r.begin != s.next) bad = "sample_begin " + std::to_string(r.begin) + " does not continue the previous pass, which ended at " + std::to_string(s.next);
+    else if (p->width != s.p.width || p->height != s.p.height) bad = "width / height differ from the frame's first pass";
+    else if (p->spp != s.p.spp) bad = "spp differs from the frame's first pass";
+    else if (p->frame != s.p.frame) bad = "frame differs from the frame's first pass";
+    else if (p->seed != s.p.seed) bad = "seed differs from the frame's first pass";
+    else if (p->integrator != s.p.integrator) bad = "integrator differs from the frame's first pass";
+    else if (memcmp(&p->camera, &s.p.camera, sizeof(hjr_camera)) != 0) bad = "camera differs from the frame's first pass";
+    else if (memcmp(p->sky, s.p.sky, sizeof(p->sky)) != 0 || memcmp(&p->ibl_intensity, &s.p.ibl_intensity, sizeof(float)) != 0) bad = "sky / ibl_intensity differ from the frame's first pass";
+    else if (p->rank != s.p.rank || p->world_size != s.p.world_size) bad = "rank / world_size differ from the frame's first pass";
+    else if ((p->flags & PASS_FLAGS) != (s.p.flags & PASS_FLAGS)) bad = "flags PACKED / ZERO_UNOWNED / FAST_MATH differ from the frame's first pass";
+    else if (aovs != s.aovs) bad = "the set of AOVs differs from the frame's first pass";
+    else if (c->frame_gen != s.gen) bad = "the frame data changed since the frame's first pass (scene, transforms, LUT or sky)";
+    if (!bad.empty()) { set_error("hjr_render: sample pass [" + std::to_string(r.begin) + ", " + std::to_string(r.end) + ") refused: " + bad); return HJR_ERR_STATE; }
+    return HJR_OK;
+}
+// after a launch was enqueued: the progressive frame goes on to r.end, or ends (last pass, or a whole-frame render)
+static void end_pass(hjr_ctx* c, const hjr_params* p, const PassRange& r)
+{
+    hjr_ctx::PassSession& s = c->pass;
+    if (!r.pass || r.end == p->spp) { s.active = false; return; }
+    if (r.begin == 0) { s.p = *p; s.aovs = r.aovs; s.gen = c->frame_gen; }
+    s.active = true;
+    s.next = r.end;
+}
+
 // this rank's share of a frame
 struct FrameGeom {
     uint32_t world, tiles_x, chunk_spp, n_chunks;
+    uint32_t chunk0, pass_chunks; // the chunks this launch renders: [chunk0, chunk0 + pass_chunks) (all n_chunks for a whole frame)
     uint64_t owned, n_items;
     int lds_mode; // LaunchPlan::lds_mode of the frame data
+    PassRange pr;
 };
 
 // argument checks and tile geometry
-static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_color, FrameGeom& g)
+static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_color, const PassRange& pr, FrameGeom& g)
 {
     if (!c || !p || !d_color) { set_error("hjr_render: null argument"); return HJR_ERR_ARG; }
     if (!c->have_scene || !c->have_frame) { set_error("hjr_render: upload a scene and set transforms first"); return HJR_ERR_STATE; }
@@ -433,7 +499,10 @@ static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_c
     const uint64_t n_tiles = (uint64_t)g.tiles_x * ((p->height + HJR_TILE - 1) / HJR_TILE);
     g.owned = (n_tiles > p->rank) ? (n_tiles - p->rank + g.world - 1) / g.world : 0;
     g.chunk_spp = hjr_chunk_spp(p->spp); g.n_chunks = hjr_n_chunks(p->spp);
-    g.n_items = g.owned * g.n_chunks * 64;
+    g.pr = pr;
+    g.chunk0 = pr.pass ? pr.begin / g.chunk_spp : 0u;
+    g.pass_chunks = pr.pass ? (pr.end - pr.begin + g.chunk_spp - 1) / g.chunk_spp : g.n_chunks;
+    g.n_items = g.owned * g.pass_chunks * 64;
     // the 32-bit queue head overshoots n_items by at most 64 per wave of the persistent grid (every wave stops fetching once it
     // has seen the queue dry, hjr_kernel.hip.h); 2^24 covers 262 144 waves, far more than any resident grid
     if (g.n_items >= 0xffffffffull - (1ull << 24)) { set_error("hjr_render: image too large (more than 2^32 - 2^24 work items per launch)"); return HJR_ERR_ARG; }
@@ -462,17 +531,34 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
     memset(&kp, 0, sizeof(kp));
     kp.n_owned_tiles = (uint32_t)g.owned;
     if (g.n_chunks > 1) {
-        // chunk sums of THIS rank's tiles only: [chunk][owned tile][64] float4 (1/world of the frame; allocated once per size)
-        const size_t part_bytes = (size_t)g.owned * 64u * 16u * g.n_chunks;
+        // chunk sums of THIS rank's tiles and this launch's chunks only: [chunk - chunk0][owned tile][64] float4 (1/world of the frame;
+        // a sample pass needs its own chunks only; allocated once per size)
+        const size_t part_bytes = (size_t)g.owned * 64u * 16u * g.pass_chunks;
         DevBuf* pb[3] = { &c->d_part_color, &c->d_part_albedo, &c->d_part_normal };
+        DevBuf* rb[3] = { &c->d_run_color, &c->d_run_albedo, &c->d_run_normal };
         void* want[3] = { d_color, d_albedo, d_normal };
-        for (int i = 0; i < 3; i++)
+        for (int i = 0; i < 3; i++) {
             if (want[i] && !pb[i]->reserve(part_bytes)) { set_error("hjr_render: chunk-sum buffer allocation failed"); return HJR_ERR_DEVICE; }
-        kp.part_color = (float4*)c->d_part_color.p;
-        kp.part_albedo = d_albedo ? (float4*)c->d_part_albedo.p : nullptr;
-        kp.part_normal = d_normal ? (float4*)c->d_part_normal.p : nullptr;
+            // running sums of a progressive frame, [owned tile][64] float4; the same size for every pass of one frame, so kept across them
+            if (want[i] && g.pr.pass && !rb[i]->reserve((size_t)g.owned * 64u * 16u)) { set_error("hjr_render: running-sum buffer allocation failed"); return HJR_ERR_DEVICE; }
+        }
+        // the render kernels address chunk k at k * owned * 64: a sample pass's buffers start at its first chunk, so the pointers are
+        // moved back by chunk0 chunks (no chunk below chunk0 is stored or read; 0 for a one-shot frame)
+        const size_t back = (size_t)g.chunk0 * g.owned * 64u;
+        kp.part_color = (float4*)c->d_part_color.p - back;
+        kp.part_albedo = d_albedo ? (float4*)c->d_part_albedo.p - back : nullptr;
+        kp.part_normal = d_normal ? (float4*)c->d_part_normal.p - back : nullptr;
+        if (g.pr.pass) {
+            kp.run_color = (float4*)c->d_run_color.p;
+            kp.run_albedo = d_albedo ? (float4*)c->d_run_albedo.p : nullptr;
+            kp.run_normal = d_normal ? (float4*)c->d_run_normal.p : nullptr;
+            kp.run_load = g.pr.begin > 0 ? 1u : 0u;
+            kp.run_store = g.pr.end < p->spp ? 1u : 0u;
+            kp.sample_end = g.pr.end;
+        }
     }
     kp.chunk_spp = g.chunk_spp; kp.n_chunks = g.n_chunks;
+    kp.chunk0 = g.chunk0; kp.pass_chunks = g.pass_chunks;
     kp.nodes = (const float4*)c->d_nodes.p;
     kp.tri_geom = (const float4*)c->d_tri_geom.p;
     kp.tri_shade = (const float4*)c->d_tri_shade.p;
@@ -540,7 +626,11 @@ static int order_tiles(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KPar
         c->cost_tag = tag;
         kp.tile_cost = (uint32_t*)c->d_tile_cost.p;
         kp.cost_hist = (uint32_t*)(work + WorkArea::COST_HIST);
-        kp.cost_div = 64u * p->spp;
+        // the costs were measured by the previous launch of this configuration: normalised by ITS samples (a whole frame, or the
+        // previous sample pass of a progressive frame, whose later passes thus reuse the costs measured by the earlier ones)
+        const uint32_t launch_samples = g.pr.pass ? g.pr.end - g.pr.begin : p->spp;
+        kp.cost_div = 64u * (have_cost && c->cost_samples ? c->cost_samples : launch_samples);
+        c->cost_samples = launch_samples;
     }
     const unsigned tg = (unsigned)((g.owned + 255) / 256);
     if (have_cost) {
@@ -586,23 +676,26 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
     return HJR_OK;
 }
 
-// sums of the sample chunks -> pixel means
+// sums of the sample chunks -> pixel means (a sample pass: -> running sums and running means)
 static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, const KParams& kp, hipStream_t st)
 {
     if (g.n_chunks <= 1) return HJR_OK;
     const size_t n_slots = (size_t)g.owned * 64u;
+    if (n_slots == 0) return HJR_OK;
     unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
-    hipLaunchKernelGGL(hjr_finalize_kernel, dim3(fb), dim3(256), 0, st, kp);
+    if (g.pr.pass) hipLaunchKernelGGL(hjr_accumulate_kernel, dim3(fb), dim3(256), 0, st, kp);
+    else hipLaunchKernelGGL(hjr_finalize_kernel, dim3(fb), dim3(256), 0, st, kp);
     HIPCHK(hipGetLastError());
     return HJR_OK;
 }
 
-static int render_impl(hjr_ctx* c, const hjr_params* p, void* d_color, void* d_albedo, void* d_normal, hipStream_t st)
+// pr: check_pass of this call, made before the caller enqueued anything
+static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, hipStream_t st)
 {
     FrameGeom g;
     KParams kp;
     int rc;
-    if ((rc = frame_geometry(c, p, d_color, g)) != HJR_OK) return rc;
+    if ((rc = frame_geometry(c, p, d_color, pr, g)) != HJR_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
     if ((rc = bind_params(c, p, g, d_color, d_albedo, d_normal, st, kp)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev0, st));
@@ -611,6 +704,9 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, void* d_color, void* d_a
     if ((rc = finalize_chunks(c, g, kp, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
+    if (pr.pass && c->opt.get(hjr::OPT_VERBOSE, 0))
+        fprintf(stderr, "[hjr] frame %u: sample pass [%u, %u) of %u spp, chunks %u..%u of %u\n", p->frame, pr.begin, pr.end, p->spp, g.chunk0, g.chunk0 + g.pass_chunks - 1, g.n_chunks);
+    end_pass(c, p, pr);
     return HJR_OK;
 }
 
@@ -688,7 +784,9 @@ extern "C" int hjr_render_device(hjr_ctx* c, const hjr_params* p_user, void* d_c
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_device")) { if (!c) set_error("hjr_render_device: null context"); return HJR_ERR_ARG; }
     const hjr_params* p = &params;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    return render_impl(c, p, d_color, d_albedo, d_normal, st);
+    PassRange pr;
+    if (const int rc = check_pass(c, p, (d_color ? 1u : 0u) | (d_albedo ? 2u : 0u) | (d_normal ? 4u : 0u), pr)) return rc;
+    return render_impl(c, p, pr, d_color, d_albedo, d_normal, st);
 }
 
 // OptixDenoiserManager::denoise() replacement (csrc/hjr_denoise.hip.h), device buffers, asynchronous on `hip_stream`
@@ -762,13 +860,15 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     const size_t in_bytes = (size_t)p->width * p->height * 16, out_bytes = (size_t)out_w * out_h * 16;
     if (in_bytes == 0 || out_bytes == 0) { set_error("hjr_render_denoised: empty image"); return HJR_ERR_ARG; }
     const bool guides = render_mode != HJR_MODE_DEFAULT;
+    PassRange pr; // a sample pass: the running mean is filtered (a denoised preview; the last pass gives the one-shot call's image)
+    if (const int rc = check_pass(c, p, guides ? 7u : 1u, pr)) return rc;
     if (!c->d_color.reserve(in_bytes) || (guides && (!c->d_albedo.reserve(in_bytes) || !c->d_normal.reserve(in_bytes))) || !c->d_dn_out.reserve(out_bytes)) {
         set_error("hjr_render_denoised: allocation failed");
         return HJR_ERR_DEVICE;
     }
     HIPCHK(hipMemsetAsync(c->d_color.p, 0, in_bytes, c->stream));
     if (guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
-    int rc = render_impl(c, p, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, c->stream);
+    int rc = render_impl(c, p, pr, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
     rc = hjr_denoise_device(c, render_mode, p->width, p->height, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr,
                             c->d_dn_out.p, out_w, out_h, c->stream);
@@ -864,7 +964,9 @@ extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, fl
     const bool packed_out = (p->flags & HJR_FLAG_PACKED) != 0;
     if (p->rank >= (p->world_size ? p->world_size : 1u)) { set_error("hjr_render: rank >= world_size"); return HJR_ERR_ARG; }
     const size_t bytes = packed_out ? (size_t)hjr_owned_tiles(p->width, p->height, p->rank, p->world_size ? p->world_size : 1u) * 64u * 16u : (size_t)p->width * p->height * 16;
-    if (bytes == 0) return HJR_OK; // a rank without tiles
+    PassRange pr;
+    if (const int rc = check_pass(c, p, 1u | (albedo ? 2u : 0u) | (normal ? 4u : 0u), pr)) return rc;
+    if (bytes == 0) { end_pass(c, p, pr); return HJR_OK; } // a rank without tiles
     DevBuf* bufs[3] = { &c->d_color, &c->d_albedo, &c->d_normal };
     float* host[3] = { color, albedo, normal };
     for (int i = 0; i < 3; i++) {
@@ -872,7 +974,7 @@ extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, fl
         if (!bufs[i]->reserve(bytes)) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
         if (!packed_out) HIPCHK(hipMemsetAsync(bufs[i]->p, 0, bytes, c->stream));
     }
-    int rc = render_impl(c, p, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr, c->stream);
+    int rc = render_impl(c, p, pr, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
     for (int i = 0; i < 3; i++)
         if (host[i]) HIPCHK(hipMemcpyAsync(host[i], bufs[i]->p, bytes, hipMemcpyDeviceToHost, c->stream));

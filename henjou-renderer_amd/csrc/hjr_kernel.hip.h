@@ -352,6 +352,7 @@ template <bool AOVS> HD void write_out(const KParams& P, LaneCtx& c)
         }
     } else { // chunk sum -> HBM; hjr_finalize_kernel adds the chunks of a pixel in chunk order.  The buffers hold this rank's
              // tiles only: slot = ((chunk * owned tiles) + owned tile index) * 64 + pixel in tile
+        // (a sample pass, DESIGN.md §4.4, holds the sums of its own chunks only: the host offsets part_* by -chunk0 chunks)
         const uint32_t otile = hjr_tile_id(HJR_PX(c) / HJR_TILE, HJR_PY(c) / HJR_TILE, tiles_x) / world;
         const size_t slot = ((size_t)HJR_CHUNK(c) * HJR_COLD(n_owned_tiles) + otile) * 64u + ((HJR_PY(c) & 7u) * 8u + (HJR_PX(c) & 7u));
         float4* const part_color = HJR_COLD(part_color);
@@ -366,11 +367,13 @@ template <bool AOVS> HD void write_out(const KParams& P, LaneCtx& c)
     c.write_pending = false;
 }
 
-// decode of the 64 aligned items [base, base + 64) of the megakernel's queue: item q = ((owned tile * n_chunks) + chunk) * 64 + pixel-in-tile
-HD uint32_t decode_range(uint32_t base, uint32_t n_chunks, uint32_t tiles_x, uint32_t world, uint32_t rank, const uint32_t* tile_order)
+// decode of the 64 aligned items [base, base + 64) of the megakernel's queue: item q = ((owned tile * pass_chunks) + chunk - chunk0) * 64 +
+// pixel-in-tile.  A launch renders the chunks [chunk0, chunk0 + pass_chunks) of the frame (all of them unless it is a sample pass); the
+// item word keeps the ABSOLUTE chunk, so a sample's number and RNG stream do not depend on the pass it was rendered in
+HD uint32_t decode_range(uint32_t base, uint32_t pass_chunks, uint32_t chunk0, uint32_t tiles_x, uint32_t world, uint32_t rank, const uint32_t* tile_order)
 {
     const uint32_t tc = base >> 6;
-    const uint32_t owned = tc / n_chunks, chunk = tc - owned * n_chunks;
+    const uint32_t owned = tc / pass_chunks, chunk = chunk0 + (tc - owned * pass_chunks);
     const uint32_t tile = tile_order ? tile_order[owned] : owned * world + rank;
     uint32_t tx, ty;
     hjr_tile_xy(tile, tiles_x, &tx, &ty);
@@ -421,7 +424,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             const uint32_t n = (uint32_t)__popcll(m);
             const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             // (cold parameters, read here and not kept in SGPRs across the render loop: see cold_param)
-            const uint32_t n_owned_items = HJR_COLD(n_owned_items), n_chunks = HJR_COLD(n_chunks), tiles_x = HJR_COLD(tiles_x), world = HJR_COLD(world);
+            const uint32_t n_owned_items = HJR_COLD(n_owned_items), pass_chunks = HJR_COLD(pass_chunks), tiles_x = HJR_COLD(tiles_x), world = HJR_COLD(world);
             const uint32_t* const tile_order = HJR_COLD(tile_order);
             uint32_t* const tile_cost = HJR_COLD(tile_cost);
             uint32_t q;
@@ -451,7 +454,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
                     if (prefix >= have) q = 0xffffffffu;
                     wr.next = wr.end = 0u;
                 } else {
-                    const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)decode_range(base, n_chunks, tiles_x, world, HJR_COLD(rank), tile_order)); // (wave-uniform)
+                    const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)decode_range(base, pass_chunks, HJR_COLD(chunk0), tiles_x, world, HJR_COLD(rank), tile_order)); // (wave-uniform)
                     if (prefix >= have) { q = base + (prefix - have); r_item = bi; }
                     wr.next = base + (n - have);
                     wr.end = base + 64u;
@@ -462,7 +465,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             // measured cost of a tile (orders the tiles of the next frame, hjr_cost_hist_kernel): a lane sums the rays of its
             // consecutive items of one tile and flushes when it moves on; lanes leaving the same tile together (the usual
             // case) share one atomic.  All lanes are here (m is wave-uniform), so the shuffles below are well defined.
-            if (wr.shared && need && q < n_owned_items) r_item = decode_range(q & ~63u, n_chunks, tiles_x, world, HJR_COLD(rank), tile_order); // (wavefront kernel: runs of the shared range, decoded per lane)
+            if (wr.shared && need && q < n_owned_items) r_item = decode_range(q & ~63u, pass_chunks, HJR_COLD(chunk0), tiles_x, world, HJR_COLD(rank), tile_order); // (wavefront kernel: runs of the shared range, decoded per lane)
             if (tile_cost) {
                 const uint32_t old_tile = hjr_tile_id(HJR_PX(c) / HJR_TILE, HJR_PY(c) / HJR_TILE, tiles_x);
                 const uint32_t new_tile = (need && q < n_owned_items) ? hjr_tile_id((r_item & 0x1fffu) / HJR_TILE, ((r_item >> 13) & 0x1fffu) / HJR_TILE, tiles_x) : 0xffffffffu;

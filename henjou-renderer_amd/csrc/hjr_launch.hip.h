@@ -56,21 +56,35 @@ struct hjr_ctx {
     uint32_t n_textures = 0;
     int lut_w = 0, lut_h = 0;
     DevBuf d_color, d_albedo, d_normal; // staging for hjr_render (host buffers)
-    DevBuf d_part_color, d_part_albedo, d_part_normal; // chunk sums [n_chunks][H][W] float4
+    DevBuf d_part_color, d_part_albedo, d_part_normal; // chunk sums [pass_chunks][owned tile][64] float4
+    DevBuf d_run_color, d_run_albedo, d_run_normal; // running sums of a frame rendered in sample passes, [owned tile][64] float4
     DevBuf d_spill; // overflow of the short traversal stacks (memory-path kernels)
     DevBuf d_wf_ctx; // context planes of the wavefront kernel
     DevBuf d_tiles; // [tile_order | tile_class] of the cost-ordered tile list
     DevBuf d_tile_cost; // measured per-tile cost of the previous frame
     uint64_t cost_tag = 0; // (width, height, spp, rank, world, integrator) the costs belong to; 0 = none
+    uint32_t cost_samples = 0; // samples per pixel of the launch that measured them (a whole frame or a sample pass)
     DevBuf d_dn_a, d_dn_b, d_dn_out; // denoise ping-pong / host-entry staging
     hjr_stats stats;
     bool event_pending = false;
+    // Frame data generation: hjr_upload_scene, hjr_set_lut, hjr_set_sky and a commit that replaces the frame data bump it, so a frame
+    // rendered in sample passes can tell that what it renders changed between two passes
+    uint64_t frame_gen = 0;
+    // The one frame of this context that is being rendered in sample passes (hjr_params.sample_begin / sample_end):
+    // the parameters of its first pass, the sample its next pass must start at, the AOVs it writes (bit 0 colour, 1 albedo, 2 normal)
+    // and the frame data generation it was started on
+    struct PassSession {
+        bool active = false;
+        hjr_params p;
+        uint32_t next = 0, aovs = 0;
+        uint64_t gen = 0;
+    } pass;
     hjr::Options opt; // hjr_set_option (host/options.hpp): the library reads no environment variable
 
     void release_buffers()
     {
         for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
-                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out })
+                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out })
             b->release();
         dbvh.release();
     }

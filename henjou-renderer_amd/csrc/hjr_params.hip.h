@@ -28,7 +28,7 @@ struct KParams {
     int sky_w, sky_h;
     uint32_t n_lights;
     uint32_t width, height, spp, frame, seed, integrator;
-    uint32_t tiles_x, n_owned_items; // items = owned tiles * n_chunks * 64
+    uint32_t tiles_x, n_owned_items; // items = owned tiles * pass_chunks * 64
     uint32_t rank, world;
     uint32_t packed;                 // HJR_FLAG_PACKED: the AOV buffers hold this rank's tiles only, [owned tile][64] float4
     uint32_t chunk_spp, n_chunks;    // samples per work item, work items per pixel (hjr_chunking)
@@ -44,7 +44,7 @@ struct KParams {
     uint32_t* tile_bucket;           // per owned tile: sort key of the measured-cost order
     uint32_t* tile_cost;             // per owned tile: closest-hit rays traced for it this frame (feeds the next frame's tile order)
     uint32_t* cost_hist;             // [0..63] tiles per cost bucket, [64..127] scatter cursors
-    uint32_t cost_div;               // 64 * spp: rays per tile at one ray per sample
+    uint32_t cost_div;               // 64 * samples of the launch that measured tile_cost: rays per tile at one ray per sample
     uint32_t spill_stride;           // lanes in the grid
     uint32_t n_top_nodes;            // memory-path megakernel, BVH4: nodes [0, n_top_nodes) are also staged in LDS by every workgroup (0: none)
     uint32_t stack_lds_entries;      // memory-path kernels: stack entries per lane kept in LDS (the rest overflow to stack_spill)
@@ -55,11 +55,20 @@ struct KParams {
     uint32_t wf_cap;                 // contexts per workgroup (power of two, <= 32768: ids travel as uint16 + 1)
     uint32_t wf_refill, wf_trace_min; // trace-stage hand-over threshold (lanes without a ray) / scheduler preference for TRACE (queued rays)
     uint32_t wf_prefetch_min;        // trace-stage hand-over threshold (lanes that have used up their prefetched context)
-    float4* part_color;              // [n_chunks][owned tile][64] chunk sums when n_chunks > 1
+    float4* part_color;              // [n_chunks][owned tile][64] chunk sums when n_chunks > 1, as the render kernels address them; a sample pass
+                                     // allocates its own chunks only and passes the buffer minus chunk0 chunks (only chunks >= chunk0 are stored)
     float4* part_albedo;
     float4* part_normal;
     float cam_pos[3], cam_dir[3], cam_up[3], cam_right[3];
     float cam_f;
     float sky[3]; // scene_sky_default * ibl_intensity
     float ibl_intensity;
+    // sample pass (hjr_params.sample_begin / sample_end): the launch renders chunks [chunk0, chunk0 + pass_chunks) of the
+    // frame's n_chunks (0 / n_chunks for a whole frame); the buffers behind part_* hold those chunks only
+    uint32_t chunk0, pass_chunks;
+    float4* run_color;               // hjr_accumulate_kernel: running sums of the frame's earlier passes, [owned tile][64] float4 per AOV
+    float4* run_albedo;
+    float4* run_normal;
+    uint32_t run_load, run_store;    // 1: the running sums hold earlier passes (else they start at +0.0f) / are written back (not the last pass)
+    uint32_t sample_end;             // the mean is running sum * (1 / sample_end)
 };

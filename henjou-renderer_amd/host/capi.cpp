@@ -172,6 +172,26 @@ extern "C" uint32_t hjr_owned_tiles(uint32_t w, uint32_t h, uint32_t rank, uint3
     const uint64_t n_tiles = (uint64_t)((w + 7u) / 8u) * ((h + 7u) / 8u);
     return n_tiles > rank ? (uint32_t)((n_tiles - rank + world - 1) / world) : 0u;
 }
+// sample-pass ends of a frame of spp samples in n passes ("Henjou_HIP": {"passes": n}): k * spp / n rounded down to the granule, the last one
+// spp; passes that come out empty are dropped, so a frame never has more passes than chunks.  henjou_cli's rank path splits the same way.
+static std::vector<uint32_t> pass_ends(uint32_t spp, uint32_t n)
+{
+    const uint32_t g = hjr_sample_granule(spp);
+    std::vector<uint32_t> ends;
+    for (uint32_t k = 1; k < n && g; k++) {
+        const uint32_t e = (uint32_t)((uint64_t)k * spp / n) / g * g;
+        if (e > (ends.empty() ? 0u : ends.back())) ends.push_back(e);
+    }
+    ends.push_back(spp);
+    return ends;
+}
+// boundary granule of sample passes: one work-item chunk, or the whole frame when it is a single chunk
+extern "C" uint32_t hjr_sample_granule(uint32_t spp)
+{
+    if (spp == 0) return 0;
+    const uint32_t g = hjr_chunk_spp(spp);
+    return g >= spp ? spp : g;
+}
 template <bool PACK> static int tiles_copy(const float* src, float* dst, uint32_t w, uint32_t h, uint32_t rank, uint32_t world)
 {
     if (!src || !dst || w == 0 || h == 0 || world == 0 || rank >= world) { set_error("hjr_pack_tiles / hjr_unpack_tiles: bad argument"); return HJR_ERR_ARG; }
@@ -359,14 +379,21 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
             cv.wait(lk, [&] { return !sl.full; });
             if (write_rc != HJR_OK) { rc = write_rc; break; }
         }
-        if (opt.render_mode == HJR_MODE_DEFAULT) rc = hjr_render(ctx, &p, sl.color.data(), nullptr, nullptr);
-        else rc = hjr_render_denoised(ctx, &p, opt.render_mode, sl.color.data(), opt.image_width, opt.image_height); // renderer.h:1258-1281
+        // "passes": the frame in sample passes; each pass overwrites the slot with the running mean, the last one with the frame
+        const std::vector<uint32_t> ends = pass_ends(p.spp, opt.passes ? opt.passes : 1u);
+        float kernel_ms = 0.0f;
+        for (size_t k = 0; rc == HJR_OK && k < ends.size(); k++) {
+            if (ends.size() > 1) { p.sample_begin = k ? ends[k - 1] : 0u; p.sample_end = ends[k]; }
+            if (opt.render_mode == HJR_MODE_DEFAULT) rc = hjr_render(ctx, &p, sl.color.data(), nullptr, nullptr);
+            else rc = hjr_render_denoised(ctx, &p, opt.render_mode, sl.color.data(), opt.image_width, opt.image_height); // renderer.h:1258-1281
+            hjr_stats st;
+            HJR_INIT(st);
+            if (rc == HJR_OK && hjr_get_stats(ctx, &st) == HJR_OK) kernel_ms += st.last_kernel_ms;
+        }
         if (rc != HJR_OK) break;
-        hjr_stats st;
-        HJR_INIT(st);
-        if (hjr_get_stats(ctx, &st) == HJR_OK)
-            fprintf(stderr, "[henjou] frame %u: %ux%u, %u spp, kernel %.3f ms (%.2f Msamples/s)\n", frame, p.width, p.height, p.spp,
-                    st.last_kernel_ms, st.last_kernel_ms > 0 ? (double)p.width * p.height * p.spp / (st.last_kernel_ms * 1e3) : 0.0);
+        fprintf(stderr, "[henjou] frame %u: %ux%u, %u spp, kernel %.3f ms (%.2f Msamples/s)%s\n", frame, p.width, p.height, p.spp,
+                kernel_ms, kernel_ms > 0 ? (double)p.width * p.height * p.spp / (kernel_ms * 1e3) : 0.0,
+                ends.size() > 1 ? (", " + std::to_string(ends.size()) + " sample passes").c_str() : "");
         std::string str_frame = std::to_string(frame); // renderer.h:1291-1302
         if (str_frame.size() < 2) str_frame = "00" + str_frame;
         else if (str_frame.size() < 3) str_frame = "0" + str_frame;

@@ -54,6 +54,7 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
     o.integrator = HJR_INTEGRATOR_NEE;
     o.devices = 1;
     o.tile = 8;
+    o.passes = 1;
     std::string text;
     if (!read_file(path, text)) { err = "File " + path + " not found"; return false; }
     try {
@@ -137,6 +138,12 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 const double r = v->is_number() ? v->as_number() : -1.0;
                 if (!(r >= 0 && r <= 3) || r != (double)(uint32_t)r) throw JsonError("Henjou_HIP.device_bvh_opt must be an integer in [0, 3]");
                 o.device_bvh_opt = (int32_t)r;
+            }
+            // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
+            if (const Json* v = h->find("passes")) {
+                const double n = v->is_number() ? v->as_number() : -1.0;
+                if (!(n >= 1 && n <= 64) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.passes must be an integer in [1, 64]");
+                o.passes = (uint32_t)n;
             }
         }
     } catch (std::exception& e) { // :222-225

@@ -139,6 +139,8 @@ typedef struct hjr_render_option {
     int32_t force_rebuild;       /* default 0; 1: hjr_render_file rebuilds the frame data every frame even when nothing moved (benchmarking) */
     int32_t device_bvh;          /* default 0; 1: hjr_render_file / henjou_cli build the frame data on the device (option "device_bvh") */
     int32_t device_bvh_opt;      /* default 0; 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt") */
+    uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
+                                  * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
 } hjr_render_option;
 
 typedef struct hjr_camera {      /* Params.camera_* (renderer/renderer.h:1187-1191) */
@@ -159,7 +161,26 @@ typedef struct hjr_params {
     float ibl_intensity;         /* params.ibl_intensity */
     uint32_t rank, world_size;   /* pixel-tile shard: this launch renders the 8x8 tiles whose id t (see hjr_owned_tiles) has t % world_size == rank */
     uint32_t flags;              /* HJR_FLAG_* */
+    uint32_t sample_begin, sample_end; /* sample pass of a progressive frame (below); sample_end 0 = the whole frame */
 } hjr_params;
+/* ---- Rendering one frame in sample passes (progressive rendering) ------------------------------------------------
+ * sample_end == 0 (what an older, shorter hjr_params reads as), or sample_begin == 0 with sample_end == spp: the whole frame in one launch.
+ * Otherwise the call renders samples [sample_begin, sample_end) of the spp-sample frame and writes, to every AOV it is given, the running
+ * mean over samples [0, sample_end): running sum * (1.0f / (float)sample_end).  The pass that ends at spp writes the bits of the one-shot
+ * frame.  A boundary is a multiple of hjr_sample_granule(spp) or equal to spp, and sample_begin < sample_end <= spp; anything else is
+ * HJR_ERR_ARG (a frame of a single chunk, granule == spp, accepts only the whole range).
+ * One progressive frame per context:
+ *   - a pass with sample_begin == 0 starts it, replacing an unfinished one;
+ *   - a pass with sample_begin > 0 continues it: sample_begin must equal the previous pass's sample_end; width, height, spp, frame, seed,
+ *     integrator, camera, sky, ibl_intensity, rank, world_size and the flags PACKED, ZERO_UNOWNED and FAST_MATH must be those of the first
+ *     pass (STATS may differ from pass to pass), the same set of AOVs must be requested, and the frame data must be unchanged
+ *     (hjr_upload_scene, hjr_set_lut, hjr_set_sky, and a hjr_set_transforms / hjr_commit_transforms that replaces the frame data, all end
+ *     it; a commit of unchanged transforms does not).  Otherwise the call returns HJR_ERR_STATE, naming the mismatch, enqueues nothing,
+ *     writes no output and leaves the frame as it was, so that a corrected call can follow;
+ *   - the pass that ends at spp, or any whole-frame render on the context, ends it.
+ * Passes are stream-ordered like every launch: the passes of one frame go on one stream (or the caller orders them).  The output pointers
+ * may differ from pass to pass; hjr_stats describes the last launch.  hjr_render, hjr_render_device and hjr_render_denoised (which then
+ * filters the running mean) all take passes.  Chunk-sum memory is bounded by the pass, plus one running sum per AOV. */
 #define HJR_FLAG_STATS 1u        /* run the counting variant of the kernel (slower; fills hjr_stats) */
 #define HJR_FLAG_ZERO_UNOWNED 2u /* clear pixels of tiles this rank does not own (for a sum-reduce exchange) */
 #define HJR_FLAG_PACKED 4u       /* the AOV buffers (device or host) are PACKED — this rank's tiles only, back to back, each
@@ -252,6 +273,9 @@ int hjr_synchronize(hjr_ctx*);
  * rank's tiles run along diagonals instead of forming vertical stripes when tiles_x is a multiple of world_size); tile t belongs to
  * rank t % world_size and is that rank's (t / world_size)-th tile. */
 uint32_t hjr_owned_tiles(uint32_t width, uint32_t height, uint32_t rank, uint32_t world_size);
+/* Boundary granule of a frame's sample passes (hjr_params.sample_begin / sample_end): the samples of one work-item chunk, 8 up to 512 spp,
+ * 16 at 1024, 64 at 4096; spp itself when the frame is a single chunk.  Host only, no GPU needed. */
+uint32_t hjr_sample_granule(uint32_t spp);
 /* host arrays: row-major float4 frame <-> packed [owned tile][64] float4 of one rank (frame pixels of other ranks untouched) */
 int hjr_pack_tiles(const float* frame_rgba, uint32_t width, uint32_t height, uint32_t rank, uint32_t world_size, float* packed_rgba);
 int hjr_unpack_tiles(const float* packed_rgba, uint32_t width, uint32_t height, uint32_t rank, uint32_t world_size, float* frame_rgba);
@@ -297,7 +321,7 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *   "wf_cap"          64..32768   wavefront kernel: path contexts per workgroup, a power of two (2048 in LDS layouts, 4096 otherwise)
  *   "wf_refill" / "wf_prefetch_min" / "wf_trace_min"   wavefront kernel: hand-over thresholds of the trace stage, scheduler preference
  *   "host_threads"    1..256      worker threads of the per-frame host preparation, process-wide (min(hardware threads, 16))
- *   "verbose"         0 1         BVH format, sizes, host build stages per frame on stderr (0)
+ *   "verbose"         0 1         BVH format, sizes, host build stages per frame, one line per sample pass on stderr (0)
  *   "force_rebuild"   0 1         rebuild the frame data even when the transforms did not change (0)
  *   "device_bvh"      0 1         0: flatten + BVH build on host threads (default); 1: on the device, as kernels on the context's stream
  *                                 (Morton-order tree collapsed to BVH4, always the memory layout: lds_mode 0).  hjr_prepare_transforms then
@@ -309,6 +333,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *                                 scene 1 round took the build from 5.5 to 10.4 ms and the render from 151 to 135 ms.  The host build
  *                                 ignores it                                                                                   [*]
  *   [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
+ * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
+ * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
