@@ -7,15 +7,19 @@ scene, no external data), and for N > 1 the ranks' packed colour tiles (1 / N of
 collective over xGMI and scattered into the frame there.
 Scene, BVH and all buffers are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080 --spp 256] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080 --spp 256] [--dump-outputs DIR] [--full]
     N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
             or plainly `python bench.py --gpus N ...`: without WORLD_SIZE in the environment bench.py starts that launcher itself as a
             child process (before anything touches the GPU), relays its output and exits with its code.
 
 Prints ONE JSON line on rank 0 (contract in the task statement).  `value` is the rate of the launch the reference's raygen
-performs (colour + albedo + normal AOVs, renderer/renderer.h:1222-1224); `color_only` carries the rate of the lean colour-only
-instantiation next to it.  Plus
+performs (colour + albedo + normal AOVs, renderer/renderer.h:1222-1224).  A plain run does only what that figure needs: set-up,
+W warm-up and K timed steps, --dump-outputs, the line.  Its set-up ends with one untimed launch of the headline frame, which loads
+the kernels, allocates the frame's buffers and sets up the collective, as the runs that --full times before the headline do.
+--full adds the rest of the record (--no-pmc, --no-secondary and --no-cpu-baseline leave parts of it out):
+  "color_only":   the lean colour-only instantiation, W + K steps timed like the headline, before it;
+  "fast_math":    N = 1: the opt-in approximate-arithmetic kernels, W + K steps timed before the headline, and their RMSE against its frame;
   "roofline":     the bound is chosen per launch from hardware counters collected IN THIS RUN (rocprofv3 --pmc passes over
                   tools/kbench, the same library and workload, started before this process touches the GPU):
                     * "valu": VALU lane-slot utilisation in the peak's units: every VALU wave instruction x its active lanes counted as
@@ -27,6 +31,7 @@ instantiation next to it.  Plus
                   whichever fraction is larger is the roof the launch is closer to and becomes `bound` / `frac` (both <= 1 by
                   construction, both reported under `counters`).
                   SURVEY.md section 8d's algorithmic-bytes figure stays as a side field (it counts reads that LDS serves).
+  "secondary":    N = 1, cornell scene: the generated ~1 M-triangle scene through tools/kbench (kernel time, counter bytes);
   "cpu_baseline": the CPU oracle (a from-scratch port; the reference has no CPU path) timed on the host cores
 
 --dump-outputs DIR writes what the headline's last timed step computed, the float32 H x W x RGBA AOVs a caller of render_device
@@ -196,6 +201,9 @@ def main():
                     help="oracle threads for the CPU baseline (a 1-GPU box's CPU share is 16 cores)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the AOVs of the headline's last timed step to DIR/<name>.npy (float32, at most 64 MB; module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the colour-only and fast-math rates, the roofline counters, the large scene and the CPU baseline "
+                         "(module docstring); --no-pmc / --no-secondary / --no-cpu-baseline apply to this run")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -222,7 +230,7 @@ def main():
     # ---- hardware counters of this workload, collected in child processes BEFORE this process initialises the GPU
     pmc, pmc_full, pmc_error = None, None, None
     config_json = {"cornell": "render_option_c2.json", "thinfilm": "render_option_c3.json", "ior15": "render_option_c4.json"}.get(args.scene)
-    if rank == 0 and not args.no_pmc and "HJR_BENCH_DEVICE" not in os.environ:
+    if rank == 0 and args.full and not args.no_pmc and "HJR_BENCH_DEVICE" not in os.environ:
         try:
             kcfg = config_json
             if args.scene == "stress":
@@ -246,7 +254,7 @@ def main():
         except Exception as ex:  # reported on the line; never silently replaced by a committed file
             pmc_error = "%s: %s" % (type(ex).__name__, ex)
     secondary = None
-    if rank == 0 and world == 1 and args.scene == "cornell" and not args.no_pmc and not args.no_secondary and "HJR_BENCH_DEVICE" not in os.environ:
+    if rank == 0 and world == 1 and args.full and args.scene == "cornell" and not args.no_pmc and not args.no_secondary and "HJR_BENCH_DEVICE" not in os.environ:
         try:
             secondary = stress_secondary(os.environ.get("HJR_LIB") or os.path.join(ROOT, "henjou-renderer_amd", "libhenjou_hip.so"), args.stress_spheres, args.stress_segments)
         except Exception as ex:
@@ -355,10 +363,13 @@ def main():
             el = float(t.item())
         return el, ms, {0: "persistent megakernel", 1: "workgroup-local wavefront kernel"}[r.device.stats()["pipeline"]]
 
-    elapsed_color, kernel_ms_color, pipe_color = timed(step_color)
+    if args.full:
+        elapsed_color, kernel_ms_color, pipe_color = timed(step_color)
+    else:  # one untimed launch leaves the headline, even at --warmup 0, where the runs above leave it: kernels loaded, buffers allocated
+        step_full()
     # opt-in approximate-arithmetic kernels (HJR_FLAG_FAST_MATH; megakernel family): a named side block, never the headline
     fast_block = None
-    if world == 1:
+    if args.full and world == 1:
         params_exact = params
         params, _ = r.frame_params(frame, rank=rank, world_size=world, flags=hjr.FLAG_FAST_MATH)
         elapsed_fast, kernel_ms_fast, _ = timed(step_full)
@@ -367,7 +378,7 @@ def main():
     elapsed, kernel_ms, pipe_full = timed(step_full)  # the headline: EXACTLY args.steps steps between the fences
     if args.dump_outputs and rank == 0:  # before the counting and CPU-baseline launches below reuse fb
         dump_outputs(args.dump_outputs, {"color": fb} if world > 1 else {"color": fb, "albedo": fb_albedo, "normal": fb_normal})
-    if world == 1:
+    if args.full and world == 1:
         d2 = (fast_frame[..., :3].double() - fb[..., :3].double()) ** 2
         fast_block = {"value": round(float(W) * H * SPP * args.steps / elapsed_fast / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(elapsed_fast / args.steps * 1e3, 3),
                       "kernel_ms_avg": round(sum(kernel_ms_fast) / len(kernel_ms_fast), 3),
@@ -386,10 +397,13 @@ def main():
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "aovs": "color+albedo+normal (the reference raygen's outputs)",
-        "color_only": {"value": round(total_samples / elapsed_color / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(elapsed_color / args.steps * 1e3, 3),
-                       "kernel_ms_avg": round(sum(kernel_ms_color) / len(kernel_ms_color), 3), "pipeline": pipe_color,
-                       "note": "same workload, aov_color only (lean kernel instantiation; Default mode writes only this AOV to the PNG)"},
-        "fast_math": fast_block,
+    }
+    if args.full:
+        out["color_only"] = {"value": round(total_samples / elapsed_color / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(elapsed_color / args.steps * 1e3, 3),
+                             "kernel_ms_avg": round(sum(kernel_ms_color) / len(kernel_ms_color), 3), "pipeline": pipe_color,
+                             "note": "same workload, aov_color only (lean kernel instantiation; Default mode writes only this AOV to the PNG)"}
+        out["fast_math"] = fast_block
+    out.update({
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -399,9 +413,9 @@ def main():
                    "scene": args.scene, "triangles": int(r.scene.view.n_triangles),
                    "width": W, "height": H, "spp": SPP, "integrator": args.integrator,
                    "parallelism": "8x8 pixel tiles round-robin over %d GPU(s)%s" % (world, " + RCCL gather of each rank's packed colour tiles onto rank 0" if world > 1 else "")},
-    }
+    })
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant (only) kernel: counters from the counting variant at 1/16 of the samples
         sp = hjr.make_params(W, H, max(SPP // 16, 1), params.camera, frame=params.frame, seed=params.seed, integrator=integ,
                              sky=tuple(params.sky), ibl_intensity=params.ibl_intensity, rank=rank, world_size=world,
@@ -523,6 +537,7 @@ def main():
                                    "rmse_gpu_vs_cpu": {"value": rmse, "spp": cspp, "pixels": ww * wh, "tolerance": 1e-3,
                                                        "note": "per-pixel RMSE (linear RGB) of the HIP frame against the CPU restatement with glibc transcendentals, "
                                                                "identical sample streams; no OptiX render can exist here (SURVEY.md section 0)"}}
+    if rank == 0:
         print(json.dumps(out))
         sys.stdout.flush()
     if world > 1:

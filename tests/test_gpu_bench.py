@@ -12,6 +12,7 @@ from scene_util import ROOT, hjr
 pytestmark = pytest.mark.gpu
 REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config"]
+FULL_ONLY = ["color_only", "fast_math", "roofline", "secondary", "cpu_baseline"]
 
 
 def run(cmd, env=None):
@@ -23,12 +24,16 @@ def run(cmd, env=None):
 
 
 def test_bench_single_gpu_contract():
-    d = run([sys.executable, "bench.py", "--width", "320", "--height", "200", "--spp", "32", "--steps", "2", "--warmup", "1", "--cpu-spp", "2",
-             "--stress-spheres", "8", "--stress-segments", "32"])
-    for k in REQUIRED:
-        assert k in d, k
-    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "Msamples/s" and d["dtype"] == "f32"
-    assert d["value"] > 0 and d["higher_is_better"] is True and d["vs_baseline"] is None and "workload" in d["config"]
+    """The plain line carries the headline only; --full adds the measured side blocks to the same keys."""
+    cmd = [sys.executable, "bench.py", "--width", "320", "--height", "200", "--spp", "32", "--steps", "2", "--warmup", "1", "--cpu-spp", "2",
+           "--stress-spheres", "8", "--stress-segments", "32"]
+    plain, d = run(cmd), run(cmd + ["--full"])
+    assert not [k for k in FULL_ONLY if k in plain], plain
+    for line in (plain, d):
+        for k in REQUIRED:
+            assert k in line, k
+        assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "Msamples/s" and line["dtype"] == "f32"
+        assert line["value"] > 0 and line["higher_is_better"] is True and line["vs_baseline"] is None and "workload" in line["config"]
     r = d["roofline"]
     # the bound is chosen from counters collected inside the run: VALU lane-operations for a scene served by LDS / L2
     assert r["counters"]["source"].startswith("rocprofv3"), r["counters"]
@@ -83,7 +88,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, HJR_BENCH_DEVICE="0", HJR_BENCH_BACKEND="gloo")
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
              "--master-port", "29577", "bench.py", "--gpus", "2", "--width", "320", "--height", "200", "--spp", "32", "--steps", "1",
-             "--warmup", "1"], env=env)
+             "--warmup", "1", "--full"], env=env)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0 and "cpu_baseline" not in d
     assert "gather" in d["config"]["parallelism"]
 
