@@ -78,7 +78,8 @@ class RenderOption(_Sized):
                 ("scene_sky_default", C.c_float * 3), ("use_date", C.c_int32), ("save_renderOption", C.c_int32),
                 ("LUT_path", C.c_char * 512), ("seed", C.c_uint32), ("integrator", C.c_int32),
                 ("devices", C.c_uint32), ("tile", C.c_uint32), ("serial_io", C.c_int32), ("fast_math", C.c_int32), ("force_rebuild", C.c_int32),
-                ("device_bvh", C.c_int32), ("device_bvh_opt", C.c_int32), ("passes", C.c_uint32)]
+                ("device_bvh", C.c_int32), ("device_bvh_opt", C.c_int32), ("passes", C.c_uint32),
+                ("noise_threshold", C.c_float), ("min_samples", C.c_uint32)]
 
 
 class Camera(C.Structure):
@@ -124,6 +125,17 @@ class StatsV2(Stats):
     """hjr_stats with the fields appended after `Stats` (the layout up to nan_where).  Both are valid callers under the sized-struct
     rule: the library writes min(struct_size, its sizeof) bytes.  Device.stats() uses this one."""
     _fields_ = [("bvh_builder", C.c_uint32), ("frame_build_ms", C.c_float)]
+
+
+class Adaptive(_Sized):
+    """hjr_adaptive: the adaptive-sampling setting of a context (hjr_set_adaptive)."""
+    _fields_ = [("struct_size", C.c_uint32), ("noise_threshold", C.c_float), ("min_samples", C.c_uint32)]
+
+
+class AdaptiveState(_Sized):
+    """hjr_adaptive_state: the context's adaptive progressive frame after its last pass (hjr_get_adaptive_state)."""
+    _fields_ = [("struct_size", C.c_uint32), ("owned_tiles", C.c_uint32), ("active_tiles", C.c_uint32), ("sample_end", C.c_uint32),
+                ("samples_rendered", C.c_uint64)]
 
 
 _lib = None
@@ -180,6 +192,9 @@ def lib():
             "hjr_pack_tiles_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
             "hjr_unpack_tiles_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
             "hjr_selftest_stack16": [],
+            "hjr_set_adaptive": [C.c_void_p, C.c_void_p],
+            "hjr_get_adaptive_state": [C.c_void_p, C.c_void_p],
+            "hjr_copy_tile_samples": [C.c_void_p, C.c_void_p, C.c_size_t],
         }.items():
             fn = getattr(L, name)
             fn.restype = C.c_int
@@ -420,6 +435,33 @@ class Device:
             p.sample_begin, p.sample_end = begin, end
             color, albedo, normal = self.render(p, want_aovs)
             yield end, color, albedo, normal
+
+    def set_adaptive(self, noise_threshold, min_samples=0):
+        """hjr_set_adaptive: converged 8x8 tiles stop between the sample passes of a frame (mean relative error of the tile's pixels at
+        most noise_threshold; no decision before min_samples, 0 = two granules).  0 switches it off.  Ends an unfinished progressive frame."""
+        a = Adaptive()
+        a.noise_threshold, a.min_samples = noise_threshold, min_samples
+        _check(lib().hjr_set_adaptive(self._h, C.byref(a)), "hjr_set_adaptive")
+
+    def adaptive_state(self):
+        """hjr_get_adaptive_state as a dict: owned_tiles, active_tiles, sample_end, samples_rendered (synchronous)."""
+        s = AdaptiveState()
+        _check(lib().hjr_get_adaptive_state(self._h, C.byref(s)), "hjr_get_adaptive_state")
+        return {n: int(getattr(s, n)) for n, _ in AdaptiveState._fields_ if n != "struct_size"}
+
+    def tile_samples(self):
+        """hjr_copy_tile_samples: uint32 [owned tiles], the samples each owned tile of the adaptive frame has received."""
+        out = np.zeros(self.adaptive_state()["owned_tiles"], dtype=np.uint32)
+        _check(lib().hjr_copy_tile_samples(self._h, out.ctypes.data, out.size), "hjr_copy_tile_samples")
+        return out
+
+    def render_adaptive(self, params, passes, want_aovs=True):
+        """render_progressive for a context with set_adaptive on: yields (sample_end, color, albedo, normal) after each pass and ends with
+        the first pass that leaves no tile active (or at spp); the last AOVs yielded are the frame."""
+        for out in self.render_progressive(params, passes, want_aovs):
+            yield out
+            if out[0] < params.spp and self.adaptive_state()["active_tiles"] == 0:
+                return
 
     def render_device(self, params, d_color, d_albedo=None, d_normal=None, stream=None):
         """Asynchronous render into device pointers (ints, e.g. torch tensor .data_ptr()) on a hipStream_t (int)."""

@@ -64,6 +64,15 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     if (opt.device_bvh) HJRX(hjr_set_option(ctx, "device_bvh", 1));
     if (opt.device_bvh_opt) HJRX(hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt));
     HJRX(hjr_upload_scene(ctx, &view));
+    // "noise_threshold": each rank stops its own converged tiles between the sample passes (the rule does not depend on the rank); the one
+    // gather per frame is unchanged.  A rank without tiles has nothing to adapt.
+    const bool adaptive = opt.noise_threshold > 0.0f && hjr_owned_tiles(opt.image_width, opt.image_height, (uint32_t)rank, (uint32_t)world) > 0;
+    if (adaptive) {
+        hjr_adaptive ad;
+        HJR_INIT(ad);
+        ad.noise_threshold = opt.noise_threshold; ad.min_samples = opt.min_samples;
+        HJRX(hjr_set_adaptive(ctx, &ad));
+    }
     {
         uint8_t* lut = nullptr; int lw = 0, lh = 0;
         if (hjr_load_png_rgba8(opt.LUT_path, &lut, &lw, &lh) == HJR_OK) { HJRX(hjr_set_lut(ctx, lut, lw, lh)); hjr_free(lut); }
@@ -121,6 +130,15 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
             HJRX(hjr_render_device(ctx, &p, d_packed, nullptr, nullptr, st));
             begin = end;
             n_done++;
+            if (adaptive && p.sample_end && !(p.sample_begin == 0 && p.sample_end == p.spp)) { // (a frame of a single pass is a whole-frame render: not adaptive)
+                hjr_adaptive_state as;
+                HJR_INIT(as);
+                HJRX(hjr_get_adaptive_state(ctx, &as));
+                if (as.active_tiles == 0 || end == p.spp)
+                    fprintf(stderr, "[henjou %d/%d] frame %u: adaptive: %u of %u tiles active at %u spp, %llu samples rendered\n", rank, world, f, as.active_tiles, as.owned_tiles,
+                            as.sample_end, (unsigned long long)as.samples_rendered);
+                if (as.active_tiles == 0) break;
+            }
         }
         NCCLX(ncclGather(d_packed, d_all, block * 4, ncclFloat, 0, comm, st)); // the one data-path collective of a frame
         if (rank == 0) {

@@ -173,6 +173,97 @@ __global__ void __launch_bounds__(256) hjr_accumulate_kernel(const KParams P)
     }
 }
 
+// ---- adaptive sampling (hjr_set_adaptive).  hjr_accumulate_kernel's streaming shape with one wave per owned tile: the
+// grid stride is a multiple of 64 and n_slots is one, so the 64 lanes of a wave always hold the 64 pixels of one tile and leave the loop
+// together.  An ACTIVE tile (ad_state 0) adds this pass's chunk sums to its running sums with the accumulate kernel's expressions and
+// updates the per-pixel statistic (S1, S2) over y = (c.x + c.y) + c.z in chunk order; a STOPPED tile (ad_state = n_tile) reads no chunk
+// sum (the render kernel left its slots alone: they are stale).  After a pass that decides, every active tile evaluates the stopping
+// rule of DESIGN.md §4.5 rule 6: IEEE fp32 + - * / sqrt max as written (this translation unit is built with correctly rounded divide /
+// sqrt and without contraction) and a fixed xor butterfly, so numpy float32 restates it bit for bit.  Out-of-image lanes of an edge tile
+// are predicated, never skipped: they carry e = 0 into the butterfly.  Every pass writes every owned pixel of every requested AOV.
+__global__ void __launch_bounds__(256) hjr_accumulate_adaptive_kernel(const KParams P)
+{
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t otile = (uint32_t)(sl >> 6);
+        const uint32_t tile = otile * P.world + P.rank;
+        uint32_t tx, ty;
+        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
+        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+        const bool inside = x < P.width && y < P.height;
+        uint32_t n_tile = P.run_load ? P.ad_state[otile] : 0u; // (wave-uniform) 0: the tile is active
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
+        float2 s = make_float2(0.0f, 0.0f);
+        if (inside && P.run_load) {
+            a = P.run_color[sl];
+            if (P.aov_albedo) b = P.run_albedo[sl];
+            if (P.aov_normal) c = P.run_normal[sl];
+            s = P.ad_stat[sl];
+        }
+        if (n_tile == 0u) {
+            if (inside) {
+                for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
+                    const float4 v = P.part_color[(size_t)k * n_slots + sl];
+                    a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
+                    const float yk = (v.x + v.y) + v.z;
+                    s.x = s.x + yk; s.y = s.y + yk * yk;
+                    if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
+                    if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
+                }
+                if (P.run_store) {
+                    P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
+                    if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
+                    if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
+                    P.ad_stat[sl] = s;
+                }
+            }
+            if (P.ad_decide) { // (wave-uniform branch: all 64 lanes take the butterfly)
+                const float n = (float)P.sample_end, m = (float)(P.sample_end / P.chunk_spp);
+                const float q = fmaxf(m * s.y - s.x * s.x, 0.0f);
+                const float e = sqrtf(q / (m - 1.0f)) / (s.x + HJR_ADAPTIVE_EPS * n);
+                float v = inside ? e : 0.0f;
+                for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
+                if (v <= P.ad_threshold * 64.0f) n_tile = P.sample_end;
+            }
+            if ((threadIdx.x & 63u) == 0u) {
+                P.ad_state[otile] = n_tile;
+                if (n_tile == 0u) atomicAdd(&P.ad_state[P.n_owned_tiles], 1u);
+            }
+        }
+        if (!inside) continue; // (after the butterfly)
+        const float inv = 1.0f / (float)(n_tile ? n_tile : P.sample_end);
+        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
+        P.aov_color[pix] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
+        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv, b.y * inv, b.z * inv, 1.0f);
+        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv, c.y * inv, c.z * inv, 1.0f);
+    }
+}
+
+// The launch's tile list without the stopped tiles: a STABLE compaction of ad_src (the cost order hjr_order_tiles_kernel /
+// hjr_cost_scatter_kernel just produced, or the plain round-robin order when there is none), so the expensive-first order survives and the
+// result is the same for the same input.  At most 129 600 tiles (4K): one workgroup walks the list in steps of 1024 with a ballot per wave
+// and a scan over the 16 wave counts in LDS.
+__global__ void __launch_bounds__(1024) hjr_filter_tiles_kernel(const KParams P)
+{
+    __shared__ uint32_t wave_n[16];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t done = 0; // tiles kept so far (the same in every thread)
+    for (uint32_t base = 0; base < P.n_owned_tiles; base += 1024u) {
+        const uint32_t idx = base + threadIdx.x;
+        const bool live = idx < P.n_owned_tiles;
+        const uint32_t tile = live ? (P.ad_src ? P.ad_src[idx] : idx * P.world + P.rank) : 0u;
+        const bool keep = live && P.ad_state[tile / P.world] == 0u;
+        const unsigned long long mk = __ballot(keep);
+        if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(mk);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < 16u; w++) { const uint32_t nw = wave_n[w]; before += w < wave ? nw : 0u; total += nw; }
+        if (keep) P.ad_list[done + before + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))] = tile;
+        done += total;
+        __syncthreads(); // wave_n is rewritten by the next step
+    }
+}
+
 // ---- tile pack / unpack: the multi-GPU exchange moves only owned tiles ([owned tile][64] float4)
 __global__ void __launch_bounds__(256) hjr_pack_tiles_kernel(const float4* frame, float4* packed, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_owned, uint32_t rank, uint32_t world)
 {

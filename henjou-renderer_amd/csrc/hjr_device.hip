@@ -689,6 +689,61 @@ static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, const KParams& kp, hi
     return HJR_OK;
 }
 
+// An adaptive sample pass (hjr_set_adaptive), before bind_params: the tiles still active size the launch.  A continuing
+// pass waits here for the count the previous pass of its frame read back (4 bytes, pinned).  The first adaptive pass of a context creates
+// the event and the pinned word.
+static int adaptive_items(hjr_ctx* c, FrameGeom& g, uint32_t& active)
+{
+    hjr_ctx::Adaptive& ad = c->ad;
+    if (!ad.ready) HIPCHK(hipEventCreateWithFlags(&ad.ready, hipEventDisableTiming));
+    if (!ad.h_active) HIPCHK(hipHostMalloc((void**)&ad.h_active, sizeof(uint32_t), hipHostMallocDefault));
+    active = (uint32_t)g.owned;
+    if (g.pr.begin > 0) {
+        if (!ad.frame || ad.owned != (uint32_t)g.owned) { set_error("hjr_render: the progressive frame has no adaptive state"); return HJR_ERR_STATE; }
+        HIPCHK(hipEventSynchronize(ad.ready));
+        active = *ad.h_active;
+    }
+    g.n_items = (uint64_t)active * g.pass_chunks * 64; // the render kernels' queue holds the active tiles only
+    return HJR_OK;
+}
+// ... after bind_params: the statistic, the tile states (+ the counter word) and the compacted list, kept across the passes of a frame
+static int adaptive_bind(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KParams& kp)
+{
+    hjr_ctx::Adaptive& ad = c->ad;
+    if (!ad.stat.reserve((size_t)g.owned * 64u * sizeof(float2)) || !ad.state.reserve(((size_t)g.owned + 1u) * 4u) || !ad.list.reserve((size_t)g.owned * 4u)) {
+        set_error("hjr_render: adaptive-sampling buffer allocation failed");
+        return HJR_ERR_DEVICE;
+    }
+    kp.ad_stat = (float2*)ad.stat.p; kp.ad_state = (uint32_t*)ad.state.p;
+    kp.ad_threshold = ad.threshold;
+    const uint32_t gr = g.chunk_spp, ms = ad.min_samples ? (ad.min_samples + gr - 1) / gr * gr : 2u * gr;
+    kp.ad_decide = (g.pr.end < p->spp && g.pr.end >= ms && g.pr.end / gr >= 2u) ? 1u : 0u;
+    return HJR_OK;
+}
+// ... after order_tiles: the stopped tiles leave the launch's tile list (stable: the cost order survives)
+static int adaptive_filter(hjr_ctx* c, KParams& kp, hipStream_t st)
+{
+    kp.ad_src = kp.tile_order; kp.ad_list = (uint32_t*)c->ad.list.p;
+    hipLaunchKernelGGL(hjr_filter_tiles_kernel, dim3(1), dim3(1024), 0, st, kp);
+    HIPCHK(hipGetLastError());
+    kp.tile_order = kp.ad_list;
+    return HJR_OK;
+}
+// ... instead of finalize_chunks: running sums, statistic, stop decisions, AOVs; then the count of tiles still active goes to the host
+static int adaptive_accumulate(hjr_ctx* c, const FrameGeom& g, const KParams& kp, hipStream_t st)
+{
+    hjr_ctx::Adaptive& ad = c->ad;
+    const size_t n_slots = (size_t)g.owned * 64u;
+    uint32_t* const d_count = (uint32_t*)ad.state.p + g.owned;
+    HIPCHK(hipMemsetAsync(d_count, 0, 4, st));
+    const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
+    hipLaunchKernelGGL(hjr_accumulate_adaptive_kernel, dim3(fb), dim3(256), 0, st, kp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ad.h_active, d_count, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(ad.ready, st));
+    return HJR_OK;
+}
+
 // pr: check_pass of this call, made before the caller enqueued anything
 static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, hipStream_t st)
 {
@@ -697,16 +752,75 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, voi
     int rc;
     if ((rc = frame_geometry(c, p, d_color, pr, g)) != HJR_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
+    // adaptive sampling acts on sample passes only; with it off (or a whole-frame render) nothing below differs from the plain launch
+    const bool adaptive = pr.pass && c->ad.threshold > 0.0f && g.owned > 0;
+    uint32_t active = (uint32_t)g.owned;
+    if (adaptive && (rc = adaptive_items(c, g, active)) != HJR_OK) return rc;
     if ((rc = bind_params(c, p, g, d_color, d_albedo, d_normal, st, kp)) != HJR_OK) return rc;
+    if (adaptive && (rc = adaptive_bind(c, p, g, kp)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev0, st));
-    if ((rc = order_tiles(c, p, g, kp, st)) != HJR_OK) return rc;
-    if ((rc = launch_render(c, p, g, kp, st)) != HJR_OK) return rc;
-    if ((rc = finalize_chunks(c, g, kp, st)) != HJR_OK) return rc;
+    if (!adaptive || active > 0) { // (an adaptive pass with no active tile launches no render kernel and still writes the AOVs)
+        if ((rc = order_tiles(c, p, g, kp, st)) != HJR_OK) return rc;
+        if (adaptive && active < g.owned && (rc = adaptive_filter(c, kp, st)) != HJR_OK) return rc;
+        if ((rc = launch_render(c, p, g, kp, st)) != HJR_OK) return rc;
+    }
+    if ((rc = adaptive ? adaptive_accumulate(c, g, kp, st) : finalize_chunks(c, g, kp, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
     if (pr.pass && c->opt.get(hjr::OPT_VERBOSE, 0))
         fprintf(stderr, "[hjr] frame %u: sample pass [%u, %u) of %u spp, chunks %u..%u of %u\n", p->frame, pr.begin, pr.end, p->spp, g.chunk0, g.chunk0 + g.pass_chunks - 1, g.n_chunks);
+    hjr_ctx::Adaptive& ad = c->ad;
+    ad.frame = adaptive;
+    if (adaptive) {
+        ad.owned = (uint32_t)g.owned; ad.last_end = pr.end;
+        ad.samples = (pr.begin ? ad.samples : 0ull) + (uint64_t)active * (pr.end - pr.begin) * 64ull;
+        if (c->opt.get(hjr::OPT_VERBOSE, 0))
+            fprintf(stderr, "[hjr] frame %u: adaptive pass [%u, %u): %u of %u tiles active, %llu samples rendered so far%s\n", p->frame, pr.begin, pr.end, active, ad.owned,
+                    (unsigned long long)ad.samples, kp.ad_decide ? ", stop decision after it" : "");
+    }
     end_pass(c, p, pr);
+    return HJR_OK;
+}
+
+extern "C" int hjr_set_adaptive(hjr_ctx* c, const hjr_adaptive* a_user)
+{
+    if (!c) { set_error("hjr_set_adaptive: null context"); return HJR_ERR_ARG; }
+    hjr_adaptive a; // sized struct
+    memset(&a, 0, sizeof(a));
+    if (a_user && !hjr::abi_take(a_user, a, "hjr_set_adaptive")) return HJR_ERR_ARG;
+    if (!std::isfinite(a.noise_threshold) || a.noise_threshold < 0.0f) { set_error("hjr_set_adaptive: noise_threshold must be finite and >= 0"); return HJR_ERR_ARG; }
+    if (a.min_samples > 0x7fffffffu) { set_error("hjr_set_adaptive: min_samples out of range"); return HJR_ERR_ARG; }
+    c->ad.threshold = a.noise_threshold; c->ad.min_samples = a.min_samples;
+    c->ad.frame = false;
+    c->pass.active = false; // an unfinished progressive frame ends: it cannot change its rule half way
+    return HJR_OK;
+}
+
+extern "C" int hjr_get_adaptive_state(hjr_ctx* c, hjr_adaptive_state* out)
+{
+    if (!c || !out) { set_error("hjr_get_adaptive_state: null argument"); return HJR_ERR_ARG; }
+    uint32_t out_size;
+    if (!hjr::abi_size(out, out_size, "hjr_get_adaptive_state")) return HJR_ERR_ARG;
+    if (!c->ad.frame) { set_error("hjr_get_adaptive_state: the context's last render was not an adaptive sample pass"); return HJR_ERR_STATE; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->ad.ready));
+    hjr_adaptive_state s;
+    memset(&s, 0, sizeof(s));
+    s.struct_size = (uint32_t)sizeof(s);
+    s.owned_tiles = c->ad.owned; s.active_tiles = *c->ad.h_active; s.sample_end = c->ad.last_end; s.samples_rendered = c->ad.samples;
+    return hjr::abi_give(out, s, "hjr_get_adaptive_state") ? HJR_OK : HJR_ERR_ARG;
+}
+
+extern "C" int hjr_copy_tile_samples(hjr_ctx* c, uint32_t* dst, size_t n_owned_tiles)
+{
+    if (!c || !dst) { set_error("hjr_copy_tile_samples: null argument"); return HJR_ERR_ARG; }
+    if (!c->ad.frame) { set_error("hjr_copy_tile_samples: the context's last render was not an adaptive sample pass"); return HJR_ERR_STATE; }
+    if (n_owned_tiles != c->ad.owned) { set_error("hjr_copy_tile_samples: n_owned_tiles must be hjr_adaptive_state.owned_tiles = " + std::to_string(c->ad.owned)); return HJR_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->ad.ready));
+    HIPCHK(hipMemcpy(dst, c->ad.state.p, n_owned_tiles * 4u, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_owned_tiles; i++)
+        if (dst[i] == 0u) dst[i] = c->ad.last_end; // still active: it has received every sample so far
     return HJR_OK;
 }
 

@@ -79,13 +79,27 @@ struct hjr_ctx {
         uint32_t next = 0, aovs = 0;
         uint64_t gen = 0;
     } pass;
+    // Adaptive sampling (hjr_set_adaptive).  Nothing below is allocated or created before the first adaptive sample pass.
+    struct Adaptive {
+        float threshold = 0.0f;    // hjr_adaptive.noise_threshold; 0 = off
+        uint32_t min_samples = 0;  // as given (0 = two granules; rounded up to the frame's granule at its passes)
+        bool frame = false;        // the context's last render was an adaptive sample pass: the fields below describe its frame
+        uint32_t owned = 0, last_end = 0;
+        uint64_t samples = 0;      // 64 x samples handed to active tiles so far (known on the host: active tiles at launch x pass length)
+        DevBuf stat, state, list;  // [owned tile][64] float2 (S1, S2) | [owned tile] uint32 n_tile (0 = active) + 1 counter | compacted tile list
+        uint32_t* h_active = nullptr; // pinned: tiles still active after the last pass, valid once `ready` has happened
+        hipEvent_t ready = nullptr;
+    } ad;
     hjr::Options opt; // hjr_set_option (host/options.hpp): the library reads no environment variable
 
     void release_buffers()
     {
         for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
-                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out })
+                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &ad.stat, &ad.state, &ad.list })
             b->release();
+        if (ad.h_active) (void)hipHostFree(ad.h_active);
+        if (ad.ready) (void)hipEventDestroy(ad.ready);
+        ad.h_active = nullptr; ad.ready = nullptr;
         dbvh.release();
     }
 };

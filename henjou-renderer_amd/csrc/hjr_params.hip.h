@@ -71,4 +71,12 @@ struct KParams {
     float4* run_normal;
     uint32_t run_load, run_store;    // 1: the running sums hold earlier passes (else they start at +0.0f) / are written back (not the last pass)
     uint32_t sample_end;             // the mean is running sum * (1 / sample_end)
+    // adaptive sampling (hjr_set_adaptive): all null / 0 unless the launch is an adaptive sample pass
+    float2* ad_stat;                 // hjr_accumulate_adaptive_kernel: per owned pixel (S1, S2) over the chunk sums received so far, [owned tile][64]
+    uint32_t* ad_state;              // per owned tile: 0 = active, else n_tile (the sample_end the tile stopped at); word [n_owned_tiles] counts
+                                     // the tiles still active after the pass (zeroed before the accumulate kernel, read back by the host)
+    const uint32_t* ad_src;          // hjr_filter_tiles_kernel: the launch's tile order (null = plain round-robin order) ...
+    uint32_t* ad_list;               // ... and its stable compaction to the active tiles, which becomes tile_order
+    float ad_threshold;              // noise_threshold
+    uint32_t ad_decide;              // 1: a stop decision is taken after this pass (sample_end < spp, >= min_samples, >= 2 chunks)
 };

@@ -145,6 +145,19 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 if (!(n >= 1 && n <= 64) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.passes must be an integer in [1, 64]");
                 o.passes = (uint32_t)n;
             }
+            // noise_threshold / min_samples: adaptive sampling of the frame's sample passes (hjr_set_adaptive); a threshold without a
+            // "passes" key splits the frame into 8 passes
+            if (const Json* v = h->find("noise_threshold")) {
+                const double t = v->is_number() ? v->as_number() : -1.0;
+                if (!(t >= 0.0) || !std::isfinite(t) || !std::isfinite((float)t)) throw JsonError("Henjou_HIP.noise_threshold must be a finite number >= 0");
+                o.noise_threshold = (float)t;
+                if (o.noise_threshold > 0.0f && !h->find("passes")) o.passes = 8;
+            }
+            if (const Json* v = h->find("min_samples")) {
+                const double n = v->is_number() ? v->as_number() : -1.0;
+                if (!(n >= 0 && n <= 1048576.0) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.min_samples must be an integer in [0, 1048576]");
+                o.min_samples = (uint32_t)n;
+            }
         }
     } catch (std::exception& e) { // :222-225
         err = std::string("Caught exception: ") + e.what();

@@ -1,0 +1,234 @@
+// The whole-file driver of the C-ABI: hjr_render_file == Renderer::initializeAndRender (renderer/renderer.h:1053-1317).  The one host
+// file that drives the device half of the library (context, uploads, sample passes, adaptive sampling) through its public entry points.
+#include <chrono>
+#include <condition_variable>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/henjou_hip.h"
+
+namespace hjr {
+void set_error(const std::string& s);
+bool write_png(const std::string& path, const uint8_t* rgba, uint32_t w, uint32_t h, bool flip_y, std::string& err);
+void float4_to_srgb8(const float* rgba, uint8_t* out, uint32_t n);
+} // namespace hjr
+using hjr::set_error;
+
+// sample-pass ends of a frame of spp samples in n passes ("Henjou_HIP": {"passes": n}): k * spp / n rounded down to the granule, the last one
+// spp; passes that come out empty are dropped, so a frame never has more passes than chunks.  henjou_cli's rank path splits the same way.
+static std::vector<uint32_t> pass_ends(uint32_t spp, uint32_t n)
+{
+    const uint32_t g = hjr_sample_granule(spp);
+    std::vector<uint32_t> ends;
+    for (uint32_t k = 1; k < n && g; k++) {
+        const uint32_t e = (uint32_t)((uint64_t)k * spp / n) / g * g;
+        if (e > (ends.empty() ? 0u : ends.back())) ends.push_back(e);
+    }
+    ends.push_back(spp);
+    return ends;
+}
+
+// Renderer::initializeAndRender — renderer/renderer.h:1053-1317.  Render_mode "Default" is the pass-through of the reference
+// (its denoiser runs with blendFactor 1); "Denoise" / "DenoiseUpScale2X" keep the reference's data flow with the HIP a-trous
+// filter in place of the closed OptiX network (csrc/hjr_denoise.hip.h).
+extern "C" int hjr_render_file(const char* render_option_json, int device)
+{
+    if (!render_option_json) { set_error("hjr_render_file: null path"); return HJR_ERR_ARG; }
+    hjr_render_option opt;
+    HJR_INIT(opt);
+    int rc = hjr_load_render_option(render_option_json, &opt);
+    if (rc != HJR_OK) return rc;
+    if (opt.render_mode != HJR_MODE_DEFAULT && opt.render_mode != HJR_MODE_DENOISE && opt.render_mode != HJR_MODE_DENOISE_UPSCALE2X) {
+        set_error("hjr_render_file: Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)");
+        return HJR_ERR_ARG;
+    }
+    hjr_scene* scene = nullptr;
+    rc = hjr_scene_load_gltf(opt.gltf_path, opt.gltf_name, &opt, &scene);
+    if (rc != HJR_OK) return rc;
+    hjr_ctx* ctx = nullptr;
+    rc = hjr_create(device, &ctx);
+    if (rc != HJR_OK) { hjr_scene_free(scene); return rc; }
+    hjr_scene_view view;
+    HJR_INIT(view);
+    hjr_scene_get_view(scene, &view);
+    if (opt.force_rebuild) (void)hjr_set_option(ctx, "force_rebuild", 1);
+    if (opt.device_bvh) (void)hjr_set_option(ctx, "device_bvh", 1);
+    if (opt.device_bvh_opt) (void)hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt);
+    const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes
+    rc = hjr_upload_scene(ctx, &view);
+    if (rc == HJR_OK && adaptive) {
+        hjr_adaptive ad;
+        HJR_INIT(ad);
+        ad.noise_threshold = opt.noise_threshold; ad.min_samples = opt.min_samples;
+        rc = hjr_set_adaptive(ctx, &ad);
+    }
+    if (rc == HJR_OK) { // setLUT (renderer.h:854-898); a missing LUT file only matters if a material uses it
+        uint8_t* lut = nullptr;
+        int lw = 0, lh = 0;
+        if (hjr_load_png_rgba8(opt.LUT_path, &lut, &lw, &lh) == HJR_OK) {
+            rc = hjr_set_lut(ctx, lut, lw, lh);
+            hjr_free(lut);
+        } else {
+            bool needs = false;
+            for (uint32_t i = 0; i < view.n_materials; i++) needs = needs || view.materials[i].is_thinfilm;
+            if (needs) rc = HJR_ERR_IO; // hjr_last_error() already holds the PNG error
+        }
+    }
+    if (rc == HJR_OK && opt.use_IBL) { // setSky (renderer.h:802-851): a missing / undecodable HDR falls back to the 1x1 scene_sky_default texel (texture.h:89-98)
+        float* sky = nullptr;
+        int sw = 0, sh = 0;
+        if (hjr_load_hdr_rgba32f(opt.IBL_path, &sky, &sw, &sh) == HJR_OK) {
+            rc = hjr_set_sky(ctx, sky, sw, sh);
+            hjr_free(sky);
+        } else fprintf(stderr, "[henjou] %s NOT FOUND: using scene_sky_default\n", opt.IBL_path);
+    }
+    std::vector<float> m((size_t)view.n_instances * 12), inv((size_t)view.n_instances * 12);
+    // Image Scale Setting (renderer.h:1089-1099): DenoiseUpScale2X renders at half the output size
+    const uint32_t in_w = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_width / 2u : opt.image_width;
+    const uint32_t in_h = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_height / 2u : opt.image_height;
+    if (in_w == 0 || in_h == 0) { set_error("hjr_render_file: image too small for DenoiseUpScale2X"); hjr_destroy(ctx); hjr_scene_free(scene); return HJR_ERR_ARG; }
+    const size_t npx = (size_t)opt.image_width * opt.image_height;
+    // Output stage off the critical path: float4 -> sRGB8 -> PNG -> file runs on a writer thread while the main thread
+    // already builds and renders the next frame (two frame buffers in rotation).  The reference's loop is serial
+    // (renderer.h:1281-1302); the files are the same.  Only aov_color is produced: Default mode never reads the albedo /
+    // normal AOVs (they feed the OptiX denoiser, denoiser.h:94-97).  "Henjou_HIP": {"serial_io": true} disables the overlap.
+    struct Slot { std::vector<float> color; std::string name; bool full = false; };
+    Slot slots[2];
+    for (Slot& sl : slots) sl.color.resize(npx * 4);
+    std::mutex mu;
+    std::condition_variable cv;
+    bool quit = false;
+    int write_rc = HJR_OK;
+    std::string write_err;
+    const bool serial_io = opt.serial_io != 0;
+    auto write_slot = [&](Slot& sl) -> int {
+        std::vector<uint8_t> rgba8(npx * 4);
+        hjr::float4_to_srgb8(sl.color.data(), rgba8.data(), (uint32_t)npx);
+        std::string err;
+        if (!hjr::write_png(sl.name, rgba8.data(), opt.image_width, opt.image_height, true, err)) {
+            std::lock_guard<std::mutex> lk(mu);
+            write_err = err;
+            return HJR_ERR_IO;
+        }
+        return HJR_OK;
+    };
+    std::thread writer;
+    if (!serial_io)
+        writer = std::thread([&]() {
+            int next = 0;
+            for (;;) {
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return slots[next].full || quit; });
+                    if (!slots[next].full) return; // quit with nothing pending
+                }
+                const int r = write_slot(slots[next]);
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    slots[next].full = false;
+                    if (r != HJR_OK && write_rc == HJR_OK) write_rc = r;
+                }
+                cv.notify_all();
+                next ^= 1;
+            }
+        });
+    int cur = 0;
+    const auto t_all0 = std::chrono::steady_clock::now();
+    uint32_t n_frames = 0;
+    // scene update of frame f + 1 (host: TRS evaluation, flatten, BVH build) runs on a helper thread while frame f renders;
+    // only its upload (hjr_commit_transforms) waits for the render.  The reference's loop is serial (renderer.h:1128-1137).
+    std::thread prep;
+    int prep_rc = HJR_OK;
+    std::string prep_err;
+    auto prepare = [&](uint32_t frame) {
+        float time = frame / float(opt.fps); // renderer.h:1128
+        hjr_scene_eval_transforms(scene, time, m.data(), inv.data());
+        prep_rc = hjr_prepare_transforms(ctx, m.data(), inv.data(), view.n_instances);
+        if (prep_rc != HJR_OK) prep_err = hjr_last_error(); // thread-local on the helper thread
+    };
+    if (opt.start_frame < opt.end_frame) prepare(opt.start_frame);
+    for (uint32_t frame = opt.start_frame; rc == HJR_OK && frame < opt.end_frame; frame++) {
+        float time = frame / float(opt.fps); // renderer.h:1128
+        if (prep.joinable()) prep.join();
+        if (prep_rc != HJR_OK) { rc = prep_rc; set_error(prep_err); break; }
+        rc = hjr_commit_transforms(ctx);
+        if (rc != HJR_OK) break;
+        if (frame + 1 < opt.end_frame && !serial_io) prep = std::thread(prepare, frame + 1);
+        hjr_params p;
+        HJR_INIT(p);
+        p.width = in_w; p.height = in_h;
+        p.spp = opt.max_spp; p.frame = frame; p.seed = opt.seed; p.integrator = (uint32_t)opt.integrator;
+        hjr_scene_eval_camera(scene, &opt, time, &p.camera);
+        for (int k = 0; k < 3; k++) p.sky[k] = opt.scene_sky_default[k];
+        p.ibl_intensity = opt.IBL_intensity;
+        p.rank = 0; p.world_size = 1;
+        if (opt.fast_math) p.flags |= HJR_FLAG_FAST_MATH; // "Henjou_HIP": {"fast_math": true}
+        Slot& sl = slots[cur];
+        if (!serial_io) { // the slot may still be with the writer (two frames behind)
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return !sl.full; });
+            if (write_rc != HJR_OK) { rc = write_rc; break; }
+        }
+        // "passes": the frame in sample passes; each pass overwrites the slot with the running mean, the last one with the frame
+        const std::vector<uint32_t> ends = pass_ends(p.spp, opt.passes ? opt.passes : 1u);
+        // "noise_threshold": the frame ends with the first pass that leaves no tile active; the slot then holds the frame
+        float kernel_ms = 0.0f;
+        size_t n_done = 0;
+        hjr_adaptive_state as;
+        HJR_INIT(as);
+        for (size_t k = 0; rc == HJR_OK && k < ends.size(); k++) {
+            if (ends.size() > 1) { p.sample_begin = k ? ends[k - 1] : 0u; p.sample_end = ends[k]; }
+            if (opt.render_mode == HJR_MODE_DEFAULT) rc = hjr_render(ctx, &p, sl.color.data(), nullptr, nullptr);
+            else rc = hjr_render_denoised(ctx, &p, opt.render_mode, sl.color.data(), opt.image_width, opt.image_height); // renderer.h:1258-1281
+            hjr_stats st;
+            HJR_INIT(st);
+            if (rc == HJR_OK && hjr_get_stats(ctx, &st) == HJR_OK) kernel_ms += st.last_kernel_ms;
+            n_done++;
+            if (rc == HJR_OK && adaptive && ends.size() > 1) {
+                rc = hjr_get_adaptive_state(ctx, &as);
+                if (rc == HJR_OK && as.active_tiles == 0) break;
+            }
+        }
+        if (rc != HJR_OK) break;
+        std::string note = ends.size() > 1 ? ", " + std::to_string(n_done) + " sample passes" : "";
+        if (adaptive && ends.size() > 1)
+            note += ", adaptive: " + std::to_string(as.active_tiles) + " of " + std::to_string(as.owned_tiles) + " tiles active at " + std::to_string(as.sample_end) + " spp, " +
+                    std::to_string(as.samples_rendered) + " samples rendered";
+        fprintf(stderr, "[henjou] frame %u: %ux%u, %u spp, kernel %.3f ms (%.2f Msamples/s)%s\n", frame, p.width, p.height, p.spp,
+                kernel_ms, kernel_ms > 0 ? (double)p.width * p.height * p.spp / (kernel_ms * 1e3) : 0.0, note.c_str());
+        std::string str_frame = std::to_string(frame); // renderer.h:1291-1302
+        if (str_frame.size() < 2) str_frame = "00" + str_frame;
+        else if (str_frame.size() < 3) str_frame = "0" + str_frame;
+        sl.name = std::string(opt.image_name) + "_" + str_frame + ".png";
+        n_frames++;
+        if (serial_io) { rc = write_slot(sl); if (rc != HJR_OK) set_error(write_err); if (rc == HJR_OK && frame + 1 < opt.end_frame) prepare(frame + 1); }
+        else {
+            { std::lock_guard<std::mutex> lk(mu); sl.full = true; }
+            cv.notify_all();
+            cur ^= 1;
+        }
+    }
+    if (prep.joinable()) prep.join();
+    if (!serial_io) {
+        { // drain: the writer takes the slots in order, then quits
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return !slots[0].full && !slots[1].full; });
+            quit = true;
+        }
+        cv.notify_all();
+        writer.join();
+        if (rc == HJR_OK && write_rc != HJR_OK) { rc = write_rc; set_error(write_err); }
+    }
+    if (n_frames) {
+        const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all0).count();
+        fprintf(stderr, "[henjou] %u frame(s) in %.3f s wall (%.1f ms per frame incl. scene update, download and PNG output)\n", n_frames, wall, 1e3 * wall / n_frames);
+    }
+    hjr_destroy(ctx);
+    hjr_scene_free(scene);
+    return rc;
+}

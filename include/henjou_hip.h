@@ -29,7 +29,7 @@ extern "C" {
 #define HJR_ERR_STATE (-5)   /* call order violated (render before upload, ...) */
 
 /* ---- Sized structs (the rule that keeps callers and library binary-compatible across releases) --------------------------------
- * hjr_scene_view, hjr_render_option, hjr_params and hjr_stats may GROW at their end in later releases.  Each starts with
+ * hjr_scene_view, hjr_render_option, hjr_params, hjr_stats, hjr_adaptive and hjr_adaptive_state may GROW at their end in later releases.  Each starts with
  * `struct_size`: the CALLER sets it to sizeof(its own struct) before handing the struct to ANY entry point, input or output
  * (HJR_INIT does it together with the zero fill).  The library copies min(struct_size, its own sizeof) bytes in either direction:
  *   - a field the caller's (older, shorter) struct does not have is never written and reads as 0, which selects the default;
@@ -141,6 +141,10 @@ typedef struct hjr_render_option {
     int32_t device_bvh_opt;      /* default 0; 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt") */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
+    float noise_threshold;       /* default 0 (off); > 0: hjr_render_file / henjou_cli set hjr_adaptive.noise_threshold, render each frame in
+                                  * `passes` sample passes (8 when the file has no "passes" key), stop when no tile is active and write the
+                                  * PNG from the last pass ("noise_threshold") */
+    uint32_t min_samples;        /* default 0 = two granules: hjr_adaptive.min_samples ("min_samples") */
 } hjr_render_option;
 
 typedef struct hjr_camera {      /* Params.camera_* (renderer/renderer.h:1187-1191) */
@@ -193,6 +197,35 @@ typedef struct hjr_params {
                                   * (exact) kernels: they agree within the metric's tolerance (per-pixel RMSE < 1e-3 at 1024 spp; tests/test_gpu_fast_math.py).
                                   * Megakernel family only (NEE and Pathtrace); ignored by HJR_FLAG_STATS launches and by MIS launches, whose exact wavefront
                                   * kernels are faster than an approximate megakernel would be (hjr_stats.fast_math tells what ran). */
+
+/* ---- Adaptive sampling: stop converged 8x8 tiles between the sample passes of a frame ---------------------------
+ * A setting of the context (like the LUT and the sky), off by default.  It acts on sample passes only: a whole-frame render (sample_end == 0,
+ * or [0, spp)) ignores it and is the launch it always was, bit for bit.  With it on, a pass renders only the tiles still ACTIVE; after a pass
+ * that ends at n = sample_end with n < spp, n >= min_samples and m = n / hjr_sample_granule(spp) >= 2, every active tile is judged from the
+ * spread of its pixels' chunk sums.  Per owned pixel two fp32 statistics over the chunk colour sums c received so far, in chunk order from
+ * +0.0f, no contraction:   y = (c.x + c.y) + c.z ;  S1 = S1 + y ;  S2 = S2 + y * y.   Then, all fp32 as written (m, n converted to float):
+ *     q = max(m * S2 - S1 * S1, 0.0f) ;   e = sqrt(q / (m - 1.0f)) / (S1 + HJR_ADAPTIVE_EPS * n)
+ * (the standard error of the pixel's sum relative to the sum; pixels of an edge tile outside the image have e = 0), the tile's 64 e are
+ * added by the xor butterfly v = v + v[lane ^ k], k = 32, 16, 8, 4, 2, 1, and the tile STOPS iff v <= noise_threshold * 64.0f, i.e. its mean
+ * relative error is at most the threshold.  A stopped tile never restarts within the frame and keeps n_tile = that sample_end; every pass
+ * still writes every owned pixel of every AOV: running sum * (1.0f / (float)n_tile) for a stopped tile, * (1.0f / (float)sample_end)
+ * otherwise.  The rule is plain IEEE arithmetic in a fixed order: the result does not depend on rank, GPU count, kernel family or layout.
+ * The cancellation in m * S2 - S1 * S1 costs about 1e-7 of S1 * S1, so thresholds below about 1e-3 are accepted but resolve nothing.
+ * The next pass needs the number of active tiles to size its launch: an adaptive pass with sample_begin > 0 WAITS on the host for the
+ * previous pass of its frame (4 bytes read back).  A pass with no active tile launches no render kernel and still writes the AOVs. */
+#define HJR_ADAPTIVE_EPS 1e-3f   /* keeps a black pixel at e = 0 */
+typedef struct hjr_adaptive {
+    uint32_t struct_size;        /* sizeof(hjr_adaptive) of the caller (HJR_INIT) */
+    float noise_threshold;       /* finite, >= 0; 0 = off */
+    uint32_t min_samples;        /* no decision before this many samples; 0 = two granules, other values are rounded up to a granule */
+} hjr_adaptive;
+typedef struct hjr_adaptive_state {
+    uint32_t struct_size;        /* sizeof(hjr_adaptive_state) of the caller (HJR_INIT) */
+    uint32_t owned_tiles;        /* tiles of this rank */
+    uint32_t active_tiles;       /* of them, not stopped after the last pass (the caller stops the frame at 0; the last AOVs are the frame) */
+    uint32_t sample_end;         /* where the last pass ended */
+    uint64_t samples_rendered;   /* 64 x the sum over the owned tiles of the samples each has received (whole tiles, edge tiles included) */
+} hjr_adaptive_state;
 
 typedef struct hjr_stats {
     uint32_t struct_size;        /* sizeof(hjr_stats) of the caller (HJR_INIT) */
@@ -268,6 +301,17 @@ int hjr_render(hjr_ctx*, const hjr_params*, float* aov_color, float* aov_albedo,
 int hjr_render_device(hjr_ctx*, const hjr_params*, void* d_aov_color, void* d_aov_albedo, void* d_aov_normal,
                       void* hip_stream);
 int hjr_synchronize(hjr_ctx*);
+/* Adaptive sampling of sample passes (above).  NULL or noise_threshold == 0 switches it off (the default).  noise_threshold must be finite
+ * and >= 0, else HJR_ERR_ARG.  The call ends an unfinished progressive frame, as hjr_set_sky does, so a frame cannot change its rule half
+ * way: a continuing pass after it is refused with HJR_ERR_STATE before anything is enqueued or written.  No reference counterpart (its
+ * budget is max_spp under a time limit). */
+int hjr_set_adaptive(hjr_ctx*, const hjr_adaptive*);
+/* The context's progressive adaptive frame after its last pass so far; synchronous (waits for that pass).  HJR_ERR_STATE when the last
+ * render was not an adaptive sample pass. */
+int hjr_get_adaptive_state(hjr_ctx*, hjr_adaptive_state* out);
+/* n_tile per owned tile of that frame (the samples the tile has received: where it stopped, else where the last pass ended);
+ * n_owned_tiles must be hjr_adaptive_state.owned_tiles.  Synchronous. */
+int hjr_copy_tile_samples(hjr_ctx*, uint32_t* dst, size_t n_owned_tiles);
 /* ---- pixel-tile shard helpers (no reference counterpart: the reference is single-GPU, renderer.h:1077-1078) ----
  * Tiles are 8x8 pixels; tile (tx, ty) has id t = ty * tiles_x + (tx + ty) % tiles_x (row ty of tiles rotated by ty places, so that a
  * rank's tiles run along diagonals instead of forming vertical stripes when tiles_x is a multiple of world_size); tile t belongs to
@@ -334,7 +378,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *                                 ignores it                                                                                   [*]
  *   [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
- * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.
+ * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
+ * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
