@@ -20,6 +20,7 @@ ASSETS = os.path.join(PKG_DIR, "assets")
 INTEGRATOR_NEE, INTEGRATOR_PT, INTEGRATOR_MIS = 0, 1, 2
 MODE_DEFAULT, MODE_DENOISE, MODE_DENOISE_UPSCALE2X, MODE_DEBUG = 0, 1, 2, 3  # render_option.h:38-43
 FLAG_STATS, FLAG_ZERO_UNOWNED, FLAG_PACKED, FLAG_FAST_MATH = 1, 2, 4, 8
+VARIANCE_UNKNOWN = np.float32(1e30)  # HJR_VARIANCE_UNKNOWN: fewer than two full chunks behind a pixel of the variance AOV
 FRAME_NODES, FRAME_TRI_GEOM, FRAME_TRI_SHADE, FRAME_LIGHTS = 0, 1, 2, 3  # hjr_copy_frame_data
 
 
@@ -79,7 +80,7 @@ class RenderOption(_Sized):
                 ("LUT_path", C.c_char * 512), ("seed", C.c_uint32), ("integrator", C.c_int32),
                 ("devices", C.c_uint32), ("tile", C.c_uint32), ("serial_io", C.c_int32), ("fast_math", C.c_int32), ("force_rebuild", C.c_int32),
                 ("device_bvh", C.c_int32), ("device_bvh_opt", C.c_int32), ("passes", C.c_uint32),
-                ("noise_threshold", C.c_float), ("min_samples", C.c_uint32)]
+                ("noise_threshold", C.c_float), ("min_samples", C.c_uint32), ("denoise_variance", C.c_int32)]
 
 
 class Camera(C.Structure):
@@ -172,6 +173,11 @@ def lib():
             "hjr_set_lut": [C.c_void_p, C.c_void_p, C.c_int, C.c_int],
             "hjr_render": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_render_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_render_var": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_render_device_var": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_denoise_var": [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
+            "hjr_denoise_var_device": [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                       C.c_void_p],
             "hjr_synchronize": [C.c_void_p],
             "hjr_get_stats": [C.c_void_p, C.c_void_p],
             "hjr_preview_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
@@ -414,27 +420,32 @@ class Device:
         a = np.ascontiguousarray(rgba32f, dtype=np.float32)
         _check(lib().hjr_set_sky(self._h, a.ctypes.data, a.shape[1], a.shape[0]), "hjr_set_sky")
 
-    def render(self, params, want_aovs=True):
-        """Synchronous render into host arrays (hjr_render)."""
+    def render(self, params, want_aovs=True, want_variance=False):
+        """Synchronous render into host arrays (hjr_render); want_variance: hjr_render_var, and the variance AOV (float32 [h, w]) is
+        returned as a fourth array."""
         shp = (params.height, params.width, 4)
         color = np.zeros(shp, dtype=np.float32)
         albedo = np.zeros(shp, dtype=np.float32) if want_aovs else None
         normal = np.zeros(shp, dtype=np.float32) if want_aovs else None
+        if want_variance:
+            variance = np.zeros(shp[:2], dtype=np.float32)
+            _check(lib().hjr_render_var(self._h, C.byref(params), color.ctypes.data, albedo.ctypes.data if want_aovs else None,
+                                        normal.ctypes.data if want_aovs else None, variance.ctypes.data), "hjr_render_var")
+            return color, albedo, normal, variance
         _check(lib().hjr_render(self._h, C.byref(params), color.ctypes.data,
                                 albedo.ctypes.data if want_aovs else None, normal.ctypes.data if want_aovs else None), "hjr_render")
         return color, albedo, normal
 
-    def render_progressive(self, params, passes, want_aovs=True):
+    def render_progressive(self, params, passes, want_aovs=True, want_variance=False):
         """Renders the frame of `params` in `passes` sample passes (hjr_params.sample_begin / sample_end, split by pass_bounds) and yields
         (sample_end, color, albedo, normal) after each: the running mean over samples [0, sample_end).  The last one is the one-shot frame,
-        bit for bit.  `params` itself is not modified."""
+        bit for bit.  `params` itself is not modified.  want_variance: the variance AOV of each pass is yielded as a fifth item."""
         for begin, end in pass_bounds(params.spp, passes):
             p = ParamsV2()
             C.memmove(C.addressof(p), C.addressof(params), min(C.sizeof(params), C.sizeof(p)))
             p.struct_size = C.sizeof(p)
             p.sample_begin, p.sample_end = begin, end
-            color, albedo, normal = self.render(p, want_aovs)
-            yield end, color, albedo, normal
+            yield (end,) + tuple(self.render(p, want_aovs, want_variance))
 
     def set_adaptive(self, noise_threshold, min_samples=0):
         """hjr_set_adaptive: converged 8x8 tiles stop between the sample passes of a frame (mean relative error of the tile's pixels at
@@ -455,28 +466,42 @@ class Device:
         _check(lib().hjr_copy_tile_samples(self._h, out.ctypes.data, out.size), "hjr_copy_tile_samples")
         return out
 
-    def render_adaptive(self, params, passes, want_aovs=True):
+    def render_adaptive(self, params, passes, want_aovs=True, want_variance=False):
         """render_progressive for a context with set_adaptive on: yields (sample_end, color, albedo, normal) after each pass and ends with
         the first pass that leaves no tile active (or at spp); the last AOVs yielded are the frame."""
-        for out in self.render_progressive(params, passes, want_aovs):
+        for out in self.render_progressive(params, passes, want_aovs, want_variance):
             yield out
             if out[0] < params.spp and self.adaptive_state()["active_tiles"] == 0:
                 return
 
-    def render_device(self, params, d_color, d_albedo=None, d_normal=None, stream=None):
-        """Asynchronous render into device pointers (ints, e.g. torch tensor .data_ptr()) on a hipStream_t (int)."""
+    def render_device(self, params, d_color, d_albedo=None, d_normal=None, stream=None, d_variance=None):
+        """Asynchronous render into device pointers (ints, e.g. torch tensor .data_ptr()) on a hipStream_t (int); d_variance: one float
+        per pixel (hjr_render_device_var)."""
+        if d_variance:
+            _check(lib().hjr_render_device_var(self._h, C.byref(params), C.c_void_p(d_color), C.c_void_p(d_albedo) if d_albedo else None,
+                                               C.c_void_p(d_normal) if d_normal else None, C.c_void_p(d_variance),
+                                               C.c_void_p(stream) if stream else None), "hjr_render_device_var")
+            return
         _check(lib().hjr_render_device(self._h, C.byref(params), C.c_void_p(d_color),
                                        C.c_void_p(d_albedo) if d_albedo else None, C.c_void_p(d_normal) if d_normal else None,
                                        C.c_void_p(stream) if stream else None), "hjr_render_device")
 
-    def denoise(self, mode, color, albedo=None, normal=None):
-        """OptixDenoiserManager::denoise() replacement on host float4 images (hjr_denoise); returns AOV_Output."""
+    def denoise(self, mode, color, albedo=None, normal=None, variance=None):
+        """OptixDenoiserManager::denoise() replacement on host float4 images (hjr_denoise); returns AOV_Output.  With `variance`
+        (float32 [h, w], the variance AOV) the variance-guided filter runs instead (hjr_denoise_var)."""
         color = np.ascontiguousarray(color, dtype=np.float32)
         h, w = color.shape[:2]
         ow, oh = (2 * w, 2 * h) if mode == MODE_DENOISE_UPSCALE2X else (w, h)
         a = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32)
         n = None if normal is None else np.ascontiguousarray(normal, dtype=np.float32)
         out = np.zeros((oh, ow, 4), dtype=np.float32)
+        if variance is not None:
+            v = np.ascontiguousarray(variance, dtype=np.float32)
+            if v.shape != (h, w):
+                raise ValueError("variance must be [height, width]")
+            _check(lib().hjr_denoise_var(self._h, mode, w, h, color.ctypes.data, None if a is None else a.ctypes.data,
+                                         None if n is None else n.ctypes.data, v.ctypes.data, out.ctypes.data, ow, oh), "hjr_denoise_var")
+            return out
         _check(lib().hjr_denoise(self._h, mode, w, h, color.ctypes.data, None if a is None else a.ctypes.data,
                                  None if n is None else n.ctypes.data, out.ctypes.data, ow, oh), "hjr_denoise")
         return out

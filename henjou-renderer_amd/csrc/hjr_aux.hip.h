@@ -239,6 +239,167 @@ __global__ void __launch_bounds__(256) hjr_accumulate_adaptive_kernel(const KPar
     }
 }
 
+// ---- variance AOV (hjr_render_var, DESIGN.md §4 rule 7): variants of the three streaming kernels above that also carry the per-pixel
+// statistic (S1, S2) over y = (c.x + c.y) + c.z of the FULL chunks' colour sums, in chunk order from +0.0f, and store one float per owned
+// pixel.  Launched only when a variance pointer was given: without one the kernels above run, untouched.  The colour / albedo / normal
+// expressions are the ones above, so those AOVs keep their bits.  Chunk k is full iff (k + 1) * chunk_spp <= spp; the partial last chunk
+// goes into the colour and stays out of the statistic.
+__device__ inline float hjr_variance_of_mean(float S1, float S2, uint32_t m_chunks, uint32_t granule, uint32_t n_samples)
+{
+    if (m_chunks < 2u) return HJR_VARIANCE_UNKNOWN;
+    const float m = (float)m_chunks;
+    const float q = fmaxf(m * S2 - S1 * S1, 0.0f);
+    return (q / (m * (m - 1.0f))) / ((float)granule * (float)n_samples);
+}
+// frames of a single chunk (no chunk sums exist: the render kernel wrote the means itself): every owned pixel is UNKNOWN
+__global__ void __launch_bounds__(256) hjr_fill_var_kernel(const KParams P, float* __restrict__ aov_var)
+{
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
+        uint32_t tx, ty;
+        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
+        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+        if (x >= P.width || y >= P.height) continue;
+        aov_var[P.packed ? sl : (size_t)y * P.width + x] = HJR_VARIANCE_UNKNOWN;
+    }
+}
+// hjr_finalize_kernel + the statistic: one more float store per pixel, no more loads
+__global__ void __launch_bounds__(256) hjr_finalize_var_kernel(const KParams P, float* __restrict__ aov_var)
+{
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    const float inv_spp = 1.0f / (float)P.spp;
+    const uint32_t n_full = P.spp / P.chunk_spp;
+    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
+        uint32_t tx, ty;
+        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
+        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+        if (x >= P.width || y >= P.height) continue;
+        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
+        float s1 = 0.0f, s2 = 0.0f;
+        for (uint32_t k = 0; k < P.n_chunks; k++) {
+            const float4 v = P.part_color[(size_t)k * n_slots + sl];
+            a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
+            if (k < n_full) { const float yk = (v.x + v.y) + v.z; s1 = s1 + yk; s2 = s2 + yk * yk; }
+            if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
+            if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
+        }
+        P.aov_color[pix] = make_float4(a.x * inv_spp, a.y * inv_spp, a.z * inv_spp, 1.0f);
+        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv_spp, b.y * inv_spp, b.z * inv_spp, 1.0f);
+        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv_spp, c.y * inv_spp, c.z * inv_spp, 1.0f);
+        aov_var[pix] = hjr_variance_of_mean(s1, s2, n_full, P.chunk_spp, P.spp);
+    }
+}
+// hjr_accumulate_kernel + the statistic, kept per owned pixel between the passes of the frame in var_stat ([owned tile][64] float2, like
+// ad_stat): 8 more bytes loaded and stored per pixel.  The mean is over n = sample_end samples, of m = sample_end / chunk_spp full chunks.
+__global__ void __launch_bounds__(256) hjr_accumulate_var_kernel(const KParams P, float2* __restrict__ var_stat, float* __restrict__ aov_var)
+{
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    const float inv_end = 1.0f / (float)P.sample_end;
+    const uint32_t n_full = P.spp / P.chunk_spp;
+    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
+        uint32_t tx, ty;
+        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
+        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+        if (x >= P.width || y >= P.height) continue;
+        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
+        float2 s = make_float2(0.0f, 0.0f);
+        if (P.run_load) {
+            a = P.run_color[sl];
+            if (P.aov_albedo) b = P.run_albedo[sl];
+            if (P.aov_normal) c = P.run_normal[sl];
+            s = var_stat[sl];
+        }
+        for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
+            const float4 v = P.part_color[(size_t)k * n_slots + sl];
+            a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
+            if (k < n_full) { const float yk = (v.x + v.y) + v.z; s.x = s.x + yk; s.y = s.y + yk * yk; }
+            if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
+            if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
+        }
+        if (P.run_store) {
+            P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
+            if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
+            if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
+            var_stat[sl] = s;
+        }
+        P.aov_color[pix] = make_float4(a.x * inv_end, a.y * inv_end, a.z * inv_end, 1.0f);
+        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv_end, b.y * inv_end, b.z * inv_end, 1.0f);
+        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv_end, c.y * inv_end, c.z * inv_end, 1.0f);
+        aov_var[pix] = hjr_variance_of_mean(s.x, s.y, P.sample_end / P.chunk_spp, P.chunk_spp, P.sample_end);
+    }
+}
+// hjr_accumulate_adaptive_kernel + the variance store, from the ad_stat it keeps.  The statistic `s` of the stop decision is the kernel's
+// above, partial last chunk of the frame's final pass included (no decision follows that pass and ad_stat is not stored after it); the
+// variance uses `f`, the same sums over full chunks only.  A stopped tile keeps its statistic, so its variance (over n_tile samples, of
+// n_tile / chunk_spp chunks) stays put on later passes.
+__global__ void __launch_bounds__(256) hjr_accumulate_adaptive_var_kernel(const KParams P, float* __restrict__ aov_var)
+{
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    const uint32_t n_full = P.spp / P.chunk_spp;
+    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t otile = (uint32_t)(sl >> 6);
+        const uint32_t tile = otile * P.world + P.rank;
+        uint32_t tx, ty;
+        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
+        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+        const bool inside = x < P.width && y < P.height;
+        uint32_t n_tile = P.run_load ? P.ad_state[otile] : 0u; // (wave-uniform) 0: the tile is active
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
+        float2 s = make_float2(0.0f, 0.0f);
+        if (inside && P.run_load) {
+            a = P.run_color[sl];
+            if (P.aov_albedo) b = P.run_albedo[sl];
+            if (P.aov_normal) c = P.run_normal[sl];
+            s = P.ad_stat[sl];
+        }
+        float2 f = s;
+        if (n_tile == 0u) {
+            if (inside) {
+                for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
+                    const float4 v = P.part_color[(size_t)k * n_slots + sl];
+                    a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
+                    const float yk = (v.x + v.y) + v.z;
+                    s.x = s.x + yk; s.y = s.y + yk * yk;
+                    if (k < n_full) f = s;
+                    if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
+                    if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
+                }
+                if (P.run_store) {
+                    P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
+                    if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
+                    if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
+                    P.ad_stat[sl] = s;
+                }
+            }
+            if (P.ad_decide) { // (wave-uniform branch: all 64 lanes take the butterfly)
+                const float n = (float)P.sample_end, m = (float)(P.sample_end / P.chunk_spp);
+                const float q = fmaxf(m * s.y - s.x * s.x, 0.0f);
+                const float e = sqrtf(q / (m - 1.0f)) / (s.x + HJR_ADAPTIVE_EPS * n);
+                float v = inside ? e : 0.0f;
+                for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
+                if (v <= P.ad_threshold * 64.0f) n_tile = P.sample_end;
+            }
+            if ((threadIdx.x & 63u) == 0u) {
+                P.ad_state[otile] = n_tile;
+                if (n_tile == 0u) atomicAdd(&P.ad_state[P.n_owned_tiles], 1u);
+            }
+        }
+        if (!inside) continue; // (after the butterfly)
+        const uint32_t n_mean = n_tile ? n_tile : P.sample_end;
+        const float inv = 1.0f / (float)n_mean;
+        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
+        P.aov_color[pix] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
+        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv, b.y * inv, b.z * inv, 1.0f);
+        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv, c.y * inv, c.z * inv, 1.0f);
+        aov_var[pix] = hjr_variance_of_mean(f.x, f.y, n_mean / P.chunk_spp, P.chunk_spp, n_mean);
+    }
+}
+
 // The launch's tile list without the stopped tiles: a STABLE compaction of ad_src (the cost order hjr_order_tiles_kernel /
 // hjr_cost_scatter_kernel just produced, or the plain round-robin order when there is none), so the expensive-first order survives and the
 // result is the same for the same input.  At most 129 600 tiles (4K): one workgroup walks the list in steps of 1024 with a ballot per wave

@@ -17,10 +17,32 @@
 //   at 64 spp (light sources and background excluded).
 // Streaming kernels, one lane per pixel: 75 float4 reads per pixel and pass (mostly L2 hits), bound by HBM/L2 bandwidth;
 // < 1 % of a frame's render time.
+//
+// The VARIANCE-GUIDED variant (hjr_denoise_var, option "denoise_variance"): the spatial half of SVGF (Schied et al., HPG 2017) on the
+// same guides.  The filter above has a floor (0.15 in the numbers above): its colour tolerance follows the radiance level, not how noisy
+// the pixel still is, so its bias stays when the noise is gone.  Here the tolerance is the pixel's own standard deviation, from the
+// variance AOV (hjr_render_var, DESIGN.md §4 rule 7), so the filter fades out as the frame converges.  Specified to the bit like the
+// filter above; everything not named is as above (taps, clamping, h, wn, wa, n_phi, a_phi, the p_exp / max(., -87) / min(., 1) form,
+// fp32 as written, no contraction):
+//   two images ping-pong through the 5 passes (step 1, 2, 4, 8, 16): colour C (float4) and variance V (float, one per pixel); the input
+//   variance is clamped once, as pass 0 reads it: V = fminf(fmaxf(V, 0.0f), 1e30f) (NaN and negative values act as 0);
+//   per pass and centre pixel, the prefiltered variance: a 3 x 3 Gaussian of the pass's input V at distance 1 WHATEVER the step,
+//     k3 = (0.25, 0.5, 0.25), rows outer, clamped to the frame:  gv = gv + V_t * (k3[j] * k3[i])  from +0.0f;  sd = sqrtf(gv);
+//   colour weight, in ALL five passes:  l = (c.x + c.y) + c.z;  den = sigma_l * sd + eps;
+//     wc = min(p_exp(max(-fabsf(l_c - l_t) / den, -87)), 1)   with sigma_l = 4 (the published value), eps = 1e-3;
+//   w = ((wc * wn) * wa) * (h[dy] * h[dx]);   sums from +0.0f in tap order:  s = s + tap.rgb * w;  cum = cum + w;  sv = sv + V_t * (w * w);
+//   C_out.rgb = s / cum, C_out.a = centre.a;   V_out = sv / (cum * cum)   (the variance of the weighted mean of independent taps).
+// HJR_VARIANCE_UNKNOWN (1e30) needs no special case: sd is about 1e15, wc = 1, the filter weighs by the guides only, and no term
+// overflows (V_t * w * w <= 1e30 * 0.02, 25 of them; cum >= the centre's 0.375 * 0.375).
+// One more float per tap than the filter above (52 instead of 48 bytes) plus the 9 floats of the prefilter per pixel: 0.80 ms against
+// 0.75 ms at 1080p.  On the bundled scene (96 x 64, box filling the frame, against a 16384 spp frame): RMSE 0.034 / 0.032 / 0.029 / 0.026
+// at 16 / 64 / 256 / 1024 spp where the filter above stays at 0.059 / 0.057 / 0.056 / 0.056.
 #pragma once
 #include "hjr_math.hip.h"
 
 #define HJR_ATROUS_PASSES 5
+#define HJR_DENOISE_SIGMA_L 4.0f
+#define HJR_DENOISE_VAR_EPS 1e-3f
 
 __global__ void __launch_bounds__(256) hjr_atrous_kernel(const float4* __restrict__ in, const float4* __restrict__ normal,
                                                           const float4* __restrict__ albedo, float4* __restrict__ out,
@@ -57,6 +79,57 @@ __global__ void __launch_bounds__(256) hjr_atrous_kernel(const float4* __restric
         }
     }
     out[c] = make_float4(sx / cum, sy / cum, sz / cum, c0.w);
+}
+
+// one pass of the variance-guided variant (header above); `clamp_in`: pass 0 clamps the variance as it reads it
+__global__ void __launch_bounds__(256) hjr_atrous_var_kernel(const float4* __restrict__ in, const float* __restrict__ vin, const float4* __restrict__ normal,
+                                                              const float4* __restrict__ albedo, float4* __restrict__ out, float* __restrict__ vout,
+                                                              int W, int H, int step, int clamp_in)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const float hk[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float k3[3] = { 0.25f, 0.5f, 0.25f };
+    const float n_phi = 0.25f, a_phi = 0.05f;
+    const size_t c = (size_t)y * W + x;
+    const float4 c0 = in[c], n0 = normal[c], a0 = albedo[c];
+    const float l0 = (c0.x + c0.y) + c0.z;
+    float gv = 0.0f;
+    for (int j = -1; j <= 1; j++) {
+        const int yy = min(max(y + j, 0), H - 1);
+        for (int i = -1; i <= 1; i++) {
+            const int xx = min(max(x + i, 0), W - 1);
+            float vt = vin[(size_t)yy * W + xx];
+            if (clamp_in) vt = fminf(fmaxf(vt, 0.0f), 1e30f);
+            gv = gv + vt * (k3[j + 1] * k3[i + 1]);
+        }
+    }
+    const float den = HJR_DENOISE_SIGMA_L * sqrtf(gv) + HJR_DENOISE_VAR_EPS;
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f, cum = 0.0f, sv = 0.0f;
+    for (int j = -2; j <= 2; j++) {
+        const int yy = min(max(y + j * step, 0), H - 1);
+        for (int i = -2; i <= 2; i++) {
+            const int xx = min(max(x + i * step, 0), W - 1);
+            const size_t t = (size_t)yy * W + xx;
+            const float4 ct = in[t], nt = normal[t], at = albedo[t];
+            float vt = vin[t];
+            if (clamp_in) vt = fminf(fmaxf(vt, 0.0f), 1e30f);
+            const float lt = (ct.x + ct.y) + ct.z;
+            const float wc = fminf(p_exp(fmaxf(-fabsf(l0 - lt) / den, -87.0f)), 1.0f);
+            float dx = n0.x - nt.x, dy = n0.y - nt.y, dz = n0.z - nt.z;
+            float d2 = dx * dx + dy * dy + dz * dz;
+            const float wn = fminf(p_exp(fmaxf(-d2 / n_phi, -87.0f)), 1.0f);
+            dx = a0.x - at.x; dy = a0.y - at.y; dz = a0.z - at.z;
+            d2 = dx * dx + dy * dy + dz * dz;
+            const float wa = fminf(p_exp(fmaxf(-d2 / a_phi, -87.0f)), 1.0f);
+            const float w = ((wc * wn) * wa) * (hk[j + 2] * hk[i + 2]);
+            sx = sx + ct.x * w; sy = sy + ct.y * w; sz = sz + ct.z * w;
+            cum = cum + w;
+            sv = sv + vt * (w * w);
+        }
+    }
+    out[c] = make_float4(sx / cum, sy / cum, sz / cum, c0.w);
+    vout[c] = sv / (cum * cum);
 }
 
 // 2x bilinear upscale, pixel centres: source coordinate (X + 0.5) / 2 - 0.5, i.e. weights 0.75 / 0.25 towards the nearer texel,

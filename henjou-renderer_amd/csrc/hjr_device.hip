@@ -420,7 +420,7 @@ static LaunchPlan plan_launch(const hjr_ctx* c, const KParams& kp, uint64_t n_it
 struct PassRange {
     bool pass = false;         // a sample pass (else the whole frame, the one-shot launch sequence)
     uint32_t begin = 0, end = 0;
-    uint32_t aovs = 0;         // AOVs requested: bit 0 colour, 1 albedo, 2 normal
+    uint32_t aovs = 0;         // AOVs requested: bit 0 colour, 1 albedo, 2 normal, 3 variance
 };
 static const uint32_t PASS_FLAGS = HJR_FLAG_PACKED | HJR_FLAG_ZERO_UNOWNED | HJR_FLAG_FAST_MATH; // the flags that change pixels
 
@@ -677,13 +677,22 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
 }
 
 // sums of the sample chunks -> pixel means (a sample pass: -> running sums and running means)
-static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, const KParams& kp, hipStream_t st)
+// d_var: the variance AOV was requested (hjr_render_var): the variants that also carry S1, S2; a frame of a single chunk has no chunk sums
+// and gets the fill
+static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, const KParams& kp, float* d_var, hipStream_t st)
 {
-    if (g.n_chunks <= 1) return HJR_OK;
     const size_t n_slots = (size_t)g.owned * 64u;
     if (n_slots == 0) return HJR_OK;
     unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
-    if (g.pr.pass) hipLaunchKernelGGL(hjr_accumulate_kernel, dim3(fb), dim3(256), 0, st, kp);
+    if (g.n_chunks <= 1) {
+        if (!d_var) return HJR_OK;
+        hipLaunchKernelGGL(hjr_fill_var_kernel, dim3(fb), dim3(256), 0, st, kp, d_var);
+    } else if (d_var) {
+        if (g.pr.pass) {
+            if (!c->d_var_stat.reserve(n_slots * sizeof(float2))) { set_error("hjr_render: variance statistic allocation failed"); return HJR_ERR_DEVICE; }
+            hipLaunchKernelGGL(hjr_accumulate_var_kernel, dim3(fb), dim3(256), 0, st, kp, (float2*)c->d_var_stat.p, d_var);
+        } else hipLaunchKernelGGL(hjr_finalize_var_kernel, dim3(fb), dim3(256), 0, st, kp, d_var);
+    } else if (g.pr.pass) hipLaunchKernelGGL(hjr_accumulate_kernel, dim3(fb), dim3(256), 0, st, kp);
     else hipLaunchKernelGGL(hjr_finalize_kernel, dim3(fb), dim3(256), 0, st, kp);
     HIPCHK(hipGetLastError());
     return HJR_OK;
@@ -730,14 +739,15 @@ static int adaptive_filter(hjr_ctx* c, KParams& kp, hipStream_t st)
     return HJR_OK;
 }
 // ... instead of finalize_chunks: running sums, statistic, stop decisions, AOVs; then the count of tiles still active goes to the host
-static int adaptive_accumulate(hjr_ctx* c, const FrameGeom& g, const KParams& kp, hipStream_t st)
+static int adaptive_accumulate(hjr_ctx* c, const FrameGeom& g, const KParams& kp, float* d_var, hipStream_t st)
 {
     hjr_ctx::Adaptive& ad = c->ad;
     const size_t n_slots = (size_t)g.owned * 64u;
     uint32_t* const d_count = (uint32_t*)ad.state.p + g.owned;
     HIPCHK(hipMemsetAsync(d_count, 0, 4, st));
     const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
-    hipLaunchKernelGGL(hjr_accumulate_adaptive_kernel, dim3(fb), dim3(256), 0, st, kp);
+    if (d_var) hipLaunchKernelGGL(hjr_accumulate_adaptive_var_kernel, dim3(fb), dim3(256), 0, st, kp, d_var);
+    else hipLaunchKernelGGL(hjr_accumulate_adaptive_kernel, dim3(fb), dim3(256), 0, st, kp);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(ad.h_active, d_count, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(ad.ready, st));
@@ -745,7 +755,8 @@ static int adaptive_accumulate(hjr_ctx* c, const FrameGeom& g, const KParams& kp
 }
 
 // pr: check_pass of this call, made before the caller enqueued anything
-static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, hipStream_t st)
+// d_var: the variance AOV (one float per pixel) or null
+static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st)
 {
     FrameGeom g;
     KParams kp;
@@ -758,13 +769,15 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, voi
     if (adaptive && (rc = adaptive_items(c, g, active)) != HJR_OK) return rc;
     if ((rc = bind_params(c, p, g, d_color, d_albedo, d_normal, st, kp)) != HJR_OK) return rc;
     if (adaptive && (rc = adaptive_bind(c, p, g, kp)) != HJR_OK) return rc;
+    if (d_var && !(p->flags & HJR_FLAG_PACKED) && g.world > 1 && (p->flags & HJR_FLAG_ZERO_UNOWNED)) // like the other AOVs (bind_params)
+        HIPCHK(hipMemsetAsync(d_var, 0, (size_t)p->width * p->height * sizeof(float), st));
     HIPCHK(hipEventRecord(c->ev0, st));
     if (!adaptive || active > 0) { // (an adaptive pass with no active tile launches no render kernel and still writes the AOVs)
         if ((rc = order_tiles(c, p, g, kp, st)) != HJR_OK) return rc;
         if (adaptive && active < g.owned && (rc = adaptive_filter(c, kp, st)) != HJR_OK) return rc;
         if ((rc = launch_render(c, p, g, kp, st)) != HJR_OK) return rc;
     }
-    if ((rc = adaptive ? adaptive_accumulate(c, g, kp, st) : finalize_chunks(c, g, kp, st)) != HJR_OK) return rc;
+    if ((rc = adaptive ? adaptive_accumulate(c, g, kp, (float*)d_var, st) : finalize_chunks(c, g, kp, (float*)d_var, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
     if (pr.pass && c->opt.get(hjr::OPT_VERBOSE, 0))
@@ -892,20 +905,25 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
     return HJR_OK;
 }
 
-extern "C" int hjr_render_device(hjr_ctx* c, const hjr_params* p_user, void* d_color, void* d_albedo, void* d_normal, void* stream)
+extern "C" int hjr_render_device_var(hjr_ctx* c, const hjr_params* p_user, void* d_color, void* d_albedo, void* d_normal, void* d_variance, void* stream)
 {
     hjr_params params; // sized struct
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_device")) { if (!c) set_error("hjr_render_device: null context"); return HJR_ERR_ARG; }
     const hjr_params* p = &params;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     PassRange pr;
-    if (const int rc = check_pass(c, p, (d_color ? 1u : 0u) | (d_albedo ? 2u : 0u) | (d_normal ? 4u : 0u), pr)) return rc;
-    return render_impl(c, p, pr, d_color, d_albedo, d_normal, st);
+    if (const int rc = check_pass(c, p, (d_color ? 1u : 0u) | (d_albedo ? 2u : 0u) | (d_normal ? 4u : 0u) | (d_variance ? 8u : 0u), pr)) return rc;
+    return render_impl(c, p, pr, d_color, d_albedo, d_normal, d_variance, st);
+}
+extern "C" int hjr_render_device(hjr_ctx* c, const hjr_params* p_user, void* d_color, void* d_albedo, void* d_normal, void* stream)
+{
+    return hjr_render_device_var(c, p_user, d_color, d_albedo, d_normal, nullptr, stream);
 }
 
 // OptixDenoiserManager::denoise() replacement (csrc/hjr_denoise.hip.h), device buffers, asynchronous on `hip_stream`
-extern "C" int hjr_denoise_device(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
-                                  const void* d_normal, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream)
+// `with_var`: the variance-guided variant (hjr_denoise_var_device), which also needs d_variance in the two Denoise modes
+static int denoise_device_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
+                               const void* d_normal, bool with_var, const void* d_variance, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream)
 {
     if (!c || !d_color || !d_out) { set_error("hjr_denoise: null argument"); return HJR_ERR_ARG; }
     if (in_w == 0 || in_h == 0 || in_w > 16384 || in_h > 16384) { set_error("hjr_denoise: bad input size"); return HJR_ERR_ARG; }
@@ -914,6 +932,7 @@ extern "C" int hjr_denoise_device(hjr_ctx* c, int render_mode, uint32_t in_w, ui
     if (!up && (out_w != in_w || out_h != in_h)) { set_error("hjr_denoise: output size must equal the input size in this mode"); return HJR_ERR_ARG; }
     if (up && (out_w / 2u != in_w || out_h / 2u != in_h)) { set_error("hjr_denoise: DenoiseUpScale2X renders at (out_w / 2, out_h / 2)"); return HJR_ERR_ARG; }
     if (render_mode != HJR_MODE_DEFAULT && (!d_albedo || !d_normal)) { set_error("hjr_denoise: the albedo and normal guide AOVs are required"); return HJR_ERR_ARG; }
+    if (render_mode != HJR_MODE_DEFAULT && with_var && !d_variance) { set_error("hjr_denoise_var: the variance AOV is required"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const size_t in_bytes = (size_t)in_w * in_h * 16;
@@ -922,13 +941,21 @@ extern "C" int hjr_denoise_device(hjr_ctx* c, int render_mode, uint32_t in_w, ui
         return HJR_OK;
     }
     if (!c->d_dn_a.reserve(in_bytes) || !c->d_dn_b.reserve(in_bytes)) { set_error("hjr_denoise: allocation failed"); return HJR_ERR_DEVICE; }
+    if (with_var && (!c->d_dnv_a.reserve(in_bytes / 4) || !c->d_dnv_b.reserve(in_bytes / 4))) { set_error("hjr_denoise_var: allocation failed"); return HJR_ERR_DEVICE; }
     const dim3 block(256), grid((in_w + 63) / 64, (in_h + 3) / 4);
     const float4* src = (const float4*)d_color;
     float4* pp[2] = { (float4*)c->d_dn_a.p, (float4*)c->d_dn_b.p };
+    const float* vsrc = (const float*)d_variance;
+    float* vp[2] = { (float*)c->d_dnv_a.p, (float*)c->d_dnv_b.p };
     for (int it = 0; it < HJR_ATROUS_PASSES; it++) {
         float4* dst = (!up && it == HJR_ATROUS_PASSES - 1) ? (float4*)d_out : pp[it & 1];
-        hipLaunchKernelGGL(hjr_atrous_kernel, grid, block, 0, st, src, (const float4*)d_normal, (const float4*)d_albedo, dst, (int)in_w, (int)in_h,
-                           1 << it, it < 2 ? 0.0f : 1.0f / (float)(1 << (it - 2))); // colour term: off, off, 1, 0.5, 0.25
+        if (with_var) { // colour and variance ping-pong together; the colour term is on in all five passes
+            hipLaunchKernelGGL(hjr_atrous_var_kernel, grid, block, 0, st, src, vsrc, (const float4*)d_normal, (const float4*)d_albedo, dst, vp[it & 1], (int)in_w, (int)in_h,
+                               1 << it, it == 0 ? 1 : 0);
+            vsrc = vp[it & 1];
+        } else
+            hipLaunchKernelGGL(hjr_atrous_kernel, grid, block, 0, st, src, (const float4*)d_normal, (const float4*)d_albedo, dst, (int)in_w, (int)in_h,
+                               1 << it, it < 2 ? 0.0f : 1.0f / (float)(1 << (it - 2))); // colour term: off, off, 1, 0.5, 0.25
         src = dst;
     }
     if (up) {
@@ -939,9 +966,20 @@ extern "C" int hjr_denoise_device(hjr_ctx* c, int render_mode, uint32_t in_w, ui
     return HJR_OK;
 }
 
+extern "C" int hjr_denoise_device(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
+                                  const void* d_normal, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream)
+{
+    return denoise_device_impl(c, render_mode, in_w, in_h, d_color, d_albedo, d_normal, false, nullptr, d_out, out_w, out_h, hip_stream);
+}
+extern "C" int hjr_denoise_var_device(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
+                                      const void* d_normal, const void* d_variance, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream)
+{
+    return denoise_device_impl(c, render_mode, in_w, in_h, d_color, d_albedo, d_normal, true, d_variance, d_out, out_w, out_h, hip_stream);
+}
+
 // host-buffer form (what Renderer's frame loop does with AOV_Color / AOV_Albedo / AOV_Normal -> AOV_Output); synchronous
-extern "C" int hjr_denoise(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const float* color, const float* albedo, const float* normal,
-                           float* out, uint32_t out_w, uint32_t out_h)
+static int denoise_host_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const float* color, const float* albedo, const float* normal,
+                             bool with_var, const float* variance, float* out, uint32_t out_w, uint32_t out_h)
 {
     if (!c || !color || !out) { set_error("hjr_denoise: null argument"); return HJR_ERR_ARG; }
     if (in_w == 0 || in_h == 0 || out_w == 0 || out_h == 0) { set_error("hjr_denoise: empty image"); return HJR_ERR_ARG; }
@@ -954,12 +992,26 @@ extern "C" int hjr_denoise(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t 
     HIPCHK(hipMemcpyAsync(c->d_color.p, color, in_bytes, hipMemcpyHostToDevice, c->stream));
     if (albedo) HIPCHK(hipMemcpyAsync(c->d_albedo.p, albedo, in_bytes, hipMemcpyHostToDevice, c->stream));
     if (normal) HIPCHK(hipMemcpyAsync(c->d_normal.p, normal, in_bytes, hipMemcpyHostToDevice, c->stream));
-    const int rc = hjr_denoise_device(c, render_mode, in_w, in_h, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr,
-                                      c->d_dn_out.p, out_w, out_h, c->stream);
+    if (with_var && variance) {
+        if (!c->d_variance.reserve(in_bytes / 4)) { set_error("hjr_denoise_var: allocation failed"); return HJR_ERR_DEVICE; }
+        HIPCHK(hipMemcpyAsync(c->d_variance.p, variance, in_bytes / 4, hipMemcpyHostToDevice, c->stream));
+    }
+    const int rc = denoise_device_impl(c, render_mode, in_w, in_h, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr,
+                                       with_var, with_var && variance ? c->d_variance.p : nullptr, c->d_dn_out.p, out_w, out_h, c->stream);
     if (rc != HJR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return HJR_OK;
+}
+extern "C" int hjr_denoise(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const float* color, const float* albedo, const float* normal,
+                           float* out, uint32_t out_w, uint32_t out_h)
+{
+    return denoise_host_impl(c, render_mode, in_w, in_h, color, albedo, normal, false, nullptr, out, out_w, out_h);
+}
+extern "C" int hjr_denoise_var(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const float* color, const float* albedo, const float* normal,
+                               const float* variance, float* out, uint32_t out_w, uint32_t out_h)
+{
+    return denoise_host_impl(c, render_mode, in_w, in_h, color, albedo, normal, true, variance, out, out_w, out_h);
 }
 
 // One frame of Renderer's loop in a Denoise mode, on the device: optixLaunch -> denoise -> cpyGPUBufferToHost(AOV_Output)
@@ -974,18 +1026,23 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     const size_t in_bytes = (size_t)p->width * p->height * 16, out_bytes = (size_t)out_w * out_h * 16;
     if (in_bytes == 0 || out_bytes == 0) { set_error("hjr_render_denoised: empty image"); return HJR_ERR_ARG; }
     const bool guides = render_mode != HJR_MODE_DEFAULT;
+    const bool with_var = guides && c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0; // option "denoise_variance": the variance AOV and the variance-guided filter
     PassRange pr; // a sample pass: the running mean is filtered (a denoised preview; the last pass gives the one-shot call's image)
-    if (const int rc = check_pass(c, p, guides ? 7u : 1u, pr)) return rc;
+    if (const int rc = check_pass(c, p, (guides ? 7u : 1u) | (with_var ? 8u : 0u), pr)) return rc;
+    if (with_var) {
+        if (!c->d_variance.reserve(in_bytes / 4)) { set_error("hjr_render_denoised: allocation failed"); return HJR_ERR_DEVICE; }
+        HIPCHK(hipMemsetAsync(c->d_variance.p, 0, in_bytes / 4, c->stream));
+    }
     if (!c->d_color.reserve(in_bytes) || (guides && (!c->d_albedo.reserve(in_bytes) || !c->d_normal.reserve(in_bytes))) || !c->d_dn_out.reserve(out_bytes)) {
         set_error("hjr_render_denoised: allocation failed");
         return HJR_ERR_DEVICE;
     }
     HIPCHK(hipMemsetAsync(c->d_color.p, 0, in_bytes, c->stream));
     if (guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
-    int rc = render_impl(c, p, pr, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, c->stream);
+    int rc = render_impl(c, p, pr, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var ? c->d_variance.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
-    rc = hjr_denoise_device(c, render_mode, p->width, p->height, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr,
-                            c->d_dn_out.p, out_w, out_h, c->stream);
+    rc = denoise_device_impl(c, render_mode, p->width, p->height, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr,
+                             with_var, with_var ? c->d_variance.p : nullptr, c->d_dn_out.p, out_w, out_h, c->stream);
     if (rc != HJR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1066,7 +1123,7 @@ extern "C" int hjr_get_stats(hjr_ctx* c, hjr_stats* out)
     return hjr::abi_give(out, c->stats, "hjr_get_stats") ? HJR_OK : HJR_ERR_ARG; // sized struct: at most out->struct_size bytes are written
 }
 
-extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, float* albedo, float* normal)
+extern "C" int hjr_render_var(hjr_ctx* c, const hjr_params* p_user, float* color, float* albedo, float* normal, float* variance)
 {
     if (!c || !p_user || !color) { set_error("hjr_render: null argument"); return HJR_ERR_ARG; }
     hjr_params params; // sized struct
@@ -1079,7 +1136,7 @@ extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, fl
     if (p->rank >= (p->world_size ? p->world_size : 1u)) { set_error("hjr_render: rank >= world_size"); return HJR_ERR_ARG; }
     const size_t bytes = packed_out ? (size_t)hjr_owned_tiles(p->width, p->height, p->rank, p->world_size ? p->world_size : 1u) * 64u * 16u : (size_t)p->width * p->height * 16;
     PassRange pr;
-    if (const int rc = check_pass(c, p, 1u | (albedo ? 2u : 0u) | (normal ? 4u : 0u), pr)) return rc;
+    if (const int rc = check_pass(c, p, 1u | (albedo ? 2u : 0u) | (normal ? 4u : 0u) | (variance ? 8u : 0u), pr)) return rc;
     if (bytes == 0) { end_pass(c, p, pr); return HJR_OK; } // a rank without tiles
     DevBuf* bufs[3] = { &c->d_color, &c->d_albedo, &c->d_normal };
     float* host[3] = { color, albedo, normal };
@@ -1088,10 +1145,19 @@ extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, fl
         if (!bufs[i]->reserve(bytes)) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
         if (!packed_out) HIPCHK(hipMemsetAsync(bufs[i]->p, 0, bytes, c->stream));
     }
-    int rc = render_impl(c, p, pr, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr, c->stream);
+    if (variance) { // one float per pixel: a quarter of an AOV's bytes
+        if (!c->d_variance.reserve(bytes / 4)) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
+        if (!packed_out) HIPCHK(hipMemsetAsync(c->d_variance.p, 0, bytes / 4, c->stream));
+    }
+    int rc = render_impl(c, p, pr, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr, variance ? c->d_variance.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
     for (int i = 0; i < 3; i++)
         if (host[i]) HIPCHK(hipMemcpyAsync(host[i], bufs[i]->p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (variance) HIPCHK(hipMemcpyAsync(variance, c->d_variance.p, bytes / 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream)); // CUDA_SYNC_CHECK (renderer.h:1242)
     return HJR_OK;
+}
+extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, float* albedo, float* normal)
+{
+    return hjr_render_var(c, p_user, color, albedo, normal, nullptr);
 }

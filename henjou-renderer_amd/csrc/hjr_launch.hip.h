@@ -65,13 +65,17 @@ struct hjr_ctx {
     uint64_t cost_tag = 0; // (width, height, spp, rank, world, integrator) the costs belong to; 0 = none
     uint32_t cost_samples = 0; // samples per pixel of the launch that measured them (a whole frame or a sample pass)
     DevBuf d_dn_a, d_dn_b, d_dn_out; // denoise ping-pong / host-entry staging
+    // variance AOV (hjr_render_var) and variance-guided filter (hjr_denoise_var); nothing here is allocated before a call asks for a variance
+    DevBuf d_variance;         // staging for the host-buffer entry points, one float per pixel
+    DevBuf d_var_stat;         // per owned pixel (S1, S2) of a non-adaptive frame rendered in sample passes, [owned tile][64] float2 (like ad.stat)
+    DevBuf d_dnv_a, d_dnv_b;   // the filter's variance ping-pong, one float per pixel
     hjr_stats stats;
     bool event_pending = false;
     // Frame data generation: hjr_upload_scene, hjr_set_lut, hjr_set_sky and a commit that replaces the frame data bump it, so a frame
     // rendered in sample passes can tell that what it renders changed between two passes
     uint64_t frame_gen = 0;
     // The one frame of this context that is being rendered in sample passes (hjr_params.sample_begin / sample_end):
-    // the parameters of its first pass, the sample its next pass must start at, the AOVs it writes (bit 0 colour, 1 albedo, 2 normal)
+    // the parameters of its first pass, the sample its next pass must start at, the AOVs it writes (bit 0 colour, 1 albedo, 2 normal, 3 variance)
     // and the frame data generation it was started on
     struct PassSession {
         bool active = false;
@@ -95,7 +99,7 @@ struct hjr_ctx {
     void release_buffers()
     {
         for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
-                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &ad.stat, &ad.state, &ad.list })
+                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &d_variance, &d_var_stat, &d_dnv_a, &d_dnv_b, &ad.stat, &ad.state, &ad.list })
             b->release();
         if (ad.h_active) (void)hipHostFree(ad.h_active);
         if (ad.ready) (void)hipEventDestroy(ad.ready);

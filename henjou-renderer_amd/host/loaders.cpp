@@ -133,6 +133,7 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             o.fast_math = flag("fast_math") ? 1 : 0;
             o.force_rebuild = flag("force_rebuild") ? 1 : 0;
             o.device_bvh = flag("device_bvh") ? 1 : 0; // the frame data built on the device (option "device_bvh")
+            o.denoise_variance = flag("denoise_variance") ? 1 : 0; // the variance-guided filter in the Denoise modes (option "denoise_variance")
             // device_bvh_opt: treelet-restructuring rounds of the device build (option "device_bvh_opt")
             if (const Json* v = h->find("device_bvh_opt")) {
                 const double r = v->is_number() ? v->as_number() : -1.0;

@@ -59,6 +59,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (opt.force_rebuild) (void)hjr_set_option(ctx, "force_rebuild", 1);
     if (opt.device_bvh) (void)hjr_set_option(ctx, "device_bvh", 1);
     if (opt.device_bvh_opt) (void)hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt);
+    if (opt.denoise_variance && opt.render_mode != HJR_MODE_DEFAULT) (void)hjr_set_option(ctx, "denoise_variance", 1); // (Default mode has no filter)
     const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes
     rc = hjr_upload_scene(ctx, &view);
     if (rc == HJR_OK && adaptive) {

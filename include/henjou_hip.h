@@ -145,6 +145,8 @@ typedef struct hjr_render_option {
                                   * `passes` sample passes (8 when the file has no "passes" key), stop when no tile is active and write the
                                   * PNG from the last pass ("noise_threshold") */
     uint32_t min_samples;        /* default 0 = two granules: hjr_adaptive.min_samples ("min_samples") */
+    int32_t denoise_variance;    /* default 0; 1: hjr_render_file / henjou_cli set the context option "denoise_variance" (the variance-guided
+                                  * filter in Render_mode Denoise / DenoiseUpScale2X; ignored in Default) */
 } hjr_render_option;
 
 typedef struct hjr_camera {      /* Params.camera_* (renderer/renderer.h:1187-1191) */
@@ -227,6 +229,28 @@ typedef struct hjr_adaptive_state {
     uint64_t samples_rendered;   /* 64 x the sum over the owned tiles of the samples each has received (whole tiles, edge tiles included) */
 } hjr_adaptive_state;
 
+/* ---- Variance AOV: a per-pixel error estimate of the colour AOV (hjr_render_var / hjr_render_device_var; DESIGN.md §4 rule 7) ----------
+ * An optional fourth output, ONE float per pixel: row-major [height][width]; with HJR_FLAG_PACKED [owned tile][64]; pixels of tiles this
+ * rank does not own are untouched, or zeroed with HJR_FLAG_ZERO_UNOWNED, exactly like the colour AOV.  It is computed for every kind of
+ * frame (one-shot, sample pass, adaptive) by the streaming kernels after the render; no render kernel knows about it, and the other AOVs
+ * of a call with the variance pointer have the bits of the same call without it.  Definition, fp32 in the written order, no contraction,
+ * correctly rounded divide:
+ *     g = hjr_sample_granule(spp) ;  chunk k is FULL iff (k + 1) * g <= spp ;
+ *     per pixel, over the full chunks it has received, in chunk order from +0.0f, with c = the chunk's colour sum as stored:
+ *         y = (c.x + c.y) + c.z ;  S1 = S1 + y ;  S2 = S2 + y * y ;      m = the number of those chunks ;
+ *     n = the number of samples the written mean is over: spp for a one-shot frame, sample_end on a sample pass, n_tile for a stopped
+ *         adaptive tile (whose S1, S2, m are those it stopped with: its variance stays put on later passes) ;
+ *     m >= 2:  q = max(m * S2 - S1 * S1, 0.0f) ;  var = (q / (m * (m - 1.0f))) / ((float)g * (float)n)
+ *     m <  2:  var = HJR_VARIANCE_UNKNOWN
+ * (m, g, n converted to float).  This is the variance of the pixel's mean r + g + b, estimated from the spread of its chunk sums:
+ * q / (m (m - 1)) is the sample variance of the chunk sums, / g that of one sample's sum-of-channels scaled to a chunk, / n that of the
+ * mean.  The partial last chunk (spp not a multiple of g) is added to the colour as ever and left out of S1 / S2.  m < 2 covers every
+ * frame of a single chunk (at most 8 spp: there are no chunk sums at all) and the first one-granule pass of a progressive frame.  A
+ * progressive frame keeps S1, S2 per owned pixel between its passes (8 bytes per owned pixel; an adaptive frame uses the statistic it
+ * keeps anyway).  "The same set of AOVs on every pass" includes the variance: giving or dropping the pointer on a continuing pass is
+ * HJR_ERR_STATE and enqueues nothing. */
+#define HJR_VARIANCE_UNKNOWN 1e30f
+
 typedef struct hjr_stats {
     uint32_t struct_size;        /* sizeof(hjr_stats) of the caller (HJR_INIT) */
     uint32_t _pad0;
@@ -300,6 +324,11 @@ int hjr_render(hjr_ctx*, const hjr_params*, float* aov_color, float* aov_albedo,
  * through an RCCL collective), enqueued on `hip_stream` (hipStream_t as void*, NULL = default stream).  Asynchronous. */
 int hjr_render_device(hjr_ctx*, const hjr_params*, void* d_aov_color, void* d_aov_albedo, void* d_aov_normal,
                       void* hip_stream);
+/* hjr_render / hjr_render_device with the variance AOV (above): `aov_variance` is width*height floats (HJR_FLAG_PACKED: owned tiles x 64).
+ * A NULL variance pointer makes either call behave exactly like hjr_render / hjr_render_device.  No reference counterpart. */
+int hjr_render_var(hjr_ctx*, const hjr_params*, float* aov_color, float* aov_albedo, float* aov_normal, float* aov_variance);
+int hjr_render_device_var(hjr_ctx*, const hjr_params*, void* d_aov_color, void* d_aov_albedo, void* d_aov_normal, void* d_aov_variance,
+                          void* hip_stream);
 int hjr_synchronize(hjr_ctx*);
 /* Adaptive sampling of sample passes (above).  NULL or noise_threshold == 0 switches it off (the default).  noise_threshold must be finite
  * and >= 0, else HJR_ERR_ARG.  The call ends an unfinished progressive frame, as hjr_set_sky does, so a frame cannot change its rule half
@@ -334,11 +363,21 @@ int hjr_unpack_tiles_device(hjr_ctx*, const void* d_packed, uint32_t width, uint
 int hjr_denoise(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const float* aov_color, const float* aov_albedo,
                 const float* aov_normal, float* out, uint32_t out_w, uint32_t out_h);
 /* One frame of the loop in any render mode, kept on the device: launch at p->width x p->height (the caller halves it for
- * DenoiseUpScale2X, renderer.h:1096-1099), hjr_denoise_device, download of AOV_Output only (renderer.h:1229-1281).  Synchronous. */
+ * DenoiseUpScale2X, renderer.h:1096-1099), hjr_denoise_device (option "denoise_variance" 1: the variance AOV too and
+ * hjr_denoise_var_device), download of AOV_Output only (renderer.h:1229-1281).  Synchronous. */
 int hjr_render_denoised(hjr_ctx*, const hjr_params*, int render_mode, float* out, uint32_t out_w, uint32_t out_h);
 /* the same on device pointers (float4 images), asynchronous on `hip_stream` (NULL = the context's stream) */
 int hjr_denoise_device(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
                        const void* d_normal, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream);
+/* The variance-guided variant of the filter (the spatial half of SVGF, Schied et al. 2017; csrc/hjr_denoise.hip.h has the arithmetic to
+ * the bit): `aov_variance` is in_w*in_h floats, the variance AOV of hjr_render_var (or any per-pixel variance of the colour's r + g + b;
+ * NaN and negative values act as 0, HJR_VARIANCE_UNKNOWN as "no estimate": guides only).  The colour tolerance of a pixel is 4 standard
+ * deviations, so the filter fades out as the frame converges, where hjr_denoise keeps its bias.  Same modes, size rules and argument
+ * checks as hjr_denoise / hjr_denoise_device; the variance is required in the two Denoise modes; HJR_MODE_DEFAULT copies. */
+int hjr_denoise_var(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const float* aov_color, const float* aov_albedo,
+                    const float* aov_normal, const float* aov_variance, float* out, uint32_t out_w, uint32_t out_h);
+int hjr_denoise_var_device(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
+                           const void* d_normal, const void* d_variance, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream);
 /* The 8-bit preview buffer of the raygen program — `uchar4* image` of Params, allocated at renderer/renderer.h:1102 and bound at :1175, written
  * by the missing __raygen__rg and never read back by the host.  Build-defined: a float4 colour image on the device -> tonemapper of kernel/color.h
  * (HJR_TONEMAP_*) -> toSRGB + quantise (renderer.h:73-101) -> width*height RGBA8 on the device; asynchronous on `hip_stream` (NULL = the
@@ -376,10 +415,14 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *                                 (Karras & Aila 2013; 0 = the plain Morton tree, the default).  Same frames, a better tree: on a 1 M-triangle
  *                                 scene 1 round took the build from 5.5 to 10.4 ms and the render from 151 to 135 ms.  The host build
  *                                 ignores it                                                                                   [*]
+ *   "denoise_variance" 0 1        1: hjr_render_denoised renders the variance AOV along with the guides and runs the variance-guided filter
+ *                                 (hjr_denoise_var_device) in the two Denoise modes; a sample pass filters the running mean with the variance
+ *                                 over n = sample_end.  0 (default): today's call, bit for bit
  *   [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
+ * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
