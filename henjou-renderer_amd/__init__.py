@@ -139,6 +139,13 @@ class AdaptiveState(_Sized):
                 ("samples_rendered", C.c_uint64)]
 
 
+# hjr_ray / hjr_ray_result of the ray-batch test hook (hjr_trace_rays)
+RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("valid", "<u4")])
+RAY_RESULT_DTYPE = np.dtype([("occluded", "<u4"), ("prim", "<u4"), ("k", "<u4"), ("t", "<f4"), ("b1", "<f4"), ("b2", "<f4"),
+                             ("status", "<u4"), ("pad", "<u4")])
+TRACE_STANDALONE, TRACE_FUSED, TRACE_WAVEFRONT, TRACE_FAST_BUILD = 0, 1, 2, 0x100
+TRACE_STATUS_OK, TRACE_STATUS_ROUND_CAP, TRACE_STATUS_UNTRACED = 0, 1, 2
+
 _lib = None
 
 
@@ -198,6 +205,7 @@ def lib():
             "hjr_pack_tiles_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
             "hjr_unpack_tiles_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
             "hjr_selftest_stack16": [],
+            "hjr_trace_rays": [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_set_adaptive": [C.c_void_p, C.c_void_p],
             "hjr_get_adaptive_state": [C.c_void_p, C.c_void_p],
             "hjr_copy_tile_samples": [C.c_void_p, C.c_void_p, C.c_size_t],
@@ -540,6 +548,18 @@ class Device:
         if n.value:
             _check(lib().hjr_copy_frame_data(self._h, what, out.ctypes.data, n.value, C.byref(n)), "hjr_copy_frame_data")
         return out.reshape(-1, 4)
+
+    def trace_rays(self, path, shadow, closest):
+        """hjr_trace_rays (test hook): arrays of RAY_DTYPE, pair i = (shadow[i], closest[i]) -> array of RAY_RESULT_DTYPE.
+        path = TRACE_STANDALONE / TRACE_FUSED, optionally | TRACE_FAST_BUILD."""
+        shadow = np.ascontiguousarray(shadow, dtype=RAY_DTYPE)
+        closest = np.ascontiguousarray(closest, dtype=RAY_DTYPE)
+        if shadow.shape != closest.shape or shadow.ndim != 1:
+            raise ValueError("trace_rays: shadow and closest must be 1-D arrays of the same length")
+        out = np.zeros(shadow.size, dtype=RAY_RESULT_DTYPE)
+        _check(lib().hjr_trace_rays(self._h, int(path), shadow.size, shadow.ctypes.data if shadow.size else None,
+                                    closest.ctypes.data if shadow.size else None, out.ctypes.data if shadow.size else None), "hjr_trace_rays")
+        return out
 
     def stats(self):
         st = StatsV2()

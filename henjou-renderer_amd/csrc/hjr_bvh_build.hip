@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(NT) morton_kernel(uint32_t n, float* box, cons
 {
     const uint32_t t = blockIdx.x * NT + threadIdx.x;
     if (t >= n) return;
-    const float pad = __uint_as_float(hdr[H_SMAX]) * (1.0f / 32768.0f);
+    const float pad = __uint_as_float(hdr[H_SMAX]) * (1.0f / 8192.0f);
     float4* b = reinterpret_cast<float4*>(box) + 2 * (size_t)t;
     float4 lo = b[0], hi = b[1];
     lo.x -= pad; lo.y -= pad; lo.z -= pad;

@@ -15,6 +15,10 @@
 #include "../../include/henjou_hip.h"
 #include "../host/frame.hpp"
 #include "hjr_launch.hip.h"
+#if defined(HJR_UNITY) && !defined(HJR_LEAN_VARIANT)
+#define HJR_TRACE_UNIT /* one translation unit: the hook's kernels and their launch code are compiled here (hjr_launch_trace.hip is included below) */
+#endif
+#include "hjr_trace_hook.hip.h"
 #include "../host/abi.hpp"
 #include "hjr_aux.hip.h"
 #include "hjr_denoise.hip.h"
@@ -329,6 +333,7 @@ template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const LaunchPlan&, 
 #include "hjr_launch_nee.hip"
 #include "hjr_launch_pt.hip"
 #include "hjr_launch_mis.hip"
+#include "hjr_launch_trace.hip"
 #endif
 #endif
 
@@ -512,6 +517,22 @@ static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_c
     return HJR_OK;
 }
 
+// the frame data and scene tables a kernel traverses, and their sizes (LDS staging, stack depth)
+static void bind_scene_tables(const hjr_ctx* c, KParams& kp)
+{
+    kp.nodes = (const float4*)c->d_nodes.p;
+    kp.tri_geom = (const float4*)c->d_tri_geom.p;
+    kp.tri_shade = (const float4*)c->d_tri_shade.p;
+    kp.tri_inst = (const uint32_t*)c->d_tri_inst.p;
+    kp.materials = (const float4*)c->d_materials.p;
+    kp.lights = (const float4*)c->d_lights.p;
+    kp.n_node_f4 = c->frame.n_nodes * (c->frame.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4);
+    kp.n_tri_f4 = (c->frame.n_tris ? c->frame.n_tris : 1u) * HJR_TRI_F4;
+    kp.stack_depth = c->frame.stack_need; // exact worst case for this tree (host/frame.cpp)
+    kp.n_mat_f4 = (uint32_t)c->scene.materials.size() * HJR_MAT_F4;
+    kp.n_light_f4 = c->frame.n_lights * HJR_LIGHT_F4;
+}
+
 // work area, output zeroing, chunk-sum buffers, and the kernel parameters of scene, frame and outputs
 static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void* d_color, void* d_albedo, void* d_normal, hipStream_t st, KParams& kp)
 {
@@ -559,12 +580,7 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
     }
     kp.chunk_spp = g.chunk_spp; kp.n_chunks = g.n_chunks;
     kp.chunk0 = g.chunk0; kp.pass_chunks = g.pass_chunks;
-    kp.nodes = (const float4*)c->d_nodes.p;
-    kp.tri_geom = (const float4*)c->d_tri_geom.p;
-    kp.tri_shade = (const float4*)c->d_tri_shade.p;
-    kp.tri_inst = (const uint32_t*)c->d_tri_inst.p;
-    kp.materials = (const float4*)c->d_materials.p;
-    kp.lights = (const float4*)c->d_lights.p;
+    bind_scene_tables(c, kp);
     kp.lut = (c->lut_w > 0) ? (const uchar4*)c->d_lut.p : nullptr;
     kp.lut_w = c->lut_w; kp.lut_h = c->lut_h;
     if (c->n_textures) { kp.texels = (const uchar4*)c->d_texels.p; kp.tex_desc = (const uint4*)c->d_tex_desc.p; kp.srgb_lut = (const float*)c->d_srgb_lut.p; }
@@ -587,11 +603,6 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
     }
     kp.cam_f = p->camera.f;
 
-    kp.n_node_f4 = c->frame.n_nodes * (c->frame.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4);
-    kp.n_tri_f4 = (c->frame.n_tris ? c->frame.n_tris : 1u) * HJR_TRI_F4;
-    kp.stack_depth = c->frame.stack_need; // exact worst case for this tree (host/frame.cpp)
-    kp.n_mat_f4 = (uint32_t)c->scene.materials.size() * HJR_MAT_F4;
-    kp.n_light_f4 = c->frame.n_lights * HJR_LIGHT_F4;
     c->stats.lds_mode = (uint32_t)g.lds_mode; c->stats.stack_need = c->frame.stack_need;
     return HJR_OK;
 }
@@ -1062,6 +1073,76 @@ extern "C" int hjr_selftest_stack16(void)
             if (stack_dec(stack_enc<uint16_t>(ref)) != ref) return 2;
         }
     return 0;
+}
+
+// Ray-batch test hook (include/henjou_hip.h; kernels: csrc/hjr_trace_hook.hip.h).  The layout is plan_launch's for a megakernel render of the
+// current frame data under the context's options; the rays, the results and two counters share one temporary buffer.
+extern "C" int hjr_trace_rays(hjr_ctx* c, int path, uint32_t n, const hjr_ray* shadow, const hjr_ray* closest, hjr_ray_result* out)
+{
+    const int loop = path & ~(int)HJR_TRACE_FAST_BUILD;
+    const bool fast = (path & HJR_TRACE_FAST_BUILD) != 0;
+    if (loop == HJR_TRACE_WAVEFRONT) { set_error("hjr_trace_rays: HJR_TRACE_WAVEFRONT is not built (the wavefront trace stage cannot be handed independent rays; include/henjou_hip.h)"); return HJR_ERR_ARG; }
+    if (loop != HJR_TRACE_STANDALONE && loop != HJR_TRACE_FUSED) { set_error("hjr_trace_rays: unknown path"); return HJR_ERR_ARG; }
+    if (n && (!shadow || !closest || !out)) { set_error("hjr_trace_rays: null ray or result pointer"); return HJR_ERR_ARG; }
+    if (n > (1u << 24)) { set_error("hjr_trace_rays: more than 2^24 pairs in one call"); return HJR_ERR_ARG; }
+    if (!c) { set_error("hjr_trace_rays: null context"); return HJR_ERR_ARG; }
+    if (!c->have_scene || !c->have_frame) { set_error("hjr_trace_rays: no frame data (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
+#ifdef HJR_LEAN_VARIANT /* the lean experiment build instantiates the NEE megakernel only: no hook kernels */
+    (void)fast;
+    set_error("hjr_trace_rays: the lean experiment build has no ray-batch kernels");
+    return HJR_ERR_ARG;
+#else
+#ifndef HJR_HAVE_FAST
+    if (fast) { set_error("hjr_trace_rays: this build has no HJR_TRACE_FAST_BUILD kernels"); return HJR_ERR_ARG; }
+#endif
+    if (n == 0) return HJR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    KParams kp;
+    memset(&kp, 0, sizeof(kp));
+    bind_scene_tables(c, kp);
+    int lds_mode = c->frame.lds_mode;
+    if (lds_mode == 0 && c->frame.width == 2) lds_mode = 3;
+    // (`fast` of plan_launch = "megakernel family whatever option pipeline says": the hook has no wavefront path)
+    const LaunchPlan pl = plan_launch(c, kp, n, lds_mode, HJR_INTEGRATOR_NEE, true);
+    const size_t rays = (size_t)n * sizeof(hjr_ray);
+    DevBuf buf;
+    if (!buf.reserve(64 + 3 * rays)) { set_error("hjr_trace_rays: device allocation failed"); return HJR_ERR_DEVICE; }
+    char* const base = (char*)buf.p;
+    TraceArgs a;
+    memset(&a, 0, sizeof(a));
+    a.next = (unsigned int*)base; a.n_over = (unsigned long long*)(base + 8);
+    a.shadow = (const hjr_ray*)(base + 64); a.closest = (const hjr_ray*)(base + 64 + rays); a.out = (hjr_ray_result*)(base + 64 + 2 * rays);
+    a.n = n; a.round_cap = 2u * n + 64u;
+    std::vector<hjr_ray_result> init(n);
+    memset(init.data(), 0, rays);
+    for (uint32_t i = 0; i < n; i++) { init[i].prim = 0xffffffffu; init[i].status = HJR_TRACE_STATUS_UNTRACED; }
+    int rc = HJR_OK;
+    unsigned long long n_over = 0;
+    hipError_t e = hipMemsetAsync(base, 0, 64, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + 64, shadow, rays, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + 64 + rays, closest, rays, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + 64 + 2 * rays, init.data(), rays, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+#ifdef HJR_HAVE_FAST
+        rc = fast ? hjr_launch_trace_fast(c, pl, loop == HJR_TRACE_FUSED, a, c->stream) : hjr_launch_trace(c, pl, loop == HJR_TRACE_FUSED, a, c->stream);
+#else
+        rc = hjr_launch_trace(c, pl, loop == HJR_TRACE_FUSED, a, c->stream);
+#endif
+        if (rc == HJR_OK) e = hipGetLastError();
+    }
+    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out, base + 64 + 2 * rays, rays, hipMemcpyDeviceToHost, c->stream);
+    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(&n_over, base + 8, 8, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    buf.release();
+    if (rc != HJR_OK) return rc;
+    if (e != hipSuccess) { set_error(std::string("hjr_trace_rays: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
+    if (c->event_pending) { hjr_stats prev; memset(&prev, 0, sizeof(prev)); prev.struct_size = (uint32_t)sizeof(prev); (void)hjr_get_stats(c, &prev); } // counters of an earlier render land first
+    c->stats.lds_mode = (uint32_t)lds_mode; c->stats.stack_need = c->frame.stack_need; c->stats.stack_lds_entries = pl.kp.stack_lds_entries;
+    c->stats.stack_overflow_pushes = n_over;
+    return HJR_OK;
+#endif
 }
 
 extern "C" int hjr_pack_tiles_device(hjr_ctx* c, const void* d_frame, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, void* d_packed, void* hip_stream)

@@ -695,7 +695,7 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
     constexpr bool AOVS = VAR >= 1, TEX = VAR == 2;
     typedef typename std::conditional<STACK16, uint16_t, uint32_t>::type SE; // stack entry type
     typedef LaneStack<SE, BLOCK, !LDSBVH, STATS, LDSBVH> ST;
-    ST stack;
+    ST stack; // (this set-up, down to the `top` copy, is restated in hjr_trace_hook.hip.h::TraceLayout::setup for the ray-batch test hook: change both)
     stack.n_over = 0;
     stack.lds = reinterpret_cast<SE*>(hjr_smem) + threadIdx.x;
     stack.spill = P.stack_spill + (blockIdx.x * BLOCK + threadIdx.x);

@@ -3,7 +3,9 @@
 #pragma once
 #include "hjr_params.hip.h"
 
-#ifdef HJR_FAST_MATH /* the traversal and the triangle test are the same operations in every build: no mul + add fusion here */
+#ifdef HJR_FAST_MATH /* the traversal and the triangle test are the same operations in every build: no mul + add fusion here.  The unit must be
+                      * compiled with -ffp-contract=fast-honor-pragmas for this to hold (plain =fast fuses in the backend regardless: the Makefile
+                      * has the story); hjr_trace_rays' HJR_TRACE_FAST_BUILD checks it ray by ray */
 #pragma clang fp contract(off)
 #endif
 
@@ -179,7 +181,12 @@ HD uint32_t node_step(const float4* nodes, uint32_t& cur, const BoxRay<WIDTH, ST
     const v2u cc = node_ld<v2u>(anx, 48); // the child refs are stored twice (bytes 48 and 56): one immediate offset from the near-x address
     const f3 inv = R.inv, oi = R.oi;
     // min(t, tfar) spelled as the instruction: fminf() puts a quieting copy of tfar (v_max_f32 t, t) in front of it in every step of this loop,
-    // because the compiler cannot see that hit.t is never a signalling NaN; the operands here never are NaNs at all (finite planes, clamped directions)
+    // because the compiler cannot see that hit.t is never a signalling NaN.  tfar never is a NaN; the slab value is one when the ray has a NaN (or
+    // 0 x inf: an infinite origin component against a zero reciprocal) on that axis — the render loop does trace such rays, its NaN guard sits
+    // after the trace.  In the kernels' float mode (IEEE) v_min_f32 then returns the other operand, tfar, as fminf / fmaxf do for the other
+    // axes: a NaN axis drops out of the slab test, which keeps the box, and ray_tri rejects every triangle for such a ray.  Whatever the
+    // comparisons return, a step descends into a child, pushes children or pops: a node is entered at most once, so the walk ends
+    // (tests/test_gpu_trace.py traces non-finite rays through every loop)
     float fz0 = fmaf(fz.x, inv.z, oi.z), fz1 = fmaf(fz.y, inv.z, oi.z);
     asm("v_min_f32 %0, %1, %2" : "=v"(fz0) : "v"(fz0), "v"(tfar));
     asm("v_min_f32 %0, %1, %2" : "=v"(fz1) : "v"(fz1), "v"(tfar));
@@ -187,7 +194,7 @@ HD uint32_t node_step(const float4* nodes, uint32_t& cur, const BoxRay<WIDTH, ST
     const float hi0 = fminf(fminf(fmaf(fx.x, inv.x, oi.x), fmaf(fy.x, inv.y, oi.y)), fz0);
     const float lo1 = fmaxf(fmaxf(fmaf(nx.y, inv.x, oi.x), fmaf(ny.y, inv.y, oi.y)), fmaxf(fmaf(nz.y, inv.z, oi.z), tmin));
     const float hi1 = fminf(fminf(fmaf(fx.y, inv.x, oi.x), fmaf(fy.y, inv.y, oi.y)), fz1);
-    const bool h0 = lo0 <= hi0, h1 = lo1 <= hi1; // conservative through the 2^-15 box padding (>= 16x the rounding error of t)
+    const bool h0 = lo0 <= hi0, h1 = lo1 <= hi1; // conservative through the 2^-13 box padding (slab rounding + rounding of the hit t, origins up to 64x max|coord|)
     const uint32_t c0 = cc.x, c1 = cc.y;
     // (the push stays a branch here: writing the farther child unconditionally and advancing the top by 0 / 1, as the BVH4 step below does,
     // was measured slower for the BVH2 layouts — megakernel 118.8 -> 120.1 ms, MIS on the wavefront kernel 176.2 -> 179.6: the LDS pipe is the busier one)

@@ -606,8 +606,11 @@ bool build_frame(const SceneCopy& sc, const float* M, const float* Mi, uint32_t 
         for (float v : part) { if (!(v <= smax)) smax = v; } // a NaN partial maximum must surface too
     }
     if (!(smax < 1e30f)) { err = "non-finite vertex after transform"; return false; }
-    // conservative padding: the slab test must never cull a triangle the canonical ray/triangle test accepts
-    float pad = smax * (1.0f / 32768.0f);
+    // conservative padding: the slab test must never cull a triangle the canonical ray/triangle test accepts.  It has to
+    // cover the slab test's own rounding AND the rounding of the t that ray_tri returns, since a box is culled against the t of the closest
+    // hit found so far: both grow with the ray origin, about 2^-23 x 65 max|coord| per rounding at the supported bound |o| <= 64 max|coord|.
+    // 2^-13 max|coord| leaves room for 16 of them (2^-15 did not: tests/test_gpu_trace.py, far origins on the translated scene)
+    float pad = smax * (1.0f / 8192.0f);
     parallel_chunks(n, 65536, [&](size_t tb, size_t te, size_t) {
         for (size_t t = tb; t < te; t++)
             for (int a = 0; a < 3; a++) { tbox[t].lo[a] -= pad; tbox[t].hi[a] += pad; }

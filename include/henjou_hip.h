@@ -433,6 +433,39 @@ int hjr_copy_frame_data(hjr_ctx*, int what, void* dst, size_t dst_bytes, size_t*
 /* Host-only self-test of the 16-bit traversal-stack encoding (csrc/hjr_traverse.hip.h): 0 when every child ref of a tree the
  * builder admits to that layout survives encode + decode.  No reference counterpart (OptiX owns its traversal stack). */
 int hjr_selftest_stack16(void);
+/* Ray-batch test hook: hands caller-chosen rays to the software traversal of the render kernels, against the frame data the context
+ * currently holds, and returns what it found (tests/test_gpu_trace.py compares that with a brute force over all triangles, bit for bit).
+ * Pair i is a shadow (any-hit) ray and a closest-hit ray; either may be invalid (valid == 0).  tmax is read for the shadow ray only: the
+ * closest-hit ray ends at 1e16 and both start at tmin = 0.001, as in the render loop.  Rays are traced as given: no normalisation.
+ * out[i] holds the shadow ray's `occluded` and the closest-hit ray's hit: global prim id, its row k in the leaf-ordered triangle array
+ * (HJR_FRAME_TRI_GEOM), t and the barycentrics; prim == 0xffffffff and zeros mean no hit.
+ * The launch uses the megakernel layout a render would get under the context's options ("lds_bvh", "lds_stack16", "bvh_width", "short_stack",
+ * "top_nodes", "node_min", "leaf_max", "device_bvh", "device_bvh_opt" all apply), builds the same per-lane stacks and runs the same LDS
+ * staging; the kernels (csrc/hjr_trace_hook.hip.h) call the traversal functions unchanged.  `path` selects the loop:
+ *   HJR_TRACE_STANDALONE  the stand-alone traversal (MIS' BSDF-sampled ray, the tile classifier): any-hit for the shadow ray, then closest hit;
+ *   HJR_TRACE_FUSED       the fused two-ray traversal with the layout's straggler carry-over and the launch's node_min, driven in rounds like
+ *                         the render loop by a small persistent grid (one workgroup for the LDS layouts, two for the memory layouts): a lane
+ *                         takes the next pair when its previous one is resolved, a lane still in flight resumes next to the others' fresh pairs;
+ *   HJR_TRACE_WAVEFRONT   NOT BUILT: returns HJR_ERR_ARG.  The wavefront kernel's trace stage takes its rays from parked path contexts
+ *                         whose two rays share one origin (or the launch's camera position) and whose hit record has no t, so it cannot be
+ *                         handed independent rays, nor return t, without changing the stage's own code; the frame-level comparison of the
+ *                         two kernel families (tests/test_gpu_variants.py) stays its check.
+ * `path | HJR_TRACE_FAST_BUILD` runs the instantiation of the same kernels that is compiled with the flags of the HJR_FLAG_FAST_MATH render
+ * kernels; its results must equal the exact build's, bit for bit.
+ * status: HJR_TRACE_STATUS_OK; HJR_TRACE_STATUS_ROUND_CAP when a wave of the fused path gave up after 2 n + 64 rounds with the pair still in
+ * flight (every round resolves at least one lane, so this is never expected); HJR_TRACE_STATUS_UNTRACED for a pair no lane took after that.
+ * Checks, in this order and all before any launch: the path (HJR_ERR_ARG: unknown, or HJR_TRACE_WAVEFRONT), null ray / result pointers with
+ * n > 0 (HJR_ERR_ARG), n > 2^24 (HJR_ERR_ARG), a null context (HJR_ERR_ARG), no frame data (HJR_ERR_STATE — also for n == 0), a
+ * HJR_TRACE_FAST_BUILD the build does not have (HJR_ERR_ARG).  A call that passes them with n == 0 does nothing and returns HJR_OK.
+ * Synchronous.  The call overwrites part of the context's hjr_stats: stack_overflow_pushes, lds_mode, stack_need and stack_lds_entries then
+ * describe THIS launch.  If a render's counters are still pending (an asynchronous hjr_render_device not yet followed by hjr_get_stats) they
+ * are fetched first, so that they do not land on top of the hook's values later; those four fields of that render are then lost — read a
+ * render's statistics before tracing.  No reference counterpart. */
+typedef struct hjr_ray { float o[3]; float tmax; float d[3]; uint32_t valid; } hjr_ray;                                    /* 32 bytes */
+typedef struct hjr_ray_result { uint32_t occluded, prim, k; float t, b1, b2; uint32_t status, pad; } hjr_ray_result; /* 32 bytes */
+enum { HJR_TRACE_STANDALONE = 0, HJR_TRACE_FUSED = 1, HJR_TRACE_WAVEFRONT = 2, HJR_TRACE_FAST_BUILD = 0x100 };
+enum { HJR_TRACE_STATUS_OK = 0, HJR_TRACE_STATUS_ROUND_CAP = 1, HJR_TRACE_STATUS_UNTRACED = 2 };
+int hjr_trace_rays(hjr_ctx*, int path, uint32_t n, const hjr_ray* shadow, const hjr_ray* closest, hjr_ray_result* out);
 
 /* ---------------- output stage (host) ---------------- */
 /* float4ConvertColor: toSRGB + quantizeUnsignedChar — renderer/renderer.h:73-101 */

@@ -909,7 +909,7 @@ static void build_bvh(hjo_ctx* c)
         c->order[t] = t;
     }
     /* conservative padding so the slab test can never cull a triangle the canonical test accepts */
-    float pad = smax * (1.0f / 32768.0f);
+    float pad = smax * (1.0f / 8192.0f); /* as host/frame.cpp: slab rounding + rounding of the hit t, origins up to 64 x max|coord| */
     for (uint32_t t = 0; t < n; t++)
         for (int a = 0; a < 3; a++) { tb[t].lo[a] -= pad; tb[t].hi[a] += pad; }
     c->n_nodes = 0;

@@ -22,7 +22,7 @@ def declared_symbols():
 def test_library_exports_every_declared_symbol():
     L = hjr.lib()
     syms = declared_symbols()
-    assert len(syms) >= 20 and "hjr_render_device" in syms and "hjr_scene_load_gltf" in syms
+    assert len(syms) >= 20 and "hjr_render_device" in syms and "hjr_scene_load_gltf" in syms and "hjr_trace_rays" in syms
     for s in syms:
         assert hasattr(L, s), "libhenjou_hip.so does not export " + s
 
@@ -33,6 +33,12 @@ def test_struct_layouts_match_header():
     assert C.sizeof(hjr.Params) == 4 + 6 * 4 + 52 + 12 + 4 + 12
     assert C.sizeof(hjr.Stats) == 8 + 10 * 8 + 16 + 16 + 8 + 8 + 96
     assert C.sizeof(hjr.SceneView) == 8 * 4 + 13 * 8
+    # hjr_ray / hjr_ray_result of the ray-batch test hook: 32 bytes each, fields where the header puts them
+    assert hjr.RAY_DTYPE.itemsize == 32 and [hjr.RAY_DTYPE.fields[k][1] for k in ("o", "tmax", "d", "valid")] == [0, 12, 16, 28]
+    assert hjr.RAY_RESULT_DTYPE.itemsize == 32 and [hjr.RAY_RESULT_DTYPE.fields[k][1] for k in ("occluded", "prim", "k", "t", "b1", "b2", "status", "pad")] == list(range(0, 32, 4))
+    hdr = open(HEADER).read()
+    assert "typedef struct hjr_ray { float o[3]; float tmax; float d[3]; uint32_t valid; } hjr_ray;" in hdr
+    assert "typedef struct hjr_ray_result { uint32_t occluded, prim, k; float t, b1, b2; uint32_t status, pad; } hjr_ray_result;" in hdr
     for t in (hjr.Params, hjr.Stats, hjr.SceneView, hjr.RenderOption): # sized structs: struct_size leads and is set on construction
         assert t.struct_size.offset == 0 and t().struct_size == C.sizeof(t)
 
