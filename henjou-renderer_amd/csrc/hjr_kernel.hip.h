@@ -30,6 +30,7 @@ struct HitInfo { // the Payload fields the integrators read (kernel/Payload.h:12
     f3 position, normal, emission;
     Surface surf;
     uint32_t prim;
+    uint32_t k; // row of the hit triangle in tri_geom (leaf order)
 };
 
 // __closesthit__ch / __miss__ms for a finished closest-hit traversal
@@ -44,7 +45,7 @@ HD void hit_program(const KParams& P, const float4* tris, const float4* mats, co
         prd.surf.basecolor = V1(0.0f); // Payload default (Payload.h:25)
         prd.surf.metallic = 0.0f; prd.surf.roughness = 0.0f; prd.surf.sheen = 0.0f; prd.surf.clearcoat = 0.0f; prd.surf.ior = 1.0f;
         prd.surf.is_specular = false; prd.surf.is_thinfilm = false;
-        prd.prim = 0xffffffffu;
+        prd.prim = 0xffffffffu; prd.k = 0u;
         return;
     }
     // __closesthit__ch: barycentric interpolation of the pre-transformed vertices / normals with (1-b1-b2, b1, b2);
@@ -104,7 +105,7 @@ HD void hit_program(const KParams& P, const float4* tris, const float4* mats, co
     prd.is_light = f2bits(m3.x) != 0;
     prd.surf.is_specular = f2bits(m3.y) != 0;
     prd.surf.is_thinfilm = f2bits(m3.z) != 0;
-    prd.prim = h.prim;
+    prd.prim = h.prim; prd.k = h.k;
     if (STATS) lc[7] += 1;
 }
 
@@ -613,21 +614,17 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
                 const float cosine2 = absdot(-wi, lh.normal);
                 const float light_distance = length3(lh.position - prd.position);
                 const float invG = light_distance * light_distance / cosine2;
-                // getLightPDF(prim, inst) (light_sample.h:77-92): 1 / (area * light_prim_count), area from the light
-                // table's world vertices (== transform_position of the same object vertices); the table row of an
-                // emissive triangle is found by its global prim id (l4.w)
+                // getLightPDF(prim, inst) (light_sample.h:77-92): 1 / (area * light_prim_count), area from the world vertices of the
+                // triangle that was hit (tri_geom holds transform_position of the same object vertices).  The reference does not consult
+                // the light list here: an emissive triangle that is not listed, or is listed twice, gets the same pdf
                 float lp = 0.0f;
                 if (!sf.is_specular) {
-                    for (uint32_t li = 0; li < P.n_lights; li++) {
-                        const float4* Lr = lights + li * HJR_LIGHT_F4;
-                        if (f2bits(Lr[4].w) == lh.prim) {
-                            const float4 a0 = Lr[0], a1 = Lr[1], a2 = Lr[2];
-                            const f3 cr = cross(V(a1.x, a1.y, a1.z) - V(a0.x, a0.y, a0.z), V(a2.x, a2.y, a2.z) - V(a0.x, a0.y, a0.z));
-                            const float area = length3(cr) * 0.5f;
-                            lp = 1.0f / (area * P.n_lights);
-                            break;
-                        }
-                    }
+                    const float4* g = tris + lh.k * HJR_TRI_F4;
+                    const float4 a0 = g[0], a1 = g[1], a2 = g[2];
+                    const f3 v0 = V(a0.x, a0.y, a0.z);
+                    const f3 cr = cross(V(a0.w, a1.x, a1.y) - v0, V(a1.z, a1.w, a2.x) - v0);
+                    const float area = length3(cr) * 0.5f;
+                    lp = 1.0f / (area * P.n_lights);
                     lp = lp * invG;
                 }
                 const float mis_weight = pt_pdf / (pt_pdf + lp);

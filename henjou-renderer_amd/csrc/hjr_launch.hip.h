@@ -166,14 +166,17 @@ static int launch_plan(hjr_ctx* c, const LaunchPlan& pl, RenderKernel kern, uint
     // persistent grid = resident workgroups only: CUs x (workgroups the kernel's VGPR/LDS budget admits per CU), capped by the
     // number of batches of work; option "blocks_per_cu" overrides the occupancy query
     int per_cu = pl.per_cu;
-    if (per_cu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, pl.block, pl.smem) != hipSuccess || per_cu < 1))
+    if (per_cu == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, pl.block, pl.smem) != hipSuccess || per_cu < 1)) {
         per_cu = 2;
+        (void)hipGetLastError(); // a failed query must not show up as the error of this launch
+    }
     uint64_t blocks = (uint64_t)c->n_cus * (uint64_t)per_cu;
     const uint64_t per_block = pl.wf ? pl.kp.wf_cap : pl.block; // work items a workgroup holds at a time
     const uint64_t max_useful = (n_items + per_block - 1) / per_block;
     if (blocks > max_useful) blocks = max_useful ? max_useful : 1;
     if (pl.set_smem && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem) != hipSuccess) {
         set_error("hjr_render: could not reserve " + std::to_string(pl.smem) + " bytes of dynamic LDS");
+        (void)hipGetLastError(); // the refusal is reported here: the runtime's last-error slot must not fail the context's next launch
         return HJR_ERR_DEVICE;
     }
     KParams kp = pl.kp;

@@ -526,7 +526,7 @@ void build_lights(const SceneCopy& sc, const float* M, const float* Mi, FrameDat
         }
         L[3] = pdf;
         L[23] = 1.0f / pdf; // l5.w: float3 / pdf is float3 * (1.0f / pdf) (vec_math.h), the same IEEE division here as on the device
-        L[19] = u2f(prim); // l4.w: global prim id (MIS looks the emissive triangle up by it)
+        L[19] = u2f(prim); // l4.w: global prim id of the row (hjr_copy_frame_data; the kernels do not read it)
         L[7] = sc.light_prim_emission[3 * l]; L[11] = sc.light_prim_emission[3 * l + 1]; L[15] = sc.light_prim_emission[3 * l + 2];
     }
 }
