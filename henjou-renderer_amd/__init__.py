@@ -146,6 +146,21 @@ RAY_RESULT_DTYPE = np.dtype([("occluded", "<u4"), ("prim", "<u4"), ("k", "<u4"),
 TRACE_STANDALONE, TRACE_FUSED, TRACE_WAVEFRONT, TRACE_FAST_BUILD = 0, 1, 2, 0x100
 TRACE_STATUS_OK, TRACE_STATUS_ROUND_CAP, TRACE_STATUS_UNTRACED = 0, 1, 2
 
+
+# hjr_gbuffer_px: one record per pixel of the G-buffer pass (hjr_render_gbuffer); prim == GBUFFER_MISS and zeros elsewhere for a miss
+GBUFFER_DTYPE = np.dtype([("prim", "<u4"), ("inst", "<u4"), ("t", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("pos", "<f4", 3), ("ng", "<f4", 3),
+                          ("pad", "<u4")])
+GBUFFER_MISS = 0xffffffff
+TEMPORAL_ALPHA = np.float32(0.2)  # HJR_TEMPORAL_ALPHA
+
+
+class TemporalFrame(_Sized):
+    """hjr_temporal_frame: one side (previous / current frame) of hjr_temporal_accumulate."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("n_instances", C.c_uint32), ("camera", Camera),
+                ("transforms12", C.c_void_p), ("inv_transforms12", C.c_void_p), ("gbuffer", C.c_void_p), ("color", C.c_void_p),
+                ("variance", C.c_void_p), ("history", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -209,6 +224,11 @@ def lib():
             "hjr_set_adaptive": [C.c_void_p, C.c_void_p],
             "hjr_get_adaptive_state": [C.c_void_p, C.c_void_p],
             "hjr_copy_tile_samples": [C.c_void_p, C.c_void_p, C.c_size_t],
+            "hjr_render_gbuffer": [C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_render_gbuffer_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_temporal_accumulate": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_temporal_accumulate_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_temporal_reset": [C.c_void_p],
         }.items():
             fn = getattr(L, name)
             fn.restype = C.c_int
@@ -521,6 +541,59 @@ class Device:
         out = np.zeros((oh, ow, 4), dtype=np.float32)
         _check(lib().hjr_render_denoised(self._h, C.byref(params), mode, out.ctypes.data, ow, oh), "hjr_render_denoised")
         return out
+
+    def gbuffer(self, params):
+        """hjr_render_gbuffer: the first hit of every pixel's centre ray against the current frame data, GBUFFER_DTYPE [height, width]
+        (width, height and camera of `params` are read)."""
+        out = np.zeros((params.height, params.width), dtype=GBUFFER_DTYPE)
+        _check(lib().hjr_render_gbuffer(self._h, C.byref(params), out.ctypes.data), "hjr_render_gbuffer")
+        return out
+
+    @staticmethod
+    def _temporal_frame(d, keep):
+        """dict -> TemporalFrame: camera (Camera or dict), transforms / inv_transforms [n, 12], gbuffer (GBUFFER_DTYPE [h, w]), color
+        [h, w, 4], variance [h, w] and, for the previous frame, history [h, w]."""
+        g = np.ascontiguousarray(d["gbuffer"], dtype=GBUFFER_DTYPE)
+        h, w = g.shape
+        m = np.ascontiguousarray(d["transforms"], dtype=np.float32).reshape(-1, 12)
+        inv = np.ascontiguousarray(d["inv_transforms"], dtype=np.float32).reshape(-1, 12)
+        col = np.ascontiguousarray(d["color"], dtype=np.float32)
+        var = np.ascontiguousarray(d["variance"], dtype=np.float32)
+        if m.shape != inv.shape or col.shape != (h, w, 4) or var.shape != (h, w):
+            raise ValueError("temporal frame: array shapes do not agree")
+        f = TemporalFrame()
+        f.width, f.height, f.n_instances = w, h, m.shape[0]
+        cam = d["camera"]
+        f.camera = cam if isinstance(cam, Camera) else make_params(w, h, 1, cam).camera
+        arrs = [m, inv, g, col, var]
+        f.transforms12, f.inv_transforms12 = m.ctypes.data if m.size else None, inv.ctypes.data if inv.size else None
+        f.gbuffer, f.color, f.variance = g.ctypes.data, col.ctypes.data, var.ctypes.data
+        if d.get("history") is not None:
+            hist = np.ascontiguousarray(d["history"], dtype=np.float32)
+            if hist.shape != (h, w):
+                raise ValueError("temporal frame: history must be [height, width]")
+            f.history = hist.ctypes.data
+            arrs.append(hist)
+        keep.append(arrs)
+        return f
+
+    def temporal_accumulate(self, prev, cur):
+        """hjr_temporal_accumulate on dicts of arrays (keys: camera, transforms, inv_transforms, gbuffer, color, variance; prev also
+        history; prev None = no previous frame): returns (color [h, w, 4], variance [h, w], history [h, w])."""
+        keep = []
+        fc = self._temporal_frame(cur, keep)
+        fp = None if prev is None else self._temporal_frame(prev, keep)
+        h, w = fc.height, fc.width
+        color = np.zeros((h, w, 4), dtype=np.float32)
+        variance = np.zeros((h, w), dtype=np.float32)
+        history = np.zeros((h, w), dtype=np.float32)
+        _check(lib().hjr_temporal_accumulate(self._h, None if fp is None else C.byref(fp), C.byref(fc), color.ctypes.data, variance.ctypes.data,
+                                             history.ctypes.data), "hjr_temporal_accumulate")
+        return color, variance, history
+
+    def temporal_reset(self):
+        """hjr_temporal_reset: drops the history of option "denoise_temporal"; the next frame restarts everywhere."""
+        _check(lib().hjr_temporal_reset(self._h), "hjr_temporal_reset")
 
     def synchronize(self):
         _check(lib().hjr_synchronize(self._h), "hjr_synchronize")

@@ -22,6 +22,7 @@
 #include "../host/abi.hpp"
 #include "hjr_aux.hip.h"
 #include "hjr_denoise.hip.h"
+#include "hjr_temporal.hip.h"
 
 #define HIPCHK(call)                                                                                            \
     do {                                                                                                        \
@@ -84,6 +85,7 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
         return HJR_ERR_ARG;
     }
     c->opt.v[i] = value;
+    if (i == hjr::OPT_DENOISE_TEMPORAL) c->tmp.have_prev = false; // setting the option drops the history
     if (i == hjr::OPT_HOST_THREADS) hjr::set_host_threads(value);
     return HJR_OK;
 }
@@ -140,6 +142,7 @@ extern "C" int hjr_upload_scene(hjr_ctx* c, const hjr_scene_view* v)
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->frame_gen++;
+    c->tmp.have_prev = false; // temporal history: another scene
     c->have_scene = true;
     c->have_frame = false;
     c->dbvh.have_scene = false; // the device builder uploads the new scene at its next build
@@ -292,6 +295,7 @@ extern "C" int hjr_set_lut(hjr_ctx* c, const uint8_t* rgba, int w, int h)
     if (!c) { set_error("hjr_set_lut: null context"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     c->frame_gen++;
+    c->tmp.have_prev = false; // temporal history: the shading changes
     if (!rgba || w <= 0 || h <= 0) { c->lut_w = c->lut_h = 0; return HJR_OK; }
     if (!c->d_lut.upload(rgba, (size_t)w * (size_t)h * 4, c->stream)) { set_error("hjr_set_lut: upload failed"); return HJR_ERR_DEVICE; }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -304,6 +308,7 @@ extern "C" int hjr_set_sky(hjr_ctx* c, const float* rgba, int w, int h)
     if (!c) { set_error("hjr_set_sky: null context"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     c->frame_gen++;
+    c->tmp.have_prev = false; // temporal history: the lighting changes
     if (!rgba || w <= 0 || h <= 0) { c->sky_w = c->sky_h = 0; return HJR_OK; }
     if (!c->d_sky.upload(rgba, (size_t)w * (size_t)h * 16, c->stream)) { set_error("hjr_set_sky: upload failed"); return HJR_ERR_DEVICE; }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1025,6 +1030,180 @@ extern "C" int hjr_denoise_var(hjr_ctx* c, int render_mode, uint32_t in_w, uint3
     return denoise_host_impl(c, render_mode, in_w, in_h, color, albedo, normal, true, variance, out, out_w, out_h);
 }
 
+// ---- temporal accumulation with reprojection (csrc/hjr_temporal.hip.h; include/henjou_hip.h)
+// G-buffer pass on device memory: the classifier's launch shape (one wave per tile, its stacks in dynamic LDS)
+static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hipStream_t st)
+{
+    if (!c || !p || !d_out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
+    if (!c->have_scene || !c->have_frame) { set_error("hjr_render_gbuffer: no frame data (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
+    if (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED)) { set_error("hjr_render_gbuffer: world_size > 1 and HJR_FLAG_PACKED are not supported"); return HJR_ERR_ARG; }
+    if (p->width == 0 || p->height == 0) { set_error("hjr_render_gbuffer: empty image"); return HJR_ERR_ARG; }
+    if (p->width > 8192 || p->height > 8192) { set_error("hjr_render_gbuffer: frames larger than 8192 x 8192 are not supported"); return HJR_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    GbufArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nodes = (const float4*)c->d_nodes.p; a.tri_geom = (const float4*)c->d_tri_geom.p; a.tri_inst = (const uint32_t*)c->d_tri_inst.p;
+    a.n_tris = c->frame.n_tris; a.width = p->width; a.height = p->height;
+    a.tiles_x = (p->width + HJR_TILE - 1) / HJR_TILE;
+    a.n_tiles = a.tiles_x * ((p->height + HJR_TILE - 1) / HJR_TILE);
+    a.cam = p->camera;
+    a.out = (hjr_gbuffer_px*)d_out;
+    const unsigned grid = (unsigned)std::min<uint64_t>(a.n_tiles, (uint64_t)c->n_cus * 16);
+    const size_t smem = (size_t)64 * c->frame.stack_need * 4;
+    if (c->frame.width == 2) hipLaunchKernelGGL(hjr_gbuffer_kernel<2>, dim3(grid), dim3(64), smem, st, a);
+    else hipLaunchKernelGGL(hjr_gbuffer_kernel<4>, dim3(grid), dim3(64), smem, st, a);
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+extern "C" int hjr_render_gbuffer_device(hjr_ctx* c, const hjr_params* p_user, void* d_out, void* hip_stream)
+{
+    hjr_params params; // sized struct
+    if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
+    return gbuffer_device_impl(c, &params, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+extern "C" int hjr_render_gbuffer(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out)
+{
+    hjr_params params; // sized struct
+    if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
+    if (!out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
+    const size_t bytes = (size_t)params.width * params.height * sizeof(hjr_gbuffer_px);
+    DevBuf buf;
+    if (bytes && !buf.reserve(bytes)) { set_error("hjr_render_gbuffer: device allocation failed"); return HJR_ERR_DEVICE; }
+    int rc = gbuffer_device_impl(c, &params, bytes ? buf.p : (void*)out, c->stream);
+    hipError_t e = hipSuccess;
+    if (rc == HJR_OK) e = hipMemcpyAsync(out, buf.p, bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    buf.release();
+    if (rc != HJR_OK) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { set_error(std::string("hjr_render_gbuffer: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
+    return HJR_OK;
+}
+
+// the accumulation kernel on device memory; the two frames were checked by the callers
+static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_color, void* d_var, void* d_hist, hipStream_t st)
+{
+    TemporalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cur = cur;
+    if (prev) { a.prev = *prev; a.have_prev = 1u; }
+    a.width = w; a.height = h; a.n_instances = n_inst;
+    a.n_tris = c->have_scene ? c->scene.n_triangles : 0xffffffffu; // prim ids are checked against the uploaded scene
+    a.out_color = (float4*)d_color; a.out_variance = (float*)d_var; a.out_history = (float*)d_hist;
+    hipLaunchKernelGGL(hjr_temporal_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+// argument checks of hjr_temporal_accumulate[_device]: the sized structs, sizes that agree, every pointer the kernel reads
+static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, hjr_temporal_frame& prev, hjr_temporal_frame& cur, bool& have_prev)
+{
+    if (!hjr::abi_take(cur_user, cur, "hjr_temporal_accumulate")) return HJR_ERR_ARG;
+    have_prev = prev_user != nullptr;
+    if (have_prev && !hjr::abi_take(prev_user, prev, "hjr_temporal_accumulate")) return HJR_ERR_ARG;
+    if (cur.width == 0 || cur.height == 0 || cur.width > 16384 || cur.height > 16384) { set_error("hjr_temporal_accumulate: bad image size"); return HJR_ERR_ARG; }
+    if (!cur.gbuffer || !cur.color || !cur.variance || (cur.n_instances && (!cur.transforms12 || !cur.inv_transforms12))) { set_error("hjr_temporal_accumulate: null pointer in the current frame"); return HJR_ERR_ARG; }
+    if (have_prev) {
+        if (prev.width != cur.width || prev.height != cur.height || prev.n_instances != cur.n_instances) { set_error("hjr_temporal_accumulate: width, height and n_instances of the two frames must agree"); return HJR_ERR_ARG; }
+        if (!prev.gbuffer || !prev.color || !prev.variance || !prev.history || (prev.n_instances && (!prev.transforms12 || !prev.inv_transforms12))) { set_error("hjr_temporal_accumulate: null pointer in the previous frame"); return HJR_ERR_ARG; }
+    }
+    return HJR_OK;
+}
+static TemporalSide temporal_side(const hjr_temporal_frame& f)
+{
+    TemporalSide s;
+    s.cam = f.camera; s.m = f.transforms12; s.inv = f.inv_transforms12; s.gbuf = f.gbuffer;
+    s.color = (const float4*)f.color; s.variance = f.variance; s.history = f.history;
+    return s;
+}
+extern "C" int hjr_temporal_accumulate_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist, void* hip_stream)
+{
+    if (!c || !d_color || !d_var || !d_hist) { set_error("hjr_temporal_accumulate: null argument"); return HJR_ERR_ARG; }
+    hjr_temporal_frame prev, cur;
+    bool have_prev;
+    if (const int rc = temporal_take(prev_user, cur_user, prev, cur, have_prev)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const TemporalSide ps = have_prev ? temporal_side(prev) : TemporalSide(), cs = temporal_side(cur);
+    return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist)
+{
+    if (!c || !out_color || !out_var || !out_hist) { set_error("hjr_temporal_accumulate: null argument"); return HJR_ERR_ARG; }
+    hjr_temporal_frame f[2]; // [0] prev, [1] cur
+    bool have_prev;
+    if (const int rc = temporal_take(prev_user, cur_user, f[0], f[1], have_prev)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t npx = (size_t)f[1].width * f[1].height, nx = (size_t)f[1].n_instances * 48;
+    // one temporary buffer: per side [M | M^-1 | gbuffer | colour | variance | history], then the three outputs
+    const size_t side = (2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4) + 255) & ~(size_t)255, outs = npx * (16 + 4 + 4); // (float4 images stay 16-byte aligned)
+    DevBuf buf;
+    if (!buf.reserve(2 * side + outs)) { set_error("hjr_temporal_accumulate: device allocation failed"); return HJR_ERR_DEVICE; }
+    TemporalSide s[2];
+    hipError_t e = hipSuccess;
+    for (int i = have_prev ? 0 : 1; i < 2; i++) {
+        char* b = (char*)buf.p + (size_t)i * side;
+        const void* src[6] = { f[i].transforms12, f[i].inv_transforms12, f[i].gbuffer, f[i].color, f[i].variance, i == 0 ? f[i].history : nullptr };
+        const size_t len[6] = { nx, nx, npx * sizeof(hjr_gbuffer_px), npx * 16, npx * 4, npx * 4 };
+        const void* dst[6];
+        for (int k = 0; k < 6; k++) {
+            dst[k] = b;
+            if (src[k] && len[k] && e == hipSuccess) e = hipMemcpyAsync(b, src[k], len[k], hipMemcpyHostToDevice, c->stream);
+            b += len[k];
+        }
+        s[i].cam = f[i].camera; s[i].m = (const float*)dst[0]; s[i].inv = (const float*)dst[1]; s[i].gbuf = (const hjr_gbuffer_px*)dst[2];
+        s[i].color = (const float4*)dst[3]; s[i].variance = (const float*)dst[4]; s[i].history = (const float*)dst[5];
+    }
+    char* const o = (char*)buf.p + 2 * side;
+    int rc = HJR_OK;
+    if (e == hipSuccess) rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream);
+    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_color, o, npx * 16, hipMemcpyDeviceToHost, c->stream);
+    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_var, o + npx * 16, npx * 4, hipMemcpyDeviceToHost, c->stream);
+    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_hist, o + npx * 20, npx * 4, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    buf.release();
+    if (rc != HJR_OK) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { set_error(std::string("hjr_temporal_accumulate: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
+    return HJR_OK;
+}
+extern "C" int hjr_temporal_reset(hjr_ctx* c)
+{
+    if (!c) { set_error("hjr_temporal_reset: null context"); return HJR_ERR_ARG; }
+    c->tmp.have_prev = false;
+    return HJR_OK;
+}
+
+// Option "denoise_temporal", between the render and the filter of hjr_render_denoised, all on the context's stream: G-buffer of this frame,
+// a device copy of the transforms the current frame data was built from (last_m / last_inv: what hjr_commit_transforms made current, so a
+// frame loop that already prepares the next frame on another thread cannot be seen here), accumulation against the previous slot.
+// `commit`: this call ends the frame (a whole-frame render, or the sample pass that ends at spp): the slots rotate.
+static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var)
+{
+    hjr_ctx::Temporal& t = c->tmp;
+    const uint32_t n_inst = (uint32_t)(c->last_m.size() / 12);
+    if (t.have_prev && (t.width != p->width || t.height != p->height || t.mode != render_mode || t.n_instances != n_inst)) t.have_prev = false;
+    const size_t npx = (size_t)p->width * p->height, nx = (size_t)n_inst * 48;
+    const int k = t.cur;
+    if (!t.color[k].reserve(npx * 16) || !t.variance[k].reserve(npx * 4) || !t.history[k].reserve(npx * 4) || !t.gbuf[k].reserve(npx * sizeof(hjr_gbuffer_px)) ||
+        !t.xf[k].reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
+    if (const int rc = gbuffer_device_impl(c, p, t.gbuf[k].p, c->stream)) return rc;
+    if (nx) {
+        HIPCHK(hipMemcpyAsync(t.xf[k].p, c->last_m.data(), nx, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync((char*)t.xf[k].p + nx, c->last_inv.data(), nx, hipMemcpyHostToDevice, c->stream));
+    }
+    t.cam[k] = p->camera;
+    TemporalSide s[2];
+    for (int i = 0; i < 2; i++) {
+        const int q = i == 0 ? (k ^ 1) : k;
+        s[i].cam = t.cam[q]; s[i].m = (const float*)t.xf[q].p; s[i].inv = (const float*)((const char*)t.xf[q].p + nx); s[i].gbuf = (const hjr_gbuffer_px*)t.gbuf[q].p;
+        s[i].color = (const float4*)t.color[q].p; s[i].variance = (const float*)t.variance[q].p; s[i].history = (const float*)t.history[q].p;
+    }
+    s[1].color = (const float4*)d_color; s[1].variance = (const float*)d_var; s[1].history = nullptr;
+    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, c->stream)) return rc;
+    d_color = t.color[k].p; d_var = t.variance[k].p;
+    if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur = k ^ 1; }
+    return HJR_OK;
+}
+
 // One frame of Renderer's loop in a Denoise mode, on the device: optixLaunch -> denoise -> cpyGPUBufferToHost(AOV_Output)
 // (renderer.h:1229-1281).  p->width x p->height is the RENDER size (already halved by the caller for DenoiseUpScale2X).
 extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int render_mode, float* out, uint32_t out_w, uint32_t out_h)
@@ -1037,7 +1216,9 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     const size_t in_bytes = (size_t)p->width * p->height * 16, out_bytes = (size_t)out_w * out_h * 16;
     if (in_bytes == 0 || out_bytes == 0) { set_error("hjr_render_denoised: empty image"); return HJR_ERR_ARG; }
     const bool guides = render_mode != HJR_MODE_DEFAULT;
-    const bool with_var = guides && c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0; // option "denoise_variance": the variance AOV and the variance-guided filter
+    const bool temporal = guides && c->opt.get(hjr::OPT_DENOISE_TEMPORAL, 0) != 0; // option "denoise_temporal": accumulation over frames in front of the filter
+    if (temporal && (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED))) { set_error("hjr_render_denoised: option \"denoise_temporal\" does not take world_size > 1 or HJR_FLAG_PACKED"); return HJR_ERR_ARG; }
+    const bool with_var = guides && (temporal || c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0); // option "denoise_variance": the variance AOV and the variance-guided filter
     PassRange pr; // a sample pass: the running mean is filtered (a denoised preview; the last pass gives the one-shot call's image)
     if (const int rc = check_pass(c, p, (guides ? 7u : 1u) | (with_var ? 8u : 0u), pr)) return rc;
     if (with_var) {
@@ -1052,8 +1233,10 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     if (guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
     int rc = render_impl(c, p, pr, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var ? c->d_variance.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
-    rc = denoise_device_impl(c, render_mode, p->width, p->height, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr,
-                             with_var, with_var ? c->d_variance.p : nullptr, c->d_dn_out.p, out_w, out_h, c->stream);
+    const void *f_color = c->d_color.p, *f_var = with_var ? c->d_variance.p : nullptr; // what the filter reads
+    if (temporal && (rc = temporal_stage(c, p, render_mode, !pr.pass || pr.end == p->spp, f_color, f_var)) != HJR_OK) return rc;
+    rc = denoise_device_impl(c, render_mode, p->width, p->height, f_color, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr,
+                             with_var, f_var, c->d_dn_out.p, out_w, out_h, c->stream);
     if (rc != HJR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -94,6 +94,16 @@ struct hjr_ctx {
         uint32_t* h_active = nullptr; // pinned: tiles still active after the last pass, valid once `ready` has happened
         hipEvent_t ready = nullptr;
     } ad;
+    // Temporal accumulation (option "denoise_temporal", csrc/hjr_temporal.hip.h).  Nothing here is allocated before the first render with the
+    // option on.  Two slots in rotation: `cur` receives the frame being rendered, cur ^ 1 holds the committed previous frame (if have_prev).
+    struct Temporal {
+        bool have_prev = false;
+        int cur = 0;
+        uint32_t width = 0, height = 0, n_instances = 0; // of the previous frame
+        int mode = 0;
+        hjr_camera cam[2];
+        DevBuf color[2], variance[2], history[2], gbuf[2], xf[2]; // accumulated unfiltered colour | its variance | h | G-buffer | [M | M^-1] of that render
+    } tmp;
     hjr::Options opt; // hjr_set_option (host/options.hpp): the library reads no environment variable
 
     void release_buffers()
@@ -101,6 +111,8 @@ struct hjr_ctx {
         for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
                            &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &d_variance, &d_var_stat, &d_dnv_a, &d_dnv_b, &ad.stat, &ad.state, &ad.list })
             b->release();
+        for (int i = 0; i < 2; i++)
+            for (DevBuf* b : { &tmp.color[i], &tmp.variance[i], &tmp.history[i], &tmp.gbuf[i], &tmp.xf[i] }) b->release();
         if (ad.h_active) (void)hipHostFree(ad.h_active);
         if (ad.ready) (void)hipEventDestroy(ad.ready);
         ad.h_active = nullptr; ad.ready = nullptr;

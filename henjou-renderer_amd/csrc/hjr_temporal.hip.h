@@ -1,0 +1,200 @@
+// Temporal accumulation with reprojection for the Denoise modes: the temporal half of SVGF (Schied et al., HPG 2017) in front of the
+// variance-guided a-trous filter (hjr_denoise.hip.h).  Two kernels, both outside the render kernels (no render kernel knows about them):
+//   hjr_gbuffer_kernel<WIDTH>   first-hit record of every pixel's centre ray, by the stand-alone traversal the tile classifier uses;
+//   hjr_temporal_kernel         one lane per pixel: reprojects the pixel's surface point into the previous frame, gathers the previous
+//                               frame's accumulated colour / variance / history length with four validated bilinear taps and blends.
+// Included by hjr_device.hip only: correctly rounded divide, no contraction, denormals on.  Specified to the bit, so that the test suite's
+// CPU checker (tests/native/temporal_ref.cpp) restates it independently.  fp32 throughout, every operation as written, left to right:
+//   dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z ;   cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x) ;
+//   a 3 x 4 row-major transform M (12 floats, as hjr_set_transforms) applied to a point:  xf(M, p).i = ((M[4i] * p.x + M[4i+1] * p.y) + M[4i+2] * p.z) + M[4i+3],
+//   its linear part applied to a vector:  lin(M, d).i = (M[4i] * d.x + M[4i+1] * d.y) + M[4i+2] * d.z ;   finite(x) = fabsf(x) <= FLT_MAX.
+//
+// G-BUFFER.  Pixel (px, py), W x H, exactly the tile classifier's ray:  u = (2 (px + 0.5) - W) / H,  v = (2 (py + 0.5) - H) / H,
+//   d = normalize(dir * f + right * u + up * v), origin cam.pos, tmin 0.001, tmax 1e16; traverse<ANY = false> against the frame data read
+//   from memory.  A hit with row k of the leaf-ordered triangle array (v0, v1, v2 world space) gives the record
+//     prim, inst = tri_inst[prim], t, b1, b2,  pos = v0 * (1 - b1 - b2) + v1 * b1 + v2 * b2  (hit_program's expression: per component
+//     (v0.c * w0 + v1.c * b1) + v2.c * b2 with w0 = (1 - b1) - b2),  ng = cross(v1 - v0, v2 - v0)  (not normalised),  pad = 0.
+//   A miss (or a prim id outside the triangle table) is prim = 0xffffffff and every other field 0.
+//
+// ACCUMULATION.  Pixel (x, y) of the current frame, G = cur.gbuffer[y W + x]; cur / prev: hjr_temporal_frame.  RESTART means
+//   out = cur.color, var = cur.variance, h = 1  (all three copied as stored).
+//   1. RESTART if there is no previous frame, or G.prim == 0xffffffff, or G.prim >= n_triangles, or G.inst >= n_instances.
+//   2. p_obj = xf(Minv_cur[G.inst], G.pos);  p_prev = xf(M_prev[G.inst], p_obj);  w = p_prev - prev.camera.pos;
+//      a = prev.camera.dir * prev.camera.f,  b = prev.camera.right,  c = prev.camera.up  (right is not normalised: a full 3 x 3 solve);
+//      bc = cross(b, c);  det = dot(a, bc);  s = dot(w, bc) / det;  su = dot(a, cross(w, c)) / det;  sv = dot(a, cross(b, w)) / det;
+//      u = su / s;  v = sv / s;   RESTART unless det != 0 and s > 0 and finite(s), finite(u), finite(v);
+//      xp = (u * H + W) * 0.5 - 0.5;  yp = (v * H + H) * 0.5 - 0.5;   RESTART unless xp >= -1 and xp < W and yp >= -1 and yp < H  (float compares);
+//      fx = floorf(xp), fy = floorf(yp);  x0 = (int)fx, y0 = (int)fy;  tx = xp - fx, ty = yp - fy.
+//   3. Taps k = 0..3 at (x0 + (k & 1), y0 + (k >> 1)), weights  w0 = (1 - tx) * (1 - ty), w1 = tx * (1 - ty), w2 = (1 - tx) * ty, w3 = tx * ty.
+//      Tap k with record T = prev.gbuffer[tap] is VALID iff it lies inside the image, T.prim != 0xffffffff, T.prim < n_triangles,
+//      T.inst == G.inst, and with
+//        e = xf(Minv_prev[T.inst], T.pos) - p_obj;  D = lin(M_cur[G.inst], e);  view = G.pos - cur.camera.pos;  ng = G.ng;
+//        vv = dot(view, view);  fh = cur.camera.f * H;  fp2 = (vv * 4) / (fh * fh);  nn = dot(ng, ng);  nd = dot(ng, D);  nv = dot(ng, view);
+//      both   nd * nd <= ((K_PLANE * K_PLANE) * fp2) * nn   and   dot(D, D) * (nv * nv) <= (((K_DIST * K_DIST) * fp2) * nn) * vv
+//      hold (a NaN fails a comparison).  fp2 is the squared footprint of a pixel at the point's distance; the first test is the distance
+//      from the current tangent plane, the second the distance in the plane scaled by the cosine of the view angle.
+//   4. In tap order over the valid taps, all sums from +0.0f:  S = S + w_k;  C.c = C.c + prev.color[tap].c * w_k (c = r, g, b);
+//      with pv = prev.variance[tap]:  unknown |= !(pv < HJR_VARIANCE_UNKNOWN)  (NaN included);  V = V + fmaxf(pv, 0) * w_k;
+//      Hs = Hs + prev.history[tap] * w_k.   RESTART unless S > 0.   c_prev = C / S,  v_prev = V / S,  h_prev = Hs / S  (one divide each);
+//      h = fminf(fmaxf(h_prev + 1, 1), 64);   al = fmaxf(1 / h, HJR_TEMPORAL_ALPHA);
+//      out.c = c_prev.c + (cur.c - c_prev.c) * al,  out.a = cur.a;
+//      cv = cur.variance;  unknown |= !(cv < HJR_VARIANCE_UNKNOWN);  om = 1 - al;
+//      var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0)     (fmaxf(NaN, 0) = 0 never reaches the sum).
+//   The variance is that of a convex combination of independent estimates (frames are independent: the RNG index is frame * spp + s), which
+//   is why it is propagated and not estimated from temporal moments.  K_PLANE = 1, K_DIST = 3: "a tap is at most one pixel from the exact
+//   point" (DESIGN.md §11 has what was measured).
+// Hostile input: every table index (instance of the current record and of each tap) is range-checked before it is used, no tap outside the
+// image is read, and float -> int conversion happens only after the float range check; nothing else indexes memory.
+#pragma once
+#include "hjr_kernel.hip.h"
+
+#define HJR_TEMPORAL_K_PLANE 1.0f
+#define HJR_TEMPORAL_K_DIST 3.0f
+#define HJR_TEMPORAL_H_MAX 64.0f
+
+struct GbufArgs {
+    const float4* nodes;
+    const float4* tri_geom;
+    const uint32_t* tri_inst;
+    uint32_t n_tris, width, height, tiles_x, n_tiles;
+    hjr_camera cam;
+    hjr_gbuffer_px* out;
+};
+
+// one wave per 8 x 8 tile, grid-stride over the tiles; 64 * stack_depth * 4 bytes of dynamic LDS (the classifier's stacks)
+template <int WIDTH>
+__global__ void __launch_bounds__(64) hjr_gbuffer_kernel(const GbufArgs A)
+{
+    typedef LaneStack<uint32_t, 64, false> ST;
+    ST stack;
+    stack.lds = reinterpret_cast<uint32_t*>(hjr_smem) + threadIdx.x;
+    stack.spill = nullptr; stack.spill_stride = 0; stack.lds_n = 0; stack.n_over = 0; stack.top = nullptr; stack.n_top = 0u;
+    for (uint32_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
+        uint32_t tx, ty;
+        hjr_tile_xy(tile, A.tiles_x, &tx, &ty);
+        const uint32_t px = tx * HJR_TILE + (threadIdx.x & 7u), py = ty * HJR_TILE + (threadIdx.x >> 3);
+        if (px >= A.width || py >= A.height) continue;
+        const float W = (float)A.width, H = (float)A.height;
+        const float u = (2.0f * ((float)px + 0.5f) - W) / H, v = (2.0f * ((float)py + 0.5f) - H) / H;
+        const f3 cd = V(A.cam.dir[0], A.cam.dir[1], A.cam.dir[2]), cu = V(A.cam.up[0], A.cam.up[1], A.cam.up[2]);
+        const f3 cr = V(A.cam.right[0], A.cam.right[1], A.cam.right[2]);
+        const f3 d = normalize(cd * A.cam.f + cr * u + cu * v);
+        Hit h;
+        Counters cnt; cnt.box = cnt.tri = 0;
+        hjr_gbuffer_px r;
+        r.prim = 0xffffffffu; r.inst = 0u; r.t = r.b1 = r.b2 = 0.0f; r.pad = 0u;
+        for (int k = 0; k < 3; k++) r.pos[k] = r.ng[k] = 0.0f;
+        if (traverse<false, false, WIDTH, 64, ST>(A.nodes, A.tri_geom, V(A.cam.pos[0], A.cam.pos[1], A.cam.pos[2]), d, 0.001f, 1e16f, h, stack, cnt) && h.prim < A.n_tris) {
+            const float4* g = A.tri_geom + (size_t)h.k * HJR_TRI_F4;
+            const float4 g0 = g[0], g1 = g[1], g2 = g[2];
+            const f3 v0 = V(g0.x, g0.y, g0.z), v1 = V(g0.w, g1.x, g1.y), v2 = V(g1.z, g1.w, g2.x);
+            const float w0 = 1.0f - h.b1 - h.b2;
+            const f3 pos = v0 * w0 + v1 * h.b1 + v2 * h.b2;
+            const f3 ng = cross(v1 - v0, v2 - v0);
+            r.prim = h.prim; r.inst = A.tri_inst[h.prim];
+            r.t = h.t; r.b1 = h.b1; r.b2 = h.b2;
+            r.pos[0] = pos.x; r.pos[1] = pos.y; r.pos[2] = pos.z;
+            r.ng[0] = ng.x; r.ng[1] = ng.y; r.ng[2] = ng.z;
+        }
+        A.out[(size_t)py * A.width + px] = r;
+    }
+}
+
+// device view of one hjr_temporal_frame
+struct TemporalSide {
+    hjr_camera cam;
+    const float* m;             // n_instances x 12
+    const float* inv;           // n_instances x 12
+    const hjr_gbuffer_px* gbuf;
+    const float4* color;
+    const float* variance;
+    const float* history;       // prev only
+};
+struct TemporalArgs {
+    TemporalSide prev, cur;
+    uint32_t have_prev, width, height, n_instances, n_tris;
+    float4* out_color;
+    float* out_variance;
+    float* out_history;
+};
+
+HD float t_dot(f3 a, f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+HD f3 t_xf(const float* __restrict__ m, f3 p)
+{
+    return V(((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7], ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]);
+}
+HD f3 t_lin(const float* __restrict__ m, f3 d)
+{
+    return V((m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z, (m[8] * d.x + m[9] * d.y) + m[10] * d.z);
+}
+HD bool t_finite(float x) { return fabsf(x) <= HJ_FLT_MAX; }
+
+__global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= A.width || y >= A.height) return;
+    const size_t pix = (size_t)y * A.width + x;
+    const float4 cc = A.cur.color[pix];
+    const float cv = A.cur.variance[pix];
+    float4 out = cc;
+    float var = cv, hist = 1.0f;
+    const hjr_gbuffer_px G = A.cur.gbuf[pix];
+    if (A.have_prev && G.prim != 0xffffffffu && G.prim < A.n_tris && G.inst < A.n_instances) {
+        const float W = (float)A.width, H = (float)A.height;
+        const f3 gpos = V(G.pos[0], G.pos[1], G.pos[2]);
+        const f3 p_obj = t_xf(A.cur.inv + (size_t)G.inst * 12u, gpos);
+        const f3 p_prev = t_xf(A.prev.m + (size_t)G.inst * 12u, p_obj);
+        const f3 w = p_prev - V(A.prev.cam.pos[0], A.prev.cam.pos[1], A.prev.cam.pos[2]);
+        const f3 a = V(A.prev.cam.dir[0] * A.prev.cam.f, A.prev.cam.dir[1] * A.prev.cam.f, A.prev.cam.dir[2] * A.prev.cam.f);
+        const f3 b = V(A.prev.cam.right[0], A.prev.cam.right[1], A.prev.cam.right[2]), c = V(A.prev.cam.up[0], A.prev.cam.up[1], A.prev.cam.up[2]);
+        const f3 bc = cross(b, c);
+        const float det = t_dot(a, bc);
+        const float s = t_dot(w, bc) / det, su = t_dot(a, cross(w, c)) / det, sv = t_dot(a, cross(b, w)) / det;
+        const float u = su / s, v = sv / s;
+        const float xp = (u * H + W) * 0.5f - 0.5f, yp = (v * H + H) * 0.5f - 0.5f;
+        if (det != 0.0f && s > 0.0f && t_finite(s) && t_finite(u) && t_finite(v) && xp >= -1.0f && xp < W && yp >= -1.0f && yp < H) {
+            const float fx = floorf(xp), fy = floorf(yp);
+            const int x0 = (int)fx, y0 = (int)fy;
+            const float tx = xp - fx, ty = yp - fy;
+            const float wk[4] = { (1.0f - tx) * (1.0f - ty), tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty };
+            const f3 view = gpos - V(A.cur.cam.pos[0], A.cur.cam.pos[1], A.cur.cam.pos[2]), ng = V(G.ng[0], G.ng[1], G.ng[2]);
+            const float vv = t_dot(view, view), fh = A.cur.cam.f * H;
+            const float fp2 = (vv * 4.0f) / (fh * fh), nn = t_dot(ng, ng), nv = t_dot(ng, view);
+            const float lim_plane = ((HJR_TEMPORAL_K_PLANE * HJR_TEMPORAL_K_PLANE) * fp2) * nn;
+            const float lim_dist = (((HJR_TEMPORAL_K_DIST * HJR_TEMPORAL_K_DIST) * fp2) * nn) * vv;
+            const float* const m_cur = A.cur.m + (size_t)G.inst * 12u;
+            float S = 0.0f, Cx = 0.0f, Cy = 0.0f, Cz = 0.0f, Vs = 0.0f, Hs = 0.0f;
+            bool unknown = false;
+            for (int k = 0; k < 4; k++) {
+                const int xt = x0 + (k & 1), yt = y0 + (k >> 1);
+                if (xt < 0 || yt < 0 || xt >= (int)A.width || yt >= (int)A.height) continue;
+                const size_t tap = (size_t)yt * A.width + (size_t)xt;
+                const hjr_gbuffer_px T = A.prev.gbuf[tap];
+                if (T.prim == 0xffffffffu || T.prim >= A.n_tris || T.inst != G.inst) continue; // (G.inst < n_instances: so is T.inst)
+                const f3 e = t_xf(A.prev.inv + (size_t)T.inst * 12u, V(T.pos[0], T.pos[1], T.pos[2])) - p_obj;
+                const f3 D = t_lin(m_cur, e);
+                const float nd = t_dot(ng, D);
+                if (!(nd * nd <= lim_plane) || !(t_dot(D, D) * (nv * nv) <= lim_dist)) continue;
+                const float4 pc = A.prev.color[tap];
+                const float pv = A.prev.variance[tap];
+                S = S + wk[k];
+                Cx = Cx + pc.x * wk[k]; Cy = Cy + pc.y * wk[k]; Cz = Cz + pc.z * wk[k];
+                unknown = unknown || !(pv < HJR_VARIANCE_UNKNOWN);
+                Vs = Vs + fmaxf(pv, 0.0f) * wk[k];
+                Hs = Hs + A.prev.history[tap] * wk[k];
+            }
+            if (S > 0.0f) {
+                const float px_ = Cx / S, py_ = Cy / S, pz_ = Cz / S, v_prev = Vs / S, h_prev = Hs / S;
+                hist = fminf(fmaxf(h_prev + 1.0f, 1.0f), HJR_TEMPORAL_H_MAX);
+                const float al = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA);
+                out.x = px_ + (cc.x - px_) * al; out.y = py_ + (cc.y - py_) * al; out.z = pz_ + (cc.z - pz_) * al;
+                unknown = unknown || !(cv < HJR_VARIANCE_UNKNOWN);
+                const float om = 1.0f - al;
+                var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0.0f);
+            }
+        }
+    }
+    A.out_color[pix] = out;
+    A.out_variance[pix] = var;
+    A.out_history[pix] = hist;
+}

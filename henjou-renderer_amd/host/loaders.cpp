@@ -134,6 +134,7 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             o.force_rebuild = flag("force_rebuild") ? 1 : 0;
             o.device_bvh = flag("device_bvh") ? 1 : 0; // the frame data built on the device (option "device_bvh")
             o.denoise_variance = flag("denoise_variance") ? 1 : 0; // the variance-guided filter in the Denoise modes (option "denoise_variance")
+            if (flag("denoise_temporal")) o.denoise_variance = 2; // ... plus temporal accumulation (option "denoise_temporal"); the struct does not grow for it
             // device_bvh_opt: treelet-restructuring rounds of the device build (option "device_bvh_opt")
             if (const Json* v = h->find("device_bvh_opt")) {
                 const double r = v->is_number() ? v->as_number() : -1.0;

@@ -47,6 +47,12 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
         set_error("hjr_render_file: Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)");
         return HJR_ERR_ARG;
     }
+    // "denoise_temporal" (stored as denoise_variance == 2) in a Denoise mode; Default mode ignores the field as before
+    const bool temporal = opt.denoise_variance == 2 && opt.render_mode != HJR_MODE_DEFAULT;
+    if (temporal && opt.noise_threshold > 0.0f) {
+        set_error("hjr_render_file: \"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history");
+        return HJR_ERR_ARG;
+    }
     hjr_scene* scene = nullptr;
     rc = hjr_scene_load_gltf(opt.gltf_path, opt.gltf_name, &opt, &scene);
     if (rc != HJR_OK) return rc;
@@ -60,6 +66,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (opt.device_bvh) (void)hjr_set_option(ctx, "device_bvh", 1);
     if (opt.device_bvh_opt) (void)hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt);
     if (opt.denoise_variance && opt.render_mode != HJR_MODE_DEFAULT) (void)hjr_set_option(ctx, "denoise_variance", 1); // (Default mode has no filter)
+    if (temporal) (void)hjr_set_option(ctx, "denoise_temporal", 1);
     const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes
     rc = hjr_upload_scene(ctx, &view);
     if (rc == HJR_OK && adaptive) {

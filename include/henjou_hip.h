@@ -146,7 +146,8 @@ typedef struct hjr_render_option {
                                   * PNG from the last pass ("noise_threshold") */
     uint32_t min_samples;        /* default 0 = two granules: hjr_adaptive.min_samples ("min_samples") */
     int32_t denoise_variance;    /* default 0; 1: hjr_render_file / henjou_cli set the context option "denoise_variance" (the variance-guided
-                                  * filter in Render_mode Denoise / DenoiseUpScale2X; ignored in Default) */
+                                  * filter in Render_mode Denoise / DenoiseUpScale2X; ignored in Default); 2: that and the option
+                                  * "denoise_temporal" (key "denoise_temporal": true; the struct does not grow for it) */
 } hjr_render_option;
 
 typedef struct hjr_camera {      /* Params.camera_* (renderer/renderer.h:1187-1191) */
@@ -378,6 +379,42 @@ int hjr_denoise_var(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, con
                     const float* aov_normal, const float* aov_variance, float* out, uint32_t out_w, uint32_t out_h);
 int hjr_denoise_var_device(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
                            const void* d_normal, const void* d_variance, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream);
+/* ---- Temporal accumulation with reprojection (the temporal half of SVGF; csrc/hjr_temporal.hip.h has the arithmetic to the bit, DESIGN.md
+ * §11.2 the rule, its limits and what was measured).  Two stateless building blocks and a context option that chains them.
+ * G-buffer: the first hit of every pixel's centre ray (no RNG; the ray of the tile classifier) against the context's current frame data,
+ * either builder, every layout option.  One 48-byte record per pixel, row-major; a miss is prim = 0xffffffff and zeros elsewhere.  `pos` is the
+ * hit point as the closest-hit program computes it, `ng` the world-space geometric normal cross(v1 - v0, v2 - v0), not normalised.
+ * hjr_render_gbuffer reads width, height and camera of hjr_params only.  HJR_ERR_STATE without frame data; HJR_ERR_ARG for world_size > 1,
+ * HJR_FLAG_PACKED or an empty image.  Host form synchronous; device form asynchronous on `hip_stream` (NULL = the context's stream). */
+typedef struct hjr_gbuffer_px { uint32_t prim, inst; float t, b1, b2; float pos[3]; float ng[3]; uint32_t pad; } hjr_gbuffer_px; /* 48 bytes */
+int hjr_render_gbuffer(hjr_ctx*, const hjr_params*, hjr_gbuffer_px* out);
+int hjr_render_gbuffer_device(hjr_ctx*, const hjr_params*, void* d_out, void* hip_stream);
+/* Accumulation: per pixel of the current frame, the surface point is taken back to object space with the current inverse transform of its
+ * instance, forward with the previous transform, and projected with the previous camera; four bilinear taps of the previous frame's
+ * accumulated colour, variance and history length are kept if they show the same instance and the same surface point (plane distance and
+ * in-plane distance against the pixel footprint), and the current colour is blended in with alpha = max(1 / h, HJR_TEMPORAL_ALPHA),
+ * h = min(h_prev + 1, 64).  The variance is propagated as that of a convex combination of independent estimates; HJR_VARIANCE_UNKNOWN or NaN
+ * on either side gives HJR_VARIANCE_UNKNOWN, negative values act as 0.  A miss, a disocclusion or prev == NULL restarts the pixel:
+ * out = cur colour, cur variance, h = 1.  A sized struct describes either side; all pointers of one call are host pointers
+ * (hjr_temporal_accumulate, synchronous) or device pointers (hjr_temporal_accumulate_device, asynchronous on `hip_stream`).  cur.history is
+ * ignored.  width, height and n_instances must agree between the two sides, else HJR_ERR_ARG.  Outputs: float4 colour (alpha = cur's),
+ * float variance, float history length, width x height each.  Caller-made records are range-checked before any table lookup: an instance
+ * or prim id out of range is a miss (current pixel) or an invalid tap; prim ids are checked against the uploaded scene's triangle count. */
+#define HJR_TEMPORAL_ALPHA 0.2f  /* the published value */
+typedef struct hjr_temporal_frame {
+    uint32_t struct_size, width, height, n_instances;
+    hjr_camera camera;
+    const float *transforms12, *inv_transforms12;   /* n_instances x 12, as hjr_set_transforms */
+    const hjr_gbuffer_px* gbuffer;
+    const float *color /* float4 */, *variance /* float */, *history /* float: frames accumulated */;
+} hjr_temporal_frame;
+int hjr_temporal_accumulate(hjr_ctx*, const hjr_temporal_frame* prev /* NULL = none */, const hjr_temporal_frame* cur, float* out_color,
+                            float* out_variance, float* out_history);
+int hjr_temporal_accumulate_device(hjr_ctx*, const hjr_temporal_frame* prev, const hjr_temporal_frame* cur, void* d_out_color, void* d_out_variance,
+                                   void* d_out_history, void* hip_stream);
+/* Drops the history that option "denoise_temporal" keeps in the context: the next frame restarts everywhere.  So do hjr_upload_scene,
+ * hjr_set_lut, hjr_set_sky, a change of width, height or render mode, and setting the option. */
+int hjr_temporal_reset(hjr_ctx*);
 /* The 8-bit preview buffer of the raygen program — `uchar4* image` of Params, allocated at renderer/renderer.h:1102 and bound at :1175, written
  * by the missing __raygen__rg and never read back by the host.  Build-defined: a float4 colour image on the device -> tonemapper of kernel/color.h
  * (HJR_TONEMAP_*) -> toSRGB + quantise (renderer.h:73-101) -> width*height RGBA8 on the device; asynchronous on `hip_stream` (NULL = the
@@ -418,11 +455,21 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *   "denoise_variance" 0 1        1: hjr_render_denoised renders the variance AOV along with the guides and runs the variance-guided filter
  *                                 (hjr_denoise_var_device) in the two Denoise modes; a sample pass filters the running mean with the variance
  *                                 over n = sample_end.  0 (default): today's call, bit for bit
- *   [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
+ *   "denoise_temporal" 0 1        1: hjr_render_denoised in the two Denoise modes renders guides and the variance AOV (whatever "denoise_variance"
+                                 says), runs the G-buffer pass, accumulates against the history the context keeps (hjr_temporal_accumulate's
+                                 rule), and hands the accumulated colour and variance to the variance-guided filter; DenoiseUpScale2X keeps the
+                                 history at the render size.  A whole-frame render, or the sample pass that ends at spp, makes the current
+                                 frame the previous one; an earlier sample pass reads the history and does not advance it.  The caller
+                                 advances hjr_params.frame between frames: the same frame number twice blends identical samples and the
+                                 propagated variance then understates.  world_size > 1 or HJR_FLAG_PACKED is HJR_ERR_ARG with it;
+                                 HJR_MODE_DEFAULT ignores it.  Setting it (any value) drops the history.  0 (default): today's call, bit for bit
+   [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
- * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name.
+ * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name; "denoise_temporal": true
+ * of that section is stored as hjr_render_option.denoise_variance = 2 and sets both options (refused together with "noise_threshold" > 0:
+ * an adaptive frame that stops early never reaches the pass that advances the history).
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
