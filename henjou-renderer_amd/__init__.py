@@ -116,7 +116,7 @@ class Stats(_Sized):
 
     def as_dict(self):
         names = [n for k in reversed(type(self).__mro__) for n, _ in getattr(k, "_fields_", [])]
-        d = {n: (float(getattr(self, n)) if n in ("last_kernel_ms", "frame_build_ms") else int(getattr(self, n)))
+        d = {n: (float(getattr(self, n)) if n in ("last_kernel_ms", "frame_build_ms", "bvh_sah") else int(getattr(self, n)))
              for n in names if n not in ("struct_size", "_pad0", "nan_where")}
         d["nan_where"] = [tuple(int(v) for v in self.nan_where[i]) for i in range(int(self.nan_located))]  # (x, y, sample)
         return d
@@ -124,8 +124,13 @@ class Stats(_Sized):
 
 class StatsV2(Stats):
     """hjr_stats with the fields appended after `Stats` (the layout up to nan_where).  Both are valid callers under the sized-struct
-    rule: the library writes min(struct_size, its sizeof) bytes.  Device.stats() uses this one."""
+    rule: the library writes min(struct_size, its sizeof) bytes."""
     _fields_ = [("bvh_builder", C.c_uint32), ("frame_build_ms", C.c_float)]
+
+
+class StatsV3(StatsV2):
+    """hjr_stats with the refit fields appended after `StatsV2` (option "device_bvh_refit").  Device.stats() uses this one."""
+    _fields_ = [("bvh_refits", C.c_uint32), ("bvh_sah", C.c_float)]
 
 
 class Adaptive(_Sized):
@@ -635,7 +640,7 @@ class Device:
         return out
 
     def stats(self):
-        st = StatsV2()
+        st = StatsV3()
         _check(lib().hjr_get_stats(self._h, C.byref(st)), "hjr_get_stats")
         return st.as_dict()
 

@@ -53,6 +53,7 @@ struct DeviceBvh {
 struct DeviceBvhResult {
     uint32_t n_nodes = 0, stack_need = 0, depth = 0;
     float build_ms = 0.0f; // HIP-event time of the build's kernels
+    float sah = 0.0f;      // BVH4 SAH of the nodes, computed on the device in a fixed summation order (0: empty scene)
 };
 
 // Enqueues the whole build on `st` behind whatever is already there, waits for it and reads back its header.  HJR_ERR_ARG with `err`
@@ -61,4 +62,11 @@ struct DeviceBvhResult {
 // `opt_rounds` (option "device_bvh_opt", 0..3) treelet-restructuring rounds run over the BVH2 before the collapse; 0 leaves the build as it was.
 int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
                      const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+// Option "device_bvh_refit": the frame data for new transforms over the topology of the CURRENT frame data (`cur_nodes`, `cur_geom`: a
+// device build or refit of the same scene with n_nodes nodes; only the refs rows and the prim ids are read, nothing is written there).
+// Flatten in leaf order, node boxes bottom-up over the BVH4, tree cost; one host wait.  Writes b.nodes / tri_* / lights like the build;
+// r.stack_need and r.depth stay 0 (the topology's, which the caller has).  Errors as device_bvh_build; HJR_ERR_DEVICE when the current
+// data fails a bound.  At least 2 triangles.
+int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const DevBuf& cur_nodes, const DevBuf& cur_geom,
+                     uint32_t n_nodes, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
 } // namespace hjr

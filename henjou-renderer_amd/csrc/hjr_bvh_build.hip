@@ -8,6 +8,9 @@
 //   treelets     ("device_bvh_opt" rounds) Karras & Aila 2013: bottom-up climbs with the same hand-off, a wave per 7-leaf treelet
 //                finds its SAH-optimal topology; then leaf positions and inner ranges are recomputed and tri_geom is gathered in the new order
 //   collapse     BVH4 level by level with emit_bvh4's rules; ids from a scan of each level (breadth-first, same bytes every run)
+//   cost         BVH4 SAH of the final nodes, summed in a fixed order (the same bits every run); also after a refit
+// Refit (option "device_bvh_refit", device_bvh_refit below): new transforms over the CURRENT frame data's topology.  flatten in leaf order
+// (the prim id of every tri_geom row), then the node boxes bottom-up over the BVH4 itself with the hand-off of `boxes`; no sort, no hierarchy.
 // No workgroup ever waits for another one; every cross-launch size the host does not know is read by the kernels from `hdr`.
 #include <hip/hip_runtime.h>
 
@@ -37,7 +40,8 @@ enum Hdr {
     H_BASE = 9,      // first wide id of the current level
     H_F = 10,        // nodes of the current level
     H_NEXT = 11,     // nodes of the next level (scan total)
-    H_ERR = 12,      // non-zero: the restructured BVH2 failed a structural bound (a bug, reported as HJR_ERR_DEVICE)
+    H_ERR = 12,      // non-zero: the restructured BVH2, or the BVH4 a refit walks, failed a structural bound (reported as HJR_ERR_DEVICE)
+    H_SAH = 13,      // float bits: BVH4 SAH of the final nodes (sah_top_kernel)
     H_WORDS = 16
 };
 
@@ -132,6 +136,40 @@ struct FlattenArgs {
     uint32_t *inst, *hdr;
 };
 
+// triangle t under its instance's transform: world vertices v[9], shading record s[16]; returns the instance
+__device__ __forceinline__ uint32_t flatten_tri(const FlattenArgs& a, uint32_t t, float* v, float* s)
+{
+    uint32_t lo = 0, hi = a.n_inst; // last prim_offset <= t (prim_offset[0] == 0)
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.prim_off[mid] <= t) lo = mid; else hi = mid; }
+    const float* m = a.xf + 24 * (size_t)lo;
+    const float* mi = m + 12;
+    float uv[6];
+    for (int k = 0; k < 3; k++) {
+        const uint32_t ix = a.idx[3 * (size_t)t + k];
+        xform_pos(m, a.vert[3 * (size_t)ix], a.vert[3 * (size_t)ix + 1], a.vert[3 * (size_t)ix + 2], &v[3 * k]);
+        float nn[3];
+        xform_nrm(mi, a.norm[3 * (size_t)ix], a.norm[3 * (size_t)ix + 1], a.norm[3 * (size_t)ix + 2], nn);
+        const float inv = 1.0f / sqrtf(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
+        s[4 * k + 0] = nn[0] * inv; s[4 * k + 1] = nn[1] * inv; s[4 * k + 2] = nn[2] * inv;
+        uv[2 * k] = a.uv[2 * (size_t)ix]; uv[2 * k + 1] = a.uv[2 * (size_t)ix + 1];
+    }
+    s[3] = uv[0]; s[7] = uv[1]; s[11] = uv[2];
+    s[12] = uv[3]; s[13] = uv[4]; s[14] = uv[5];
+    s[15] = __uint_as_float(a.mat[t]);
+    return lo;
+}
+// unpadded box of the triangle; returns its max |coordinate|
+__device__ __forceinline__ float tri_box(const float* v, float* bl, float* bh)
+{
+    float mx = 0.0f;
+    for (int ax = 0; ax < 3; ax++) {
+        bl[ax] = 3.402823466e+38f; bh[ax] = -3.402823466e+38f;
+        for (int k = 0; k < 3; k++) { bl[ax] = smin(bl[ax], v[3 * k + ax]); bh[ax] = smax(bh[ax], v[3 * k + ax]); }
+    }
+    for (int ax = 0; ax < 3; ax++) mx = smax(mx, smax(fabsf(bl[ax]), fabsf(bh[ax])));
+    return mx;
+}
+
 __global__ void __launch_bounds__(NT) flatten_kernel(FlattenArgs a)
 {
     __shared__ uint32_t s_red[7];
@@ -139,36 +177,15 @@ __global__ void __launch_bounds__(NT) flatten_kernel(FlattenArgs a)
     __syncthreads();
     const uint32_t t = blockIdx.x * NT + threadIdx.x;
     if (t < a.n) {
-        uint32_t lo = 0, hi = a.n_inst; // last prim_offset <= t (prim_offset[0] == 0)
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.prim_off[mid] <= t) lo = mid; else hi = mid; }
-        const float* m = a.xf + 24 * (size_t)lo;
-        const float* mi = m + 12;
-        float v[9], s[16], uv[6];
-        for (int k = 0; k < 3; k++) {
-            const uint32_t ix = a.idx[3 * (size_t)t + k];
-            xform_pos(m, a.vert[3 * (size_t)ix], a.vert[3 * (size_t)ix + 1], a.vert[3 * (size_t)ix + 2], &v[3 * k]);
-            float nn[3];
-            xform_nrm(mi, a.norm[3 * (size_t)ix], a.norm[3 * (size_t)ix + 1], a.norm[3 * (size_t)ix + 2], nn);
-            const float inv = 1.0f / sqrtf(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
-            s[4 * k + 0] = nn[0] * inv; s[4 * k + 1] = nn[1] * inv; s[4 * k + 2] = nn[2] * inv;
-            uv[2 * k] = a.uv[2 * (size_t)ix]; uv[2 * k + 1] = a.uv[2 * (size_t)ix + 1];
-        }
-        s[3] = uv[0]; s[7] = uv[1]; s[11] = uv[2];
-        s[12] = uv[3]; s[13] = uv[4]; s[14] = uv[5];
-        s[15] = __uint_as_float(a.mat[t]);
+        float v[9], s[16];
+        const uint32_t lo = flatten_tri(a, t, v, s);
         float4* sd = reinterpret_cast<float4*>(a.shade) + 4 * (size_t)t;
         for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
         for (int k = 0; k < 9; k++) a.wv[9 * (size_t)t + k] = v[k];
         a.inst[t] = lo;
-        float bl[3], bh[3], c[3], mx = 0.0f;
-        for (int ax = 0; ax < 3; ax++) {
-            bl[ax] = 3.402823466e+38f; bh[ax] = -3.402823466e+38f;
-            for (int k = 0; k < 3; k++) { bl[ax] = smin(bl[ax], v[3 * k + ax]); bh[ax] = smax(bh[ax], v[3 * k + ax]); }
-        }
-        for (int ax = 0; ax < 3; ax++) {
-            c[ax] = 0.5f * (bl[ax] + bh[ax]);
-            mx = smax(mx, smax(fabsf(bl[ax]), fabsf(bh[ax])));
-        }
+        float bl[3], bh[3], c[3];
+        const float mx = tri_box(v, bl, bh);
+        for (int ax = 0; ax < 3; ax++) c[ax] = 0.5f * (bl[ax] + bh[ax]);
         float4* bd = reinterpret_cast<float4*>(a.box) + 2 * (size_t)t;
         bd[0] = make_float4(bl[0], bl[1], bl[2], 0.0f);
         bd[1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
@@ -751,9 +768,197 @@ __global__ void collapse_init_kernel(uint32_t n, Front* fr, uint32_t* hdr)
     hdr[H_BASE] = 0;
     hdr[H_F] = 1;
 }
+__global__ void set_word_kernel(uint32_t* w, uint32_t v) { *w = v; }
 __global__ void hdr_init_kernel(uint32_t* hdr)
 {
     if (threadIdx.x < H_WORDS) hdr[threadIdx.x] = threadIdx.x >= H_CMIN && threadIdx.x < H_CMAX ? 0xffffffffu : 0u;
+}
+
+// ---- tree cost: BVH4 SAH of the final nodes (tools/device_bvh_bench.py::bvh4_sah) -------------------------------------------------
+// Ci per inner slot, Ct per triangle of a leaf slot, by slot area; sah_top_kernel divides by the root's area.  fp32 in a fixed order:
+// a lane adds its nodes' terms in index order, then block_sum's tree, then the SCAN_G partial sums through the same tree.  No float
+// atomics: the value has the same bits on every run and after a build and a refit that wrote the same nodes.
+__device__ __forceinline__ float slot_area(float lx, float hx, float ly, float hy, float lz, float hz)
+{
+    const float dx = fmaxf(hx - lx, 0.0f), dy = fmaxf(hy - ly, 0.0f), dz = fmaxf(hz - lz, 0.0f);
+    return 2.0f * (dx * dy + dy * dz + dz * dx);
+}
+__device__ __forceinline__ uint32_t ref_of(const float4& r, int c)
+{
+    return __float_as_uint(c == 0 ? r.x : (c == 1 ? r.y : (c == 2 ? r.z : r.w)));
+}
+__device__ __forceinline__ float f4_at(const float4& r, int c) { return c == 0 ? r.x : (c == 1 ? r.y : (c == 2 ? r.z : r.w)); }
+__device__ __forceinline__ bool ref_inner(uint32_t ref) { return !(ref & HJR_LEAF_FLAG); }
+__device__ __forceinline__ uint32_t inner_slots(const float4& r)
+{
+    return (ref_inner(__float_as_uint(r.x)) ? 1u : 0u) + (ref_inner(__float_as_uint(r.y)) ? 1u : 0u) + (ref_inner(__float_as_uint(r.z)) ? 1u : 0u) +
+           (ref_inner(__float_as_uint(r.w)) ? 1u : 0u);
+}
+__device__ __forceinline__ float node_sah_term(const float4* nd)
+{
+    const float4 r = nd[6];
+    float term = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const uint32_t ref = ref_of(r, c);
+        if (ref == HJR_LEAF_FLAG) continue;
+        const float w = ref_inner(ref) ? SAH_CI : SAH_CT * (float)((ref >> 27) & 15u);
+        term += w * slot_area(f4_at(nd[0], c), f4_at(nd[1], c), f4_at(nd[2], c), f4_at(nd[3], c), f4_at(nd[4], c), f4_at(nd[5], c));
+    }
+    return term;
+}
+// sum over a 256-thread workgroup in a fixed tree; `s` holds 4 floats of LDS
+__device__ float block_sum(float v, float* s)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float t = (s[0] + s[1]) + (s[2] + s[3]);
+    __syncthreads();
+    return t;
+}
+// `counter` (refit only, else null): a node whose inner children did not all arrive was never written -> H_ERR
+__global__ void __launch_bounds__(NT) sah_reduce_kernel(const float4* nodes, const uint32_t* n_ptr, uint32_t cap, const uint32_t* counter, float* part, uint32_t* hdr)
+{
+    __shared__ float s[4];
+    const uint32_t n = min(*n_ptr, cap);
+    uint32_t b0, b1;
+    scan_range(n, b0, b1);
+    float acc = 0.0f;
+    bool bad = false;
+    for (uint32_t i = b0 + threadIdx.x; i < b1; i += NT) {
+        const float4* nd = nodes + (size_t)i * HJR_NODE4_F4;
+        acc += node_sah_term(nd);
+        if (counter && counter[i] != inner_slots(nd[6])) bad = true;
+    }
+    if (bad) atomicOr(&hdr[H_ERR], 64u);
+    const float tot = block_sum(acc, s);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(NT) sah_top_kernel(const float4* nodes, const float* part, uint32_t* hdr)
+{
+    __shared__ float s[4];
+    const float tot = block_sum(part[threadIdx.x], s);
+    if (threadIdx.x == 0) {
+        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
+        for (int c = 0; c < 4; c++) {
+            if (ref_of(nodes[6], c) == HJR_LEAF_FLAG) continue;
+            for (int ax = 0; ax < 3; ax++) { lo[ax] = smin(lo[ax], f4_at(nodes[2 * ax], c)); hi[ax] = smax(hi[ax], f4_at(nodes[2 * ax + 1], c)); }
+        }
+        const float ra = slot_area(lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]);
+        hdr[H_SAH] = __float_as_uint(ra > 0.0f ? tot / ra : 0.0f);
+    }
+}
+
+// ---- refit (option "device_bvh_refit"): new transforms, the current tree ---------------------------------------------------------
+// Every index read from the current frame data is checked before it is used; a violated bound sets an H_ERR bit and the commit fails.
+struct RefitArgs {
+    FlattenArgs f;           // scene, transforms, shade / inst / hdr (wv, box, cent unused)
+    uint32_t n_nodes;
+    const float4 *cur_nodes, *cur_geom; // the current frame data: only the refs rows and the prim ids are read
+    float4 *nodes, *geom;    // the builder's output
+    uint32_t *parent, *counter; // per node: 4 * parent + slot | inner children that have arrived
+};
+// flatten in leaf order: row d takes the triangle the current row d holds
+__global__ void __launch_bounds__(NT) refit_flatten_kernel(RefitArgs a)
+{
+    __shared__ uint32_t s_max;
+    if (threadIdx.x == 0) s_max = 0u;
+    __syncthreads();
+    const uint32_t d = blockIdx.x * NT + threadIdx.x;
+    if (d < a.f.n) {
+        const uint32_t t = __float_as_uint(a.cur_geom[HJR_TRI_F4 * (size_t)d + 2].y);
+        if (t >= a.f.n) atomicOr(&a.f.hdr[H_ERR], 4u);
+        else {
+            float v[9], s[16], bl[3], bh[3];
+            const uint32_t inst = flatten_tri(a.f, t, v, s);
+            float4* sd = reinterpret_cast<float4*>(a.f.shade) + 4 * (size_t)t;
+            for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+            a.f.inst[t] = inst;
+            float4* g = a.geom + HJR_TRI_F4 * (size_t)d;
+            g[0] = make_float4(v[0], v[1], v[2], v[3]);
+            g[1] = make_float4(v[4], v[5], v[6], v[7]);
+            g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(a.f.mat[t]), 0.0f);
+            atomicMax(&s_max, __float_as_uint(tri_box(v, bl, bh)));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) atomicMax(&a.f.hdr[H_SMAX], s_max);
+}
+// parent and slot of every node from the refs, and the refs' bounds: ids are breadth-first, so a child's id is above its parent's
+__global__ void __launch_bounds__(NT) refit_parent_kernel(RefitArgs a)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i >= a.n_nodes) return;
+    const float4 r = a.cur_nodes[(size_t)i * HJR_NODE4_F4 + 6];
+    uint32_t err = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const uint32_t ref = ref_of(r, c);
+        if (ref_inner(ref)) {
+            if (ref <= i || ref >= a.n_nodes) err |= 8u;
+            else a.parent[ref] = 4u * i + (uint32_t)c;
+        } else if ((ref & 0x7ffffffu) + ((ref >> 27) & 15u) > a.f.n) err |= 16u;
+    }
+    if (err) atomicOr(&a.f.hdr[H_ERR], err);
+}
+// writes node i of the output: refs unchanged, leaf slots from the new triangles, inner slots from the child nodes already written
+__device__ __forceinline__ void refit_node(const RefitArgs& a, uint32_t i, const float4& r, float pad)
+{
+    float q[24];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const uint32_t ref = ref_of(r, c);
+        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f }; // unused slot: inverted box
+        if (ref_inner(ref)) {
+            if (ref > i && ref < a.n_nodes) { // an unused slot of the child (1e30 / -1e30) changes no min / max
+                const float4* ch = a.nodes + (size_t)ref * HJR_NODE4_F4;
+                for (int ax = 0; ax < 3; ax++) {
+                    const float4 l = ch[2 * ax], h = ch[2 * ax + 1];
+                    lo[ax] = smin(smin(l.x, l.y), smin(l.z, l.w));
+                    hi[ax] = smax(smax(h.x, h.y), smax(h.z, h.w));
+                }
+            }
+        } else if (ref != HJR_LEAF_FLAG) {
+            const uint32_t first = ref & 0x7ffffffu, cnt = (ref >> 27) & 15u;
+            if (first + cnt <= a.f.n && cnt > 0) {
+                for (int ax = 0; ax < 3; ax++) { lo[ax] = 3.402823466e+38f; hi[ax] = -3.402823466e+38f; }
+                for (uint32_t k = 0; k < cnt; k++) {
+                    const float4* g = a.geom + HJR_TRI_F4 * (size_t)(first + k);
+                    const float4 g0 = g[0], g1 = g[1], g2 = g[2];
+                    lo[0] = smin(smin(lo[0], g0.x), smin(g0.w, g1.z)); hi[0] = smax(smax(hi[0], g0.x), smax(g0.w, g1.z));
+                    lo[1] = smin(smin(lo[1], g0.y), smin(g1.x, g1.w)); hi[1] = smax(smax(hi[1], g0.y), smax(g1.x, g1.w));
+                    lo[2] = smin(smin(lo[2], g0.z), smin(g1.y, g2.x)); hi[2] = smax(smax(hi[2], g0.z), smax(g1.y, g2.x));
+                }
+                for (int ax = 0; ax < 3; ax++) { lo[ax] -= pad; hi[ax] += pad; }
+            }
+        }
+        for (int ax = 0; ax < 3; ax++) { q[8 * ax + c] = lo[ax]; q[8 * ax + 4 + c] = hi[ax]; }
+    }
+    float4* o = a.nodes + (size_t)i * HJR_NODE4_F4;
+    for (int v = 0; v < 6; v++) o[v] = make_float4(q[4 * v], q[4 * v + 1], q[4 * v + 2], q[4 * v + 3]);
+    o[6] = r;
+}
+// One lane per node without inner children starts there and climbs while it is the last inner child to reach the parent: boxes_kernel's
+// hand-off.  The lane stores the node it finished, then its agent-scope acq_rel add on the parent's counter releases those stores and,
+// for the last arriver, acquires the siblings' before it reads their nodes.  A parent id is below the child's, so every climb ends.
+__global__ void __launch_bounds__(NT) refit_boxes_kernel(RefitArgs a)
+{
+    uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i >= a.n_nodes) return;
+    float4 r = a.cur_nodes[(size_t)i * HJR_NODE4_F4 + 6];
+    if (inner_slots(r) != 0) return;
+    const float pad = __uint_as_float(a.f.hdr[H_SMAX]) * (1.0f / 8192.0f);
+    for (;;) {
+        refit_node(a, i, r, pad);
+        if (i == 0) return;
+        const uint32_t p = a.parent[i] >> 2;
+        if (p >= i) { atomicOr(&a.f.hdr[H_ERR], 32u); return; } // not the parent pass's value: no slot refers to this node
+        r = a.cur_nodes[(size_t)p * HJR_NODE4_F4 + 6];
+        const uint32_t before = __hip_atomic_fetch_add(&a.counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before + 1u != inner_slots(r)) return; // a sibling's lane finishes the parent
+        i = p;
+    }
 }
 
 inline unsigned blocks_for(size_t n) { return (unsigned)std::max<size_t>(1, (n + NT - 1) / NT); }
@@ -787,6 +992,14 @@ static int scan(uint32_t* in_out, const uint32_t* n_ptr, uint32_t n_const, uint3
     hipLaunchKernelGGL(scan_down_kernel, dim3(SCAN_G), dim3(NT), 0, st, in_out, in_out, n_ptr, n_const, part);
     DCHK(hipGetLastError());
     return HJR_OK;
+}
+
+// the tree cost of `nodes` (their count at *n_ptr, at most cap) into hdr[H_SAH]
+static void launch_sah(DeviceBvh& b, const float4* nodes, const uint32_t* n_ptr, uint32_t cap, const uint32_t* counter, hipStream_t st)
+{
+    uint32_t* hdr = (uint32_t*)b.hdr.p;
+    hipLaunchKernelGGL(sah_reduce_kernel, dim3(SCAN_G), dim3(NT), 0, st, nodes, n_ptr, cap, counter, (float*)b.part.p, hdr);
+    hipLaunchKernelGGL(sah_top_kernel, dim3(1), dim3(NT), 0, st, nodes, (const float*)b.part.p, hdr);
 }
 
 int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
@@ -911,6 +1124,8 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         DCHK(hipMemcpyAsync(&F, hdr + H_F, 4, hipMemcpyDeviceToHost, st));
         DCHK(hipStreamSynchronize(st));
     }
+    launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, (uint32_t)nn, nullptr, st);
+    DCHK(hipGetLastError());
     DCHK(hipEventRecord(b.ev1, st));
     uint32_t h[H_WORDS];
     DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -920,9 +1135,65 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
     if (h[H_ERR]) { err = "device BVH: the restructured tree failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
     r.n_nodes = h[H_BASE];
+    r.sah = __builtin_bit_cast(float, h[H_SAH]);
     r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
     r.depth = h[H_DEPTH];
     if (F > 0 || r.stack_need > DEVICE_BVH_MAX_STACK) { err = "BVH deeper than the traversal stack"; return HJR_ERR_ARG; }
+    return HJR_OK;
+}
+
+int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const DevBuf& cur_nodes, const DevBuf& cur_geom,
+                     uint32_t n_nodes, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+{
+    const uint32_t n = sc.n_triangles;
+    r = DeviceBvhResult();
+    const size_t node_bytes = (size_t)n_nodes * HJR_NODE4_F4 * 16, geom_bytes = (size_t)n * HJR_TRI_F4 * 16;
+    if (!b.have_scene || !b.ev0 || !b.ev1 || n < 2 || n_nodes == 0 || n_nodes > n || cur_nodes.cap < node_bytes || cur_geom.cap < geom_bytes) {
+        err = "device BVH refit: no device-built frame data of this scene";
+        return HJR_ERR_DEVICE;
+    }
+    std::vector<float> xf((size_t)n_inst * 24);
+    for (uint32_t i = 0; i < n_inst; i++) {
+        memcpy(&xf[24 * (size_t)i], M + 12 * (size_t)i, 48);
+        memcpy(&xf[24 * (size_t)i + 12], Mi + 12 * (size_t)i, 48);
+    }
+    if (!b.xf.upload(xf.data(), xf.size() * 4, st) || !b.lights.upload(lights, light_floats * 4, st) || !b.hdr.reserve(H_WORDS * 4) || !b.nodes.reserve(node_bytes) ||
+        !b.tri_geom.reserve(geom_bytes) || !b.tri_shade.reserve((size_t)n * HJR_SHADE_F4 * 16) || !b.tri_inst.reserve((size_t)n * 4) ||
+        !b.parent.reserve((size_t)n_nodes * 4) || !b.counter.reserve((size_t)n_nodes * 4) || !b.part.reserve(SCAN_G * 4)) {
+        err = "device BVH: allocation or upload failed";
+        return HJR_ERR_DEVICE;
+    }
+    uint32_t* hdr = (uint32_t*)b.hdr.p;
+    RefitArgs a;
+    a.f.vert = (const float*)b.vert.p; a.f.norm = (const float*)b.norm.p; a.f.uv = (const float*)b.uv.p; a.f.xf = (const float*)b.xf.p;
+    a.f.idx = (const uint32_t*)b.idx.p; a.f.mat = (const uint32_t*)b.mat.p; a.f.prim_off = (const uint32_t*)b.prim_off.p;
+    a.f.n = n; a.f.n_inst = n_inst;
+    a.f.wv = nullptr; a.f.box = nullptr; a.f.cent = nullptr;
+    a.f.shade = (float*)b.tri_shade.p; a.f.inst = (uint32_t*)b.tri_inst.p; a.f.hdr = hdr;
+    a.n_nodes = n_nodes;
+    a.cur_nodes = (const float4*)cur_nodes.p; a.cur_geom = (const float4*)cur_geom.p;
+    a.nodes = (float4*)b.nodes.p; a.geom = (float4*)b.tri_geom.p;
+    a.parent = (uint32_t*)b.parent.p; a.counter = (uint32_t*)b.counter.p;
+    DCHK(hipEventRecord(b.ev0, st));
+    hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
+    DCHK(hipMemsetAsync(b.parent.p, 0xff, (size_t)n_nodes * 4, st)); // a node no slot refers to has no parent below it
+    DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)n_nodes * 4, st));
+    hipLaunchKernelGGL(refit_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(refit_parent_kernel, dim3(blocks_for(n_nodes)), dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(refit_boxes_kernel, dim3(blocks_for(n_nodes)), dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, st, hdr + H_BASE, n_nodes);
+    launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, n_nodes, (const uint32_t*)b.counter.p, st);
+    DCHK(hipGetLastError());
+    DCHK(hipEventRecord(b.ev1, st));
+    uint32_t h[H_WORDS];
+    DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st)); // the refit's one host wait
+    DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
+    const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
+    if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
+    if (h[H_ERR]) { err = "device BVH refit: the current tree failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
+    r.n_nodes = n_nodes;
+    r.sah = __builtin_bit_cast(float, h[H_SAH]);
     return HJR_OK;
 }
 

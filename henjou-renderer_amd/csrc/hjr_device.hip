@@ -146,6 +146,7 @@ extern "C" int hjr_upload_scene(hjr_ctx* c, const hjr_scene_view* v)
     c->have_scene = true;
     c->have_frame = false;
     c->dbvh.have_scene = false; // the device builder uploads the new scene at its next build
+    c->refit = hjr_ctx::Refit(); // ... which is a full one
     return HJR_OK;
 }
 
@@ -203,19 +204,37 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
 // option "device_bvh": the build of the prepared transforms as kernels on the context's stream, behind what is already queued there.
 // It writes the builder's own buffers; they become current (swapped with d_nodes, d_tri_*, d_lights) only when it succeeds, so a
 // failed build leaves the previous frame current.
+// Option "device_bvh_refit": up to that many consecutive commits after a full build keep its topology and refit the boxes
+// (hjr::device_bvh_refit), while the current data is a device build of this scene with these build options and the cost guard holds.
 static int commit_device(hjr_ctx* c)
 {
     const int leaf_max = c->opt.get(hjr::OPT_LEAF_MAX, (int)HJR_LEAF_DEFAULT);
     const int opt_rounds = c->opt.get(hjr::OPT_DEVICE_BVH_OPT, 0); // option "device_bvh_opt": treelet-restructuring rounds
+    const uint32_t limit = (uint32_t)c->opt.get(hjr::OPT_DEVICE_BVH_REFIT, 0);
+    const uint32_t n_inst = (uint32_t)(c->pending_m.size() / 12);
+    hjr_ctx::Refit& rf = c->refit;
+    const bool refit = c->have_frame && rf.device && c->dbvh.have_scene && !rf.rebuild && rf.count < limit && rf.tag == c->pending_build_tag &&
+                       c->last_m.size() == c->pending_m.size() && c->scene.n_triangles >= 2 && c->frame.n_tris == c->scene.n_triangles;
     hjr::DeviceBvhResult r;
     std::string err;
     hjr::FrameData& f = c->pending;
-    const int rc = hjr::device_bvh_build(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), (uint32_t)(c->pending_m.size() / 12), (uint32_t)leaf_max,
-                                         (uint32_t)opt_rounds, f.lights.data(), f.lights.size(), c->stream, r, err);
+    const int rc = refit ? hjr::device_bvh_refit(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, c->d_nodes, c->d_tri_geom, c->frame.n_nodes,
+                                                 f.lights.data(), f.lights.size(), c->stream, r, err)
+                         : hjr::device_bvh_build(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds,
+                                                 f.lights.data(), f.lights.size(), c->stream, r, err);
     if (rc != HJR_OK) { set_error("hjr_set_transforms: " + err); return rc; }
     c->d_nodes.swap(c->dbvh.nodes); c->d_tri_geom.swap(c->dbvh.tri_geom); c->d_tri_shade.swap(c->dbvh.tri_shade);
     c->d_tri_inst.swap(c->dbvh.tri_inst); c->d_lights.swap(c->dbvh.lights);
-    f.n_nodes = r.n_nodes; f.stack_need = r.stack_need; f.depth = r.depth;
+    if (refit) { // the topology's
+        f.n_nodes = c->frame.n_nodes; f.stack_need = c->frame.stack_need; f.depth = c->frame.depth;
+        rf.count++;
+        // the refit just made stays current; a tree that has grown past the guard is rebuilt at the next commit
+        rf.rebuild = (double)r.sah > (double)rf.sah_full * (1.0 + c->opt.get(hjr::OPT_DEVICE_BVH_REFIT_GROWTH, 10) / 100.0);
+    } else {
+        f.n_nodes = r.n_nodes; f.stack_need = r.stack_need; f.depth = r.depth;
+        rf.device = true; rf.rebuild = false; rf.count = 0; rf.tag = c->pending_build_tag; rf.sah_full = r.sah;
+    }
+    rf.sah = r.sah;
     c->pending_build_ms = r.build_ms;
     return HJR_OK;
 }
@@ -236,6 +255,7 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
         std::swap(c->frame, c->pending);
     } else {
         std::swap(c->frame, c->pending);
+        c->refit = hjr_ctx::Refit(); // host-built data: nothing to refit
         const hjr::FrameData& f = c->frame;
         bool ok = c->d_nodes.upload(f.nodes.data(), f.nodes.size() * 4, c->stream) &&
                   c->d_tri_geom.upload(f.tri_geom.data(), f.tri_geom.size() * 4, c->stream) &&
@@ -252,10 +272,13 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
     c->stats.bvh_depth = f.depth;
     c->stats.bvh_builder = c->pending_device ? 1u : 0u;
     c->stats.frame_build_ms = (float)c->pending_build_ms;
+    c->stats.bvh_refits = c->refit.count;
+    c->stats.bvh_sah = c->refit.sah;
+    const bool refitted = c->pending_device && c->refit.count > 0;
     if (c->opt.get(hjr::OPT_VERBOSE, 0))
-        fprintf(stderr, "[hjr] BVH%u (lds_mode %d): %u nodes (%zu KB), %u triangles (%zu KB), stack %u entries/lane, %s build %.1f ms\n", f.width, f.lds_mode, f.n_nodes,
+        fprintf(stderr, "[hjr] BVH%u (lds_mode %d): %u nodes (%zu KB), %u triangles (%zu KB), stack %u entries/lane, %s %s %.1f ms\n", f.width, f.lds_mode, f.n_nodes,
                 (size_t)f.n_nodes * (f.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4) * 16 / 1024, f.n_tris, (size_t)std::max(f.n_tris, 1u) * HJR_TRI_F4 * 16 / 1024,
-                f.stack_need, c->pending_device ? "device" : "host", c->pending_build_ms);
+                f.stack_need, c->pending_device ? "device" : "host", refitted ? "refit" : "build", c->pending_build_ms);
     c->stats.n_triangles = f.n_tris;
     return HJR_OK;
 }

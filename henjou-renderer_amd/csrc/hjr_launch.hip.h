@@ -50,6 +50,14 @@ struct hjr_ctx {
     bool pending_device = false; // option "device_bvh": hjr_commit_transforms runs the build (pending.lights is the host-built light table)
     hjr::FrameData frame; // device-built frame data: the counts, format and lights only (the arrays live in d_nodes, d_tri_*)
     hjr::DeviceBvh dbvh;  // the device builder's scene copy, scratch and pending output buffers
+    // option "device_bvh_refit": what the next commit needs to know about the current frame data
+    struct Refit {
+        bool device = false;   // it came from a device build or refit (of the scene dbvh holds while dbvh.have_scene)
+        bool rebuild = false;  // the growth guard tripped: the next commit is a full build
+        uint32_t tag = 0;      // build tag of its last full build
+        uint32_t count = 0;    // consecutive refits behind it
+        float sah = 0.0f, sah_full = 0.0f; // its tree cost, its last full build's
+    } refit;
     DevBuf d_nodes, d_tri_geom, d_tri_shade, d_tri_inst, d_materials, d_lights, d_lut, d_work;
     DevBuf d_texels, d_tex_desc, d_srgb_lut, d_sky;
     int sky_w = 0, sky_h = 0;

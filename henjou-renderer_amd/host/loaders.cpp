@@ -132,7 +132,16 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             o.serial_io = flag("serial_io") ? 1 : 0;
             o.fast_math = flag("fast_math") ? 1 : 0;
             o.force_rebuild = flag("force_rebuild") ? 1 : 0;
+            if (flag("verbose")) o.force_rebuild |= 2; // option "verbose" (one stderr line per frame-data build); the struct does not grow for it
             o.device_bvh = flag("device_bvh") ? 1 : 0; // the frame data built on the device (option "device_bvh")
+            // device_bvh_refit: consecutive refits between two device builds (option "device_bvh_refit"), stored as device_bvh = 1 + N:
+            // the struct does not grow for it and every reader takes non-zero as "device build"
+            if (const Json* v = h->find("device_bvh_refit")) {
+                const double n = v->is_number() ? v->as_number() : -1.0;
+                if (!(n >= 0 && n <= 1000) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.device_bvh_refit must be an integer in [0, 1000]");
+                if (!o.device_bvh) throw JsonError("Henjou_HIP.device_bvh_refit needs \"device_bvh\": true");
+                o.device_bvh = 1 + (int32_t)n;
+            }
             o.denoise_variance = flag("denoise_variance") ? 1 : 0; // the variance-guided filter in the Denoise modes (option "denoise_variance")
             if (flag("denoise_temporal")) o.denoise_variance = 2; // ... plus temporal accumulation (option "denoise_temporal"); the struct does not grow for it
             // device_bvh_opt: treelet-restructuring rounds of the device build (option "device_bvh_opt")

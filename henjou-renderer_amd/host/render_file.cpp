@@ -62,8 +62,10 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     hjr_scene_view view;
     HJR_INIT(view);
     hjr_scene_get_view(scene, &view);
-    if (opt.force_rebuild) (void)hjr_set_option(ctx, "force_rebuild", 1);
+    if (opt.force_rebuild & 1) (void)hjr_set_option(ctx, "force_rebuild", 1);
+    if (opt.force_rebuild & 2) (void)hjr_set_option(ctx, "verbose", 1); // key "verbose": stored as bit 1
     if (opt.device_bvh) (void)hjr_set_option(ctx, "device_bvh", 1);
+    if (opt.device_bvh > 1) (void)hjr_set_option(ctx, "device_bvh_refit", opt.device_bvh - 1); // key "device_bvh_refit": stored as 1 + N
     if (opt.device_bvh_opt) (void)hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt);
     if (opt.denoise_variance && opt.render_mode != HJR_MODE_DEFAULT) (void)hjr_set_option(ctx, "denoise_variance", 1); // (Default mode has no filter)
     if (temporal) (void)hjr_set_option(ctx, "denoise_temporal", 1);

@@ -136,8 +136,10 @@ typedef struct hjr_render_option {
     uint32_t tile;               /* shard granularity in pixels; 8 is the only supported value */
     int32_t serial_io;           /* default 0; 1: hjr_render_file renders, writes and prepares the next frame one after the other (no overlap) */
     int32_t fast_math;           /* default 0; 1: hjr_render_file / henjou_cli launch with HJR_FLAG_FAST_MATH */
-    int32_t force_rebuild;       /* default 0; 1: hjr_render_file rebuilds the frame data every frame even when nothing moved (benchmarking) */
-    int32_t device_bvh;          /* default 0; 1: hjr_render_file / henjou_cli build the frame data on the device (option "device_bvh") */
+    int32_t force_rebuild;       /* default 0; bit 0: hjr_render_file rebuilds the frame data every frame even when nothing moved (benchmarking);
+                                  * bit 1: hjr_render_file / henjou_cli set the context option "verbose" (key "verbose": true; the struct does not grow for it) */
+    int32_t device_bvh;          /* default 0; 1: hjr_render_file / henjou_cli build the frame data on the device (option "device_bvh");
+                                  * 1 + N: that and option "device_bvh_refit" N (key "device_bvh_refit": N; the struct does not grow for it) */
     int32_t device_bvh_opt;      /* default 0; 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt") */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
@@ -272,7 +274,10 @@ typedef struct hjr_stats {
     uint32_t fast_math;          /* 1: the last launch ran the HJR_FLAG_FAST_MATH kernels */
     uint32_t nan_where[8][3];
     uint32_t bvh_builder;        /* who built the current frame data: 0 = host threads, 1 = device kernels (option "device_bvh") */
-    float    frame_build_ms;     /* its build time: host wall time of flatten + BVH build, or HIP-event time of the device build */
+    float    frame_build_ms;     /* its build time: host wall time of flatten + BVH build, or HIP-event time of the device build or refit */
+    uint32_t bvh_refits;         /* consecutive refits behind the current frame data (option "device_bvh_refit"); 0 = a full build */
+    float    bvh_sah;            /* BVH4 SAH of a device-built or refitted tree, computed on the device (Ci 1.2 per inner slot, Ct 1 per triangle
+                                  * of a leaf slot, slot area over root area; the same bits every run); 0 for host-built data */
 } hjr_stats;
 
 typedef struct hjr_scene hjr_scene; /* owning, host side (SceneData + animations) */
@@ -452,6 +457,15 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *                                 (Karras & Aila 2013; 0 = the plain Morton tree, the default).  Same frames, a better tree: on a 1 M-triangle
  *                                 scene 1 round took the build from 5.5 to 10.4 ms and the render from 151 to 135 ms.  The host build
  *                                 ignores it                                                                                   [*]
+ *   "device_bvh_refit" 0..1000    with "device_bvh" 1: after a full device build, up to this many consecutive commits keep its topology and
+ *                                 refit it (new triangles in the same leaf order, node boxes bottom-up, one host wait) instead of building;
+ *                                 the next commit builds again.  Frames do not depend on the tree, so they stay the same bits.  A commit
+ *                                 refits only while the current data is a device build or refit of the same uploaded scene under the same
+ *                                 build options and instance count, the scene has at least 2 triangles and the cost guard below holds;
+ *                                 "force_rebuild" still only means "do not skip unchanged transforms".  hjr_stats.bvh_refits / bvh_sah
+ *                                 report it; bvh_builder stays 1.  0 (default): every commit builds.  The host build ignores it        [*]
+ *   "device_bvh_refit_growth" 0..10000  percent (default 10): when a refit's tree cost (hjr_stats.bvh_sah) exceeds the last full build's by
+ *                                 more than this, the NEXT commit is a full build; the refit just made stays current                   [*]
  *   "denoise_variance" 0 1        1: hjr_render_denoised renders the variance AOV along with the guides and runs the variance-guided filter
  *                                 (hjr_denoise_var_device) in the two Denoise modes; a sample pass filters the running mean with the variance
  *                                 over n = sample_end.  0 (default): today's call, bit for bit
@@ -467,6 +481,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
+ * "device_bvh_refit": N (integer 0..1000, only together with "device_bvh": true) of that section is stored as hjr_render_option.device_bvh
+ * = 1 + N (the struct does not grow for it): hjr_render_file and henjou_cli set "device_bvh" 1 and "device_bvh_refit" N.
  * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name; "denoise_temporal": true
  * of that section is stored as hjr_render_option.denoise_variance = 2 and sets both options (refused together with "noise_threshold" > 0:
  * an adaptive frame that stops early never reaches the pass that advances the history).
