@@ -108,142 +108,18 @@ __global__ void __launch_bounds__(256) hjr_cost_scatter_kernel(const KParams P)
     if (live) P.tile_order_w[base[b] + rank_in_block] = idx * P.world + P.rank;
 }
 
-// Adds the chunk sums of every owned pixel in chunk order and scales by 1/spp: a fixed summation
-// tree, so the frame is bitwise independent of which lane/wave/GPU rendered which chunk.  Streaming kernel: one lane
-// per pixel of an owned tile, n_chunks coalesced float4 loads ([chunk][owned tile][64] layout), one float4 store.
-__global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P)
+// ---- slot -> pixel.  Everything behind the render kernels is laid out [owned tile][64]: slot sl is pixel (sl & 7, (sl >> 3) & 7) of
+// this rank's owned tile sl >> 6.  Returns whether the pixel lies inside the image (edge tiles are partial).
+__device__ inline bool hjr_slot_xy(size_t sl, uint32_t rank, uint32_t world, uint32_t tiles_x, uint32_t width, uint32_t height, uint32_t* x, uint32_t* y)
 {
-    const size_t n_slots = (size_t)P.n_owned_tiles * 64u; // chunk-sum slots per chunk: 64 per owned tile
-    const float inv_spp = 1.0f / (float)P.spp;
-    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-        if (x >= P.width || y >= P.height) continue;
-        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
-        for (uint32_t k = 0; k < P.n_chunks; k++) {
-            const float4 v = P.part_color[(size_t)k * n_slots + sl];
-            a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
-            if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
-            if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
-        }
-        P.aov_color[pix] = make_float4(a.x * inv_spp, a.y * inv_spp, a.z * inv_spp, 1.0f);
-        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv_spp, b.y * inv_spp, b.z * inv_spp, 1.0f);
-        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv_spp, c.y * inv_spp, c.z * inv_spp, 1.0f);
-    }
+    uint32_t tx, ty;
+    hjr_tile_xy((uint32_t)(sl >> 6) * world + rank, tiles_x, &tx, &ty);
+    *x = tx * HJR_TILE + ((uint32_t)sl & 7u);
+    *y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+    return *x < width && *y < height;
 }
 
-// A sample pass (hjr_params.sample_begin / sample_end) instead of hjr_finalize_kernel: a = the running sum of the frame's
-// earlier passes (+0.0f on its first pass), then this pass's chunk sums added in chunk order with the finalize kernel's expressions; a goes
-// back unless this is the frame's last pass, and the AOV gets a * (1 / sample_end).  Chunk by chunk this is the finalize kernel's summation,
-// so the last pass writes the one-shot frame's bits.  Same streaming shape: one lane per owned pixel, coalesced float4 loads and stores.
-__global__ void __launch_bounds__(256) hjr_accumulate_kernel(const KParams P)
-{
-    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
-    const float inv_end = 1.0f / (float)P.sample_end;
-    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-        if (x >= P.width || y >= P.height) continue;
-        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
-        if (P.run_load) {
-            a = P.run_color[sl];
-            if (P.aov_albedo) b = P.run_albedo[sl];
-            if (P.aov_normal) c = P.run_normal[sl];
-        }
-        for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
-            const float4 v = P.part_color[(size_t)k * n_slots + sl];
-            a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
-            if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
-            if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
-        }
-        if (P.run_store) {
-            P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
-            if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
-            if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
-        }
-        P.aov_color[pix] = make_float4(a.x * inv_end, a.y * inv_end, a.z * inv_end, 1.0f);
-        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv_end, b.y * inv_end, b.z * inv_end, 1.0f);
-        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv_end, c.y * inv_end, c.z * inv_end, 1.0f);
-    }
-}
-
-// ---- adaptive sampling (hjr_set_adaptive).  hjr_accumulate_kernel's streaming shape with one wave per owned tile: the
-// grid stride is a multiple of 64 and n_slots is one, so the 64 lanes of a wave always hold the 64 pixels of one tile and leave the loop
-// together.  An ACTIVE tile (ad_state 0) adds this pass's chunk sums to its running sums with the accumulate kernel's expressions and
-// updates the per-pixel statistic (S1, S2) over y = (c.x + c.y) + c.z in chunk order; a STOPPED tile (ad_state = n_tile) reads no chunk
-// sum (the render kernel left its slots alone: they are stale).  After a pass that decides, every active tile evaluates the stopping
-// rule of DESIGN.md §4.5 rule 6: IEEE fp32 + - * / sqrt max as written (this translation unit is built with correctly rounded divide /
-// sqrt and without contraction) and a fixed xor butterfly, so numpy float32 restates it bit for bit.  Out-of-image lanes of an edge tile
-// are predicated, never skipped: they carry e = 0 into the butterfly.  Every pass writes every owned pixel of every requested AOV.
-__global__ void __launch_bounds__(256) hjr_accumulate_adaptive_kernel(const KParams P)
-{
-    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
-    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t otile = (uint32_t)(sl >> 6);
-        const uint32_t tile = otile * P.world + P.rank;
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-        const bool inside = x < P.width && y < P.height;
-        uint32_t n_tile = P.run_load ? P.ad_state[otile] : 0u; // (wave-uniform) 0: the tile is active
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
-        float2 s = make_float2(0.0f, 0.0f);
-        if (inside && P.run_load) {
-            a = P.run_color[sl];
-            if (P.aov_albedo) b = P.run_albedo[sl];
-            if (P.aov_normal) c = P.run_normal[sl];
-            s = P.ad_stat[sl];
-        }
-        if (n_tile == 0u) {
-            if (inside) {
-                for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
-                    const float4 v = P.part_color[(size_t)k * n_slots + sl];
-                    a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
-                    const float yk = (v.x + v.y) + v.z;
-                    s.x = s.x + yk; s.y = s.y + yk * yk;
-                    if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
-                    if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
-                }
-                if (P.run_store) {
-                    P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
-                    if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
-                    if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
-                    P.ad_stat[sl] = s;
-                }
-            }
-            if (P.ad_decide) { // (wave-uniform branch: all 64 lanes take the butterfly)
-                const float n = (float)P.sample_end, m = (float)(P.sample_end / P.chunk_spp);
-                const float q = fmaxf(m * s.y - s.x * s.x, 0.0f);
-                const float e = sqrtf(q / (m - 1.0f)) / (s.x + HJR_ADAPTIVE_EPS * n);
-                float v = inside ? e : 0.0f;
-                for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
-                if (v <= P.ad_threshold * 64.0f) n_tile = P.sample_end;
-            }
-            if ((threadIdx.x & 63u) == 0u) {
-                P.ad_state[otile] = n_tile;
-                if (n_tile == 0u) atomicAdd(&P.ad_state[P.n_owned_tiles], 1u);
-            }
-        }
-        if (!inside) continue; // (after the butterfly)
-        const float inv = 1.0f / (float)(n_tile ? n_tile : P.sample_end);
-        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
-        P.aov_color[pix] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
-        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv, b.y * inv, b.z * inv, 1.0f);
-        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv, c.y * inv, c.z * inv, 1.0f);
-    }
-}
-
-// ---- variance AOV (hjr_render_var, DESIGN.md §4 rule 7): variants of the three streaming kernels above that also carry the per-pixel
-// statistic (S1, S2) over y = (c.x + c.y) + c.z of the FULL chunks' colour sums, in chunk order from +0.0f, and store one float per owned
-// pixel.  Launched only when a variance pointer was given: without one the kernels above run, untouched.  The colour / albedo / normal
-// expressions are the ones above, so those AOVs keep their bits.  Chunk k is full iff (k + 1) * chunk_spp <= spp; the partial last chunk
-// goes into the colour and stays out of the statistic.
+// variance of a pixel's mean from the statistic of its chunk sums (DESIGN.md §4 rule 7)
 __device__ inline float hjr_variance_of_mean(float S1, float S2, uint32_t m_chunks, uint32_t granule, uint32_t n_samples)
 {
     if (m_chunks < 2u) return HJR_VARIANCE_UNKNOWN;
@@ -256,147 +132,94 @@ __global__ void __launch_bounds__(256) hjr_fill_var_kernel(const KParams P, floa
 {
     const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
     for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-        if (x >= P.width || y >= P.height) continue;
+        uint32_t x, y;
+        if (!hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y)) continue;
         aov_var[P.packed ? sl : (size_t)y * P.width + x] = HJR_VARIANCE_UNKNOWN;
     }
 }
-// hjr_finalize_kernel + the statistic: one more float store per pixel, no more loads
-__global__ void __launch_bounds__(256) hjr_finalize_var_kernel(const KParams P, float* __restrict__ aov_var)
+
+// ---- chunk sums -> pixel means (DESIGN.md §4 rules 4 - 7, §6.2).  Adds the chunk sums of every owned pixel in chunk order and scales by
+// 1/n: a fixed summation tree, so the frame is bitwise independent of which lane/wave/GPU rendered which chunk.  Streaming kernel: one lane
+// per pixel of an owned tile, coalesced float4 loads ([chunk][owned tile][64] layout), one float4 store per AOV.  The summation is written
+// ONCE, here; the flags only select what surrounds it, at compile time, so an instantiation holds no code of a feature it does not have:
+//   PASS      a sample pass (hjr_params.sample_begin / sample_end, rule 5): chunks [chunk0, chunk0 + pass_chunks) instead of [0, n_chunks),
+//             added to the running sum of the frame's earlier passes (+0.0f on its first pass), which goes back unless this is the frame's
+//             last pass; the mean is over sample_end samples instead of spp.  Chunk by chunk this is the one-shot summation, so the pass
+//             that ends at spp writes the one-shot frame's bits.
+//   ADAPTIVE  adaptive sampling (hjr_set_adaptive, rule 6; implies PASS): one wave per owned tile (the grid stride is a multiple of 64 and
+//             n_slots is one, so the 64 lanes of a wave always hold the 64 pixels of one tile and leave the loop together).  A STOPPED tile
+//             (ad_state = n_tile) reads no chunk sum (the render kernel left its slots alone: they are stale) and keeps its mean over
+//             n_tile samples.  After a pass that decides, every ACTIVE tile (ad_state 0) evaluates the stopping rule: IEEE fp32 + - * /
+//             sqrt max as written (this translation unit is built with correctly rounded divide / sqrt and without contraction) and a
+//             fixed xor butterfly, so numpy float32 restates it bit for bit.  Out-of-image lanes of an edge tile are predicated, never
+//             skipped, until after the butterfly: they carry e = 0 into it.  Every pass writes every owned pixel of every requested AOV.
+//   VAR       the variance AOV (hjr_render_var, rule 7): one more float store per pixel.
+// The statistic (S1, S2) over y = (c.x + c.y) + c.z of the colour sums exists iff ADAPTIVE || VAR, and is over the FULL chunks a pixel has
+// received (k < spp / chunk_spp), in chunk order from +0.0f; the partial last chunk goes into the colour only.  A pass keeps it per owned
+// pixel in P.stat.
+template <bool PASS, bool ADAPTIVE, bool VAR>
+__global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P, float* __restrict__ aov_var)
 {
-    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
-    const float inv_spp = 1.0f / (float)P.spp;
+    static_assert(PASS || !ADAPTIVE, "adaptive sampling acts on sample passes");
+    constexpr bool STAT = ADAPTIVE || VAR;
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u; // chunk-sum slots per chunk: 64 per owned tile
+    const uint32_t k_begin = PASS ? P.chunk0 : 0u, k_end = PASS ? P.chunk0 + P.pass_chunks : P.n_chunks; // (part_* are offset by -chunk0 chunks: see KParams)
     const uint32_t n_full = P.spp / P.chunk_spp;
+    const uint32_t n_frame = PASS ? P.sample_end : P.spp;
+    const bool run_load = PASS && P.run_load, run_store = PASS && P.run_store;
     for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-        if (x >= P.width || y >= P.height) continue;
-        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
-        float s1 = 0.0f, s2 = 0.0f;
-        for (uint32_t k = 0; k < P.n_chunks; k++) {
-            const float4 v = P.part_color[(size_t)k * n_slots + sl];
-            a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
-            if (k < n_full) { const float yk = (v.x + v.y) + v.z; s1 = s1 + yk; s2 = s2 + yk * yk; }
-            if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
-            if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
-        }
-        P.aov_color[pix] = make_float4(a.x * inv_spp, a.y * inv_spp, a.z * inv_spp, 1.0f);
-        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv_spp, b.y * inv_spp, b.z * inv_spp, 1.0f);
-        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv_spp, c.y * inv_spp, c.z * inv_spp, 1.0f);
-        aov_var[pix] = hjr_variance_of_mean(s1, s2, n_full, P.chunk_spp, P.spp);
-    }
-}
-// hjr_accumulate_kernel + the statistic, kept per owned pixel between the passes of the frame in var_stat ([owned tile][64] float2, like
-// ad_stat): 8 more bytes loaded and stored per pixel.  The mean is over n = sample_end samples, of m = sample_end / chunk_spp full chunks.
-__global__ void __launch_bounds__(256) hjr_accumulate_var_kernel(const KParams P, float2* __restrict__ var_stat, float* __restrict__ aov_var)
-{
-    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
-    const float inv_end = 1.0f / (float)P.sample_end;
-    const uint32_t n_full = P.spp / P.chunk_spp;
-    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t tile = (uint32_t)(sl >> 6) * P.world + P.rank;
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-        if (x >= P.width || y >= P.height) continue;
-        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
+        uint32_t x, y;
+        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y);
+        if constexpr (!ADAPTIVE) { if (!inside) continue; }
+        uint32_t n_tile = 0u; // (wave-uniform) 0: the tile is active
+        if constexpr (ADAPTIVE) n_tile = run_load ? P.ad_state[sl >> 6] : 0u;
         float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
         float2 s = make_float2(0.0f, 0.0f);
-        if (P.run_load) {
+        if (inside && run_load) {
             a = P.run_color[sl];
             if (P.aov_albedo) b = P.run_albedo[sl];
             if (P.aov_normal) c = P.run_normal[sl];
-            s = var_stat[sl];
+            if constexpr (STAT) s = P.stat[sl];
         }
-        for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
-            const float4 v = P.part_color[(size_t)k * n_slots + sl];
-            a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
-            if (k < n_full) { const float yk = (v.x + v.y) + v.z; s.x = s.x + yk; s.y = s.y + yk * yk; }
-            if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
-            if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
-        }
-        if (P.run_store) {
-            P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
-            if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
-            if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
-            var_stat[sl] = s;
-        }
-        P.aov_color[pix] = make_float4(a.x * inv_end, a.y * inv_end, a.z * inv_end, 1.0f);
-        if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv_end, b.y * inv_end, b.z * inv_end, 1.0f);
-        if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv_end, c.y * inv_end, c.z * inv_end, 1.0f);
-        aov_var[pix] = hjr_variance_of_mean(s.x, s.y, P.sample_end / P.chunk_spp, P.chunk_spp, P.sample_end);
-    }
-}
-// hjr_accumulate_adaptive_kernel + the variance store, from the ad_stat it keeps.  The statistic `s` of the stop decision is the kernel's
-// above, partial last chunk of the frame's final pass included (no decision follows that pass and ad_stat is not stored after it); the
-// variance uses `f`, the same sums over full chunks only.  A stopped tile keeps its statistic, so its variance (over n_tile samples, of
-// n_tile / chunk_spp chunks) stays put on later passes.
-__global__ void __launch_bounds__(256) hjr_accumulate_adaptive_var_kernel(const KParams P, float* __restrict__ aov_var)
-{
-    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
-    const uint32_t n_full = P.spp / P.chunk_spp;
-    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t otile = (uint32_t)(sl >> 6);
-        const uint32_t tile = otile * P.world + P.rank;
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-        const bool inside = x < P.width && y < P.height;
-        uint32_t n_tile = P.run_load ? P.ad_state[otile] : 0u; // (wave-uniform) 0: the tile is active
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a;
-        float2 s = make_float2(0.0f, 0.0f);
-        if (inside && P.run_load) {
-            a = P.run_color[sl];
-            if (P.aov_albedo) b = P.run_albedo[sl];
-            if (P.aov_normal) c = P.run_normal[sl];
-            s = P.ad_stat[sl];
-        }
-        float2 f = s;
         if (n_tile == 0u) {
             if (inside) {
-                for (uint32_t k = P.chunk0; k < P.chunk0 + P.pass_chunks; k++) { // (part_* are offset by -chunk0 chunks: see KParams)
+                for (uint32_t k = k_begin; k < k_end; k++) {
                     const float4 v = P.part_color[(size_t)k * n_slots + sl];
                     a.x = a.x + v.x; a.y = a.y + v.y; a.z = a.z + v.z;
-                    const float yk = (v.x + v.y) + v.z;
-                    s.x = s.x + yk; s.y = s.y + yk * yk;
-                    if (k < n_full) f = s;
+                    if constexpr (STAT) if (k < n_full) { const float yk = (v.x + v.y) + v.z; s.x = s.x + yk; s.y = s.y + yk * yk; }
                     if (P.aov_albedo) { const float4 w = P.part_albedo[(size_t)k * n_slots + sl]; b.x = b.x + w.x; b.y = b.y + w.y; b.z = b.z + w.z; }
                     if (P.aov_normal) { const float4 w = P.part_normal[(size_t)k * n_slots + sl]; c.x = c.x + w.x; c.y = c.y + w.y; c.z = c.z + w.z; }
                 }
-                if (P.run_store) {
+                if (run_store) {
                     P.run_color[sl] = make_float4(a.x, a.y, a.z, 0.0f);
                     if (P.aov_albedo) P.run_albedo[sl] = make_float4(b.x, b.y, b.z, 0.0f);
                     if (P.aov_normal) P.run_normal[sl] = make_float4(c.x, c.y, c.z, 0.0f);
-                    P.ad_stat[sl] = s;
+                    if constexpr (STAT) P.stat[sl] = s;
                 }
             }
-            if (P.ad_decide) { // (wave-uniform branch: all 64 lanes take the butterfly)
-                const float n = (float)P.sample_end, m = (float)(P.sample_end / P.chunk_spp);
-                const float q = fmaxf(m * s.y - s.x * s.x, 0.0f);
-                const float e = sqrtf(q / (m - 1.0f)) / (s.x + HJR_ADAPTIVE_EPS * n);
-                float v = inside ? e : 0.0f;
-                for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
-                if (v <= P.ad_threshold * 64.0f) n_tile = P.sample_end;
-            }
-            if ((threadIdx.x & 63u) == 0u) {
-                P.ad_state[otile] = n_tile;
-                if (n_tile == 0u) atomicAdd(&P.ad_state[P.n_owned_tiles], 1u);
+            if constexpr (ADAPTIVE) {
+                if (P.ad_decide) { // (wave-uniform branch: all 64 lanes take the butterfly)
+                    const float n = (float)P.sample_end, m = (float)(P.sample_end / P.chunk_spp);
+                    const float q = fmaxf(m * s.y - s.x * s.x, 0.0f);
+                    const float e = sqrtf(q / (m - 1.0f)) / (s.x + HJR_ADAPTIVE_EPS * n);
+                    float v = inside ? e : 0.0f;
+                    for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
+                    if (v <= P.ad_threshold * 64.0f) n_tile = P.sample_end;
+                }
+                if ((threadIdx.x & 63u) == 0u) {
+                    P.ad_state[sl >> 6] = n_tile;
+                    if (n_tile == 0u) atomicAdd(&P.ad_state[P.n_owned_tiles], 1u);
+                }
             }
         }
-        if (!inside) continue; // (after the butterfly)
-        const uint32_t n_mean = n_tile ? n_tile : P.sample_end;
+        if constexpr (ADAPTIVE) { if (!inside) continue; } // (after the butterfly)
+        const uint32_t n_mean = n_tile ? n_tile : n_frame; // the samples the written mean is over
         const float inv = 1.0f / (float)n_mean;
         const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
         P.aov_color[pix] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
         if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv, b.y * inv, b.z * inv, 1.0f);
         if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv, c.y * inv, c.z * inv, 1.0f);
-        aov_var[pix] = hjr_variance_of_mean(f.x, f.y, n_mean / P.chunk_spp, P.chunk_spp, n_mean);
+        if constexpr (VAR) aov_var[pix] = hjr_variance_of_mean(s.x, s.y, n_mean / P.chunk_spp, P.chunk_spp, n_mean);
     }
 }
 
@@ -430,21 +253,16 @@ __global__ void __launch_bounds__(256) hjr_pack_tiles_kernel(const float4* frame
 {
     const size_t sl = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (sl >= (size_t)n_owned * 64u) return;
-    const uint32_t tile = (uint32_t)(sl >> 6) * world + rank;
-    uint32_t tx, ty;
-    hjr_tile_xy(tile, tiles_x, &tx, &ty);
-    const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-    packed[sl] = (x < width && y < height) ? frame[(size_t)y * width + x] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uint32_t x, y;
+    const bool inside = hjr_slot_xy(sl, rank, world, tiles_x, width, height, &x, &y);
+    packed[sl] = inside ? frame[(size_t)y * width + x] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 __global__ void __launch_bounds__(256) hjr_unpack_tiles_kernel(const float4* packed, float4* frame, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_owned, uint32_t rank, uint32_t world)
 {
     const size_t sl = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (sl >= (size_t)n_owned * 64u) return;
-    const uint32_t tile = (uint32_t)(sl >> 6) * world + rank;
-    uint32_t tx, ty;
-    hjr_tile_xy(tile, tiles_x, &tx, &ty);
-    const uint32_t x = tx * HJR_TILE + ((uint32_t)sl & 7u), y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-    if (x < width && y < height) frame[(size_t)y * width + x] = packed[sl];
+    uint32_t x, y;
+    if (hjr_slot_xy(sl, rank, world, tiles_x, width, height, &x, &y)) frame[(size_t)y * width + x] = packed[sl];
 }
 
 // ---- the 8-bit preview buffer of the raygen program (`uchar4* image` of Params, renderer/renderer.h:1102, 1175: written by the missing

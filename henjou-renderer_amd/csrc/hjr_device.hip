@@ -562,7 +562,7 @@ static void bind_scene_tables(const hjr_ctx* c, KParams& kp)
 }
 
 // work area, output zeroing, chunk-sum buffers, and the kernel parameters of scene, frame and outputs
-static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void* d_color, void* d_albedo, void* d_normal, hipStream_t st, KParams& kp)
+static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st, KParams& kp)
 {
     if (c->d_work.cap < WorkArea::BYTES) {
         std::vector<unsigned char> z(WorkArea::BYTES, 0);
@@ -575,6 +575,7 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
         HIPCHK(hipMemsetAsync(d_color, 0, img_bytes, st));
         if (d_albedo) HIPCHK(hipMemsetAsync(d_albedo, 0, img_bytes, st));
         if (d_normal) HIPCHK(hipMemsetAsync(d_normal, 0, img_bytes, st));
+        if (d_var) HIPCHK(hipMemsetAsync(d_var, 0, img_bytes / 4, st)); // one float per pixel
     }
 
     memset(&kp, 0, sizeof(kp));
@@ -715,28 +716,6 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
     return HJR_OK;
 }
 
-// sums of the sample chunks -> pixel means (a sample pass: -> running sums and running means)
-// d_var: the variance AOV was requested (hjr_render_var): the variants that also carry S1, S2; a frame of a single chunk has no chunk sums
-// and gets the fill
-static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, const KParams& kp, float* d_var, hipStream_t st)
-{
-    const size_t n_slots = (size_t)g.owned * 64u;
-    if (n_slots == 0) return HJR_OK;
-    unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
-    if (g.n_chunks <= 1) {
-        if (!d_var) return HJR_OK;
-        hipLaunchKernelGGL(hjr_fill_var_kernel, dim3(fb), dim3(256), 0, st, kp, d_var);
-    } else if (d_var) {
-        if (g.pr.pass) {
-            if (!c->d_var_stat.reserve(n_slots * sizeof(float2))) { set_error("hjr_render: variance statistic allocation failed"); return HJR_ERR_DEVICE; }
-            hipLaunchKernelGGL(hjr_accumulate_var_kernel, dim3(fb), dim3(256), 0, st, kp, (float2*)c->d_var_stat.p, d_var);
-        } else hipLaunchKernelGGL(hjr_finalize_var_kernel, dim3(fb), dim3(256), 0, st, kp, d_var);
-    } else if (g.pr.pass) hipLaunchKernelGGL(hjr_accumulate_kernel, dim3(fb), dim3(256), 0, st, kp);
-    else hipLaunchKernelGGL(hjr_finalize_kernel, dim3(fb), dim3(256), 0, st, kp);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
-}
-
 // An adaptive sample pass (hjr_set_adaptive), before bind_params: the tiles still active size the launch.  A continuing
 // pass waits here for the count the previous pass of its frame read back (4 bytes, pinned).  The first adaptive pass of a context creates
 // the event and the pinned word.
@@ -754,15 +733,15 @@ static int adaptive_items(hjr_ctx* c, FrameGeom& g, uint32_t& active)
     g.n_items = (uint64_t)active * g.pass_chunks * 64; // the render kernels' queue holds the active tiles only
     return HJR_OK;
 }
-// ... after bind_params: the statistic, the tile states (+ the counter word) and the compacted list, kept across the passes of a frame
+// ... after bind_params: the tile states (+ the counter word) and the compacted list, kept across the passes of a frame
 static int adaptive_bind(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KParams& kp)
 {
     hjr_ctx::Adaptive& ad = c->ad;
-    if (!ad.stat.reserve((size_t)g.owned * 64u * sizeof(float2)) || !ad.state.reserve(((size_t)g.owned + 1u) * 4u) || !ad.list.reserve((size_t)g.owned * 4u)) {
+    if (!ad.state.reserve(((size_t)g.owned + 1u) * 4u) || !ad.list.reserve((size_t)g.owned * 4u)) {
         set_error("hjr_render: adaptive-sampling buffer allocation failed");
         return HJR_ERR_DEVICE;
     }
-    kp.ad_stat = (float2*)ad.stat.p; kp.ad_state = (uint32_t*)ad.state.p;
+    kp.ad_state = (uint32_t*)ad.state.p;
     kp.ad_threshold = ad.threshold;
     const uint32_t gr = g.chunk_spp, ms = ad.min_samples ? (ad.min_samples + gr - 1) / gr * gr : 2u * gr;
     kp.ad_decide = (g.pr.end < p->spp && g.pr.end >= ms && g.pr.end / gr >= 2u) ? 1u : 0u;
@@ -777,19 +756,33 @@ static int adaptive_filter(hjr_ctx* c, KParams& kp, hipStream_t st)
     kp.tile_order = kp.ad_list;
     return HJR_OK;
 }
-// ... instead of finalize_chunks: running sums, statistic, stop decisions, AOVs; then the count of tiles still active goes to the host
-static int adaptive_accumulate(hjr_ctx* c, const FrameGeom& g, const KParams& kp, float* d_var, hipStream_t st)
+// ... after the render kernel, for every launch: sums of the sample chunks -> pixel means (a sample pass: -> running sums and running means;
+// an adaptive one: statistic and stop decisions too, then the count of tiles still active goes to the host).  d_var: the variance AOV was
+// requested (hjr_render_var); a frame of a single chunk has no chunk sums and gets the fill.
+static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, KParams& kp, bool adaptive, float* d_var, hipStream_t st)
 {
-    hjr_ctx::Adaptive& ad = c->ad;
+    using Kernel = void (*)(KParams, float*);
+    static const Kernel kernels[2][2][2] = { // [pass][adaptive][variance]
+        { { hjr_finalize_kernel<false, false, false>, hjr_finalize_kernel<false, false, true> }, { nullptr, nullptr } },
+        { { hjr_finalize_kernel<true, false, false>, hjr_finalize_kernel<true, false, true> }, { hjr_finalize_kernel<true, true, false>, hjr_finalize_kernel<true, true, true> } },
+    };
     const size_t n_slots = (size_t)g.owned * 64u;
-    uint32_t* const d_count = (uint32_t*)ad.state.p + g.owned;
-    HIPCHK(hipMemsetAsync(d_count, 0, 4, st));
+    if (n_slots == 0) return HJR_OK;
+    Kernel kern = g.n_chunks > 1 ? kernels[g.pr.pass][adaptive][d_var != nullptr] : d_var ? hjr_fill_var_kernel : nullptr;
+    if (!kern) return HJR_OK;
+    if (g.pr.pass && (adaptive || d_var)) { // the statistic, kept across the passes of a frame
+        if (!c->d_stat.reserve(n_slots * sizeof(float2))) { set_error("hjr_render: statistic buffer allocation failed"); return HJR_ERR_DEVICE; }
+        kp.stat = (float2*)c->d_stat.p;
+    }
+    uint32_t* const d_count = adaptive ? (uint32_t*)c->ad.state.p + g.owned : nullptr;
+    if (adaptive) HIPCHK(hipMemsetAsync(d_count, 0, 4, st));
     const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
-    if (d_var) hipLaunchKernelGGL(hjr_accumulate_adaptive_var_kernel, dim3(fb), dim3(256), 0, st, kp, d_var);
-    else hipLaunchKernelGGL(hjr_accumulate_adaptive_kernel, dim3(fb), dim3(256), 0, st, kp);
+    hipLaunchKernelGGL(kern, dim3(fb), dim3(256), 0, st, kp, d_var);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ad.h_active, d_count, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(ad.ready, st));
+    if (adaptive) {
+        HIPCHK(hipMemcpyAsync(c->ad.h_active, d_count, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(c->ad.ready, st));
+    }
     return HJR_OK;
 }
 
@@ -806,17 +799,15 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, voi
     const bool adaptive = pr.pass && c->ad.threshold > 0.0f && g.owned > 0;
     uint32_t active = (uint32_t)g.owned;
     if (adaptive && (rc = adaptive_items(c, g, active)) != HJR_OK) return rc;
-    if ((rc = bind_params(c, p, g, d_color, d_albedo, d_normal, st, kp)) != HJR_OK) return rc;
+    if ((rc = bind_params(c, p, g, d_color, d_albedo, d_normal, d_var, st, kp)) != HJR_OK) return rc;
     if (adaptive && (rc = adaptive_bind(c, p, g, kp)) != HJR_OK) return rc;
-    if (d_var && !(p->flags & HJR_FLAG_PACKED) && g.world > 1 && (p->flags & HJR_FLAG_ZERO_UNOWNED)) // like the other AOVs (bind_params)
-        HIPCHK(hipMemsetAsync(d_var, 0, (size_t)p->width * p->height * sizeof(float), st));
     HIPCHK(hipEventRecord(c->ev0, st));
     if (!adaptive || active > 0) { // (an adaptive pass with no active tile launches no render kernel and still writes the AOVs)
         if ((rc = order_tiles(c, p, g, kp, st)) != HJR_OK) return rc;
         if (adaptive && active < g.owned && (rc = adaptive_filter(c, kp, st)) != HJR_OK) return rc;
         if ((rc = launch_render(c, p, g, kp, st)) != HJR_OK) return rc;
     }
-    if ((rc = adaptive ? adaptive_accumulate(c, g, kp, (float*)d_var, st) : finalize_chunks(c, g, kp, (float*)d_var, st)) != HJR_OK) return rc;
+    if ((rc = finalize_chunks(c, g, kp, adaptive, (float*)d_var, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
     if (pr.pass && c->opt.get(hjr::OPT_VERBOSE, 0))

@@ -66,6 +66,7 @@ struct hjr_ctx {
     DevBuf d_color, d_albedo, d_normal; // staging for hjr_render (host buffers)
     DevBuf d_part_color, d_part_albedo, d_part_normal; // chunk sums [pass_chunks][owned tile][64] float4
     DevBuf d_run_color, d_run_albedo, d_run_normal; // running sums of a frame rendered in sample passes, [owned tile][64] float4
+    DevBuf d_stat; // per owned pixel (S1, S2) of such a frame, [owned tile][64] float2; allocated at the first adaptive pass or pass with a variance
     DevBuf d_spill; // overflow of the short traversal stacks (memory-path kernels)
     DevBuf d_wf_ctx; // context planes of the wavefront kernel
     DevBuf d_tiles; // [tile_order | tile_class] of the cost-ordered tile list
@@ -75,7 +76,6 @@ struct hjr_ctx {
     DevBuf d_dn_a, d_dn_b, d_dn_out; // denoise ping-pong / host-entry staging
     // variance AOV (hjr_render_var) and variance-guided filter (hjr_denoise_var); nothing here is allocated before a call asks for a variance
     DevBuf d_variance;         // staging for the host-buffer entry points, one float per pixel
-    DevBuf d_var_stat;         // per owned pixel (S1, S2) of a non-adaptive frame rendered in sample passes, [owned tile][64] float2 (like ad.stat)
     DevBuf d_dnv_a, d_dnv_b;   // the filter's variance ping-pong, one float per pixel
     hjr_stats stats;
     bool event_pending = false;
@@ -98,7 +98,7 @@ struct hjr_ctx {
         bool frame = false;        // the context's last render was an adaptive sample pass: the fields below describe its frame
         uint32_t owned = 0, last_end = 0;
         uint64_t samples = 0;      // 64 x samples handed to active tiles so far (known on the host: active tiles at launch x pass length)
-        DevBuf stat, state, list;  // [owned tile][64] float2 (S1, S2) | [owned tile] uint32 n_tile (0 = active) + 1 counter | compacted tile list
+        DevBuf state, list;        // [owned tile] uint32 n_tile (0 = active) + 1 counter | compacted tile list
         uint32_t* h_active = nullptr; // pinned: tiles still active after the last pass, valid once `ready` has happened
         hipEvent_t ready = nullptr;
     } ad;
@@ -117,7 +117,7 @@ struct hjr_ctx {
     void release_buffers()
     {
         for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
-                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &d_variance, &d_var_stat, &d_dnv_a, &d_dnv_b, &ad.stat, &ad.state, &ad.list })
+                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_stat, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &d_variance, &d_dnv_a, &d_dnv_b, &ad.state, &ad.list })
             b->release();
         for (int i = 0; i < 2; i++)
             for (DevBuf* b : { &tmp.color[i], &tmp.variance[i], &tmp.history[i], &tmp.gbuf[i], &tmp.xf[i] }) b->release();

@@ -66,15 +66,16 @@ struct KParams {
     // sample pass (hjr_params.sample_begin / sample_end): the launch renders chunks [chunk0, chunk0 + pass_chunks) of the
     // frame's n_chunks (0 / n_chunks for a whole frame); the buffers behind part_* hold those chunks only
     uint32_t chunk0, pass_chunks;
-    float4* run_color;               // hjr_accumulate_kernel: running sums of the frame's earlier passes, [owned tile][64] float4 per AOV
+    float4* run_color;               // hjr_finalize_kernel<PASS>: running sums of the frame's earlier passes, [owned tile][64] float4 per AOV
     float4* run_albedo;
     float4* run_normal;
     uint32_t run_load, run_store;    // 1: the running sums hold earlier passes (else they start at +0.0f) / are written back (not the last pass)
     uint32_t sample_end;             // the mean is running sum * (1 / sample_end)
+    float2* stat;                    // hjr_finalize_kernel<PASS, ADAPTIVE || VAR>: per owned pixel (S1, S2) over the full chunks received so far,
+                                     // [owned tile][64]; null unless the launch is an adaptive sample pass or a sample pass with the variance AOV
     // adaptive sampling (hjr_set_adaptive): all null / 0 unless the launch is an adaptive sample pass
-    float2* ad_stat;                 // hjr_accumulate_adaptive_kernel: per owned pixel (S1, S2) over the chunk sums received so far, [owned tile][64]
     uint32_t* ad_state;              // per owned tile: 0 = active, else n_tile (the sample_end the tile stopped at); word [n_owned_tiles] counts
-                                     // the tiles still active after the pass (zeroed before the accumulate kernel, read back by the host)
+                                     // the tiles still active after the pass (zeroed before hjr_finalize_kernel, read back by the host)
     const uint32_t* ad_src;          // hjr_filter_tiles_kernel: the launch's tile order (null = plain round-robin order) ...
     uint32_t* ad_list;               // ... and its stable compaction to the active tiles, which becomes tile_order
     float ad_threshold;              // noise_threshold

@@ -81,9 +81,10 @@ def predict(chunk, w, h, spp, bounds, threshold, min_samples=0):
         for k in range(b // G, (e + G - 1) // G):
             c = pad[k]
             run = np.where(act[..., None, None], run + c, run)
-            y = (c[..., 0, 0] + c[..., 0, 1]) + c[..., 0, 2]
-            S1 = np.where(act, S1 + y, S1)
-            S2 = np.where(act, S2 + y * y, S2)
+            if k < spp // G:  # the statistic is over full chunks
+                y = (c[..., 0, 0] + c[..., 0, 1]) + c[..., 0, 2]
+                S1 = np.where(act, S1 + y, S1)
+                S2 = np.where(act, S2 + y * y, S2)
         if e < spp and e >= ms and e // G >= 2:
             m, n = f32(e // G), f32(e)
             q = np.maximum(m * S2 - S1 * S1, f32(0))

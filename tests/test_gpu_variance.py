@@ -12,7 +12,7 @@ import pytest
 import oracle_binding as ob
 from denoise_var_util import UNKNOWN, variance_rule
 from scene_util import Cornell, hjr
-from test_gpu_adaptive import even_bounds, oracle_chunks, predict
+from test_gpu_adaptive import even_bounds, oracle_chunks, owned_samples, predict
 from test_gpu_progressive import SENTINEL, assert_same, bits, with_range
 
 pytestmark = pytest.mark.gpu
@@ -200,6 +200,42 @@ def test_adaptive_frame(cornell):
             if stopped.any():
                 assert np.array_equal(bits(var)[stopped], bits(prev)[stopped]), "a stopped tile's variance moved"
         prev = var
+    dev.close()
+
+
+def test_adaptive_partial_tiles_partial_last_chunk(cornell):
+    """20 x 12 (3 x 2 tiles, partial in x and in y), 44 spp (five full chunks and one of 4) as [0, 16) [16, 32) [32, 44), threshold 0.08,
+    min_samples 16: tiles stop at 16 and at 32, and the tiles still active receive the partial chunk on the last pass, which their colour
+    gets and neither the stop statistic nor the variance does.  After every pass tile_samples, the active count, the three AOVs and the
+    variance are the prediction's bits, and a stopped tile's variance stays put; with all AOVs and with colour + variance only."""
+    spp, thr, bounds = 44, 0.08, [(0, 16), (16, 32), (32, 44)]
+    chunk, g, n_full = chunk_sums(cornell, W, H, spp)
+    assert g == 8 and n_full == 5 and chunk.shape[0] == 6
+    pred = predict(chunk, W, H, spp, bounds, thr, 16)
+    last = pred[-1][0]
+    assert last.shape == (2, 3) and (last == 16).any() and (last == 32).any() and (last == spp).any()  # before the GPU is touched
+    dev = cornell.device()
+    dev.set_adaptive(thr, 16)
+    p = cornell.hjr_params(W, H, spp)
+    for aovs in (True, False):
+        prev = None
+        for (b, e), (n_tile, want, active) in zip(bounds, pred):
+            what = "%s, adaptive pass [%d, %d)" % ("all AOVs" if aovs else "colour + variance", b, e)
+            rc, out, var = render_var(dev, with_range(p, b, e), (H, W, 4), aovs=aovs)
+            assert rc == 0, hjr.lib().hjr_last_error()
+            assert (dev.tile_samples() == owned_samples(n_tile)).all(), what
+            assert dev.adaptive_state()["active_tiles"] == active, what
+            assert_same(out, want if aovs else [want[0], None, None], what)
+            n_px = np.kron(n_tile, np.ones((8, 8), np.uint32))[:H, :W]
+            exp = np.zeros((H, W), f32)
+            for n in np.unique(n_px):
+                exp = np.where(n_px == n, variance_rule(chunk[:, :, :, 0, :], 8, int(n) // 8, int(n)), exp)
+            same_bits(var, exp, what)
+            stopped = n_px <= b  # stopped before this pass began
+            assert stopped.any() == (b > 0)
+            if stopped.any():
+                assert np.array_equal(bits(var)[stopped], bits(prev)[stopped]), what + ": a stopped tile's variance moved"
+            prev = var
     dev.close()
 
 

@@ -1,4 +1,4 @@
-"""tools/progressive_bench.py [--out profiles/progressive.json] [--repeats R] -- the cost of rendering a frame in sample passes
+"""tools/progressive_bench.py [--out profiles/progressive.json] [--repeats R] [--variance] -- the cost of rendering a frame in sample passes
 (hjr_params.sample_begin / sample_end).  Run on the GPU machine from the repository root.
 
 Two workloads, each rendered in 1, 2, 4, 8 and 32 passes split by hjr.pass_bounds (passes that come out empty are dropped, so the
@@ -11,6 +11,7 @@ Per pass count, after one warm-up frame, R frames each of:
   chunk_bytes      peak chunk-sum bytes (owned tiles x 64 x 16 B x the largest pass's chunks x AOVs) and running-sum bytes (x AOVs when
                    the frame has more than one pass), from the library's allocation rule (csrc/hjr_device.hip::bind_params)
 The last pass's colour is checked bit for bit against the one-pass frame.
+--variance: every render also writes the variance AOV (a fourth device tensor, one float per pixel; DESIGN.md §4 rule 7).
 """
 import argparse
 import json
@@ -33,11 +34,12 @@ def chunk_spp(spp):
     return 8 * (((spp + 7) // 8 + 63) // 64)
 
 
-def measure(dev, p, n_pass, aovs, repeats):
+def measure(dev, p, n_pass, aovs, repeats, variance):
     import torch
     W, H = p.width, p.height
     bufs = [torch.empty((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(3 if aovs else 1)]
     ptrs = [b.data_ptr() for b in bufs] + [None] * (3 - len(bufs))
+    var = torch.empty((H, W), dtype=torch.float32, device="cuda") if variance else None
     stream = torch.cuda.current_stream().cuda_stream
     bounds = hjr.pass_bounds(p.spp, n_pass)
 
@@ -47,7 +49,7 @@ def measure(dev, p, n_pass, aovs, repeats):
             q = hjr.ParamsV2.from_buffer_copy(p)
             if len(bounds) > 1:
                 q.sample_begin, q.sample_end = b, e
-            dev.render_device(q, *ptrs, stream=stream)
+            dev.render_device(q, *ptrs, stream=stream, d_variance=var.data_ptr() if variance else None)
             if with_stats:
                 ms += dev.stats()["last_kernel_ms"]
         torch.cuda.synchronize()
@@ -72,7 +74,7 @@ def measure(dev, p, n_pass, aovs, repeats):
             "color": bufs[0].cpu().numpy()}
 
 
-def workload(name, scene, arrays, cam, opt, spp, aovs, repeats):
+def workload(name, scene, arrays, cam, opt, spp, aovs, repeats, variance):
     dev = hjr.Device(0)
     try:
         dev.upload_scene(scene.view)
@@ -84,7 +86,7 @@ def workload(name, scene, arrays, cam, opt, spp, aovs, repeats):
                             sky=tuple(opt.scene_sky_default), ibl_intensity=opt.IBL_intensity)
         rows, ref = [], None
         for n in PASSES:
-            r = measure(dev, p, n, aovs, repeats)
+            r = measure(dev, p, n, aovs, repeats, variance)
             col = r.pop("color")
             if ref is None:
                 ref = col
@@ -99,7 +101,7 @@ def workload(name, scene, arrays, cam, opt, spp, aovs, repeats):
             extra = r["passes"] - 1
             r["kernel_overhead_ms_per_extra_pass"] = (r["kernel_ms"] - base["kernel_ms"]) / extra if extra else None
             r["wall_overhead_ms_per_extra_pass"] = (r["wall_ms"] - base["wall_ms"]) / extra if extra else None
-        return {"width": 1920, "height": 1080, "spp": spp, "integrator": "NEE", "aovs": "color+albedo+normal" if aovs else "color",
+        return {"width": 1920, "height": 1080, "spp": spp, "integrator": "NEE", "aovs": ("color+albedo+normal" if aovs else "color") + ("+variance" if variance else ""),
                 "granule": hjr.sample_granule(spp), "rows": rows}
     finally:
         dev.close()
@@ -109,6 +111,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "progressive.json"))
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--variance", action="store_true")
     a = ap.parse_args()
     out = {}
     cwd = os.getcwd()
@@ -117,7 +120,7 @@ def main():
         opt = hjr.load_render_option("render_option_c2.json")
         scene = hjr.Scene(opt.gltf_path.decode(), opt.gltf_name.decode(), opt)
         t = 1 / float(opt.fps)
-        out["c2"] = workload("c2", scene, scene.arrays(t), scene.camera(opt, t), opt, 256, True, a.repeats)
+        out["c2"] = workload("c2", scene, scene.arrays(t), scene.camera(opt, t), opt, 256, True, a.repeats, a.variance)
     finally:
         os.chdir(cwd)
     work = tempfile.mkdtemp()
@@ -125,7 +128,7 @@ def main():
     opt = hjr.load_render_option(os.path.join(work, "render_option_stress.json"))
     scene = hjr.Scene(opt.gltf_path.decode(), opt.gltf_name.decode(), opt)
     t = 1 / float(opt.fps)
-    out["stress"] = workload("stress", scene, scene.arrays(t), scene.camera(opt, t), opt, 64, False, a.repeats)
+    out["stress"] = workload("stress", scene, scene.arrays(t), scene.camera(opt, t), opt, 64, False, a.repeats, a.variance)
     out["stress"]["triangles"] = int(scene.view.n_triangles)
     out["note"] = ("kernel_ms: median over frames of the summed HIP-event time of the passes; wall_ms: median host wall time of a frame "
                    "(all passes enqueued, one synchronize); overheads are per extra pass against the one-pass frame")
