@@ -116,7 +116,7 @@ class Stats(_Sized):
 
     def as_dict(self):
         names = [n for k in reversed(type(self).__mro__) for n, _ in getattr(k, "_fields_", [])]
-        d = {n: (float(getattr(self, n)) if n in ("last_kernel_ms", "frame_build_ms", "bvh_sah") else int(getattr(self, n)))
+        d = {n: (float(getattr(self, n)) if n in ("last_kernel_ms", "frame_build_ms", "bvh_sah", "bvh_topology_ms") else int(getattr(self, n)))
              for n in names if n not in ("struct_size", "_pad0", "nan_where")}
         d["nan_where"] = [tuple(int(v) for v in self.nan_where[i]) for i in range(int(self.nan_located))]  # (x, y, sample)
         return d
@@ -129,8 +129,13 @@ class StatsV2(Stats):
 
 
 class StatsV3(StatsV2):
-    """hjr_stats with the refit fields appended after `StatsV2` (option "device_bvh_refit").  Device.stats() uses this one."""
+    """hjr_stats with the refit fields appended after `StatsV2` (option "device_bvh_refit")."""
     _fields_ = [("bvh_refits", C.c_uint32), ("bvh_sah", C.c_float)]
+
+
+class StatsV4(StatsV3):
+    """hjr_stats with the instance-tree fields appended after `StatsV3` (option "device_bvh_instances").  Device.stats() uses this one."""
+    _fields_ = [("bvh_instances", C.c_uint32), ("bvh_topology_ms", C.c_float)]
 
 
 class Adaptive(_Sized):
@@ -640,7 +645,7 @@ class Device:
         return out
 
     def stats(self):
-        st = StatsV3()
+        st = StatsV4()
         _check(lib().hjr_get_stats(self._h, C.byref(st)), "hjr_get_stats")
         return st.as_dict()
 

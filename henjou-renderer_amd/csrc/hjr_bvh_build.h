@@ -35,6 +35,8 @@ struct SceneCopy;
 // Traversal-stack entries a device-built tree may need: the tile classifier takes 64 * stack_need * 4 bytes of dynamic LDS without
 // raising the kernel's limit (hjr_device.hip::order_tiles), which stays at 32 KB with this cap.
 constexpr uint32_t DEVICE_BVH_MAX_STACK = 128;
+// Option "device_bvh_instances": instance subtrees one top tree takes (its clusters live in the LDS of one workgroup)
+constexpr uint32_t HJR_TOP_MAX = 1024;
 
 struct DeviceBvh {
     // object-space scene, uploaded at the first device build after hjr_upload_scene (have_scene = false drops it)
@@ -46,6 +48,19 @@ struct DeviceBvh {
     DevBuf node_count, node_cost, leaf_pos; // scratch of the treelet restructuring ("device_bvh_opt")
     // the frame data a build writes; hjr_commit_transforms swaps them with the context's current buffers when the build succeeds
     DevBuf nodes, tri_geom, tri_shade, tri_inst, lights;
+    // Option "device_bvh_instances": the BVH2 whose subtrees are the instances, built once per uploaded scene and build tag and kept
+    // between commits.  A commit rewrites only the k - 1 `top` nodes above the instance roots (child, range, parent of their children).
+    struct Topology {
+        DevBuf child, range, parent;  // per inner node (first row, triangles) | parent: inner nodes, then the sorted leaves
+        DevBuf pos, order;            // per sorted leaf: its tri_geom row, its triangle
+        DevBuf top, top_ids;          // per inner node: 1 above the instance roots | those nodes' ids, ascending (the root first)
+        DevBuf root, list;            // per instance: BVH2 ref of its subtree | the non-empty instances, ascending
+        DevBuf bounds;                // scratch of the build: per instance centroid bounds
+        bool valid = false;
+        uint32_t tag = 0, k = 0;      // build tag it was built under, non-empty instances
+        float ms = 0.0f;              // HIP-event time of its build
+    } topo;
+    void drop_topology();
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release();
 };
@@ -54,6 +69,8 @@ struct DeviceBvhResult {
     uint32_t n_nodes = 0, stack_need = 0, depth = 0;
     float build_ms = 0.0f; // HIP-event time of the build's kernels
     float sah = 0.0f;      // BVH4 SAH of the nodes, computed on the device in a fixed summation order (0: empty scene)
+    uint32_t instances = 0; // device_bvh_instances: instance subtrees under the top tree (0: an ordinary build)
+    bool too_deep = false;  // the error is "BVH deeper than the traversal stack"
 };
 
 // Enqueues the whole build on `st` behind whatever is already there, waits for it and reads back its header.  HJR_ERR_ARG with `err`
@@ -69,4 +86,12 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
 // data fails a bound.  At least 2 triangles.
 int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const DevBuf& cur_nodes, const DevBuf& cur_geom,
                      uint32_t n_nodes, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+// Option "device_bvh_instances": the frame data for these transforms from per-instance trees.  The topology (a BVH2 over object-space
+// boxes whose subtrees are the instances: sort keys carry the instance id above the Morton code; `opt_rounds` treelet rounds that never
+// cross an instance) is built when b.topo is not valid for `tag`, and kept.  Every call flattens in its leaf order, computes the world
+// boxes inside the instance subtrees, builds the top tree over the instance boxes in one workgroup, collapses and costs like a build.
+// No non-empty instance, more than HJR_TOP_MAX of them, or a tree deeper than the traversal stack: device_bvh_build runs instead
+// (r.instances == 0).  Writes and errors as device_bvh_build.
+int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
+                         uint32_t tag, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
 } // namespace hjr

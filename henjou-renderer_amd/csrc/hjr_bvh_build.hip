@@ -11,6 +11,9 @@
 //   cost         BVH4 SAH of the final nodes, summed in a fixed order (the same bits every run); also after a refit
 // Refit (option "device_bvh_refit", device_bvh_refit below): new transforms over the CURRENT frame data's topology.  flatten in leaf order
 // (the prim id of every tri_geom row), then the node boxes bottom-up over the BVH4 itself with the hand-off of `boxes`; no sort, no hierarchy.
+// Instance trees (option "device_bvh_instances", device_bvh_instances below): the BVH2 is built once per scene over object-space boxes with
+// the instance id on top of the sort key, so that every instance is one subtree, and kept; a commit flattens in its leaf order, computes
+// the world boxes inside the instance subtrees, builds the top tree over the instance boxes in one workgroup, then collapse and cost.
 // No workgroup ever waits for another one; every cross-launch size the host does not know is read by the kernels from `hdr`.
 #include <hip/hip_runtime.h>
 
@@ -40,7 +43,7 @@ enum Hdr {
     H_BASE = 9,      // first wide id of the current level
     H_F = 10,        // nodes of the current level
     H_NEXT = 11,     // nodes of the next level (scan total)
-    H_ERR = 12,      // non-zero: the restructured BVH2, or the BVH4 a refit walks, failed a structural bound (reported as HJR_ERR_DEVICE)
+    H_ERR = 12,      // non-zero: the restructured BVH2, the BVH4 a refit walks, or the kept instance topology failed a structural bound (reported as HJR_ERR_DEVICE)
     H_SAH = 13,      // float bits: BVH4 SAH of the final nodes (sah_top_kernel)
     H_WORDS = 16
 };
@@ -436,6 +439,7 @@ struct TreeletArgs {
     float* cost;                        // collapse-aware SAH of each inner node
     const float4* leaf_box;
     float4* inner_box;
+    const uint32_t* top; // device_bvh_instances: per inner node, 1 above the instance roots: never a treelet root (null: an ordinary build)
 };
 __device__ __forceinline__ void node_sah(const TreeletArgs& a, uint32_t ref, uint32_t& cnt, float& cost)
 {
@@ -587,7 +591,8 @@ __device__ float treelet(const TreeletArgs& a, TreeletLds& L, uint32_t R, float 
 }
 
 // One restructuring round: boxes_kernel's climb (one lane per leaf, the second lane to reach a node continues; nothing waits) computes
-// every inner node's count and cost, and a node of at least gamma triangles is a treelet root.  The wave takes its lanes' roots one
+// every inner node's count and cost, and a node of at least gamma triangles (under device_bvh_instances: whose leaves lie in one
+// instance, so that no treelet rewires across an instance boundary) is a treelet root.  The wave takes its lanes' roots one
 // after the other, all 64 lanes in each, and no lane leaves the loop before the wave is done.  A treelet only rewires nodes under its
 // root, which are complete, so the result is the same whatever order the lanes run in.
 __global__ void __launch_bounds__(NT) treelet_kernel(TreeletArgs a)
@@ -618,7 +623,7 @@ __global__ void __launch_bounds__(NT) treelet_kernel(TreeletArgs a)
                 done = true;
             }
         }
-        for (uint64_t roots = __ballot(done && cnt >= a.gamma); roots; roots &= roots - 1) {
+        for (uint64_t roots = __ballot(done && cnt >= a.gamma && !(a.top && a.top[p])); roots; roots &= roots - 1) {
             const int src = __ffsll((unsigned long long)roots) - 1;
             const float nc = treelet(a, L, __shfl(p, src), __shfl(cost, src), lane);
             if (lane == src) cost = nc;
@@ -675,11 +680,13 @@ struct CollapseArgs {
     uint32_t leaf_max;
     uint32_t cap; // wide nodes the buffers hold (>= the wide nodes of any tree over these triangles)
     uint32_t* hdr;
+    const uint32_t* top; // device_bvh_instances: per inner node, 1 above the instance roots (null: an ordinary build)
 };
-// a BVH2 node that becomes a wide node: inner, and the root or more than leaf_max triangles (frame.cpp:166)
+// a BVH2 node that becomes a wide node: inner, and the root or more than leaf_max triangles (frame.cpp:166).  A node above the
+// instance roots always does: instances keep their id order in tri_geom, so its triangles are no contiguous row range.
 __device__ __forceinline__ bool is_inner(const CollapseArgs& a, uint32_t ref)
 {
-    return !(ref & REF_LEAF) && (ref == 0 || a.range[ref].y > a.leaf_max);
+    return !(ref & REF_LEAF) && (ref == 0 || (a.top && a.top[ref]) || a.range[ref].y > a.leaf_max);
 }
 __device__ __forceinline__ float area_of(const CollapseArgs& a, uint32_t ref)
 {
@@ -961,6 +968,271 @@ __global__ void __launch_bounds__(NT) refit_boxes_kernel(RefitArgs a)
     }
 }
 
+// ---- instance trees (option "device_bvh_instances") ---------------------------------------------------------------------------------
+// Topology, once per uploaded scene and build tag: the builder's own passes over object-space boxes, with the instance id in the top
+// bits of the sort key.  Keys that share a prefix form one subtree of a binary radix tree, so every instance is one contiguous range of
+// the sorted order and one subtree; the k - 1 `top` nodes above the instance roots are a radix tree over instance ids, spatially
+// meaningless: storage for the top tree every commit builds.  No transform enters the topology.
+// Every commit: flatten in leaf order, boxes bottom-up inside the instance subtrees, the top tree, then the build's collapse and cost.
+// H_ERR bits of these kernels: 4 leaf order, 128 top-node list, 256 subtree walk, 512 instance roots, 1024 top tree.
+__global__ void __launch_bounds__(NT) obj_box_kernel(FlattenArgs a, uint32_t* bmin, uint32_t* bmax)
+{
+    const uint32_t t = blockIdx.x * NT + threadIdx.x;
+    if (t >= a.n) return;
+    uint32_t lo = 0, hi = a.n_inst; // last prim_offset <= t, as flatten_tri
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.prim_off[mid] <= t) lo = mid; else hi = mid; }
+    float v[9], bl[3], bh[3];
+    for (int k = 0; k < 3; k++) {
+        const uint32_t ix = a.idx[3 * (size_t)t + k];
+        for (int ax = 0; ax < 3; ax++) v[3 * k + ax] = a.vert[3 * (size_t)ix + ax];
+    }
+    (void)tri_box(v, bl, bh);
+    float4* bd = reinterpret_cast<float4*>(a.box) + 2 * (size_t)t;
+    bd[0] = make_float4(bl[0], bl[1], bl[2], 0.0f);
+    bd[1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
+    a.inst[t] = lo;
+    float c[3];
+    for (int ax = 0; ax < 3; ax++) c[ax] = 0.5f * (bl[ax] + bh[ax]);
+    reinterpret_cast<float4*>(a.cent)[t] = make_float4(c[0], c[1], c[2], 0.0f);
+    // exact, order-independent bounds per instance.  The words only ever move outwards, so a stale plain read shows a tighter
+    // bound than the current one: an atomic it lets through is redundant at worst, and one it skips would not have changed the word
+    for (int ax = 0; ax < 3; ax++) {
+        const uint32_t o = f2o(c[ax]);
+        if (o < bmin[3 * (size_t)lo + ax]) atomicMin(&bmin[3 * (size_t)lo + ax], o);
+        if (o > bmax[3 * (size_t)lo + ax]) atomicMax(&bmax[3 * (size_t)lo + ax], o);
+    }
+}
+// key: instance id in the top `bits` bits of 63, the Morton code over the instance's own centroid bounds (its top 63 - bits bits) below
+__global__ void __launch_bounds__(NT) obj_morton_kernel(uint32_t n, const float* cent, const uint32_t* inst, const uint32_t* bmin, const uint32_t* bmax, int bits,
+                                                        uint64_t* keys, uint32_t* vals)
+{
+    const uint32_t t = blockIdx.x * NT + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t in = inst[t];
+    const float4 c = reinterpret_cast<const float4*>(cent)[t];
+    const float cc[3] = { c.x, c.y, c.z };
+    uint64_t key = 0;
+    for (int ax = 0; ax < 3; ax++) {
+        const float l = o2f(bmin[3 * (size_t)in + ax]), h = o2f(bmax[3 * (size_t)in + ax]);
+        const float ext = h - l;
+        const float scale = ext > 0.0f ? 2097152.0f / ext : 0.0f;
+        key |= spread21(quantize21(cc[ax], l, scale)) << (2 - ax);
+    }
+    keys[t] = bits ? (((uint64_t)in << (63 - bits)) | (key >> bits)) : key;
+    vals[t] = t;
+}
+// top[i]: inner node i's leaves (its Karras range of the sorted order) lie in more than one instance
+__global__ void __launch_bounds__(NT) top_flag_kernel(int n, const uint64_t* keys, const uint2* range, int shift, uint32_t* top)
+{
+    const int i = (int)(blockIdx.x * NT + threadIdx.x);
+    if (i >= n - 1) return;
+    const uint2 r = range[i];
+    const uint32_t last = min(r.x + r.y - 1u, (uint32_t)(n - 1));
+    top[i] = r.x < (uint32_t)n && (keys[r.x] >> shift) != (keys[last] >> shift) ? 1u : 0u;
+}
+// root[instance]: the node (or single leaf) that is not a top node and has none but top nodes above it
+__global__ void __launch_bounds__(NT) inst_root_kernel(int n, uint32_t n_inst, const uint64_t* keys, const uint2* range, const uint32_t* parent, const uint32_t* top,
+                                                       int shift, uint32_t* root, uint32_t* hdr)
+{
+    const uint32_t s = blockIdx.x * NT + threadIdx.x;
+    if (s >= 2u * (uint32_t)n - 1u) return;
+    const bool inner = s < (uint32_t)(n - 1);
+    if (inner && top[s]) return;
+    if (n >= 2 && s != 0) {
+        const uint32_t p = parent[s];
+        if (p >= (uint32_t)(n - 1)) { atomicOr(&hdr[H_ERR], 512u); return; }
+        if (!top[p]) return;
+    }
+    const uint32_t leaf = inner ? range[s].x : s - (uint32_t)(n - 1);
+    const uint64_t in = leaf < (uint32_t)n ? keys[leaf] >> shift : ~0ull;
+    if (in >= n_inst) { atomicOr(&hdr[H_ERR], 512u); return; }
+    root[in] = inner ? s : (REF_LEAF | leaf);
+}
+// ids of the top nodes in ascending order (one workgroup); there are k - 1 of them and the first is the root
+__global__ void __launch_bounds__(NT) top_ids_kernel(uint32_t n_inner, const uint32_t* top, uint32_t k, uint32_t* ids, uint32_t* hdr)
+{
+    __shared__ uint32_t s[4];
+    uint32_t run = 0, tot;
+    for (uint32_t base = 0; base < n_inner; base += NT) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t f = i < n_inner && top[i] ? 1u : 0u;
+        const uint32_t at = run + block_scan(f, tot, s);
+        if (f && at + 1 < k) ids[at] = i;
+        run += tot;
+    }
+    if (threadIdx.x == 0 && (run + 1 != k || (k >= 2 && !top[0]))) atomicOr(&hdr[H_ERR], 128u);
+}
+__global__ void __launch_bounds__(NT) iota_kernel(uint32_t n, uint32_t* out)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i < n) out[i] = i;
+}
+
+struct InstArgs {
+    FlattenArgs f;           // scene, transforms, shade / inst / hdr (wv, box, cent unused)
+    const uint32_t *order, *pos, *top, *parent; // the kept topology; every index read from it is checked before it is used
+    const uint2* child;
+    uint32_t* counter;
+    float4 *geom, *leaf_box, *inner_box;
+};
+// refit_flatten_kernel's shape over the kept leaf order: sorted leaf k holds triangle order[k] in tri_geom row pos[k]; its unpadded
+// world box goes to leaf_box[k]
+__global__ void __launch_bounds__(NT) inst_flatten_kernel(InstArgs a)
+{
+    __shared__ uint32_t s_max;
+    if (threadIdx.x == 0) s_max = 0u;
+    __syncthreads();
+    const uint32_t k = blockIdx.x * NT + threadIdx.x;
+    if (k < a.f.n) {
+        const uint32_t t = a.order[k], d = a.pos[k];
+        if (t >= a.f.n || d >= a.f.n) atomicOr(&a.f.hdr[H_ERR], 4u);
+        else {
+            float v[9], s[16], bl[3], bh[3];
+            const uint32_t inst = flatten_tri(a.f, t, v, s);
+            float4* sd = reinterpret_cast<float4*>(a.f.shade) + 4 * (size_t)t;
+            for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+            a.f.inst[t] = inst;
+            float4* g = a.geom + HJR_TRI_F4 * (size_t)d;
+            g[0] = make_float4(v[0], v[1], v[2], v[3]);
+            g[1] = make_float4(v[4], v[5], v[6], v[7]);
+            g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(a.f.mat[t]), 0.0f);
+            atomicMax(&s_max, __float_as_uint(tri_box(v, bl, bh)));
+            a.leaf_box[2 * (size_t)k] = make_float4(bl[0], bl[1], bl[2], 0.0f);
+            a.leaf_box[2 * (size_t)k + 1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) atomicMax(&a.f.hdr[H_SMAX], s_max);
+}
+// boxes_kernel's climb and hand-off, inside the instance subtrees only: the lane pads its leaf's box with this pose's padding, then
+// climbs while it is the second to reach a node and stops below the first top node (min / max are exact and rounding is monotone:
+// the union of padded boxes is the padded union).  Nothing waits; a walk of more than n steps or an index out of range sets H_ERR.
+__global__ void __launch_bounds__(NT) inst_boxes_kernel(InstArgs a)
+{
+    const uint32_t n = a.f.n;
+    const uint32_t k = blockIdx.x * NT + threadIdx.x;
+    if (k >= n) return;
+    const float pad = __uint_as_float(a.f.hdr[H_SMAX]) * (1.0f / 8192.0f);
+    float4 lo = a.leaf_box[2 * (size_t)k], hi = a.leaf_box[2 * (size_t)k + 1];
+    lo.x -= pad; lo.y -= pad; lo.z -= pad;
+    hi.x += pad; hi.y += pad; hi.z += pad;
+    a.leaf_box[2 * (size_t)k] = lo;
+    a.leaf_box[2 * (size_t)k + 1] = hi;
+    if (n < 2) return;
+    uint32_t p = a.parent[(size_t)(n - 1) + k];
+    for (uint32_t steps = 0;; steps++) {
+        if (p >= n - 1 || steps >= n) { atomicOr(&a.f.hdr[H_ERR], 256u); return; }
+        if (a.top[p]) return; // the node below is an instance root
+        const uint32_t before = __hip_atomic_fetch_add(&a.counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == 0) return; // the sibling's lane finishes this node
+        const uint2 c = a.child[p];
+        const uint32_t bx = (c.x & REF_LEAF) ? n : n - 1, by = (c.y & REF_LEAF) ? n : n - 1;
+        if ((c.x & ~REF_LEAF) >= bx || (c.y & ~REF_LEAF) >= by) { atomicOr(&a.f.hdr[H_ERR], 256u); return; }
+        float4 l0, h0, l1, h1;
+        box_of(c.x, a.leaf_box, a.inner_box, l0, h0);
+        box_of(c.y, a.leaf_box, a.inner_box, l1, h1);
+        a.inner_box[2 * (size_t)p] = make_float4(smin(l0.x, l1.x), smin(l0.y, l1.y), smin(l0.z, l1.z), 0.0f);
+        a.inner_box[2 * (size_t)p + 1] = make_float4(smax(h0.x, h1.x), smax(h0.y, h1.y), smax(h0.z, h1.z), 0.0f);
+        if (p == 0) return;
+        p = a.parent[p];
+    }
+}
+
+// The top tree: agglomerative clustering of the k instance boxes in one workgroup (workgroup barriers only).  Per round every active
+// cluster picks the partner of smallest union area (ties: the smaller slot); pairs that picked each other merge into the smaller
+// slot, left child the smaller slot, and take their node ids in slot order.  The smallest pair of minimal area is always mutual, so
+// a round merges at least one pair and k - 1 rounds suffice.  A box that encloses many others merges last and ends up under the root.
+// Merge number m takes node top_ids[k - 2 - m]: the last one is the root, node 0.
+struct TopArgs {
+    uint32_t n, n_inst, k;
+    const uint32_t *list, *root, *top, *top_ids;
+    uint2 *child, *range;
+    uint32_t* parent;
+    const float4* leaf_box;
+    float4* inner_box;
+    uint32_t* hdr;
+};
+constexpr uint32_t TOP_NONE = 0xffffffffu;
+using hjr::HJR_TOP_MAX;
+__global__ void __launch_bounds__(NT) inst_top_kernel(TopArgs a)
+{
+    __shared__ float s_lo[3][HJR_TOP_MAX], s_hi[3][HJR_TOP_MAX];
+    __shared__ uint32_t s_ref[HJR_TOP_MAX], s_cnt[HJR_TOP_MAX], s_partner[HJR_TOP_MAX]; // s_cnt 0: the slot is not an active cluster
+    __shared__ uint32_t s_scan[4], s_err;
+    const uint32_t k = min(a.k, HJR_TOP_MAX), n = a.n;
+    if (threadIdx.x == 0) s_err = 0u;
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < k; s += NT) {
+        const uint32_t in = a.list[s];
+        const uint32_t ref = in < a.n_inst ? a.root[in] : TOP_NONE;
+        const uint32_t id = ref & ~REF_LEAF;
+        const bool ok = ref != TOP_NONE && ((ref & REF_LEAF) ? id < n : (id + 1 < n && !a.top[id]));
+        float4 lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi = lo;
+        uint32_t cnt = 1;
+        if (ok) {
+            box_of(ref, a.leaf_box, a.inner_box, lo, hi);
+            if (!(ref & REF_LEAF)) cnt = a.range[id].y;
+        }
+        if (!ok || cnt == 0) s_err = 1u;
+        s_lo[0][s] = lo.x; s_lo[1][s] = lo.y; s_lo[2][s] = lo.z;
+        s_hi[0][s] = hi.x; s_hi[1][s] = hi.y; s_hi[2][s] = hi.z;
+        s_ref[s] = ref; s_cnt[s] = cnt;
+    }
+    __syncthreads();
+    if (s_err) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 512u); return; }
+    uint32_t merged = 0;
+    for (uint32_t round = 0; merged + 1 < k; round++) {
+        if (round >= k) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (never: every round merges)
+        for (uint32_t s = threadIdx.x; s < k; s += NT) {
+            uint32_t bj = TOP_NONE;
+            if (s_cnt[s]) {
+                const float lx = s_lo[0][s], ly = s_lo[1][s], lz = s_lo[2][s], hx = s_hi[0][s], hy = s_hi[1][s], hz = s_hi[2][s];
+                float best = 0.0f;
+                for (uint32_t j = 0; j < k; j++) {
+                    if (j == s || !s_cnt[j]) continue;
+                    const float dx = smax(hx, s_hi[0][j]) - smin(lx, s_lo[0][j]), dy = smax(hy, s_hi[1][j]) - smin(ly, s_lo[1][j]),
+                                dz = smax(hz, s_hi[2][j]) - smin(lz, s_lo[2][j]);
+                    const float area = dx * dy + dy * dz + dz * dx;
+                    if (bj == TOP_NONE || area < best) { best = area; bj = j; }
+                }
+            }
+            s_partner[s] = bj;
+        }
+        __syncthreads();
+        // a thread owns four consecutive slots, so that the scan numbers the round's merges in slot order
+        uint32_t mine = 0, tot;
+        bool m[4];
+        for (uint32_t q = 0; q < 4; q++) {
+            const uint32_t s = 4 * threadIdx.x + q;
+            const uint32_t j = s < k ? s_partner[s] : TOP_NONE;
+            m[q] = j != TOP_NONE && j > s && j < k && s_partner[j] == s;
+            mine += m[q] ? 1u : 0u;
+        }
+        uint32_t at = merged + block_scan(mine, tot, s_scan);
+        for (uint32_t q = 0; q < 4; q++) {
+            if (!m[q]) continue;
+            const uint32_t s = 4 * threadIdx.x + q, j = s_partner[s], idx = at++;
+            const uint32_t id = idx + 2 <= k ? a.top_ids[k - 2 - idx] : TOP_NONE;
+            const uint32_t rs = s_ref[s], rj = s_ref[j];
+            const size_t ps = parent_slot((int)n, rs), pj = parent_slot((int)n, rj), slots = 2 * (size_t)n - 1;
+            if (id + 1 >= n || id == TOP_NONE || !a.top[id] || ps >= slots || pj >= slots) { s_err = 1u; continue; }
+            for (int ax = 0; ax < 3; ax++) { s_lo[ax][s] = smin(s_lo[ax][s], s_lo[ax][j]); s_hi[ax][s] = smax(s_hi[ax][s], s_hi[ax][j]); }
+            s_cnt[s] += s_cnt[j];
+            s_cnt[j] = 0;
+            s_ref[s] = id;
+            a.child[id] = make_uint2(rs, rj);
+            a.range[id] = make_uint2(0u, s_cnt[s]); // only the count: a top node is never a BVH4 leaf
+            a.inner_box[2 * (size_t)id] = make_float4(s_lo[0][s], s_lo[1][s], s_lo[2][s], 0.0f);
+            a.inner_box[2 * (size_t)id + 1] = make_float4(s_hi[0][s], s_hi[1][s], s_hi[2][s], 0.0f);
+            a.parent[ps] = id;
+            a.parent[pj] = id;
+        }
+        __syncthreads();
+        if (s_err || tot == 0) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (tot 0: a non-finite box, reported before this bit)
+        merged += tot;
+    }
+}
+
 inline unsigned blocks_for(size_t n) { return (unsigned)std::max<size_t>(1, (n + NT - 1) / NT); }
 
 } // namespace
@@ -973,10 +1245,18 @@ void DeviceBvh::release()
                        &inner_box, &inner_child, &inner_range, &parent, &counter, &frontier[0], &frontier[1], &wide, &hdr, &node_count, &node_cost, &leaf_pos,
                        &nodes, &tri_geom, &tri_shade, &tri_inst, &lights })
         x->release();
+    drop_topology();
     have_scene = false;
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     ev0 = ev1 = nullptr;
+}
+
+void DeviceBvh::drop_topology()
+{
+    for (DevBuf* x : { &topo.child, &topo.range, &topo.parent, &topo.pos, &topo.order, &topo.top, &topo.top_ids, &topo.root, &topo.list, &topo.bounds }) x->release();
+    topo.valid = false;
+    topo.k = 0;
 }
 
 #define DCHK(call)                                                                                           \
@@ -1000,6 +1280,63 @@ static void launch_sah(DeviceBvh& b, const float4* nodes, const uint32_t* n_ptr,
     uint32_t* hdr = (uint32_t*)b.hdr.p;
     hipLaunchKernelGGL(sah_reduce_kernel, dim3(SCAN_G), dim3(NT), 0, st, nodes, n_ptr, cap, counter, (float*)b.part.p, hdr);
     hipLaunchKernelGGL(sah_top_kernel, dim3(1), dim3(NT), 0, st, nodes, (const float*)b.part.p, hdr);
+}
+
+// stable sort of keys[0] / vals[0] (n pairs, nb tiles): 8 x 8 bits, the result is back in keys[0] / vals[0]
+static int sort_pairs(DeviceBvh& b, uint32_t n, uint32_t nb, hipStream_t st, std::string& err)
+{
+    uint64_t* keys[2] = { (uint64_t*)b.keys[0].p, (uint64_t*)b.keys[1].p };
+    uint32_t* vals[2] = { (uint32_t*)b.vals[0].p, (uint32_t*)b.vals[1].p };
+    for (int pass = 0; pass < 8; pass++) {
+        const int s = pass & 1;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], n, 8 * pass, (uint32_t*)b.hist.p, nb);
+        if (const int rc = scan((uint32_t*)b.hist.p, nullptr, nb * 256u, (uint32_t*)b.part.p, nullptr, st, err)) return rc;
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], (const uint32_t*)vals[s], n, 8 * pass,
+                           (const uint32_t*)b.hist.p, nb, keys[s ^ 1], vals[s ^ 1]);
+    }
+    return HJR_OK;
+}
+
+// The BVH2 `ca` describes over n >= 1 triangles -> b.nodes, level by level; then the tree cost, the build's one read of the header
+// and its results.  `what` names the tree in the structural-bound error.
+static int collapse_and_cost(DeviceBvh& b, const CollapseArgs& ca, uint32_t n, size_t nn, hipStream_t st, DeviceBvhResult& r, const char* what, std::string& err)
+{
+    uint32_t* hdr = ca.hdr;
+    Front* fr[2] = { (Front*)b.frontier[0].p, (Front*)b.frontier[1].p };
+    Wide* wide = (Wide*)b.wide.p;
+    uint32_t* n_inner = (uint32_t*)((char*)b.wide.p + nn * sizeof(Wide));
+    hipLaunchKernelGGL(collapse_init_kernel, dim3(1), dim3(1), 0, st, n, fr[0], hdr);
+    const unsigned grid = (unsigned)std::min<size_t>(blocks_for(nn), 1024);
+    uint32_t level = 0, F = 1;
+    while (F > 0 && level < hjr::DEVICE_BVH_MAX_STACK) {
+        for (int k = 0; k < LEVEL_BATCH; k++, level++) {
+            Front* cur = fr[level & 1];
+            hipLaunchKernelGGL(wide_expand_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Front*)cur, wide, n_inner);
+            if (const int rc = scan(n_inner, hdr + H_F, 0u, (uint32_t*)b.part.p, hdr + H_NEXT, st, err)) return rc;
+            hipLaunchKernelGGL(wide_emit_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Wide*)wide, (const uint32_t*)n_inner, fr[(level + 1) & 1],
+                               (float4*)b.nodes.p);
+            hipLaunchKernelGGL(level_advance_kernel, dim3(1), dim3(1), 0, st, hdr);
+        }
+        DCHK(hipGetLastError());
+        DCHK(hipMemcpyAsync(&F, hdr + H_F, 4, hipMemcpyDeviceToHost, st));
+        DCHK(hipStreamSynchronize(st));
+    }
+    launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, (uint32_t)nn, nullptr, st);
+    DCHK(hipGetLastError());
+    DCHK(hipEventRecord(b.ev1, st));
+    uint32_t h[H_WORDS];
+    DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
+    const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
+    if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
+    if (h[H_ERR]) { err = std::string("device BVH: ") + what + " failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
+    r.n_nodes = h[H_BASE];
+    r.sah = __builtin_bit_cast(float, h[H_SAH]);
+    r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
+    r.depth = h[H_DEPTH];
+    if (F > 0 || r.stack_need > hjr::DEVICE_BVH_MAX_STACK) { err = "BVH deeper than the traversal stack"; r.too_deep = true; return HJR_ERR_ARG; }
+    return HJR_OK;
 }
 
 int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
@@ -1064,13 +1401,7 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     uint64_t* keys[2] = { (uint64_t*)b.keys[0].p, (uint64_t*)b.keys[1].p };
     uint32_t* vals[2] = { (uint32_t*)b.vals[0].p, (uint32_t*)b.vals[1].p };
     hipLaunchKernelGGL(morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (float*)b.box.p, (const float*)b.cent.p, (const uint32_t*)hdr, keys[0], vals[0]);
-    for (int pass = 0; pass < 8; pass++) { // 8 x 8 bits: the result is back in keys[0] / vals[0]
-        const int s = pass & 1;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], n, 8 * pass, (uint32_t*)b.hist.p, nb);
-        if (const int rc = scan((uint32_t*)b.hist.p, nullptr, nb * 256u, (uint32_t*)b.part.p, nullptr, st, err)) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], (const uint32_t*)vals[s], n, 8 * pass,
-                           (const uint32_t*)b.hist.p, nb, keys[s ^ 1], vals[s ^ 1]);
-    }
+    if (const int rc = sort_pairs(b, n, nb, st, err)) return rc;
     // with a restructuring, tri_geom waits for the leaves' new positions
     hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals[0], (const uint32_t*)nullptr, (const float*)b.wv.p,
                        (const uint32_t*)b.mat.p, (const float*)b.box.p, restructure ? (float*)nullptr : (float*)b.tri_geom.p, (float*)b.leaf_box.p);
@@ -1086,7 +1417,7 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         ta.n = (int)n; ta.leaf_max = leaf_max;
         ta.child = (uint2*)b.inner_child.p; ta.parent = (uint32_t*)b.parent.p; ta.counter = (uint32_t*)b.counter.p;
         ta.count = (uint32_t*)b.node_count.p; ta.cost = (float*)b.node_cost.p;
-        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p;
+        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p; ta.top = nullptr;
         for (uint32_t round = 0; round < opt_rounds; round++) {
             ta.gamma = TREELET << round; // the paper's schedule: the treelet size, doubled every round
             DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
@@ -1105,41 +1436,8 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
     ca.leaf_pos = restructure ? (const uint32_t*)b.leaf_pos.p : nullptr;
     ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
-    Front* fr[2] = { (Front*)b.frontier[0].p, (Front*)b.frontier[1].p };
-    Wide* wide = (Wide*)b.wide.p;
-    uint32_t* n_inner = (uint32_t*)((char*)b.wide.p + nn * sizeof(Wide));
-    hipLaunchKernelGGL(collapse_init_kernel, dim3(1), dim3(1), 0, st, n, fr[0], hdr);
-    const unsigned grid = (unsigned)std::min<size_t>(blocks_for(nn), 1024);
-    uint32_t level = 0, F = 1;
-    while (F > 0 && level < DEVICE_BVH_MAX_STACK) {
-        for (int k = 0; k < LEVEL_BATCH; k++, level++) {
-            Front* cur = fr[level & 1];
-            hipLaunchKernelGGL(wide_expand_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Front*)cur, wide, n_inner);
-            if (const int rc = scan(n_inner, hdr + H_F, 0u, (uint32_t*)b.part.p, hdr + H_NEXT, st, err)) return rc;
-            hipLaunchKernelGGL(wide_emit_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Wide*)wide, (const uint32_t*)n_inner, fr[(level + 1) & 1],
-                               (float4*)b.nodes.p);
-            hipLaunchKernelGGL(level_advance_kernel, dim3(1), dim3(1), 0, st, hdr);
-        }
-        DCHK(hipGetLastError());
-        DCHK(hipMemcpyAsync(&F, hdr + H_F, 4, hipMemcpyDeviceToHost, st));
-        DCHK(hipStreamSynchronize(st));
-    }
-    launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, (uint32_t)nn, nullptr, st);
-    DCHK(hipGetLastError());
-    DCHK(hipEventRecord(b.ev1, st));
-    uint32_t h[H_WORDS];
-    DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-    DCHK(hipStreamSynchronize(st));
-    DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
-    const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
-    if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
-    if (h[H_ERR]) { err = "device BVH: the restructured tree failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
-    r.n_nodes = h[H_BASE];
-    r.sah = __builtin_bit_cast(float, h[H_SAH]);
-    r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
-    r.depth = h[H_DEPTH];
-    if (F > 0 || r.stack_need > DEVICE_BVH_MAX_STACK) { err = "BVH deeper than the traversal stack"; return HJR_ERR_ARG; }
-    return HJR_OK;
+    ca.top = nullptr;
+    return collapse_and_cost(b, ca, n, nn, st, r, "the restructured tree", err);
 }
 
 int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const DevBuf& cur_nodes, const DevBuf& cur_geom,
@@ -1195,6 +1493,163 @@ int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     r.n_nodes = n_nodes;
     r.sah = __builtin_bit_cast(float, h[H_SAH]);
     return HJR_OK;
+}
+
+// The topology of option "device_bvh_instances" into b.topo (kernel comment above); the object-space scene is on the device and the
+// build's scratch is reserved.  One host wait; b.topo.ms is its HIP-event time.
+static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds, const std::vector<uint32_t>& list, hipStream_t st,
+                          std::string& err)
+{
+    DeviceBvh::Topology& T = b.topo;
+    T.valid = false;
+    const size_t nn = std::max<uint32_t>(n, 1u);
+    const uint32_t k = (uint32_t)list.size(), nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+    if (!T.child.reserve(nn * 8) || !T.range.reserve(nn * 8) || !T.parent.reserve(2 * nn * 4) || !T.pos.reserve(nn * 4) || !T.order.reserve(nn * 4) ||
+        !T.top.reserve(nn * 4) || !T.top_ids.reserve((size_t)std::max(k, 1u) * 4) || !T.root.reserve((size_t)std::max(n_inst, 1u) * 4) ||
+        !T.bounds.reserve((size_t)std::max(n_inst, 1u) * 24) || !T.list.upload(list.data(), list.size() * 4, st)) {
+        err = "device BVH: allocation or upload failed";
+        return HJR_ERR_DEVICE;
+    }
+    int bits = 0;
+    while (bits < 32 && (1ull << bits) < n_inst) bits++;
+    const int shift = 63 - bits;
+    uint32_t* hdr = (uint32_t*)b.hdr.p;
+    uint32_t *bmin = (uint32_t*)T.bounds.p, *bmax = bmin + 3 * (size_t)n_inst;
+    uint64_t* keys = (uint64_t*)b.keys[0].p;
+    uint32_t* vals = (uint32_t*)b.vals[0].p;
+    const bool restructure = opt_rounds > 0 && n >= 2;
+    DCHK(hipEventRecord(b.ev0, st));
+    hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
+    DCHK(hipMemsetAsync(bmin, 0xff, (size_t)n_inst * 12, st));
+    DCHK(hipMemsetAsync(bmax, 0, (size_t)n_inst * 12, st));
+    DCHK(hipMemsetAsync(T.root.p, 0xff, (size_t)n_inst * 4, st));
+    FlattenArgs fa = FlattenArgs();
+    fa.vert = (const float*)b.vert.p; fa.idx = (const uint32_t*)b.idx.p; fa.prim_off = (const uint32_t*)b.prim_off.p;
+    fa.n = n; fa.n_inst = n_inst;
+    fa.box = (float*)b.box.p; fa.cent = (float*)b.cent.p; fa.inst = (uint32_t*)b.tri_inst.p; fa.hdr = hdr; // tri_inst: scratch until the commit's flatten
+    hipLaunchKernelGGL(obj_box_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, fa, bmin, bmax);
+    hipLaunchKernelGGL(obj_morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const float*)b.cent.p, (const uint32_t*)b.tri_inst.p, (const uint32_t*)bmin,
+                       (const uint32_t*)bmax, bits, keys, vals);
+    if (const int rc = sort_pairs(b, n, nb, st, err)) return rc;
+    DCHK(hipMemcpyAsync(T.order.p, vals, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (n >= 2) {
+        hipLaunchKernelGGL(karras_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint64_t*)keys, (uint2*)T.child.p, (uint2*)T.range.p,
+                           (uint32_t*)T.parent.p);
+        hipLaunchKernelGGL(top_flag_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint64_t*)keys, (const uint2*)T.range.p, shift, (uint32_t*)T.top.p);
+    }
+    hipLaunchKernelGGL(inst_root_kernel, dim3(blocks_for(2 * (size_t)n - 1)), dim3(NT), 0, st, (int)n, n_inst, (const uint64_t*)keys, (const uint2*)T.range.p,
+                       (const uint32_t*)T.parent.p, (const uint32_t*)T.top.p, shift, (uint32_t*)T.root.p, hdr);
+    hipLaunchKernelGGL(top_ids_kernel, dim3(1), dim3(NT), 0, st, n - 1, (const uint32_t*)T.top.p, k, (uint32_t*)T.top_ids.p, hdr);
+    if (restructure) { // "device_bvh_opt" rounds on the object-space boxes, inside the instances
+        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals, (const uint32_t*)nullptr, (const float*)nullptr,
+                           (const uint32_t*)b.mat.p, (const float*)b.box.p, (float*)nullptr, (float*)b.leaf_box.p);
+        DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+        hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)T.parent.p, (uint32_t*)b.counter.p,
+                           (const float4*)b.leaf_box.p, (float4*)b.inner_box.p);
+        TreeletArgs ta;
+        ta.n = (int)n; ta.leaf_max = leaf_max;
+        ta.child = (uint2*)T.child.p; ta.parent = (uint32_t*)T.parent.p; ta.counter = (uint32_t*)b.counter.p;
+        ta.count = (uint32_t*)b.node_count.p; ta.cost = (float*)b.node_cost.p;
+        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p; ta.top = (const uint32_t*)T.top.p;
+        for (uint32_t round = 0; round < opt_rounds; round++) {
+            ta.gamma = TREELET << round;
+            DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+            hipLaunchKernelGGL(treelet_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, ta);
+        }
+        hipLaunchKernelGGL(leaf_pos_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)T.parent.p,
+                           (const uint32_t*)b.node_count.p, (uint32_t*)T.pos.p, hdr);
+        hipLaunchKernelGGL(inner_range_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)b.node_count.p,
+                           (const uint32_t*)T.pos.p, (uint2*)T.range.p, hdr);
+    } else
+        hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (uint32_t*)T.pos.p);
+    DCHK(hipGetLastError());
+    DCHK(hipEventRecord(b.ev1, st));
+    uint32_t h[H_WORDS];
+    DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    DCHK(hipEventElapsedTime(&T.ms, b.ev0, b.ev1));
+    if (h[H_ERR]) { err = "device BVH: the instance topology failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
+    T.k = k;
+    T.valid = true;
+    return HJR_OK;
+}
+
+int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
+                         uint32_t tag, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+{
+    const uint32_t n = sc.n_triangles;
+    std::vector<uint32_t> list; // the non-empty instances
+    for (uint32_t i = 0; i < n_inst && i < sc.prim_offset.size(); i++)
+        if ((i + 1 < n_inst && i + 1 < sc.prim_offset.size() ? sc.prim_offset[i + 1] : n) > sc.prim_offset[i]) list.push_back(i);
+    auto ordinary = [&] { return device_bvh_build(b, sc, M, Mi, n_inst, leaf_max, opt_rounds, lights, light_floats, st, r, err); };
+    if (n == 0 || list.empty() || list.size() > HJR_TOP_MAX) return ordinary();
+    r = DeviceBvhResult();
+    if (!b.ev0) DCHK(hipEventCreate(&b.ev0));
+    if (!b.ev1) DCHK(hipEventCreate(&b.ev1));
+    auto fail_alloc = [&] { err = "device BVH: allocation or upload failed"; return HJR_ERR_DEVICE; };
+    if (!b.have_scene) {
+        if (!b.vert.upload(sc.vertices.data(), sc.vertices.size() * 4, st) || !b.norm.upload(sc.normals.data(), sc.normals.size() * 4, st) ||
+            !b.uv.upload(sc.texcoords.data(), sc.texcoords.size() * 4, st) || !b.idx.upload(sc.indices.data(), sc.indices.size() * 4, st) ||
+            !b.mat.upload(sc.material_ids.data(), sc.material_ids.size() * 4, st) || !b.prim_off.upload(sc.prim_offset.data(), sc.prim_offset.size() * 4, st))
+            return fail_alloc();
+        b.have_scene = true;
+        b.topo.valid = false;
+    }
+    std::vector<float> xf((size_t)n_inst * 24);
+    for (uint32_t i = 0; i < n_inst; i++) {
+        memcpy(&xf[24 * (size_t)i], M + 12 * (size_t)i, 48);
+        memcpy(&xf[24 * (size_t)i + 12], Mi + 12 * (size_t)i, 48);
+    }
+    const size_t nn = n;
+    const uint32_t nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+    if (!b.xf.upload(xf.data(), xf.size() * 4, st) || !b.lights.upload(lights, light_floats * 4, st) || !b.hdr.reserve(H_WORDS * 4) ||
+        !b.nodes.reserve(nn * HJR_NODE4_F4 * 16) || !b.tri_geom.reserve(nn * HJR_TRI_F4 * 16) || !b.tri_shade.reserve(nn * HJR_SHADE_F4 * 16) ||
+        !b.tri_inst.reserve(nn * 4) || !b.part.reserve(SCAN_G * 4) || !b.leaf_box.reserve(nn * 32) || !b.inner_box.reserve(nn * 32) || !b.counter.reserve(nn * 4) ||
+        !b.frontier[0].reserve(nn * sizeof(Front)) || !b.frontier[1].reserve(nn * sizeof(Front)) || !b.wide.reserve(nn * (sizeof(Wide) + 4)))
+        return fail_alloc();
+    DeviceBvh::Topology& T = b.topo;
+    if (!T.valid || T.tag != tag || T.k != list.size()) {
+        if (!b.box.reserve(nn * 32) || !b.cent.reserve(nn * 16) || !b.keys[0].reserve(nn * 8) || !b.keys[1].reserve(nn * 8) || !b.vals[0].reserve(nn * 4) ||
+            !b.vals[1].reserve(nn * 4) || !b.hist.reserve(std::max<size_t>(1, (size_t)nb * 256 * 4)) || !b.node_count.reserve(nn * 4) || !b.node_cost.reserve(nn * 4))
+            return fail_alloc();
+        if (const int rc = build_topology(b, n, n_inst, leaf_max, opt_rounds, list, st, err)) return rc;
+        T.tag = tag;
+    }
+    const uint32_t k = T.k;
+    uint32_t* hdr = (uint32_t*)b.hdr.p;
+    InstArgs a;
+    a.f = FlattenArgs();
+    a.f.vert = (const float*)b.vert.p; a.f.norm = (const float*)b.norm.p; a.f.uv = (const float*)b.uv.p; a.f.xf = (const float*)b.xf.p;
+    a.f.idx = (const uint32_t*)b.idx.p; a.f.mat = (const uint32_t*)b.mat.p; a.f.prim_off = (const uint32_t*)b.prim_off.p;
+    a.f.n = n; a.f.n_inst = n_inst;
+    a.f.shade = (float*)b.tri_shade.p; a.f.inst = (uint32_t*)b.tri_inst.p; a.f.hdr = hdr;
+    a.order = (const uint32_t*)T.order.p; a.pos = (const uint32_t*)T.pos.p; a.top = (const uint32_t*)T.top.p; a.parent = (const uint32_t*)T.parent.p;
+    a.child = (const uint2*)T.child.p; a.counter = (uint32_t*)b.counter.p;
+    a.geom = (float4*)b.tri_geom.p; a.leaf_box = (float4*)b.leaf_box.p; a.inner_box = (float4*)b.inner_box.p;
+    DCHK(hipEventRecord(b.ev0, st));
+    hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
+    if (n >= 2) DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+    hipLaunchKernelGGL(inst_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(inst_boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
+    if (k >= 2) {
+        TopArgs ta;
+        ta.n = n; ta.n_inst = n_inst; ta.k = k;
+        ta.list = (const uint32_t*)T.list.p; ta.root = (const uint32_t*)T.root.p; ta.top = (const uint32_t*)T.top.p; ta.top_ids = (const uint32_t*)T.top_ids.p;
+        ta.child = (uint2*)T.child.p; ta.range = (uint2*)T.range.p; ta.parent = (uint32_t*)T.parent.p;
+        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p; ta.hdr = hdr;
+        hipLaunchKernelGGL(inst_top_kernel, dim3(1), dim3(NT), 0, st, ta);
+    }
+    DCHK(hipGetLastError());
+    CollapseArgs ca;
+    ca.child = (const uint2*)T.child.p; ca.range = (const uint2*)T.range.p;
+    ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
+    ca.leaf_pos = (const uint32_t*)T.pos.p;
+    ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
+    ca.top = (const uint32_t*)T.top.p;
+    const int rc = collapse_and_cost(b, ca, n, nn, st, r, "the instance tree", err);
+    if (rc != HJR_OK && r.too_deep) return ordinary(); // a chain-shaped top tree (nested instances): the Morton tree over all triangles
+    if (rc == HJR_OK) r.instances = k;
+    return rc;
 }
 
 } // namespace hjr

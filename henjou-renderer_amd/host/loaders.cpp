@@ -150,6 +150,14 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 if (!(r >= 0 && r <= 3) || r != (double)(uint32_t)r) throw JsonError("Henjou_HIP.device_bvh_opt must be an integer in [0, 3]");
                 o.device_bvh_opt = (int32_t)r;
             }
+            // device_bvh_instances: per-instance trees under a per-commit top tree (option "device_bvh_instances"), stored as bit 8 of
+            // device_bvh_opt: the struct does not grow for it and the low bits stay the rounds
+            if (const Json* v = h->find("device_bvh_instances")) {
+                const bool ok = v->is_bool() || (v->is_number() && (v->as_number() == 0.0 || v->as_number() == 1.0));
+                if (!ok) throw JsonError("Henjou_HIP.device_bvh_instances must be true, false, 0 or 1");
+                if (!o.device_bvh) throw JsonError("Henjou_HIP.device_bvh_instances needs \"device_bvh\": true");
+                if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x100;
+            }
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
             if (const Json* v = h->find("passes")) {
                 const double n = v->is_number() ? v->as_number() : -1.0;

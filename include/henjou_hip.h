@@ -140,7 +140,8 @@ typedef struct hjr_render_option {
                                   * bit 1: hjr_render_file / henjou_cli set the context option "verbose" (key "verbose": true; the struct does not grow for it) */
     int32_t device_bvh;          /* default 0; 1: hjr_render_file / henjou_cli build the frame data on the device (option "device_bvh");
                                   * 1 + N: that and option "device_bvh_refit" N (key "device_bvh_refit": N; the struct does not grow for it) */
-    int32_t device_bvh_opt;      /* default 0; 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt") */
+    int32_t device_bvh_opt;      /* default 0; low 8 bits: 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt");
+                                  * bit 8: key "device_bvh_instances" (option of the same name; the struct does not grow for it) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
     float noise_threshold;       /* default 0 (off); > 0: hjr_render_file / henjou_cli set hjr_adaptive.noise_threshold, render each frame in
@@ -278,6 +279,10 @@ typedef struct hjr_stats {
     uint32_t bvh_refits;         /* consecutive refits behind the current frame data (option "device_bvh_refit"); 0 = a full build */
     float    bvh_sah;            /* BVH4 SAH of a device-built or refitted tree, computed on the device (Ci 1.2 per inner slot, Ct 1 per triangle
                                   * of a leaf slot, slot area over root area; the same bits every run); 0 for host-built data */
+    uint32_t bvh_instances;      /* instance subtrees under the top tree of the current frame data (option "device_bvh_instances");
+                                  * 0 = an ordinary build or host-built data */
+    float    bvh_topology_ms;    /* HIP-event time of the last per-instance topology build of that option; the commits that reuse the
+                                  * topology leave it as it is */
 } hjr_stats;
 
 typedef struct hjr_scene hjr_scene; /* owning, host side (SceneData + animations) */
@@ -466,6 +471,14 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *                                 report it; bvh_builder stays 1.  0 (default): every commit builds.  The host build ignores it        [*]
  *   "device_bvh_refit_growth" 0..10000  percent (default 10): when a refit's tree cost (hjr_stats.bvh_sah) exceeds the last full build's by
  *                                 more than this, the NEXT commit is a full build; the refit just made stays current                   [*]
+ *   "device_bvh_instances" 0 1    with "device_bvh" 1: the topology of every instance's triangles is built once per uploaded scene and build
+ *                                 options (object space, "device_bvh_opt" rounds inside an instance) and kept on the device; every commit
+ *                                 flattens in that leaf order, recomputes the boxes inside the instance subtrees, builds a top tree over the
+ *                                 instances' world boxes (at most 1024 non-empty instances) and collapses to one world-space BVH4.  Same
+ *                                 frames; rigid motion never degrades the tree.  "device_bvh_refit" / "device_bvh_refit_growth" are ignored
+ *                                 with it (hjr_stats.bvh_refits stays 0); hjr_stats.bvh_instances / bvh_topology_ms report it.  More than
+ *                                 1024 non-empty instances, or a top tree deeper than the traversal stack, silently take the ordinary build
+ *                                 (bvh_instances 0).  0 (default): the ordinary build.  The host build ignores it                    [*]
  *   "denoise_variance" 0 1        1: hjr_render_denoised renders the variance AOV along with the guides and runs the variance-guided filter
  *                                 (hjr_denoise_var_device) in the two Denoise modes; a sample pass filters the running mean with the variance
  *                                 over n = sample_end.  0 (default): today's call, bit for bit
@@ -483,6 +496,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
  * "device_bvh_refit": N (integer 0..1000, only together with "device_bvh": true) of that section is stored as hjr_render_option.device_bvh
  * = 1 + N (the struct does not grow for it): hjr_render_file and henjou_cli set "device_bvh" 1 and "device_bvh_refit" N.
+ * "device_bvh_instances": true (only together with "device_bvh": true) is stored as bit 8 of hjr_render_option.device_bvh_opt, whose low
+ * 8 bits stay the treelet rounds: hjr_render_file and henjou_cli mask the field and set both options.
  * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name; "denoise_temporal": true
  * of that section is stored as hjr_render_option.denoise_variance = 2 and sets both options (refused together with "noise_threshold" > 0:
  * an adaptive frame that stops early never reaches the pass that advances the history).
