@@ -66,6 +66,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     if (opt.device_bvh > 1) HJRX(hjr_set_option(ctx, "device_bvh_refit", opt.device_bvh - 1)); // key "device_bvh_refit": stored as 1 + N
     if (opt.device_bvh_opt & 0xff) HJRX(hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt & 0xff));
     if (opt.device_bvh_opt & 0x100) HJRX(hjr_set_option(ctx, "device_bvh_instances", 1)); // key "device_bvh_instances": bit 8 of the field
+    if (opt.device_bvh_opt & 0x200) HJRX(hjr_set_option(ctx, "device_bvh_graft", 1)); // key "device_bvh_graft": bit 9
     HJRX(hjr_upload_scene(ctx, &view));
     // "noise_threshold": each rank stops its own converged tiles between the sample passes (the rule does not depend on the rank); the one
     // gather per frame is unchanged.  A rank without tiles has nothing to adapt.

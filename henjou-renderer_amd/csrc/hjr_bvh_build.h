@@ -48,6 +48,7 @@ struct DeviceBvh {
     DevBuf node_count, node_cost, leaf_pos; // scratch of the treelet restructuring ("device_bvh_opt")
     // the frame data a build writes; hjr_commit_transforms swaps them with the context's current buffers when the build succeeds
     DevBuf nodes, tri_geom, tri_shade, tri_inst, lights;
+    DevBuf stage; // option "device_bvh_graft": a commit's skeleton nodes at their skeleton ids, before the top-node count is known
     // Option "device_bvh_instances": the BVH2 whose subtrees are the instances, built once per uploaded scene and build tag and kept
     // between commits.  A commit rewrites only the k - 1 `top` nodes above the instance roots (child, range, parent of their children).
     struct Topology {
@@ -56,6 +57,13 @@ struct DeviceBvh {
         DevBuf top, top_ids;          // per inner node: 1 above the instance roots | those nodes' ids, ascending (the root first)
         DevBuf root, list;            // per instance: BVH2 ref of its subtree | the non-empty instances, ascending
         DevBuf bounds;                // scratch of the build: per instance centroid bounds
+        // Option "device_bvh_graft": the BVH4 collapse of every instance subtree of more than leaf_max triangles ("skeleton"), made once
+        // from the object-space boxes; ids breadth-first over all instances together.  With it only pos, order, list and these are kept.
+        DevBuf skel_refs, skel_parent; // per skeleton node: refs row (inner refs are skeleton ids) | 4 * parent + slot (0xffffffff: an instance root)
+        DevBuf inst_ref, inst_stat;    // per non-empty instance: skeleton id of its root, or its leaf ref (<= leaf_max triangles) | worst pending entries, largest leaf depth below its root
+        DevBuf top_box;                // scratch of a commit: boxes of the k instances, then of the k - 1 binary top nodes
+        bool graft = false, skel_deep = false; // built with the skeleton | a skeleton deeper than the traversal stack: commits take the ordinary build
+        uint32_t n_skel = 0;           // skeleton nodes
         bool valid = false;
         uint32_t tag = 0, k = 0;      // build tag it was built under, non-empty instances
         float ms = 0.0f;              // HIP-event time of its build
@@ -92,6 +100,10 @@ int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
 // boxes inside the instance subtrees, builds the top tree over the instance boxes in one workgroup, collapses and costs like a build.
 // No non-empty instance, more than HJR_TOP_MAX of them, or a tree deeper than the traversal stack: device_bvh_build runs instead
 // (r.instances == 0).  Writes and errors as device_bvh_build.
+// `graft` (option "device_bvh_graft"): the topology also holds every instance's BVH4, collapsed once by object-space areas; a commit
+// flattens, refits those nodes bottom-up (device_bvh_refit's climb), builds and collapses the top tree over the instance boxes in one
+// workgroup and places the instance nodes behind the top nodes.  No per-level launches, one host wait; the BVH2 is freed after the
+// topology build.  The same fallbacks.
 int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
-                         uint32_t tag, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+                         uint32_t tag, bool graft, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
 } // namespace hjr

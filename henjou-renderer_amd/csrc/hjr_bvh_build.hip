@@ -14,6 +14,9 @@
 // Instance trees (option "device_bvh_instances", device_bvh_instances below): the BVH2 is built once per scene over object-space boxes with
 // the instance id on top of the sort key, so that every instance is one subtree, and kept; a commit flattens in its leaf order, computes
 // the world boxes inside the instance subtrees, builds the top tree over the instance boxes in one workgroup, then collapse and cost.
+// Grafted instance trees (option "device_bvh_graft" with it): the topology also keeps every instance's BVH4, collapsed once by the
+// object-space areas (the skeleton); a commit flattens, refits the skeleton's boxes with the refit's climb, clusters and collapses the
+// top tree in one workgroup and places the skeleton behind the top nodes: no per-level launches and no BVH2 after the topology build.
 // No workgroup ever waits for another one; every cross-launch size the host does not know is read by the kernels from `hdr`.
 #include <hip/hip_runtime.h>
 
@@ -670,8 +673,8 @@ __global__ void __launch_bounds__(NT) inner_range_kernel(int n, const uint2* chi
 }
 
 // ---- collapse to BVH4 (frame.cpp::emit_bvh4) ------------------------------------------------------------------------------------
-struct Front { uint32_t ref, pend, depth, pad; };     // a wide node of the current level: its BVH2 node, pending entries above it, its depth
-struct Wide { uint32_t child[4], depth[4], n, pend, pad[2]; }; // children in emit_bvh4's slot order
+struct Front { uint32_t ref, pend, depth, tag; };     // a wide node of the current level: its BVH2 node, pending entries above it, its depth, its instance (skeleton; else 0)
+struct Wide { uint32_t child[4], depth[4], n, pend, tag, pad; }; // children in emit_bvh4's slot order
 
 struct CollapseArgs {
     const uint2 *child, *range;
@@ -681,6 +684,7 @@ struct CollapseArgs {
     uint32_t cap; // wide nodes the buffers hold (>= the wide nodes of any tree over these triangles)
     uint32_t* hdr;
     const uint32_t* top; // device_bvh_instances: per inner node, 1 above the instance roots (null: an ordinary build)
+    uint32_t* inst_stat; // device_bvh_graft, the skeleton: per instance (Front::tag) the maxima of h and of the leaf depth (null otherwise)
 };
 // a BVH2 node that becomes a wide node: inner, and the root or more than leaf_max triangles (frame.cpp:166).  A node above the
 // instance roots always does: instances keep their id order in tri_geom, so its triangles are no contiguous row range.
@@ -721,6 +725,8 @@ __global__ void __launch_bounds__(NT) wide_expand_kernel(CollapseArgs a, const F
         uint32_t ni = 0;
         for (uint32_t k = 0; k < w.n; k++) ni += is_inner(a, w.child[k]) ? 1u : 0u;
         w.pend = f.pend;
+        w.tag = f.tag;
+        w.pad = 0u;
         wide[i] = w;
         n_inner[i] = ni;
     }
@@ -737,6 +743,7 @@ __global__ void __launch_bounds__(NT) wide_emit_kernel(CollapseArgs a, const Wid
         // emit_bvh4's stack bound: a visited wide node leaves (children - 1) entries pending above those of its parent
         const uint32_t h = w.pend + (w.n > 0 ? w.n - 1 : 0);
         worst = max(worst, h);
+        uint32_t leaf_depth = 0;
         for (int c = 0; c < 4; c++) {
             if ((uint32_t)c < w.n) {
                 const uint32_t r = w.child[c];
@@ -747,16 +754,21 @@ __global__ void __launch_bounds__(NT) wide_emit_kernel(CollapseArgs a, const Wid
                 if (is_inner(a, r)) {
                     const uint32_t j = off[i] + k_in++;
                     ref = base + F + j;
-                    if (j < a.cap) next[j] = Front{ r, h, w.depth[c], 0u };
+                    if (j < a.cap) next[j] = Front{ r, h, w.depth[c], w.tag };
                 } else {
                     ref = (r & REF_LEAF) ? (HJR_LEAF_FLAG | (1u << 27) | (a.leaf_pos ? a.leaf_pos[r & ~REF_LEAF] : (r & ~REF_LEAF))) : (HJR_LEAF_FLAG | (a.range[r].y << 27) | a.range[r].x);
-                    depth = max(depth, w.depth[c]);
+                    leaf_depth = max(leaf_depth, w.depth[c]);
                 }
                 q[24 + c] = __uint_as_float(ref);
             } else { // unused slot: inverted box, empty leaf
                 q[c] = 1e30f; q[4 + c] = -1e30f; q[8 + c] = 1e30f; q[12 + c] = -1e30f; q[16 + c] = 1e30f; q[20 + c] = -1e30f;
                 q[24 + c] = __uint_as_float(HJR_LEAF_FLAG);
             }
+        }
+        depth = max(depth, leaf_depth);
+        if (a.inst_stat) { // integer maxima: the same values whatever order the lanes run in
+            atomicMax(&a.inst_stat[2 * (size_t)w.tag], h);
+            atomicMax(&a.inst_stat[2 * (size_t)w.tag + 1], leaf_depth);
         }
         float4* o = nodes + (size_t)(base + i) * HJR_NODE4_F4;
         for (int v = 0; v < HJR_NODE4_F4; v++) o[v] = make_float4(q[4 * v], q[4 * v + 1], q[4 * v + 2], q[4 * v + 3]);
@@ -1097,8 +1109,10 @@ __global__ void __launch_bounds__(NT) inst_flatten_kernel(InstArgs a)
             g[1] = make_float4(v[4], v[5], v[6], v[7]);
             g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(a.f.mat[t]), 0.0f);
             atomicMax(&s_max, __float_as_uint(tri_box(v, bl, bh)));
-            a.leaf_box[2 * (size_t)k] = make_float4(bl[0], bl[1], bl[2], 0.0f);
-            a.leaf_box[2 * (size_t)k + 1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
+            if (a.leaf_box) { // (null under device_bvh_graft: the skeleton's boxes come from tri_geom)
+                a.leaf_box[2 * (size_t)k] = make_float4(bl[0], bl[1], bl[2], 0.0f);
+                a.leaf_box[2 * (size_t)k + 1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
+            }
         }
     }
     __syncthreads();
@@ -1233,6 +1247,326 @@ __global__ void __launch_bounds__(NT) inst_top_kernel(TopArgs a)
     }
 }
 
+// ---- grafted instance trees (option "device_bvh_graft") -----------------------------------------------------------------------------
+// Skeleton, once per topology: the collapse's own kernels (wide_expand_kernel / wide_emit_kernel: emit_bvh4's rules on the object-space
+// boxes) run level by level from a frontier that holds the root of every instance of more than leaf_max triangles, in instance order,
+// so that ids are breadth-first over all instances together from 0.  Of the nodes they write only the refs rows are kept, with the
+// parent slot of every node, and per instance the maxima of the pending-entry count and of the leaf depth below its root.
+// Every commit: graft_boxes_kernel (the refit's climb over the skeleton, into `stage` at the skeleton ids), graft_top_kernel (instance
+// boxes, top tree, its collapse: the top nodes [0, base)), graft_place_kernel (stage -> nodes at base + id, base added to the inner
+// refs).  The top-node count depends on the clustering, which needs this pose's instance boxes: it cannot be known before the boxes.
+// H_ERR bits of these kernels: 8 / 16 skeleton refs, 32 skeleton parent, 64 a skeleton node that was not written, 512 instance roots,
+// 1024 top tree, 2048 more nodes than the buffers hold.
+constexpr uint32_t SK_NONE = 0xffffffffu;
+
+// the frontier of the skeleton's first level and inst_ref of every non-empty instance (one workgroup; a thread owns four consecutive
+// instances, so that the scan numbers the roots in instance order)
+__global__ void __launch_bounds__(NT) skel_init_kernel(uint32_t n, uint32_t n_inst, uint32_t k, uint32_t leaf_max, const uint32_t* list, const uint32_t* root,
+                                                       const uint32_t* top, const uint2* range, const uint32_t* pos, Front* fr, uint32_t* inst_ref, uint32_t* hdr)
+{
+    __shared__ uint32_t s_scan[4];
+    uint32_t big[4], mine = 0, tot;
+    bool bad = false;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) {
+        const uint32_t s = 4 * threadIdx.x + q;
+        big[q] = SK_NONE;
+        if (s >= k) continue;
+        const uint32_t in = list[s];
+        const uint32_t ref = in < n_inst ? root[in] : SK_NONE;
+        const uint32_t id = ref & ~REF_LEAF;
+        uint32_t leaf = HJR_LEAF_FLAG;
+        if (ref == SK_NONE) bad = true;
+        else if (ref & REF_LEAF) {
+            if (id < n && pos[id] < n) leaf = HJR_LEAF_FLAG | (1u << 27) | pos[id];
+            else bad = true;
+        } else if (id + 1 < n && !top[id]) {
+            const uint2 rg = range[id];
+            if (rg.y == 0 || rg.x >= n || rg.y > n - rg.x) bad = true;
+            else if (rg.y > leaf_max) { big[q] = id; mine++; }
+            else leaf = HJR_LEAF_FLAG | (rg.y << 27) | rg.x;
+        } else bad = true;
+        inst_ref[s] = leaf;
+    }
+    uint32_t at = block_scan(mine, tot, s_scan);
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) {
+        if (big[q] == SK_NONE) continue;
+        const uint32_t s = 4 * threadIdx.x + q;
+        inst_ref[s] = at;
+        fr[at++] = Front{ big[q], 0u, 0u, s };
+    }
+    if (bad) atomicOr(&hdr[H_ERR], 512u);
+    if (threadIdx.x == 0) { hdr[H_BASE] = 0; hdr[H_F] = tot; }
+}
+// what is kept of the n_skel nodes the collapse wrote: the refs row, and 4 * parent + slot of every node an inner slot refers to
+__global__ void __launch_bounds__(NT) skel_keep_kernel(uint32_t n_skel, const float4* nodes, float4* refs, uint32_t* parent, uint32_t* hdr)
+{
+    const uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i >= n_skel) return;
+    const float4 r = nodes[(size_t)i * HJR_NODE4_F4 + 6];
+    refs[i] = r;
+    uint32_t err = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const uint32_t ref = ref_of(r, c);
+        if (!ref_inner(ref)) continue;
+        if (ref <= i || ref >= n_skel) err |= 8u;
+        else parent[ref] = 4u * i + (uint32_t)c;
+    }
+    if (err) atomicOr(&hdr[H_ERR], err);
+}
+
+// refit_boxes_kernel over the skeleton: a.nodes is the stage, a.n_nodes the skeleton's size, a.parent the kept parent slots; a lane
+// starts at every node without inner children and stops at an instance root.  refit_node checks every ref before it follows it, a
+// parent id must be below the child's (so every climb ends), and graft_place_kernel finds a node whose children did not all arrive.
+__global__ void __launch_bounds__(NT) graft_boxes_kernel(RefitArgs a, const float4* refs)
+{
+    uint32_t i = blockIdx.x * NT + threadIdx.x;
+    if (i >= a.n_nodes) return;
+    float4 r = refs[i];
+    if (inner_slots(r) != 0) return;
+    const float pad = __uint_as_float(a.f.hdr[H_SMAX]) * (1.0f / 8192.0f);
+    for (;;) {
+        refit_node(a, i, r, pad);
+        const uint32_t ps = a.parent[i];
+        if (ps == SK_NONE) return; // an instance root
+        const uint32_t p = ps >> 2;
+        if (p >= i) { atomicOr(&a.f.hdr[H_ERR], 32u); return; }
+        r = refs[p];
+        const uint32_t before = __hip_atomic_fetch_add(&a.counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before + 1u != inner_slots(r)) return; // a sibling's lane finishes the parent
+        i = p;
+    }
+}
+
+// The top tree over the instance boxes and its BVH4, in one workgroup (workgroup barriers only).  An instance's box is the union of
+// its root node's slot boxes in the stage, or of its triangles' padded boxes when it has no node.  Clustering: inst_top_kernel's rule
+// (smallest union area, mutual pairs merge into the smaller slot, ties to the smaller slot); merge number m is binary node m, the
+// last one the root.  Top-tree refs: an instance slot s < k, or k + m.  The binary tree is collapsed breadth-first with
+// wide_expand_kernel's rule, where only binary nodes are expanded and an instance is a leaf slot (<= leaf_max triangles) or an inner
+// slot (base + its root's skeleton id).  `base`, the number of top nodes, is what the first of two identical walks counts; the second
+// one writes.  Boxes of instances and binary nodes live in a.box (global, written and read by this workgroup only, barriers between).
+struct GraftTopArgs {
+    uint32_t n, k, n_skel, cap;
+    const uint32_t *inst_ref, *inst_stat;
+    const float4 *stage, *geom;
+    float4 *box, *nodes;
+    uint32_t* hdr;
+};
+__device__ __forceinline__ uint32_t pick4(const uint32_t (&v)[4], uint32_t i) { return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3])); }
+__device__ __forceinline__ void put4(uint32_t (&v)[4], uint32_t i, uint32_t x)
+{
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) if (c == i) v[c] = x;
+}
+__global__ void __launch_bounds__(NT) graft_top_kernel(GraftTopArgs a)
+{
+    __shared__ float s_box[6][HJR_TOP_MAX];                       // the clusters' boxes; after the clustering the two frontiers
+    __shared__ uint32_t s_ref[HJR_TOP_MAX], s_partner[HJR_TOP_MAX]; // s_ref TOP_NONE: the slot is not an active cluster
+    __shared__ uint2 s_kid[HJR_TOP_MAX];                          // binary node m: its two top-tree refs
+    __shared__ float s_area[HJR_TOP_MAX];                         // ... and its area (area_of's expression)
+    __shared__ uint32_t s_scan[4], s_err;
+    const uint32_t k = min(a.k, HJR_TOP_MAX), n = a.n;
+    if (threadIdx.x == 0) s_err = 0u;
+    __syncthreads();
+    const float pad = __uint_as_float(a.hdr[H_SMAX]) * (1.0f / 8192.0f);
+    for (uint32_t s = threadIdx.x; s < k; s += NT) {
+        const uint32_t ref = a.inst_ref[s];
+        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
+        if (ref_inner(ref)) {
+            if (ref < a.n_skel) {
+                const float4* nd = a.stage + (size_t)ref * HJR_NODE4_F4;
+                for (int ax = 0; ax < 3; ax++) {
+                    const float4 l = nd[2 * ax], h = nd[2 * ax + 1];
+                    lo[ax] = smin(smin(l.x, l.y), smin(l.z, l.w));
+                    hi[ax] = smax(smax(h.x, h.y), smax(h.z, h.w));
+                }
+            } else s_err = 1u;
+        } else {
+            const uint32_t first = ref & 0x7ffffffu, cnt = (ref >> 27) & 15u;
+            if (cnt > 0 && first < n && cnt <= n - first) {
+                for (int ax = 0; ax < 3; ax++) { lo[ax] = 3.402823466e+38f; hi[ax] = -3.402823466e+38f; }
+                for (uint32_t t = 0; t < cnt; t++) {
+                    const float4* g = a.geom + HJR_TRI_F4 * (size_t)(first + t);
+                    const float4 g0 = g[0], g1 = g[1], g2 = g[2];
+                    lo[0] = smin(smin(lo[0], g0.x), smin(g0.w, g1.z)); hi[0] = smax(smax(hi[0], g0.x), smax(g0.w, g1.z));
+                    lo[1] = smin(smin(lo[1], g0.y), smin(g1.x, g1.w)); hi[1] = smax(smax(hi[1], g0.y), smax(g1.x, g1.w));
+                    lo[2] = smin(smin(lo[2], g0.z), smin(g1.y, g2.x)); hi[2] = smax(smax(hi[2], g0.z), smax(g1.y, g2.x));
+                }
+                for (int ax = 0; ax < 3; ax++) { lo[ax] -= pad; hi[ax] += pad; }
+            } else s_err = 1u;
+        }
+        for (int ax = 0; ax < 3; ax++) { s_box[ax][s] = lo[ax]; s_box[3 + ax][s] = hi[ax]; }
+        s_ref[s] = s;
+        a.box[2 * (size_t)s] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+        a.box[2 * (size_t)s + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+    }
+    __syncthreads();
+    if (s_err) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 512u); return; }
+    uint32_t merged = 0;
+    for (uint32_t round = 0; merged + 1 < k; round++) {
+        if (round >= k) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (never: every round merges)
+        for (uint32_t s = threadIdx.x; s < k; s += NT) {
+            uint32_t bj = TOP_NONE;
+            if (s_ref[s] != TOP_NONE) {
+                const float lx = s_box[0][s], ly = s_box[1][s], lz = s_box[2][s], hx = s_box[3][s], hy = s_box[4][s], hz = s_box[5][s];
+                float best = 0.0f;
+                for (uint32_t j = 0; j < k; j++) {
+                    if (j == s || s_ref[j] == TOP_NONE) continue;
+                    const float dx = smax(hx, s_box[3][j]) - smin(lx, s_box[0][j]), dy = smax(hy, s_box[4][j]) - smin(ly, s_box[1][j]),
+                                dz = smax(hz, s_box[5][j]) - smin(lz, s_box[2][j]);
+                    const float area = dx * dy + dy * dz + dz * dx;
+                    if (bj == TOP_NONE || area < best) { best = area; bj = j; }
+                }
+            }
+            s_partner[s] = bj;
+        }
+        __syncthreads();
+        uint32_t mine = 0, tot;
+        bool m[4];
+        for (uint32_t q = 0; q < 4; q++) {
+            const uint32_t s = 4 * threadIdx.x + q;
+            const uint32_t j = s < k ? s_partner[s] : TOP_NONE;
+            m[q] = j != TOP_NONE && j > s && j < k && s_partner[j] == s;
+            mine += m[q] ? 1u : 0u;
+        }
+        uint32_t at = merged + block_scan(mine, tot, s_scan);
+        for (uint32_t q = 0; q < 4; q++) {
+            if (!m[q]) continue;
+            const uint32_t s = 4 * threadIdx.x + q, j = s_partner[s], idx = at++;
+            if (idx + 1 >= k) { s_err = 1u; continue; } // (never: k - 1 merges in all)
+            float lo[3], hi[3];
+            for (int ax = 0; ax < 3; ax++) {
+                lo[ax] = s_box[ax][s] = smin(s_box[ax][s], s_box[ax][j]);
+                hi[ax] = s_box[3 + ax][s] = smax(s_box[3 + ax][s], s_box[3 + ax][j]);
+            }
+            const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+            s_kid[idx] = make_uint2(s_ref[s], s_ref[j]);
+            s_area[idx] = (dx < 0) ? 0.0f : 2.0f * (dx * dy + dy * dz + dz * dx);
+            s_ref[s] = k + idx;
+            s_ref[j] = TOP_NONE;
+            a.box[2 * (size_t)(k + idx)] = make_float4(lo[0], lo[1], lo[2], 0.0f);
+            a.box[2 * (size_t)(k + idx) + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
+        }
+        __syncthreads();
+        if (s_err || tot == 0) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (tot 0: a non-finite box, reported before this bit)
+        merged += tot;
+    }
+    // the BVH4 of the top tree.  Frontier entries: top-tree ref, pending entries above the node, its binary depth
+    uint32_t* fr = reinterpret_cast<uint32_t*>(&s_box[0][0]);
+    uint32_t worst = 0, depth = 0, base = 0;
+    const bool single_leaf = k == 1 && !ref_inner(a.inst_ref[0]); // one instance without a node: a root with one leaf slot
+    for (int pass = (k == 1 && !single_leaf) ? 2 : 0; pass < 2; pass++) { // (one instance with nodes: its skeleton is the tree)
+        uint32_t *cur = fr, *next = fr + 3 * HJR_TOP_MAX;
+        uint32_t F = 1, lbase = 0;
+        __syncthreads();
+        if (threadIdx.x == 0) { cur[0] = k == 1 ? 0u : 2 * k - 2; cur[HJR_TOP_MAX] = 0u; cur[2 * HJR_TOP_MAX] = 0u; }
+        __syncthreads();
+        while (F > 0) {
+            uint32_t run = 0;
+            for (uint32_t chunk = 0; chunk < F; chunk += NT) {
+                const uint32_t i = chunk + threadIdx.x;
+                const bool valid = i < F;
+                uint32_t ch[4] = { 0u, 0u, 0u, 0u }, dp[4] = { 0u, 0u, 0u, 0u }, nc = 0, ni = 0, pend = 0;
+                if (valid) {
+                    const uint32_t ref = cur[i], d0 = cur[2 * HJR_TOP_MAX + i];
+                    pend = cur[HJR_TOP_MAX + i];
+                    if (ref < k) { ch[0] = ref; dp[0] = d0; nc = 1; }
+                    else {
+                        const uint2 c = s_kid[ref - k];
+                        ch[0] = c.x; ch[1] = c.y; dp[0] = dp[1] = d0 + 1; nc = 2;
+                    }
+                    while (nc < 4) { // replace the binary child of largest area by its two children
+                        uint32_t best = 4;
+                        float barea = -1.0f;
+#pragma unroll
+                        for (uint32_t c = 0; c < 4; c++)
+                            if (c < nc && ch[c] >= k) { const float ar = s_area[ch[c] - k]; if (ar > barea) { barea = ar; best = c; } }
+                        if (best == 4) break;
+                        const uint2 c = s_kid[pick4(ch, best) - k];
+                        const uint32_t dd = pick4(dp, best) + 1;
+                        put4(ch, best, c.x); put4(dp, best, dd);
+                        put4(ch, nc, c.y); put4(dp, nc, dd);
+                        nc++;
+                    }
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; c++) ni += c < nc && ch[c] >= k ? 1u : 0u;
+                }
+                uint32_t tot;
+                const uint32_t off = run + block_scan(ni, tot, s_scan);
+                if (valid) {
+                    const uint32_t h = pend + nc - 1;
+                    worst = max(worst, h);
+                    float q[28];
+                    uint32_t k_in = 0;
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; c++) {
+                        uint32_t ref = HJR_LEAF_FLAG;
+                        float4 lo = make_float4(1e30f, 1e30f, 1e30f, 0.0f), hi = make_float4(-1e30f, -1e30f, -1e30f, 0.0f);
+                        if (c < nc) {
+                            const uint32_t r = ch[c];
+                            if (r >= k) {
+                                const uint32_t j = off + k_in++;
+                                ref = lbase + F + j;
+                                if (j < HJR_TOP_MAX) { next[j] = r; next[HJR_TOP_MAX + j] = h; next[2 * HJR_TOP_MAX + j] = dp[c]; }
+                            } else {
+                                const uint32_t ir = a.inst_ref[r];
+                                if (ref_inner(ir)) {
+                                    ref = base + ir;
+                                    worst = max(worst, h + a.inst_stat[2 * (size_t)r]);
+                                    depth = max(depth, dp[c] + a.inst_stat[2 * (size_t)r + 1]);
+                                } else {
+                                    ref = ir;
+                                    depth = max(depth, dp[c]);
+                                }
+                            }
+                            if (pass == 1) { lo = a.box[2 * (size_t)r]; hi = a.box[2 * (size_t)r + 1]; }
+                        }
+                        q[c] = lo.x; q[4 + c] = hi.x; q[8 + c] = lo.y; q[12 + c] = hi.y; q[16 + c] = lo.z; q[20 + c] = hi.z;
+                        q[24 + c] = __uint_as_float(ref);
+                    }
+                    if (pass == 1 && lbase + i < a.cap) {
+                        float4* o = a.nodes + (size_t)(lbase + i) * HJR_NODE4_F4;
+                        for (int v = 0; v < HJR_NODE4_F4; v++) o[v] = make_float4(q[4 * v], q[4 * v + 1], q[4 * v + 2], q[4 * v + 3]);
+                    }
+                }
+                run += tot;
+            }
+            __syncthreads();
+            lbase += F;
+            F = min(run, HJR_TOP_MAX);
+            uint32_t* t = cur; cur = next; next = t;
+        }
+        if (pass == 0) { base = lbase; worst = 0; depth = 0; }
+    }
+    if (k == 1 && !single_leaf && threadIdx.x == 0) { worst = a.inst_stat[0]; depth = a.inst_stat[1]; }
+    if (worst) atomicMax(&a.hdr[H_WORST], worst);
+    if (depth) atomicMax(&a.hdr[H_DEPTH], depth);
+    if (threadIdx.x == 0) {
+        if (base > a.cap || a.n_skel > a.cap - base) atomicOr(&a.hdr[H_ERR], 2048u);
+        else { a.hdr[H_F] = base; a.hdr[H_BASE] = base + a.n_skel; } // the top-node count for graft_place_kernel, all nodes for the cost
+    }
+}
+
+// stage -> nodes behind the hdr[H_F] top nodes, one lane per float4; the inner refs of a refs row become final ids
+__global__ void __launch_bounds__(NT) graft_place_kernel(uint32_t n_skel, uint32_t cap, const float4* stage, const uint32_t* counter, float4* nodes, uint32_t* hdr)
+{
+    const size_t t = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (t >= (size_t)n_skel * HJR_NODE4_F4) return;
+    const uint32_t base = hdr[H_F], id = (uint32_t)(t / HJR_NODE4_F4);
+    if (base > cap || n_skel > cap - base) return; // (graft_top_kernel set the bit)
+    float4 x = stage[t];
+    if (t % HJR_NODE4_F4 == 6) {
+        if (counter[id] != inner_slots(x)) atomicOr(&hdr[H_ERR], 64u); // its children did not all arrive: the node was never written
+        uint32_t r[4] = { __float_as_uint(x.x), __float_as_uint(x.y), __float_as_uint(x.z), __float_as_uint(x.w) };
+#pragma unroll
+        for (int c = 0; c < 4; c++) if (ref_inner(r[c])) r[c] += base;
+        x = make_float4(__uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2]), __uint_as_float(r[3]));
+    }
+    nodes[(size_t)base * HJR_NODE4_F4 + t] = x;
+}
+
 inline unsigned blocks_for(size_t n) { return (unsigned)std::max<size_t>(1, (n + NT - 1) / NT); }
 
 } // namespace
@@ -1241,7 +1575,7 @@ namespace hjr {
 
 void DeviceBvh::release()
 {
-    for (DevBuf* x : { &vert, &norm, &uv, &idx, &mat, &prim_off, &xf, &wv, &box, &cent, &keys[0], &keys[1], &vals[0], &vals[1], &hist, &part, &leaf_box,
+    for (DevBuf* x : { &stage, &vert, &norm, &uv, &idx, &mat, &prim_off, &xf, &wv, &box, &cent, &keys[0], &keys[1], &vals[0], &vals[1], &hist, &part, &leaf_box,
                        &inner_box, &inner_child, &inner_range, &parent, &counter, &frontier[0], &frontier[1], &wide, &hdr, &node_count, &node_cost, &leaf_pos,
                        &nodes, &tri_geom, &tri_shade, &tri_inst, &lights })
         x->release();
@@ -1254,9 +1588,11 @@ void DeviceBvh::release()
 
 void DeviceBvh::drop_topology()
 {
-    for (DevBuf* x : { &topo.child, &topo.range, &topo.parent, &topo.pos, &topo.order, &topo.top, &topo.top_ids, &topo.root, &topo.list, &topo.bounds }) x->release();
-    topo.valid = false;
-    topo.k = 0;
+    for (DevBuf* x : { &topo.child, &topo.range, &topo.parent, &topo.pos, &topo.order, &topo.top, &topo.top_ids, &topo.root, &topo.list, &topo.bounds,
+                       &topo.skel_refs, &topo.skel_parent, &topo.inst_ref, &topo.inst_stat, &topo.top_box })
+        x->release();
+    topo.valid = topo.graft = topo.skel_deep = false;
+    topo.k = topo.n_skel = 0;
 }
 
 #define DCHK(call)                                                                                           \
@@ -1436,7 +1772,7 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
     ca.leaf_pos = restructure ? (const uint32_t*)b.leaf_pos.p : nullptr;
     ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
-    ca.top = nullptr;
+    ca.top = nullptr; ca.inst_stat = nullptr;
     return collapse_and_cost(b, ca, n, nn, st, r, "the restructured tree", err);
 }
 
@@ -1497,8 +1833,69 @@ int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
 
 // The topology of option "device_bvh_instances" into b.topo (kernel comment above); the object-space scene is on the device and the
 // build's scratch is reserved.  One host wait; b.topo.ms is its HIP-event time.
-static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds, const std::vector<uint32_t>& list, hipStream_t st,
-                          std::string& err)
+// The skeleton of option "device_bvh_graft" (kernel comment above) from the finished BVH2 of b.topo: the collapse's level loop from the
+// instance roots, into b.nodes as scratch; then the BVH2 is freed.  b.leaf_box / b.inner_box hold the object-space boxes.
+static int build_skeleton(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t leaf_max, bool have_boxes, hipStream_t st, std::string& err)
+{
+    DeviceBvh::Topology& T = b.topo;
+    const size_t nn = std::max<uint32_t>(n, 1u);
+    const uint32_t k = T.k;
+    uint32_t* hdr = (uint32_t*)b.hdr.p;
+    if (!T.inst_ref.reserve((size_t)k * 4) || !T.inst_stat.reserve((size_t)k * 8) || !T.top_box.reserve((size_t)k * 64)) {
+        err = "device BVH: allocation or upload failed";
+        return HJR_ERR_DEVICE;
+    }
+    if (!have_boxes && n >= 2) { // without treelet rounds the topology build had no use for the object-space node boxes
+        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)T.order.p, (const uint32_t*)nullptr, (const float*)nullptr,
+                           (const uint32_t*)b.mat.p, (const float*)b.box.p, (float*)nullptr, (float*)b.leaf_box.p);
+        DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+        hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)T.parent.p, (uint32_t*)b.counter.p,
+                           (const float4*)b.leaf_box.p, (float4*)b.inner_box.p);
+    }
+    DCHK(hipMemsetAsync(T.inst_stat.p, 0, (size_t)k * 8, st));
+    Front* fr[2] = { (Front*)b.frontier[0].p, (Front*)b.frontier[1].p };
+    Wide* wide = (Wide*)b.wide.p;
+    uint32_t* n_inner = (uint32_t*)((char*)b.wide.p + nn * sizeof(Wide));
+    hipLaunchKernelGGL(skel_init_kernel, dim3(1), dim3(NT), 0, st, n, n_inst, k, leaf_max, (const uint32_t*)T.list.p, (const uint32_t*)T.root.p, (const uint32_t*)T.top.p,
+                       (const uint2*)T.range.p, (const uint32_t*)T.pos.p, fr[0], (uint32_t*)T.inst_ref.p, hdr);
+    CollapseArgs ca;
+    ca.child = (const uint2*)T.child.p; ca.range = (const uint2*)T.range.p;
+    ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
+    ca.leaf_pos = (const uint32_t*)T.pos.p;
+    ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
+    ca.top = nullptr; // nothing under an instance root is a top node
+    ca.inst_stat = (uint32_t*)T.inst_stat.p;
+    const unsigned grid = (unsigned)std::min<size_t>(blocks_for(nn), 1024);
+    uint32_t level = 0, F = 1;
+    while (F > 0 && level < hjr::DEVICE_BVH_MAX_STACK) {
+        for (int q = 0; q < LEVEL_BATCH; q++, level++) {
+            hipLaunchKernelGGL(wide_expand_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Front*)fr[level & 1], wide, n_inner);
+            if (const int rc = scan(n_inner, hdr + H_F, 0u, (uint32_t*)b.part.p, hdr + H_NEXT, st, err)) return rc;
+            hipLaunchKernelGGL(wide_emit_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Wide*)wide, (const uint32_t*)n_inner, fr[(level + 1) & 1], (float4*)b.nodes.p);
+            hipLaunchKernelGGL(level_advance_kernel, dim3(1), dim3(1), 0, st, hdr);
+        }
+        DCHK(hipGetLastError());
+        DCHK(hipMemcpyAsync(&F, hdr + H_F, 4, hipMemcpyDeviceToHost, st));
+        DCHK(hipStreamSynchronize(st));
+    }
+    uint32_t S = 0;
+    DCHK(hipMemcpyAsync(&S, hdr + H_BASE, 4, hipMemcpyDeviceToHost, st));
+    DCHK(hipStreamSynchronize(st));
+    T.skel_deep = F > 0;
+    T.n_skel = S = std::min<uint32_t>(S, (uint32_t)nn);
+    if (!T.skel_refs.reserve(std::max<size_t>(1, (size_t)S * 16)) || !T.skel_parent.reserve(std::max<size_t>(1, (size_t)S * 4)) ||
+        !b.stage.reserve(std::max<size_t>(1, (size_t)S * HJR_NODE4_F4 * 16))) {
+        err = "device BVH: allocation or upload failed";
+        return HJR_ERR_DEVICE;
+    }
+    DCHK(hipMemsetAsync(T.skel_parent.p, 0xff, (size_t)S * 4, st));
+    if (S) hipLaunchKernelGGL(skel_keep_kernel, dim3(blocks_for(S)), dim3(NT), 0, st, S, (const float4*)b.nodes.p, (float4*)T.skel_refs.p, (uint32_t*)T.skel_parent.p, hdr);
+    DCHK(hipGetLastError());
+    return HJR_OK;
+}
+
+static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds, bool graft, const std::vector<uint32_t>& list,
+                          hipStream_t st, std::string& err)
 {
     DeviceBvh::Topology& T = b.topo;
     T.valid = false;
@@ -1563,19 +1960,31 @@ static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t le
     } else
         hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (uint32_t*)T.pos.p);
     DCHK(hipGetLastError());
-    DCHK(hipEventRecord(b.ev1, st));
     uint32_t h[H_WORDS];
+    const char* failed = "device BVH: the instance topology failed a structural bound (";
+    T.k = k;
+    T.graft = graft;
+    T.skel_deep = false;
+    T.n_skel = 0;
+    if (graft) { // the skeleton walks the BVH2: only one that passed its bounds
+        DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+        DCHK(hipStreamSynchronize(st));
+        if (h[H_ERR]) { err = failed + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
+        if (const int rc = build_skeleton(b, n, n_inst, leaf_max, restructure, st, err)) return rc;
+    }
+    DCHK(hipEventRecord(b.ev1, st));
     DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
     DCHK(hipStreamSynchronize(st));
     DCHK(hipEventElapsedTime(&T.ms, b.ev0, b.ev1));
-    if (h[H_ERR]) { err = "device BVH: the instance topology failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
-    T.k = k;
+    if (h[H_ERR]) { err = failed + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
+    if (graft) // a commit reads pos, order, list and the skeleton only
+        for (DevBuf* x : { &T.child, &T.range, &T.parent, &T.top, &T.top_ids, &T.root, &T.bounds }) x->release();
     T.valid = true;
     return HJR_OK;
 }
 
 int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
-                         uint32_t tag, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+                         uint32_t tag, bool graft, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
 {
     const uint32_t n = sc.n_triangles;
     std::vector<uint32_t> list; // the non-empty instances
@@ -1608,15 +2017,16 @@ int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, cons
         !b.frontier[0].reserve(nn * sizeof(Front)) || !b.frontier[1].reserve(nn * sizeof(Front)) || !b.wide.reserve(nn * (sizeof(Wide) + 4)))
         return fail_alloc();
     DeviceBvh::Topology& T = b.topo;
-    if (!T.valid || T.tag != tag || T.k != list.size()) {
+    if (!T.valid || T.tag != tag || T.k != list.size() || T.graft != graft) {
         if (!b.box.reserve(nn * 32) || !b.cent.reserve(nn * 16) || !b.keys[0].reserve(nn * 8) || !b.keys[1].reserve(nn * 8) || !b.vals[0].reserve(nn * 4) ||
             !b.vals[1].reserve(nn * 4) || !b.hist.reserve(std::max<size_t>(1, (size_t)nb * 256 * 4)) || !b.node_count.reserve(nn * 4) || !b.node_cost.reserve(nn * 4))
             return fail_alloc();
-        if (const int rc = build_topology(b, n, n_inst, leaf_max, opt_rounds, list, st, err)) return rc;
+        if (const int rc = build_topology(b, n, n_inst, leaf_max, opt_rounds, graft, list, st, err)) return rc;
         T.tag = tag;
     }
     const uint32_t k = T.k;
     uint32_t* hdr = (uint32_t*)b.hdr.p;
+    if (graft && T.skel_deep) return ordinary(); // an instance tree deeper than the traversal stack
     InstArgs a;
     a.f = FlattenArgs();
     a.f.vert = (const float*)b.vert.p; a.f.norm = (const float*)b.norm.p; a.f.uv = (const float*)b.uv.p; a.f.xf = (const float*)b.xf.p;
@@ -1626,6 +2036,47 @@ int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, cons
     a.order = (const uint32_t*)T.order.p; a.pos = (const uint32_t*)T.pos.p; a.top = (const uint32_t*)T.top.p; a.parent = (const uint32_t*)T.parent.p;
     a.child = (const uint2*)T.child.p; a.counter = (uint32_t*)b.counter.p;
     a.geom = (float4*)b.tri_geom.p; a.leaf_box = (float4*)b.leaf_box.p; a.inner_box = (float4*)b.inner_box.p;
+    if (graft) { // flatten, skeleton boxes, top tree, placement, cost: one host wait
+        const uint32_t S = T.n_skel;
+        a.order = (const uint32_t*)T.order.p; a.pos = (const uint32_t*)T.pos.p; a.top = nullptr; a.parent = nullptr; a.child = nullptr;
+        a.leaf_box = nullptr; a.inner_box = nullptr;
+        RefitArgs ra;
+        ra.f = a.f;
+        ra.n_nodes = S;
+        ra.cur_nodes = nullptr; ra.cur_geom = nullptr;
+        ra.nodes = (float4*)b.stage.p; ra.geom = (float4*)b.tri_geom.p;
+        ra.parent = (uint32_t*)T.skel_parent.p; ra.counter = (uint32_t*)b.counter.p;
+        GraftTopArgs ga;
+        ga.n = n; ga.k = k; ga.n_skel = S; ga.cap = (uint32_t)nn;
+        ga.inst_ref = (const uint32_t*)T.inst_ref.p; ga.inst_stat = (const uint32_t*)T.inst_stat.p;
+        ga.stage = (const float4*)b.stage.p; ga.geom = (const float4*)b.tri_geom.p;
+        ga.box = (float4*)T.top_box.p; ga.nodes = (float4*)b.nodes.p; ga.hdr = hdr;
+        DCHK(hipEventRecord(b.ev0, st));
+        hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
+        if (S) DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)S * 4, st));
+        hipLaunchKernelGGL(inst_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
+        if (S) hipLaunchKernelGGL(graft_boxes_kernel, dim3(blocks_for(S)), dim3(NT), 0, st, ra, (const float4*)T.skel_refs.p);
+        hipLaunchKernelGGL(graft_top_kernel, dim3(1), dim3(NT), 0, st, ga);
+        if (S) hipLaunchKernelGGL(graft_place_kernel, dim3(blocks_for((size_t)S * HJR_NODE4_F4)), dim3(NT), 0, st, S, (uint32_t)nn, (const float4*)b.stage.p,
+                                  (const uint32_t*)b.counter.p, (float4*)b.nodes.p, hdr);
+        launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, (uint32_t)nn, nullptr, st);
+        DCHK(hipGetLastError());
+        DCHK(hipEventRecord(b.ev1, st));
+        uint32_t h[H_WORDS];
+        DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+        DCHK(hipStreamSynchronize(st));
+        DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
+        const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
+        if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
+        if (h[H_ERR]) { err = "device BVH: the grafted instance tree failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
+        r.n_nodes = h[H_BASE];
+        r.sah = __builtin_bit_cast(float, h[H_SAH]);
+        r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
+        r.depth = h[H_DEPTH];
+        if (r.stack_need > hjr::DEVICE_BVH_MAX_STACK) return ordinary(); // a chain-shaped top tree (nested instances)
+        r.instances = k;
+        return HJR_OK;
+    }
     DCHK(hipEventRecord(b.ev0, st));
     hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
     if (n >= 2) DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
@@ -1645,7 +2096,7 @@ int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, cons
     ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
     ca.leaf_pos = (const uint32_t*)T.pos.p;
     ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
-    ca.top = (const uint32_t*)T.top.p;
+    ca.top = (const uint32_t*)T.top.p; ca.inst_stat = nullptr;
     const int rc = collapse_and_cost(b, ca, n, nn, st, r, "the instance tree", err);
     if (rc != HJR_OK && r.too_deep) return ordinary(); // a chain-shaped top tree (nested instances): the Morton tree over all triangles
     if (rc == HJR_OK) r.instances = k;

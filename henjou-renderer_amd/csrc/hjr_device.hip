@@ -175,7 +175,8 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
     }
     const uint32_t build_tag = (bo.allow_lds ? 1u : 0u) | (bo.prefer_stack16 ? 2u : 0u) | ((uint32_t)(bo.bvh_width + 1) << 2) | ((uint32_t)(bo.leaf_max + 1) << 6) | ((uint32_t)(bo.refine + 1) << 10) | (device ? 1u << 16 : 0u) |
                                (device ? (uint32_t)c->opt.get(hjr::OPT_DEVICE_BVH_OPT, 0) << 17 : 0u) |
-                               (device && c->opt.get(hjr::OPT_DEVICE_BVH_INSTANCES, 0) ? 1u << 19 : 0u);
+                               (device && c->opt.get(hjr::OPT_DEVICE_BVH_INSTANCES, 0) ? 1u << 19 : 0u) |
+                               (device && c->opt.get(hjr::OPT_DEVICE_BVH_INSTANCES, 0) && c->opt.get(hjr::OPT_DEVICE_BVH_GRAFT, 0) ? 1u << 20 : 0u);
     c->pending_valid = false;
     c->pending_same = false;
     // unchanged instance transforms (static geometry, e.g. a camera-only animation): the world-space arrays and the BVH of the
@@ -216,7 +217,8 @@ static int commit_device(hjr_ctx* c)
     const uint32_t n_inst = (uint32_t)(c->pending_m.size() / 12);
     hjr_ctx::Refit& rf = c->refit;
     // Option "device_bvh_instances" (the tag's bit 19): per-instance trees kept in dbvh.topo, a top tree per commit; no refits with it
-    const bool instances = (c->pending_build_tag >> 19) & 1u;
+    // Option "device_bvh_graft" (bit 20, only ever set with bit 19): the instances' BVH4s collapsed once, grafted under a BVH4 top tree
+    const bool instances = (c->pending_build_tag >> 19) & 1u, graft = (c->pending_build_tag >> 20) & 1u;
     if (!instances) c->dbvh.drop_topology();
     const bool refit = !instances && c->have_frame && rf.device && c->dbvh.have_scene && !rf.rebuild && rf.count < limit && rf.tag == c->pending_build_tag &&
                        c->last_m.size() == c->pending_m.size() && c->scene.n_triangles >= 2 && c->frame.n_tris == c->scene.n_triangles;
@@ -224,7 +226,7 @@ static int commit_device(hjr_ctx* c)
     std::string err;
     hjr::FrameData& f = c->pending;
     const int rc = instances ? hjr::device_bvh_instances(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds,
-                                                         c->pending_build_tag, f.lights.data(), f.lights.size(), c->stream, r, err)
+                                                         c->pending_build_tag, graft, f.lights.data(), f.lights.size(), c->stream, r, err)
                    : refit ? hjr::device_bvh_refit(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, c->d_nodes, c->d_tri_geom, c->frame.n_nodes,
                                                  f.lights.data(), f.lights.size(), c->stream, r, err)
                          : hjr::device_bvh_build(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds,
@@ -243,6 +245,7 @@ static int commit_device(hjr_ctx* c)
     }
     rf.sah = r.sah;
     c->pending_instances = r.instances;
+    c->pending_grafted = graft && r.instances > 0;
     c->pending_build_ms = r.build_ms;
     return HJR_OK;
 }
@@ -265,6 +268,7 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
         std::swap(c->frame, c->pending);
         c->refit = hjr_ctx::Refit(); // host-built data: nothing to refit
         c->pending_instances = 0;
+        c->pending_grafted = false;
         c->dbvh.drop_topology();
         const hjr::FrameData& f = c->frame;
         bool ok = c->d_nodes.upload(f.nodes.data(), f.nodes.size() * 4, c->stream) &&
@@ -290,7 +294,7 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
     if (c->opt.get(hjr::OPT_VERBOSE, 0))
         fprintf(stderr, "[hjr] BVH%u (lds_mode %d): %u nodes (%zu KB), %u triangles (%zu KB), stack %u entries/lane, %s %s %.1f ms\n", f.width, f.lds_mode, f.n_nodes,
                 (size_t)f.n_nodes * (f.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4) * 16 / 1024, f.n_tris, (size_t)std::max(f.n_tris, 1u) * HJR_TRI_F4 * 16 / 1024,
-                f.stack_need, c->pending_device ? "device" : "host", refitted ? "refit" : (c->pending_instances ? "instance build" : "build"), c->pending_build_ms);
+                f.stack_need, c->pending_device ? "device" : "host", refitted ? "refit" : (c->pending_instances ? (c->pending_grafted ? "grafted instance build" : "instance build") : "build"), c->pending_build_ms);
     c->stats.n_triangles = f.n_tris;
     return HJR_OK;
 }

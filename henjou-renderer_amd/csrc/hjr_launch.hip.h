@@ -47,6 +47,7 @@ struct hjr_ctx {
     bool pending_valid = false, pending_same = false;
     uint32_t pending_build_tag = 0;
     double pending_build_ms = 0.0;
+    bool pending_grafted = false;   // ... and they were grafted under a BVH4 top tree (option "device_bvh_graft")
     uint32_t pending_instances = 0; // option "device_bvh_instances": instance subtrees of the commit being made (0: an ordinary build)
     bool pending_device = false; // option "device_bvh": hjr_commit_transforms runs the build (pending.lights is the host-built light table)
     hjr::FrameData frame; // device-built frame data: the counts, format and lights only (the arrays live in d_nodes, d_tri_*)

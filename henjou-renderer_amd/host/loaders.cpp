@@ -158,6 +158,14 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 if (!o.device_bvh) throw JsonError("Henjou_HIP.device_bvh_instances needs \"device_bvh\": true");
                 if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x100;
             }
+            // device_bvh_graft: the instances' BVH4s collapsed once and grafted under a BVH4 top tree (option "device_bvh_graft"), bit 9 of
+            // the same field; it acts only on instance trees, so it is refused without them
+            if (const Json* v = h->find("device_bvh_graft")) {
+                const bool ok = v->is_bool() || (v->is_number() && (v->as_number() == 0.0 || v->as_number() == 1.0));
+                if (!ok) throw JsonError("Henjou_HIP.device_bvh_graft must be true, false, 0 or 1");
+                if (!(o.device_bvh_opt & 0x100)) throw JsonError("Henjou_HIP.device_bvh_graft needs \"device_bvh_instances\": true");
+                if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x200;
+            }
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
             if (const Json* v = h->find("passes")) {
                 const double n = v->is_number() ? v->as_number() : -1.0;

@@ -68,6 +68,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (opt.device_bvh > 1) (void)hjr_set_option(ctx, "device_bvh_refit", opt.device_bvh - 1); // key "device_bvh_refit": stored as 1 + N
     if (opt.device_bvh_opt & 0xff) (void)hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt & 0xff);
     if (opt.device_bvh_opt & 0x100) (void)hjr_set_option(ctx, "device_bvh_instances", 1); // key "device_bvh_instances": bit 8 of the field
+    if (opt.device_bvh_opt & 0x200) (void)hjr_set_option(ctx, "device_bvh_graft", 1); // key "device_bvh_graft": bit 9
     if (opt.denoise_variance && opt.render_mode != HJR_MODE_DEFAULT) (void)hjr_set_option(ctx, "denoise_variance", 1); // (Default mode has no filter)
     if (temporal) (void)hjr_set_option(ctx, "denoise_temporal", 1);
     const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes

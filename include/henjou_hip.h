@@ -141,7 +141,8 @@ typedef struct hjr_render_option {
     int32_t device_bvh;          /* default 0; 1: hjr_render_file / henjou_cli build the frame data on the device (option "device_bvh");
                                   * 1 + N: that and option "device_bvh_refit" N (key "device_bvh_refit": N; the struct does not grow for it) */
     int32_t device_bvh_opt;      /* default 0; low 8 bits: 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt");
-                                  * bit 8: key "device_bvh_instances" (option of the same name; the struct does not grow for it) */
+                                  * bit 8: key "device_bvh_instances", bit 9: key "device_bvh_graft" (options of the same names; the
+                                  * struct does not grow for them) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
     float noise_threshold;       /* default 0 (off); > 0: hjr_render_file / henjou_cli set hjr_adaptive.noise_threshold, render each frame in
@@ -479,6 +480,13 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  *                                 with it (hjr_stats.bvh_refits stays 0); hjr_stats.bvh_instances / bvh_topology_ms report it.  More than
  *                                 1024 non-empty instances, or a top tree deeper than the traversal stack, silently take the ordinary build
  *                                 (bvh_instances 0).  0 (default): the ordinary build.  The host build ignores it                    [*]
+ *   "device_bvh_graft" 0 1        with "device_bvh" 1 and "device_bvh_instances" 1: the BVH4 of every instance of more than "leaf_max"
+ *                                 triangles is collapsed once with the topology, from the object-space boxes, and kept instead of the
+ *                                 binary tree; every commit flattens, recomputes those nodes' boxes bottom-up, builds a BVH4 top tree over
+ *                                 the instances' world boxes and puts the instances' nodes behind it.  Same frames; the nodes differ from
+ *                                 those of "device_bvh_instances" alone.  The same fallbacks and the same hjr_stats fields
+ *                                 (bvh_topology_ms includes the one-off collapse).  Accepted and without effect when either of the two
+ *                                 other options is off.  0 (default)                                                                [*]
  *   "denoise_variance" 0 1        1: hjr_render_denoised renders the variance AOV along with the guides and runs the variance-guided filter
  *                                 (hjr_denoise_var_device) in the two Denoise modes; a sample pass filters the running mean with the variance
  *                                 over n = sample_end.  0 (default): today's call, bit for bit
@@ -498,6 +506,7 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * = 1 + N (the struct does not grow for it): hjr_render_file and henjou_cli set "device_bvh" 1 and "device_bvh_refit" N.
  * "device_bvh_instances": true (only together with "device_bvh": true) is stored as bit 8 of hjr_render_option.device_bvh_opt, whose low
  * 8 bits stay the treelet rounds: hjr_render_file and henjou_cli mask the field and set both options.
+ * "device_bvh_graft": true (only together with "device_bvh_instances": true) is bit 9 of the same field and sets the option of that name.
  * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name; "denoise_temporal": true
  * of that section is stored as hjr_render_option.denoise_variance = 2 and sets both options (refused together with "noise_threshold" > 0:
  * an adaptive frame that stops early never reaches the pass that advances the history).
