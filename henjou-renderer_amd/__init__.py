@@ -171,6 +171,13 @@ class TemporalFrame(_Sized):
                 ("variance", C.c_void_p), ("history", C.c_void_p)]
 
 
+class Shards(_Sized):
+    """hjr_shards: the gathered blocks of a multi-GPU frame as rank 0 holds them (hjr_assemble_shards / hjr_denoise_shards_device): rank r's
+    block of every AOV lies r * rank_stride bytes behind rank 0's; a null pointer is an absent AOV."""
+    _fields_ = [("struct_size", C.c_uint32), ("world_size", C.c_uint32), ("rank_stride", C.c_uint64), ("color", C.c_void_p),
+                ("albedo", C.c_void_p), ("normal", C.c_void_p), ("variance", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -239,6 +246,9 @@ def lib():
             "hjr_temporal_accumulate": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_reset": [C.c_void_p],
+            "hjr_assemble_shards": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_assemble_shards_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_denoise_shards_device": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
         }.items():
             fn = getattr(L, name)
             fn.restype = C.c_int
@@ -552,6 +562,24 @@ class Device:
         _check(lib().hjr_render_denoised(self._h, C.byref(params), mode, out.ctypes.data, ow, oh), "hjr_render_denoised")
         return out
 
+    def assemble_shards_device(self, shards, width, height, d_color=None, d_albedo=None, d_normal=None, d_variance=None, stream=None):
+        """hjr_assemble_shards_device: one launch scatters the gathered blocks of every rank and AOV of `shards` (a Shards of device
+        pointers) into row-major frames at the device pointers given (ints; None for an AOV the shards do not carry).  Asynchronous."""
+        _check(lib().hjr_assemble_shards_device(self._h, C.byref(shards), width, height, *[C.c_void_p(d) if d else None for d in (d_color, d_albedo, d_normal, d_variance)],
+                                                C.c_void_p(stream) if stream else None), "hjr_assemble_shards_device")
+
+    def denoise_shards(self, params, mode, shards, out_w=None, out_h=None):
+        """Rank 0's half of a multi-GPU frame in a Denoise mode (hjr_denoise_shards_device): `shards` (a Shards of device pointers) are
+        assembled and go through what render_denoised runs after its render, under the same context options; `params` describes the whole
+        frame at the render size.  Runs on the context's stream; returns AOV_Output as numpy."""
+        import torch
+        ow = out_w if out_w is not None else (2 * params.width if mode == MODE_DENOISE_UPSCALE2X else params.width)
+        oh = out_h if out_h is not None else (2 * params.height if mode == MODE_DENOISE_UPSCALE2X else params.height)
+        out = torch.empty((max(oh, 1), max(ow, 1), 4), dtype=torch.float32, device="cuda")
+        _check(lib().hjr_denoise_shards_device(self._h, C.byref(params), mode, C.byref(shards), C.c_void_p(out.data_ptr()), ow, oh, None), "hjr_denoise_shards_device")
+        self.synchronize()
+        return out[:oh, :ow].cpu().numpy()
+
     def gbuffer(self, params):
         """hjr_render_gbuffer: the first hit of every pixel's centre ray against the current frame data, GBUFFER_DTYPE [height, width]
         (width, height and camera of `params` are read)."""
@@ -730,6 +758,36 @@ def unpack_tiles(packed, frame, rank, world_size):
     assert frame.dtype == np.float32 and frame.flags["C_CONTIGUOUS"]
     _check(lib().hjr_unpack_tiles(packed.ctypes.data, w, h, rank, world_size, frame.ctypes.data), "hjr_unpack_tiles")
     return frame
+
+
+def shards_layout(width, height, world_size, guides=True, variance=True):
+    """The per-rank buffer of a Denoise-mode multi-GPU frame, colour | albedo | normal | variance, every AOV sized for rank 0 (which owns the
+    most tiles): ({aov name: byte offset}, bytes per rank = the rank_stride of the gathered buffer)."""
+    slots = owned_tiles(width, height, 0, world_size) * 64
+    names = ["color"] + (["albedo", "normal"] if guides else []) + (["variance"] if variance else [])
+    off, n = {}, 0
+    for k in names:
+        off[k] = n
+        n += slots * (4 if k == "variance" else 16)
+    return off, n
+
+
+def make_shards(base_ptr, world_size, rank_stride, offsets):
+    """Shards over one gathered buffer at address `base_ptr` (host or device), laid out per rank as shards_layout says."""
+    s = Shards()
+    s.world_size, s.rank_stride = world_size, rank_stride
+    for k, o in offsets.items():
+        setattr(s, k, base_ptr + o)
+    return s
+
+
+def assemble_shards(shards, width, height):
+    """Host form (hjr_assemble_shards; no GPU): scatters the blocks of every rank and AOV of `shards` (a Shards of host pointers) into
+    row-major frames; returns (color, albedo, normal [h, w, 4], variance [h, w]) with None for an AOV the shards do not carry."""
+    outs = [np.zeros((height, width, 4), dtype=np.float32) if getattr(shards, k) else None for k in ("color", "albedo", "normal")]
+    outs.append(np.zeros((height, width), dtype=np.float32) if shards.variance else None)
+    _check(lib().hjr_assemble_shards(C.byref(shards), width, height, *[None if o is None else o.ctypes.data for o in outs]), "hjr_assemble_shards")
+    return tuple(outs)
 
 
 def gather_tiles(packed, width, height, device=None, dst=0, frame=None):

@@ -8,6 +8,8 @@
 // all peers in parallel, 1 / N of the frame per rank; SURVEY.md §8e option b).  Rank 0 scatters the N blocks into the frame
 // (hjr_unpack_tiles_device), downloads it and writes <image_name>_<fff>.png exactly like the single-GPU path.  The assembled
 // frame is bit-identical to the 1-GPU frame: per-pixel sample order does not depend on which GPU owns the pixel.
+// Render_mode Denoise / DenoiseUpScale2X: the ranks render the guide AOVs (and the variance AOV) too, the gather moves them in the same one
+// collective, and rank 0 runs hjr_denoise_shards_device: assemble, temporal accumulation, filter, upscale (DESIGN.md §7 "Denoise modes").
 // The RCCL id travels over pipes the ranks inherit from the launcher (rank 0 -> launcher -> every other rank): no file, no name
 // another user of the machine could guess.  A rank does everything that can fail (config, scene, device context, uploads) BEFORE it
 // joins the communicator; the launcher reaps its children as they end, and the first one that fails or is signalled makes it
@@ -53,7 +55,24 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     hjr_render_option opt;
     HJR_INIT(opt);
     HJRX(hjr_load_render_option(json, &opt));
-    if (opt.render_mode != HJR_MODE_DEFAULT) { fprintf(stderr, "henjou_cli: the multi-GPU path renders Render_mode \"Default\" only\n"); return 1; }
+    if (opt.render_mode != HJR_MODE_DEFAULT && opt.render_mode != HJR_MODE_DENOISE && opt.render_mode != HJR_MODE_DENOISE_UPSCALE2X) {
+        fprintf(stderr, "henjou_cli: Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)\n");
+        return 1;
+    }
+    // Denoise modes (DESIGN.md §7 "Denoise modes"): every rank renders its tiles with the guide AOVs, and the variance AOV when the filter
+    // options ask for it, into ONE per-rank buffer colour | albedo | normal | variance; the frame's one gather moves that buffer, and rank 0
+    // assembles, accumulates and filters (hjr_denoise_shards_device).  The filter needs the whole frame, so it is not distributed.
+    const bool denoise = opt.render_mode != HJR_MODE_DEFAULT;
+    const bool with_var = denoise && opt.denoise_variance != 0;   // "denoise_variance" / "denoise_temporal" (stored as 2)
+    const bool temporal = denoise && opt.denoise_variance == 2;
+    if (temporal && opt.noise_threshold > 0.0f) {
+        fprintf(stderr, "henjou_cli: \"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history\n");
+        return 1;
+    }
+    // Image Scale Setting (renderer.h:1089-1099): DenoiseUpScale2X renders at half the output size, as hjr_render_file does
+    const uint32_t W = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_width / 2u : opt.image_width;
+    const uint32_t H = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_height / 2u : opt.image_height;
+    if (W == 0 || H == 0) { fprintf(stderr, "henjou_cli: image too small for DenoiseUpScale2X\n"); return 1; }
     hjr_scene* scene = nullptr;
     HJRX(hjr_scene_load_gltf(opt.gltf_path, opt.gltf_name, &opt, &scene));
     hjr_scene_view view;
@@ -67,10 +86,12 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     if (opt.device_bvh_opt & 0xff) HJRX(hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt & 0xff));
     if (opt.device_bvh_opt & 0x100) HJRX(hjr_set_option(ctx, "device_bvh_instances", 1)); // key "device_bvh_instances": bit 8 of the field
     if (opt.device_bvh_opt & 0x200) HJRX(hjr_set_option(ctx, "device_bvh_graft", 1)); // key "device_bvh_graft": bit 9
+    if (rank == 0 && with_var) HJRX(hjr_set_option(ctx, "denoise_variance", 1)); // rank 0 filters
+    if (rank == 0 && temporal) HJRX(hjr_set_option(ctx, "denoise_temporal", 1));
     HJRX(hjr_upload_scene(ctx, &view));
     // "noise_threshold": each rank stops its own converged tiles between the sample passes (the rule does not depend on the rank); the one
     // gather per frame is unchanged.  A rank without tiles has nothing to adapt.
-    const bool adaptive = opt.noise_threshold > 0.0f && hjr_owned_tiles(opt.image_width, opt.image_height, (uint32_t)rank, (uint32_t)world) > 0;
+    const bool adaptive = opt.noise_threshold > 0.0f && hjr_owned_tiles(W, H, (uint32_t)rank, (uint32_t)world) > 0;
     if (adaptive) {
         hjr_adaptive ad;
         HJR_INIT(ad);
@@ -99,16 +120,19 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     hipStream_t st;
     HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 
-    const uint32_t W = opt.image_width, H = opt.image_height;
-    const size_t block = (size_t)hjr_owned_tiles(W, H, 0, (uint32_t)world) * 64; // float4 per rank (rank 0 owns the most tiles; others pad)
+    const uint32_t OW = opt.image_width, OH = opt.image_height; // the PNG's size; W x H is the render size
+    const size_t block = (size_t)hjr_owned_tiles(W, H, 0, (uint32_t)world) * 64; // slots per rank and AOV (rank 0 owns the most tiles; others pad)
+    const size_t rank_floats = block * (denoise ? (with_var ? 13u : 12u) : 4u);  // the per-rank buffer: three float4 AOVs and one float, or the colour alone
     float *d_packed = nullptr, *d_all = nullptr, *d_frame = nullptr;
-    HIPX(hipMalloc(&d_packed, block * 16));
-    HIPX(hipMemset(d_packed, 0, block * 16));
+    HIPX(hipMalloc(&d_packed, rank_floats * 4));
+    HIPX(hipMemset(d_packed, 0, rank_floats * 4));
+    float *const d_albedo = denoise ? d_packed + block * 4 : nullptr, *const d_normal = denoise ? d_packed + block * 8 : nullptr;
+    float* const d_var = with_var ? d_packed + block * 12 : nullptr;
     std::vector<float> frame;
     if (rank == 0) {
-        HIPX(hipMalloc(&d_all, block * 16 * world));
-        HIPX(hipMalloc(&d_frame, (size_t)W * H * 16));
-        frame.resize((size_t)W * H * 4);
+        HIPX(hipMalloc(&d_all, rank_floats * 4 * world));
+        HIPX(hipMalloc(&d_frame, (size_t)OW * OH * 16));
+        frame.resize((size_t)OW * OH * 4);
     }
     std::vector<float> m((size_t)view.n_instances * 12), inv((size_t)view.n_instances * 12);
     for (uint32_t f = opt.start_frame; f < opt.end_frame; f++) {
@@ -131,7 +155,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
             const uint32_t end = k == n_pass ? p.spp : (g ? (uint32_t)((uint64_t)k * p.spp / n_pass) / g * g : 0u);
             if (end <= begin) continue;
             if (n_pass > 1) { p.sample_begin = begin; p.sample_end = end; }
-            HJRX(hjr_render_device(ctx, &p, d_packed, nullptr, nullptr, st));
+            HJRX(hjr_render_device_var(ctx, &p, d_packed, d_albedo, d_normal, d_var, st)); // (Default: the colour alone, hjr_render_device's launch)
             begin = end;
             n_done++;
             if (adaptive && p.sample_end && !(p.sample_begin == 0 && p.sample_end == p.spp)) { // (a frame of a single pass is a whole-frame render: not adaptive)
@@ -144,8 +168,18 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
                 if (as.active_tiles == 0) break;
             }
         }
-        NCCLX(ncclGather(d_packed, d_all, block * 4, ncclFloat, 0, comm, st)); // the one data-path collective of a frame
-        if (rank == 0) {
+        NCCLX(ncclGather(d_packed, d_all, rank_floats, ncclFloat, 0, comm, st)); // the one data-path collective of a frame
+        if (rank == 0 && denoise) { // the gathered blocks -> frames -> (temporal accumulation) -> filter -> (upscale), all on st
+            hjr_shards sh;
+            HJR_INIT(sh);
+            sh.world_size = (uint32_t)world; sh.rank_stride = rank_floats * 4;
+            sh.color = d_all; sh.albedo = d_all + block * 4; sh.normal = d_all + block * 8;
+            sh.variance = with_var ? d_all + block * 12 : nullptr;
+            hjr_params whole = p; // the gather follows the frame's last pass: rank 0 ends the frame (the history advances once per frame)
+            whole.sample_begin = whole.sample_end = 0;
+            HJRX(hjr_denoise_shards_device(ctx, &whole, opt.render_mode, &sh, d_frame, OW, OH, st));
+            HIPX(hipMemcpyAsync(frame.data(), d_frame, frame.size() * 4, hipMemcpyDeviceToHost, st));
+        } else if (rank == 0) {
             for (int r = 0; r < world; r++) HJRX(hjr_unpack_tiles_device(ctx, d_all + (size_t)r * block * 4, W, H, (uint32_t)r, (uint32_t)world, d_frame, st));
             HIPX(hipMemcpyAsync(frame.data(), d_frame, frame.size() * 4, hipMemcpyDeviceToHost, st));
         }
@@ -157,11 +191,11 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
             fprintf(stderr, "[henjou %d/%d] frame %u: kernel %.3f ms, render + gather + assemble %.3f ms%s\n", rank, world, f, s.last_kernel_ms, ms,
                     n_done > 1 ? (", " + std::to_string(n_done) + " sample passes").c_str() : "");
         if (rank == 0) {
-            std::vector<uint8_t> rgba8((size_t)W * H * 4);
-            HJRX(hjr_float4_to_srgb8(frame.data(), rgba8.data(), W * H));
+            std::vector<uint8_t> rgba8((size_t)OW * OH * 4);
+            HJRX(hjr_float4_to_srgb8(frame.data(), rgba8.data(), OW * OH));
             std::string n = std::to_string(f); // renderer.h:1291-1302
             while (n.size() < 3) n = "0" + n;
-            HJRX(hjr_write_png((std::string(opt.image_name) + "_" + n + ".png").c_str(), rgba8.data(), W, H, 1));
+            HJRX(hjr_write_png((std::string(opt.image_name) + "_" + n + ".png").c_str(), rgba8.data(), OW, OH, 1));
         }
     }
     ncclCommDestroy(comm);

@@ -966,17 +966,25 @@ extern "C" int hjr_render_device(hjr_ctx* c, const hjr_params* p_user, void* d_c
     return hjr_render_device_var(c, p_user, d_color, d_albedo, d_normal, nullptr, stream);
 }
 
+// the mode and size rules of every denoise entry point (include/henjou_hip.h: hjr_denoise)
+static int denoise_check_sizes(int render_mode, uint32_t in_w, uint32_t in_h, uint32_t out_w, uint32_t out_h)
+{
+    if (in_w == 0 || in_h == 0 || in_w > 16384 || in_h > 16384) { set_error("hjr_denoise: bad input size"); return HJR_ERR_ARG; }
+    const bool up = render_mode == HJR_MODE_DENOISE_UPSCALE2X;
+    if (render_mode != HJR_MODE_DEFAULT && render_mode != HJR_MODE_DENOISE && !up) { set_error("hjr_denoise: unknown render mode"); return HJR_ERR_ARG; }
+    if (!up && (out_w != in_w || out_h != in_h)) { set_error("hjr_denoise: output size must equal the input size in this mode"); return HJR_ERR_ARG; }
+    if (up && (out_w / 2u != in_w || out_h / 2u != in_h)) { set_error("hjr_denoise: DenoiseUpScale2X renders at (out_w / 2, out_h / 2)"); return HJR_ERR_ARG; }
+    return HJR_OK;
+}
+
 // OptixDenoiserManager::denoise() replacement (csrc/hjr_denoise.hip.h), device buffers, asynchronous on `hip_stream`
 // `with_var`: the variance-guided variant (hjr_denoise_var_device), which also needs d_variance in the two Denoise modes
 static int denoise_device_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
                                const void* d_normal, bool with_var, const void* d_variance, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream)
 {
     if (!c || !d_color || !d_out) { set_error("hjr_denoise: null argument"); return HJR_ERR_ARG; }
-    if (in_w == 0 || in_h == 0 || in_w > 16384 || in_h > 16384) { set_error("hjr_denoise: bad input size"); return HJR_ERR_ARG; }
+    if (const int rc = denoise_check_sizes(render_mode, in_w, in_h, out_w, out_h)) return rc;
     const bool up = render_mode == HJR_MODE_DENOISE_UPSCALE2X;
-    if (render_mode != HJR_MODE_DEFAULT && render_mode != HJR_MODE_DENOISE && !up) { set_error("hjr_denoise: unknown render mode"); return HJR_ERR_ARG; }
-    if (!up && (out_w != in_w || out_h != in_h)) { set_error("hjr_denoise: output size must equal the input size in this mode"); return HJR_ERR_ARG; }
-    if (up && (out_w / 2u != in_w || out_h / 2u != in_h)) { set_error("hjr_denoise: DenoiseUpScale2X renders at (out_w / 2, out_h / 2)"); return HJR_ERR_ARG; }
     if (render_mode != HJR_MODE_DEFAULT && (!d_albedo || !d_normal)) { set_error("hjr_denoise: the albedo and normal guide AOVs are required"); return HJR_ERR_ARG; }
     if (render_mode != HJR_MODE_DEFAULT && with_var && !d_variance) { set_error("hjr_denoise_var: the variance AOV is required"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
@@ -1202,23 +1210,32 @@ extern "C" int hjr_temporal_reset(hjr_ctx* c)
     return HJR_OK;
 }
 
-// Option "denoise_temporal", between the render and the filter of hjr_render_denoised, all on the context's stream: G-buffer of this frame,
+// Option "denoise_temporal", between the render (or the assembly of gathered shards) and the filter, all on `st`: G-buffer of this frame,
 // a device copy of the transforms the current frame data was built from (last_m / last_inv: what hjr_commit_transforms made current, so a
 // frame loop that already prepares the next frame on another thread cannot be seen here), accumulation against the previous slot.
 // `commit`: this call ends the frame (a whole-frame render, or the sample pass that ends at spp): the slots rotate.
-static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var)
+// the current slot's buffers (no enqueue: hjr_denoise_shards_device calls it ahead of its first launch, temporal_stage again to no effect)
+static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
+{
+    hjr_ctx::Temporal& t = c->tmp;
+    const size_t npx = (size_t)p->width * p->height, nx = c->last_m.size() * 4;
+    const int k = t.cur;
+    if (!t.color[k].reserve(npx * 16) || !t.variance[k].reserve(npx * 4) || !t.history[k].reserve(npx * 4) || !t.gbuf[k].reserve(npx * sizeof(hjr_gbuffer_px)) ||
+        !t.xf[k].reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
+    return HJR_OK;
+}
+static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
 {
     hjr_ctx::Temporal& t = c->tmp;
     const uint32_t n_inst = (uint32_t)(c->last_m.size() / 12);
     if (t.have_prev && (t.width != p->width || t.height != p->height || t.mode != render_mode || t.n_instances != n_inst)) t.have_prev = false;
-    const size_t npx = (size_t)p->width * p->height, nx = (size_t)n_inst * 48;
+    const size_t nx = (size_t)n_inst * 48;
     const int k = t.cur;
-    if (!t.color[k].reserve(npx * 16) || !t.variance[k].reserve(npx * 4) || !t.history[k].reserve(npx * 4) || !t.gbuf[k].reserve(npx * sizeof(hjr_gbuffer_px)) ||
-        !t.xf[k].reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
-    if (const int rc = gbuffer_device_impl(c, p, t.gbuf[k].p, c->stream)) return rc;
+    if (const int rc = temporal_reserve(c, p)) return rc;
+    if (const int rc = gbuffer_device_impl(c, p, t.gbuf[k].p, st)) return rc;
     if (nx) {
-        HIPCHK(hipMemcpyAsync(t.xf[k].p, c->last_m.data(), nx, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync((char*)t.xf[k].p + nx, c->last_inv.data(), nx, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(t.xf[k].p, c->last_m.data(), nx, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((char*)t.xf[k].p + nx, c->last_inv.data(), nx, hipMemcpyHostToDevice, st));
     }
     t.cam[k] = p->camera;
     TemporalSide s[2];
@@ -1228,10 +1245,24 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
         s[i].color = (const float4*)t.color[q].p; s[i].variance = (const float*)t.variance[q].p; s[i].history = (const float*)t.history[q].p;
     }
     s[1].color = (const float4*)d_color; s[1].variance = (const float*)d_var; s[1].history = nullptr;
-    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, c->stream)) return rc;
+    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, st)) return rc;
     d_color = t.color[k].p; d_var = t.variance[k].p;
     if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur = k ^ 1; }
     return HJR_OK;
+}
+
+// What a frame in a render mode runs once its AOVs stand in the context's d_color / d_albedo / d_normal (/ d_variance), whether a render left
+// them there (hjr_render_denoised) or the assembly of gathered shards (hjr_denoise_shards_device): the temporal stage if the option is on
+// (`commit`: this call ends the frame), then the filter, plain or variance-guided, and the upscale of DenoiseUpScale2X.  All on `st`.
+static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool temporal, bool with_var, bool commit, void* d_out, uint32_t out_w, uint32_t out_h,
+                              hipStream_t st)
+{
+    const bool guides = render_mode != HJR_MODE_DEFAULT;
+    const void *f_color = c->d_color.p, *f_var = with_var ? c->d_variance.p : nullptr; // what the filter reads
+    if (temporal)
+        if (const int rc = temporal_stage(c, p, render_mode, commit, f_color, f_var, st)) return rc;
+    return denoise_device_impl(c, render_mode, p->width, p->height, f_color, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var, f_var, d_out,
+                               out_w, out_h, st);
 }
 
 // One frame of Renderer's loop in a Denoise mode, on the device: optixLaunch -> denoise -> cpyGPUBufferToHost(AOV_Output)
@@ -1263,14 +1294,78 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     if (guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
     int rc = render_impl(c, p, pr, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var ? c->d_variance.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
-    const void *f_color = c->d_color.p, *f_var = with_var ? c->d_variance.p : nullptr; // what the filter reads
-    if (temporal && (rc = temporal_stage(c, p, render_mode, !pr.pass || pr.end == p->spp, f_color, f_var)) != HJR_OK) return rc;
-    rc = denoise_device_impl(c, render_mode, p->width, p->height, f_color, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr,
-                             with_var, f_var, c->d_dn_out.p, out_w, out_h, c->stream);
+    rc = denoise_post_stage(c, p, render_mode, temporal, with_var, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
     if (rc != HJR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return HJR_OK;
+}
+
+// ---- gathered shards of a multi-GPU frame (include/henjou_hip.h; kernel: csrc/hjr_aux.hip.h)
+static int assemble_launch(const hjr_shards& s, uint32_t w, uint32_t h, void* d_color, void* d_albedo, void* d_normal, void* d_variance, hipStream_t st)
+{
+    ShardArgs a;
+    memset(&a, 0, sizeof(a));
+    a.color = (const char*)s.color; a.albedo = (const char*)s.albedo; a.normal = (const char*)s.normal; a.variance = (const char*)s.variance;
+    a.out_color = (float4*)d_color; a.out_albedo = (float4*)d_albedo; a.out_normal = (float4*)d_normal; a.out_variance = (float*)d_variance;
+    a.rank_stride = s.rank_stride; a.width = w; a.height = h; a.world = s.world_size;
+    a.tiles_x = (w + HJR_TILE - 1) / HJR_TILE;
+    hipLaunchKernelGGL(hjr_assemble_shards_kernel, dim3((a.tiles_x + 3u) / 4u, (h + HJR_TILE - 1) / HJR_TILE), dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+extern "C" int hjr_assemble_shards_device(hjr_ctx* c, const hjr_shards* shards, uint32_t w, uint32_t h, void* d_color, void* d_albedo, void* d_normal, void* d_variance,
+                                          void* hip_stream)
+{
+    if (!c) { set_error("hjr_assemble_shards_device: null context"); return HJR_ERR_ARG; }
+    hjr_shards s;
+    const void* const out[4] = { d_color, d_albedo, d_normal, d_variance };
+    if (!hjr::abi_take(shards, s, "hjr_assemble_shards_device")) return HJR_ERR_ARG;
+    if (const int rc = hjr::check_shards(s, w, h, out, "hjr_assemble_shards_device")) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return assemble_launch(s, w, h, d_color, d_albedo, d_normal, d_variance, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+// Rank 0's half of a multi-GPU frame in a Denoise mode: the gathered blocks -> the context's AOV buffers -> the post stage of hjr_render_denoised.
+// Every argument and state check comes before the first enqueue.
+extern "C" int hjr_denoise_shards_device(hjr_ctx* c, const hjr_params* p_user, int render_mode, const hjr_shards* gathered, void* d_out, uint32_t out_w, uint32_t out_h,
+                                         void* hip_stream)
+{
+    hjr_params params; // sized struct
+    if (!c || !hjr::abi_take(p_user, params, "hjr_denoise_shards_device")) { if (!c) set_error("hjr_denoise_shards_device: null context"); return HJR_ERR_ARG; }
+    if (!d_out) { set_error("hjr_denoise_shards_device: null argument"); return HJR_ERR_ARG; }
+    if (render_mode == HJR_MODE_DEFAULT) { set_error("hjr_denoise_shards_device: Render_mode Default has no filter (hjr_assemble_shards_device assembles the frame)"); return HJR_ERR_ARG; }
+    params.rank = 0; params.world_size = 1; params.flags &= ~HJR_FLAG_PACKED; // `frame` describes the whole frame; gathered->world_size is how it was rendered
+    const hjr_params* p = &params;
+    if (const int rc = denoise_check_sizes(render_mode, p->width, p->height, out_w, out_h)) return rc;
+    const bool whole = p->sample_end == 0 || (p->sample_begin == 0 && p->sample_end == p->spp);
+    if (!whole && (p->sample_begin >= p->sample_end || p->sample_end > p->spp)) { set_error("hjr_denoise_shards_device: bad sample range"); return HJR_ERR_ARG; }
+    const bool temporal = c->opt.get(hjr::OPT_DENOISE_TEMPORAL, 0) != 0;
+    const bool with_var = temporal || c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0;
+    HIPCHK(hipSetDevice(c->device));
+    hjr_shards s; // sized struct
+    if (!hjr::abi_take(gathered, s, "hjr_denoise_shards_device")) return HJR_ERR_ARG;
+    if (!s.color || !s.albedo || !s.normal) { set_error("hjr_denoise_shards_device: the colour, albedo and normal blocks are required"); return HJR_ERR_ARG; }
+    if (with_var && !s.variance) { set_error("hjr_denoise_shards_device: options \"denoise_variance\" / \"denoise_temporal\" need the variance block"); return HJR_ERR_ARG; }
+    if (!with_var) s.variance = nullptr; // a block the filter does not read stays where it is
+    const size_t in_bytes = (size_t)p->width * p->height * 16;
+    if (!c->d_color.reserve(in_bytes) || !c->d_albedo.reserve(in_bytes) || !c->d_normal.reserve(in_bytes) || (with_var && !c->d_variance.reserve(in_bytes / 4))) {
+        set_error("hjr_denoise_shards_device: allocation failed");
+        return HJR_ERR_DEVICE;
+    }
+    const void* const out[4] = { c->d_color.p, c->d_albedo.p, c->d_normal.p, with_var ? c->d_variance.p : nullptr };
+    if (const int rc = hjr::check_shards(s, p->width, p->height, out, "hjr_denoise_shards_device")) return rc;
+    if (temporal) { // gbuffer_device_impl's checks, ahead of the assembly
+        if (!c->have_scene || !c->have_frame) { set_error("hjr_denoise_shards_device: option \"denoise_temporal\" needs the frame data of this frame (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
+        if (p->width > 8192 || p->height > 8192) { set_error("hjr_denoise_shards_device: option \"denoise_temporal\" does not take frames larger than 8192 x 8192"); return HJR_ERR_ARG; }
+        if (const int rc = temporal_reserve(c, p)) return rc;
+    }
+    if (!c->d_dn_a.reserve(in_bytes) || !c->d_dn_b.reserve(in_bytes) || (with_var && (!c->d_dnv_a.reserve(in_bytes / 4) || !c->d_dnv_b.reserve(in_bytes / 4)))) {
+        set_error("hjr_denoise_shards_device: allocation failed"); // (the filter's ping-pong buffers: nothing may fail behind the first launch)
+        return HJR_ERR_DEVICE;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (const int rc = assemble_launch(s, p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, with_var ? c->d_variance.p : nullptr, st)) return rc;
+    return denoise_post_stage(c, p, render_mode, temporal, with_var, whole || p->sample_end == p->spp, d_out, out_w, out_h, st);
 }
 
 // Round-trips every child ref the builder can emit for a tree that host/frame.cpp admits to the 16-bit-stack layout

@@ -9,8 +9,12 @@
 #include <cstring>
 #include <string>
 
+struct hjr_shards; // include/henjou_hip.h
 namespace hjr {
 void set_error(const std::string& s);
+// the argument rule of hjr_assemble_shards, hjr_assemble_shards_device and hjr_denoise_shards_device in one place (host/capi.cpp): sizes,
+// alignment, and per AOV "source block and output both or neither"; `s` has been through abi_take
+int check_shards(const hjr_shards& s, uint32_t w, uint32_t h, const void* const out[4], const char* who);
 
 inline bool abi_size(const void* user, uint32_t& n, const char* who)
 {

@@ -197,6 +197,51 @@ template <bool PACK> static int tiles_copy(const float* src, float* dst, uint32_
 extern "C" int hjr_pack_tiles(const float* frame, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, float* packed) { return tiles_copy<true>(frame, packed, w, h, rank, world); }
 extern "C" int hjr_unpack_tiles(const float* packed, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, float* frame) { return tiles_copy<false>(packed, frame, w, h, rank, world); }
 
+// ---- gathered shards -> frames (include/henjou_hip.h, DESIGN.md §7 "Denoise modes").  The argument rule of hjr_assemble_shards and
+// hjr_assemble_shards_device (csrc/hjr_device.hip) in one place: sizes, alignment, and per AOV "source and output both or neither".
+namespace hjr {
+int check_shards(const hjr_shards& s, uint32_t w, uint32_t h, const void* const out[4], const char* who)
+{
+    const std::string me = who;
+    if (w == 0 || h == 0 || w > 16384 || h > 16384) { set_error(me + ": bad image size"); return HJR_ERR_ARG; }
+    if (s.world_size == 0) { set_error(me + ": world_size is 0"); return HJR_ERR_ARG; }
+    const void* const src[4] = { s.color, s.albedo, s.normal, s.variance };
+    bool any = false;
+    for (int k = 0; k < 4; k++) {
+        if ((src[k] != nullptr) != (out[k] != nullptr)) { set_error(me + ": an output needs its source block and a source block its output (both NULL or neither)"); return HJR_ERR_ARG; }
+        if (k < 3 && src[k] && (((uintptr_t)src[k] | (uintptr_t)out[k]) & 15u)) { set_error(me + ": float4 blocks and frames must be 16-byte aligned"); return HJR_ERR_ARG; }
+        if (k == 3 && src[k] && (((uintptr_t)src[k] | (uintptr_t)out[k]) & 3u)) { set_error(me + ": the variance block and frame must be 4-byte aligned"); return HJR_ERR_ARG; }
+        any = any || src[k];
+    }
+    if (!any) { set_error(me + ": no AOV given"); return HJR_ERR_ARG; }
+    if (s.rank_stride % 16u) { set_error(me + ": rank_stride must be a multiple of 16"); return HJR_ERR_ARG; }
+    // blocks of two ranks must not overlap: rank 0 owns the most tiles
+    const uint64_t need = (uint64_t)hjr_owned_tiles(w, h, 0, s.world_size) * 64u * ((s.color || s.albedo || s.normal) ? 16u : 4u);
+    if (s.world_size > 1 && s.rank_stride < need) { set_error(me + ": rank_stride is smaller than rank 0's block"); return HJR_ERR_ARG; }
+    return HJR_OK;
+}
+} // namespace hjr
+// host form: per pixel the arithmetic of csrc/hjr_aux.hip.h::hjr_assemble_shards_kernel (tile id -> owner and slot; no table of owners)
+extern "C" int hjr_assemble_shards(const hjr_shards* shards, uint32_t w, uint32_t h, float* color, float* albedo, float* normal, float* variance)
+{
+    hjr_shards s;
+    const void* const out[4] = { color, albedo, normal, variance };
+    if (!hjr::abi_take(shards, s, "hjr_assemble_shards")) return HJR_ERR_ARG;
+    if (const int rc = hjr::check_shards(s, w, h, out, "hjr_assemble_shards")) return rc;
+    const uint32_t tiles_x = (w + 7u) / 8u;
+    const char* const src4[3] = { (const char*)s.color, (const char*)s.albedo, (const char*)s.normal };
+    float* const dst4[3] = { color, albedo, normal };
+    for (uint32_t y = 0; y < h; y++)
+        for (uint32_t x = 0; x < w; x++) {
+            const uint32_t t = hjr_tile_id(x / 8u, y / 8u, tiles_x);
+            const size_t off = (size_t)(t % s.world_size) * s.rank_stride, slot = (size_t)(t / s.world_size) * 64u + (y & 7u) * 8u + (x & 7u), pix = (size_t)y * w + x;
+            for (int k = 0; k < 3; k++)
+                if (dst4[k]) memcpy(dst4[k] + pix * 4, src4[k] + off + slot * 16, 16);
+            if (variance) memcpy(variance + pix, (const char*)s.variance + off + slot * 4, 4);
+        }
+    return HJR_OK;
+}
+
 extern "C" int hjr_float4_to_srgb8(const float* rgba, uint8_t* out, uint32_t n)
 {
     if ((!rgba || !out) && n) { set_error("hjr_float4_to_srgb8: null argument"); return HJR_ERR_ARG; }

@@ -29,7 +29,7 @@ extern "C" {
 #define HJR_ERR_STATE (-5)   /* call order violated (render before upload, ...) */
 
 /* ---- Sized structs (the rule that keeps callers and library binary-compatible across releases) --------------------------------
- * hjr_scene_view, hjr_render_option, hjr_params, hjr_stats, hjr_adaptive and hjr_adaptive_state may GROW at their end in later releases.  Each starts with
+ * hjr_scene_view, hjr_render_option, hjr_params, hjr_stats, hjr_adaptive, hjr_adaptive_state and hjr_shards may GROW at their end in later releases.  Each starts with
  * `struct_size`: the CALLER sets it to sizeof(its own struct) before handing the struct to ANY entry point, input or output
  * (HJR_INIT does it together with the zero fill).  The library copies min(struct_size, its own sizeof) bytes in either direction:
  *   - a field the caller's (older, shorter) struct does not have is never written and reads as 0, which selects the default;
@@ -367,6 +367,29 @@ int hjr_unpack_tiles(const float* packed_rgba, uint32_t width, uint32_t height, 
 /* the same on device pointers, asynchronous on `hip_stream` (NULL = the context's stream) */
 int hjr_pack_tiles_device(hjr_ctx*, const void* d_frame, uint32_t width, uint32_t height, uint32_t rank, uint32_t world_size, void* d_packed, void* hip_stream);
 int hjr_unpack_tiles_device(hjr_ctx*, const void* d_packed, uint32_t width, uint32_t height, uint32_t rank, uint32_t world_size, void* d_frame, void* hip_stream);
+/* ---- gathered shards -> frames (DESIGN.md §7 "Denoise modes").  What rank 0 holds after the one gather of a frame: world_size blocks, one per
+ * rank, rank r's at byte offset r * rank_stride from each of up to four base pointers (rank 0's packed AOVs): colour, albedo and normal as
+ * [owned tile][64] float4, the variance AOV as [owned tile][64] float; NULL = absent.  One gather of a per-rank buffer laid out
+ * colour | albedo | normal | variance yields exactly this: the pointers are offsets into rank 0's block and rank_stride is the size of the
+ * per-rank buffer.  rank_stride is a multiple of 16, and with world_size > 1 at least the size of rank 0's largest block (float4 AOVs:
+ * hjr_owned_tiles(w, h, 0, world_size) * 1024 bytes); the float4 pointers are 16-byte aligned.  Only slots of pixels inside the image are
+ * read: neither the out-of-image lanes of an edge tile nor the padding behind a rank's last tile.
+ * hjr_assemble_shards scatters every block of every AOV into row-major frames (the inverse of the packed layout for all ranks at once);
+ * every pixel of every requested output is written exactly once.  An output whose source is NULL must be NULL and the reverse, and at
+ * least one AOV must be given, else HJR_ERR_ARG.  Host form: host pointers, needs no context and no GPU.  Device form: device pointers,
+ * one kernel launch, asynchronous on `hip_stream` (NULL = the context's stream). */
+typedef struct hjr_shards {
+    uint32_t struct_size;        /* sizeof(hjr_shards) of the caller (HJR_INIT) */
+    uint32_t world_size;         /* N the blocks were rendered with */
+    uint64_t rank_stride;        /* bytes from rank r's block to rank r + 1's; the same for all four pointers; a multiple of 16 */
+    const void* color;           /* rank 0's packed colour tiles, [owned tile][64] float4; must not be NULL for hjr_denoise_shards_device */
+    const void* albedo;          /* NULL = absent */
+    const void* normal;
+    const void* variance;        /* [owned tile][64] float */
+} hjr_shards;
+int hjr_assemble_shards(const hjr_shards*, uint32_t width, uint32_t height, float* color, float* albedo, float* normal, float* variance);
+int hjr_assemble_shards_device(hjr_ctx*, const hjr_shards*, uint32_t width, uint32_t height, void* d_color, void* d_albedo, void* d_normal,
+                               void* d_variance, void* hip_stream);
 /* OptixDenoiserManager::layerSet + denoise() — renderer/denoiser.h:42-189, renderer/renderer.h:1093-1120, 1258-1270:
  * (aov_color | guide albedo | guide normal) of in_w x in_h -> AOV_Output of out_w x out_h.  The OptiX AI network is closed, so
  * this is a REPLACEMENT with the same data flow, not a reproduction of its pixels: HJR_MODE_DEFAULT copies
@@ -378,6 +401,19 @@ int hjr_denoise(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const f
  * DenoiseUpScale2X, renderer.h:1096-1099), hjr_denoise_device (option "denoise_variance" 1: the variance AOV too and
  * hjr_denoise_var_device), download of AOV_Output only (renderer.h:1229-1281).  Synchronous. */
 int hjr_render_denoised(hjr_ctx*, const hjr_params*, int render_mode, float* out, uint32_t out_w, uint32_t out_h);
+/* The same frame from the gathered shards of a multi-GPU render instead of from a render (rank 0 of henjou_cli's multi-GPU path):
+ * hjr_assemble_shards_device into the context's AOV buffers, then exactly what hjr_render_denoised runs after its render, under the same
+ * context options: with "denoise_temporal" the G-buffer pass (of the context's current frame data: rank 0 has set the frame's transforms),
+ * the accumulation against the context's history and its commit (a whole frame, or the pass that ends at spp); then the filter, plain or
+ * variance-guided, and in DenoiseUpScale2X the upscale.  The output has the bits of hjr_render_denoised: shards only move data.
+ * `frame` describes the WHOLE frame: width x height (the render size), camera, spp, sample_begin / sample_end (which pass of the frame the
+ * shards hold; 0 / 0 = the whole frame); its rank, world_size and HJR_FLAG_PACKED are ignored, gathered->world_size says how the blocks were
+ * made.  Device pointers; every stage is asynchronous on `hip_stream` (NULL = the context's stream); d_out is out_w x out_h float4.
+ * HJR_ERR_ARG: HJR_MODE_DEFAULT (nothing to filter: hjr_assemble_shards_device is the whole job) or an unknown mode, a missing colour, albedo
+ * or normal block, a variance block the options need ("denoise_variance" / "denoise_temporal") and the shards lack, bad sizes or sample range.
+ * HJR_ERR_STATE: "denoise_temporal" without current frame data.  In every error case nothing is enqueued.  No reference counterpart. */
+int hjr_denoise_shards_device(hjr_ctx*, const hjr_params* frame, int render_mode, const hjr_shards* gathered, void* d_out, uint32_t out_w,
+                              uint32_t out_h, void* hip_stream);
 /* the same on device pointers (float4 images), asynchronous on `hip_stream` (NULL = the context's stream) */
 int hjr_denoise_device(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
                        const void* d_normal, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream);
@@ -496,8 +532,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  history at the render size.  A whole-frame render, or the sample pass that ends at spp, makes the current
                                  frame the previous one; an earlier sample pass reads the history and does not advance it.  The caller
                                  advances hjr_params.frame between frames: the same frame number twice blends identical samples and the
-                                 propagated variance then understates.  world_size > 1 or HJR_FLAG_PACKED is HJR_ERR_ARG with it;
-                                 HJR_MODE_DEFAULT ignores it.  Setting it (any value) drops the history.  0 (default): today's call, bit for bit
+                                 propagated variance then understates.  world_size > 1 or HJR_FLAG_PACKED is HJR_ERR_ARG with it (a sharded
+                                 frame goes through hjr_denoise_shards_device, which honours both options); HJR_MODE_DEFAULT ignores it.  Setting it (any value) drops the history.  0 (default): today's call, bit for bit
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
