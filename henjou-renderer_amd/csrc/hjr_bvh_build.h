@@ -10,6 +10,7 @@
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    template <class T> T* as() const { return static_cast<T*>(p); }
     // grow without copying to exactly `bytes` (the old contents are lost); *grown tells whether the buffer was reallocated
     bool reserve(size_t bytes, bool* grown = nullptr)
     {

@@ -142,11 +142,17 @@ struct FlattenArgs {
     uint32_t *inst, *hdr;
 };
 
+// the instance of triangle t: the last prim_offset <= t (prim_offset[0] == 0)
+__device__ __forceinline__ uint32_t instance_of(const FlattenArgs& a, uint32_t t)
+{
+    uint32_t lo = 0, hi = a.n_inst;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.prim_off[mid] <= t) lo = mid; else hi = mid; }
+    return lo;
+}
 // triangle t under its instance's transform: world vertices v[9], shading record s[16]; returns the instance
 __device__ __forceinline__ uint32_t flatten_tri(const FlattenArgs& a, uint32_t t, float* v, float* s)
 {
-    uint32_t lo = 0, hi = a.n_inst; // last prim_offset <= t (prim_offset[0] == 0)
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.prim_off[mid] <= t) lo = mid; else hi = mid; }
+    const uint32_t lo = instance_of(a, t);
     const float* m = a.xf + 24 * (size_t)lo;
     const float* mi = m + 12;
     float uv[6];
@@ -164,6 +170,20 @@ __device__ __forceinline__ uint32_t flatten_tri(const FlattenArgs& a, uint32_t t
     s[15] = __uint_as_float(a.mat[t]);
     return lo;
 }
+__device__ __forceinline__ void store_shade(float* shade, uint32_t t, const float* s)
+{
+    float4* sd = reinterpret_cast<float4*>(shade) + 4 * (size_t)t;
+    for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+}
+// a tri_geom row (frame.cpp:652-660): the world vertices v[9] of triangle t
+__device__ __forceinline__ void store_geom_row(float4* g, const float* v, uint32_t t, uint32_t mat)
+{
+    g[0] = make_float4(v[0], v[1], v[2], v[3]);
+    g[1] = make_float4(v[4], v[5], v[6], v[7]);
+    g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(mat), 0.0f);
+}
+// the padding of every leaf box (frame.cpp:603-609) from the finished maximum |coordinate|
+__device__ __forceinline__ float frame_pad(const uint32_t* hdr) { return __uint_as_float(hdr[H_SMAX]) * (1.0f / 8192.0f); }
 // unpadded box of the triangle; returns its max |coordinate|
 __device__ __forceinline__ float tri_box(const float* v, float* bl, float* bh)
 {
@@ -185,8 +205,7 @@ __global__ void __launch_bounds__(NT) flatten_kernel(FlattenArgs a)
     if (t < a.n) {
         float v[9], s[16];
         const uint32_t lo = flatten_tri(a, t, v, s);
-        float4* sd = reinterpret_cast<float4*>(a.shade) + 4 * (size_t)t;
-        for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+        store_shade(a.shade, t, s);
         for (int k = 0; k < 9; k++) a.wv[9 * (size_t)t + k] = v[k];
         a.inst[t] = lo;
         float bl[3], bh[3], c[3];
@@ -226,7 +245,7 @@ __global__ void __launch_bounds__(NT) morton_kernel(uint32_t n, float* box, cons
 {
     const uint32_t t = blockIdx.x * NT + threadIdx.x;
     if (t >= n) return;
-    const float pad = __uint_as_float(hdr[H_SMAX]) * (1.0f / 8192.0f);
+    const float pad = frame_pad(hdr);
     float4* b = reinterpret_cast<float4*>(box) + 2 * (size_t)t;
     float4 lo = b[0], hi = b[1];
     lo.x -= pad; lo.y -= pad; lo.z -= pad;
@@ -307,13 +326,7 @@ __global__ void __launch_bounds__(NT) gather_kernel(uint32_t n, const uint32_t* 
     if (k >= n) return;
     const uint32_t t = order[k];
     const uint32_t d = pos ? pos[k] : k;
-    if (tri_geom && d < n) {
-        const float* v = wv + 9 * (size_t)t;
-        float4* g = reinterpret_cast<float4*>(tri_geom) + 3 * (size_t)d;
-        g[0] = make_float4(v[0], v[1], v[2], v[3]);
-        g[1] = make_float4(v[4], v[5], v[6], v[7]);
-        g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(mat[t]), 0.0f);
-    }
+    if (tri_geom && d < n) store_geom_row(reinterpret_cast<float4*>(tri_geom) + 3 * (size_t)d, wv + 9 * (size_t)t, t, mat[t]);
     if (leaf_box) {
         const float4* b = reinterpret_cast<const float4*>(box) + 2 * (size_t)t;
         float4* lb = reinterpret_cast<float4*>(leaf_box) + 2 * (size_t)k;
@@ -372,6 +385,12 @@ __device__ __forceinline__ void box_of(uint32_t ref, const float4* leaf_box, con
     lo = b[0];
     hi = b[1];
 }
+// the union into (lo, hi): exact min / max
+__device__ __forceinline__ void box_union(float4& lo, float4& hi, const float4& l1, const float4& h1)
+{
+    lo = make_float4(smin(lo.x, l1.x), smin(lo.y, l1.y), smin(lo.z, l1.z), 0.0f);
+    hi = make_float4(smax(hi.x, h1.x), smax(hi.y, h1.y), smax(hi.z, h1.z), 0.0f);
+}
 __global__ void __launch_bounds__(NT) boxes_kernel(int n, const uint2* child, const uint32_t* parent, uint32_t* counter, const float4* leaf_box, float4* inner_box)
 {
     const int k = (int)(blockIdx.x * NT + threadIdx.x);
@@ -384,8 +403,9 @@ __global__ void __launch_bounds__(NT) boxes_kernel(int n, const uint2* child, co
         float4 l0, h0, l1, h1;
         box_of(c.x, leaf_box, inner_box, l0, h0);
         box_of(c.y, leaf_box, inner_box, l1, h1);
-        inner_box[2 * (size_t)p] = make_float4(smin(l0.x, l1.x), smin(l0.y, l1.y), smin(l0.z, l1.z), 0.0f);
-        inner_box[2 * (size_t)p + 1] = make_float4(smax(h0.x, h1.x), smax(h0.y, h1.y), smax(h0.z, h1.z), 0.0f);
+        box_union(l0, h0, l1, h1);
+        inner_box[2 * (size_t)p] = l0;
+        inner_box[2 * (size_t)p + 1] = h0;
         if (p == 0) return;
         p = parent[p];
     }
@@ -515,9 +535,7 @@ __device__ float treelet(const TreeletArgs& a, TreeletLds& L, uint32_t R, float 
         uint32_t c = L.cnt[1u << i0];
         for (uint32_t m = s & (s - 1); m; m &= m - 1) {
             const int i = __ffs(m) - 1;
-            const float4 l1 = L.lo[i], h1 = L.hi[i];
-            bl = make_float4(smin(bl.x, l1.x), smin(bl.y, l1.y), smin(bl.z, l1.z), 0.0f);
-            bh = make_float4(smax(bh.x, h1.x), smax(bh.y, h1.y), smax(bh.z, h1.z), 0.0f);
+            box_union(bl, bh, L.lo[i], L.hi[i]);
             c += L.cnt[1u << i];
         }
         L.area[s] = sah_area(bl, bh);
@@ -580,9 +598,7 @@ __device__ float treelet(const TreeletArgs& a, TreeletLds& L, uint32_t R, float 
             float4 bl = L.lo[i0], bh = L.hi[i0];
             for (uint32_t m = s & (s - 1); m; m &= m - 1) {
                 const int i = __ffs(m) - 1;
-                const float4 l1 = L.lo[i], h1 = L.hi[i];
-                bl = make_float4(smin(bl.x, l1.x), smin(bl.y, l1.y), smin(bl.z, l1.z), 0.0f);
-                bh = make_float4(smax(bh.x, h1.x), smax(bh.y, h1.y), smax(bh.z, h1.z), 0.0f);
+                box_union(bl, bh, L.lo[i], L.hi[i]);
             }
             a.inner_box[2 * (size_t)id] = bl;
             a.inner_box[2 * (size_t)id + 1] = bh;
@@ -692,12 +708,17 @@ __device__ __forceinline__ bool is_inner(const CollapseArgs& a, uint32_t ref)
 {
     return !(ref & REF_LEAF) && (ref == 0 || (a.top && a.top[ref]) || a.range[ref].y > a.leaf_max);
 }
-__device__ __forceinline__ float area_of(const CollapseArgs& a, uint32_t ref)
+// unused slot of a node: inverted box, empty leaf
+constexpr float EMPTY_LO = 1e30f, EMPTY_HI = -1e30f;
+__host__ __device__ inline void empty_slot(float* q, int c)
 {
-    float4 lo, hi;
-    box_of(ref, a.leaf_box, a.inner_box, lo, hi);
-    const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
-    return (dx < 0) ? 0.0f : 2.0f * (dx * dy + dy * dz + dz * dx);
+    for (int ax = 0; ax < 3; ax++) { q[8 * ax + c] = EMPTY_LO; q[8 * ax + 4 + c] = EMPTY_HI; }
+    q[24 + c] = __builtin_bit_cast(float, (uint32_t)HJR_LEAF_FLAG);
+}
+// q[28]: six rows of slot bounds (lo x, hi x, lo y, ...) and the refs row -> the node's seven float4
+__device__ __forceinline__ void store_node(float4* o, const float* q)
+{
+    for (int v = 0; v < HJR_NODE4_F4; v++) o[v] = make_float4(q[4 * v], q[4 * v + 1], q[4 * v + 2], q[4 * v + 3]);
 }
 __global__ void __launch_bounds__(NT) wide_expand_kernel(CollapseArgs a, const Front* fr, Wide* wide, uint32_t* n_inner)
 {
@@ -715,7 +736,12 @@ __global__ void __launch_bounds__(NT) wide_expand_kernel(CollapseArgs a, const F
             int best = -1;
             float barea = -1.0f;
             for (uint32_t k = 0; k < w.n; k++)
-                if (is_inner(a, w.child[k])) { const float ar = area_of(a, w.child[k]); if (ar > barea) { barea = ar; best = (int)k; } }
+                if (is_inner(a, w.child[k])) {
+                    float4 lo, hi;
+                    box_of(w.child[k], a.leaf_box, a.inner_box, lo, hi);
+                    const float ar = sah_area(lo, hi);
+                    if (ar > barea) { barea = ar; best = (int)k; }
+                }
             if (best < 0) break;
             const uint2 c = a.child[w.child[best]];
             const uint32_t dd = w.depth[best] + 1;
@@ -760,18 +786,14 @@ __global__ void __launch_bounds__(NT) wide_emit_kernel(CollapseArgs a, const Wid
                     leaf_depth = max(leaf_depth, w.depth[c]);
                 }
                 q[24 + c] = __uint_as_float(ref);
-            } else { // unused slot: inverted box, empty leaf
-                q[c] = 1e30f; q[4 + c] = -1e30f; q[8 + c] = 1e30f; q[12 + c] = -1e30f; q[16 + c] = 1e30f; q[20 + c] = -1e30f;
-                q[24 + c] = __uint_as_float(HJR_LEAF_FLAG);
-            }
+            } else empty_slot(q, c);
         }
         depth = max(depth, leaf_depth);
         if (a.inst_stat) { // integer maxima: the same values whatever order the lanes run in
             atomicMax(&a.inst_stat[2 * (size_t)w.tag], h);
             atomicMax(&a.inst_stat[2 * (size_t)w.tag + 1], leaf_depth);
         }
-        float4* o = nodes + (size_t)(base + i) * HJR_NODE4_F4;
-        for (int v = 0; v < HJR_NODE4_F4; v++) o[v] = make_float4(q[4 * v], q[4 * v + 1], q[4 * v + 2], q[4 * v + 3]);
+        store_node(nodes + (size_t)(base + i) * HJR_NODE4_F4, q);
     }
     if (worst) atomicMax(&a.hdr[H_WORST], worst);
     if (depth) atomicMax(&a.hdr[H_DEPTH], depth);
@@ -869,88 +891,108 @@ __global__ void __launch_bounds__(NT) sah_top_kernel(const float4* nodes, const 
     }
 }
 
-// ---- refit (option "device_bvh_refit"): new transforms, the current tree ---------------------------------------------------------
-// Every index read from the current frame data is checked before it is used; a violated bound sets an H_ERR bit and the commit fails.
-struct RefitArgs {
-    FlattenArgs f;           // scene, transforms, shade / inst / hdr (wv, box, cent unused)
-    uint32_t n_nodes;
-    const float4 *cur_nodes, *cur_geom; // the current frame data: only the refs rows and the prim ids are read
-    float4 *nodes, *geom;    // the builder's output
-    uint32_t *parent, *counter; // per node: 4 * parent + slot | inner children that have arrived
+// ---- leaf-order flatten, parent pass and node-box climb over a BVH4: the refit, the instance trees and the grafted skeleton -------
+// Every index read from kept data (the current frame data, the kept topology) is checked before it is used; a violated bound sets an
+// H_ERR bit and the commit fails.
+struct LeafFlattenArgs {
+    FlattenArgs f;               // scene, transforms, shade / inst / hdr (wv, box, cent unused)
+    const float4* cur_geom;      // the refit: row d takes the triangle the current row d holds (its prim id) ...
+    const uint32_t *order, *pos; // ... or (cur_geom null) the kept leaf order: sorted leaf k holds triangle order[k] in tri_geom row pos[k]
+    float4* geom;                // the builder's tri_geom
+    float4* leaf_box;            // per leaf k its unpadded world box (null: the node boxes come from tri_geom)
 };
-// flatten in leaf order: row d takes the triangle the current row d holds
-__global__ void __launch_bounds__(NT) refit_flatten_kernel(RefitArgs a)
+__global__ void __launch_bounds__(NT) leaf_flatten_kernel(LeafFlattenArgs a)
 {
     __shared__ uint32_t s_max;
     if (threadIdx.x == 0) s_max = 0u;
     __syncthreads();
-    const uint32_t d = blockIdx.x * NT + threadIdx.x;
-    if (d < a.f.n) {
-        const uint32_t t = __float_as_uint(a.cur_geom[HJR_TRI_F4 * (size_t)d + 2].y);
-        if (t >= a.f.n) atomicOr(&a.f.hdr[H_ERR], 4u);
+    const uint32_t k = blockIdx.x * NT + threadIdx.x;
+    if (k < a.f.n) {
+        const uint32_t t = a.cur_geom ? __float_as_uint(a.cur_geom[HJR_TRI_F4 * (size_t)k + 2].y) : a.order[k];
+        const uint32_t d = a.cur_geom ? k : a.pos[k];
+        if (t >= a.f.n || d >= a.f.n) atomicOr(&a.f.hdr[H_ERR], 4u);
         else {
             float v[9], s[16], bl[3], bh[3];
             const uint32_t inst = flatten_tri(a.f, t, v, s);
-            float4* sd = reinterpret_cast<float4*>(a.f.shade) + 4 * (size_t)t;
-            for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+            store_shade(a.f.shade, t, s);
             a.f.inst[t] = inst;
-            float4* g = a.geom + HJR_TRI_F4 * (size_t)d;
-            g[0] = make_float4(v[0], v[1], v[2], v[3]);
-            g[1] = make_float4(v[4], v[5], v[6], v[7]);
-            g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(a.f.mat[t]), 0.0f);
+            store_geom_row(a.geom + HJR_TRI_F4 * (size_t)d, v, t, a.f.mat[t]);
             atomicMax(&s_max, __float_as_uint(tri_box(v, bl, bh)));
+            if (a.leaf_box) {
+                a.leaf_box[2 * (size_t)k] = make_float4(bl[0], bl[1], bl[2], 0.0f);
+                a.leaf_box[2 * (size_t)k + 1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
+            }
         }
     }
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(&a.f.hdr[H_SMAX], s_max);
 }
-// parent and slot of every node from the refs, and the refs' bounds: ids are breadth-first, so a child's id is above its parent's
-__global__ void __launch_bounds__(NT) refit_parent_kernel(RefitArgs a)
+// 4 * parent + slot of every node an inner slot refers to, from the refs rows refs[i * stride]: ids are breadth-first, so a child's id
+// is above its parent's.  `n_tris` (0: unchecked) bounds the leaf refs; `keep` (or null) takes a copy of the refs rows.
+__global__ void __launch_bounds__(NT) node_parent_kernel(uint32_t n_nodes, const float4* refs, uint32_t stride, uint32_t n_tris, float4* keep, uint32_t* parent,
+                                                         uint32_t* hdr)
 {
     const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    if (i >= a.n_nodes) return;
-    const float4 r = a.cur_nodes[(size_t)i * HJR_NODE4_F4 + 6];
+    if (i >= n_nodes) return;
+    const float4 r = refs[(size_t)i * stride];
+    if (keep) keep[i] = r;
     uint32_t err = 0;
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         const uint32_t ref = ref_of(r, c);
         if (ref_inner(ref)) {
-            if (ref <= i || ref >= a.n_nodes) err |= 8u;
-            else a.parent[ref] = 4u * i + (uint32_t)c;
-        } else if ((ref & 0x7ffffffu) + ((ref >> 27) & 15u) > a.f.n) err |= 16u;
+            if (ref <= i || ref >= n_nodes) err |= 8u;
+            else parent[ref] = 4u * i + (uint32_t)c;
+        } else if (n_tris && (ref & 0x7ffffffu) + ((ref >> 27) & 15u) > n_tris) err |= 16u;
     }
-    if (err) atomicOr(&a.f.hdr[H_ERR], err);
+    if (err) atomicOr(&hdr[H_ERR], err);
 }
+// the box of a node's four slots; an unused slot (EMPTY_LO / EMPTY_HI) changes no min / max
+__device__ __forceinline__ void slots_box(const float4* nd, float* lo, float* hi)
+{
+    for (int ax = 0; ax < 3; ax++) {
+        const float4 l = nd[2 * ax], h = nd[2 * ax + 1];
+        lo[ax] = smin(smin(l.x, l.y), smin(l.z, l.w));
+        hi[ax] = smax(smax(h.x, h.y), smax(h.z, h.w));
+    }
+}
+// the padded box of the cnt > 0 tri_geom rows from `first`
+__device__ __forceinline__ void rows_box(const float4* geom, uint32_t first, uint32_t cnt, float pad, float* lo, float* hi)
+{
+    for (int ax = 0; ax < 3; ax++) { lo[ax] = 3.402823466e+38f; hi[ax] = -3.402823466e+38f; }
+    for (uint32_t k = 0; k < cnt; k++) {
+        const float4* g = geom + HJR_TRI_F4 * (size_t)(first + k);
+        const float4 g0 = g[0], g1 = g[1], g2 = g[2];
+        lo[0] = smin(smin(lo[0], g0.x), smin(g0.w, g1.z)); hi[0] = smax(smax(hi[0], g0.x), smax(g0.w, g1.z));
+        lo[1] = smin(smin(lo[1], g0.y), smin(g1.x, g1.w)); hi[1] = smax(smax(hi[1], g0.y), smax(g1.x, g1.w));
+        lo[2] = smin(smin(lo[2], g0.z), smin(g1.y, g2.x)); hi[2] = smax(smax(hi[2], g0.z), smax(g1.y, g2.x));
+    }
+    for (int ax = 0; ax < 3; ax++) { lo[ax] -= pad; hi[ax] += pad; }
+}
+struct NodeBoxArgs {
+    uint32_t n, n_nodes;     // triangles, nodes
+    const float4* refs;      // the refs row of node i is refs[i * stride]: the current nodes (stride HJR_NODE4_F4, from row 6) or the kept rows (1)
+    uint32_t stride;
+    bool forest;             // the skeleton: a climb ends at a node whose parent word is SK_NONE (else at node 0)
+    const float4* geom;      // this commit's tri_geom
+    float4* nodes;           // the output, n_nodes nodes
+    const uint32_t* parent;  // per node: 4 * parent + slot
+    uint32_t *counter, *hdr; // per node: inner children that have arrived
+};
+constexpr uint32_t SK_NONE = 0xffffffffu;
 // writes node i of the output: refs unchanged, leaf slots from the new triangles, inner slots from the child nodes already written
-__device__ __forceinline__ void refit_node(const RefitArgs& a, uint32_t i, const float4& r, float pad)
+__device__ __forceinline__ void refit_node(const NodeBoxArgs& a, uint32_t i, const float4& r, float pad)
 {
     float q[24];
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         const uint32_t ref = ref_of(r, c);
-        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f }; // unused slot: inverted box
+        float lo[3] = { EMPTY_LO, EMPTY_LO, EMPTY_LO }, hi[3] = { EMPTY_HI, EMPTY_HI, EMPTY_HI };
         if (ref_inner(ref)) {
-            if (ref > i && ref < a.n_nodes) { // an unused slot of the child (1e30 / -1e30) changes no min / max
-                const float4* ch = a.nodes + (size_t)ref * HJR_NODE4_F4;
-                for (int ax = 0; ax < 3; ax++) {
-                    const float4 l = ch[2 * ax], h = ch[2 * ax + 1];
-                    lo[ax] = smin(smin(l.x, l.y), smin(l.z, l.w));
-                    hi[ax] = smax(smax(h.x, h.y), smax(h.z, h.w));
-                }
-            }
+            if (ref > i && ref < a.n_nodes) slots_box(a.nodes + (size_t)ref * HJR_NODE4_F4, lo, hi);
         } else if (ref != HJR_LEAF_FLAG) {
             const uint32_t first = ref & 0x7ffffffu, cnt = (ref >> 27) & 15u;
-            if (first + cnt <= a.f.n && cnt > 0) {
-                for (int ax = 0; ax < 3; ax++) { lo[ax] = 3.402823466e+38f; hi[ax] = -3.402823466e+38f; }
-                for (uint32_t k = 0; k < cnt; k++) {
-                    const float4* g = a.geom + HJR_TRI_F4 * (size_t)(first + k);
-                    const float4 g0 = g[0], g1 = g[1], g2 = g[2];
-                    lo[0] = smin(smin(lo[0], g0.x), smin(g0.w, g1.z)); hi[0] = smax(smax(hi[0], g0.x), smax(g0.w, g1.z));
-                    lo[1] = smin(smin(lo[1], g0.y), smin(g1.x, g1.w)); hi[1] = smax(smax(hi[1], g0.y), smax(g1.x, g1.w));
-                    lo[2] = smin(smin(lo[2], g0.z), smin(g1.y, g2.x)); hi[2] = smax(smax(hi[2], g0.z), smax(g1.y, g2.x));
-                }
-                for (int ax = 0; ax < 3; ax++) { lo[ax] -= pad; hi[ax] += pad; }
-            }
+            if (first + cnt <= a.n && cnt > 0) rows_box(a.geom, first, cnt, pad, lo, hi);
         }
         for (int ax = 0; ax < 3; ax++) { q[8 * ax + c] = lo[ax]; q[8 * ax + 4 + c] = hi[ax]; }
     }
@@ -960,20 +1002,24 @@ __device__ __forceinline__ void refit_node(const RefitArgs& a, uint32_t i, const
 }
 // One lane per node without inner children starts there and climbs while it is the last inner child to reach the parent: boxes_kernel's
 // hand-off.  The lane stores the node it finished, then its agent-scope acq_rel add on the parent's counter releases those stores and,
-// for the last arriver, acquires the siblings' before it reads their nodes.  A parent id is below the child's, so every climb ends.
-__global__ void __launch_bounds__(NT) refit_boxes_kernel(RefitArgs a)
+// for the last arriver, acquires the siblings' before it reads their nodes.  refit_node checks every ref before it follows it and a
+// parent id must be below the child's, so every climb ends; a node whose children did not all arrive is found by the tree cost (the
+// refit) or by graft_place_kernel (the skeleton, whose output is the stage at the skeleton ids).
+__global__ void __launch_bounds__(NT) node_boxes_kernel(NodeBoxArgs a)
 {
     uint32_t i = blockIdx.x * NT + threadIdx.x;
     if (i >= a.n_nodes) return;
-    float4 r = a.cur_nodes[(size_t)i * HJR_NODE4_F4 + 6];
+    float4 r = a.refs[(size_t)i * a.stride];
     if (inner_slots(r) != 0) return;
-    const float pad = __uint_as_float(a.f.hdr[H_SMAX]) * (1.0f / 8192.0f);
+    const float pad = frame_pad(a.hdr);
     for (;;) {
         refit_node(a, i, r, pad);
-        if (i == 0) return;
-        const uint32_t p = a.parent[i] >> 2;
-        if (p >= i) { atomicOr(&a.f.hdr[H_ERR], 32u); return; } // not the parent pass's value: no slot refers to this node
-        r = a.cur_nodes[(size_t)p * HJR_NODE4_F4 + 6];
+        if (!a.forest && i == 0) return;
+        const uint32_t ps = a.parent[i];
+        if (a.forest && ps == SK_NONE) return; // an instance root
+        const uint32_t p = ps >> 2;
+        if (p >= i) { atomicOr(&a.hdr[H_ERR], 32u); return; } // not the parent pass's value: no slot refers to this node
+        r = a.refs[(size_t)p * a.stride];
         const uint32_t before = __hip_atomic_fetch_add(&a.counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         if (before + 1u != inner_slots(r)) return; // a sibling's lane finishes the parent
         i = p;
@@ -991,8 +1037,7 @@ __global__ void __launch_bounds__(NT) obj_box_kernel(FlattenArgs a, uint32_t* bm
 {
     const uint32_t t = blockIdx.x * NT + threadIdx.x;
     if (t >= a.n) return;
-    uint32_t lo = 0, hi = a.n_inst; // last prim_offset <= t, as flatten_tri
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.prim_off[mid] <= t) lo = mid; else hi = mid; }
+    const uint32_t lo = instance_of(a, t);
     float v[9], bl[3], bh[3];
     for (int k = 0; k < 3; k++) {
         const uint32_t ix = a.idx[3 * (size_t)t + k];
@@ -1081,52 +1126,21 @@ __global__ void __launch_bounds__(NT) iota_kernel(uint32_t n, uint32_t* out)
 }
 
 struct InstArgs {
-    FlattenArgs f;           // scene, transforms, shade / inst / hdr (wv, box, cent unused)
-    const uint32_t *order, *pos, *top, *parent; // the kept topology; every index read from it is checked before it is used
+    uint32_t n;
+    const uint32_t *top, *parent; // the kept topology; every index read from it is checked before it is used
     const uint2* child;
-    uint32_t* counter;
-    float4 *geom, *leaf_box, *inner_box;
+    uint32_t *counter, *hdr;
+    float4 *leaf_box, *inner_box;
 };
-// refit_flatten_kernel's shape over the kept leaf order: sorted leaf k holds triangle order[k] in tri_geom row pos[k]; its unpadded
-// world box goes to leaf_box[k]
-__global__ void __launch_bounds__(NT) inst_flatten_kernel(InstArgs a)
-{
-    __shared__ uint32_t s_max;
-    if (threadIdx.x == 0) s_max = 0u;
-    __syncthreads();
-    const uint32_t k = blockIdx.x * NT + threadIdx.x;
-    if (k < a.f.n) {
-        const uint32_t t = a.order[k], d = a.pos[k];
-        if (t >= a.f.n || d >= a.f.n) atomicOr(&a.f.hdr[H_ERR], 4u);
-        else {
-            float v[9], s[16], bl[3], bh[3];
-            const uint32_t inst = flatten_tri(a.f, t, v, s);
-            float4* sd = reinterpret_cast<float4*>(a.f.shade) + 4 * (size_t)t;
-            for (int q = 0; q < 4; q++) sd[q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
-            a.f.inst[t] = inst;
-            float4* g = a.geom + HJR_TRI_F4 * (size_t)d;
-            g[0] = make_float4(v[0], v[1], v[2], v[3]);
-            g[1] = make_float4(v[4], v[5], v[6], v[7]);
-            g[2] = make_float4(v[8], __uint_as_float(t), __uint_as_float(a.f.mat[t]), 0.0f);
-            atomicMax(&s_max, __float_as_uint(tri_box(v, bl, bh)));
-            if (a.leaf_box) { // (null under device_bvh_graft: the skeleton's boxes come from tri_geom)
-                a.leaf_box[2 * (size_t)k] = make_float4(bl[0], bl[1], bl[2], 0.0f);
-                a.leaf_box[2 * (size_t)k + 1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(&a.f.hdr[H_SMAX], s_max);
-}
 // boxes_kernel's climb and hand-off, inside the instance subtrees only: the lane pads its leaf's box with this pose's padding, then
 // climbs while it is the second to reach a node and stops below the first top node (min / max are exact and rounding is monotone:
 // the union of padded boxes is the padded union).  Nothing waits; a walk of more than n steps or an index out of range sets H_ERR.
 __global__ void __launch_bounds__(NT) inst_boxes_kernel(InstArgs a)
 {
-    const uint32_t n = a.f.n;
+    const uint32_t n = a.n;
     const uint32_t k = blockIdx.x * NT + threadIdx.x;
     if (k >= n) return;
-    const float pad = __uint_as_float(a.f.hdr[H_SMAX]) * (1.0f / 8192.0f);
+    const float pad = frame_pad(a.hdr);
     float4 lo = a.leaf_box[2 * (size_t)k], hi = a.leaf_box[2 * (size_t)k + 1];
     lo.x -= pad; lo.y -= pad; lo.z -= pad;
     hi.x += pad; hi.y += pad; hi.z += pad;
@@ -1135,18 +1149,19 @@ __global__ void __launch_bounds__(NT) inst_boxes_kernel(InstArgs a)
     if (n < 2) return;
     uint32_t p = a.parent[(size_t)(n - 1) + k];
     for (uint32_t steps = 0;; steps++) {
-        if (p >= n - 1 || steps >= n) { atomicOr(&a.f.hdr[H_ERR], 256u); return; }
+        if (p >= n - 1 || steps >= n) { atomicOr(&a.hdr[H_ERR], 256u); return; }
         if (a.top[p]) return; // the node below is an instance root
         const uint32_t before = __hip_atomic_fetch_add(&a.counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         if (before == 0) return; // the sibling's lane finishes this node
         const uint2 c = a.child[p];
         const uint32_t bx = (c.x & REF_LEAF) ? n : n - 1, by = (c.y & REF_LEAF) ? n : n - 1;
-        if ((c.x & ~REF_LEAF) >= bx || (c.y & ~REF_LEAF) >= by) { atomicOr(&a.f.hdr[H_ERR], 256u); return; }
+        if ((c.x & ~REF_LEAF) >= bx || (c.y & ~REF_LEAF) >= by) { atomicOr(&a.hdr[H_ERR], 256u); return; }
         float4 l0, h0, l1, h1;
         box_of(c.x, a.leaf_box, a.inner_box, l0, h0);
         box_of(c.y, a.leaf_box, a.inner_box, l1, h1);
-        a.inner_box[2 * (size_t)p] = make_float4(smin(l0.x, l1.x), smin(l0.y, l1.y), smin(l0.z, l1.z), 0.0f);
-        a.inner_box[2 * (size_t)p + 1] = make_float4(smax(h0.x, h1.x), smax(h0.y, h1.y), smax(h0.z, h1.z), 0.0f);
+        box_union(l0, h0, l1, h1);
+        a.inner_box[2 * (size_t)p] = l0;
+        a.inner_box[2 * (size_t)p + 1] = h0;
         if (p == 0) return;
         p = a.parent[p];
     }
@@ -1168,10 +1183,68 @@ struct TopArgs {
 };
 constexpr uint32_t TOP_NONE = 0xffffffffu;
 using hjr::HJR_TOP_MAX;
+// The clustering rounds of both top trees over k slots: box[0..2] the clusters' minima, box[3..5] their maxima, ref[s] == TOP_NONE: slot
+// s is not an active cluster.  merge(s, j, idx) unites the mutual pair s < j, merge number idx in slot order, in slot s: it checks its
+// bounds (false: one failed, nothing is written), calls cluster_union, names the new cluster in ref[s] and sets ref[j] = TOP_NONE.
+// False: H_ERR bit 1024 is set and the workgroup returns.
+__device__ __forceinline__ void cluster_union(float (&box)[6][HJR_TOP_MAX], uint32_t s, uint32_t j, float4& lo, float4& hi)
+{
+    float l[3], h[3];
+    for (int ax = 0; ax < 3; ax++) {
+        l[ax] = box[ax][s] = smin(box[ax][s], box[ax][j]);
+        h[ax] = box[3 + ax][s] = smax(box[3 + ax][s], box[3 + ax][j]);
+    }
+    lo = make_float4(l[0], l[1], l[2], 0.0f);
+    hi = make_float4(h[0], h[1], h[2], 0.0f);
+}
+template <class Merge>
+__device__ __forceinline__ bool cluster_rounds(uint32_t k, float (&box)[6][HJR_TOP_MAX], const uint32_t* ref, uint32_t* partner, uint32_t* scan, uint32_t& err,
+                                               uint32_t* hdr, Merge merge)
+{
+    uint32_t merged = 0;
+    for (uint32_t round = 0; merged + 1 < k; round++) {
+        if (round >= k) { if (threadIdx.x == 0) atomicOr(&hdr[H_ERR], 1024u); return false; } // (never: every round merges)
+        for (uint32_t s = threadIdx.x; s < k; s += NT) {
+            uint32_t bj = TOP_NONE;
+            if (ref[s] != TOP_NONE) {
+                const float lx = box[0][s], ly = box[1][s], lz = box[2][s], hx = box[3][s], hy = box[4][s], hz = box[5][s];
+                float best = 0.0f;
+                for (uint32_t j = 0; j < k; j++) {
+                    if (j == s || ref[j] == TOP_NONE) continue;
+                    const float dx = smax(hx, box[3][j]) - smin(lx, box[0][j]), dy = smax(hy, box[4][j]) - smin(ly, box[1][j]),
+                                dz = smax(hz, box[5][j]) - smin(lz, box[2][j]);
+                    const float area = dx * dy + dy * dz + dz * dx;
+                    if (bj == TOP_NONE || area < best) { best = area; bj = j; }
+                }
+            }
+            partner[s] = bj;
+        }
+        __syncthreads();
+        // a thread owns four consecutive slots, so that the scan numbers the round's merges in slot order
+        uint32_t mine = 0, tot;
+        bool m[4];
+        for (uint32_t q = 0; q < 4; q++) {
+            const uint32_t s = 4 * threadIdx.x + q;
+            const uint32_t j = s < k ? partner[s] : TOP_NONE;
+            m[q] = j != TOP_NONE && j > s && j < k && partner[j] == s;
+            mine += m[q] ? 1u : 0u;
+        }
+        uint32_t at = merged + block_scan(mine, tot, scan);
+        for (uint32_t q = 0; q < 4; q++) {
+            if (!m[q]) continue;
+            const uint32_t s = 4 * threadIdx.x + q;
+            if (!merge(s, partner[s], at++)) err = 1u;
+        }
+        __syncthreads();
+        if (err || tot == 0) { if (threadIdx.x == 0) atomicOr(&hdr[H_ERR], 1024u); return false; } // (tot 0: a non-finite box, reported before this bit)
+        merged += tot;
+    }
+    return true;
+}
 __global__ void __launch_bounds__(NT) inst_top_kernel(TopArgs a)
 {
-    __shared__ float s_lo[3][HJR_TOP_MAX], s_hi[3][HJR_TOP_MAX];
-    __shared__ uint32_t s_ref[HJR_TOP_MAX], s_cnt[HJR_TOP_MAX], s_partner[HJR_TOP_MAX]; // s_cnt 0: the slot is not an active cluster
+    __shared__ float s_box[6][HJR_TOP_MAX];
+    __shared__ uint32_t s_ref[HJR_TOP_MAX], s_cnt[HJR_TOP_MAX], s_partner[HJR_TOP_MAX]; // s_ref: the cluster's BVH2 ref | s_cnt: its triangles
     __shared__ uint32_t s_scan[4], s_err;
     const uint32_t k = min(a.k, HJR_TOP_MAX), n = a.n;
     if (threadIdx.x == 0) s_err = 0u;
@@ -1188,63 +1261,30 @@ __global__ void __launch_bounds__(NT) inst_top_kernel(TopArgs a)
             if (!(ref & REF_LEAF)) cnt = a.range[id].y;
         }
         if (!ok || cnt == 0) s_err = 1u;
-        s_lo[0][s] = lo.x; s_lo[1][s] = lo.y; s_lo[2][s] = lo.z;
-        s_hi[0][s] = hi.x; s_hi[1][s] = hi.y; s_hi[2][s] = hi.z;
+        s_box[0][s] = lo.x; s_box[1][s] = lo.y; s_box[2][s] = lo.z;
+        s_box[3][s] = hi.x; s_box[4][s] = hi.y; s_box[5][s] = hi.z;
         s_ref[s] = ref; s_cnt[s] = cnt;
     }
     __syncthreads();
     if (s_err) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 512u); return; }
-    uint32_t merged = 0;
-    for (uint32_t round = 0; merged + 1 < k; round++) {
-        if (round >= k) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (never: every round merges)
-        for (uint32_t s = threadIdx.x; s < k; s += NT) {
-            uint32_t bj = TOP_NONE;
-            if (s_cnt[s]) {
-                const float lx = s_lo[0][s], ly = s_lo[1][s], lz = s_lo[2][s], hx = s_hi[0][s], hy = s_hi[1][s], hz = s_hi[2][s];
-                float best = 0.0f;
-                for (uint32_t j = 0; j < k; j++) {
-                    if (j == s || !s_cnt[j]) continue;
-                    const float dx = smax(hx, s_hi[0][j]) - smin(lx, s_lo[0][j]), dy = smax(hy, s_hi[1][j]) - smin(ly, s_lo[1][j]),
-                                dz = smax(hz, s_hi[2][j]) - smin(lz, s_lo[2][j]);
-                    const float area = dx * dy + dy * dz + dz * dx;
-                    if (bj == TOP_NONE || area < best) { best = area; bj = j; }
-                }
-            }
-            s_partner[s] = bj;
-        }
-        __syncthreads();
-        // a thread owns four consecutive slots, so that the scan numbers the round's merges in slot order
-        uint32_t mine = 0, tot;
-        bool m[4];
-        for (uint32_t q = 0; q < 4; q++) {
-            const uint32_t s = 4 * threadIdx.x + q;
-            const uint32_t j = s < k ? s_partner[s] : TOP_NONE;
-            m[q] = j != TOP_NONE && j > s && j < k && s_partner[j] == s;
-            mine += m[q] ? 1u : 0u;
-        }
-        uint32_t at = merged + block_scan(mine, tot, s_scan);
-        for (uint32_t q = 0; q < 4; q++) {
-            if (!m[q]) continue;
-            const uint32_t s = 4 * threadIdx.x + q, j = s_partner[s], idx = at++;
-            const uint32_t id = idx + 2 <= k ? a.top_ids[k - 2 - idx] : TOP_NONE;
-            const uint32_t rs = s_ref[s], rj = s_ref[j];
-            const size_t ps = parent_slot((int)n, rs), pj = parent_slot((int)n, rj), slots = 2 * (size_t)n - 1;
-            if (id + 1 >= n || id == TOP_NONE || !a.top[id] || ps >= slots || pj >= slots) { s_err = 1u; continue; }
-            for (int ax = 0; ax < 3; ax++) { s_lo[ax][s] = smin(s_lo[ax][s], s_lo[ax][j]); s_hi[ax][s] = smax(s_hi[ax][s], s_hi[ax][j]); }
-            s_cnt[s] += s_cnt[j];
-            s_cnt[j] = 0;
-            s_ref[s] = id;
-            a.child[id] = make_uint2(rs, rj);
-            a.range[id] = make_uint2(0u, s_cnt[s]); // only the count: a top node is never a BVH4 leaf
-            a.inner_box[2 * (size_t)id] = make_float4(s_lo[0][s], s_lo[1][s], s_lo[2][s], 0.0f);
-            a.inner_box[2 * (size_t)id + 1] = make_float4(s_hi[0][s], s_hi[1][s], s_hi[2][s], 0.0f);
-            a.parent[ps] = id;
-            a.parent[pj] = id;
-        }
-        __syncthreads();
-        if (s_err || tot == 0) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (tot 0: a non-finite box, reported before this bit)
-        merged += tot;
-    }
+    cluster_rounds(k, s_box, s_ref, s_partner, s_scan, s_err, a.hdr, [&](uint32_t s, uint32_t j, uint32_t idx) {
+        const uint32_t id = idx + 2 <= k ? a.top_ids[k - 2 - idx] : TOP_NONE;
+        const uint32_t rs = s_ref[s], rj = s_ref[j];
+        const size_t ps = parent_slot((int)n, rs), pj = parent_slot((int)n, rj), slots = 2 * (size_t)n - 1;
+        if (id + 1 >= n || id == TOP_NONE || !a.top[id] || ps >= slots || pj >= slots) return false;
+        float4 lo, hi;
+        cluster_union(s_box, s, j, lo, hi);
+        s_cnt[s] += s_cnt[j];
+        s_ref[s] = id;
+        s_ref[j] = TOP_NONE;
+        a.child[id] = make_uint2(rs, rj);
+        a.range[id] = make_uint2(0u, s_cnt[s]); // only the count: a top node is never a BVH4 leaf
+        a.inner_box[2 * (size_t)id] = lo;
+        a.inner_box[2 * (size_t)id + 1] = hi;
+        a.parent[ps] = id;
+        a.parent[pj] = id;
+        return true;
+    });
 }
 
 // ---- grafted instance trees (option "device_bvh_graft") -----------------------------------------------------------------------------
@@ -1252,12 +1292,11 @@ __global__ void __launch_bounds__(NT) inst_top_kernel(TopArgs a)
 // boxes) run level by level from a frontier that holds the root of every instance of more than leaf_max triangles, in instance order,
 // so that ids are breadth-first over all instances together from 0.  Of the nodes they write only the refs rows are kept, with the
 // parent slot of every node, and per instance the maxima of the pending-entry count and of the leaf depth below its root.
-// Every commit: graft_boxes_kernel (the refit's climb over the skeleton, into `stage` at the skeleton ids), graft_top_kernel (instance
+// Every commit: node_boxes_kernel (the refit's climb over the skeleton, into `stage` at the skeleton ids), graft_top_kernel (instance
 // boxes, top tree, its collapse: the top nodes [0, base)), graft_place_kernel (stage -> nodes at base + id, base added to the inner
 // refs).  The top-node count depends on the clustering, which needs this pose's instance boxes: it cannot be known before the boxes.
 // H_ERR bits of these kernels: 8 / 16 skeleton refs, 32 skeleton parent, 64 a skeleton node that was not written, 512 instance roots,
 // 1024 top tree, 2048 more nodes than the buffers hold.
-constexpr uint32_t SK_NONE = 0xffffffffu;
 
 // the frontier of the skeleton's first level and inst_ref of every non-empty instance (one workgroup; a thread owns four consecutive
 // instances, so that the scan numbers the roots in instance order)
@@ -1299,49 +1338,9 @@ __global__ void __launch_bounds__(NT) skel_init_kernel(uint32_t n, uint32_t n_in
     if (bad) atomicOr(&hdr[H_ERR], 512u);
     if (threadIdx.x == 0) { hdr[H_BASE] = 0; hdr[H_F] = tot; }
 }
-// what is kept of the n_skel nodes the collapse wrote: the refs row, and 4 * parent + slot of every node an inner slot refers to
-__global__ void __launch_bounds__(NT) skel_keep_kernel(uint32_t n_skel, const float4* nodes, float4* refs, uint32_t* parent, uint32_t* hdr)
-{
-    const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    if (i >= n_skel) return;
-    const float4 r = nodes[(size_t)i * HJR_NODE4_F4 + 6];
-    refs[i] = r;
-    uint32_t err = 0;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const uint32_t ref = ref_of(r, c);
-        if (!ref_inner(ref)) continue;
-        if (ref <= i || ref >= n_skel) err |= 8u;
-        else parent[ref] = 4u * i + (uint32_t)c;
-    }
-    if (err) atomicOr(&hdr[H_ERR], err);
-}
-
-// refit_boxes_kernel over the skeleton: a.nodes is the stage, a.n_nodes the skeleton's size, a.parent the kept parent slots; a lane
-// starts at every node without inner children and stops at an instance root.  refit_node checks every ref before it follows it, a
-// parent id must be below the child's (so every climb ends), and graft_place_kernel finds a node whose children did not all arrive.
-__global__ void __launch_bounds__(NT) graft_boxes_kernel(RefitArgs a, const float4* refs)
-{
-    uint32_t i = blockIdx.x * NT + threadIdx.x;
-    if (i >= a.n_nodes) return;
-    float4 r = refs[i];
-    if (inner_slots(r) != 0) return;
-    const float pad = __uint_as_float(a.f.hdr[H_SMAX]) * (1.0f / 8192.0f);
-    for (;;) {
-        refit_node(a, i, r, pad);
-        const uint32_t ps = a.parent[i];
-        if (ps == SK_NONE) return; // an instance root
-        const uint32_t p = ps >> 2;
-        if (p >= i) { atomicOr(&a.f.hdr[H_ERR], 32u); return; }
-        r = refs[p];
-        const uint32_t before = __hip_atomic_fetch_add(&a.counter[p], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (before + 1u != inner_slots(r)) return; // a sibling's lane finishes the parent
-        i = p;
-    }
-}
 
 // The top tree over the instance boxes and its BVH4, in one workgroup (workgroup barriers only).  An instance's box is the union of
-// its root node's slot boxes in the stage, or of its triangles' padded boxes when it has no node.  Clustering: inst_top_kernel's rule
+// its root node's slot boxes in the stage, or of its triangles' padded boxes when it has no node.  Clustering: cluster_rounds
 // (smallest union area, mutual pairs merge into the smaller slot, ties to the smaller slot); merge number m is binary node m, the
 // last one the root.  Top-tree refs: an instance slot s < k, or k + m.  The binary tree is collapsed breadth-first with
 // wide_expand_kernel's rule, where only binary nodes are expanded and an instance is a leaf slot (<= leaf_max triangles) or an inner
@@ -1365,37 +1364,22 @@ __global__ void __launch_bounds__(NT) graft_top_kernel(GraftTopArgs a)
     __shared__ float s_box[6][HJR_TOP_MAX];                       // the clusters' boxes; after the clustering the two frontiers
     __shared__ uint32_t s_ref[HJR_TOP_MAX], s_partner[HJR_TOP_MAX]; // s_ref TOP_NONE: the slot is not an active cluster
     __shared__ uint2 s_kid[HJR_TOP_MAX];                          // binary node m: its two top-tree refs
-    __shared__ float s_area[HJR_TOP_MAX];                         // ... and its area (area_of's expression)
+    __shared__ float s_area[HJR_TOP_MAX];                         // ... and its area (sah_area)
     __shared__ uint32_t s_scan[4], s_err;
     const uint32_t k = min(a.k, HJR_TOP_MAX), n = a.n;
     if (threadIdx.x == 0) s_err = 0u;
     __syncthreads();
-    const float pad = __uint_as_float(a.hdr[H_SMAX]) * (1.0f / 8192.0f);
+    const float pad = frame_pad(a.hdr);
     for (uint32_t s = threadIdx.x; s < k; s += NT) {
         const uint32_t ref = a.inst_ref[s];
-        float lo[3] = { 1e30f, 1e30f, 1e30f }, hi[3] = { -1e30f, -1e30f, -1e30f };
+        float lo[3] = { EMPTY_LO, EMPTY_LO, EMPTY_LO }, hi[3] = { EMPTY_HI, EMPTY_HI, EMPTY_HI };
         if (ref_inner(ref)) {
-            if (ref < a.n_skel) {
-                const float4* nd = a.stage + (size_t)ref * HJR_NODE4_F4;
-                for (int ax = 0; ax < 3; ax++) {
-                    const float4 l = nd[2 * ax], h = nd[2 * ax + 1];
-                    lo[ax] = smin(smin(l.x, l.y), smin(l.z, l.w));
-                    hi[ax] = smax(smax(h.x, h.y), smax(h.z, h.w));
-                }
-            } else s_err = 1u;
+            if (ref < a.n_skel) slots_box(a.stage + (size_t)ref * HJR_NODE4_F4, lo, hi);
+            else s_err = 1u;
         } else {
             const uint32_t first = ref & 0x7ffffffu, cnt = (ref >> 27) & 15u;
-            if (cnt > 0 && first < n && cnt <= n - first) {
-                for (int ax = 0; ax < 3; ax++) { lo[ax] = 3.402823466e+38f; hi[ax] = -3.402823466e+38f; }
-                for (uint32_t t = 0; t < cnt; t++) {
-                    const float4* g = a.geom + HJR_TRI_F4 * (size_t)(first + t);
-                    const float4 g0 = g[0], g1 = g[1], g2 = g[2];
-                    lo[0] = smin(smin(lo[0], g0.x), smin(g0.w, g1.z)); hi[0] = smax(smax(hi[0], g0.x), smax(g0.w, g1.z));
-                    lo[1] = smin(smin(lo[1], g0.y), smin(g1.x, g1.w)); hi[1] = smax(smax(hi[1], g0.y), smax(g1.x, g1.w));
-                    lo[2] = smin(smin(lo[2], g0.z), smin(g1.y, g2.x)); hi[2] = smax(smax(hi[2], g0.z), smax(g1.y, g2.x));
-                }
-                for (int ax = 0; ax < 3; ax++) { lo[ax] -= pad; hi[ax] += pad; }
-            } else s_err = 1u;
+            if (cnt > 0 && first < n && cnt <= n - first) rows_box(a.geom, first, cnt, pad, lo, hi);
+            else s_err = 1u;
         }
         for (int ax = 0; ax < 3; ax++) { s_box[ax][s] = lo[ax]; s_box[3 + ax][s] = hi[ax]; }
         s_ref[s] = s;
@@ -1404,55 +1388,19 @@ __global__ void __launch_bounds__(NT) graft_top_kernel(GraftTopArgs a)
     }
     __syncthreads();
     if (s_err) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 512u); return; }
-    uint32_t merged = 0;
-    for (uint32_t round = 0; merged + 1 < k; round++) {
-        if (round >= k) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (never: every round merges)
-        for (uint32_t s = threadIdx.x; s < k; s += NT) {
-            uint32_t bj = TOP_NONE;
-            if (s_ref[s] != TOP_NONE) {
-                const float lx = s_box[0][s], ly = s_box[1][s], lz = s_box[2][s], hx = s_box[3][s], hy = s_box[4][s], hz = s_box[5][s];
-                float best = 0.0f;
-                for (uint32_t j = 0; j < k; j++) {
-                    if (j == s || s_ref[j] == TOP_NONE) continue;
-                    const float dx = smax(hx, s_box[3][j]) - smin(lx, s_box[0][j]), dy = smax(hy, s_box[4][j]) - smin(ly, s_box[1][j]),
-                                dz = smax(hz, s_box[5][j]) - smin(lz, s_box[2][j]);
-                    const float area = dx * dy + dy * dz + dz * dx;
-                    if (bj == TOP_NONE || area < best) { best = area; bj = j; }
-                }
-            }
-            s_partner[s] = bj;
-        }
-        __syncthreads();
-        uint32_t mine = 0, tot;
-        bool m[4];
-        for (uint32_t q = 0; q < 4; q++) {
-            const uint32_t s = 4 * threadIdx.x + q;
-            const uint32_t j = s < k ? s_partner[s] : TOP_NONE;
-            m[q] = j != TOP_NONE && j > s && j < k && s_partner[j] == s;
-            mine += m[q] ? 1u : 0u;
-        }
-        uint32_t at = merged + block_scan(mine, tot, s_scan);
-        for (uint32_t q = 0; q < 4; q++) {
-            if (!m[q]) continue;
-            const uint32_t s = 4 * threadIdx.x + q, j = s_partner[s], idx = at++;
-            if (idx + 1 >= k) { s_err = 1u; continue; } // (never: k - 1 merges in all)
-            float lo[3], hi[3];
-            for (int ax = 0; ax < 3; ax++) {
-                lo[ax] = s_box[ax][s] = smin(s_box[ax][s], s_box[ax][j]);
-                hi[ax] = s_box[3 + ax][s] = smax(s_box[3 + ax][s], s_box[3 + ax][j]);
-            }
-            const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-            s_kid[idx] = make_uint2(s_ref[s], s_ref[j]);
-            s_area[idx] = (dx < 0) ? 0.0f : 2.0f * (dx * dy + dy * dz + dz * dx);
-            s_ref[s] = k + idx;
-            s_ref[j] = TOP_NONE;
-            a.box[2 * (size_t)(k + idx)] = make_float4(lo[0], lo[1], lo[2], 0.0f);
-            a.box[2 * (size_t)(k + idx) + 1] = make_float4(hi[0], hi[1], hi[2], 0.0f);
-        }
-        __syncthreads();
-        if (s_err || tot == 0) { if (threadIdx.x == 0) atomicOr(&a.hdr[H_ERR], 1024u); return; } // (tot 0: a non-finite box, reported before this bit)
-        merged += tot;
-    }
+    const bool clustered = cluster_rounds(k, s_box, s_ref, s_partner, s_scan, s_err, a.hdr, [&](uint32_t s, uint32_t j, uint32_t idx) {
+        if (idx + 1 >= k) return false; // (never: k - 1 merges in all)
+        float4 lo, hi;
+        cluster_union(s_box, s, j, lo, hi);
+        s_kid[idx] = make_uint2(s_ref[s], s_ref[j]);
+        s_area[idx] = sah_area(lo, hi);
+        s_ref[s] = k + idx;
+        s_ref[j] = TOP_NONE;
+        a.box[2 * (size_t)(k + idx)] = lo;
+        a.box[2 * (size_t)(k + idx) + 1] = hi;
+        return true;
+    });
+    if (!clustered) return;
     // the BVH4 of the top tree.  Frontier entries: top-tree ref, pending entries above the node, its binary depth
     uint32_t* fr = reinterpret_cast<uint32_t*>(&s_box[0][0]);
     uint32_t worst = 0, depth = 0, base = 0;
@@ -1503,7 +1451,7 @@ __global__ void __launch_bounds__(NT) graft_top_kernel(GraftTopArgs a)
 #pragma unroll
                     for (uint32_t c = 0; c < 4; c++) {
                         uint32_t ref = HJR_LEAF_FLAG;
-                        float4 lo = make_float4(1e30f, 1e30f, 1e30f, 0.0f), hi = make_float4(-1e30f, -1e30f, -1e30f, 0.0f);
+                        float4 lo = make_float4(EMPTY_LO, EMPTY_LO, EMPTY_LO, 0.0f), hi = make_float4(EMPTY_HI, EMPTY_HI, EMPTY_HI, 0.0f);
                         if (c < nc) {
                             const uint32_t r = ch[c];
                             if (r >= k) {
@@ -1526,10 +1474,7 @@ __global__ void __launch_bounds__(NT) graft_top_kernel(GraftTopArgs a)
                         q[c] = lo.x; q[4 + c] = hi.x; q[8 + c] = lo.y; q[12 + c] = hi.y; q[16 + c] = lo.z; q[20 + c] = hi.z;
                         q[24 + c] = __uint_as_float(ref);
                     }
-                    if (pass == 1 && lbase + i < a.cap) {
-                        float4* o = a.nodes + (size_t)(lbase + i) * HJR_NODE4_F4;
-                        for (int v = 0; v < HJR_NODE4_F4; v++) o[v] = make_float4(q[4 * v], q[4 * v + 1], q[4 * v + 2], q[4 * v + 3]);
-                    }
+                    if (pass == 1 && lbase + i < a.cap) store_node(a.nodes + (size_t)(lbase + i) * HJR_NODE4_F4, q);
                 }
                 run += tot;
             }
@@ -1601,6 +1546,48 @@ void DeviceBvh::drop_topology()
         if (e_ != hipSuccess) { err = std::string(#call) + " failed: " + hipGetErrorString(e_); return HJR_ERR_DEVICE; } \
     } while (0)
 
+static int fail_alloc(std::string& err)
+{
+    err = "device BVH: allocation or upload failed";
+    return HJR_ERR_DEVICE;
+}
+
+// the object-space scene, once per hjr_upload_scene; a topology of the scene before it is no longer valid
+static bool upload_scene(DeviceBvh& b, const SceneCopy& sc, hipStream_t st)
+{
+    if (b.have_scene) return true;
+    if (!b.vert.upload(sc.vertices.data(), sc.vertices.size() * 4, st) || !b.norm.upload(sc.normals.data(), sc.normals.size() * 4, st) ||
+        !b.uv.upload(sc.texcoords.data(), sc.texcoords.size() * 4, st) || !b.idx.upload(sc.indices.data(), sc.indices.size() * 4, st) ||
+        !b.mat.upload(sc.material_ids.data(), sc.material_ids.size() * 4, st) || !b.prim_off.upload(sc.prim_offset.data(), sc.prim_offset.size() * 4, st))
+        return false;
+    b.have_scene = true;
+    b.topo.valid = false;
+    return true;
+}
+
+// what b.xf takes per instance: 12 floats of M, then 12 of Mi (the caller keeps it until its host wait)
+static std::vector<float> pack_transforms(const float* M, const float* Mi, uint32_t n_inst)
+{
+    std::vector<float> xf((size_t)n_inst * 24);
+    for (uint32_t i = 0; i < n_inst; i++) {
+        memcpy(&xf[24 * (size_t)i], M + 12 * (size_t)i, 48);
+        memcpy(&xf[24 * (size_t)i + 12], Mi + 12 * (size_t)i, 48);
+    }
+    return xf;
+}
+
+// the scene, the transforms and the builder's per-triangle buffers; a kernel reads only those its pass has reserved
+static FlattenArgs flatten_args(const DeviceBvh& b, uint32_t n, uint32_t n_inst)
+{
+    FlattenArgs fa;
+    fa.vert = b.vert.as<float>(); fa.norm = b.norm.as<float>(); fa.uv = b.uv.as<float>(); fa.xf = b.xf.as<float>();
+    fa.idx = b.idx.as<uint32_t>(); fa.mat = b.mat.as<uint32_t>(); fa.prim_off = b.prim_off.as<uint32_t>();
+    fa.n = n; fa.n_inst = n_inst;
+    fa.wv = b.wv.as<float>(); fa.shade = b.tri_shade.as<float>(); fa.box = b.box.as<float>(); fa.cent = b.cent.as<float>();
+    fa.inst = b.tri_inst.as<uint32_t>(); fa.hdr = b.hdr.as<uint32_t>();
+    return fa;
+}
+
 static int scan(uint32_t* in_out, const uint32_t* n_ptr, uint32_t n_const, uint32_t* part, uint32_t* total, hipStream_t st, std::string& err)
 {
     hipLaunchKernelGGL(scan_reduce_kernel, dim3(SCAN_G), dim3(NT), 0, st, in_out, n_ptr, n_const, part);
@@ -1613,64 +1600,112 @@ static int scan(uint32_t* in_out, const uint32_t* n_ptr, uint32_t n_const, uint3
 // the tree cost of `nodes` (their count at *n_ptr, at most cap) into hdr[H_SAH]
 static void launch_sah(DeviceBvh& b, const float4* nodes, const uint32_t* n_ptr, uint32_t cap, const uint32_t* counter, hipStream_t st)
 {
-    uint32_t* hdr = (uint32_t*)b.hdr.p;
-    hipLaunchKernelGGL(sah_reduce_kernel, dim3(SCAN_G), dim3(NT), 0, st, nodes, n_ptr, cap, counter, (float*)b.part.p, hdr);
-    hipLaunchKernelGGL(sah_top_kernel, dim3(1), dim3(NT), 0, st, nodes, (const float*)b.part.p, hdr);
+    uint32_t* hdr = b.hdr.as<uint32_t>();
+    hipLaunchKernelGGL(sah_reduce_kernel, dim3(SCAN_G), dim3(NT), 0, st, nodes, n_ptr, cap, counter, b.part.as<float>(), hdr);
+    hipLaunchKernelGGL(sah_top_kernel, dim3(1), dim3(NT), 0, st, nodes, b.part.as<const float>(), hdr);
 }
 
 // stable sort of keys[0] / vals[0] (n pairs, nb tiles): 8 x 8 bits, the result is back in keys[0] / vals[0]
 static int sort_pairs(DeviceBvh& b, uint32_t n, uint32_t nb, hipStream_t st, std::string& err)
 {
-    uint64_t* keys[2] = { (uint64_t*)b.keys[0].p, (uint64_t*)b.keys[1].p };
-    uint32_t* vals[2] = { (uint32_t*)b.vals[0].p, (uint32_t*)b.vals[1].p };
+    uint64_t* keys[2] = { b.keys[0].as<uint64_t>(), b.keys[1].as<uint64_t>() };
+    uint32_t* vals[2] = { b.vals[0].as<uint32_t>(), b.vals[1].as<uint32_t>() };
     for (int pass = 0; pass < 8; pass++) {
         const int s = pass & 1;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], n, 8 * pass, (uint32_t*)b.hist.p, nb);
-        if (const int rc = scan((uint32_t*)b.hist.p, nullptr, nb * 256u, (uint32_t*)b.part.p, nullptr, st, err)) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, st, (const uint64_t*)keys[s], (const uint32_t*)vals[s], n, 8 * pass,
-                           (const uint32_t*)b.hist.p, nb, keys[s ^ 1], vals[s ^ 1]);
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(NT), 0, st, keys[s], n, 8 * pass, b.hist.as<uint32_t>(), nb);
+        if (const int rc = scan(b.hist.as<uint32_t>(), nullptr, nb * 256u, b.part.as<uint32_t>(), nullptr, st, err)) return rc;
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, st, keys[s], vals[s], n, 8 * pass, b.hist.as<uint32_t>(), nb, keys[s ^ 1], vals[s ^ 1]);
     }
     return HJR_OK;
 }
 
-// The BVH2 `ca` describes over n >= 1 triangles -> b.nodes, level by level; then the tree cost, the build's one read of the header
-// and its results.  `what` names the tree in the structural-bound error.
-static int collapse_and_cost(DeviceBvh& b, const CollapseArgs& ca, uint32_t n, size_t nn, hipStream_t st, DeviceBvhResult& r, const char* what, std::string& err)
+// The boxes of the BVH2 (child, parent) over n >= 2 sorted leaves into b.inner_box, bottom-up from b.leaf_box; with `order`, the leaf
+// boxes are first gathered from b.box in that order.
+static int bvh2_boxes(DeviceBvh& b, uint32_t n, const uint32_t* order, const uint2* child, const uint32_t* parent, hipStream_t st, std::string& err)
+{
+    if (order)
+        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, order, nullptr, nullptr, b.mat.as<uint32_t>(), b.box.as<float>(), nullptr,
+                           b.leaf_box.as<float>());
+    DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+    hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, child, parent, b.counter.as<uint32_t>(), b.leaf_box.as<float4>(),
+                       b.inner_box.as<float4>());
+    return HJR_OK;
+}
+
+// Option "device_bvh_opt": the treelet rounds over the BVH2 (child, parent; its boxes in b.leaf_box / b.inner_box; `top` as TreeletArgs),
+// then every sorted leaf's tri_geom row into `pos` and the inner nodes' (first, count) into `range`.
+static int restructure_bvh2(DeviceBvh& b, uint32_t n, uint32_t leaf_max, uint32_t opt_rounds, uint2* child, uint32_t* parent, const uint32_t* top, uint32_t* pos,
+                            uint2* range, hipStream_t st, std::string& err)
+{
+    TreeletArgs ta;
+    ta.n = (int)n; ta.leaf_max = leaf_max;
+    ta.child = child; ta.parent = parent; ta.counter = b.counter.as<uint32_t>();
+    ta.count = b.node_count.as<uint32_t>(); ta.cost = b.node_cost.as<float>();
+    ta.leaf_box = b.leaf_box.as<float4>(); ta.inner_box = b.inner_box.as<float4>(); ta.top = top;
+    for (uint32_t round = 0; round < opt_rounds; round++) {
+        ta.gamma = TREELET << round; // the paper's schedule: the treelet size, doubled every round
+        DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
+        hipLaunchKernelGGL(treelet_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, ta);
+    }
+    hipLaunchKernelGGL(leaf_pos_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, child, parent, ta.count, pos, b.hdr.as<uint32_t>());
+    hipLaunchKernelGGL(inner_range_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, child, ta.count, pos, range, b.hdr.as<uint32_t>());
+    return HJR_OK;
+}
+
+// The collapse's levels -> b.nodes, from the frontier in b.frontier[0] with hdr[H_BASE] / hdr[H_F] set: LEVEL_BATCH levels between two
+// reads of the frontier size.  F: the nodes still to expand when the levels ran out (0: the tree is complete, its size in hdr[H_BASE]).
+static int collapse_levels(DeviceBvh& b, const CollapseArgs& ca, size_t nn, hipStream_t st, uint32_t& F, std::string& err)
 {
     uint32_t* hdr = ca.hdr;
-    Front* fr[2] = { (Front*)b.frontier[0].p, (Front*)b.frontier[1].p };
-    Wide* wide = (Wide*)b.wide.p;
-    uint32_t* n_inner = (uint32_t*)((char*)b.wide.p + nn * sizeof(Wide));
-    hipLaunchKernelGGL(collapse_init_kernel, dim3(1), dim3(1), 0, st, n, fr[0], hdr);
+    Front* fr[2] = { b.frontier[0].as<Front>(), b.frontier[1].as<Front>() };
+    Wide* wide = b.wide.as<Wide>();
+    uint32_t* n_inner = reinterpret_cast<uint32_t*>(b.wide.as<char>() + nn * sizeof(Wide));
     const unsigned grid = (unsigned)std::min<size_t>(blocks_for(nn), 1024);
-    uint32_t level = 0, F = 1;
+    uint32_t level = 0;
+    F = 1;
     while (F > 0 && level < hjr::DEVICE_BVH_MAX_STACK) {
         for (int k = 0; k < LEVEL_BATCH; k++, level++) {
-            Front* cur = fr[level & 1];
-            hipLaunchKernelGGL(wide_expand_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Front*)cur, wide, n_inner);
-            if (const int rc = scan(n_inner, hdr + H_F, 0u, (uint32_t*)b.part.p, hdr + H_NEXT, st, err)) return rc;
-            hipLaunchKernelGGL(wide_emit_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Wide*)wide, (const uint32_t*)n_inner, fr[(level + 1) & 1],
-                               (float4*)b.nodes.p);
+            hipLaunchKernelGGL(wide_expand_kernel, dim3(grid), dim3(NT), 0, st, ca, fr[level & 1], wide, n_inner);
+            if (const int rc = scan(n_inner, hdr + H_F, 0u, b.part.as<uint32_t>(), hdr + H_NEXT, st, err)) return rc;
+            hipLaunchKernelGGL(wide_emit_kernel, dim3(grid), dim3(NT), 0, st, ca, wide, n_inner, fr[(level + 1) & 1], b.nodes.as<float4>());
             hipLaunchKernelGGL(level_advance_kernel, dim3(1), dim3(1), 0, st, hdr);
         }
         DCHK(hipGetLastError());
         DCHK(hipMemcpyAsync(&F, hdr + H_F, 4, hipMemcpyDeviceToHost, st));
         DCHK(hipStreamSynchronize(st));
     }
-    launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, (uint32_t)nn, nullptr, st);
-    DCHK(hipGetLastError());
+    return HJR_OK;
+}
+
+// The one read of the header that ends a build, a refit or a commit: the host wait, the HIP-event time since ev0, the checks and the
+// results.  `what` names the tree in the structural-bound error.
+static int read_header(DeviceBvh& b, hipStream_t st, DeviceBvhResult& r, const char* what, std::string& err)
+{
     DCHK(hipEventRecord(b.ev1, st));
     uint32_t h[H_WORDS];
-    DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    DCHK(hipMemcpyAsync(h, b.hdr.p, sizeof(h), hipMemcpyDeviceToHost, st));
     DCHK(hipStreamSynchronize(st));
     DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
     const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
     if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
-    if (h[H_ERR]) { err = std::string("device BVH: ") + what + " failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
+    if (h[H_ERR]) { err = std::string(what) + " failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
     r.n_nodes = h[H_BASE];
     r.sah = __builtin_bit_cast(float, h[H_SAH]);
     r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
     r.depth = h[H_DEPTH];
+    return HJR_OK;
+}
+
+// The BVH2 `ca` describes over n >= 1 triangles -> b.nodes, level by level; then the tree cost, the build's one read of the header
+// and its results.
+static int collapse_and_cost(DeviceBvh& b, const CollapseArgs& ca, uint32_t n, size_t nn, hipStream_t st, DeviceBvhResult& r, const char* what, std::string& err)
+{
+    hipLaunchKernelGGL(collapse_init_kernel, dim3(1), dim3(1), 0, st, n, b.frontier[0].as<Front>(), ca.hdr);
+    uint32_t F;
+    if (const int rc = collapse_levels(b, ca, nn, st, F, err)) return rc;
+    launch_sah(b, b.nodes.as<float4>(), ca.hdr + H_BASE, (uint32_t)nn, nullptr, st);
+    DCHK(hipGetLastError());
+    if (const int rc = read_header(b, st, r, what, err)) return rc;
     if (F > 0 || r.stack_need > hjr::DEVICE_BVH_MAX_STACK) { err = "BVH deeper than the traversal stack"; r.too_deep = true; return HJR_ERR_ARG; }
     return HJR_OK;
 }
@@ -1682,20 +1717,8 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     r = DeviceBvhResult();
     if (!b.ev0) DCHK(hipEventCreate(&b.ev0));
     if (!b.ev1) DCHK(hipEventCreate(&b.ev1));
-    auto fail_alloc = [&] { err = "device BVH: allocation or upload failed"; return HJR_ERR_DEVICE; };
-    // object-space scene, once per hjr_upload_scene
-    if (!b.have_scene) {
-        if (!b.vert.upload(sc.vertices.data(), sc.vertices.size() * 4, st) || !b.norm.upload(sc.normals.data(), sc.normals.size() * 4, st) ||
-            !b.uv.upload(sc.texcoords.data(), sc.texcoords.size() * 4, st) || !b.idx.upload(sc.indices.data(), sc.indices.size() * 4, st) ||
-            !b.mat.upload(sc.material_ids.data(), sc.material_ids.size() * 4, st) || !b.prim_off.upload(sc.prim_offset.data(), sc.prim_offset.size() * 4, st))
-            return fail_alloc();
-        b.have_scene = true;
-    }
-    std::vector<float> xf((size_t)n_inst * 24);
-    for (uint32_t i = 0; i < n_inst; i++) {
-        memcpy(&xf[24 * (size_t)i], M + 12 * (size_t)i, 48);
-        memcpy(&xf[24 * (size_t)i + 12], Mi + 12 * (size_t)i, 48);
-    }
+    if (!upload_scene(b, sc, st)) return fail_alloc(err);
+    const std::vector<float> xf = pack_transforms(M, Mi, n_inst);
     const size_t nn = std::max<uint32_t>(n, 1u);            // node / frontier capacity: a wide node takes at least one BVH2 inner node
     const uint32_t nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
     if (!b.xf.upload(xf.data(), xf.size() * 4, st) || !b.lights.upload(lights, light_floats * 4, st) || !b.hdr.reserve(H_WORDS * 4) ||
@@ -1705,20 +1728,16 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         !b.part.reserve(SCAN_G * 4) || !b.leaf_box.reserve(nn * 32) || !b.inner_box.reserve(nn * 32) || !b.inner_child.reserve(nn * 8) ||
         !b.inner_range.reserve(nn * 8) || !b.parent.reserve(2 * nn * 4) || !b.counter.reserve(nn * 4) || !b.frontier[0].reserve(nn * sizeof(Front)) ||
         !b.frontier[1].reserve(nn * sizeof(Front)) || !b.wide.reserve(nn * (sizeof(Wide) + 4)))
-        return fail_alloc();
+        return fail_alloc(err);
     const bool restructure = opt_rounds > 0 && n >= 2;
     if (restructure && (!b.node_count.reserve(nn * 4) || !b.node_cost.reserve(nn * 4) || !b.leaf_pos.reserve(nn * 4)))
-        return fail_alloc();
-    uint32_t* hdr = (uint32_t*)b.hdr.p;
+        return fail_alloc(err);
+    uint32_t* hdr = b.hdr.as<uint32_t>();
     DCHK(hipEventRecord(b.ev0, st));
     hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
     if (n == 0) { // empty scene: one root with four empty slots (frame.cpp:614-624), one zero triangle record
         float q[28];
-        for (int c = 0; c < 4; c++) {
-            for (int ax = 0; ax < 3; ax++) { q[8 * ax + c] = 1e30f; q[8 * ax + 4 + c] = -1e30f; }
-            const uint32_t e = HJR_LEAF_FLAG;
-            memcpy(&q[24 + c], &e, 4);
-        }
+        for (int c = 0; c < 4; c++) empty_slot(q, c);
         DCHK(hipMemcpyAsync(b.nodes.p, q, sizeof(q), hipMemcpyHostToDevice, st));
         DCHK(hipMemsetAsync(b.tri_geom.p, 0, HJR_TRI_F4 * 16, st));
         DCHK(hipEventRecord(b.ev1, st));
@@ -1727,53 +1746,31 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
         return HJR_OK;
     }
-    FlattenArgs fa;
-    fa.vert = (const float*)b.vert.p; fa.norm = (const float*)b.norm.p; fa.uv = (const float*)b.uv.p; fa.xf = (const float*)b.xf.p;
-    fa.idx = (const uint32_t*)b.idx.p; fa.mat = (const uint32_t*)b.mat.p; fa.prim_off = (const uint32_t*)b.prim_off.p;
-    fa.n = n; fa.n_inst = n_inst;
-    fa.wv = (float*)b.wv.p; fa.shade = (float*)b.tri_shade.p; fa.box = (float*)b.box.p; fa.cent = (float*)b.cent.p;
-    fa.inst = (uint32_t*)b.tri_inst.p; fa.hdr = hdr;
-    hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, fa);
-    uint64_t* keys[2] = { (uint64_t*)b.keys[0].p, (uint64_t*)b.keys[1].p };
-    uint32_t* vals[2] = { (uint32_t*)b.vals[0].p, (uint32_t*)b.vals[1].p };
-    hipLaunchKernelGGL(morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (float*)b.box.p, (const float*)b.cent.p, (const uint32_t*)hdr, keys[0], vals[0]);
+    uint2* child = b.inner_child.as<uint2>();
+    uint32_t *parent = b.parent.as<uint32_t>(), *order = b.vals[0].as<uint32_t>();
+    hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, flatten_args(b, n, n_inst));
+    hipLaunchKernelGGL(morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, b.box.as<float>(), b.cent.as<float>(), hdr, b.keys[0].as<uint64_t>(), order);
     if (const int rc = sort_pairs(b, n, nb, st, err)) return rc;
     // with a restructuring, tri_geom waits for the leaves' new positions
-    hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals[0], (const uint32_t*)nullptr, (const float*)b.wv.p,
-                       (const uint32_t*)b.mat.p, (const float*)b.box.p, restructure ? (float*)nullptr : (float*)b.tri_geom.p, (float*)b.leaf_box.p);
+    hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, order, nullptr, b.wv.as<float>(), b.mat.as<uint32_t>(), b.box.as<float>(),
+                       restructure ? nullptr : b.tri_geom.as<float>(), b.leaf_box.as<float>());
     if (n >= 2) {
-        hipLaunchKernelGGL(karras_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint64_t*)keys[0], (uint2*)b.inner_child.p,
-                           (uint2*)b.inner_range.p, (uint32_t*)b.parent.p);
-        DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
-        hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)b.inner_child.p, (const uint32_t*)b.parent.p,
-                           (uint32_t*)b.counter.p, (const float4*)b.leaf_box.p, (float4*)b.inner_box.p);
+        hipLaunchKernelGGL(karras_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, b.keys[0].as<uint64_t>(), child, b.inner_range.as<uint2>(), parent);
+        if (const int rc = bvh2_boxes(b, n, nullptr, child, parent, st, err)) return rc;
     }
     if (restructure) { // option "device_bvh_opt"
-        TreeletArgs ta;
-        ta.n = (int)n; ta.leaf_max = leaf_max;
-        ta.child = (uint2*)b.inner_child.p; ta.parent = (uint32_t*)b.parent.p; ta.counter = (uint32_t*)b.counter.p;
-        ta.count = (uint32_t*)b.node_count.p; ta.cost = (float*)b.node_cost.p;
-        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p; ta.top = nullptr;
-        for (uint32_t round = 0; round < opt_rounds; round++) {
-            ta.gamma = TREELET << round; // the paper's schedule: the treelet size, doubled every round
-            DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
-            hipLaunchKernelGGL(treelet_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, ta);
-        }
-        hipLaunchKernelGGL(leaf_pos_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)b.inner_child.p, (const uint32_t*)b.parent.p,
-                           (const uint32_t*)b.node_count.p, (uint32_t*)b.leaf_pos.p, hdr);
-        hipLaunchKernelGGL(inner_range_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint2*)b.inner_child.p,
-                           (const uint32_t*)b.node_count.p, (const uint32_t*)b.leaf_pos.p, (uint2*)b.inner_range.p, hdr);
-        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals[0], (const uint32_t*)b.leaf_pos.p,
-                           (const float*)b.wv.p, (const uint32_t*)b.mat.p, (const float*)b.box.p, (float*)b.tri_geom.p, (float*)nullptr);
+        if (const int rc = restructure_bvh2(b, n, leaf_max, opt_rounds, child, parent, nullptr, b.leaf_pos.as<uint32_t>(), b.inner_range.as<uint2>(), st, err)) return rc;
+        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, order, b.leaf_pos.as<uint32_t>(), b.wv.as<float>(), b.mat.as<uint32_t>(),
+                           b.box.as<float>(), b.tri_geom.as<float>(), nullptr);
     }
     DCHK(hipGetLastError());
     CollapseArgs ca;
-    ca.child = (const uint2*)b.inner_child.p; ca.range = (const uint2*)b.inner_range.p;
-    ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
-    ca.leaf_pos = restructure ? (const uint32_t*)b.leaf_pos.p : nullptr;
+    ca.child = child; ca.range = b.inner_range.as<uint2>();
+    ca.leaf_box = b.leaf_box.as<float4>(); ca.inner_box = b.inner_box.as<float4>();
+    ca.leaf_pos = restructure ? b.leaf_pos.as<uint32_t>() : nullptr;
     ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
     ca.top = nullptr; ca.inst_stat = nullptr;
-    return collapse_and_cost(b, ca, n, nn, st, r, "the restructured tree", err);
+    return collapse_and_cost(b, ca, n, nn, st, r, "device BVH: the restructured tree", err);
 }
 
 int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const DevBuf& cur_nodes, const DevBuf& cur_geom,
@@ -1786,53 +1783,30 @@ int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         err = "device BVH refit: no device-built frame data of this scene";
         return HJR_ERR_DEVICE;
     }
-    std::vector<float> xf((size_t)n_inst * 24);
-    for (uint32_t i = 0; i < n_inst; i++) {
-        memcpy(&xf[24 * (size_t)i], M + 12 * (size_t)i, 48);
-        memcpy(&xf[24 * (size_t)i + 12], Mi + 12 * (size_t)i, 48);
-    }
+    const std::vector<float> xf = pack_transforms(M, Mi, n_inst);
     if (!b.xf.upload(xf.data(), xf.size() * 4, st) || !b.lights.upload(lights, light_floats * 4, st) || !b.hdr.reserve(H_WORDS * 4) || !b.nodes.reserve(node_bytes) ||
         !b.tri_geom.reserve(geom_bytes) || !b.tri_shade.reserve((size_t)n * HJR_SHADE_F4 * 16) || !b.tri_inst.reserve((size_t)n * 4) ||
-        !b.parent.reserve((size_t)n_nodes * 4) || !b.counter.reserve((size_t)n_nodes * 4) || !b.part.reserve(SCAN_G * 4)) {
-        err = "device BVH: allocation or upload failed";
-        return HJR_ERR_DEVICE;
-    }
-    uint32_t* hdr = (uint32_t*)b.hdr.p;
-    RefitArgs a;
-    a.f.vert = (const float*)b.vert.p; a.f.norm = (const float*)b.norm.p; a.f.uv = (const float*)b.uv.p; a.f.xf = (const float*)b.xf.p;
-    a.f.idx = (const uint32_t*)b.idx.p; a.f.mat = (const uint32_t*)b.mat.p; a.f.prim_off = (const uint32_t*)b.prim_off.p;
-    a.f.n = n; a.f.n_inst = n_inst;
-    a.f.wv = nullptr; a.f.box = nullptr; a.f.cent = nullptr;
-    a.f.shade = (float*)b.tri_shade.p; a.f.inst = (uint32_t*)b.tri_inst.p; a.f.hdr = hdr;
-    a.n_nodes = n_nodes;
-    a.cur_nodes = (const float4*)cur_nodes.p; a.cur_geom = (const float4*)cur_geom.p;
-    a.nodes = (float4*)b.nodes.p; a.geom = (float4*)b.tri_geom.p;
-    a.parent = (uint32_t*)b.parent.p; a.counter = (uint32_t*)b.counter.p;
+        !b.parent.reserve((size_t)n_nodes * 4) || !b.counter.reserve((size_t)n_nodes * 4) || !b.part.reserve(SCAN_G * 4))
+        return fail_alloc(err);
+    uint32_t* hdr = b.hdr.as<uint32_t>();
+    const float4* refs = cur_nodes.as<float4>() + 6; // only the refs rows and the prim ids of the current frame data are read
+    LeafFlattenArgs fa = { flatten_args(b, n, n_inst), cur_geom.as<float4>(), nullptr, nullptr, b.tri_geom.as<float4>(), nullptr };
+    NodeBoxArgs na = { n, n_nodes, refs, HJR_NODE4_F4, false, b.tri_geom.as<float4>(), b.nodes.as<float4>(), b.parent.as<uint32_t>(), b.counter.as<uint32_t>(), hdr };
     DCHK(hipEventRecord(b.ev0, st));
     hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
     DCHK(hipMemsetAsync(b.parent.p, 0xff, (size_t)n_nodes * 4, st)); // a node no slot refers to has no parent below it
     DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)n_nodes * 4, st));
-    hipLaunchKernelGGL(refit_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
-    hipLaunchKernelGGL(refit_parent_kernel, dim3(blocks_for(n_nodes)), dim3(NT), 0, st, a);
-    hipLaunchKernelGGL(refit_boxes_kernel, dim3(blocks_for(n_nodes)), dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(leaf_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, fa);
+    hipLaunchKernelGGL(node_parent_kernel, dim3(blocks_for(n_nodes)), dim3(NT), 0, st, n_nodes, refs, (uint32_t)HJR_NODE4_F4, n, nullptr, b.parent.as<uint32_t>(), hdr);
+    hipLaunchKernelGGL(node_boxes_kernel, dim3(blocks_for(n_nodes)), dim3(NT), 0, st, na);
     hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, st, hdr + H_BASE, n_nodes);
-    launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, n_nodes, (const uint32_t*)b.counter.p, st);
+    launch_sah(b, b.nodes.as<float4>(), hdr + H_BASE, n_nodes, b.counter.as<uint32_t>(), st);
     DCHK(hipGetLastError());
-    DCHK(hipEventRecord(b.ev1, st));
-    uint32_t h[H_WORDS];
-    DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-    DCHK(hipStreamSynchronize(st)); // the refit's one host wait
-    DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
-    const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
-    if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
-    if (h[H_ERR]) { err = "device BVH refit: the current tree failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
-    r.n_nodes = n_nodes;
-    r.sah = __builtin_bit_cast(float, h[H_SAH]);
+    if (const int rc = read_header(b, st, r, "device BVH refit: the current tree", err)) return rc; // the refit's one host wait
+    r.stack_need = r.depth = 0; // the topology's, which the caller has
     return HJR_OK;
 }
 
-// The topology of option "device_bvh_instances" into b.topo (kernel comment above); the object-space scene is on the device and the
-// build's scratch is reserved.  One host wait; b.topo.ms is its HIP-event time.
 // The skeleton of option "device_bvh_graft" (kernel comment above) from the finished BVH2 of b.topo: the collapse's level loop from the
 // instance roots, into b.nodes as scratch; then the BVH2 is freed.  b.leaf_box / b.inner_box hold the object-space boxes.
 static int build_skeleton(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t leaf_max, bool have_boxes, hipStream_t st, std::string& err)
@@ -1840,60 +1814,39 @@ static int build_skeleton(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t le
     DeviceBvh::Topology& T = b.topo;
     const size_t nn = std::max<uint32_t>(n, 1u);
     const uint32_t k = T.k;
-    uint32_t* hdr = (uint32_t*)b.hdr.p;
-    if (!T.inst_ref.reserve((size_t)k * 4) || !T.inst_stat.reserve((size_t)k * 8) || !T.top_box.reserve((size_t)k * 64)) {
-        err = "device BVH: allocation or upload failed";
-        return HJR_ERR_DEVICE;
-    }
-    if (!have_boxes && n >= 2) { // without treelet rounds the topology build had no use for the object-space node boxes
-        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)T.order.p, (const uint32_t*)nullptr, (const float*)nullptr,
-                           (const uint32_t*)b.mat.p, (const float*)b.box.p, (float*)nullptr, (float*)b.leaf_box.p);
-        DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
-        hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)T.parent.p, (uint32_t*)b.counter.p,
-                           (const float4*)b.leaf_box.p, (float4*)b.inner_box.p);
-    }
+    uint32_t* hdr = b.hdr.as<uint32_t>();
+    if (!T.inst_ref.reserve((size_t)k * 4) || !T.inst_stat.reserve((size_t)k * 8) || !T.top_box.reserve((size_t)k * 64)) return fail_alloc(err);
+    if (!have_boxes && n >= 2) // without treelet rounds the topology build had no use for the object-space node boxes
+        if (const int rc = bvh2_boxes(b, n, T.order.as<uint32_t>(), T.child.as<uint2>(), T.parent.as<uint32_t>(), st, err)) return rc;
     DCHK(hipMemsetAsync(T.inst_stat.p, 0, (size_t)k * 8, st));
-    Front* fr[2] = { (Front*)b.frontier[0].p, (Front*)b.frontier[1].p };
-    Wide* wide = (Wide*)b.wide.p;
-    uint32_t* n_inner = (uint32_t*)((char*)b.wide.p + nn * sizeof(Wide));
-    hipLaunchKernelGGL(skel_init_kernel, dim3(1), dim3(NT), 0, st, n, n_inst, k, leaf_max, (const uint32_t*)T.list.p, (const uint32_t*)T.root.p, (const uint32_t*)T.top.p,
-                       (const uint2*)T.range.p, (const uint32_t*)T.pos.p, fr[0], (uint32_t*)T.inst_ref.p, hdr);
+    hipLaunchKernelGGL(skel_init_kernel, dim3(1), dim3(NT), 0, st, n, n_inst, k, leaf_max, T.list.as<uint32_t>(), T.root.as<uint32_t>(), T.top.as<uint32_t>(),
+                       T.range.as<uint2>(), T.pos.as<uint32_t>(), b.frontier[0].as<Front>(), T.inst_ref.as<uint32_t>(), hdr);
     CollapseArgs ca;
-    ca.child = (const uint2*)T.child.p; ca.range = (const uint2*)T.range.p;
-    ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
-    ca.leaf_pos = (const uint32_t*)T.pos.p;
+    ca.child = T.child.as<uint2>(); ca.range = T.range.as<uint2>();
+    ca.leaf_box = b.leaf_box.as<float4>(); ca.inner_box = b.inner_box.as<float4>();
+    ca.leaf_pos = T.pos.as<uint32_t>();
     ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
     ca.top = nullptr; // nothing under an instance root is a top node
-    ca.inst_stat = (uint32_t*)T.inst_stat.p;
-    const unsigned grid = (unsigned)std::min<size_t>(blocks_for(nn), 1024);
-    uint32_t level = 0, F = 1;
-    while (F > 0 && level < hjr::DEVICE_BVH_MAX_STACK) {
-        for (int q = 0; q < LEVEL_BATCH; q++, level++) {
-            hipLaunchKernelGGL(wide_expand_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Front*)fr[level & 1], wide, n_inner);
-            if (const int rc = scan(n_inner, hdr + H_F, 0u, (uint32_t*)b.part.p, hdr + H_NEXT, st, err)) return rc;
-            hipLaunchKernelGGL(wide_emit_kernel, dim3(grid), dim3(NT), 0, st, ca, (const Wide*)wide, (const uint32_t*)n_inner, fr[(level + 1) & 1], (float4*)b.nodes.p);
-            hipLaunchKernelGGL(level_advance_kernel, dim3(1), dim3(1), 0, st, hdr);
-        }
-        DCHK(hipGetLastError());
-        DCHK(hipMemcpyAsync(&F, hdr + H_F, 4, hipMemcpyDeviceToHost, st));
-        DCHK(hipStreamSynchronize(st));
-    }
-    uint32_t S = 0;
+    ca.inst_stat = T.inst_stat.as<uint32_t>();
+    uint32_t F, S = 0;
+    if (const int rc = collapse_levels(b, ca, nn, st, F, err)) return rc;
     DCHK(hipMemcpyAsync(&S, hdr + H_BASE, 4, hipMemcpyDeviceToHost, st));
     DCHK(hipStreamSynchronize(st));
     T.skel_deep = F > 0;
     T.n_skel = S = std::min<uint32_t>(S, (uint32_t)nn);
     if (!T.skel_refs.reserve(std::max<size_t>(1, (size_t)S * 16)) || !T.skel_parent.reserve(std::max<size_t>(1, (size_t)S * 4)) ||
-        !b.stage.reserve(std::max<size_t>(1, (size_t)S * HJR_NODE4_F4 * 16))) {
-        err = "device BVH: allocation or upload failed";
-        return HJR_ERR_DEVICE;
-    }
+        !b.stage.reserve(std::max<size_t>(1, (size_t)S * HJR_NODE4_F4 * 16)))
+        return fail_alloc(err);
     DCHK(hipMemsetAsync(T.skel_parent.p, 0xff, (size_t)S * 4, st));
-    if (S) hipLaunchKernelGGL(skel_keep_kernel, dim3(blocks_for(S)), dim3(NT), 0, st, S, (const float4*)b.nodes.p, (float4*)T.skel_refs.p, (uint32_t*)T.skel_parent.p, hdr);
+    // what is kept of the S nodes the collapse wrote: the refs rows, and 4 * parent + slot of every node an inner slot refers to
+    if (S) hipLaunchKernelGGL(node_parent_kernel, dim3(blocks_for(S)), dim3(NT), 0, st, S, b.nodes.as<float4>() + 6, (uint32_t)HJR_NODE4_F4, 0u, T.skel_refs.as<float4>(),
+                              T.skel_parent.as<uint32_t>(), hdr);
     DCHK(hipGetLastError());
     return HJR_OK;
 }
 
+// The topology of option "device_bvh_instances" into b.topo (kernel comment above); the object-space scene is on the device and the
+// build's scratch is reserved.  One host wait; b.topo.ms is its HIP-event time.
 static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds, bool graft, const std::vector<uint32_t>& list,
                           hipStream_t st, std::string& err)
 {
@@ -1903,62 +1856,37 @@ static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t le
     const uint32_t k = (uint32_t)list.size(), nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
     if (!T.child.reserve(nn * 8) || !T.range.reserve(nn * 8) || !T.parent.reserve(2 * nn * 4) || !T.pos.reserve(nn * 4) || !T.order.reserve(nn * 4) ||
         !T.top.reserve(nn * 4) || !T.top_ids.reserve((size_t)std::max(k, 1u) * 4) || !T.root.reserve((size_t)std::max(n_inst, 1u) * 4) ||
-        !T.bounds.reserve((size_t)std::max(n_inst, 1u) * 24) || !T.list.upload(list.data(), list.size() * 4, st)) {
-        err = "device BVH: allocation or upload failed";
-        return HJR_ERR_DEVICE;
-    }
+        !T.bounds.reserve((size_t)std::max(n_inst, 1u) * 24) || !T.list.upload(list.data(), list.size() * 4, st))
+        return fail_alloc(err);
     int bits = 0;
     while (bits < 32 && (1ull << bits) < n_inst) bits++;
     const int shift = 63 - bits;
-    uint32_t* hdr = (uint32_t*)b.hdr.p;
-    uint32_t *bmin = (uint32_t*)T.bounds.p, *bmax = bmin + 3 * (size_t)n_inst;
-    uint64_t* keys = (uint64_t*)b.keys[0].p;
-    uint32_t* vals = (uint32_t*)b.vals[0].p;
+    uint32_t* hdr = b.hdr.as<uint32_t>();
+    uint32_t *bmin = T.bounds.as<uint32_t>(), *bmax = bmin + 3 * (size_t)n_inst;
+    uint64_t* keys = b.keys[0].as<uint64_t>();
+    uint32_t *vals = b.vals[0].as<uint32_t>(), *parent = T.parent.as<uint32_t>(), *top = T.top.as<uint32_t>();
+    uint2 *child = T.child.as<uint2>(), *range = T.range.as<uint2>();
     const bool restructure = opt_rounds > 0 && n >= 2;
     DCHK(hipEventRecord(b.ev0, st));
     hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
     DCHK(hipMemsetAsync(bmin, 0xff, (size_t)n_inst * 12, st));
     DCHK(hipMemsetAsync(bmax, 0, (size_t)n_inst * 12, st));
     DCHK(hipMemsetAsync(T.root.p, 0xff, (size_t)n_inst * 4, st));
-    FlattenArgs fa = FlattenArgs();
-    fa.vert = (const float*)b.vert.p; fa.idx = (const uint32_t*)b.idx.p; fa.prim_off = (const uint32_t*)b.prim_off.p;
-    fa.n = n; fa.n_inst = n_inst;
-    fa.box = (float*)b.box.p; fa.cent = (float*)b.cent.p; fa.inst = (uint32_t*)b.tri_inst.p; fa.hdr = hdr; // tri_inst: scratch until the commit's flatten
-    hipLaunchKernelGGL(obj_box_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, fa, bmin, bmax);
-    hipLaunchKernelGGL(obj_morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const float*)b.cent.p, (const uint32_t*)b.tri_inst.p, (const uint32_t*)bmin,
-                       (const uint32_t*)bmax, bits, keys, vals);
+    hipLaunchKernelGGL(obj_box_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, flatten_args(b, n, n_inst), bmin, bmax); // tri_inst: scratch until the commit's flatten
+    hipLaunchKernelGGL(obj_morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, b.cent.as<float>(), b.tri_inst.as<uint32_t>(), bmin, bmax, bits, keys, vals);
     if (const int rc = sort_pairs(b, n, nb, st, err)) return rc;
     DCHK(hipMemcpyAsync(T.order.p, vals, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     if (n >= 2) {
-        hipLaunchKernelGGL(karras_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint64_t*)keys, (uint2*)T.child.p, (uint2*)T.range.p,
-                           (uint32_t*)T.parent.p);
-        hipLaunchKernelGGL(top_flag_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint64_t*)keys, (const uint2*)T.range.p, shift, (uint32_t*)T.top.p);
+        hipLaunchKernelGGL(karras_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, keys, child, range, parent);
+        hipLaunchKernelGGL(top_flag_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, keys, range, shift, top);
     }
-    hipLaunchKernelGGL(inst_root_kernel, dim3(blocks_for(2 * (size_t)n - 1)), dim3(NT), 0, st, (int)n, n_inst, (const uint64_t*)keys, (const uint2*)T.range.p,
-                       (const uint32_t*)T.parent.p, (const uint32_t*)T.top.p, shift, (uint32_t*)T.root.p, hdr);
-    hipLaunchKernelGGL(top_ids_kernel, dim3(1), dim3(NT), 0, st, n - 1, (const uint32_t*)T.top.p, k, (uint32_t*)T.top_ids.p, hdr);
+    hipLaunchKernelGGL(inst_root_kernel, dim3(blocks_for(2 * (size_t)n - 1)), dim3(NT), 0, st, (int)n, n_inst, keys, range, parent, top, shift, T.root.as<uint32_t>(), hdr);
+    hipLaunchKernelGGL(top_ids_kernel, dim3(1), dim3(NT), 0, st, n - 1, top, k, T.top_ids.as<uint32_t>(), hdr);
     if (restructure) { // "device_bvh_opt" rounds on the object-space boxes, inside the instances
-        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (const uint32_t*)vals, (const uint32_t*)nullptr, (const float*)nullptr,
-                           (const uint32_t*)b.mat.p, (const float*)b.box.p, (float*)nullptr, (float*)b.leaf_box.p);
-        DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
-        hipLaunchKernelGGL(boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)T.parent.p, (uint32_t*)b.counter.p,
-                           (const float4*)b.leaf_box.p, (float4*)b.inner_box.p);
-        TreeletArgs ta;
-        ta.n = (int)n; ta.leaf_max = leaf_max;
-        ta.child = (uint2*)T.child.p; ta.parent = (uint32_t*)T.parent.p; ta.counter = (uint32_t*)b.counter.p;
-        ta.count = (uint32_t*)b.node_count.p; ta.cost = (float*)b.node_cost.p;
-        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p; ta.top = (const uint32_t*)T.top.p;
-        for (uint32_t round = 0; round < opt_rounds; round++) {
-            ta.gamma = TREELET << round;
-            DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
-            hipLaunchKernelGGL(treelet_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, ta);
-        }
-        hipLaunchKernelGGL(leaf_pos_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)T.parent.p,
-                           (const uint32_t*)b.node_count.p, (uint32_t*)T.pos.p, hdr);
-        hipLaunchKernelGGL(inner_range_kernel, dim3(blocks_for(n - 1)), dim3(NT), 0, st, (int)n, (const uint2*)T.child.p, (const uint32_t*)b.node_count.p,
-                           (const uint32_t*)T.pos.p, (uint2*)T.range.p, hdr);
+        if (const int rc = bvh2_boxes(b, n, vals, child, parent, st, err)) return rc;
+        if (const int rc = restructure_bvh2(b, n, leaf_max, opt_rounds, child, parent, top, T.pos.as<uint32_t>(), range, st, err)) return rc;
     } else
-        hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, (uint32_t*)T.pos.p);
+        hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, T.pos.as<uint32_t>());
     DCHK(hipGetLastError());
     uint32_t h[H_WORDS];
     const char* failed = "device BVH: the instance topology failed a structural bound (";
@@ -1995,109 +1923,74 @@ int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, cons
     r = DeviceBvhResult();
     if (!b.ev0) DCHK(hipEventCreate(&b.ev0));
     if (!b.ev1) DCHK(hipEventCreate(&b.ev1));
-    auto fail_alloc = [&] { err = "device BVH: allocation or upload failed"; return HJR_ERR_DEVICE; };
-    if (!b.have_scene) {
-        if (!b.vert.upload(sc.vertices.data(), sc.vertices.size() * 4, st) || !b.norm.upload(sc.normals.data(), sc.normals.size() * 4, st) ||
-            !b.uv.upload(sc.texcoords.data(), sc.texcoords.size() * 4, st) || !b.idx.upload(sc.indices.data(), sc.indices.size() * 4, st) ||
-            !b.mat.upload(sc.material_ids.data(), sc.material_ids.size() * 4, st) || !b.prim_off.upload(sc.prim_offset.data(), sc.prim_offset.size() * 4, st))
-            return fail_alloc();
-        b.have_scene = true;
-        b.topo.valid = false;
-    }
-    std::vector<float> xf((size_t)n_inst * 24);
-    for (uint32_t i = 0; i < n_inst; i++) {
-        memcpy(&xf[24 * (size_t)i], M + 12 * (size_t)i, 48);
-        memcpy(&xf[24 * (size_t)i + 12], Mi + 12 * (size_t)i, 48);
-    }
+    if (!upload_scene(b, sc, st)) return fail_alloc(err);
+    const std::vector<float> xf = pack_transforms(M, Mi, n_inst);
     const size_t nn = n;
     const uint32_t nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
     if (!b.xf.upload(xf.data(), xf.size() * 4, st) || !b.lights.upload(lights, light_floats * 4, st) || !b.hdr.reserve(H_WORDS * 4) ||
         !b.nodes.reserve(nn * HJR_NODE4_F4 * 16) || !b.tri_geom.reserve(nn * HJR_TRI_F4 * 16) || !b.tri_shade.reserve(nn * HJR_SHADE_F4 * 16) ||
         !b.tri_inst.reserve(nn * 4) || !b.part.reserve(SCAN_G * 4) || !b.leaf_box.reserve(nn * 32) || !b.inner_box.reserve(nn * 32) || !b.counter.reserve(nn * 4) ||
         !b.frontier[0].reserve(nn * sizeof(Front)) || !b.frontier[1].reserve(nn * sizeof(Front)) || !b.wide.reserve(nn * (sizeof(Wide) + 4)))
-        return fail_alloc();
+        return fail_alloc(err);
     DeviceBvh::Topology& T = b.topo;
     if (!T.valid || T.tag != tag || T.k != list.size() || T.graft != graft) {
         if (!b.box.reserve(nn * 32) || !b.cent.reserve(nn * 16) || !b.keys[0].reserve(nn * 8) || !b.keys[1].reserve(nn * 8) || !b.vals[0].reserve(nn * 4) ||
             !b.vals[1].reserve(nn * 4) || !b.hist.reserve(std::max<size_t>(1, (size_t)nb * 256 * 4)) || !b.node_count.reserve(nn * 4) || !b.node_cost.reserve(nn * 4))
-            return fail_alloc();
+            return fail_alloc(err);
         if (const int rc = build_topology(b, n, n_inst, leaf_max, opt_rounds, graft, list, st, err)) return rc;
         T.tag = tag;
     }
     const uint32_t k = T.k;
-    uint32_t* hdr = (uint32_t*)b.hdr.p;
+    uint32_t* hdr = b.hdr.as<uint32_t>();
     if (graft && T.skel_deep) return ordinary(); // an instance tree deeper than the traversal stack
-    InstArgs a;
-    a.f = FlattenArgs();
-    a.f.vert = (const float*)b.vert.p; a.f.norm = (const float*)b.norm.p; a.f.uv = (const float*)b.uv.p; a.f.xf = (const float*)b.xf.p;
-    a.f.idx = (const uint32_t*)b.idx.p; a.f.mat = (const uint32_t*)b.mat.p; a.f.prim_off = (const uint32_t*)b.prim_off.p;
-    a.f.n = n; a.f.n_inst = n_inst;
-    a.f.shade = (float*)b.tri_shade.p; a.f.inst = (uint32_t*)b.tri_inst.p; a.f.hdr = hdr;
-    a.order = (const uint32_t*)T.order.p; a.pos = (const uint32_t*)T.pos.p; a.top = (const uint32_t*)T.top.p; a.parent = (const uint32_t*)T.parent.p;
-    a.child = (const uint2*)T.child.p; a.counter = (uint32_t*)b.counter.p;
-    a.geom = (float4*)b.tri_geom.p; a.leaf_box = (float4*)b.leaf_box.p; a.inner_box = (float4*)b.inner_box.p;
+    // under device_bvh_graft no leaf boxes: the skeleton's boxes come from tri_geom
+    LeafFlattenArgs fa = { flatten_args(b, n, n_inst), nullptr, T.order.as<uint32_t>(), T.pos.as<uint32_t>(), b.tri_geom.as<float4>(),
+                           graft ? nullptr : b.leaf_box.as<float4>() };
     if (graft) { // flatten, skeleton boxes, top tree, placement, cost: one host wait
         const uint32_t S = T.n_skel;
-        a.order = (const uint32_t*)T.order.p; a.pos = (const uint32_t*)T.pos.p; a.top = nullptr; a.parent = nullptr; a.child = nullptr;
-        a.leaf_box = nullptr; a.inner_box = nullptr;
-        RefitArgs ra;
-        ra.f = a.f;
-        ra.n_nodes = S;
-        ra.cur_nodes = nullptr; ra.cur_geom = nullptr;
-        ra.nodes = (float4*)b.stage.p; ra.geom = (float4*)b.tri_geom.p;
-        ra.parent = (uint32_t*)T.skel_parent.p; ra.counter = (uint32_t*)b.counter.p;
+        NodeBoxArgs na = { n, S, T.skel_refs.as<float4>(), 1u, true, b.tri_geom.as<float4>(), b.stage.as<float4>(), T.skel_parent.as<uint32_t>(), b.counter.as<uint32_t>(), hdr };
         GraftTopArgs ga;
         ga.n = n; ga.k = k; ga.n_skel = S; ga.cap = (uint32_t)nn;
-        ga.inst_ref = (const uint32_t*)T.inst_ref.p; ga.inst_stat = (const uint32_t*)T.inst_stat.p;
-        ga.stage = (const float4*)b.stage.p; ga.geom = (const float4*)b.tri_geom.p;
-        ga.box = (float4*)T.top_box.p; ga.nodes = (float4*)b.nodes.p; ga.hdr = hdr;
+        ga.inst_ref = T.inst_ref.as<uint32_t>(); ga.inst_stat = T.inst_stat.as<uint32_t>();
+        ga.stage = b.stage.as<float4>(); ga.geom = b.tri_geom.as<float4>();
+        ga.box = T.top_box.as<float4>(); ga.nodes = b.nodes.as<float4>(); ga.hdr = hdr;
         DCHK(hipEventRecord(b.ev0, st));
         hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
         if (S) DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)S * 4, st));
-        hipLaunchKernelGGL(inst_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
-        if (S) hipLaunchKernelGGL(graft_boxes_kernel, dim3(blocks_for(S)), dim3(NT), 0, st, ra, (const float4*)T.skel_refs.p);
+        hipLaunchKernelGGL(leaf_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, fa);
+        if (S) hipLaunchKernelGGL(node_boxes_kernel, dim3(blocks_for(S)), dim3(NT), 0, st, na);
         hipLaunchKernelGGL(graft_top_kernel, dim3(1), dim3(NT), 0, st, ga);
-        if (S) hipLaunchKernelGGL(graft_place_kernel, dim3(blocks_for((size_t)S * HJR_NODE4_F4)), dim3(NT), 0, st, S, (uint32_t)nn, (const float4*)b.stage.p,
-                                  (const uint32_t*)b.counter.p, (float4*)b.nodes.p, hdr);
-        launch_sah(b, (const float4*)b.nodes.p, hdr + H_BASE, (uint32_t)nn, nullptr, st);
+        if (S) hipLaunchKernelGGL(graft_place_kernel, dim3(blocks_for((size_t)S * HJR_NODE4_F4)), dim3(NT), 0, st, S, (uint32_t)nn, b.stage.as<float4>(),
+                                  b.counter.as<uint32_t>(), b.nodes.as<float4>(), hdr);
+        launch_sah(b, b.nodes.as<float4>(), hdr + H_BASE, (uint32_t)nn, nullptr, st);
         DCHK(hipGetLastError());
-        DCHK(hipEventRecord(b.ev1, st));
-        uint32_t h[H_WORDS];
-        DCHK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, st));
-        DCHK(hipStreamSynchronize(st));
-        DCHK(hipEventElapsedTime(&r.build_ms, b.ev0, b.ev1));
-        const float smax_v = __builtin_bit_cast(float, h[H_SMAX]);
-        if (!(smax_v < 1e30f)) { err = "non-finite vertex after transform"; return HJR_ERR_ARG; }
-        if (h[H_ERR]) { err = "device BVH: the grafted instance tree failed a structural bound (" + std::to_string(h[H_ERR]) + ")"; return HJR_ERR_DEVICE; }
-        r.n_nodes = h[H_BASE];
-        r.sah = __builtin_bit_cast(float, h[H_SAH]);
-        r.stack_need = std::max<uint32_t>(h[H_WORST], 1u) + 1;
-        r.depth = h[H_DEPTH];
+        if (const int rc = read_header(b, st, r, "device BVH: the grafted instance tree", err)) return rc;
         if (r.stack_need > hjr::DEVICE_BVH_MAX_STACK) return ordinary(); // a chain-shaped top tree (nested instances)
         r.instances = k;
         return HJR_OK;
     }
+    InstArgs a = { n, T.top.as<uint32_t>(), T.parent.as<uint32_t>(), T.child.as<uint2>(), b.counter.as<uint32_t>(), hdr, b.leaf_box.as<float4>(), b.inner_box.as<float4>() };
     DCHK(hipEventRecord(b.ev0, st));
     hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
     if (n >= 2) DCHK(hipMemsetAsync(b.counter.p, 0, (size_t)(n - 1) * 4, st));
-    hipLaunchKernelGGL(inst_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(leaf_flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, fa);
     hipLaunchKernelGGL(inst_boxes_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, a);
     if (k >= 2) {
         TopArgs ta;
         ta.n = n; ta.n_inst = n_inst; ta.k = k;
-        ta.list = (const uint32_t*)T.list.p; ta.root = (const uint32_t*)T.root.p; ta.top = (const uint32_t*)T.top.p; ta.top_ids = (const uint32_t*)T.top_ids.p;
-        ta.child = (uint2*)T.child.p; ta.range = (uint2*)T.range.p; ta.parent = (uint32_t*)T.parent.p;
-        ta.leaf_box = (const float4*)b.leaf_box.p; ta.inner_box = (float4*)b.inner_box.p; ta.hdr = hdr;
+        ta.list = T.list.as<uint32_t>(); ta.root = T.root.as<uint32_t>(); ta.top = T.top.as<uint32_t>(); ta.top_ids = T.top_ids.as<uint32_t>();
+        ta.child = T.child.as<uint2>(); ta.range = T.range.as<uint2>(); ta.parent = T.parent.as<uint32_t>();
+        ta.leaf_box = b.leaf_box.as<float4>(); ta.inner_box = b.inner_box.as<float4>(); ta.hdr = hdr;
         hipLaunchKernelGGL(inst_top_kernel, dim3(1), dim3(NT), 0, st, ta);
     }
     DCHK(hipGetLastError());
     CollapseArgs ca;
-    ca.child = (const uint2*)T.child.p; ca.range = (const uint2*)T.range.p;
-    ca.leaf_box = (const float4*)b.leaf_box.p; ca.inner_box = (const float4*)b.inner_box.p;
-    ca.leaf_pos = (const uint32_t*)T.pos.p;
+    ca.child = T.child.as<uint2>(); ca.range = T.range.as<uint2>();
+    ca.leaf_box = b.leaf_box.as<float4>(); ca.inner_box = b.inner_box.as<float4>();
+    ca.leaf_pos = T.pos.as<uint32_t>();
     ca.leaf_max = leaf_max; ca.cap = (uint32_t)nn; ca.hdr = hdr;
-    ca.top = (const uint32_t*)T.top.p; ca.inst_stat = nullptr;
-    const int rc = collapse_and_cost(b, ca, n, nn, st, r, "the instance tree", err);
+    ca.top = T.top.as<uint32_t>(); ca.inst_stat = nullptr;
+    const int rc = collapse_and_cost(b, ca, n, nn, st, r, "device BVH: the instance tree", err);
     if (rc != HJR_OK && r.too_deep) return ordinary(); // a chain-shaped top tree (nested instances): the Morton tree over all triangles
     if (rc == HJR_OK) r.instances = k;
     return rc;
