@@ -134,8 +134,13 @@ class StatsV3(StatsV2):
 
 
 class StatsV4(StatsV3):
-    """hjr_stats with the instance-tree fields appended after `StatsV3` (option "device_bvh_instances").  Device.stats() uses this one."""
+    """hjr_stats with the instance-tree fields appended after `StatsV3` (option "device_bvh_instances")."""
     _fields_ = [("bvh_instances", C.c_uint32), ("bvh_topology_ms", C.c_float)]
+
+
+class StatsV5(StatsV4):
+    """hjr_stats with the firefly-clamp counter appended after `StatsV4` (option "firefly_clamp").  Device.stats() uses this one."""
+    _fields_ = [("firefly_clamped", C.c_uint64)]
 
 
 class Adaptive(_Sized):
@@ -673,7 +678,7 @@ class Device:
         return out
 
     def stats(self):
-        st = StatsV4()
+        st = StatsV5()
         _check(lib().hjr_get_stats(self._h, C.byref(st)), "hjr_get_stats")
         return st.as_dict()
 

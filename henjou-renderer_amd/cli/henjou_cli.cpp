@@ -69,6 +69,13 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
         fprintf(stderr, "henjou_cli: \"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history\n");
         return 1;
     }
+    // "firefly_clamp" (stored in bits 16..22 of device_bvh_opt) acts on whole-frame renders only, as in hjr_render_file; every rank clamps
+    // its own pixels (the rule is per pixel), so the gathered frame is the single-GPU one
+    const int firefly = (opt.device_bvh_opt >> 16) & 0x7f;
+    if (firefly && (opt.passes > 1 || opt.noise_threshold > 0.0f)) {
+        fprintf(stderr, "henjou_cli: \"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only\n");
+        return 1;
+    }
     // Image Scale Setting (renderer.h:1089-1099): DenoiseUpScale2X renders at half the output size, as hjr_render_file does
     const uint32_t W = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_width / 2u : opt.image_width;
     const uint32_t H = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_height / 2u : opt.image_height;
@@ -88,6 +95,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     if (opt.device_bvh_opt & 0x200) HJRX(hjr_set_option(ctx, "device_bvh_graft", 1)); // key "device_bvh_graft": bit 9
     if (rank == 0 && with_var) HJRX(hjr_set_option(ctx, "denoise_variance", 1)); // rank 0 filters
     if (rank == 0 && temporal) HJRX(hjr_set_option(ctx, "denoise_temporal", 1));
+    if (firefly) HJRX(hjr_set_option(ctx, "firefly_clamp", firefly));
     HJRX(hjr_upload_scene(ctx, &view));
     // "noise_threshold": each rank stops its own converged tiles between the sample passes (the rule does not depend on the rank); the one
     // gather per frame is unchanged.  A rank without tiles has nothing to adapt.

@@ -223,6 +223,72 @@ __global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P, floa
     }
 }
 
+// ---- firefly clamp (option "firefly_clamp", DESIGN.md §4 rule 9; the rule is stated in include/henjou_hip.h).  Runs BEHIND
+// hjr_finalize_kernel<false, false, VAR> on a one-shot frame of m = spp / chunk_spp >= 4 full chunks: the plain frame, its albedo, normal and
+// variance stand as that kernel wrote them (the summation stays written once, there), and this kernel rewrites the COLOUR of exactly the pixels
+// that have a scaled chunk, so every other pixel keeps the plain frame's bits by construction.  What it adds is a different sum: every chunk
+// whose y = (c.x + c.y) + c.z exceeds kappa x the lower median of the pixel's full chunks (+ eps x granule) is scaled down to that limit.
+// One lane per pixel of an owned tile, whole waves per tile (n_slots and the grid stride are multiples of 64).  Stream 1 puts the y of the
+// full chunks into the lane's LDS column (ys[k * BLOCK]: conflict-free, at most 64 x BLOCK floats; no per-lane array, no scratch) and keeps
+// their maximum; the median is the y of rank (m - 1) / 2 in the order (y, k), found by counting, O(m^2) LDS reads; stream 2, entered only by
+// waves with a lane over its limit, reads the colour sums again (the pixel's 16 m bytes were read a moment ago: L2) and adds them scaled, in
+// chunk order from +0.0f.  The scaled (pixel, chunk) pairs are counted per lane, added over the wave, one integer atomic per wave.
+// fp32 as written, correctly rounded divide, no contraction (this translation unit's flags): numpy float32 restates it bit for bit.
+template <uint32_t BLOCK>
+__global__ void __launch_bounds__(BLOCK) hjr_firefly_kernel(const KParams P, const float kappa, unsigned long long* __restrict__ n_clamped)
+{
+    float* const ys = reinterpret_cast<float*>(hjr_smem) + threadIdx.x;
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    const uint32_t g = P.chunk_spp, m = P.spp / g, r = P.spp - m * g; // full chunks, samples of the partial last chunk (chunk m, if r > 0)
+    const uint32_t want = (m - 1u) / 2u;                              // rank of the lower median
+    const float inv = 1.0f / (float)P.spp;
+    uint32_t n_scaled = 0u;
+    for (size_t sl = (size_t)blockIdx.x * BLOCK + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * BLOCK) {
+        uint32_t x, y;
+        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y);
+        float lim = 0.0f, lim_r = 0.0f;
+        bool over = false;
+        if (inside) {
+            float y_max = -INFINITY;
+            for (uint32_t k = 0; k < m; k++) {
+                const float4 v = P.part_color[(size_t)k * n_slots + sl];
+                const float yk = (v.x + v.y) + v.z;
+                ys[k * BLOCK] = yk;
+                y_max = fmaxf(y_max, yk);
+            }
+            float med = 0.0f;
+            for (uint32_t k = 0; k < m; k++) {
+                const float yk = ys[k * BLOCK];
+                uint32_t below = 0u;
+                for (uint32_t j = 0; j < m; j++) { const float yj = ys[j * BLOCK]; below += (yj < yk || (yj == yk && j < k)) ? 1u : 0u; }
+                if (below == want) med = yk;
+            }
+            lim = kappa * med + HJR_FIREFLY_EPS * (float)g;
+            over = y_max > lim;
+            if (r) {
+                lim_r = lim * ((float)r / (float)g);
+                const float4 v = P.part_color[(size_t)m * n_slots + sl];
+                over = over || (v.x + v.y) + v.z > lim_r;
+            }
+        }
+        if (!__any(over)) continue; // (wave-uniform)
+        if (over) {
+            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            for (uint32_t k = 0; k < P.n_chunks; k++) {
+                const float4 v = P.part_color[(size_t)k * n_slots + sl];
+                const float yk = (v.x + v.y) + v.z, L = k < m ? lim : lim_r;
+                const bool scale = yk > L;
+                const float s = scale ? L / yk : 1.0f;
+                a.x = a.x + v.x * s; a.y = a.y + v.y * s; a.z = a.z + v.z * s;
+                n_scaled += scale ? 1u : 0u;
+            }
+            P.aov_color[P.packed ? sl : (size_t)y * P.width + x] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
+        }
+    }
+    for (int k = 32; k >= 1; k >>= 1) n_scaled += (uint32_t)__shfl_xor((int)n_scaled, k, 64);
+    if ((threadIdx.x & 63u) == 0u && n_scaled) atomicAdd(n_clamped, (unsigned long long)n_scaled);
+}
+
 // The launch's tile list without the stopped tiles: a STABLE compaction of ad_src (the cost order hjr_order_tiles_kernel /
 // hjr_cost_scatter_kernel just produced, or the plain round-robin order when there is none), so the expensive-first order survives and the
 // result is the same for the same input.  At most 129 600 tiles (4K): one workgroup walks the list in steps of 1024 with a ballot per wave

@@ -485,6 +485,11 @@ static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, Pass
     }
     if (p->spp == 0) { set_error("hjr_render: width, height and spp must be positive"); return HJR_ERR_ARG; }
     if (p->sample_begin == 0 && p->sample_end == p->spp) return HJR_OK; // the whole frame, through the same path
+    if (c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0) > 0) { // the rule needs every chunk sum of a pixel; a progressive frame keeps running sums only
+        set_error("hjr_render: option \"firefly_clamp\" takes whole-frame renders only: sample pass [" + std::to_string(p->sample_begin) + ", " + std::to_string(p->sample_end) +
+                  ") of " + std::to_string(p->spp) + " spp refused");
+        return HJR_ERR_ARG;
+    }
     const uint32_t g = hjr_chunk_spp(p->spp);
     if (p->sample_begin >= p->sample_end || p->sample_end > p->spp) {
         set_error("hjr_render: sample pass [" + std::to_string(p->sample_begin) + ", " + std::to_string(p->sample_end) + ") is not a range inside [0, spp = " + std::to_string(p->spp) + "]");
@@ -802,6 +807,22 @@ static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, KParams& kp, bool ada
     return HJR_OK;
 }
 
+// Option "firefly_clamp" (hjr_firefly_kernel, DESIGN.md §4 rule 9), behind finalize_chunks on a one-shot frame: the colour of the pixels with a
+// chunk over their limit is rewritten.  With the option off, or a frame of fewer than 4 full chunks, nothing is launched.
+static int firefly_clamp(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, const KParams& kp, hipStream_t st)
+{
+    constexpr uint32_t FB = 128; // lanes per workgroup: 64 chunks x 128 lanes x 4 bytes = 32 KiB of LDS at most
+    const int kappa = c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0);
+    const uint32_t m = p->spp / g.chunk_spp;
+    const size_t n_slots = (size_t)g.owned * 64u;
+    if (kappa <= 0 || g.pr.pass || g.n_chunks < 2 || m < 4 || n_slots == 0) return HJR_OK;
+    const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + FB - 1) / FB, (size_t)c->n_cus * 16));
+    hipLaunchKernelGGL(hjr_firefly_kernel<FB>, dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kp, (float)kappa,
+                       (unsigned long long*)((char*)c->d_work.p + WorkArea::FIREFLY));
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+
 // pr: check_pass of this call, made before the caller enqueued anything
 // d_var: the variance AOV (one float per pixel) or null
 static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st)
@@ -824,6 +845,7 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, voi
         if ((rc = launch_render(c, p, g, kp, st)) != HJR_OK) return rc;
     }
     if ((rc = finalize_chunks(c, g, kp, adaptive, (float*)d_var, st)) != HJR_OK) return rc;
+    if ((rc = firefly_clamp(c, p, g, kp, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
     if (pr.pass && c->opt.get(hjr::OPT_VERBOSE, 0))
@@ -891,6 +913,11 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
     uint64_t* dst = &c->stats.samples;
     for (int i = 0; i < 10; i++) dst[i] = h[i];
     c->stats.stack_overflow_pushes = h[10];
+    { // option "firefly_clamp": the work area is zeroed before every launch, so a launch on which the rule did not act reads 0
+        unsigned long long n = 0;
+        HIPCHK(hipMemcpy(&n, (char*)c->d_work.p + WorkArea::FIREFLY, sizeof(n), hipMemcpyDeviceToHost));
+        c->stats.firefly_clamped = n;
+    }
     {
         unsigned long long nl[1 + HJR_NAN_LIST];
         HIPCHK(hipMemcpy(nl, (char*)c->d_work.p + WorkArea::NAN_LIST, sizeof(nl), hipMemcpyDeviceToHost));

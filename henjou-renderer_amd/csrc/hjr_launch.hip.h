@@ -30,7 +30,8 @@ struct WorkArea {
     static constexpr size_t TILE_COUNT = DIAG + 20 * 8;          // 8 uint32 tile-class counters (hjr_aux.hip.h)
     static constexpr size_t COST_HIST = TILE_COUNT + 32;         // 128 uint32: cost histogram and bucket cursors (hjr_aux.hip.h)
     static constexpr size_t NAN_LIST = COST_HIST + 512;          // uint64 count, then HJR_NAN_LIST located samples
-    static constexpr size_t BYTES = NAN_LIST + (1 + HJR_NAN_LIST) * 8;
+    static constexpr size_t FIREFLY = NAN_LIST + (1 + HJR_NAN_LIST) * 8; // uint64: (pixel, chunk) pairs scaled by hjr_firefly_kernel (hjr_aux.hip.h)
+    static constexpr size_t BYTES = FIREFLY + 8;
 };
 
 struct hjr_ctx {

@@ -166,6 +166,13 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 if (!(o.device_bvh_opt & 0x100)) throw JsonError("Henjou_HIP.device_bvh_graft needs \"device_bvh_instances\": true");
                 if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x200;
             }
+            // firefly_clamp: kappa of the firefly clamp on whole-frame renders (option "firefly_clamp"), bits 16..22 of device_bvh_opt, the
+            // section's spare bits: the struct does not grow for it and the readers of the BVH bits mask the field
+            if (const Json* v = h->find("firefly_clamp")) {
+                const double n = v->is_number() ? v->as_number() : -1.0;
+                if (!(n >= 0 && n <= 64) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.firefly_clamp must be an integer in [0, 64]");
+                o.device_bvh_opt |= (int32_t)n << 16;
+            }
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
             if (const Json* v = h->find("passes")) {
                 const double n = v->is_number() ? v->as_number() : -1.0;

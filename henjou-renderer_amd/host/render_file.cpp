@@ -53,6 +53,12 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
         set_error("hjr_render_file: \"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history");
         return HJR_ERR_ARG;
     }
+    // "firefly_clamp" (stored in bits 16..22 of device_bvh_opt) acts on whole-frame renders only
+    const int firefly = (opt.device_bvh_opt >> 16) & 0x7f;
+    if (firefly && (opt.passes > 1 || opt.noise_threshold > 0.0f)) {
+        set_error("hjr_render_file: \"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only");
+        return HJR_ERR_ARG;
+    }
     hjr_scene* scene = nullptr;
     rc = hjr_scene_load_gltf(opt.gltf_path, opt.gltf_name, &opt, &scene);
     if (rc != HJR_OK) return rc;
@@ -71,6 +77,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (opt.device_bvh_opt & 0x200) (void)hjr_set_option(ctx, "device_bvh_graft", 1); // key "device_bvh_graft": bit 9
     if (opt.denoise_variance && opt.render_mode != HJR_MODE_DEFAULT) (void)hjr_set_option(ctx, "denoise_variance", 1); // (Default mode has no filter)
     if (temporal) (void)hjr_set_option(ctx, "denoise_temporal", 1);
+    if (firefly) (void)hjr_set_option(ctx, "firefly_clamp", firefly);
     const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes
     rc = hjr_upload_scene(ctx, &view);
     if (rc == HJR_OK && adaptive) {

@@ -142,7 +142,8 @@ typedef struct hjr_render_option {
                                   * 1 + N: that and option "device_bvh_refit" N (key "device_bvh_refit": N; the struct does not grow for it) */
     int32_t device_bvh_opt;      /* default 0; low 8 bits: 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt");
                                   * bit 8: key "device_bvh_instances", bit 9: key "device_bvh_graft" (options of the same names; the
-                                  * struct does not grow for them) */
+                                  * struct does not grow for them); bits 16..22: key "firefly_clamp" 0..64 (option of the same name; the
+                                  * field is the section's spare bits, the key has nothing to do with the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
     float noise_threshold;       /* default 0 (off); > 0: hjr_render_file / henjou_cli set hjr_adaptive.noise_threshold, render each frame in
@@ -256,6 +257,31 @@ typedef struct hjr_adaptive_state {
  * HJR_ERR_STATE and enqueues nothing. */
 #define HJR_VARIANCE_UNKNOWN 1e30f
 
+/* ---- Firefly clamp: a robust per-pixel mean from the chunk sums (option "firefly_clamp" = kappa; DESIGN.md §4 rule 9) -------------------
+ * Opt-in and BIASED: it removes energy where rare paths carry it (DESIGN.md gives the measured figures).  Off (0, the default) every call
+ * is the call it always was, bit for bit, and launches the same kernels.  With kappa in 1..64 (4 is the recommended value) every
+ * WHOLE-FRAME render (hjr_render[_var], hjr_render_device[_var], hjr_render_denoised with sample_end == 0 or [0, spp)) computes the colour
+ * AOV as follows, per pixel, fp32 in the written order, no contraction, correctly rounded divide:
+ *     g = hjr_sample_granule(spp) ;  m = spp / g (the full chunks) ;  r = spp - m * g (samples of the partial last chunk, if any) ;
+ *     c_k = chunk k's colour sum as stored ;  y_k = (c_k.x + c_k.y) + c_k.z ;
+ *  1. the rule ACTS iff kappa > 0 and m >= 4; otherwise the frame is the plain frame, bit for bit (every frame of at most 8 spp has no
+ *     chunk sums at all, and hjr_sample_granule(spp) = spp there gives m = 1);
+ *  2. med = the lower median of y_0 .. y_{m-1}: the value of rank (m - 1) / 2 (integer division) in ascending order; the partial chunk
+ *     is not among them;
+ *  3. lim = (float)kappa * med + HJR_FIREFLY_EPS * (float)g ;
+ *  4. for the partial chunk  lim_r = lim * ((float)r / (float)g) ;
+ *  5. in chunk order from +0.0f:  s = (y_k > L) ? L / y_k : 1.0f  with L = lim for a full chunk, lim_r for the partial one;
+ *     a.c = a.c + c_k.c * s  for c = x, y, z ;
+ *  6. out = a * (1.0f / (float)spp), alpha 1.
+ * c * 1.0f is exact, so a pixel none of whose chunks is scaled keeps the plain frame's bits.  Albedo, normal and the variance AOV are
+ * untouched: they have the bits of the same call with the option off, and the variance stays the statistic of the RAW chunk sums (it
+ * describes the samples, not the clamped mean).  The rule is per pixel and does not depend on rank, GPU count, kernel family or layout:
+ * HJR_FLAG_PACKED, HJR_FLAG_ZERO_UNOWNED and sharded launches behave as for the plain frame, and N ranks give the one-rank frame.
+ * hjr_stats.firefly_clamped counts the scaled (pixel, chunk) pairs of the launch.
+ * The rule needs all chunk sums of a pixel and a progressive frame keeps running sums only: on a context with the option on, a sample
+ * pass that is not the whole range [0, spp) is HJR_ERR_ARG (the error names the option); nothing is enqueued or written. */
+#define HJR_FIREFLY_EPS 1e-3f    /* keeps the limit of a pixel whose median chunk is black above 0 */
+
 typedef struct hjr_stats {
     uint32_t struct_size;        /* sizeof(hjr_stats) of the caller (HJR_INIT) */
     uint32_t _pad0;
@@ -284,6 +310,7 @@ typedef struct hjr_stats {
                                   * 0 = an ordinary build or host-built data */
     float    bvh_topology_ms;    /* HIP-event time of the last per-instance topology build of that option; the commits that reuse the
                                   * topology leave it as it is */
+    uint64_t firefly_clamped;    /* option "firefly_clamp": (pixel, chunk) pairs the last whole-frame launch scaled down; 0 when the rule did not act */
 } hjr_stats;
 
 typedef struct hjr_scene hjr_scene; /* owning, host side (SceneData + animations) */
@@ -534,6 +561,10 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  advances hjr_params.frame between frames: the same frame number twice blends identical samples and the
                                  propagated variance then understates.  world_size > 1 or HJR_FLAG_PACKED is HJR_ERR_ARG with it (a sharded
                                  frame goes through hjr_denoise_shards_device, which honours both options); HJR_MODE_DEFAULT ignores it.  Setting it (any value) drops the history.  0 (default): today's call, bit for bit
+   "firefly_clamp"  0..64        kappa of the firefly clamp (above, "Firefly clamp"): whole-frame renders scale every chunk sum of a pixel that
+                                 exceeds kappa x the lower median of the pixel's full chunks down to that limit.  Biased, opt-in; 4 is the
+                                 recommended value.  Sample passes other than [0, spp) are HJR_ERR_ARG with it.  0 (default): today's call,
+                                 bit for bit, the same kernels
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
@@ -546,6 +577,9 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name; "denoise_temporal": true
  * of that section is stored as hjr_render_option.denoise_variance = 2 and sets both options (refused together with "noise_threshold" > 0:
  * an adaptive frame that stops early never reaches the pass that advances the history).
+ * "firefly_clamp": N (integer 0..64) of that section is stored in bits 16..22 of hjr_render_option.device_bvh_opt (the struct does not grow
+ * for it; readers of the BVH bits mask the field as before) and sets the option of that name, single-GPU and --devices N; refused together
+ * with "passes" > 1 or "noise_threshold" > 0: the rule needs every chunk sum of a pixel and a frame in sample passes keeps running sums only.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
