@@ -117,7 +117,7 @@ class Stats(_Sized):
     def as_dict(self):
         names = [n for k in reversed(type(self).__mro__) for n, _ in getattr(k, "_fields_", [])]
         d = {n: (float(getattr(self, n)) if n in ("last_kernel_ms", "frame_build_ms", "bvh_sah", "bvh_topology_ms") else int(getattr(self, n)))
-             for n in names if n not in ("struct_size", "_pad0", "nan_where")}
+             for n in names if n not in ("struct_size", "_pad0", "_pad1", "nan_where")}
         d["nan_where"] = [tuple(int(v) for v in self.nan_where[i]) for i in range(int(self.nan_located))]  # (x, y, sample)
         return d
 
@@ -139,8 +139,13 @@ class StatsV4(StatsV3):
 
 
 class StatsV5(StatsV4):
-    """hjr_stats with the firefly-clamp counter appended after `StatsV4` (option "firefly_clamp").  Device.stats() uses this one."""
+    """hjr_stats with the firefly-clamp counter appended after `StatsV4` (option "firefly_clamp")."""
     _fields_ = [("firefly_clamped", C.c_uint64)]
+
+
+class StatsV6(StatsV5):
+    """hjr_stats with the work-item length of the last launch appended after `StatsV5` (option "item_chunks").  Device.stats() uses this one."""
+    _fields_ = [("item_chunks", C.c_uint32), ("_pad1", C.c_uint32)]
 
 
 class Adaptive(_Sized):
@@ -678,7 +683,7 @@ class Device:
         return out
 
     def stats(self):
-        st = StatsV5()
+        st = StatsV6()
         _check(lib().hjr_get_stats(self._h, C.byref(st)), "hjr_get_stats")
         return st.as_dict()
 

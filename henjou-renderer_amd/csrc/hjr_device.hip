@@ -80,7 +80,7 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
     const int i = hjr::opt_find(key);
     if (i < 0) { set_error(std::string("hjr_set_option: unknown option \"") + (key ? key : "(null)") + "\""); return HJR_ERR_ARG; }
     const hjr::OptDesc& d = hjr::opt_table()[i];
-    if (value != -1 && (value < d.lo || value > d.hi || (i == hjr::OPT_BVH_WIDTH && value == 3) || (i == hjr::OPT_WF_CAP && (value & (value - 1)) != 0))) {
+    if (value != -1 && (value < d.lo || value > d.hi || (i == hjr::OPT_BVH_WIDTH && value == 3) || ((i == hjr::OPT_WF_CAP || i == hjr::OPT_ITEM_CHUNKS) && (value & (value - 1)) != 0))) {
         set_error(std::string("hjr_set_option: value out of range for \"") + d.key + "\" (" + std::to_string(d.lo) + " .. " + std::to_string(d.hi) + ", or -1 for the default)");
         return HJR_ERR_ARG;
     }
@@ -397,6 +397,12 @@ template int hjr_launch<HJR_INTEGRATOR_NEE, false>(hjr_ctx*, const LaunchPlan&, 
 #ifndef HJR_HOLD_MIN
 #define HJR_HOLD_MIN 8 /* megakernel: lanes of the rare material class (multiple-scattering GGX) a wave collects before it shades them (0: never hold; C2 with AOVs, 0 / 4 / 8 / 16 / 32: 129.0 / 126.5 / 126.2 / 127.9 / 144.2 ms) */
 #endif
+#ifndef HJR_ITEM_CHUNKS
+#define HJR_ITEM_CHUNKS 2 /* long single-GPU megakernel launches: chunks of a pixel per work item (option "item_chunks"; launch_render) */
+#endif
+#ifndef HJR_ITEM_GROUP_MIN
+#define HJR_ITEM_GROUP_MIN 192u /* ... "long": single-chunk items per lane of a full grid from which the chunks are grouped */
+#endif
 #ifndef HJR_HOLD_AGE
 #define HJR_HOLD_AGE 2 /* ... or rounds the oldest of them has waited */
 #endif
@@ -629,7 +635,7 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
         }
     }
     kp.chunk_spp = g.chunk_spp; kp.n_chunks = g.n_chunks;
-    kp.chunk0 = g.chunk0; kp.pass_chunks = g.pass_chunks;
+    kp.chunk0 = g.chunk0; kp.pass_chunks = g.pass_chunks; kp.item_chunks = 1u; // (launch_render groups chunks for the megakernel)
     bind_scene_tables(c, kp);
     kp.lut = (c->lut_w > 0) ? (const uchar4*)c->d_lut.p : nullptr;
     kp.lut_w = c->lut_w; kp.lut_h = c->lut_h;
@@ -719,7 +725,28 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
     // wavefront kernels, which beat the approximate megakernel (C2: 175 vs 185 ms), so the flag would only make it slower
     fast = (p->flags & HJR_FLAG_FAST_MATH) && !stats && p->integrator != HJR_INTEGRATOR_MIS;
 #endif
-    const LaunchPlan pl = plan_launch(c, kp, g.n_items, g.lds_mode, p->integrator, fast);
+    LaunchPlan pl = plan_launch(c, kp, g.n_items, g.lds_mode, p->integrator, fast);
+    // Megakernel: a work item is a pixel's group of r consecutive chunks (hjr_layout.h: hjr_item_range), r = the largest power of two <=
+    // option "item_chunks" that divides the launch's chunk count.  The queue then holds 1 / r of the single-chunk items frame_geometry
+    // counted, and its head still overshoots by at most 64 per wave, so the margin taken there covers every r.
+    // Default (MI355X, profiles/item_chunks.json): longer items save a lane the item-end work and the idle round behind an item, a share of
+    // the launch, and add a cost that grows with the item's length and not with the launch's.  1080p, bundled scene, kernel ms with single
+    // chunks -> pairs: 256 spp 108.9 -> 107.3, 192 spp 82.2 -> 82.0, 128 spp 55.5 -> 56.2, 96 spp 42.4 -> 43.7; groups of 4 / 8 chunks lose at
+    // every length measured.  So: pairs when a lane of the full grid has at least HJR_ITEM_GROUP_MIN single-chunk items to go through
+    // (253 at 256 spp, 190 at 192), else single chunks.  The threshold rests on this one scene at this one resolution, and the
+    // difference at 192 spp is inside the run-to-run spread: between the loss at 127 items per lane and the gain at 253 it is an
+    // interpolation.  Single chunks for a rank of a shard (an 8-GPU share took 19.0 ms with 8-sample runs against 21.0 ms with 16) and for
+    // counting launches, and for frames of more than 512 spp, whose chunks are 16 samples and longer: a pair of those is as long as four
+    // 8-sample chunks, and at 1024 spp pairs measured 412.3 against 411.7 ms.  A launch of single chunks runs the SINGLE instantiation of its kernel, which does not carry the item rule.
+    uint64_t n_items = g.n_items;
+    if (!pl.wf && p->integrator != HJR_INTEGRATOR_MIS) { // (MIS runs the wavefront kernels; its megakernel, an option, keeps single chunks)
+        const bool is_long = g.n_items >= (uint64_t)(c->n_cus > 0 ? c->n_cus : 1) * HJR_BLOCK_LDS * HJR_ITEM_GROUP_MIN;
+        const int def = (g.world > 1 || stats || !is_long || g.chunk_spp > 8u) ? 1 : HJR_ITEM_CHUNKS;
+        pl.kp.item_chunks = hjr_item_chunks((uint32_t)c->opt.get(hjr::OPT_ITEM_CHUNKS, def), g.pass_chunks);
+        n_items = hjr_item_count(g.n_items / ((uint64_t)g.pass_chunks * 64u), g.pass_chunks, pl.kp.item_chunks); // (g.n_items counts the active tiles of an adaptive pass)
+        pl.kp.n_owned_items = (uint32_t)n_items;
+    }
+    c->stats.item_chunks = pl.kp.item_chunks;
     c->stats.pipeline = pl.wf ? 1u : 0u; c->stats.fast_math = fast ? 1u : 0u; c->stats.stack_lds_entries = pl.kp.stack_lds_entries;
     using LaunchFn = int (*)(hjr_ctx*, const LaunchPlan&, uint64_t, hipStream_t);
 #ifdef HJR_LEAN_VARIANT
@@ -732,7 +759,7 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
     if (fast) fn = p->integrator == HJR_INTEGRATOR_NEE ? hjr_launch_fast<HJR_INTEGRATOR_NEE> : hjr_launch_fast<HJR_INTEGRATOR_PT>;
 #endif
 #endif
-    if (const int rc = fn(c, pl, g.n_items, st)) return rc;
+    if (const int rc = fn(c, pl, n_items, st)) return rc;
     HIPCHK(hipGetLastError());
     return HJR_OK;
 }

@@ -3,8 +3,10 @@
 //   multiple-scattering GGX) -> next-event-estimation integrator (also Pathtrace / MIS).
 //
 // Execution model
-//   * a work item is one pixel's run of 8 consecutive samples, executed in order by one lane, so every per-pixel fp32 sum has
-//     a fixed order (bitwise independent of scheduling, tile sharding and GPU count);
+//   * a pixel's samples are cut into chunks of 8 consecutive samples; a chunk is executed in order by one lane and summed on its own, so
+//     every per-pixel fp32 sum has a fixed order (bitwise independent of scheduling, tile sharding and GPU count).  A work item is one
+//     pixel's group of 1, 2, 4 or 8 consecutive chunks (KParams::item_chunks): the lane writes each chunk's sum out as it finishes and
+//     goes on with the next chunk in the same round, as it does between two samples;
 //   * wavefronts are persistent: a wave takes 64 items at a time from a global queue with one atomic and hands them to its
 //     idle lanes with ballot + mbcnt prefix sums; tiles are queued expensive first (cost-ordered tile list);
 //   * paths are regenerated in place: a lane whose path ended (Russian roulette, miss, light hit, depth cap)
@@ -209,10 +211,10 @@ extern __shared__ float4 hjr_smem[];
 struct LaneCtx {
     bool has_item, dead, path_live;
     bool fin_pending;   // a finished path whose L still waits for its last NEE shadow ray
-    bool write_pending; // the item's last sample is finished; sums go out once fin_pending is resolved
+    bool write_pending; // the last sample of the item's current chunk is finished; sums go out once fin_pending is resolved
     bool sh_valid;      // pending NEE shadow ray of the bounce shaded last
     bool fresh;         // the closest-hit ray of this lane starts at the camera (ps.ro is then the origin of the pending shadow ray only)
-    uint32_t item;      // px | py << 13 | chunk << 26
+    uint32_t item;      // px | py << 13 | chunk << 26 (the chunk whose sums the lane holds: it moves on when they are written out)
     uint32_t s;         // current sample of the item's run
     uint32_t it_cost;   // closest-hit rays traced for the current item (feeds the measured-cost tile order)
     f3 sumL, sumA, sumN;
@@ -255,7 +257,7 @@ struct SharedRange {
 };
 struct WaveRange {
     uint32_t next, end; bool exhausted; SharedRange* shared;
-    // megakernel: a private range is 64 aligned items = ONE (tile, sample chunk).  Its decode — two integer divisions, the tile-order
+    // megakernel: a private range is 64 aligned items = ONE (tile, group of sample chunks).  Its decode — two integer divisions, the tile-order
     // look-up, the tile's diagonal id turned back into (x, y) — is done once when the range is fetched, wave-uniform, not by every lane
     // at every refill (a wave refills some lane in nearly every round: ~120 instructions per round): the item word of the range's
     // pixel (0, 0)
@@ -326,14 +328,18 @@ template <bool STATS> HD void finish_sample(const KParams& P, LaneCtx& c, f3 L, 
     c.sumL = c.sumL + L;
     if (STATS) lc[0] += 1;
 }
-// sample bookkeeping at the end of a path (independent of the radiance value)
-HD void close_sample(const KParams& P, LaneCtx& c)
+// sample bookkeeping at the end of a path (independent of the radiance value).  GROUPS: the kernel's items may be groups of chunks.  The
+// rule keeps P.chunk0 / P.item_chunks in SGPRs across the render loop, which costs a launch of single chunks 0.4 %: the kernels that only
+// ever run single chunks (the wavefront kernels, hjr_render_kernel<..., SINGLE = true>) compile it away and are the code they were
+template <bool GROUPS> HD void close_sample(const KParams& P, LaneCtx& c)
 {
     c.s++;
     c.path_live = false;
-    if (c.s == HJR_S_END(c)) { c.write_pending = true; c.has_item = false; }
+    // end of the chunk: its sums go out.  The lane keeps the pixel unless that was the item's last chunk: it regenerates sample c.s, the
+    // first one of the next chunk, like any other next sample (write_out moves the item word on once the sums are stored)
+    if (c.s == HJR_S_END(c)) { c.write_pending = true; c.has_item = GROUPS && !hjr_item_last_chunk(HJR_CHUNK(c), P.chunk0, P.item_chunks); }
 }
-template <bool AOVS> HD void write_out(const KParams& P, LaneCtx& c)
+template <bool AOVS, bool GROUPS> HD void write_out(const KParams& P, LaneCtx& c)
 {
     const float inv_spp = 1.0f / (float)P.spp;
     const uint32_t tiles_x = HJR_COLD(tiles_x), world = HJR_COLD(world), n_chunks = HJR_COLD(n_chunks); // (cold parameters: see cold_param)
@@ -366,25 +372,17 @@ template <bool AOVS> HD void write_out(const KParams& P, LaneCtx& c)
         }
     }
     c.write_pending = false;
+    if (GROUPS && c.has_item) { // the item goes on with its next chunk (megakernel, item_chunks > 1): fresh sums; samples and RNG streams are those of that chunk
+        c.sumL = V1(0.0f); c.sumA = V1(0.0f); c.sumN = V1(0.0f);
+        c.item += 1u << 26;
+    }
 }
 
-// decode of the 64 aligned items [base, base + 64) of the megakernel's queue: item q = ((owned tile * pass_chunks) + chunk - chunk0) * 64 +
-// pixel-in-tile.  A launch renders the chunks [chunk0, chunk0 + pass_chunks) of the frame (all of them unless it is a sample pass); the
-// item word keeps the ABSOLUTE chunk, so a sample's number and RNG stream do not depend on the pass it was rendered in
-HD uint32_t decode_range(uint32_t base, uint32_t pass_chunks, uint32_t chunk0, uint32_t tiles_x, uint32_t world, uint32_t rank, const uint32_t* tile_order)
-{
-    const uint32_t tc = base >> 6;
-    const uint32_t owned = tc / pass_chunks, chunk = chunk0 + (tc - owned * pass_chunks);
-    const uint32_t tile = tile_order ? tile_order[owned] : owned * world + rank;
-    uint32_t tx, ty;
-    hjr_tile_xy(tile, tiles_x, &tx, &ty);
-    return (tx * HJR_TILE) | ((ty * HJR_TILE) << 13) | (chunk << 26);
-}
 // ---- first half of a bounce.  ALL 64 lanes of the wave must call it together (ballots and shuffles inside); `active` is
 // false for lanes that sit this round out (megakernel: lanes whose traversal is carried over; wavefront: lanes without a
 // context).  On return `tracing` says whether the lane has a closest-hit ray to trace (origin: camera if c.fresh, else c.ps.ro;
 // direction c.ps.rd) and c.sh_valid whether a shadow ray (origin c.ps.ro, direction c.sh_d, tmax c.sh_tmax) goes with it.
-template <bool STATS, bool AOVS, bool ONEWRITE = false>
+template <bool STATS, bool AOVS, bool ONEWRITE = false, bool GROUPS = false>
 HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool active, bool& tracing, unsigned long long* lc)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -398,12 +396,12 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             const float xi_rr = cmj_1d(rr);
             c.ps.rng_depth = rr.depth;
             if (russian_p < xi_rr) {
-                if (c.sh_valid) { c.fin_pending = true; close_sample(P, c); } // radiance final once the pending shadow ray is resolved
+                if (c.sh_valid) { c.fin_pending = true; close_sample<GROUPS>(P, c); } // radiance final once the pending shadow ray is resolved
                 else { // nothing pending: the sample is final now, and if it was the item's last one the lane refills below
                     finish_sample<STATS>(P, c, c.ps.L, lc);
                     c.ps.L = V1(0.0f);
-                    close_sample(P, c);
-                    if (!ONEWRITE && c.write_pending) write_out<AOVS>(P, c);
+                    close_sample<GROUPS>(P, c);
+                    if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
                 }
             } else c.ps.thr = c.ps.thr / russian_p;
         }
@@ -414,7 +412,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
     //      bounce_post_trace), so the write-out code (two integer divisions, up to six stores) exists once instead of four times: MIS
     //      192.9 -> 188.2 ms.  Nothing is added to an item's sums after its last sample closed, and the refill below waits for the write.
     //      The megakernel keeps the four in-place writes: there this extra test in every round cost 0.4 - 1 %.
-    if (ONEWRITE && active && c.write_pending && !c.fin_pending) write_out<AOVS>(P, c);
+    if (ONEWRITE && active && c.write_pending && !c.fin_pending) write_out<AOVS, GROUPS>(P, c);
 
     // ---- ray-queue refill (ballot + mbcnt prefix): idle lanes take consecutive items from the wave's private range
     //      [wr.next, wr.end); when it runs dry the wave fetches the next 64 items with ONE atomic on the global head.
@@ -426,6 +424,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             // (cold parameters, read here and not kept in SGPRs across the render loop: see cold_param)
             const uint32_t n_owned_items = HJR_COLD(n_owned_items), pass_chunks = HJR_COLD(pass_chunks), tiles_x = HJR_COLD(tiles_x), world = HJR_COLD(world);
+            // (item decode: hjr_layout.h::hjr_decode_range; with GROUPS, P.chunk0 / P.item_chunks are resident for close_sample anyway)
             const uint32_t* const tile_order = HJR_COLD(tile_order);
             uint32_t* const tile_cost = HJR_COLD(tile_cost);
             uint32_t q;
@@ -455,7 +454,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
                     if (prefix >= have) q = 0xffffffffu;
                     wr.next = wr.end = 0u;
                 } else {
-                    const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)decode_range(base, pass_chunks, HJR_COLD(chunk0), tiles_x, world, HJR_COLD(rank), tile_order)); // (wave-uniform)
+                    const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)hjr_decode_range(base, pass_chunks, GROUPS ? P.chunk0 : HJR_COLD(chunk0), GROUPS ? P.item_chunks : 1u, tiles_x, world, HJR_COLD(rank), tile_order)); // (wave-uniform)
                     if (prefix >= have) { q = base + (prefix - have); r_item = bi; }
                     wr.next = base + (n - have);
                     wr.end = base + 64u;
@@ -466,7 +465,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             // measured cost of a tile (orders the tiles of the next frame, hjr_cost_hist_kernel): a lane sums the rays of its
             // consecutive items of one tile and flushes when it moves on; lanes leaving the same tile together (the usual
             // case) share one atomic.  All lanes are here (m is wave-uniform), so the shuffles below are well defined.
-            if (wr.shared && need && q < n_owned_items) r_item = decode_range(q & ~63u, pass_chunks, HJR_COLD(chunk0), tiles_x, world, HJR_COLD(rank), tile_order); // (wavefront kernel: runs of the shared range, decoded per lane)
+            if (wr.shared && need && q < n_owned_items) r_item = hjr_decode_range(q & ~63u, pass_chunks, HJR_COLD(chunk0), 1u, tiles_x, world, HJR_COLD(rank), tile_order); // (wavefront kernel: runs of the shared range, decoded per lane)
             if (tile_cost) {
                 const uint32_t old_tile = hjr_tile_id(HJR_PX(c) / HJR_TILE, HJR_PY(c) / HJR_TILE, tiles_x);
                 const uint32_t new_tile = (need && q < n_owned_items) ? hjr_tile_id((r_item & 0x1fffu) / HJR_TILE, ((r_item >> 13) & 0x1fffu) / HJR_TILE, tiles_x) : 0xffffffffu;
@@ -483,8 +482,8 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             }
             if (need) {
                 if (q < n_owned_items) {
-                    // the 64 lanes of a wave start on one tile and one sample chunk (coherent primary rays): the range's item word + the pixel in the tile
-                    const uint32_t item = r_item | (q & 7u) | (((q >> 3) & 7u) << 13);
+                    // the 64 lanes of a wave start on one tile and one group of sample chunks (coherent primary rays): the range's item word + the pixel in the tile
+                    const uint32_t item = hjr_item_word(r_item, q);
                     const uint32_t px = item & 0x1fffu, py = (item >> 13) & 0x1fffu, chunk = item >> 26;
                     if (px < P.width && py < P.height) {
                         c.has_item = true; c.path_live = false;
@@ -514,7 +513,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
 
 // ---- second half of a bounce, for a lane whose rays of this round are resolved: `occluded` answers the pending shadow ray
 // (if c.sh_valid), `h` the closest-hit ray (if tracing).  Lane-private: no cross-lane operation inside.
-template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST, bool ONEWRITE = false>
+template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST, bool ONEWRITE = false, bool GROUPS = false>
 HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* tris, const float4* mats, const float4* lights, LaneCtx& c,
                           const bool tracing, const bool occluded, const Hit& h, ST& stack, unsigned long long* lc)
 {
@@ -528,7 +527,7 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
         finish_sample<STATS>(P, c, ps.L, lc, 1u);
         ps.L = V1(0.0f); // from here on ps.L belongs to the path that was regenerated (or to nothing)
         c.fin_pending = false;
-        if (!ONEWRITE && c.write_pending) write_out<AOVS>(P, c);
+        if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
     }
     if (!tracing) return;
 
@@ -547,8 +546,8 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
         // NEE / MIS count emission only at depth 0 (rt.h:196-208, 318-330); Pathtrace always (rt.h:118-126)
         if (INTEGRATOR == HJR_INTEGRATOR_PT_ || ps.depth == 0) ps.L = ps.L + ps.thr * prd.emission;
         finish_sample<STATS>(P, c, ps.L, lc);
-        close_sample(P, c);
-        if (!ONEWRITE && c.write_pending) write_out<AOVS>(P, c);
+        close_sample<GROUPS>(P, c);
+        if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
         return;
     }
     CMJState st = path_rng_from_head(P, ps.rng_head, c.s, ps.rng_depth);
@@ -653,12 +652,12 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
     ps.rng_depth = st.depth;
     ps.depth++;
     if (ps.depth == 10) { // MaxDepth (rt.h:166): the path is over; its last shadow ray, if any, is still pending
-        if (c.sh_valid) { c.fin_pending = true; close_sample(P, c); }
+        if (c.sh_valid) { c.fin_pending = true; close_sample<GROUPS>(P, c); }
         else {
             finish_sample<STATS>(P, c, ps.L, lc);
             ps.L = V1(0.0f);
-            close_sample(P, c);
-            if (!ONEWRITE && c.write_pending) write_out<AOVS>(P, c);
+            close_sample<GROUPS>(P, c);
+            if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
         }
     }
 }
@@ -686,7 +685,9 @@ HD void stage_scene_in_lds(const KParams& P, float4* base, const float4*& nodes,
 // smallest variant that does what it needs.
 // FAST only tags the symbol: the HJR_FAST_MATH translation units (hjr_launch_fast_*.hip; approximate division / square root / sine / cosine /
 // power in the SHADING code, traversal and triangle test unchanged) instantiate FAST = true, the exact ones FAST = false.
-template <int INTEGRATOR, bool STATS, int BLOCK, bool LDSBVH, bool STACK16, int WIDTH, int VAR, bool FAST = false>
+// SINGLE: a launch whose work items are single chunks (KParams::item_chunks == 1: shards, counting and short launches by default, MIS always):
+// the item rule is compiled away, the kernel is the one it was before items could be groups (close_sample).
+template <int INTEGRATOR, bool STATS, int BLOCK, bool LDSBVH, bool STACK16, int WIDTH, int VAR, bool FAST = false, bool SINGLE = false>
 __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_render_kernel(const KParams P)
 {
     constexpr bool AOVS = VAR >= 1, TEX = VAR == 2;
@@ -735,7 +736,7 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
     constexpr bool HOLD = LDSBVH; // (LDS-resident scenes only: on the 1 M-triangle scene the two extra live registers cost 3 % and the hold gains nothing)
     uint32_t hold = 0u; // > 0: this lane holds a resolved hit of a rare material class back (rounds held so far), see below
     for (;;) {
-        bounce_pre_trace<STATS, AOVS>(P, c, wr, !inflight && (!HOLD || hold == 0u), tracing, lc);
+        bounce_pre_trace<STATS, AOVS, false, !SINGLE>(P, c, wr, !inflight && (!HOLD || hold == 0u), tracing, lc);
         if (__ballot(!c.dead) == 0ull) break; // a lane only dies with nothing pending
         HJR_TICK(0)
 #ifdef HJR_TIMING
@@ -781,7 +782,7 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
         }
         if (shade) {
             if (HOLD) hold = 0u;
-            bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST>(P, nodes, tris, mats, lights, c, tracing, occluded, h, stack, lc);
+            bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, false, !SINGLE>(P, nodes, tris, mats, lights, c, tracing, occluded, h, stack, lc);
         }
         HJR_TICK(2)
     }

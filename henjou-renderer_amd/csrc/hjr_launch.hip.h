@@ -160,6 +160,16 @@ template <int I, bool S, bool LDS, int W, int A> static RenderKernel wf_kernel(b
 {
     return spill ? hjr_wavefront_kernel<I, S, HJR_BLOCK_LDS, LDS, true, W, A> : hjr_wavefront_kernel<I, S, HJR_BLOCK_LDS, LDS, false, W, A>;
 }
+template <int I, bool S, int A, bool SINGLE> static RenderKernel mega_kernel(int lds_mode)
+{
+    if (lds_mode == 1) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, false, 2, A, HJR_FAST_TAG, SINGLE>;
+    if (lds_mode == 0) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 4, A, HJR_FAST_TAG, SINGLE>;
+#ifndef HJR_LEAN_VARIANT
+    if (lds_mode == 2) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, true, 2, A, HJR_FAST_TAG, SINGLE>;
+    if (lds_mode == 3) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 2, A, HJR_FAST_TAG, SINGLE>;
+#endif
+    return nullptr;
+}
 // the kernels of this translation unit; the lean experiment build has only the NEE non-counting LDS / BVH4-memory megakernels
 template <int I, bool S> static RenderKernel pick_kernel(const LaunchPlan& pl)
 {
@@ -172,13 +182,10 @@ template <int I, bool S> static RenderKernel pick_kernel(const LaunchPlan& pl)
             return wf_kernel<I, S, false, 4, A>(pl.wf_spill);
         }
 #endif
-        if (pl.lds_mode == 1) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, false, 2, A, HJR_FAST_TAG>;
-        if (pl.lds_mode == 0) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 4, A, HJR_FAST_TAG>;
-#ifndef HJR_LEAN_VARIANT
-        if (pl.lds_mode == 2) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, true, 2, A, HJR_FAST_TAG>;
-        if (pl.lds_mode == 3) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 2, A, HJR_FAST_TAG>;
-#endif
-        return nullptr;
+        // items of several chunks (kp.item_chunks > 1; NEE and Pathtrace) run the kernels that carry the item rule, every other launch the
+        // SINGLE instantiations, which do not (hjr_kernel.hip.h: close_sample)
+        if constexpr (I != HJR_INTEGRATOR_MIS) if (pl.kp.item_chunks > 1u) return mega_kernel<I, S, A, false>(pl.lds_mode);
+        return mega_kernel<I, S, A, true>(pl.lds_mode);
     });
 }
 

@@ -69,8 +69,46 @@ HJR_LAYOUT_FN void hjr_tile_xy(uint32_t t, uint32_t tiles_x, uint32_t* tx, uint3
 
 /* Work-item chunking: a pixel's spp samples are cut into n_chunks runs of chunk_spp consecutive samples
  * (a multiple of 8, at most 64 runs); pixel mean = ((c0 + c1) + ... ) * (1/spp), ck = in-order sum of run k.  Depends on spp
- * only, so results do not depend on scheduling, tile sharding or GPU count.  A run is one work item, executed by one lane
+ * only, so results do not depend on scheduling, tile sharding or GPU count.  A run (or a few consecutive runs of one pixel, below) is one work item, executed by one lane
  * from its first to its last bounce: its length is the critical path of a launch (16-sample runs: ~4 ms for a pixel inside
  * the glass sphere, 20 % of an 8-GPU share of the C2 frame), hence runs of 8 (profiles/r01_experiments.md). */
 static inline uint32_t hjr_chunk_spp(uint32_t spp) { uint32_t n8 = (spp + 7u) / 8u; return 8u * ((n8 + 63u) / 64u); }
 static inline uint32_t hjr_n_chunks(uint32_t spp) { uint32_t s = hjr_chunk_spp(spp); return (spp + s - 1u) / s; }
+
+/* Work items of the megakernel's queue.  A launch renders the chunks [chunk0, chunk0 + pass_chunks) of the frame (all of
+ * them unless it is a sample pass).  An item is one pixel's group of r = item_chunks CONSECUTIVE chunks, [chunk0 + g r, chunk0 + (g + 1) r):
+ * a lane keeps the pixel from the first sample of the group to the last and writes every chunk's sum to that chunk's own slot, so the
+ * chunk sums, and with them every pixel, do not depend on r.  r is a power of two that divides pass_chunks.
+ *   item q = ((owned tile * (pass_chunks / r)) + group) * 64 + pixel in tile
+ * so 64 aligned items are one tile and one group (a wave's private range), and the queue holds owned * (pass_chunks / r) * 64 items. */
+/* the group length of a launch: the largest power of two that is no larger than the request and divides pass_chunks (possibly 1) */
+HJR_LAYOUT_FN uint32_t hjr_item_chunks(uint32_t request, uint32_t pass_chunks)
+{
+    uint32_t r = 1u;
+    while (r * 2u <= request && pass_chunks % (r * 2u) == 0u) r *= 2u;
+    return r;
+}
+HJR_LAYOUT_FN uint64_t hjr_item_count(uint64_t owned_tiles, uint32_t pass_chunks, uint32_t item_chunks) { return owned_tiles * (pass_chunks / item_chunks) * 64u; }
+/* the 64 aligned items [base, base + 64): position of their tile in the launch's tile list, and the first chunk of their group (ABSOLUTE) */
+HJR_LAYOUT_FN void hjr_item_range(uint32_t base, uint32_t pass_chunks, uint32_t chunk0, uint32_t item_chunks, uint32_t* owned, uint32_t* chunk)
+{
+    const uint32_t tg = base >> 6, groups = pass_chunks / item_chunks;
+    const uint32_t o = tg / groups;
+    *owned = o;
+    *chunk = chunk0 + (tg - o * groups) * item_chunks;
+}
+/* is `chunk` the last one of its item (the lane then gives the pixel up), or does the item go on with chunk + 1 */
+HJR_LAYOUT_FN bool hjr_item_last_chunk(uint32_t chunk, uint32_t chunk0, uint32_t item_chunks) { return ((chunk - chunk0 + 1u) & (item_chunks - 1u)) == 0u; }
+/* ... as the item word of pixel (0, 0) of that range: x | y << 13 | chunk << 26.  The word keeps the ABSOLUTE chunk, so a sample's number
+ * and RNG stream do not depend on the pass it was rendered in.  tile_order: the launch's tile list (null = plain round-robin order) */
+HJR_LAYOUT_FN uint32_t hjr_decode_range(uint32_t base, uint32_t pass_chunks, uint32_t chunk0, uint32_t item_chunks, uint32_t tiles_x, uint32_t world, uint32_t rank,
+                                        const uint32_t* tile_order)
+{
+    uint32_t owned, chunk, tx, ty;
+    hjr_item_range(base, pass_chunks, chunk0, item_chunks, &owned, &chunk);
+    const uint32_t tile = tile_order ? tile_order[owned] : owned * world + rank;
+    hjr_tile_xy(tile, tiles_x, &tx, &ty);
+    return (tx * HJR_TILE) | ((ty * HJR_TILE) << 13) | (chunk << 26);
+}
+/* item q of that range: the range's word + the pixel in the tile (q & 63, row-major 8 x 8) */
+HJR_LAYOUT_FN uint32_t hjr_item_word(uint32_t range_word, uint32_t q) { return range_word | (q & 7u) | (((q >> 3) & 7u) << 13); }

@@ -28,7 +28,7 @@ struct KParams {
     int sky_w, sky_h;
     uint32_t n_lights;
     uint32_t width, height, spp, frame, seed, integrator;
-    uint32_t tiles_x, n_owned_items; // items = owned tiles * pass_chunks * 64
+    uint32_t tiles_x, n_owned_items; // items of the launch's queue: owned tiles * pass_chunks * 64 single chunks, fewer when the megakernel groups them (hjr_item_count)
     uint32_t rank, world;
     uint32_t packed;                 // HJR_FLAG_PACKED: the AOV buffers hold this rank's tiles only, [owned tile][64] float4
     uint32_t chunk_spp, n_chunks;    // samples per work item, work items per pixel (hjr_chunking)
@@ -66,7 +66,10 @@ struct KParams {
     // sample pass (hjr_params.sample_begin / sample_end): the launch renders chunks [chunk0, chunk0 + pass_chunks) of the
     // frame's n_chunks (0 / n_chunks for a whole frame); the buffers behind part_* hold those chunks only
     uint32_t chunk0, pass_chunks;
-    float4* run_color;               // hjr_finalize_kernel<PASS>: running sums of the frame's earlier passes, [owned tile][64] float4 per AOV
+    // megakernel: a work item is one pixel's group of item_chunks consecutive chunks (a power of two that divides pass_chunks; hjr_layout.h:
+    // hjr_item_range).  The wavefront kernels run single chunks: 1 there
+    uint32_t item_chunks;
+    float4* run_color;              // hjr_finalize_kernel<PASS>: running sums of the frame's earlier passes, [owned tile][64] float4 per AOV
     float4* run_albedo;
     float4* run_normal;
     uint32_t run_load, run_store;    // 1: the running sums hold earlier passes (else they start at +0.0f) / are written back (not the last pass)

@@ -311,6 +311,8 @@ typedef struct hjr_stats {
     float    bvh_topology_ms;    /* HIP-event time of the last per-instance topology build of that option; the commits that reuse the
                                   * topology leave it as it is */
     uint64_t firefly_clamped;    /* option "firefly_clamp": (pixel, chunk) pairs the last whole-frame launch scaled down; 0 when the rule did not act */
+    uint32_t item_chunks;        /* chunks of a pixel per work item of the last render launch (option "item_chunks" as the launch resolved it; 1 for the wavefront kernels) */
+    uint32_t _pad1;
 } hjr_stats;
 
 typedef struct hjr_scene hjr_scene; /* owning, host side (SceneData + animations) */
@@ -565,6 +567,12 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  exceeds kappa x the lower median of the pixel's full chunks down to that limit.  Biased, opt-in; 4 is the
                                  recommended value.  Sample passes other than [0, spp) are HJR_ERR_ARG with it.  0 (default): today's call,
                                  bit for bit, the same kernels
+   "item_chunks"    1 2 4 8      megakernel: consecutive sample chunks of one pixel that form a work item of the queue.  A launch uses the
+                                 largest power of two that is no larger than this and divides the number of chunks it renders (possibly 1).
+                                 Scheduling only: every chunk is still summed on its own, frames are the same bits.  Default: 1 for launches
+                                 with world_size > 1 (short, tail-bound) and for counting launches (HJR_FLAG_STATS), else what was measured
+                                 fastest on one GPU (csrc/hjr_device.hip: HJR_ITEM_CHUNKS).  The wavefront kernels and MIS always run single chunks;
+                                 hjr_stats.item_chunks reports what the last launch used
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are

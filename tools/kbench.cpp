@@ -1,6 +1,6 @@
 // tools/kbench — kernel-variant bench over the C-ABI, no Python / torch start-up cost.
 //   kbench <libhenjou_hip.so> <render_option.json> [--width W] [--height H] [--spp S] [--integrator 0|1|2] [--reps N]
-//          [--aovs] [--rank r --world n] [--stats] [--fast] [--opt key=value ...]
+//          [--aovs] [--rank r --world n] [--stats] [--fast] [--item-chunks 1|2|4|8] [--opt key=value ...]
 // dlopens the given build of the library (so several builds can be compared inside one gpurun call), renders the start frame of
 // the config `reps` times through hjr_render (host buffers; the kernel time is the library's own HIP-event time around the
 // kernels) and prints kernel ms (min / mean), Msamples/s and an FNV-1a hash of the colour AOV (equal hashes = bit-identical
@@ -47,6 +47,7 @@ int main(int argc, char** argv)
         else if (a == "--aovs") aovs = true;
         else if (a == "--stats") stats = true;
         else if (a == "--fast") fast = true;
+        else if (a == "--item-chunks") options.push_back({ "item_chunks", val() }); // short for --opt item_chunks=N
         else if (a == "--opt" && i + 1 < argc) { std::string kv = argv[++i]; const size_t eq = kv.find('='); if (eq == std::string::npos) { fprintf(stderr, "kbench: --opt key=value\n"); return 2; } options.push_back({ kv.substr(0, eq), atoi(kv.c_str() + eq + 1) }); }
         else { fprintf(stderr, "kbench: unknown option %s\n", a.c_str()); return 2; }
     }
