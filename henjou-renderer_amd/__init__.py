@@ -227,6 +227,8 @@ def lib():
             "hjr_denoise_var": [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
             "hjr_denoise_var_device": [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                        C.c_void_p],
+            "hjr_estimate_variance": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_estimate_variance_device": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_synchronize": [C.c_void_p],
             "hjr_get_stats": [C.c_void_p, C.c_void_p],
             "hjr_preview_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p],
@@ -563,6 +565,30 @@ class Device:
         _check(lib().hjr_denoise(self._h, mode, w, h, color.ctypes.data, None if a is None else a.ctypes.data,
                                  None if n is None else n.ctypes.data, out.ctypes.data, ow, oh), "hjr_denoise")
         return out
+
+    def estimate_variance(self, color, albedo, normal, variance=None):
+        """hjr_estimate_variance on host float4 images [h, w, 4]: pixels of `variance` (float32 [h, w]; None = all of them) that are unknown
+        (VARIANCE_UNKNOWN or above) get the 3 x 3 guide-weighted variance of r + g + b, the others keep their bits.  Returns float32 [h, w]."""
+        color, albedo, normal = (np.ascontiguousarray(a, dtype=np.float32) for a in (color, albedo, normal))
+        h, w = color.shape[:2]
+        if color.shape != (h, w, 4) or albedo.shape != (h, w, 4) or normal.shape != (h, w, 4):
+            raise ValueError("color, albedo and normal must be [height, width, 4]")
+        v = None
+        if variance is not None:
+            v = np.ascontiguousarray(variance, dtype=np.float32)
+            if v.shape != (h, w):
+                raise ValueError("variance must be [height, width]")
+        out = np.zeros((h, w), dtype=np.float32)
+        _check(lib().hjr_estimate_variance(self._h, w, h, color.ctypes.data, albedo.ctypes.data, normal.ctypes.data, None if v is None else v.ctypes.data,
+                                           out.ctypes.data), "hjr_estimate_variance")
+        return out
+
+    def estimate_variance_device(self, width, height, d_color, d_albedo, d_normal, d_variance_in, d_variance_out, stream=None):
+        """hjr_estimate_variance_device: the same on device pointers (ints; d_variance_in None = every pixel unknown; d_variance_out may be
+        d_variance_in), asynchronous on a hipStream_t (int; None = the context's stream)."""
+        _check(lib().hjr_estimate_variance_device(self._h, width, height, C.c_void_p(d_color), C.c_void_p(d_albedo), C.c_void_p(d_normal),
+                                                  C.c_void_p(d_variance_in) if d_variance_in else None, C.c_void_p(d_variance_out),
+                                                  C.c_void_p(stream) if stream else None), "hjr_estimate_variance_device")
 
     def render_denoised(self, params, mode, out_w=None, out_h=None):
         """One frame in a render mode, AOVs kept on the device (hjr_render_denoised); returns AOV_Output."""

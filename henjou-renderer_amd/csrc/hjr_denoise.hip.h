@@ -37,6 +37,27 @@
 // One more float per tap than the filter above (52 instead of 48 bytes) plus the 9 floats of the prefilter per pixel: 0.80 ms against
 // 0.75 ms at 1080p.  On the bundled scene (96 x 64, box filling the frame, against a 16384 spp frame): RMSE 0.034 / 0.032 / 0.029 / 0.026
 // at 16 / 64 / 256 / 1024 spp where the filter above stays at 0.059 / 0.057 / 0.056 / 0.056.
+//
+// The SPATIAL VARIANCE ESTIMATE (hjr_estimate_variance, option "denoise_variance_spatial"): what SVGF does while its history is short.  The
+// variance AOV needs two full chunks of a pixel (rule 7), so a frame of at most 8 spp, and the first one-granule sample pass, carry
+// HJR_VARIANCE_UNKNOWN everywhere and the variant above falls back to its guides.  This kernel fills such pixels with the guide-weighted
+// second central moment of the luminance over the 3 x 3 neighbourhood and leaves every known variance as it is.  Specified to the bit;
+// fp32 as written, no contraction, correctly rounded divide, p_exp = the portable exponential:
+//   K = fminf(fmaxf(vin, 0.0f), 1e30f)          (NaN -> 0: the clamp hjr_atrous_var_kernel applies to its input)
+//   if K < 1e30f:  vout = vin as stored          (pass-through, the bits unchanged: negative values and NaN too, the filter clamps them)
+//   else (HJR_VARIANCE_UNKNOWN and above, +Inf):
+//     l = (c.x + c.y) + c.z of a tap's colour;  taps dy, dx in -1..1, rows outer, indices clamped to the frame, the centre included;
+//     w = wn * wa  with the forms and constants of the filter above: q = |d|^2 of normal / albedo against the centre's, phi 0.25 / 0.05,
+//         w? = min(p_exp(max(-q / phi, -87)), 1);
+//     from +0.0f in tap order:  s0 = s0 + w;  s1 = s1 + w * l_t;  s2 = s2 + w * (l_t * l_t);
+//     mu = s1 / s0;  v = fmaxf(s2 / s0 - mu * mu, 0.0f);
+//     vout = (v < 1e30f) ? v : HJR_VARIANCE_UNKNOWN          (+Inf stays "unknown"; fmaxf turns a NaN difference into 0)
+//   vin == NULL: every pixel is unknown.  vin is read at the centre only and by the lane that writes vout there, so vout == vin (in
+//   place) is allowed.  s0 >= 1: the centre's weight is p_exp(-0) = 1.
+// v estimates the variance of the pixel's written value r + g + b, the quantity rule 7 defines.  The window stays 3 x 3: a firefly
+// inflates the estimate of every window that holds it, the colour weight opens there and the firefly spreads.
+// One lane per pixel, 27 float4 and one float read, one float written; no LDS, no scratch.  0.055 ms at 1080p with every pixel unknown, 0.008 ms
+// with every pixel known, next to the 0.86 ms of the five filter passes that follow (profiles/spatial_var.json).
 #pragma once
 #include "hjr_math.hip.h"
 
@@ -130,6 +151,42 @@ __global__ void __launch_bounds__(256) hjr_atrous_var_kernel(const float4* __res
     }
     out[c] = make_float4(sx / cum, sy / cum, sz / cum, c0.w);
     vout[c] = sv / (cum * cum);
+}
+
+// the spatial variance estimate (header above); vin NULL = every pixel unknown; vout may be vin (neither is __restrict__)
+__global__ void __launch_bounds__(256) hjr_spatial_var_kernel(const float4* __restrict__ in, const float4* __restrict__ normal, const float4* __restrict__ albedo,
+                                                               const float* vin, float* vout, int W, int H)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const float n_phi = 0.25f, a_phi = 0.05f;
+    const size_t c = (size_t)y * W + x;
+    if (vin) {
+        const float v0 = vin[c];
+        if (fminf(fmaxf(v0, 0.0f), 1e30f) < 1e30f) { vout[c] = v0; return; }
+    }
+    const float4 n0 = normal[c], a0 = albedo[c];
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    for (int j = -1; j <= 1; j++) {
+        const int yy = min(max(y + j, 0), H - 1);
+        for (int i = -1; i <= 1; i++) {
+            const int xx = min(max(x + i, 0), W - 1);
+            const size_t t = (size_t)yy * W + xx;
+            const float4 ct = in[t], nt = normal[t], at = albedo[t];
+            const float lt = (ct.x + ct.y) + ct.z;
+            float dx = n0.x - nt.x, dy = n0.y - nt.y, dz = n0.z - nt.z;
+            float d2 = dx * dx + dy * dy + dz * dz;
+            const float wn = fminf(p_exp(fmaxf(-d2 / n_phi, -87.0f)), 1.0f);
+            dx = a0.x - at.x; dy = a0.y - at.y; dz = a0.z - at.z;
+            d2 = dx * dx + dy * dy + dz * dz;
+            const float wa = fminf(p_exp(fmaxf(-d2 / a_phi, -87.0f)), 1.0f);
+            const float w = wn * wa;
+            s0 = s0 + w; s1 = s1 + w * lt; s2 = s2 + w * (lt * lt);
+        }
+    }
+    const float mu = s1 / s0;
+    const float v = fmaxf(s2 / s0 - mu * mu, 0.0f);
+    vout[c] = (v < 1e30f) ? v : 1e30f; // HJR_VARIANCE_UNKNOWN
 }
 
 // 2x bilinear upscale, pixel centres: source coordinate (X + 0.5) / 2 - 0.5, i.e. weights 0.75 / 0.25 towards the nearer texel,

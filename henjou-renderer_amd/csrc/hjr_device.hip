@@ -85,7 +85,7 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
         return HJR_ERR_ARG;
     }
     c->opt.v[i] = value;
-    if (i == hjr::OPT_DENOISE_TEMPORAL) c->tmp.have_prev = false; // setting the option drops the history
+    if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL) c->tmp.have_prev = false; // setting either option drops the history
     if (i == hjr::OPT_HOST_THREADS) hjr::set_host_threads(value);
     return HJR_OK;
 }
@@ -1122,6 +1122,49 @@ extern "C" int hjr_denoise_var(hjr_ctx* c, int render_mode, uint32_t in_w, uint3
     return denoise_host_impl(c, render_mode, in_w, in_h, color, albedo, normal, true, variance, out, out_w, out_h);
 }
 
+// ---- spatial variance estimate (csrc/hjr_denoise.hip.h; include/henjou_hip.h: hjr_estimate_variance)
+static int estimate_variance_check(const hjr_ctx* c, uint32_t w, uint32_t h, const void* color, const void* albedo, const void* normal, const void* variance_out)
+{
+    if (!c || !color || !variance_out) { set_error("hjr_estimate_variance: null argument"); return HJR_ERR_ARG; }
+    if (w == 0 || h == 0 || w > 16384 || h > 16384) { set_error("hjr_estimate_variance: bad image size"); return HJR_ERR_ARG; }
+    if (!albedo || !normal) { set_error("hjr_estimate_variance: the albedo and normal guide AOVs are required"); return HJR_ERR_ARG; }
+    return HJR_OK;
+}
+// the kernel on device memory; the callers checked the arguments.  d_vin NULL = every pixel unknown; d_vout may be d_vin
+static int estimate_variance_launch(uint32_t w, uint32_t h, const void* d_color, const void* d_albedo, const void* d_normal, const void* d_vin, void* d_vout, hipStream_t st)
+{
+    hipLaunchKernelGGL(hjr_spatial_var_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, (const float4*)d_color, (const float4*)d_normal, (const float4*)d_albedo,
+                       (const float*)d_vin, (float*)d_vout, (int)w, (int)h);
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+extern "C" int hjr_estimate_variance_device(hjr_ctx* c, uint32_t w, uint32_t h, const void* d_color, const void* d_albedo, const void* d_normal, const void* d_variance_in,
+                                            void* d_variance_out, void* hip_stream)
+{
+    if (const int rc = estimate_variance_check(c, w, h, d_color, d_albedo, d_normal, d_variance_out)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return estimate_variance_launch(w, h, d_color, d_albedo, d_normal, d_variance_in, d_variance_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+extern "C" int hjr_estimate_variance(hjr_ctx* c, uint32_t w, uint32_t h, const float* color, const float* albedo, const float* normal, const float* variance_in,
+                                     float* variance_out)
+{
+    if (const int rc = estimate_variance_check(c, w, h, color, albedo, normal, variance_out)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t bytes = (size_t)w * h * 16;
+    if (!c->d_color.reserve(bytes) || !c->d_albedo.reserve(bytes) || !c->d_normal.reserve(bytes) || !c->d_variance.reserve(bytes / 4)) {
+        set_error("hjr_estimate_variance: allocation failed");
+        return HJR_ERR_DEVICE;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_color.p, color, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_albedo.p, albedo, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_normal.p, normal, bytes, hipMemcpyHostToDevice, c->stream));
+    if (variance_in) HIPCHK(hipMemcpyAsync(c->d_variance.p, variance_in, bytes / 4, hipMemcpyHostToDevice, c->stream));
+    if (const int rc = estimate_variance_launch(w, h, c->d_color.p, c->d_albedo.p, c->d_normal.p, variance_in ? c->d_variance.p : nullptr, c->d_variance.p, c->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(variance_out, c->d_variance.p, bytes / 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return HJR_OK;
+}
+
 // ---- temporal accumulation with reprojection (csrc/hjr_temporal.hip.h; include/henjou_hip.h)
 // G-buffer pass on device memory: the classifier's launch shape (one wave per tile, its stacks in dynamic LDS)
 static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hipStream_t st)
@@ -1308,11 +1351,14 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
 // What a frame in a render mode runs once its AOVs stand in the context's d_color / d_albedo / d_normal (/ d_variance), whether a render left
 // them there (hjr_render_denoised) or the assembly of gathered shards (hjr_denoise_shards_device): the temporal stage if the option is on
 // (`commit`: this call ends the frame), then the filter, plain or variance-guided, and the upscale of DenoiseUpScale2X.  All on `st`.
+// Option "denoise_variance_spatial" with a variance in play: ahead of both, pixels of unknown variance get the spatial estimate, in place.
 static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool temporal, bool with_var, bool commit, void* d_out, uint32_t out_w, uint32_t out_h,
                               hipStream_t st)
 {
     const bool guides = render_mode != HJR_MODE_DEFAULT;
     const void *f_color = c->d_color.p, *f_var = with_var ? c->d_variance.p : nullptr; // what the filter reads
+    if (guides && with_var && c->opt.get(hjr::OPT_DENOISE_VARIANCE_SPATIAL, 0) != 0)
+        if (const int rc = estimate_variance_launch(p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, c->d_variance.p, c->d_variance.p, st)) return rc;
     if (temporal)
         if (const int rc = temporal_stage(c, p, render_mode, commit, f_color, f_var, st)) return rc;
     return denoise_device_impl(c, render_mode, p->width, p->height, f_color, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var, f_var, d_out,

@@ -173,6 +173,9 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 if (!(n >= 0 && n <= 64) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.firefly_clamp must be an integer in [0, 64]");
                 o.device_bvh_opt |= (int32_t)n << 16;
             }
+            // denoise_variance_spatial: the 3 x 3 estimate for pixels of unknown variance (option "denoise_variance_spatial"), bit 10 of the same
+            // spare bits; it acts only where "denoise_variance" / "denoise_temporal" put a variance in play and is accepted without them
+            if (flag("denoise_variance_spatial")) o.device_bvh_opt |= 0x400;
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
             if (const Json* v = h->find("passes")) {
                 const double n = v->is_number() ? v->as_number() : -1.0;

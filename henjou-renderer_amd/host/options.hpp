@@ -11,7 +11,8 @@ enum Opt {
     OPT_PIPELINE, OPT_LDS_BVH, OPT_LDS_STACK16, OPT_BVH_WIDTH, OPT_LEAF_MAX, OPT_NODE_MIN, OPT_HOLD_MIN, OPT_HOLD_AGE, OPT_SHORT_STACK,
     OPT_BLOCKS_PER_CU, OPT_TILE_ORDER, OPT_WF_CAP, OPT_WF_REFILL, OPT_WF_PREFETCH_MIN, OPT_WF_TRACE_MIN, OPT_HOST_THREADS, OPT_VERBOSE,
     OPT_FORCE_REBUILD, OPT_TOP_NODES, OPT_BVH_REFINE, OPT_DEVICE_BVH, OPT_DEVICE_BVH_OPT, OPT_DENOISE_VARIANCE, OPT_DENOISE_TEMPORAL, OPT_DEVICE_BVH_REFIT,
-    OPT_DEVICE_BVH_REFIT_GROWTH, OPT_DEVICE_BVH_INSTANCES, OPT_DEVICE_BVH_GRAFT, OPT_FIREFLY_CLAMP, OPT_ITEM_CHUNKS, OPT_COUNT
+    OPT_DEVICE_BVH_REFIT_GROWTH, OPT_DEVICE_BVH_INSTANCES, OPT_DEVICE_BVH_GRAFT, OPT_FIREFLY_CLAMP, OPT_ITEM_CHUNKS, OPT_DENOISE_VARIANCE_SPATIAL,
+    OPT_COUNT
 };
 struct OptDesc { const char* key; int lo, hi; };
 // value -1 always means "the library's default"; the ranges are those of explicit values
@@ -48,6 +49,7 @@ inline const OptDesc* opt_table()
         { "device_bvh_graft", 0, 1 },            // device_bvh 1 and device_bvh_instances 1: every instance's BVH4 collapsed once and grafted under a BVH4 top tree per commit (default 0; ignored otherwise) [next hjr_set_transforms]
         { "firefly_clamp", 0, 64 },              // kappa of the firefly clamp on whole-frame renders: chunk sums above kappa x the pixel's median chunk are scaled down to it (default 0 = off; 4 recommended; biased)
         { "item_chunks", 1, 8 },                 // megakernel: consecutive chunks of a pixel in one work item: 1, 2, 4 or 8; a launch uses the largest power of two <= this that divides its chunk count (default: measured per launch kind, hjr_device.hip)
+        { "denoise_variance_spatial", 0, 1 },    // "denoise_variance" / "denoise_temporal" on: 1 fills pixels whose variance is unknown (frames of at most 8 spp, a first one-granule pass) with a 3 x 3 guide-weighted estimate in front of the temporal stage and the filter (default 0; no effect otherwise)
     };
     return t;
 }

@@ -77,6 +77,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (opt.device_bvh_opt & 0x200) (void)hjr_set_option(ctx, "device_bvh_graft", 1); // key "device_bvh_graft": bit 9
     if (opt.denoise_variance && opt.render_mode != HJR_MODE_DEFAULT) (void)hjr_set_option(ctx, "denoise_variance", 1); // (Default mode has no filter)
     if (temporal) (void)hjr_set_option(ctx, "denoise_temporal", 1);
+    if (opt.device_bvh_opt & 0x400) (void)hjr_set_option(ctx, "denoise_variance_spatial", 1); // key "denoise_variance_spatial": bit 10
     if (firefly) (void)hjr_set_option(ctx, "firefly_clamp", firefly);
     const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes
     rc = hjr_upload_scene(ctx, &view);

@@ -142,8 +142,9 @@ typedef struct hjr_render_option {
                                   * 1 + N: that and option "device_bvh_refit" N (key "device_bvh_refit": N; the struct does not grow for it) */
     int32_t device_bvh_opt;      /* default 0; low 8 bits: 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt");
                                   * bit 8: key "device_bvh_instances", bit 9: key "device_bvh_graft" (options of the same names; the
-                                  * struct does not grow for them); bits 16..22: key "firefly_clamp" 0..64 (option of the same name; the
-                                  * field is the section's spare bits, the key has nothing to do with the BVH) */
+                                  * struct does not grow for them); bit 10: key "denoise_variance_spatial"; bits 16..22: key "firefly_clamp"
+                                  * 0..64 (options of the same names; the field is the section's spare bits, the keys have nothing to do
+                                  * with the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
     float noise_threshold;       /* default 0 (off); > 0: hjr_render_file / henjou_cli set hjr_adaptive.noise_threshold, render each frame in
@@ -455,6 +456,20 @@ int hjr_denoise_var(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, con
                     const float* aov_normal, const float* aov_variance, float* out, uint32_t out_w, uint32_t out_h);
 int hjr_denoise_var_device(hjr_ctx*, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
                            const void* d_normal, const void* d_variance, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream);
+/* The spatial variance estimate (what SVGF does while its history is short; csrc/hjr_denoise.hip.h has the arithmetic to the bit, DESIGN.md
+ * §11.3 what was measured): the variance AOV needs two full chunks of a pixel, so a frame of at most 8 spp, and a first one-granule sample
+ * pass, carry HJR_VARIANCE_UNKNOWN everywhere.  Every pixel whose input variance is unknown (>= HJR_VARIANCE_UNKNOWN after the filter's
+ * clamp, +Inf included) gets the guide-weighted variance of the luminance r + g + b over its 3 x 3 neighbourhood (the filter's normal and
+ * albedo weights, indices clamped to the frame); every other pixel keeps its input bits, NaN and negative values too.  An estimate that is
+ * not below HJR_VARIANCE_UNKNOWN is written as HJR_VARIANCE_UNKNOWN.  variance_in NULL = every pixel unknown.  w x h float4 colour, albedo and
+ * normal, w x h float variances.  HJR_ERR_ARG before anything is enqueued: a null colour, guide or output, an empty image, a side above
+ * 16384.  hjr_estimate_variance: host pointers, synchronous.  hjr_estimate_variance_device: device pointers, one launch, asynchronous on
+ * `hip_stream` (NULL = the context's stream); d_variance_out may be d_variance_in (in place: a pixel's input is read by the lane that writes
+ * it only). */
+int hjr_estimate_variance(hjr_ctx*, uint32_t w, uint32_t h, const float* aov_color, const float* aov_albedo, const float* aov_normal,
+                          const float* variance_in, float* variance_out);
+int hjr_estimate_variance_device(hjr_ctx*, uint32_t w, uint32_t h, const void* d_color, const void* d_albedo, const void* d_normal,
+                                 const void* d_variance_in, void* d_variance_out, void* hip_stream);
 /* ---- Temporal accumulation with reprojection (the temporal half of SVGF; csrc/hjr_temporal.hip.h has the arithmetic to the bit, DESIGN.md
  * §11.2 the rule, its limits and what was measured).  Two stateless building blocks and a context option that chains them.
  * G-buffer: the first hit of every pixel's centre ray (no RNG; the ray of the tile classifier) against the context's current frame data,
@@ -573,6 +588,13 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  with world_size > 1 (short, tail-bound) and for counting launches (HJR_FLAG_STATS), else what was measured
                                  fastest on one GPU (csrc/hjr_device.hip: HJR_ITEM_CHUNKS).  The wavefront kernels and MIS always run single chunks;
                                  hjr_stats.item_chunks reports what the last launch used
+   "denoise_variance_spatial" 0 1  1: with "denoise_variance" or "denoise_temporal" on, hjr_render_denoised and hjr_denoise_shards_device run
+                                 hjr_estimate_variance_device in place on the frame's variance AOV before the temporal stage and the filter:
+                                 pixels of unknown variance (every pixel of a frame of at most 8 spp or of a first one-granule sample pass) get
+                                 the 3 x 3 estimate, and the temporal stage propagates it by its own rule; a known variance is untouched, so
+                                 from 16 spp on the frame is the same bits as with 0.  Accepted and without effect when neither of the two
+                                 other options is on, and in HJR_MODE_DEFAULT.  The variance AOV of hjr_render_var is not changed by it.
+                                 Setting it (any value) drops the temporal history.  0 (default): today's call, bit for bit, the same launches
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
@@ -588,6 +610,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * "firefly_clamp": N (integer 0..64) of that section is stored in bits 16..22 of hjr_render_option.device_bvh_opt (the struct does not grow
  * for it; readers of the BVH bits mask the field as before) and sets the option of that name, single-GPU and --devices N; refused together
  * with "passes" > 1 or "noise_threshold" > 0: the rule needs every chunk sum of a pixel and a frame in sample passes keeps running sums only.
+ * "denoise_variance_spatial": true of that section is stored as bit 10 of hjr_render_option.device_bvh_opt (the struct does not grow for it; the
+ * key has nothing to do with the BVH) and sets the option of that name, single-GPU and on rank 0 of --devices N.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
