@@ -258,6 +258,9 @@ def lib():
             "hjr_temporal_accumulate": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_reset": [C.c_void_p],
+            "hjr_upscale_guided": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
+            "hjr_upscale_guided_device": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.c_void_p],
             "hjr_assemble_shards": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_assemble_shards_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_denoise_shards_device": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
@@ -664,6 +667,30 @@ class Device:
         _check(lib().hjr_temporal_accumulate(self._h, None if fp is None else C.byref(fp), C.byref(fc), color.ctypes.data, variance.ctypes.data,
                                              history.ctypes.data), "hjr_temporal_accumulate")
         return color, variance, history
+
+    def upscale_guided(self, color_lo, gbuffer_lo, cam, gbuffer_hi):
+        """hjr_upscale_guided on host arrays: color_lo float32 [h, w, 4] (the filtered half-size image), gbuffer_lo GBUFFER_DTYPE [h, w],
+        gbuffer_hi GBUFFER_DTYPE [oh, ow] with ow // 2 == w and oh // 2 == h (Device.gbuffer at both sizes from `cam`, a Camera or dict).
+        Returns float32 [oh, ow, 4]."""
+        color_lo = np.ascontiguousarray(color_lo, dtype=np.float32)
+        lo = np.ascontiguousarray(gbuffer_lo, dtype=GBUFFER_DTYPE)
+        hi = np.ascontiguousarray(gbuffer_hi, dtype=GBUFFER_DTYPE)
+        h, w = lo.shape
+        oh, ow = hi.shape
+        if color_lo.shape != (h, w, 4):
+            raise ValueError("color_lo must be [height, width, 4] of gbuffer_lo's size")
+        c = cam if isinstance(cam, Camera) else make_params(w, h, 1, cam).camera
+        out = np.zeros((oh, ow, 4), dtype=np.float32)
+        _check(lib().hjr_upscale_guided(self._h, w, h, color_lo.ctypes.data, lo.ctypes.data, C.byref(c), hi.ctypes.data, out.ctypes.data, ow, oh),
+               "hjr_upscale_guided")
+        return out
+
+    def upscale_guided_device(self, width, height, d_color_lo, d_gbuffer_lo, cam, d_gbuffer_hi, d_out, out_w, out_h, stream=None):
+        """hjr_upscale_guided_device: the same on device pointers (ints), one launch, asynchronous on a hipStream_t (int; None = the
+        context's stream); `cam` is a Camera or dict, read during the call."""
+        c = cam if isinstance(cam, Camera) else make_params(width, height, 1, cam).camera
+        _check(lib().hjr_upscale_guided_device(self._h, width, height, C.c_void_p(d_color_lo), C.c_void_p(d_gbuffer_lo), C.byref(c), C.c_void_p(d_gbuffer_hi),
+                                               C.c_void_p(d_out), out_w, out_h, C.c_void_p(stream) if stream else None), "hjr_upscale_guided_device")
 
     def temporal_reset(self):
         """hjr_temporal_reset: drops the history of option "denoise_temporal"; the next frame restarts everywhere."""

@@ -58,6 +58,31 @@
 // inflates the estimate of every window that holds it, the colour weight opens there and the firefly spreads.
 // One lane per pixel, 27 float4 and one float read, one float written; no LDS, no scratch.  0.055 ms at 1080p with every pixel unknown, 0.008 ms
 // with every pixel known, next to the 0.86 ms of the five filter passes that follow (profiles/spatial_var.json).
+//
+// The GUIDED UPSCALE (hjr_upscale_guided, option "upscale_guided"): a joint-bilateral 2x upscale for DenoiseUpScale2X.  The a-trous passes
+// are edge-avoiding so that colour does not cross a silhouette; the bilinear upscale below then crosses it again, and every geometric edge
+// of the output is a two-pixel ramp between unrelated surfaces.  Here an output pixel keeps only those bilinear taps that lie on the surface
+// its own centre ray hits, judged from two G-buffers of one camera (hjr_gbuffer_kernel at iw x ih and at ow x oh: the centre-ray expression
+// u = (2 (px + 0.5) - W) / H sees the same view at both sizes).  Specified to the bit; fp32 as written, no contraction, correctly rounded
+// divide.  Output pixel (X, Y) of ow x oh, low-resolution image iw x ih with ow / 2 == iw and oh / 2 == ih (integer division):
+//   1. TAPS.  x0, y0, fx, fy, gx = 1 - fx, gy = 1 - fy and the clamped xa, xb, ya, yb exactly as hjr_upscale2x_kernel computes them.
+//      Taps in order  a = (xa, ya), b = (xb, ya), c = (xa, yb), d = (xb, yb);  weights  w_a = gx * gy, w_b = fx * gy, w_c = gx * fy,
+//      w_d = fx * fy  (products of quarters: exact).
+//   2. RECORDS.  G = hi[Y * ow + X], T_k = lo[tap k], both hjr_gbuffer_px; cam: the one camera both G-buffers were traced from.
+//   3. VALIDITY of tap k.  If G.prim == 0xffffffff (a miss): valid iff T_k.prim == 0xffffffff.  Otherwise valid iff T_k.prim != 0xffffffff,
+//      T_k.inst == G.inst and both tests below hold (a NaN fails a comparison), with dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z:
+//        D = T_k.pos - G.pos;  view = G.pos - cam.pos;  vv = dot(view, view);  fh = cam.f * (float)ih;  fp2 = (vv * 4) / (fh * fh)  (the squared
+//        footprint of a LOW-resolution pixel at the point's distance);  nn = dot(G.ng, G.ng);  nd = dot(G.ng, D);  nt = T_k.ng;  cs = dot(G.ng, nt);
+//        plane test:   nd * nd <= ((K_PLANE * K_PLANE) * fp2) * nn,  K_PLANE = 1;
+//        normal test:  cs > 0  and  cs * cs >= ((K_NORMAL * K_NORMAL) * nn) * dot(nt, nt),  K_NORMAL = 0.9.
+//   4. RESULT.  All four taps valid, or none: the bilinear expression of hjr_upscale2x_kernel as written, all four channels (such a pixel has
+//      the BITS of the plain upscale).  Otherwise, from +0.0f, in tap order, over the valid taps only:  S = S + w_k;  C.c = C.c + tap.c * w_k
+//      (c = x, y, z, w);  out.c = C.c / S.   S >= 0.0625: no division by zero.
+// By construction: only pixels with at least one invalid tap change; memory is indexed by pixel coordinates only (no field of a caller-made
+// record is an index, so hostile records cannot fault); a G-buffer in which no tap is ever valid gives the bilinear image.
+// One lane per output pixel, 64 x 4 pixels per workgroup: 4 float4 colours, 4 low-resolution records and the lane's own record per lane (of
+// a 48-byte record the 32 bytes prim .. ng are used), neighbouring lanes share their taps (L1 / L2 hits).  No LDS, no scratch.
+// DESIGN.md §11.4 has the rehearsal and what was measured.
 #pragma once
 #include "hjr_math.hip.h"
 
@@ -206,5 +231,60 @@ __global__ void __launch_bounds__(256) hjr_upscale2x_kernel(const float4* __rest
     r.y = (a.y * gx + b.y * fx) * gy + (c.y * gx + d.y * fx) * fy;
     r.z = (a.z * gx + b.z * fx) * gy + (c.z * gx + d.z * fx) * fy;
     r.w = (a.w * gx + b.w * fx) * gy + (c.w * gx + d.w * fx) * fy;
+    out[(size_t)Y * ow + X] = r;
+}
+
+// the guided 2x upscale (header above): is the low-resolution record T on the surface of the output pixel's record G?
+#define HJR_UPSCALE_K_PLANE 1.0f
+#define HJR_UPSCALE_K_NORMAL 0.9f
+__device__ __forceinline__ bool hjr_upscale_tap_valid(const hjr_gbuffer_px& G, const hjr_gbuffer_px& T, float lim_plane, float lim_normal)
+{
+    if (G.prim == 0xffffffffu) return T.prim == 0xffffffffu;
+    if (T.prim == 0xffffffffu || T.inst != G.inst) return false;
+    const float dx = T.pos[0] - G.pos[0], dy = T.pos[1] - G.pos[1], dz = T.pos[2] - G.pos[2];
+    const float nd = (G.ng[0] * dx + G.ng[1] * dy) + G.ng[2] * dz;
+    const float cs = (G.ng[0] * T.ng[0] + G.ng[1] * T.ng[1]) + G.ng[2] * T.ng[2];
+    const float tt = (T.ng[0] * T.ng[0] + T.ng[1] * T.ng[1]) + T.ng[2] * T.ng[2];
+    return nd * nd <= lim_plane && cs > 0.0f && cs * cs >= lim_normal * tt;
+}
+
+__global__ void __launch_bounds__(256) hjr_upscale_guided_kernel(const float4* __restrict__ in, const hjr_gbuffer_px* __restrict__ lo, const hjr_gbuffer_px* __restrict__ hi,
+                                                                  float4* __restrict__ out, const hjr_camera cam, int iw, int ih, int ow, int oh)
+{
+    const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (X >= ow || Y >= oh) return;
+    const int x0 = (X & 1) ? (X >> 1) : (X >> 1) - 1, y0 = (Y & 1) ? (Y >> 1) : (Y >> 1) - 1;
+    const float fx = (X & 1) ? 0.25f : 0.75f, fy = (Y & 1) ? 0.25f : 0.75f;
+    const int xa = min(max(x0, 0), iw - 1), xb = min(max(x0 + 1, 0), iw - 1);
+    const int ya = min(max(y0, 0), ih - 1), yb = min(max(y0 + 1, 0), ih - 1);
+    const size_t ta = (size_t)ya * iw + xa, tb = (size_t)ya * iw + xb, tc = (size_t)yb * iw + xa, td = (size_t)yb * iw + xb;
+    const float4 a = in[ta], b = in[tb], c = in[tc], d = in[td];
+    const hjr_gbuffer_px G = hi[(size_t)Y * ow + X];
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const float vx = G.pos[0] - cam.pos[0], vy = G.pos[1] - cam.pos[1], vz = G.pos[2] - cam.pos[2];
+    const float vv = (vx * vx + vy * vy) + vz * vz;
+    const float fh = cam.f * (float)ih;
+    const float fp2 = (vv * 4.0f) / (fh * fh);
+    const float nn = (G.ng[0] * G.ng[0] + G.ng[1] * G.ng[1]) + G.ng[2] * G.ng[2];
+    const float lim_plane = ((HJR_UPSCALE_K_PLANE * HJR_UPSCALE_K_PLANE) * fp2) * nn;
+    const float lim_normal = (HJR_UPSCALE_K_NORMAL * HJR_UPSCALE_K_NORMAL) * nn;
+    const bool va = hjr_upscale_tap_valid(G, lo[ta], lim_plane, lim_normal), vb = hjr_upscale_tap_valid(G, lo[tb], lim_plane, lim_normal);
+    const bool vc = hjr_upscale_tap_valid(G, lo[tc], lim_plane, lim_normal), vd = hjr_upscale_tap_valid(G, lo[td], lim_plane, lim_normal);
+    const int n_valid = (int)va + (int)vb + (int)vc + (int)vd;
+    float4 r;
+    if (n_valid == 4 || n_valid == 0) {
+        r.x = (a.x * gx + b.x * fx) * gy + (c.x * gx + d.x * fx) * fy;
+        r.y = (a.y * gx + b.y * fx) * gy + (c.y * gx + d.y * fx) * fy;
+        r.z = (a.z * gx + b.z * fx) * gy + (c.z * gx + d.z * fx) * fy;
+        r.w = (a.w * gx + b.w * fx) * gy + (c.w * gx + d.w * fx) * fy;
+    } else {
+        const float wa = gx * gy, wb = fx * gy, wc = gx * fy, wd = fx * fy;
+        float S = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f, cw = 0.0f;
+        if (va) { S = S + wa; cx = cx + a.x * wa; cy = cy + a.y * wa; cz = cz + a.z * wa; cw = cw + a.w * wa; }
+        if (vb) { S = S + wb; cx = cx + b.x * wb; cy = cy + b.y * wb; cz = cz + b.z * wb; cw = cw + b.w * wb; }
+        if (vc) { S = S + wc; cx = cx + c.x * wc; cy = cy + c.y * wc; cz = cz + c.z * wc; cw = cw + c.w * wc; }
+        if (vd) { S = S + wd; cx = cx + d.x * wd; cy = cy + d.y * wd; cz = cz + d.z * wd; cw = cw + d.w * wd; }
+        r = make_float4(cx / S, cy / S, cz / S, cw / S);
+    }
     out[(size_t)Y * ow + X] = r;
 }

@@ -1348,21 +1348,101 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
     return HJR_OK;
 }
 
+// ---- guided 2x upscale (csrc/hjr_denoise.hip.h; include/henjou_hip.h: hjr_upscale_guided)
+#define HJR_GBUFFER_MAX_SIDE 8192u /* gbuffer_device_impl's limit */
+static int upscale_guided_check(const hjr_ctx* c, uint32_t in_w, uint32_t in_h, const void* color_lo, const void* gbuffer_lo, const hjr_camera* cam, const void* gbuffer_hi,
+                                const void* out, uint32_t out_w, uint32_t out_h)
+{
+    if (!c || !color_lo || !gbuffer_lo || !cam || !gbuffer_hi || !out) { set_error("hjr_upscale_guided: null argument"); return HJR_ERR_ARG; }
+    if (in_w == 0 || in_h == 0 || out_w == 0 || out_h == 0) { set_error("hjr_upscale_guided: empty image"); return HJR_ERR_ARG; }
+    if (out_w / 2u != in_w || out_h / 2u != in_h) { set_error("hjr_upscale_guided: the input is (out_w / 2, out_h / 2)"); return HJR_ERR_ARG; }
+    if (out_w > HJR_GBUFFER_MAX_SIDE || out_h > HJR_GBUFFER_MAX_SIDE) { set_error("hjr_upscale_guided: images larger than 8192 x 8192 are not supported"); return HJR_ERR_ARG; }
+    return HJR_OK;
+}
+// the kernel on device memory; the callers checked the arguments
+static int upscale_guided_launch(uint32_t in_w, uint32_t in_h, const void* d_color_lo, const void* d_gbuffer_lo, const hjr_camera& cam, const void* d_gbuffer_hi, void* d_out,
+                                 uint32_t out_w, uint32_t out_h, hipStream_t st)
+{
+    hipLaunchKernelGGL(hjr_upscale_guided_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(256), 0, st, (const float4*)d_color_lo, (const hjr_gbuffer_px*)d_gbuffer_lo,
+                       (const hjr_gbuffer_px*)d_gbuffer_hi, (float4*)d_out, cam, (int)in_w, (int)in_h, (int)out_w, (int)out_h);
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+extern "C" int hjr_upscale_guided_device(hjr_ctx* c, uint32_t in_w, uint32_t in_h, const void* d_color_lo, const void* d_gbuffer_lo, const hjr_camera* cam,
+                                         const void* d_gbuffer_hi, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream)
+{
+    if (const int rc = upscale_guided_check(c, in_w, in_h, d_color_lo, d_gbuffer_lo, cam, d_gbuffer_hi, d_out, out_w, out_h)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return upscale_guided_launch(in_w, in_h, d_color_lo, d_gbuffer_lo, *cam, d_gbuffer_hi, d_out, out_w, out_h, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+extern "C" int hjr_upscale_guided(hjr_ctx* c, uint32_t in_w, uint32_t in_h, const float* color_lo, const hjr_gbuffer_px* gbuffer_lo, const hjr_camera* cam,
+                                  const hjr_gbuffer_px* gbuffer_hi, float* out, uint32_t out_w, uint32_t out_h)
+{
+    if (const int rc = upscale_guided_check(c, in_w, in_h, color_lo, gbuffer_lo, cam, gbuffer_hi, out, out_w, out_h)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n_in = (size_t)in_w * in_h, n_out = (size_t)out_w * out_h;
+    // one temporary buffer: [colour | output | low-resolution records | output-size records] (float4 images first: they stay 16-byte aligned)
+    DevBuf buf;
+    if (!buf.reserve((n_in + n_out) * (16 + sizeof(hjr_gbuffer_px)))) { set_error("hjr_upscale_guided: device allocation failed"); return HJR_ERR_DEVICE; }
+    char* const d_color = (char*)buf.p, *const d_out = d_color + n_in * 16, *const d_lo = d_out + n_out * 16, *const d_hi = d_lo + n_in * sizeof(hjr_gbuffer_px);
+    hipError_t e = hipMemcpyAsync(d_color, color_lo, n_in * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lo, gbuffer_lo, n_in * sizeof(hjr_gbuffer_px), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_hi, gbuffer_hi, n_out * sizeof(hjr_gbuffer_px), hipMemcpyHostToDevice, c->stream);
+    int rc = HJR_OK;
+    if (e == hipSuccess) rc = upscale_guided_launch(in_w, in_h, d_color, d_lo, *cam, d_hi, d_out, out_w, out_h, c->stream);
+    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out, d_out, n_out * 16, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    buf.release();
+    if (rc != HJR_OK) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { set_error(std::string("hjr_upscale_guided: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
+    return HJR_OK;
+}
+// Option "upscale_guided" in DenoiseUpScale2X: what hjr_render_denoised and hjr_denoise_shards_device (`who`) check and allocate ahead of their
+// first enqueue, so that nothing of the guided stage can fail behind it: the size rule, gbuffer_device_impl's checks for both sizes, the
+// filter's ping-pong buffer the last pass goes to, and the two G-buffers (the temporal stage traces the render-size one itself).
+static int upscale_guided_reserve(hjr_ctx* c, const hjr_params* p, bool temporal, uint32_t out_w, uint32_t out_h, const char* who)
+{
+    if (const int rc = denoise_check_sizes(HJR_MODE_DENOISE_UPSCALE2X, p->width, p->height, out_w, out_h)) return rc;
+    if (!c->have_scene || !c->have_frame) { set_error(std::string(who) + ": option \"upscale_guided\" needs the frame data of this frame (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
+    if (out_w > HJR_GBUFFER_MAX_SIDE || out_h > HJR_GBUFFER_MAX_SIDE) { set_error(std::string(who) + ": option \"upscale_guided\" does not take outputs larger than 8192 x 8192"); return HJR_ERR_ARG; }
+    const size_t n_in = (size_t)p->width * p->height, n_out = (size_t)out_w * out_h;
+    if (!c->d_dn_a.reserve(n_in * 16) || (!temporal && !c->d_ug_lo.reserve(n_in * sizeof(hjr_gbuffer_px))) || !c->d_ug_hi.reserve(n_out * sizeof(hjr_gbuffer_px))) {
+        set_error(std::string(who) + ": allocation failed");
+        return HJR_ERR_DEVICE;
+    }
+    return HJR_OK;
+}
+
 // What a frame in a render mode runs once its AOVs stand in the context's d_color / d_albedo / d_normal (/ d_variance), whether a render left
 // them there (hjr_render_denoised) or the assembly of gathered shards (hjr_denoise_shards_device): the temporal stage if the option is on
 // (`commit`: this call ends the frame), then the filter, plain or variance-guided, and the upscale of DenoiseUpScale2X.  All on `st`.
 // Option "denoise_variance_spatial" with a variance in play: ahead of both, pixels of unknown variance get the spatial estimate, in place.
-static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool temporal, bool with_var, bool commit, void* d_out, uint32_t out_w, uint32_t out_h,
-                              hipStream_t st)
+// `guided` (option "upscale_guided" in DenoiseUpScale2X; the caller ran upscale_guided_reserve): the filter as in Denoise mode with its last
+// pass into the ping-pong buffer, the G-buffer at the render size (the temporal stage's of this frame if there is one) and at the output
+// size from the same camera, and the guided kernel in place of the bilinear one.
+static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool temporal, bool with_var, bool guided, bool commit, void* d_out, uint32_t out_w,
+                              uint32_t out_h, hipStream_t st)
 {
     const bool guides = render_mode != HJR_MODE_DEFAULT;
     const void *f_color = c->d_color.p, *f_var = with_var ? c->d_variance.p : nullptr; // what the filter reads
     if (guides && with_var && c->opt.get(hjr::OPT_DENOISE_VARIANCE_SPATIAL, 0) != 0)
         if (const int rc = estimate_variance_launch(p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, c->d_variance.p, c->d_variance.p, st)) return rc;
+    const int slot = c->tmp.cur; // the temporal stage's slot of this frame (a commit rotates the slots)
     if (temporal)
         if (const int rc = temporal_stage(c, p, render_mode, commit, f_color, f_var, st)) return rc;
-    return denoise_device_impl(c, render_mode, p->width, p->height, f_color, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var, f_var, d_out,
-                               out_w, out_h, st);
+    if (!guided)
+        return denoise_device_impl(c, render_mode, p->width, p->height, f_color, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var, f_var, d_out,
+                                   out_w, out_h, st);
+    void* const filtered = c->d_dn_a.p; // the last pass reads d_dn_b: the bilinear path's buffers
+    if (const int rc = denoise_device_impl(c, HJR_MODE_DENOISE, p->width, p->height, f_color, c->d_albedo.p, c->d_normal.p, with_var, f_var, filtered, p->width, p->height, st)) return rc;
+    const void* g_lo = temporal ? c->tmp.gbuf[slot].p : c->d_ug_lo.p;
+    if (!temporal)
+        if (const int rc = gbuffer_device_impl(c, p, c->d_ug_lo.p, st)) return rc;
+    hjr_params hi = *p;
+    hi.width = out_w; hi.height = out_h;
+    if (const int rc = gbuffer_device_impl(c, &hi, c->d_ug_hi.p, st)) return rc;
+    return upscale_guided_launch(p->width, p->height, filtered, g_lo, p->camera, c->d_ug_hi.p, d_out, out_w, out_h, st);
 }
 
 // One frame of Renderer's loop in a Denoise mode, on the device: optixLaunch -> denoise -> cpyGPUBufferToHost(AOV_Output)
@@ -1380,6 +1460,10 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     const bool temporal = guides && c->opt.get(hjr::OPT_DENOISE_TEMPORAL, 0) != 0; // option "denoise_temporal": accumulation over frames in front of the filter
     if (temporal && (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED))) { set_error("hjr_render_denoised: option \"denoise_temporal\" does not take world_size > 1 or HJR_FLAG_PACKED"); return HJR_ERR_ARG; }
     const bool with_var = guides && (temporal || c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0); // option "denoise_variance": the variance AOV and the variance-guided filter
+    const bool guided = render_mode == HJR_MODE_DENOISE_UPSCALE2X && c->opt.get(hjr::OPT_UPSCALE_GUIDED, 0) != 0; // option "upscale_guided": G-buffers and the guided upscale
+    if (guided && (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED))) { set_error("hjr_render_denoised: option \"upscale_guided\" does not take world_size > 1 or HJR_FLAG_PACKED"); return HJR_ERR_ARG; }
+    if (guided)
+        if (const int rc = upscale_guided_reserve(c, p, temporal, out_w, out_h, "hjr_render_denoised")) return rc;
     PassRange pr; // a sample pass: the running mean is filtered (a denoised preview; the last pass gives the one-shot call's image)
     if (const int rc = check_pass(c, p, (guides ? 7u : 1u) | (with_var ? 8u : 0u), pr)) return rc;
     if (with_var) {
@@ -1394,7 +1478,7 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     if (guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
     int rc = render_impl(c, p, pr, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var ? c->d_variance.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
-    rc = denoise_post_stage(c, p, render_mode, temporal, with_var, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
+    rc = denoise_post_stage(c, p, render_mode, temporal, with_var, guided, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
     if (rc != HJR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1441,6 +1525,8 @@ extern "C" int hjr_denoise_shards_device(hjr_ctx* c, const hjr_params* p_user, i
     if (!whole && (p->sample_begin >= p->sample_end || p->sample_end > p->spp)) { set_error("hjr_denoise_shards_device: bad sample range"); return HJR_ERR_ARG; }
     const bool temporal = c->opt.get(hjr::OPT_DENOISE_TEMPORAL, 0) != 0;
     const bool with_var = temporal || c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0;
+    const bool guided = render_mode == HJR_MODE_DENOISE_UPSCALE2X && c->opt.get(hjr::OPT_UPSCALE_GUIDED, 0) != 0;
+    if (guided && (out_w > HJR_GBUFFER_MAX_SIDE || out_h > HJR_GBUFFER_MAX_SIDE)) { set_error("hjr_denoise_shards_device: option \"upscale_guided\" does not take outputs larger than 8192 x 8192"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     hjr_shards s; // sized struct
     if (!hjr::abi_take(gathered, s, "hjr_denoise_shards_device")) return HJR_ERR_ARG;
@@ -1459,13 +1545,15 @@ extern "C" int hjr_denoise_shards_device(hjr_ctx* c, const hjr_params* p_user, i
         if (p->width > 8192 || p->height > 8192) { set_error("hjr_denoise_shards_device: option \"denoise_temporal\" does not take frames larger than 8192 x 8192"); return HJR_ERR_ARG; }
         if (const int rc = temporal_reserve(c, p)) return rc;
     }
+    if (guided) // the G-buffer passes' checks and buffers, ahead of the assembly
+        if (const int rc = upscale_guided_reserve(c, p, temporal, out_w, out_h, "hjr_denoise_shards_device")) return rc;
     if (!c->d_dn_a.reserve(in_bytes) || !c->d_dn_b.reserve(in_bytes) || (with_var && (!c->d_dnv_a.reserve(in_bytes / 4) || !c->d_dnv_b.reserve(in_bytes / 4)))) {
         set_error("hjr_denoise_shards_device: allocation failed"); // (the filter's ping-pong buffers: nothing may fail behind the first launch)
         return HJR_ERR_DEVICE;
     }
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     if (const int rc = assemble_launch(s, p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, with_var ? c->d_variance.p : nullptr, st)) return rc;
-    return denoise_post_stage(c, p, render_mode, temporal, with_var, whole || p->sample_end == p->spp, d_out, out_w, out_h, st);
+    return denoise_post_stage(c, p, render_mode, temporal, with_var, guided, whole || p->sample_end == p->spp, d_out, out_w, out_h, st);
 }
 
 // Round-trips every child ref the builder can emit for a tree that host/frame.cpp admits to the 16-bit-stack layout

@@ -80,6 +80,7 @@ struct hjr_ctx {
     // variance AOV (hjr_render_var) and variance-guided filter (hjr_denoise_var); nothing here is allocated before a call asks for a variance
     DevBuf d_variance;         // staging for the host-buffer entry points, one float per pixel
     DevBuf d_dnv_a, d_dnv_b;   // the filter's variance ping-pong, one float per pixel
+    DevBuf d_ug_lo, d_ug_hi;   // option "upscale_guided": the G-buffers at the render size (unless the temporal stage traced it) and at the output size
     hjr_stats stats;
     bool event_pending = false;
     // Frame data generation: hjr_upload_scene, hjr_set_lut, hjr_set_sky and a commit that replaces the frame data bump it, so a frame
@@ -120,7 +121,7 @@ struct hjr_ctx {
     void release_buffers()
     {
         for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
-                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_stat, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &d_variance, &d_dnv_a, &d_dnv_b, &ad.state, &ad.list })
+                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_stat, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &d_variance, &d_dnv_a, &d_dnv_b, &d_ug_lo, &d_ug_hi, &ad.state, &ad.list })
             b->release();
         for (int i = 0; i < 2; i++)
             for (DevBuf* b : { &tmp.color[i], &tmp.variance[i], &tmp.history[i], &tmp.gbuf[i], &tmp.xf[i] }) b->release();

@@ -176,6 +176,13 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             // denoise_variance_spatial: the 3 x 3 estimate for pixels of unknown variance (option "denoise_variance_spatial"), bit 10 of the same
             // spare bits; it acts only where "denoise_variance" / "denoise_temporal" put a variance in play and is accepted without them
             if (flag("denoise_variance_spatial")) o.device_bvh_opt |= 0x400;
+            // upscale_guided: the guided 2x upscale of DenoiseUpScale2X (option "upscale_guided"), bit 11 of the same spare bits; the other
+            // render modes accept it and ignore it
+            if (const Json* v = h->find("upscale_guided")) {
+                const bool ok = v->is_bool() || (v->is_number() && (v->as_number() == 0.0 || v->as_number() == 1.0));
+                if (!ok) throw JsonError("Henjou_HIP.upscale_guided must be true, false, 0 or 1");
+                if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x800;
+            }
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
             if (const Json* v = h->find("passes")) {
                 const double n = v->is_number() ? v->as_number() : -1.0;

@@ -142,7 +142,7 @@ typedef struct hjr_render_option {
                                   * 1 + N: that and option "device_bvh_refit" N (key "device_bvh_refit": N; the struct does not grow for it) */
     int32_t device_bvh_opt;      /* default 0; low 8 bits: 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt");
                                   * bit 8: key "device_bvh_instances", bit 9: key "device_bvh_graft" (options of the same names; the
-                                  * struct does not grow for them); bit 10: key "denoise_variance_spatial"; bits 16..22: key "firefly_clamp"
+                                  * struct does not grow for them); bit 10: key "denoise_variance_spatial"; bit 11: key "upscale_guided"; bits 16..22: key "firefly_clamp"
                                   * 0..64 (options of the same names; the field is the section's spare bits, the keys have nothing to do
                                   * with the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
@@ -503,6 +503,20 @@ int hjr_temporal_accumulate(hjr_ctx*, const hjr_temporal_frame* prev /* NULL = n
                             float* out_variance, float* out_history);
 int hjr_temporal_accumulate_device(hjr_ctx*, const hjr_temporal_frame* prev, const hjr_temporal_frame* cur, void* d_out_color, void* d_out_variance,
                                    void* d_out_history, void* hip_stream);
+/* The guided 2x upscale (csrc/hjr_denoise.hip.h has the arithmetic to the bit, DESIGN.md §11.4 what was measured): a joint-bilateral stand-in
+ * for the bilinear upscale of HJR_MODE_DENOISE_UPSCALE2X.  Every pixel of the out_w x out_h output takes the four bilinear taps (weights 0.75 /
+ * 0.25, clamped indices) of the in_w x in_h colour image and keeps those whose low-resolution G-buffer record shows the surface of the output
+ * pixel's own record: both misses, or the same instance, the tap's point within one low-resolution pixel footprint of the output pixel's
+ * tangent plane, and normals within acos(0.9).  The kept taps are renormalised; a pixel whose four taps all pass, or all fail, has the bits
+ * of the bilinear upscale.  gbuffer_lo (in_w x in_h) and gbuffer_hi (out_w x out_h) come from hjr_render_gbuffer with the one camera `cam`;
+ * records are compared, never used as indices, so caller-made ones cannot fault.  out_w / 2 == in_w and out_h / 2 == in_h (integer
+ * division; odd output sizes are legal).  HJR_ERR_ARG before anything is enqueued: a null pointer, an empty image, sizes that break the
+ * rule, an output side above 8192 (the G-buffer's limit).  hjr_upscale_guided: host pointers, synchronous.  hjr_upscale_guided_device: device
+ * pointers (cam stays a host pointer, read during the call), one launch, asynchronous on `hip_stream` (NULL = the context's stream). */
+int hjr_upscale_guided(hjr_ctx*, uint32_t in_w, uint32_t in_h, const float* color_lo, const hjr_gbuffer_px* gbuffer_lo, const hjr_camera* cam,
+                       const hjr_gbuffer_px* gbuffer_hi, float* out, uint32_t out_w, uint32_t out_h);
+int hjr_upscale_guided_device(hjr_ctx*, uint32_t in_w, uint32_t in_h, const void* d_color_lo, const void* d_gbuffer_lo, const hjr_camera* cam,
+                              const void* d_gbuffer_hi, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream);
 /* Drops the history that option "denoise_temporal" keeps in the context: the next frame restarts everywhere.  So do hjr_upload_scene,
  * hjr_set_lut, hjr_set_sky, a change of width, height or render mode, and setting the option. */
 int hjr_temporal_reset(hjr_ctx*);
@@ -595,6 +609,15 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  from 16 spp on the frame is the same bits as with 0.  Accepted and without effect when neither of the two
                                  other options is on, and in HJR_MODE_DEFAULT.  The variance AOV of hjr_render_var is not changed by it.
                                  Setting it (any value) drops the temporal history.  0 (default): today's call, bit for bit, the same launches
+   "upscale_guided" 0 1          1: hjr_render_denoised and hjr_denoise_shards_device in HJR_MODE_DENOISE_UPSCALE2X run the filter as today with its
+                                 last pass into a buffer at the render size, trace the G-buffer at the render size (the one "denoise_temporal"
+                                 traced for this frame is reused) and at out_w x out_h from the same hjr_params.camera, and run
+                                 hjr_upscale_guided_device instead of the bilinear upscale, all on the call's stream.  Composes with the filter
+                                 options, sample passes, adaptive passes and "firefly_clamp"; the temporal history stays at the render size.
+                                 hjr_render_denoised with world_size > 1 or HJR_FLAG_PACKED is HJR_ERR_ARG with it, hjr_denoise_shards_device
+                                 without current frame data HJR_ERR_STATE, an output side above 8192 HJR_ERR_ARG, each before anything is
+                                 enqueued.  The other modes ignore it; the stateless hjr_denoise[_var][_device] have no camera and keep the
+                                 bilinear upscale.  0 (default): today's call, bit for bit, the same launches
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
@@ -612,6 +635,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * with "passes" > 1 or "noise_threshold" > 0: the rule needs every chunk sum of a pixel and a frame in sample passes keeps running sums only.
  * "denoise_variance_spatial": true of that section is stored as bit 10 of hjr_render_option.device_bvh_opt (the struct does not grow for it; the
  * key has nothing to do with the BVH) and sets the option of that name, single-GPU and on rank 0 of --devices N.
+ * "upscale_guided": true (or false, 0, 1; anything else is a parse error) of that section is stored as bit 11 of the same field and sets the
+ * option of that name, single-GPU and on rank 0 of --devices N (the PNG is the single-GPU run's); Default and Denoise accept and ignore it.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);

@@ -1,0 +1,363 @@
+"""The guided 2x upscale on the GPU (hjr_upscale_guided, option "upscale_guided"; csrc/hjr_denoise.hip.h): the kernel bit
+for bit against the native checker tests/native/upscale_guided_ref.cpp in both forms, the set of pixels it changes, the option inside
+hjr_render_denoised (filter options, temporal frames, sample passes) and hjr_denoise_shards_device against the composition by hand from
+the stateless calls, the option off, every refusal, and the file level.
+
+The quality comparison of DESIGN.md §11.4 is NOT asserted here: on the CPU rehearsal (tools/upscale_guided_rehearsal.py) its condition
+failed from the camera at x = 3.5 (RMSE over the changed pixels of the mask 0.0614 guided against 0.0586 bilinear) under every value of the
+two constants, while from the scene's own camera the guided upscale halves that error (0.143 against 0.287).  The plan
+fixed before the rehearsal leaves the quality test out in that case; tools/upscale_guided_bench.py records the GPU's table."""
+import ctypes as C
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from scene_util import ROOT, Cornell, hjr
+from temporal_util import camera_at, wall_camera
+from test_gpu_denoise_shards import render_shards
+from test_gpu_progressive import with_range
+from test_upscale_guided_host import SHAPES, plane_and_misses, two_planes
+from upscale_guided_util import all_miss, bilinear_np, bits, changed_pixels, hostile_gbuffer, upscale_guided_ref
+
+pytestmark = pytest.mark.gpu
+CLI = os.path.join(ROOT, "henjou-renderer_amd", "henjou_cli")
+f32 = np.float32
+KEY = "upscale_guided"
+UP = hjr.MODE_DENOISE_UPSCALE2X
+ERR_ARG, ERR_STATE = -1, -5
+RW, RH, OW, OH = 35, 18, 70, 37  # render and output size of the stateful tests: odd output height, two 64-lane blocks, ragged tiles
+
+
+@pytest.fixture(scope="module")
+def cornell():
+    return Cornell()
+
+
+@pytest.fixture(scope="module")
+def dev(cornell):
+    """A context without any option: renders, G-buffers and the stateless calls."""
+    d = cornell.device()
+    yield d
+    d.close()
+
+
+def assert_bits(got, want, what):
+    assert got.shape == want.shape, what
+    same = bits(got) == bits(want)
+    assert same.all(), "%s: %d of %d values differ" % (what, int((~same).sum()), same.size)
+
+
+def hi_params(cornell, cam=None, w=OW, h=OH):
+    return hjr.make_params(w, h, 1, cam if cam is not None else cornell.camera)
+
+
+def compose(dev, cornell, p, filtered, cam=None, ow=OW, oh=OH):
+    """The tail of the composition by hand: two Device.gbuffer calls and Device.upscale_guided."""
+    cam = cam if cam is not None else cornell.camera
+    return dev.upscale_guided(filtered, dev.gbuffer(p), cam, dev.gbuffer(hi_params(cornell, cam, ow, oh)))
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1. the kernel
+@pytest.mark.parametrize("iw,ih,ow,oh", SHAPES + [(24, 16, 48, 32)])
+def test_kernel_equals_native_checker_host_and_device_form(cornell, dev, iw, ih, ow, oh):
+    """1 x 1 (every index clamped), odd sizes in both directions, the 64-lane and the 4-row workgroup boundary, and the bundled box, each
+    with real records (hjr_render_gbuffer at both sizes), synthetic planes, all-miss and hostile records (NaN, Inf, random words)."""
+    import torch
+    col = np.random.default_rng(iw * 100 + oh).exponential(0.5, (ih, iw, 4)).astype(f32)
+    cam = camera_at(cornell)
+    cases = {"real": (cam, dev.gbuffer(hjr.make_params(iw, ih, 1, cam)), dev.gbuffer(hjr.make_params(ow, oh, 1, cam))),
+             "planes": two_planes(iw, ih, ow, oh, True), "plane and misses": plane_and_misses(iw, ih, ow, oh),
+             "all-miss": (wall_camera(), all_miss(ih, iw), all_miss(oh, ow)),
+             "hostile": (wall_camera(), hostile_gbuffer(ih, iw, 21), hostile_gbuffer(oh, ow, 22)),
+             "hostile against real": (cam, dev.gbuffer(hjr.make_params(iw, ih, 1, cam)), hostile_gbuffer(oh, ow, 23))}
+    for name, (c, lo, hi) in cases.items():
+        want, count = upscale_guided_ref(col, lo, c, hi)
+        got = dev.upscale_guided(col, lo, c, hi)
+        assert_bits(got, want, "%s, host form" % name)
+        t_col = torch.from_numpy(col).cuda()
+        t_lo, t_hi = (torch.from_numpy(np.ascontiguousarray(g).view(np.uint8).reshape(-1).copy()).cuda() for g in (lo, hi))
+        out = torch.full((oh, ow, 4), -7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        dev.upscale_guided_device(iw, ih, t_col.data_ptr(), t_lo.data_ptr(), c, t_hi.data_ptr(), out.data_ptr(), ow, oh)
+        dev.synchronize()
+        assert_bits(out.cpu().numpy(), want, "%s, device form" % name)
+        if name == "all-miss":
+            assert_bits(got, bilinear_np(col, ow, oh), "all-miss is the bilinear image")
+    if (iw, ih) == (24, 16):
+        lo, hi = cases["real"][1], cases["real"][2]
+        assert (lo["prim"] != hjr.GBUFFER_MISS).any() and (lo["prim"] == hjr.GBUFFER_MISS).any() and (hi["prim"] != hjr.GBUFFER_MISS).mean() > 0.2
+
+
+def test_changed_pixels_are_those_with_one_to_three_valid_taps(cornell, dev):
+    """The guided image differs in bits from the bilinear one (the library's own 2x upscale of the same image) only where the checker counts
+    1 to 3 valid taps, and on the box it does differ."""
+    iw, ih, ow, oh = 24, 16, 48, 32
+    p = cornell.hjr_params(iw, ih, 8)
+    c, a, n = dev.render(p)
+    filtered = dev.denoise(hjr.MODE_DENOISE, c, a, n)
+    bilinear = dev.denoise(UP, c, a, n)
+    assert_bits(bilinear, bilinear_np(filtered, ow, oh), "the numpy restatement is the library's bilinear upscale")
+    lo, hi = dev.gbuffer(p), dev.gbuffer(hi_params(cornell, None, ow, oh))
+    guided = dev.upscale_guided(filtered, lo, cornell.camera, hi)
+    _, count = upscale_guided_ref(filtered, lo, cornell.camera, hi)
+    partial = (count > 0) & (count < 4)
+    changed = changed_pixels(guided, bilinear)
+    assert changed.any() and (changed <= partial).all()
+    assert 0.02 < partial.mean() < 0.6
+
+
+def test_argument_checks(cornell, dev):
+    L = hjr.lib()
+    col = np.zeros((2, 3, 4), f32)
+    lo, hi = all_miss(2, 3), all_miss(5, 7)
+    out = np.zeros((5, 7, 4), f32)
+    cam = hjr.make_params(3, 2, 1, cornell.camera).camera
+    ptr = [col.ctypes.data, lo.ctypes.data, C.addressof(cam), hi.ctypes.data, out.ctypes.data]
+
+    def call(iw, ih, args, ow, oh):
+        rcs = (L.hjr_upscale_guided(dev._h, iw, ih, *args, ow, oh), L.hjr_upscale_guided_device(dev._h, iw, ih, *args, ow, oh, None))
+        assert rcs[0] == rcs[1]
+        return rcs[0]
+
+    assert L.hjr_upscale_guided(dev._h, 3, 2, *ptr, 7, 5) == 0
+    for k in range(5):
+        assert call(3, 2, ptr[:k] + [None] + ptr[k + 1:], 7, 5) == ERR_ARG, "null pointer %d" % k
+    for iw, ih, ow, oh in ((0, 2, 1, 5), (3, 0, 7, 1), (3, 2, 0, 0), (3, 2, 8, 5), (3, 2, 7, 6), (3, 2, 5, 5), (3, 2, 3, 2), (4097, 2, 8194, 5), (3, 4097, 7, 8194)):
+        assert call(iw, ih, ptr, ow, oh) == ERR_ARG, (iw, ih, ow, oh)
+    assert b"hjr_upscale_guided" in L.hjr_last_error()
+    assert_bits(dev.upscale_guided(col, lo, cornell.camera, hi), out * 0, "the call after the refusals")
+    with pytest.raises(ValueError):
+        dev.upscale_guided(np.zeros((3, 3, 4), f32), lo, cornell.camera, hi)
+    with pytest.raises(hjr.HjrError):
+        dev.set_option(KEY, 2)
+    assert dev.get_option(KEY) == -1
+
+
+# ------------------------------------------------------------------------------------------------------------------ 2. hjr_render_denoised
+@pytest.mark.parametrize("variance,temporal", [(0, 0), (1, 0), (0, 1), (1, 1)], ids=["plain", "variance", "temporal", "variance+temporal"])
+def test_render_denoised_equals_the_composition_by_hand(cornell, dev, variance, temporal):
+    """Option on, DenoiseUpScale2X: render -> (temporal accumulation) -> filter in Denoise mode -> Device.gbuffer at both sizes ->
+    Device.upscale_guided, bit for bit; three frames with `frame` advancing in the temporal cases (the history stays at the render size)."""
+    cam = camera_at(cornell, x=3.5) if temporal else camera_at(cornell)
+    kw = dict(sky=tuple(cornell.opt.scene_sky_default), ibl_intensity=cornell.opt.IBL_intensity)
+    xf = (cornell.arrays["transforms"], cornell.arrays["inv_transforms"])
+    d = cornell.device()
+    try:
+        d.set_option("denoise_variance", variance)
+        d.set_option("denoise_temporal", temporal)
+        d.set_option(KEY, 1)  # (fails here without the feature: the key is unknown)
+        prev = None
+        for f in (1, 2, 3) if temporal else (1,):
+            p = hjr.make_params(RW, RH, 20, cam, frame=f, **kw)
+            c, a, n, v = dev.render(p, want_variance=True)
+            if temporal:
+                cur = {"camera": cam, "transforms": xf[0], "inv_transforms": xf[1], "gbuffer": dev.gbuffer(p), "color": c, "variance": v}
+                tc, tv, th = dev.temporal_accumulate(prev, cur)
+                prev = dict(cur, color=tc, variance=tv, history=th)
+                if f > 1:
+                    assert (th > 1).mean() > 0.5
+                filtered = dev.denoise(hjr.MODE_DENOISE, tc, a, n, variance=tv)
+            else:
+                filtered = dev.denoise(hjr.MODE_DENOISE, c, a, n, variance=v if variance else None)
+            want = compose(dev, cornell, p, filtered, cam)
+            got = d.render_denoised(p, UP, OW, OH)
+            assert_bits(got, want, "frame %d" % f)
+            assert changed_pixels(got, bilinear_np(filtered, OW, OH)).any()
+    finally:
+        d.close()
+
+
+def test_two_sample_passes(cornell, dev):
+    """24 spp in the passes [0, 8) and [8, 24) with "denoise_variance": each pass is the composition on that pass's running mean (the
+    G-buffers do not depend on the pass); the second is the one-shot call's image."""
+    p = cornell.hjr_params(RW, RH, 24)
+    d = cornell.device()
+    try:
+        d.set_option("denoise_variance", 1)
+        d.set_option(KEY, 1)
+        one_shot = d.render_denoised(p, UP, OW, OH)
+        c, a, n, v = dev.render(p, want_variance=True)
+        assert_bits(one_shot, compose(dev, cornell, p, dev.denoise(hjr.MODE_DENOISE, c, a, n, variance=v)), "one shot")
+        c, a, n, v = dev.render(with_range(p, 0, 8), want_variance=True)
+        first = d.render_denoised(with_range(p, 0, 8), UP, OW, OH)
+        assert_bits(first, compose(dev, cornell, p, dev.denoise(hjr.MODE_DENOISE, c, a, n, variance=v)), "pass 1")
+        assert_bits(d.render_denoised(with_range(p, 8, 24), UP, OW, OH), one_shot, "pass 2")
+        assert not np.array_equal(first, one_shot)
+    finally:
+        d.close()
+
+
+def test_option_off_is_todays_image(cornell, dev):
+    """Never set, 0 and -1: the existing composition (hjr_denoise / hjr_denoise_var in the 2x mode).  Denoise and Default with the option on:
+    their images of today."""
+    p = cornell.hjr_params(RW, RH, 20)
+    c, a, n, v = dev.render(p, want_variance=True)
+    d = cornell.device()
+    try:
+        plain, var = dev.denoise(hjr.MODE_DENOISE, c, a, n), dev.denoise(hjr.MODE_DENOISE, c, a, n, variance=v)
+        assert_bits(d.render_denoised(p, UP, 2 * RW, 2 * RH), dev.denoise(UP, c, a, n), "never set, hjr_denoise in the 2x mode")
+        assert_bits(d.render_denoised(p, UP, OW, OH), bilinear_np(plain, OW, OH), "never set, odd output")
+        for value in (0, -1):
+            d.set_option(KEY, value)
+            assert_bits(d.render_denoised(p, UP, 2 * RW, 2 * RH), dev.denoise(UP, c, a, n), "option %d" % value)
+            d.set_option("denoise_variance", 1)
+            assert_bits(d.render_denoised(p, UP, 2 * RW, 2 * RH), dev.denoise(UP, c, a, n, variance=v), "option %d, hjr_denoise_var in the 2x mode" % value)
+            d.set_option("denoise_variance", 0)
+        d.set_option(KEY, 1)
+        assert_bits(d.render_denoised(p, hjr.MODE_DENOISE), plain, "Denoise ignores the option")
+        assert_bits(d.render_denoised(p, hjr.MODE_DEFAULT), c, "Default ignores the option")
+        d.set_option("denoise_variance", 1)
+        assert_bits(d.render_denoised(p, hjr.MODE_DENOISE), var, "Denoise with the variance filter ignores the option")
+    finally:
+        d.close()
+
+
+def test_composes_with_the_spatial_estimate_and_the_firefly_clamp(cornell, dev):
+    """4 spp with "denoise_variance" + "denoise_variance_spatial" (every variance estimated) and 32 spp with "firefly_clamp" 4: the guided
+    image is the guided upscale of what the same options give in Denoise mode."""
+    d = cornell.device()
+    try:
+        d.set_option(KEY, 1)
+        d.set_option("denoise_variance", 1)
+        d.set_option("denoise_variance_spatial", 1)
+        p = cornell.hjr_params(RW, RH, 4)
+        assert_bits(d.render_denoised(p, UP, OW, OH), compose(dev, cornell, p, d.render_denoised(p, hjr.MODE_DENOISE)), "spatial estimate")
+        d.set_option("denoise_variance_spatial", 0)
+        d.set_option("firefly_clamp", 4)
+        p = cornell.hjr_params(RW, RH, 32)
+        assert_bits(d.render_denoised(p, UP, OW, OH), compose(dev, cornell, p, d.render_denoised(p, hjr.MODE_DENOISE)), "firefly clamp")
+    finally:
+        d.close()
+
+
+def test_render_denoised_refusals(cornell):
+    """world_size > 1, HJR_FLAG_PACKED, sizes that break the rule and an output side above the G-buffer's limit are HJR_ERR_ARG with the
+    option on, before anything is enqueued; the context's next call succeeds."""
+    L = hjr.lib()
+    d = cornell.device()
+    try:
+        d.set_option(KEY, 1)
+        out = np.full((OH, OW, 4), -7.0, f32)
+        good = cornell.hjr_params(RW, RH, 8)
+
+        def call(p, ow=OW, oh=OH):
+            return L.hjr_render_denoised(d._h, C.byref(p), UP, out.ctypes.data, ow, oh), L.hjr_last_error().decode()
+
+        for p in (cornell.hjr_params(RW, RH, 8, rank=0, world_size=2), cornell.hjr_params(RW, RH, 8, flags=hjr.FLAG_PACKED)):
+            rc, msg = call(p)
+            assert rc == ERR_ARG and KEY in msg and (out == -7.0).all()
+        rc, msg = call(good, OW + 2, OH)
+        assert rc == ERR_ARG and (out == -7.0).all()
+        big = np.zeros(1, f32)  # never written: the call is refused before anything runs
+        rc = L.hjr_render_denoised(d._h, C.byref(cornell.hjr_params(4100, 1, 8)), UP, big.ctypes.data, 8200, 2)
+        assert rc == ERR_ARG and KEY in L.hjr_last_error().decode()
+        rc, msg = call(good)
+        assert rc == 0, msg
+        assert (out != -7.0).all()
+    finally:
+        d.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ 3. shards
+@pytest.mark.parametrize("filt", [None, "denoise_temporal"], ids=["plain", "temporal"])
+def test_shards_of_three_ranks_equal_the_one_rank_image(cornell, filt):
+    import torch
+    d = cornell.device()
+    try:
+        if filt:
+            d.set_option(filt, 1)
+        p = cornell.hjr_params(RW, RH, 20)
+        without = d.render_denoised(p, UP, OW, OH)
+        d.set_option(KEY, 1)
+        d.temporal_reset()  # (both images are first frames)
+        want = d.render_denoised(p, UP, OW, OH)
+        assert not np.array_equal(want, without)
+        d.temporal_reset()
+        buf, s = render_shards(torch, d, cornell, RW, RH, 20, 3, filt is not None)
+        assert_bits(d.denoise_shards(p, UP, s, OW, OH), want, "3 ranks")
+        del buf
+    finally:
+        d.close()
+
+
+def test_shards_refusals(cornell):
+    """HJR_ERR_STATE without current frame data, HJR_ERR_ARG for an output side above the limit; nothing is written, and the next call on
+    the context succeeds."""
+    import torch
+    L = hjr.lib()
+    ready = cornell.device()
+    d = hjr.Device(0)
+    try:
+        d.upload_scene(cornell.scene.view)  # no transforms yet: no frame data
+        buf, s = render_shards(torch, ready, cornell, RW, RH, 20, 3, False)
+        ready.set_option(KEY, 1)
+        want = ready.render_denoised(cornell.hjr_params(RW, RH, 20), UP, OW, OH)
+        out = torch.full((OH, OW, 4), -7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        p = cornell.hjr_params(RW, RH, 20)
+
+        def call(params=p, ow=OW, oh=OH):
+            rc = L.hjr_denoise_shards_device(d._h, C.byref(params), UP, C.byref(s), C.c_void_p(out.data_ptr()), ow, oh, None)
+            d.synchronize()
+            return rc, L.hjr_last_error().decode()
+
+        rc, msg = call()
+        assert rc == 0, msg  # the option off needs no frame data
+        assert_bits(out.cpu().numpy(), bilinear_np(ready.render_denoised(p, hjr.MODE_DENOISE), OW, OH), "option off: today's image")
+        out.fill_(-7.0)
+        torch.cuda.synchronize()
+        d.set_option(KEY, 1)
+        rc, msg = call()
+        assert rc == ERR_STATE and KEY in msg and "frame data" in msg and bool((out == -7.0).all())
+        d.set_transforms(cornell.arrays["transforms"], cornell.arrays["inv_transforms"])
+        rc, msg = call(ow=OW + 2)
+        assert rc == ERR_ARG and bool((out == -7.0).all())
+        rc = L.hjr_denoise_shards_device(d._h, C.byref(cornell.hjr_params(4100, 1, 20)), UP, C.byref(s), C.c_void_p(out.data_ptr()), 8200, 2, None)
+        assert rc == ERR_ARG and KEY in L.hjr_last_error().decode() and bool((out == -7.0).all())
+        rc, msg = call()
+        assert rc == 0, msg
+        assert_bits(out.cpu().numpy(), want, "the call after the refusals")
+        del buf
+    finally:
+        d.close()
+        ready.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ 4. file level
+def test_cli_upscale_guided_key(cornell, tmp_path):
+    """henjou_cli, Render_mode DenoiseUpScale2X, "Henjou_HIP": {"denoise_variance": true, "upscale_guided": true}: the PNG of the
+    composition by hand, single-process and through the per-rank code of --devices N (as a world of one: two ranks need two GPUs), and not
+    the frame the context gives with the option off.  (That Denoise and Default ignore the option is checked on the context, above.)"""
+    def run(name, mode, section, extra=()):
+        work = tmp_path / name
+        shutil.copytree(os.path.join(hjr.ASSETS, "Model"), work / "Model")
+        ro = json.load(open(os.path.join(hjr.ASSETS, "render_option_c1.json")))
+        ro["Image"].update(image_width=OW, image_height=OH, max_spp=20, image_name="ug")
+        ro["Animation"].update(start_frame=1, end_frame=2)
+        ro["Render_mode"] = mode
+        ro["Henjou_HIP"] = section
+        (work / "render_option.json").write_text(json.dumps(ro))
+        r = subprocess.run([CLI, "render_option.json", *extra], cwd=work, capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+        assert r.returncode == 0, r.stdout + r.stderr
+        return (work / "ug_001.png").read_bytes(), hjr.load_png(str(work / "ug_001.png"))
+
+    on_bytes, on = run("on", "DenoiseUpScale2X", {"denoise_variance": True, KEY: True})
+    rank_bytes, _ = run("rank", "DenoiseUpScale2X", {"denoise_variance": True, KEY: True}, ("--rank", "0", "--world", "1"))
+    assert rank_bytes == on_bytes, "rank path"
+    d = cornell.device()
+    try:
+        d.set_option("denoise_variance", 1)
+        p = cornell.hjr_params(RW, RH, 20, frame=1, seed=cornell.opt.seed)
+        exp = {}
+        for key in (1, 0):
+            d.set_option(KEY, key)
+            exp[key] = hjr.float4_to_srgb8(d.render_denoised(p, UP, OW, OH))[::-1]
+    finally:
+        d.close()
+    assert np.array_equal(on, exp[1]), "%d pixels differ" % int(np.sum(np.any(on != exp[1], axis=-1)))
+    assert not np.array_equal(on, exp[0]), "and not the frame of the option off"
