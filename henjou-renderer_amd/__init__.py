@@ -172,13 +172,14 @@ GBUFFER_DTYPE = np.dtype([("prim", "<u4"), ("inst", "<u4"), ("t", "<f4"), ("b1",
                           ("pad", "<u4")])
 GBUFFER_MISS = 0xffffffff
 TEMPORAL_ALPHA = np.float32(0.2)  # HJR_TEMPORAL_ALPHA
+TEMPORAL_SNAP = np.float32(0.125)  # HJR_TEMPORAL_SNAP
 
 
 class TemporalFrame(_Sized):
     """hjr_temporal_frame: one side (previous / current frame) of hjr_temporal_accumulate."""
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("n_instances", C.c_uint32), ("camera", Camera),
                 ("transforms12", C.c_void_p), ("inv_transforms12", C.c_void_p), ("gbuffer", C.c_void_p), ("color", C.c_void_p),
-                ("variance", C.c_void_p), ("history", C.c_void_p)]
+                ("variance", C.c_void_p), ("history", C.c_void_p), ("coverage", C.c_uint32)]
 
 
 class Shards(_Sized):
@@ -255,6 +256,8 @@ def lib():
             "hjr_copy_tile_samples": [C.c_void_p, C.c_void_p, C.c_size_t],
             "hjr_render_gbuffer": [C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_render_gbuffer_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_render_gbuffer_cov": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+            "hjr_render_gbuffer_cov_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_reset": [C.c_void_p],
@@ -619,17 +622,22 @@ class Device:
         self.synchronize()
         return out[:oh, :ow].cpu().numpy()
 
-    def gbuffer(self, params):
+    def gbuffer(self, params, coverage=0):
         """hjr_render_gbuffer: the first hit of every pixel's centre ray against the current frame data, GBUFFER_DTYPE [height, width]
-        (width, height and camera of `params` are read)."""
+        (width, height and camera of `params` are read).  coverage 2, 3 or 4: hjr_render_gbuffer_cov with that side, the same records
+        with pad = same | (side * side) << 8."""
         out = np.zeros((params.height, params.width), dtype=GBUFFER_DTYPE)
-        _check(lib().hjr_render_gbuffer(self._h, C.byref(params), out.ctypes.data), "hjr_render_gbuffer")
+        if coverage:
+            _check(lib().hjr_render_gbuffer_cov(self._h, C.byref(params), coverage, out.ctypes.data), "hjr_render_gbuffer_cov")
+        else:
+            _check(lib().hjr_render_gbuffer(self._h, C.byref(params), out.ctypes.data), "hjr_render_gbuffer")
         return out
 
     @staticmethod
     def _temporal_frame(d, keep):
         """dict -> TemporalFrame: camera (Camera or dict), transforms / inv_transforms [n, 12], gbuffer (GBUFFER_DTYPE [h, w]), color
-        [h, w, 4], variance [h, w] and, for the previous frame, history [h, w]."""
+        [h, w, 4], variance [h, w] and, for the previous frame, history [h, w]; optional coverage (non-zero: the G-buffer's pad words are
+        coverage counts)."""
         g = np.ascontiguousarray(d["gbuffer"], dtype=GBUFFER_DTYPE)
         h, w = g.shape
         m = np.ascontiguousarray(d["transforms"], dtype=np.float32).reshape(-1, 12)
@@ -645,6 +653,7 @@ class Device:
         arrs = [m, inv, g, col, var]
         f.transforms12, f.inv_transforms12 = m.ctypes.data if m.size else None, inv.ctypes.data if inv.size else None
         f.gbuffer, f.color, f.variance = g.ctypes.data, col.ctypes.data, var.ctypes.data
+        f.coverage = int(d.get("coverage") or 0)
         if d.get("history") is not None:
             hist = np.ascontiguousarray(d["history"], dtype=np.float32)
             if hist.shape != (h, w):
@@ -655,7 +664,7 @@ class Device:
         return f
 
     def temporal_accumulate(self, prev, cur):
-        """hjr_temporal_accumulate on dicts of arrays (keys: camera, transforms, inv_transforms, gbuffer, color, variance; prev also
+        """hjr_temporal_accumulate on dicts of arrays (keys: camera, transforms, inv_transforms, gbuffer, color, variance, optionally coverage; prev also
         history; prev None = no previous frame): returns (color [h, w, 4], variance [h, w], history [h, w])."""
         keep = []
         fc = self._temporal_frame(cur, keep)

@@ -97,6 +97,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     if (rank == 0 && temporal) HJRX(hjr_set_option(ctx, "denoise_temporal", 1));
     if (rank == 0 && (opt.device_bvh_opt & 0x400)) HJRX(hjr_set_option(ctx, "denoise_variance_spatial", 1)); // key "denoise_variance_spatial": bit 10 of the field
     if (rank == 0 && (opt.device_bvh_opt & 0x800)) HJRX(hjr_set_option(ctx, "upscale_guided", 1)); // key "upscale_guided": bit 11; rank 0 upscales, and has the frame data: it renders its own tiles
+    if (rank == 0 && ((opt.device_bvh_opt >> 12) & 7)) HJRX(hjr_set_option(ctx, "denoise_temporal_coverage", (opt.device_bvh_opt >> 12) & 7)); // key "denoise_temporal_coverage": bits 12..14; rank 0 accumulates
     if (firefly) HJRX(hjr_set_option(ctx, "firefly_clamp", firefly));
     HJRX(hjr_upload_scene(ctx, &view));
     // "noise_threshold": each rank stops its own converged tiles between the sample passes (the rule does not depend on the rank); the one

@@ -80,12 +80,12 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
     const int i = hjr::opt_find(key);
     if (i < 0) { set_error(std::string("hjr_set_option: unknown option \"") + (key ? key : "(null)") + "\""); return HJR_ERR_ARG; }
     const hjr::OptDesc& d = hjr::opt_table()[i];
-    if (value != -1 && (value < d.lo || value > d.hi || (i == hjr::OPT_BVH_WIDTH && value == 3) || ((i == hjr::OPT_WF_CAP || i == hjr::OPT_ITEM_CHUNKS) && (value & (value - 1)) != 0))) {
+    if (value != -1 && (value < d.lo || value > d.hi || hjr::opt_hole(i, value))) {
         set_error(std::string("hjr_set_option: value out of range for \"") + d.key + "\" (" + std::to_string(d.lo) + " .. " + std::to_string(d.hi) + ", or -1 for the default)");
         return HJR_ERR_ARG;
     }
     c->opt.v[i] = value;
-    if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL) c->tmp.have_prev = false; // setting either option drops the history
+    if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL || i == hjr::OPT_DENOISE_TEMPORAL_COVERAGE) c->tmp.have_prev = false; // setting any of these options drops the history
     if (i == hjr::OPT_HOST_THREADS) hjr::set_host_threads(value);
     return HJR_OK;
 }
@@ -1166,8 +1166,9 @@ extern "C" int hjr_estimate_variance(hjr_ctx* c, uint32_t w, uint32_t h, const f
 }
 
 // ---- temporal accumulation with reprojection (csrc/hjr_temporal.hip.h; include/henjou_hip.h)
-// G-buffer pass on device memory: the classifier's launch shape (one wave per tile, its stacks in dynamic LDS)
-static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hipStream_t st)
+// G-buffer pass on device memory: the classifier's launch shape (one wave per tile, its stacks in dynamic LDS).  side 0: the plain pass;
+// 2, 3, 4: the coverage pass (hjr_gbuffer_cov_kernel) with side x side sub-pixel rays
+static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hipStream_t st, uint32_t side = 0)
 {
     if (!c || !p || !d_out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
     if (!c->have_scene || !c->have_frame) { set_error("hjr_render_gbuffer: no frame data (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
@@ -1185,10 +1186,23 @@ static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hip
     a.out = (hjr_gbuffer_px*)d_out;
     const unsigned grid = (unsigned)std::min<uint64_t>(a.n_tiles, (uint64_t)c->n_cus * 16);
     const size_t smem = (size_t)64 * c->frame.stack_need * 4;
-    if (c->frame.width == 2) hipLaunchKernelGGL(hjr_gbuffer_kernel<2>, dim3(grid), dim3(64), smem, st, a);
+    if (side) {
+        GbufCovArgs b;
+        memset(&b, 0, sizeof(b));
+        b.g = a; b.tri_shade = (const uint32_t*)c->d_tri_shade.p; b.side = side;
+        if (c->frame.width == 2) hipLaunchKernelGGL(hjr_gbuffer_cov_kernel<2>, dim3(grid), dim3(64), smem, st, b);
+        else hipLaunchKernelGGL(hjr_gbuffer_cov_kernel<4>, dim3(grid), dim3(64), smem, st, b);
+    }
+    else if (c->frame.width == 2) hipLaunchKernelGGL(hjr_gbuffer_kernel<2>, dim3(grid), dim3(64), smem, st, a);
     else hipLaunchKernelGGL(hjr_gbuffer_kernel<4>, dim3(grid), dim3(64), smem, st, a);
     HIPCHK(hipGetLastError());
     return HJR_OK;
+}
+static bool coverage_side_ok(uint32_t side)
+{
+    if (side >= 2 && side <= 4) return true;
+    set_error("hjr_render_gbuffer_cov: side must be 2, 3 or 4");
+    return false;
 }
 extern "C" int hjr_render_gbuffer_device(hjr_ctx* c, const hjr_params* p_user, void* d_out, void* hip_stream)
 {
@@ -1196,7 +1210,20 @@ extern "C" int hjr_render_gbuffer_device(hjr_ctx* c, const hjr_params* p_user, v
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
     return gbuffer_device_impl(c, &params, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
-extern "C" int hjr_render_gbuffer(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out)
+static int gbuffer_host_impl(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out, uint32_t side);
+extern "C" int hjr_render_gbuffer(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out) { return gbuffer_host_impl(c, p_user, out, 0); }
+extern "C" int hjr_render_gbuffer_cov(hjr_ctx* c, const hjr_params* p_user, uint32_t side, hjr_gbuffer_px* out)
+{
+    return coverage_side_ok(side) ? gbuffer_host_impl(c, p_user, out, side) : HJR_ERR_ARG;
+}
+extern "C" int hjr_render_gbuffer_cov_device(hjr_ctx* c, const hjr_params* p_user, uint32_t side, void* d_out, void* hip_stream)
+{
+    hjr_params params; // sized struct
+    if (!coverage_side_ok(side)) return HJR_ERR_ARG;
+    if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer_cov")) { if (!c) set_error("hjr_render_gbuffer_cov: null context"); return HJR_ERR_ARG; }
+    return gbuffer_device_impl(c, &params, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream, side);
+}
+static int gbuffer_host_impl(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out, uint32_t side)
 {
     hjr_params params; // sized struct
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
@@ -1204,7 +1231,7 @@ extern "C" int hjr_render_gbuffer(hjr_ctx* c, const hjr_params* p_user, hjr_gbuf
     const size_t bytes = (size_t)params.width * params.height * sizeof(hjr_gbuffer_px);
     DevBuf buf;
     if (bytes && !buf.reserve(bytes)) { set_error("hjr_render_gbuffer: device allocation failed"); return HJR_ERR_DEVICE; }
-    int rc = gbuffer_device_impl(c, &params, bytes ? buf.p : (void*)out, c->stream);
+    int rc = gbuffer_device_impl(c, &params, bytes ? buf.p : (void*)out, c->stream, side);
     hipError_t e = hipSuccess;
     if (rc == HJR_OK) e = hipMemcpyAsync(out, buf.p, bytes, hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
@@ -1216,7 +1243,9 @@ extern "C" int hjr_render_gbuffer(hjr_ctx* c, const hjr_params* p_user, hjr_gbuf
 }
 
 // the accumulation kernel on device memory; the two frames were checked by the callers
-static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_color, void* d_var, void* d_hist, hipStream_t st)
+// prev_cov / cur_cov: the two sides' `coverage`; with both 0 the launch is hjr_temporal_kernel's, as before the coverage rules existed
+static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_color, void* d_var, void* d_hist, hipStream_t st,
+                           uint32_t prev_cov = 0, uint32_t cur_cov = 0)
 {
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
@@ -1225,7 +1254,13 @@ static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalS
     a.width = w; a.height = h; a.n_instances = n_inst;
     a.n_tris = c->have_scene ? c->scene.n_triangles : 0xffffffffu; // prim ids are checked against the uploaded scene
     a.out_color = (float4*)d_color; a.out_variance = (float*)d_var; a.out_history = (float*)d_hist;
-    hipLaunchKernelGGL(hjr_temporal_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, a);
+    if ((prev && prev_cov) || cur_cov) {
+        TemporalCovArgs b;
+        memset(&b, 0, sizeof(b));
+        b.a = a; b.prev_cov = prev ? prev_cov : 0u; b.cur_cov = cur_cov;
+        hipLaunchKernelGGL(hjr_temporal_cov_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, b);
+    }
+    else hipLaunchKernelGGL(hjr_temporal_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, a);
     HIPCHK(hipGetLastError());
     return HJR_OK;
 }
@@ -1258,7 +1293,8 @@ extern "C" int hjr_temporal_accumulate_device(hjr_ctx* c, const hjr_temporal_fra
     if (const int rc = temporal_take(prev_user, cur_user, prev, cur, have_prev)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const TemporalSide ps = have_prev ? temporal_side(prev) : TemporalSide(), cs = temporal_side(cur);
-    return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, hip_stream ? (hipStream_t)hip_stream : c->stream);
+    return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, hip_stream ? (hipStream_t)hip_stream : c->stream,
+                           have_prev ? prev.coverage : 0u, cur.coverage);
 }
 extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist)
 {
@@ -1289,7 +1325,8 @@ extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* pre
     }
     char* const o = (char*)buf.p + 2 * side;
     int rc = HJR_OK;
-    if (e == hipSuccess) rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream);
+    if (e == hipSuccess) rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream,
+                                              have_prev ? f[0].coverage : 0u, f[1].coverage);
     if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_color, o, npx * 16, hipMemcpyDeviceToHost, c->stream);
     if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_var, o + npx * 16, npx * 4, hipMemcpyDeviceToHost, c->stream);
     if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_hist, o + npx * 20, npx * 4, hipMemcpyDeviceToHost, c->stream);
@@ -1329,7 +1366,8 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
     const size_t nx = (size_t)n_inst * 48;
     const int k = t.cur;
     if (const int rc = temporal_reserve(c, p)) return rc;
-    if (const int rc = gbuffer_device_impl(c, p, t.gbuf[k].p, st)) return rc;
+    const uint32_t cov = (uint32_t)c->opt.get(hjr::OPT_DENOISE_TEMPORAL_COVERAGE, 0); // option "denoise_temporal_coverage": the coverage pass and rules 2' / 3' (setting it drops the history, so both slots agree)
+    if (const int rc = gbuffer_device_impl(c, p, t.gbuf[k].p, st, cov)) return rc;
     if (nx) {
         HIPCHK(hipMemcpyAsync(t.xf[k].p, c->last_m.data(), nx, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync((char*)t.xf[k].p + nx, c->last_inv.data(), nx, hipMemcpyHostToDevice, st));
@@ -1342,7 +1380,7 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
         s[i].color = (const float4*)t.color[q].p; s[i].variance = (const float*)t.variance[q].p; s[i].history = (const float*)t.history[q].p;
     }
     s[1].color = (const float4*)d_color; s[1].variance = (const float*)d_var; s[1].history = nullptr;
-    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, st)) return rc;
+    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, st, cov, cov)) return rc;
     d_color = t.color[k].p; d_var = t.variance[k].p;
     if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur = k ^ 1; }
     return HJR_OK;

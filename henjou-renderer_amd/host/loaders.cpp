@@ -183,6 +183,13 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 if (!ok) throw JsonError("Henjou_HIP.upscale_guided must be true, false, 0 or 1");
                 if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x800;
             }
+            // denoise_temporal_coverage: the coverage side of the temporal stage (option "denoise_temporal_coverage"), bits 12..14 of the same
+            // spare bits; accepted and without effect without "denoise_temporal"
+            if (const Json* v = h->find("denoise_temporal_coverage")) {
+                const double n = v->is_number() ? v->as_number() : -1.0;
+                if (!(n == 0.0 || n == 2.0 || n == 3.0 || n == 4.0)) throw JsonError("Henjou_HIP.denoise_temporal_coverage must be 0, 2, 3 or 4");
+                o.device_bvh_opt |= (int32_t)n << 12;
+            }
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
             if (const Json* v = h->find("passes")) {
                 const double n = v->is_number() ? v->as_number() : -1.0;

@@ -79,6 +79,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (temporal) (void)hjr_set_option(ctx, "denoise_temporal", 1);
     if (opt.device_bvh_opt & 0x400) (void)hjr_set_option(ctx, "denoise_variance_spatial", 1); // key "denoise_variance_spatial": bit 10
     if (opt.device_bvh_opt & 0x800) (void)hjr_set_option(ctx, "upscale_guided", 1); // key "upscale_guided": bit 11 (acts in DenoiseUpScale2X only)
+    if ((opt.device_bvh_opt >> 12) & 7) (void)hjr_set_option(ctx, "denoise_temporal_coverage", (opt.device_bvh_opt >> 12) & 7); // key "denoise_temporal_coverage": bits 12..14
     if (firefly) (void)hjr_set_option(ctx, "firefly_clamp", firefly);
     const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes
     rc = hjr_upload_scene(ctx, &view);

@@ -480,6 +480,13 @@ int hjr_estimate_variance_device(hjr_ctx*, uint32_t w, uint32_t h, const void* d
 typedef struct hjr_gbuffer_px { uint32_t prim, inst; float t, b1, b2; float pos[3]; float ng[3]; uint32_t pad; } hjr_gbuffer_px; /* 48 bytes */
 int hjr_render_gbuffer(hjr_ctx*, const hjr_params*, hjr_gbuffer_px* out);
 int hjr_render_gbuffer_device(hjr_ctx*, const hjr_params*, void* d_out, void* hip_stream);
+/* The coverage G-buffer: the same records, bit for bit, except `pad`.  After the centre ray every pixel traces side x side
+ * sub-pixel rays on a regular grid (no RNG; `side` is 2, 3 or 4) and counts those that land on the centre ray's surface: both miss, or both
+ * hit the same instance and the same material within one pixel footprint of the centre's tangent plane.  pad = same | (side * side) << 8;
+ * a miss record carries its counts too.  A pixel with same < side * side straddles two surfaces ("mixed").  Refuses what hjr_render_gbuffer
+ * refuses, and a `side` outside {2, 3, 4} with HJR_ERR_ARG, before anything is enqueued. */
+int hjr_render_gbuffer_cov(hjr_ctx*, const hjr_params*, uint32_t side, hjr_gbuffer_px* out);
+int hjr_render_gbuffer_cov_device(hjr_ctx*, const hjr_params*, uint32_t side, void* d_out, void* hip_stream);
 /* Accumulation: per pixel of the current frame, the surface point is taken back to object space with the current inverse transform of its
  * instance, forward with the previous transform, and projected with the previous camera; four bilinear taps of the previous frame's
  * accumulated colour, variance and history length are kept if they show the same instance and the same surface point (plane distance and
@@ -490,14 +497,23 @@ int hjr_render_gbuffer_device(hjr_ctx*, const hjr_params*, void* d_out, void* hi
  * (hjr_temporal_accumulate, synchronous) or device pointers (hjr_temporal_accumulate_device, asynchronous on `hip_stream`).  cur.history is
  * ignored.  width, height and n_instances must agree between the two sides, else HJR_ERR_ARG.  Outputs: float4 colour (alpha = cur's),
  * float variance, float history length, width x height each.  Caller-made records are range-checked before any table lookup: an instance
- * or prim id out of range is a miss (current pixel) or an invalid tap; prim ids are checked against the uploaded scene's triangle count. */
+ * or prim id out of range is a miss (current pixel) or an invalid tap; prim ids are checked against the uploaded scene's triangle count.
+ * Coverage (`coverage` != 0 on a side: its records' `pad` words are hjr_render_gbuffer_cov's; 0, or a caller whose struct ends before the
+ * field: the pad words are ignored and the rule is the one above, bit for bit).  A record of a side with coverage is mixed iff
+ * total = (pad >> 8) & 0xff is above 0 and (pad & 0xff) < total.  A current pixel that is not mixed takes no tap whose previous record is
+ * mixed.  A current pixel that is mixed keeps its history only from the previous pixel it coincides with: the reprojected position must lie
+ * within HJR_TEMPORAL_SNAP of a pixel centre in x and in y, that pixel is the only tap (weight 1, the usual validity tests) and, if the
+ * previous side carries coverage, its pad word must equal the current one; otherwise the pixel restarts.  pad is only compared, never an
+ * index. */
 #define HJR_TEMPORAL_ALPHA 0.2f  /* the published value */
+#define HJR_TEMPORAL_SNAP 0.125f /* a mixed pixel's reprojection may lie this many pixels off a pixel centre, per axis */
 typedef struct hjr_temporal_frame {
     uint32_t struct_size, width, height, n_instances;
     hjr_camera camera;
     const float *transforms12, *inv_transforms12;   /* n_instances x 12, as hjr_set_transforms */
     const hjr_gbuffer_px* gbuffer;
     const float *color /* float4 */, *variance /* float */, *history /* float: frames accumulated */;
+    uint32_t coverage;                              /* != 0: the G-buffer's pad words are coverage counts (hjr_render_gbuffer_cov) */
 } hjr_temporal_frame;
 int hjr_temporal_accumulate(hjr_ctx*, const hjr_temporal_frame* prev /* NULL = none */, const hjr_temporal_frame* cur, float* out_color,
                             float* out_variance, float* out_history);
@@ -618,6 +634,11 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  without current frame data HJR_ERR_STATE, an output side above 8192 HJR_ERR_ARG, each before anything is
                                  enqueued.  The other modes ignore it; the stateless hjr_denoise[_var][_device] have no camera and keep the
                                  bilinear upscale.  0 (default): today's call, bit for bit, the same launches
+   "denoise_temporal_coverage" 0 2 3 4  with "denoise_temporal" on: 2, 3 or 4 make hjr_render_denoised and hjr_denoise_shards_device run the
+                                 coverage pass (hjr_render_gbuffer_cov_device with that side) in place of the plain G-buffer pass, keep the coverage
+                                 records in the history slots and accumulate with `coverage` set on both sides (rules 2' and 3' of
+                                 csrc/hjr_temporal.hip.h).  1 and values above 4 are HJR_ERR_ARG.  No effect unless "denoise_temporal" is on.
+                                 Setting it (any value) drops the temporal history.  0 (default): today's call, bit for bit, the same launches
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
@@ -637,6 +658,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * key has nothing to do with the BVH) and sets the option of that name, single-GPU and on rank 0 of --devices N.
  * "upscale_guided": true (or false, 0, 1; anything else is a parse error) of that section is stored as bit 11 of the same field and sets the
  * option of that name, single-GPU and on rank 0 of --devices N (the PNG is the single-GPU run's); Default and Denoise accept and ignore it.
+ * "denoise_temporal_coverage": N (0, 2, 3 or 4; anything else is a parse error) of that section is stored in bits 12..14 of the same field and
+ * sets the option of that name, single-GPU and on rank 0 of --devices N; accepted and without effect without "denoise_temporal".
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);

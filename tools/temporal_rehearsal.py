@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/temporal_rehearsal.py [--size 48x32] [--ref-spp 4096] [--k-plane 1 --k-dist 3]
+"""tools/temporal_rehearsal.py [--size 48x32] [--ref-spp 4096] [--k-plane 1 --k-dist 3] [--coverage N [--snap 0.125]] [--seed 1] [--sequences SM]
 CPU rehearsal of the quality comparison of tests/test_gpu_temporal.py: no GPU, every stage from a CPU restatement.
 
   frames     the CPU oracle (oracle/), NEE, 16 spp, seed 1, frames 1..8 with `frame` advancing, camera at x = 3.5; the variance AOV by rule 7
@@ -9,8 +9,13 @@ CPU rehearsal of the quality comparison of tests/test_gpu_temporal.py (DESIGN.md
              triangles in numpy
   stages     tests/native/temporal_ref.cpp (accumulation) and tests/native/denoise_var_ref.cpp (variance-guided filter)
   reference  the oracle at --ref-spp samples, seed 7, of each frame's geometry (one for S, one per frame for M)
+  --coverage N (2, 3 or 4) adds a third column, the temporal path with the coverage G-buffer of side N and rules 2' / 3':
+             G-buffer and accumulation from tests/native/temporal_cov_ref.cpp (brute force over the world-space triangles in numpy's
+             float32), and prints §11.5's conditions; --snap overrides HJR_TEMPORAL_SNAP in the checker (the one re-tune); --seed is the
+             seed of the 16 spp frames; --json FILE appends the tables
 Prints the table and the conditions; exit status 1 if a condition of sequence S fails."""
 import argparse
+import json
 import os
 import sys
 
@@ -22,6 +27,7 @@ import oracle_binding as ob  # noqa: E402
 import trace_util  # noqa: E402
 from denoise_var_util import denoise_var_ref, variance_rule  # noqa: E402
 from scene_util import Cornell, hjr  # noqa: E402
+import temporal_cov_util as tcu  # noqa: E402
 from temporal_util import MISS, centre_rays, format_table, moved_consistent, quality_conditions, quality_table, temporal_ref  # noqa: E402
 
 f32 = np.float32
@@ -67,6 +73,11 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=4096)
     ap.add_argument("--k-plane", type=float, default=1.0)
     ap.add_argument("--k-dist", type=float, default=3.0)
+    ap.add_argument("--coverage", type=int, default=0, choices=(0, 2, 3, 4))
+    ap.add_argument("--snap", type=float, default=None)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sequences", default="SM")
+    ap.add_argument("--json", default=None)
     a = ap.parse_args()
     w, h = map(int, a.size.split("x"))
     cornell = Cornell()
@@ -75,9 +86,12 @@ def main():
     cam = cam.as_dict()
     n_tris = np.asarray(cornell.arrays["indices"]).size // 3
     ok = True
+    tables = {}
     for name, static in (("S", True), ("M", False)):
-        refs, out_var, out_tmp = [], [], []
-        prev = None
+        if name not in a.sequences:
+            continue
+        refs, out_var, out_tmp, out_cov = [], [], [], []
+        prev = prev_cov = None
         for f in range(1, FRAMES + 1):
             arrays = dict(cornell.arrays)
             if not static:
@@ -86,20 +100,38 @@ def main():
             if not static or f == 1:
                 ref = osc.render(cornell_params(cornell, w, h, a.ref_spp, cam, 1, 7), want_aovs=False)[0]
             refs.append(ref)
-            c, al, n, v = frame_cpu(osc, cornell_params(cornell, w, h, SPP, cam, f, 1), w, h)
+            c, al, n, v = frame_cpu(osc, cornell_params(cornell, w, h, SPP, cam, f, a.seed), w, h)
             cur = {"camera": cam, "transforms": arrays["transforms"], "inv_transforms": arrays["inv_transforms"], "gbuffer": gbuffer_cpu(osc, arrays, w, h, cam),
                    "color": c, "variance": v}
             tc, tv, th = temporal_ref(prev, cur, n_tris, (a.k_plane, a.k_dist))
             out_var.append(denoise_var_ref(1, c, al, n, v)[0])
             out_tmp.append(denoise_var_ref(1, tc, al, n, tv)[0])
             prev = dict(cur, color=tc, variance=tv, history=th)
+            if a.coverage:
+                g = tcu.gbuffer_cov_ref(*tcu.rows_from_arrays(arrays), w, h, cam, a.coverage)
+                cur = dict(cur, gbuffer=g, coverage=a.coverage)
+                cc, cv, ch = tcu.temporal_cov_ref(prev_cov, cur, n_tris, a.snap)
+                out_cov.append(denoise_var_ref(1, cc, al, n, cv)[0])
+                prev_cov = dict(cur, color=cc, variance=cv, history=ch)
+                print("%s frame %d, coverage %d: %d mixed pixels, mean history %.2f, restarted %.1f %%" % (name, f, a.coverage, int(tcu.mixed(g).sum()), float(ch.mean()),
+                                                                                                      100 * float((ch == 1).mean())), flush=True)
             print("%s frame %d: mean history %.2f, restarted %.1f %%" % (name, f, float(th.mean()), 100 * float((th == 1).mean())), flush=True)
             osc.close()
-        t = quality_table(refs, out_var, out_tmp)
-        print(format_table(name, t))
+        if a.coverage:
+            t = tcu.quality_table_cov(refs, out_var, out_tmp, out_cov)
+            print(tcu.format_table_cov(name, t))
+            for text, holds in tcu.conditions_s(t) if static else tcu.conditions_m(t):
+                print("%s   %s: %s" % (name, text, "holds" if holds else "FAILS"))
+        else:
+            t = quality_table(refs, out_var, out_tmp)
+            print(format_table(name, t))
+        tables[name] = t
         for text, holds in quality_conditions(t, static):
             print("%s   %s: %s" % (name, text, "holds" if holds else "FAILS"))
             ok = ok and (holds or not static)
+    if a.json:
+        with open(a.json, "a") as f:
+            f.write(json.dumps({"size": a.size, "seed": a.seed, "coverage": a.coverage, "snap": a.snap, "ref_spp": a.ref_spp, "tables": tables}) + "\n")
     return 0 if ok else 1
 
 
