@@ -3,6 +3,17 @@
 #pragma once
 #include "hjr_kernel.hip.h"
 
+// the stack of a lane of a one-wave workgroup that traces pixel-centre rays against the frame data in memory (the tile classifier, the G-buffer
+// pass): the lane's whole column in dynamic LDS, no overflow buffer, no staged tree top
+typedef LaneStack<uint32_t, 64, false> TileStack;
+__device__ __forceinline__ TileStack hjr_tile_stack()
+{
+    TileStack stack;
+    stack.lds = reinterpret_cast<uint32_t*>(hjr_smem) + threadIdx.x;
+    stack.spill = nullptr; stack.spill_stride = 0; stack.lds_n = 0; stack.n_over = 0; stack.top = nullptr; stack.n_top = 0u;
+    return stack;
+}
+
 // ---- cost-ordered tile list.  The frame ends when the slowest work item ends, and an item (8 samples of one pixel, each up
 // to 10 bounces, strictly sequential) can run for milliseconds: with plain scanline order the tail of the launch is whatever
 // the last tiles happen to cost (5 ms on a 64 x 64 frame, 15 % of an 18 ms launch when the frame is split over 8 GPUs).
@@ -13,10 +24,7 @@
 template <int WIDTH>
 __global__ void __launch_bounds__(64) hjr_classify_tiles_kernel(const KParams P)
 {
-    typedef LaneStack<uint32_t, 64, false> ST;
-    ST stack;
-    stack.lds = reinterpret_cast<uint32_t*>(hjr_smem) + threadIdx.x;
-    stack.spill = nullptr; stack.spill_stride = 0; stack.lds_n = 0; stack.n_over = 0; stack.top = nullptr; stack.n_top = 0u;
+    TileStack stack = hjr_tile_stack();
     uint32_t n_cls[4] = { 0u, 0u, 0u, 0u }; // per block; one atomic per class at the end (32 k atomics on four words cost 0.4 ms)
     for (uint32_t idx = blockIdx.x; idx < P.n_owned_tiles; idx += gridDim.x) {
         const uint32_t tile = idx * P.world + P.rank;
@@ -32,7 +40,7 @@ __global__ void __launch_bounds__(64) hjr_classify_tiles_kernel(const KParams P)
             const f3 d = normalize(cd * P.cam_f + cr * u + cu * v);
             Hit h;
             Counters cnt; cnt.box = cnt.tri = 0;
-            if (traverse<false, false, WIDTH, 64, ST>(P.nodes, P.tri_geom, V(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]), d, 0.001f, 1e16f, h, stack, cnt)) {
+            if (traverse<false, false, WIDTH, 64, TileStack>(P.nodes, P.tri_geom, V(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]), d, 0.001f, 1e16f, h, stack, cnt)) {
                 const float4* m = P.materials + f2bits(P.tri_geom[h.k * HJR_TRI_F4 + 2].z) * HJR_MAT_F4;
                 const float4 m0 = m[0], m3 = m[3];
                 cls = f2bits(m3.x) != 0 ? 0u : (f2bits(m3.y) != 0 ? 3u : (m0.w > 0.5f ? 2u : 1u));

@@ -43,7 +43,7 @@
 // HJR_VARIANCE_UNKNOWN everywhere and the variant above falls back to its guides.  This kernel fills such pixels with the guide-weighted
 // second central moment of the luminance over the 3 x 3 neighbourhood and leaves every known variance as it is.  Specified to the bit;
 // fp32 as written, no contraction, correctly rounded divide, p_exp = the portable exponential:
-//   K = fminf(fmaxf(vin, 0.0f), 1e30f)          (NaN -> 0: the clamp hjr_atrous_var_kernel applies to its input)
+//   K = fminf(fmaxf(vin, 0.0f), 1e30f)          (NaN -> 0: the clamp hjr_atrous_kernel<true> applies to its input)
 //   if K < 1e30f:  vout = vin as stored          (pass-through, the bits unchanged: negative values and NaN too, the filter clamps them)
 //   else (HJR_VARIANCE_UNKNOWN and above, +Inf):
 //     l = (c.x + c.y) + c.z of a tap's colour;  taps dy, dx in -1..1, rows outer, indices clamped to the frame, the centre included;
@@ -90,67 +90,50 @@
 #define HJR_DENOISE_SIGMA_L 4.0f
 #define HJR_DENOISE_VAR_EPS 1e-3f
 
-__global__ void __launch_bounds__(256) hjr_atrous_kernel(const float4* __restrict__ in, const float4* __restrict__ normal,
-                                                          const float4* __restrict__ albedo, float4* __restrict__ out,
-                                                          int W, int H, int step, float c_phi)
+#define HJR_DENOISE_N_PHI 0.25f
+#define HJR_DENOISE_A_PHI 0.05f
+
+// |a - b|^2 over x, y, z and the edge-stopping weight w? = min(p_exp(max(-q / phi, -87)), 1), as every rule above writes them
+__device__ __forceinline__ float hjr_dist2(const float4& a, const float4& b)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    const float hk[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
-    const float n_phi = 0.25f, a_phi = 0.05f;
-    const size_t c = (size_t)y * W + x;
-    const float4 c0 = in[c], n0 = normal[c], a0 = albedo[c];
-    const float s0 = (c0.x + c0.y) + c0.z;
-    const float rel = 0.01f + s0 * s0;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, cum = 0.0f;
-    for (int j = -2; j <= 2; j++) {
-        const int yy = min(max(y + j * step, 0), H - 1);
-        for (int i = -2; i <= 2; i++) {
-            const int xx = min(max(x + i * step, 0), W - 1);
-            const size_t t = (size_t)yy * W + xx;
-            const float4 ct = in[t], nt = normal[t], at = albedo[t];
-            float dx = c0.x - ct.x, dy = c0.y - ct.y, dz = c0.z - ct.z;
-            float d2 = dx * dx + dy * dy + dz * dz;
-            float wc = 1.0f;
-            if (c_phi > 0.0f) wc = fminf(p_exp(fmaxf(-(d2 / rel) / c_phi, -87.0f)), 1.0f);
-            dx = n0.x - nt.x; dy = n0.y - nt.y; dz = n0.z - nt.z;
-            d2 = dx * dx + dy * dy + dz * dz;
-            const float wn = fminf(p_exp(fmaxf(-d2 / n_phi, -87.0f)), 1.0f);
-            dx = a0.x - at.x; dy = a0.y - at.y; dz = a0.z - at.z;
-            d2 = dx * dx + dy * dy + dz * dz;
-            const float wa = fminf(p_exp(fmaxf(-d2 / a_phi, -87.0f)), 1.0f);
-            const float w = ((wc * wn) * wa) * (hk[j + 2] * hk[i + 2]);
-            sx = sx + ct.x * w; sy = sy + ct.y * w; sz = sz + ct.z * w;
-            cum = cum + w;
-        }
-    }
-    out[c] = make_float4(sx / cum, sy / cum, sz / cum, c0.w);
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return dx * dx + dy * dy + dz * dz;
+}
+__device__ __forceinline__ float hjr_edge_weight(float q, float phi) { return fminf(p_exp(fmaxf(-q / phi, -87.0f)), 1.0f); }
+
+// a variance as a pass of the variance-guided variant reads it: pass 0 (`clamp_in`) clamps its input
+__device__ __forceinline__ float hjr_read_variance(const float* __restrict__ vin, size_t t, int clamp_in)
+{
+    const float v = vin[t];
+    return clamp_in ? fminf(fmaxf(v, 0.0f), 1e30f) : v;
 }
 
-// one pass of the variance-guided variant (header above); `clamp_in`: pass 0 clamps the variance as it reads it
-__global__ void __launch_bounds__(256) hjr_atrous_var_kernel(const float4* __restrict__ in, const float* __restrict__ vin, const float4* __restrict__ normal,
-                                                              const float4* __restrict__ albedo, float4* __restrict__ out, float* __restrict__ vout,
-                                                              int W, int H, int step, int clamp_in)
+// One a-trous pass.  VAR false: the filter of the header's first block (vin, vout, clamp_in unused; c_phi 0: the colour term is off).
+// VAR true: a pass of the variance-guided variant (c_phi unused; `clamp_in`: pass 0 clamps the variance as it reads it).
+template <bool VAR>
+__global__ void __launch_bounds__(256) hjr_atrous_kernel(const float4* __restrict__ in, const float* __restrict__ vin, const float4* __restrict__ normal,
+                                                          const float4* __restrict__ albedo, float4* __restrict__ out, float* __restrict__ vout,
+                                                          int W, int H, int step, int clamp_in, float c_phi)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
     const float hk[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
-    const float k3[3] = { 0.25f, 0.5f, 0.25f };
-    const float n_phi = 0.25f, a_phi = 0.05f;
     const size_t c = (size_t)y * W + x;
     const float4 c0 = in[c], n0 = normal[c], a0 = albedo[c];
     const float l0 = (c0.x + c0.y) + c0.z;
-    float gv = 0.0f;
-    for (int j = -1; j <= 1; j++) {
-        const int yy = min(max(y + j, 0), H - 1);
-        for (int i = -1; i <= 1; i++) {
-            const int xx = min(max(x + i, 0), W - 1);
-            float vt = vin[(size_t)yy * W + xx];
-            if (clamp_in) vt = fminf(fmaxf(vt, 0.0f), 1e30f);
-            gv = gv + vt * (k3[j + 1] * k3[i + 1]);
+    float den = 0.01f + l0 * l0; // VAR false: the relative colour tolerance
+    if constexpr (VAR) {
+        const float k3[3] = { 0.25f, 0.5f, 0.25f };
+        float gv = 0.0f;
+        for (int j = -1; j <= 1; j++) {
+            const int yy = min(max(y + j, 0), H - 1);
+            for (int i = -1; i <= 1; i++) {
+                const int xx = min(max(x + i, 0), W - 1);
+                gv = gv + hjr_read_variance(vin, (size_t)yy * W + xx, clamp_in) * (k3[j + 1] * k3[i + 1]);
+            }
         }
+        den = HJR_DENOISE_SIGMA_L * sqrtf(gv) + HJR_DENOISE_VAR_EPS;
     }
-    const float den = HJR_DENOISE_SIGMA_L * sqrtf(gv) + HJR_DENOISE_VAR_EPS;
     float sx = 0.0f, sy = 0.0f, sz = 0.0f, cum = 0.0f, sv = 0.0f;
     for (int j = -2; j <= 2; j++) {
         const int yy = min(max(y + j * step, 0), H - 1);
@@ -158,24 +141,20 @@ __global__ void __launch_bounds__(256) hjr_atrous_var_kernel(const float4* __res
             const int xx = min(max(x + i * step, 0), W - 1);
             const size_t t = (size_t)yy * W + xx;
             const float4 ct = in[t], nt = normal[t], at = albedo[t];
-            float vt = vin[t];
-            if (clamp_in) vt = fminf(fmaxf(vt, 0.0f), 1e30f);
-            const float lt = (ct.x + ct.y) + ct.z;
-            const float wc = fminf(p_exp(fmaxf(-fabsf(l0 - lt) / den, -87.0f)), 1.0f);
-            float dx = n0.x - nt.x, dy = n0.y - nt.y, dz = n0.z - nt.z;
-            float d2 = dx * dx + dy * dy + dz * dz;
-            const float wn = fminf(p_exp(fmaxf(-d2 / n_phi, -87.0f)), 1.0f);
-            dx = a0.x - at.x; dy = a0.y - at.y; dz = a0.z - at.z;
-            d2 = dx * dx + dy * dy + dz * dz;
-            const float wa = fminf(p_exp(fmaxf(-d2 / a_phi, -87.0f)), 1.0f);
+            const float vt = VAR ? hjr_read_variance(vin, t, clamp_in) : 0.0f;
+            float wc = 1.0f;
+            if constexpr (VAR) wc = hjr_edge_weight(fabsf(l0 - ((ct.x + ct.y) + ct.z)), den);
+            else if (c_phi > 0.0f) wc = hjr_edge_weight(hjr_dist2(c0, ct) / den, c_phi);
+            const float wn = hjr_edge_weight(hjr_dist2(n0, nt), HJR_DENOISE_N_PHI);
+            const float wa = hjr_edge_weight(hjr_dist2(a0, at), HJR_DENOISE_A_PHI);
             const float w = ((wc * wn) * wa) * (hk[j + 2] * hk[i + 2]);
             sx = sx + ct.x * w; sy = sy + ct.y * w; sz = sz + ct.z * w;
             cum = cum + w;
-            sv = sv + vt * (w * w);
+            if constexpr (VAR) sv = sv + vt * (w * w);
         }
     }
     out[c] = make_float4(sx / cum, sy / cum, sz / cum, c0.w);
-    vout[c] = sv / (cum * cum);
+    if constexpr (VAR) vout[c] = sv / (cum * cum);
 }
 
 // the spatial variance estimate (header above); vin NULL = every pixel unknown; vout may be vin (neither is __restrict__)
@@ -184,7 +163,6 @@ __global__ void __launch_bounds__(256) hjr_spatial_var_kernel(const float4* __re
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const float n_phi = 0.25f, a_phi = 0.05f;
     const size_t c = (size_t)y * W + x;
     if (vin) {
         const float v0 = vin[c];
@@ -199,13 +177,7 @@ __global__ void __launch_bounds__(256) hjr_spatial_var_kernel(const float4* __re
             const size_t t = (size_t)yy * W + xx;
             const float4 ct = in[t], nt = normal[t], at = albedo[t];
             const float lt = (ct.x + ct.y) + ct.z;
-            float dx = n0.x - nt.x, dy = n0.y - nt.y, dz = n0.z - nt.z;
-            float d2 = dx * dx + dy * dy + dz * dz;
-            const float wn = fminf(p_exp(fmaxf(-d2 / n_phi, -87.0f)), 1.0f);
-            dx = a0.x - at.x; dy = a0.y - at.y; dz = a0.z - at.z;
-            d2 = dx * dx + dy * dy + dz * dz;
-            const float wa = fminf(p_exp(fmaxf(-d2 / a_phi, -87.0f)), 1.0f);
-            const float w = wn * wa;
+            const float w = hjr_edge_weight(hjr_dist2(n0, nt), HJR_DENOISE_N_PHI) * hjr_edge_weight(hjr_dist2(a0, at), HJR_DENOISE_A_PHI);
             s0 = s0 + w; s1 = s1 + w * lt; s2 = s2 + w * (lt * lt);
         }
     }
@@ -214,24 +186,41 @@ __global__ void __launch_bounds__(256) hjr_spatial_var_kernel(const float4* __re
     vout[c] = (v < 1e30f) ? v : 1e30f; // HJR_VARIANCE_UNKNOWN
 }
 
-// 2x bilinear upscale, pixel centres: source coordinate (X + 0.5) / 2 - 0.5, i.e. weights 0.75 / 0.25 towards the nearer texel,
-// indices clamped to the source frame; out = (a * (1 - fx) + b * fx) * (1 - fy) + (c * (1 - fx) + d * fx) * fy per channel.
-__global__ void __launch_bounds__(256) hjr_upscale2x_kernel(const float4* __restrict__ in, float4* __restrict__ out, int iw, int ih, int ow, int oh)
+// The taps of output pixel (X, Y) of a 2x upscale, pixel centres: source coordinate (X + 0.5) / 2 - 0.5, i.e. weights 0.75 / 0.25 towards
+// the nearer texel (fx, fy: the weights of the second tap column / row), indices clamped to the source frame; a, b, c, d: the taps' pixel indices
+struct Upscale2xTaps {
+    float fx, fy;
+    size_t a, b, c, d;
+};
+__device__ __forceinline__ Upscale2xTaps hjr_upscale2x_taps(int X, int Y, int iw, int ih)
 {
-    const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (X >= ow || Y >= oh) return;
     const int x0 = (X & 1) ? (X >> 1) : (X >> 1) - 1, y0 = (Y & 1) ? (Y >> 1) : (Y >> 1) - 1;
-    const float fx = (X & 1) ? 0.25f : 0.75f, fy = (Y & 1) ? 0.25f : 0.75f;
     const int xa = min(max(x0, 0), iw - 1), xb = min(max(x0 + 1, 0), iw - 1);
     const int ya = min(max(y0, 0), ih - 1), yb = min(max(y0 + 1, 0), ih - 1);
-    const float4 a = in[(size_t)ya * iw + xa], b = in[(size_t)ya * iw + xb], c = in[(size_t)yb * iw + xa], d = in[(size_t)yb * iw + xb];
+    Upscale2xTaps t;
+    t.fx = (X & 1) ? 0.25f : 0.75f; t.fy = (Y & 1) ? 0.25f : 0.75f;
+    t.a = (size_t)ya * iw + xa; t.b = (size_t)ya * iw + xb; t.c = (size_t)yb * iw + xa; t.d = (size_t)yb * iw + xb;
+    return t;
+}
+// out = (a * (1 - fx) + b * fx) * (1 - fy) + (c * (1 - fx) + d * fx) * fy per channel
+__device__ __forceinline__ float4 hjr_bilinear(const float4& a, const float4& b, const float4& c, const float4& d, float fx, float fy)
+{
     const float gx = 1.0f - fx, gy = 1.0f - fy;
     float4 r;
     r.x = (a.x * gx + b.x * fx) * gy + (c.x * gx + d.x * fx) * fy;
     r.y = (a.y * gx + b.y * fx) * gy + (c.y * gx + d.y * fx) * fy;
     r.z = (a.z * gx + b.z * fx) * gy + (c.z * gx + d.z * fx) * fy;
     r.w = (a.w * gx + b.w * fx) * gy + (c.w * gx + d.w * fx) * fy;
-    out[(size_t)Y * ow + X] = r;
+    return r;
+}
+
+// 2x bilinear upscale
+__global__ void __launch_bounds__(256) hjr_upscale2x_kernel(const float4* __restrict__ in, float4* __restrict__ out, int iw, int ih, int ow, int oh)
+{
+    const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (X >= ow || Y >= oh) return;
+    const Upscale2xTaps t = hjr_upscale2x_taps(X, Y, iw, ih);
+    out[(size_t)Y * ow + X] = hjr_bilinear(in[t.a], in[t.b], in[t.c], in[t.d], t.fx, t.fy);
 }
 
 // the guided 2x upscale (header above): is the low-resolution record T on the surface of the output pixel's record G?
@@ -253,14 +242,9 @@ __global__ void __launch_bounds__(256) hjr_upscale_guided_kernel(const float4* _
 {
     const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (X >= ow || Y >= oh) return;
-    const int x0 = (X & 1) ? (X >> 1) : (X >> 1) - 1, y0 = (Y & 1) ? (Y >> 1) : (Y >> 1) - 1;
-    const float fx = (X & 1) ? 0.25f : 0.75f, fy = (Y & 1) ? 0.25f : 0.75f;
-    const int xa = min(max(x0, 0), iw - 1), xb = min(max(x0 + 1, 0), iw - 1);
-    const int ya = min(max(y0, 0), ih - 1), yb = min(max(y0 + 1, 0), ih - 1);
-    const size_t ta = (size_t)ya * iw + xa, tb = (size_t)ya * iw + xb, tc = (size_t)yb * iw + xa, td = (size_t)yb * iw + xb;
-    const float4 a = in[ta], b = in[tb], c = in[tc], d = in[td];
+    const Upscale2xTaps t = hjr_upscale2x_taps(X, Y, iw, ih);
+    const float4 a = in[t.a], b = in[t.b], c = in[t.c], d = in[t.d];
     const hjr_gbuffer_px G = hi[(size_t)Y * ow + X];
-    const float gx = 1.0f - fx, gy = 1.0f - fy;
     const float vx = G.pos[0] - cam.pos[0], vy = G.pos[1] - cam.pos[1], vz = G.pos[2] - cam.pos[2];
     const float vv = (vx * vx + vy * vy) + vz * vz;
     const float fh = cam.f * (float)ih;
@@ -268,17 +252,14 @@ __global__ void __launch_bounds__(256) hjr_upscale_guided_kernel(const float4* _
     const float nn = (G.ng[0] * G.ng[0] + G.ng[1] * G.ng[1]) + G.ng[2] * G.ng[2];
     const float lim_plane = ((HJR_UPSCALE_K_PLANE * HJR_UPSCALE_K_PLANE) * fp2) * nn;
     const float lim_normal = (HJR_UPSCALE_K_NORMAL * HJR_UPSCALE_K_NORMAL) * nn;
-    const bool va = hjr_upscale_tap_valid(G, lo[ta], lim_plane, lim_normal), vb = hjr_upscale_tap_valid(G, lo[tb], lim_plane, lim_normal);
-    const bool vc = hjr_upscale_tap_valid(G, lo[tc], lim_plane, lim_normal), vd = hjr_upscale_tap_valid(G, lo[td], lim_plane, lim_normal);
+    const bool va = hjr_upscale_tap_valid(G, lo[t.a], lim_plane, lim_normal), vb = hjr_upscale_tap_valid(G, lo[t.b], lim_plane, lim_normal);
+    const bool vc = hjr_upscale_tap_valid(G, lo[t.c], lim_plane, lim_normal), vd = hjr_upscale_tap_valid(G, lo[t.d], lim_plane, lim_normal);
     const int n_valid = (int)va + (int)vb + (int)vc + (int)vd;
     float4 r;
-    if (n_valid == 4 || n_valid == 0) {
-        r.x = (a.x * gx + b.x * fx) * gy + (c.x * gx + d.x * fx) * fy;
-        r.y = (a.y * gx + b.y * fx) * gy + (c.y * gx + d.y * fx) * fy;
-        r.z = (a.z * gx + b.z * fx) * gy + (c.z * gx + d.z * fx) * fy;
-        r.w = (a.w * gx + b.w * fx) * gy + (c.w * gx + d.w * fx) * fy;
-    } else {
-        const float wa = gx * gy, wb = fx * gy, wc = gx * fy, wd = fx * fy;
+    if (n_valid == 4 || n_valid == 0) r = hjr_bilinear(a, b, c, d, t.fx, t.fy);
+    else {
+        const float gx = 1.0f - t.fx, gy = 1.0f - t.fy;
+        const float wa = gx * gy, wb = t.fx * gy, wc = gx * t.fy, wd = t.fx * t.fy;
         float S = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f, cw = 0.0f;
         if (va) { S = S + wa; cx = cx + a.x * wa; cy = cy + a.y * wa; cz = cz + a.z * wa; cw = cw + a.w * wa; }
         if (vb) { S = S + wb; cx = cx + b.x * wb; cy = cy + b.y * wb; cz = cz + b.z * wb; cw = cw + b.w * wb; }

@@ -1055,15 +1055,13 @@ static int denoise_device_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint3
     float4* pp[2] = { (float4*)c->d_dn_a.p, (float4*)c->d_dn_b.p };
     const float* vsrc = (const float*)d_variance;
     float* vp[2] = { (float*)c->d_dnv_a.p, (float*)c->d_dnv_b.p };
+    static decltype(&hjr_atrous_kernel<false>) const atrous[2] = { hjr_atrous_kernel<false>, hjr_atrous_kernel<true> }; // [with_var]
     for (int it = 0; it < HJR_ATROUS_PASSES; it++) {
         float4* dst = (!up && it == HJR_ATROUS_PASSES - 1) ? (float4*)d_out : pp[it & 1];
-        if (with_var) { // colour and variance ping-pong together; the colour term is on in all five passes
-            hipLaunchKernelGGL(hjr_atrous_var_kernel, grid, block, 0, st, src, vsrc, (const float4*)d_normal, (const float4*)d_albedo, dst, vp[it & 1], (int)in_w, (int)in_h,
-                               1 << it, it == 0 ? 1 : 0);
-            vsrc = vp[it & 1];
-        } else
-            hipLaunchKernelGGL(hjr_atrous_kernel, grid, block, 0, st, src, (const float4*)d_normal, (const float4*)d_albedo, dst, (int)in_w, (int)in_h,
-                               1 << it, it < 2 ? 0.0f : 1.0f / (float)(1 << (it - 2))); // colour term: off, off, 1, 0.5, 0.25
+        // plain: the colour term is off, off, 1, 0.5, 0.25.  with_var: colour and variance ping-pong together, pass 0 clamps the variance it reads
+        hipLaunchKernelGGL(atrous[with_var], grid, block, 0, st, src, vsrc, (const float4*)d_normal, (const float4*)d_albedo, dst, with_var ? vp[it & 1] : nullptr,
+                           (int)in_w, (int)in_h, 1 << it, it == 0 ? 1 : 0, it < 2 ? 0.0f : 1.0f / (float)(1 << (it - 2)));
+        if (with_var) vsrc = vp[it & 1];
         src = dst;
     }
     if (up) {
@@ -1165,20 +1163,64 @@ extern "C" int hjr_estimate_variance(hjr_ctx* c, uint32_t w, uint32_t h, const f
     return HJR_OK;
 }
 
+// Host buffers through one temporary device buffer on the context's stream: what the host-buffer entry points do that stage through no
+// context-owned buffer.  Uploads, the caller's launch (into `rc`) and downloads each happen only while everything before them succeeded;
+// finish() drains the stream, releases the buffer (on every path, and only after the stream has drained) and folds the first error.
+struct HostStage {
+    hjr_ctx* c;
+    DevBuf buf;
+    int rc = HJR_OK;           // of the launch
+    hipError_t e = hipSuccess; // the first failed runtime call
+    explicit HostStage(hjr_ctx* c_) : c(c_) {}
+    bool ok() const { return rc == HJR_OK && e == hipSuccess; }
+    void up(void* dst, const void* src, size_t n) { if (ok() && n) e = hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream); }
+    void down(void* dst, const void* src, size_t n) { if (ok() && n) e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream); }
+    int finish(const char* who)
+    {
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        buf.release();
+        if (rc != HJR_OK) return rc;
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) { set_error(std::string(who) + ": " + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
+        return HJR_OK;
+    }
+};
+
 // ---- temporal accumulation with reprojection (csrc/hjr_temporal.hip.h; include/henjou_hip.h)
+// The G-buffer pass's rules for the frame p describes, refused in the caller's words: `who` is the entry point, `t` what follows its name in
+// each refusal: the pass's own texts, or those of an entry point that runs the pass for an option and checks ahead of its first enqueue.
+#define HJR_GBUFFER_MAX_SIDE 8192
+#define HJR_STR_(x) #x
+#define HJR_STR(x) HJR_STR_(x)
+#define HJR_GBUFFER_MAX_TEXT HJR_STR(HJR_GBUFFER_MAX_SIDE) " x " HJR_STR(HJR_GBUFFER_MAX_SIDE)
+struct GbufTexts { const char *no_frame, *sharded, *too_large; };
+static const GbufTexts GBUF_OWN = { ": no frame data (upload a scene and set transforms first)", ": world_size > 1 and HJR_FLAG_PACKED are not supported",
+                                    ": frames larger than " HJR_GBUFFER_MAX_TEXT " are not supported" };
+static const GbufTexts GBUF_TEMPORAL = { ": option \"denoise_temporal\" needs the frame data of this frame (upload a scene and set transforms first)",
+                                         ": option \"denoise_temporal\" does not take world_size > 1 or HJR_FLAG_PACKED",
+                                         ": option \"denoise_temporal\" does not take frames larger than " HJR_GBUFFER_MAX_TEXT };
+static const GbufTexts GBUF_GUIDED = { ": option \"upscale_guided\" needs the frame data of this frame (upload a scene and set transforms first)",
+                                       ": option \"upscale_guided\" does not take world_size > 1 or HJR_FLAG_PACKED",
+                                       ": option \"upscale_guided\" does not take outputs larger than " HJR_GBUFFER_MAX_TEXT };
+static int gbuffer_check(const hjr_ctx* c, const hjr_params* p, const std::string& who, const GbufTexts& t)
+{
+    if (!c->have_scene || !c->have_frame) { set_error(who + t.no_frame); return HJR_ERR_STATE; }
+    if (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED)) { set_error(who + t.sharded); return HJR_ERR_ARG; }
+    if (p->width == 0 || p->height == 0) { set_error(who + ": empty image"); return HJR_ERR_ARG; }
+    if (p->width > HJR_GBUFFER_MAX_SIDE || p->height > HJR_GBUFFER_MAX_SIDE) { set_error(who + t.too_large); return HJR_ERR_ARG; }
+    return HJR_OK;
+}
 // G-buffer pass on device memory: the classifier's launch shape (one wave per tile, its stacks in dynamic LDS).  side 0: the plain pass;
-// 2, 3, 4: the coverage pass (hjr_gbuffer_cov_kernel) with side x side sub-pixel rays
-static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hipStream_t st, uint32_t side = 0)
+// 2, 3, 4: the coverage pass with side x side sub-pixel rays
+static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hipStream_t st, uint32_t side)
 {
     if (!c || !p || !d_out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
-    if (!c->have_scene || !c->have_frame) { set_error("hjr_render_gbuffer: no frame data (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
-    if (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED)) { set_error("hjr_render_gbuffer: world_size > 1 and HJR_FLAG_PACKED are not supported"); return HJR_ERR_ARG; }
-    if (p->width == 0 || p->height == 0) { set_error("hjr_render_gbuffer: empty image"); return HJR_ERR_ARG; }
-    if (p->width > 8192 || p->height > 8192) { set_error("hjr_render_gbuffer: frames larger than 8192 x 8192 are not supported"); return HJR_ERR_ARG; }
+    if (const int rc = gbuffer_check(c, p, "hjr_render_gbuffer", GBUF_OWN)) return rc;
     HIPCHK(hipSetDevice(c->device));
     GbufArgs a;
     memset(&a, 0, sizeof(a));
     a.nodes = (const float4*)c->d_nodes.p; a.tri_geom = (const float4*)c->d_tri_geom.p; a.tri_inst = (const uint32_t*)c->d_tri_inst.p;
+    a.tri_shade = (const uint32_t*)c->d_tri_shade.p; a.side = side;
     a.n_tris = c->frame.n_tris; a.width = p->width; a.height = p->height;
     a.tiles_x = (p->width + HJR_TILE - 1) / HJR_TILE;
     a.n_tiles = a.tiles_x * ((p->height + HJR_TILE - 1) / HJR_TILE);
@@ -1186,15 +1228,12 @@ static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hip
     a.out = (hjr_gbuffer_px*)d_out;
     const unsigned grid = (unsigned)std::min<uint64_t>(a.n_tiles, (uint64_t)c->n_cus * 16);
     const size_t smem = (size_t)64 * c->frame.stack_need * 4;
-    if (side) {
-        GbufCovArgs b;
-        memset(&b, 0, sizeof(b));
-        b.g = a; b.tri_shade = (const uint32_t*)c->d_tri_shade.p; b.side = side;
-        if (c->frame.width == 2) hipLaunchKernelGGL(hjr_gbuffer_cov_kernel<2>, dim3(grid), dim3(64), smem, st, b);
-        else hipLaunchKernelGGL(hjr_gbuffer_cov_kernel<4>, dim3(grid), dim3(64), smem, st, b);
-    }
-    else if (c->frame.width == 2) hipLaunchKernelGGL(hjr_gbuffer_kernel<2>, dim3(grid), dim3(64), smem, st, a);
-    else hipLaunchKernelGGL(hjr_gbuffer_kernel<4>, dim3(grid), dim3(64), smem, st, a);
+    using Kernel = void (*)(GbufArgs);
+    static const Kernel kernels[2][2] = { // [BVH4][coverage]
+        { hjr_gbuffer_kernel<2, false>, hjr_gbuffer_kernel<2, true> },
+        { hjr_gbuffer_kernel<4, false>, hjr_gbuffer_kernel<4, true> },
+    };
+    hipLaunchKernelGGL(kernels[c->frame.width != 2][side != 0], dim3(grid), dim3(64), smem, st, a);
     HIPCHK(hipGetLastError());
     return HJR_OK;
 }
@@ -1208,13 +1247,7 @@ extern "C" int hjr_render_gbuffer_device(hjr_ctx* c, const hjr_params* p_user, v
 {
     hjr_params params; // sized struct
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
-    return gbuffer_device_impl(c, &params, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-static int gbuffer_host_impl(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out, uint32_t side);
-extern "C" int hjr_render_gbuffer(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out) { return gbuffer_host_impl(c, p_user, out, 0); }
-extern "C" int hjr_render_gbuffer_cov(hjr_ctx* c, const hjr_params* p_user, uint32_t side, hjr_gbuffer_px* out)
-{
-    return coverage_side_ok(side) ? gbuffer_host_impl(c, p_user, out, side) : HJR_ERR_ARG;
+    return gbuffer_device_impl(c, &params, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream, 0);
 }
 extern "C" int hjr_render_gbuffer_cov_device(hjr_ctx* c, const hjr_params* p_user, uint32_t side, void* d_out, void* hip_stream)
 {
@@ -1229,23 +1262,22 @@ static int gbuffer_host_impl(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_p
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
     if (!out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
     const size_t bytes = (size_t)params.width * params.height * sizeof(hjr_gbuffer_px);
-    DevBuf buf;
-    if (bytes && !buf.reserve(bytes)) { set_error("hjr_render_gbuffer: device allocation failed"); return HJR_ERR_DEVICE; }
-    int rc = gbuffer_device_impl(c, &params, bytes ? buf.p : (void*)out, c->stream, side);
-    hipError_t e = hipSuccess;
-    if (rc == HJR_OK) e = hipMemcpyAsync(out, buf.p, bytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    buf.release();
-    if (rc != HJR_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) { set_error(std::string("hjr_render_gbuffer: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
-    return HJR_OK;
+    HostStage hs(c);
+    if (bytes && !hs.buf.reserve(bytes)) { set_error("hjr_render_gbuffer: device allocation failed"); return HJR_ERR_DEVICE; }
+    hs.rc = gbuffer_device_impl(c, &params, bytes ? hs.buf.p : (void*)out, c->stream, side); // (an empty image is the pass's refusal)
+    hs.down(out, hs.buf.p, bytes);
+    return hs.finish("hjr_render_gbuffer");
+}
+extern "C" int hjr_render_gbuffer(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out) { return gbuffer_host_impl(c, p_user, out, 0); }
+extern "C" int hjr_render_gbuffer_cov(hjr_ctx* c, const hjr_params* p_user, uint32_t side, hjr_gbuffer_px* out)
+{
+    return coverage_side_ok(side) ? gbuffer_host_impl(c, p_user, out, side) : HJR_ERR_ARG;
 }
 
 // the accumulation kernel on device memory; the two frames were checked by the callers
-// prev_cov / cur_cov: the two sides' `coverage`; with both 0 the launch is hjr_temporal_kernel's, as before the coverage rules existed
+// prev_cov / cur_cov: the two sides' `coverage`; with both 0 the launch is the plain instantiation's, as before the coverage rules existed
 static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_color, void* d_var, void* d_hist, hipStream_t st,
-                           uint32_t prev_cov = 0, uint32_t cur_cov = 0)
+                           uint32_t prev_cov, uint32_t cur_cov)
 {
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
@@ -1253,14 +1285,11 @@ static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalS
     if (prev) { a.prev = *prev; a.have_prev = 1u; }
     a.width = w; a.height = h; a.n_instances = n_inst;
     a.n_tris = c->have_scene ? c->scene.n_triangles : 0xffffffffu; // prim ids are checked against the uploaded scene
+    a.prev_cov = prev ? prev_cov : 0u; a.cur_cov = cur_cov;
     a.out_color = (float4*)d_color; a.out_variance = (float*)d_var; a.out_history = (float*)d_hist;
-    if ((prev && prev_cov) || cur_cov) {
-        TemporalCovArgs b;
-        memset(&b, 0, sizeof(b));
-        b.a = a; b.prev_cov = prev ? prev_cov : 0u; b.cur_cov = cur_cov;
-        hipLaunchKernelGGL(hjr_temporal_cov_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, b);
-    }
-    else hipLaunchKernelGGL(hjr_temporal_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, a);
+    using Kernel = void (*)(TemporalArgs);
+    static const Kernel kernels[2] = { hjr_temporal_kernel<false>, hjr_temporal_kernel<true> }; // [a side carries coverage]
+    hipLaunchKernelGGL(kernels[a.prev_cov || a.cur_cov], dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, a);
     HIPCHK(hipGetLastError());
     return HJR_OK;
 }
@@ -1306,36 +1335,29 @@ extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* pre
     const size_t npx = (size_t)f[1].width * f[1].height, nx = (size_t)f[1].n_instances * 48;
     // one temporary buffer: per side [M | M^-1 | gbuffer | colour | variance | history], then the three outputs
     const size_t side = (2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4) + 255) & ~(size_t)255, outs = npx * (16 + 4 + 4); // (float4 images stay 16-byte aligned)
-    DevBuf buf;
-    if (!buf.reserve(2 * side + outs)) { set_error("hjr_temporal_accumulate: device allocation failed"); return HJR_ERR_DEVICE; }
+    HostStage hs(c);
+    if (!hs.buf.reserve(2 * side + outs)) { set_error("hjr_temporal_accumulate: device allocation failed"); return HJR_ERR_DEVICE; }
     TemporalSide s[2];
-    hipError_t e = hipSuccess;
     for (int i = have_prev ? 0 : 1; i < 2; i++) {
-        char* b = (char*)buf.p + (size_t)i * side;
+        char* b = (char*)hs.buf.p + (size_t)i * side;
         const void* src[6] = { f[i].transforms12, f[i].inv_transforms12, f[i].gbuffer, f[i].color, f[i].variance, i == 0 ? f[i].history : nullptr };
         const size_t len[6] = { nx, nx, npx * sizeof(hjr_gbuffer_px), npx * 16, npx * 4, npx * 4 };
         const void* dst[6];
         for (int k = 0; k < 6; k++) {
             dst[k] = b;
-            if (src[k] && len[k] && e == hipSuccess) e = hipMemcpyAsync(b, src[k], len[k], hipMemcpyHostToDevice, c->stream);
+            if (src[k]) hs.up(b, src[k], len[k]);
             b += len[k];
         }
         s[i].cam = f[i].camera; s[i].m = (const float*)dst[0]; s[i].inv = (const float*)dst[1]; s[i].gbuf = (const hjr_gbuffer_px*)dst[2];
         s[i].color = (const float4*)dst[3]; s[i].variance = (const float*)dst[4]; s[i].history = (const float*)dst[5];
     }
-    char* const o = (char*)buf.p + 2 * side;
-    int rc = HJR_OK;
-    if (e == hipSuccess) rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream,
-                                              have_prev ? f[0].coverage : 0u, f[1].coverage);
-    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_color, o, npx * 16, hipMemcpyDeviceToHost, c->stream);
-    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_var, o + npx * 16, npx * 4, hipMemcpyDeviceToHost, c->stream);
-    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out_hist, o + npx * 20, npx * 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    buf.release();
-    if (rc != HJR_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) { set_error(std::string("hjr_temporal_accumulate: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
-    return HJR_OK;
+    char* const o = (char*)hs.buf.p + 2 * side;
+    if (hs.ok()) hs.rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream,
+                                         have_prev ? f[0].coverage : 0u, f[1].coverage);
+    hs.down(out_color, o, npx * 16);
+    hs.down(out_var, o + npx * 16, npx * 4);
+    hs.down(out_hist, o + npx * 20, npx * 4);
+    return hs.finish("hjr_temporal_accumulate");
 }
 extern "C" int hjr_temporal_reset(hjr_ctx* c)
 {
@@ -1348,7 +1370,7 @@ extern "C" int hjr_temporal_reset(hjr_ctx* c)
 // a device copy of the transforms the current frame data was built from (last_m / last_inv: what hjr_commit_transforms made current, so a
 // frame loop that already prepares the next frame on another thread cannot be seen here), accumulation against the previous slot.
 // `commit`: this call ends the frame (a whole-frame render, or the sample pass that ends at spp): the slots rotate.
-// the current slot's buffers (no enqueue: hjr_denoise_shards_device calls it ahead of its first launch, temporal_stage again to no effect)
+// the current slot's buffers (no enqueue: post_plan calls it ahead of the first launch, temporal_stage again to no effect)
 static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
 {
     hjr_ctx::Temporal& t = c->tmp;
@@ -1387,14 +1409,13 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
 }
 
 // ---- guided 2x upscale (csrc/hjr_denoise.hip.h; include/henjou_hip.h: hjr_upscale_guided)
-#define HJR_GBUFFER_MAX_SIDE 8192u /* gbuffer_device_impl's limit */
 static int upscale_guided_check(const hjr_ctx* c, uint32_t in_w, uint32_t in_h, const void* color_lo, const void* gbuffer_lo, const hjr_camera* cam, const void* gbuffer_hi,
                                 const void* out, uint32_t out_w, uint32_t out_h)
 {
     if (!c || !color_lo || !gbuffer_lo || !cam || !gbuffer_hi || !out) { set_error("hjr_upscale_guided: null argument"); return HJR_ERR_ARG; }
     if (in_w == 0 || in_h == 0 || out_w == 0 || out_h == 0) { set_error("hjr_upscale_guided: empty image"); return HJR_ERR_ARG; }
     if (out_w / 2u != in_w || out_h / 2u != in_h) { set_error("hjr_upscale_guided: the input is (out_w / 2, out_h / 2)"); return HJR_ERR_ARG; }
-    if (out_w > HJR_GBUFFER_MAX_SIDE || out_h > HJR_GBUFFER_MAX_SIDE) { set_error("hjr_upscale_guided: images larger than 8192 x 8192 are not supported"); return HJR_ERR_ARG; }
+    if (out_w > HJR_GBUFFER_MAX_SIDE || out_h > HJR_GBUFFER_MAX_SIDE) { set_error("hjr_upscale_guided: images larger than " HJR_GBUFFER_MAX_TEXT " are not supported"); return HJR_ERR_ARG; }
     return HJR_OK;
 }
 // the kernel on device memory; the callers checked the arguments
@@ -1420,66 +1441,94 @@ extern "C" int hjr_upscale_guided(hjr_ctx* c, uint32_t in_w, uint32_t in_h, cons
     HIPCHK(hipSetDevice(c->device));
     const size_t n_in = (size_t)in_w * in_h, n_out = (size_t)out_w * out_h;
     // one temporary buffer: [colour | output | low-resolution records | output-size records] (float4 images first: they stay 16-byte aligned)
-    DevBuf buf;
-    if (!buf.reserve((n_in + n_out) * (16 + sizeof(hjr_gbuffer_px)))) { set_error("hjr_upscale_guided: device allocation failed"); return HJR_ERR_DEVICE; }
-    char* const d_color = (char*)buf.p, *const d_out = d_color + n_in * 16, *const d_lo = d_out + n_out * 16, *const d_hi = d_lo + n_in * sizeof(hjr_gbuffer_px);
-    hipError_t e = hipMemcpyAsync(d_color, color_lo, n_in * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo, gbuffer_lo, n_in * sizeof(hjr_gbuffer_px), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_hi, gbuffer_hi, n_out * sizeof(hjr_gbuffer_px), hipMemcpyHostToDevice, c->stream);
-    int rc = HJR_OK;
-    if (e == hipSuccess) rc = upscale_guided_launch(in_w, in_h, d_color, d_lo, *cam, d_hi, d_out, out_w, out_h, c->stream);
-    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out, d_out, n_out * 16, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    buf.release();
-    if (rc != HJR_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) { set_error(std::string("hjr_upscale_guided: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
-    return HJR_OK;
+    HostStage hs(c);
+    if (!hs.buf.reserve((n_in + n_out) * (16 + sizeof(hjr_gbuffer_px)))) { set_error("hjr_upscale_guided: device allocation failed"); return HJR_ERR_DEVICE; }
+    char* const d_color = (char*)hs.buf.p, *const d_out = d_color + n_in * 16, *const d_lo = d_out + n_out * 16, *const d_hi = d_lo + n_in * sizeof(hjr_gbuffer_px);
+    hs.up(d_color, color_lo, n_in * 16);
+    hs.up(d_lo, gbuffer_lo, n_in * sizeof(hjr_gbuffer_px));
+    hs.up(d_hi, gbuffer_hi, n_out * sizeof(hjr_gbuffer_px));
+    if (hs.ok()) hs.rc = upscale_guided_launch(in_w, in_h, d_color, d_lo, *cam, d_hi, d_out, out_w, out_h, c->stream);
+    hs.down(out, d_out, n_out * 16);
+    return hs.finish("hjr_upscale_guided");
 }
-// Option "upscale_guided" in DenoiseUpScale2X: what hjr_render_denoised and hjr_denoise_shards_device (`who`) check and allocate ahead of their
-// first enqueue, so that nothing of the guided stage can fail behind it: the size rule, gbuffer_device_impl's checks for both sizes, the
-// filter's ping-pong buffer the last pass goes to, and the two G-buffers (the temporal stage traces the render-size one itself).
-static int upscale_guided_reserve(hjr_ctx* c, const hjr_params* p, bool temporal, uint32_t out_w, uint32_t out_h, const char* who)
+
+// The post stage of a frame in a render mode, as hjr_render_denoised and hjr_denoise_shards_device (`who`) plan it ahead of their first
+// enqueue and of any change to the progressive-frame state.
+struct PostPlan {
+    int mode;      // the render mode
+    bool guides;   // not Default: the filter runs on the albedo and normal guides
+    bool temporal; // option "denoise_temporal": accumulation over frames in front of the filter
+    bool with_var; // option "denoise_variance" (or temporal): the variance AOV and the variance-guided filter
+    bool guided;   // option "upscale_guided" in DenoiseUpScale2X: G-buffers and the guided upscale
+};
+static PostPlan post_options(const hjr_ctx* c, int render_mode)
 {
-    if (const int rc = denoise_check_sizes(HJR_MODE_DENOISE_UPSCALE2X, p->width, p->height, out_w, out_h)) return rc;
-    if (!c->have_scene || !c->have_frame) { set_error(std::string(who) + ": option \"upscale_guided\" needs the frame data of this frame (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
-    if (out_w > HJR_GBUFFER_MAX_SIDE || out_h > HJR_GBUFFER_MAX_SIDE) { set_error(std::string(who) + ": option \"upscale_guided\" does not take outputs larger than 8192 x 8192"); return HJR_ERR_ARG; }
-    const size_t n_in = (size_t)p->width * p->height, n_out = (size_t)out_w * out_h;
-    if (!c->d_dn_a.reserve(n_in * 16) || (!temporal && !c->d_ug_lo.reserve(n_in * sizeof(hjr_gbuffer_px))) || !c->d_ug_hi.reserve(n_out * sizeof(hjr_gbuffer_px))) {
-        set_error(std::string(who) + ": allocation failed");
-        return HJR_ERR_DEVICE;
+    PostPlan pl;
+    pl.mode = render_mode;
+    pl.guides = render_mode != HJR_MODE_DEFAULT;
+    pl.temporal = pl.guides && c->opt.get(hjr::OPT_DENOISE_TEMPORAL, 0) != 0;
+    pl.with_var = pl.guides && (pl.temporal || c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0);
+    pl.guided = render_mode == HJR_MODE_DENOISE_UPSCALE2X && c->opt.get(hjr::OPT_UPSCALE_GUIDED, 0) != 0;
+    return pl;
+}
+// Every refusal of the stage (world size / packed, the mode and size rules, the frame data and limits of the G-buffer passes), then every
+// buffer it needs: the AOV staging, the filter's ping-pong colour and variance, the temporal slot, the guided upscale's G-buffers (the
+// temporal stage traces the render-size one itself).  Nothing of the stage can fail behind the first launch but the runtime.
+// `pr` non-null: the caller renders the frame itself (hjr_render_denoised), and the render's pass and argument rules speak where they
+// always did, behind the guided upscale's and ahead of the filter's: *pr is the pass the render will run.
+static int post_plan(hjr_ctx* c, const hjr_params* p, const PostPlan& pl, uint32_t out_w, uint32_t out_h, const char* who, PassRange* pr)
+{
+    const bool sharded = p->world_size > 1 || (p->flags & HJR_FLAG_PACKED);
+    if (pl.temporal && sharded) { set_error(std::string(who) + GBUF_TEMPORAL.sharded); return HJR_ERR_ARG; }
+    if (pl.guided && sharded) { set_error(std::string(who) + GBUF_GUIDED.sharded); return HJR_ERR_ARG; }
+    if (pl.guided) {
+        if (const int rc = denoise_check_sizes(pl.mode, p->width, p->height, out_w, out_h)) return rc;
+        hjr_params hi = *p; // the second G-buffer pass
+        hi.width = out_w; hi.height = out_h;
+        if (const int rc = gbuffer_check(c, &hi, who, GBUF_GUIDED)) return rc;
     }
-    return HJR_OK;
+    if (pr) {
+        FrameGeom g;
+        if (const int rc = check_pass(c, p, (pl.guides ? 7u : 1u) | (pl.with_var ? 8u : 0u), *pr)) return rc;
+        if (const int rc = frame_geometry(c, p, p, *pr, g)) return rc; // (no AOV buffer yet: any non-null pointer)
+    }
+    if (const int rc = denoise_check_sizes(pl.mode, p->width, p->height, out_w, out_h)) return rc;
+    if (pl.temporal)
+        if (const int rc = gbuffer_check(c, p, who, GBUF_TEMPORAL)) return rc;
+    const size_t n_in = (size_t)p->width * p->height, n_out = (size_t)out_w * out_h;
+    bool ok = c->d_color.reserve(n_in * 16);
+    if (pl.guides) ok = ok && c->d_albedo.reserve(n_in * 16) && c->d_normal.reserve(n_in * 16) && c->d_dn_a.reserve(n_in * 16) && c->d_dn_b.reserve(n_in * 16);
+    if (pl.with_var) ok = ok && c->d_variance.reserve(n_in * 4) && c->d_dnv_a.reserve(n_in * 4) && c->d_dnv_b.reserve(n_in * 4);
+    if (pl.guided) ok = ok && (pl.temporal || c->d_ug_lo.reserve(n_in * sizeof(hjr_gbuffer_px))) && c->d_ug_hi.reserve(n_out * sizeof(hjr_gbuffer_px));
+    if (!ok) { set_error(std::string(who) + ": allocation failed"); return HJR_ERR_DEVICE; }
+    return pl.temporal ? temporal_reserve(c, p) : HJR_OK;
 }
 
 // What a frame in a render mode runs once its AOVs stand in the context's d_color / d_albedo / d_normal (/ d_variance), whether a render left
 // them there (hjr_render_denoised) or the assembly of gathered shards (hjr_denoise_shards_device): the temporal stage if the option is on
 // (`commit`: this call ends the frame), then the filter, plain or variance-guided, and the upscale of DenoiseUpScale2X.  All on `st`.
 // Option "denoise_variance_spatial" with a variance in play: ahead of both, pixels of unknown variance get the spatial estimate, in place.
-// `guided` (option "upscale_guided" in DenoiseUpScale2X; the caller ran upscale_guided_reserve): the filter as in Denoise mode with its last
-// pass into the ping-pong buffer, the G-buffer at the render size (the temporal stage's of this frame if there is one) and at the output
-// size from the same camera, and the guided kernel in place of the bilinear one.
-static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool temporal, bool with_var, bool guided, bool commit, void* d_out, uint32_t out_w,
-                              uint32_t out_h, hipStream_t st)
+// pl.guided: the filter as in Denoise mode with its last pass into the ping-pong buffer, the G-buffer at the render size (the temporal
+// stage's of this frame if there is one) and at the output size from the same camera, and the guided kernel in place of the bilinear one.
+static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, const PostPlan& pl, bool commit, void* d_out, uint32_t out_w, uint32_t out_h, hipStream_t st)
 {
-    const bool guides = render_mode != HJR_MODE_DEFAULT;
-    const void *f_color = c->d_color.p, *f_var = with_var ? c->d_variance.p : nullptr; // what the filter reads
-    if (guides && with_var && c->opt.get(hjr::OPT_DENOISE_VARIANCE_SPATIAL, 0) != 0)
+    const void *f_color = c->d_color.p, *f_var = pl.with_var ? c->d_variance.p : nullptr; // what the filter reads
+    if (pl.with_var && c->opt.get(hjr::OPT_DENOISE_VARIANCE_SPATIAL, 0) != 0)
         if (const int rc = estimate_variance_launch(p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, c->d_variance.p, c->d_variance.p, st)) return rc;
     const int slot = c->tmp.cur; // the temporal stage's slot of this frame (a commit rotates the slots)
-    if (temporal)
-        if (const int rc = temporal_stage(c, p, render_mode, commit, f_color, f_var, st)) return rc;
-    if (!guided)
-        return denoise_device_impl(c, render_mode, p->width, p->height, f_color, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var, f_var, d_out,
+    if (pl.temporal)
+        if (const int rc = temporal_stage(c, p, pl.mode, commit, f_color, f_var, st)) return rc;
+    if (!pl.guided)
+        return denoise_device_impl(c, pl.mode, p->width, p->height, f_color, pl.guides ? c->d_albedo.p : nullptr, pl.guides ? c->d_normal.p : nullptr, pl.with_var, f_var, d_out,
                                    out_w, out_h, st);
     void* const filtered = c->d_dn_a.p; // the last pass reads d_dn_b: the bilinear path's buffers
-    if (const int rc = denoise_device_impl(c, HJR_MODE_DENOISE, p->width, p->height, f_color, c->d_albedo.p, c->d_normal.p, with_var, f_var, filtered, p->width, p->height, st)) return rc;
-    const void* g_lo = temporal ? c->tmp.gbuf[slot].p : c->d_ug_lo.p;
-    if (!temporal)
-        if (const int rc = gbuffer_device_impl(c, p, c->d_ug_lo.p, st)) return rc;
+    if (const int rc = denoise_device_impl(c, HJR_MODE_DENOISE, p->width, p->height, f_color, c->d_albedo.p, c->d_normal.p, pl.with_var, f_var, filtered, p->width, p->height, st)) return rc;
+    const void* g_lo = pl.temporal ? c->tmp.gbuf[slot].p : c->d_ug_lo.p;
+    if (!pl.temporal)
+        if (const int rc = gbuffer_device_impl(c, p, c->d_ug_lo.p, st, 0)) return rc;
     hjr_params hi = *p;
     hi.width = out_w; hi.height = out_h;
-    if (const int rc = gbuffer_device_impl(c, &hi, c->d_ug_hi.p, st)) return rc;
+    if (const int rc = gbuffer_device_impl(c, &hi, c->d_ug_hi.p, st, 0)) return rc;
     return upscale_guided_launch(p->width, p->height, filtered, g_lo, p->camera, c->d_ug_hi.p, d_out, out_w, out_h, st);
 }
 
@@ -1490,33 +1539,20 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     hjr_params params; // sized struct
     if (!c || !hjr::abi_take(p_user, params, "hjr_render_denoised")) { if (!c) set_error("hjr_render_denoised: null context"); return HJR_ERR_ARG; }
     const hjr_params* p = &params;
-    if (!c || !p || !out) { set_error("hjr_render_denoised: null argument"); return HJR_ERR_ARG; }
+    if (!out) { set_error("hjr_render_denoised: null argument"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     const size_t in_bytes = (size_t)p->width * p->height * 16, out_bytes = (size_t)out_w * out_h * 16;
     if (in_bytes == 0 || out_bytes == 0) { set_error("hjr_render_denoised: empty image"); return HJR_ERR_ARG; }
-    const bool guides = render_mode != HJR_MODE_DEFAULT;
-    const bool temporal = guides && c->opt.get(hjr::OPT_DENOISE_TEMPORAL, 0) != 0; // option "denoise_temporal": accumulation over frames in front of the filter
-    if (temporal && (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED))) { set_error("hjr_render_denoised: option \"denoise_temporal\" does not take world_size > 1 or HJR_FLAG_PACKED"); return HJR_ERR_ARG; }
-    const bool with_var = guides && (temporal || c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0); // option "denoise_variance": the variance AOV and the variance-guided filter
-    const bool guided = render_mode == HJR_MODE_DENOISE_UPSCALE2X && c->opt.get(hjr::OPT_UPSCALE_GUIDED, 0) != 0; // option "upscale_guided": G-buffers and the guided upscale
-    if (guided && (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED))) { set_error("hjr_render_denoised: option \"upscale_guided\" does not take world_size > 1 or HJR_FLAG_PACKED"); return HJR_ERR_ARG; }
-    if (guided)
-        if (const int rc = upscale_guided_reserve(c, p, temporal, out_w, out_h, "hjr_render_denoised")) return rc;
+    const PostPlan pl = post_options(c, render_mode);
     PassRange pr; // a sample pass: the running mean is filtered (a denoised preview; the last pass gives the one-shot call's image)
-    if (const int rc = check_pass(c, p, (guides ? 7u : 1u) | (with_var ? 8u : 0u), pr)) return rc;
-    if (with_var) {
-        if (!c->d_variance.reserve(in_bytes / 4)) { set_error("hjr_render_denoised: allocation failed"); return HJR_ERR_DEVICE; }
-        HIPCHK(hipMemsetAsync(c->d_variance.p, 0, in_bytes / 4, c->stream));
-    }
-    if (!c->d_color.reserve(in_bytes) || (guides && (!c->d_albedo.reserve(in_bytes) || !c->d_normal.reserve(in_bytes))) || !c->d_dn_out.reserve(out_bytes)) {
-        set_error("hjr_render_denoised: allocation failed");
-        return HJR_ERR_DEVICE;
-    }
+    if (const int rc = post_plan(c, p, pl, out_w, out_h, "hjr_render_denoised", &pr)) return rc;
+    if (!c->d_dn_out.reserve(out_bytes)) { set_error("hjr_render_denoised: allocation failed"); return HJR_ERR_DEVICE; }
+    if (pl.with_var) HIPCHK(hipMemsetAsync(c->d_variance.p, 0, in_bytes / 4, c->stream));
     HIPCHK(hipMemsetAsync(c->d_color.p, 0, in_bytes, c->stream));
-    if (guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
-    int rc = render_impl(c, p, pr, c->d_color.p, guides ? c->d_albedo.p : nullptr, guides ? c->d_normal.p : nullptr, with_var ? c->d_variance.p : nullptr, c->stream);
+    if (pl.guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
+    int rc = render_impl(c, p, pr, c->d_color.p, pl.guides ? c->d_albedo.p : nullptr, pl.guides ? c->d_normal.p : nullptr, pl.with_var ? c->d_variance.p : nullptr, c->stream);
     if (rc != HJR_OK) return rc;
-    rc = denoise_post_stage(c, p, render_mode, temporal, with_var, guided, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
+    rc = denoise_post_stage(c, p, pl, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
     if (rc != HJR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1561,37 +1597,19 @@ extern "C" int hjr_denoise_shards_device(hjr_ctx* c, const hjr_params* p_user, i
     if (const int rc = denoise_check_sizes(render_mode, p->width, p->height, out_w, out_h)) return rc;
     const bool whole = p->sample_end == 0 || (p->sample_begin == 0 && p->sample_end == p->spp);
     if (!whole && (p->sample_begin >= p->sample_end || p->sample_end > p->spp)) { set_error("hjr_denoise_shards_device: bad sample range"); return HJR_ERR_ARG; }
-    const bool temporal = c->opt.get(hjr::OPT_DENOISE_TEMPORAL, 0) != 0;
-    const bool with_var = temporal || c->opt.get(hjr::OPT_DENOISE_VARIANCE, 0) != 0;
-    const bool guided = render_mode == HJR_MODE_DENOISE_UPSCALE2X && c->opt.get(hjr::OPT_UPSCALE_GUIDED, 0) != 0;
-    if (guided && (out_w > HJR_GBUFFER_MAX_SIDE || out_h > HJR_GBUFFER_MAX_SIDE)) { set_error("hjr_denoise_shards_device: option \"upscale_guided\" does not take outputs larger than 8192 x 8192"); return HJR_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
+    const PostPlan pl = post_options(c, render_mode);
     hjr_shards s; // sized struct
     if (!hjr::abi_take(gathered, s, "hjr_denoise_shards_device")) return HJR_ERR_ARG;
     if (!s.color || !s.albedo || !s.normal) { set_error("hjr_denoise_shards_device: the colour, albedo and normal blocks are required"); return HJR_ERR_ARG; }
-    if (with_var && !s.variance) { set_error("hjr_denoise_shards_device: options \"denoise_variance\" / \"denoise_temporal\" need the variance block"); return HJR_ERR_ARG; }
-    if (!with_var) s.variance = nullptr; // a block the filter does not read stays where it is
-    const size_t in_bytes = (size_t)p->width * p->height * 16;
-    if (!c->d_color.reserve(in_bytes) || !c->d_albedo.reserve(in_bytes) || !c->d_normal.reserve(in_bytes) || (with_var && !c->d_variance.reserve(in_bytes / 4))) {
-        set_error("hjr_denoise_shards_device: allocation failed");
-        return HJR_ERR_DEVICE;
-    }
-    const void* const out[4] = { c->d_color.p, c->d_albedo.p, c->d_normal.p, with_var ? c->d_variance.p : nullptr };
+    if (pl.with_var && !s.variance) { set_error("hjr_denoise_shards_device: options \"denoise_variance\" / \"denoise_temporal\" need the variance block"); return HJR_ERR_ARG; }
+    if (!pl.with_var) s.variance = nullptr; // a block the filter does not read stays where it is
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = post_plan(c, p, pl, out_w, out_h, "hjr_denoise_shards_device", nullptr)) return rc;
+    const void* const out[4] = { c->d_color.p, c->d_albedo.p, c->d_normal.p, pl.with_var ? c->d_variance.p : nullptr };
     if (const int rc = hjr::check_shards(s, p->width, p->height, out, "hjr_denoise_shards_device")) return rc;
-    if (temporal) { // gbuffer_device_impl's checks, ahead of the assembly
-        if (!c->have_scene || !c->have_frame) { set_error("hjr_denoise_shards_device: option \"denoise_temporal\" needs the frame data of this frame (upload a scene and set transforms first)"); return HJR_ERR_STATE; }
-        if (p->width > 8192 || p->height > 8192) { set_error("hjr_denoise_shards_device: option \"denoise_temporal\" does not take frames larger than 8192 x 8192"); return HJR_ERR_ARG; }
-        if (const int rc = temporal_reserve(c, p)) return rc;
-    }
-    if (guided) // the G-buffer passes' checks and buffers, ahead of the assembly
-        if (const int rc = upscale_guided_reserve(c, p, temporal, out_w, out_h, "hjr_denoise_shards_device")) return rc;
-    if (!c->d_dn_a.reserve(in_bytes) || !c->d_dn_b.reserve(in_bytes) || (with_var && (!c->d_dnv_a.reserve(in_bytes / 4) || !c->d_dnv_b.reserve(in_bytes / 4)))) {
-        set_error("hjr_denoise_shards_device: allocation failed"); // (the filter's ping-pong buffers: nothing may fail behind the first launch)
-        return HJR_ERR_DEVICE;
-    }
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    if (const int rc = assemble_launch(s, p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, with_var ? c->d_variance.p : nullptr, st)) return rc;
-    return denoise_post_stage(c, p, render_mode, temporal, with_var, guided, whole || p->sample_end == p->spp, d_out, out_w, out_h, st);
+    if (const int rc = assemble_launch(s, p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, pl.with_var ? c->d_variance.p : nullptr, st)) return rc;
+    return denoise_post_stage(c, p, pl, whole || p->sample_end == p->spp, d_out, out_w, out_h, st);
 }
 
 // Round-trips every child ref the builder can emit for a tree that host/frame.cpp admits to the 16-bit-stack layout
@@ -1640,9 +1658,9 @@ extern "C" int hjr_trace_rays(hjr_ctx* c, int path, uint32_t n, const hjr_ray* s
     // (`fast` of plan_launch = "megakernel family whatever option pipeline says": the hook has no wavefront path)
     const LaunchPlan pl = plan_launch(c, kp, n, lds_mode, HJR_INTEGRATOR_NEE, true);
     const size_t rays = (size_t)n * sizeof(hjr_ray);
-    DevBuf buf;
-    if (!buf.reserve(64 + 3 * rays)) { set_error("hjr_trace_rays: device allocation failed"); return HJR_ERR_DEVICE; }
-    char* const base = (char*)buf.p;
+    HostStage hs(c);
+    if (!hs.buf.reserve(64 + 3 * rays)) { set_error("hjr_trace_rays: device allocation failed"); return HJR_ERR_DEVICE; }
+    char* const base = (char*)hs.buf.p;
     TraceArgs a;
     memset(&a, 0, sizeof(a));
     a.next = (unsigned int*)base; a.n_over = (unsigned long long*)(base + 8);
@@ -1651,27 +1669,22 @@ extern "C" int hjr_trace_rays(hjr_ctx* c, int path, uint32_t n, const hjr_ray* s
     std::vector<hjr_ray_result> init(n);
     memset(init.data(), 0, rays);
     for (uint32_t i = 0; i < n; i++) { init[i].prim = 0xffffffffu; init[i].status = HJR_TRACE_STATUS_UNTRACED; }
-    int rc = HJR_OK;
     unsigned long long n_over = 0;
-    hipError_t e = hipMemsetAsync(base, 0, 64, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + 64, shadow, rays, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + 64 + rays, closest, rays, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + 64 + 2 * rays, init.data(), rays, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
+    hs.e = hipMemsetAsync(base, 0, 64, c->stream);
+    hs.up(base + 64, shadow, rays);
+    hs.up(base + 64 + rays, closest, rays);
+    hs.up(base + 64 + 2 * rays, init.data(), rays);
+    if (hs.ok()) {
 #ifdef HJR_HAVE_FAST
-        rc = fast ? hjr_launch_trace_fast(c, pl, loop == HJR_TRACE_FUSED, a, c->stream) : hjr_launch_trace(c, pl, loop == HJR_TRACE_FUSED, a, c->stream);
+        hs.rc = fast ? hjr_launch_trace_fast(c, pl, loop == HJR_TRACE_FUSED, a, c->stream) : hjr_launch_trace(c, pl, loop == HJR_TRACE_FUSED, a, c->stream);
 #else
-        rc = hjr_launch_trace(c, pl, loop == HJR_TRACE_FUSED, a, c->stream);
+        hs.rc = hjr_launch_trace(c, pl, loop == HJR_TRACE_FUSED, a, c->stream);
 #endif
-        if (rc == HJR_OK) e = hipGetLastError();
+        if (hs.rc == HJR_OK) hs.e = hipGetLastError();
     }
-    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(out, base + 64 + 2 * rays, rays, hipMemcpyDeviceToHost, c->stream);
-    if (rc == HJR_OK && e == hipSuccess) e = hipMemcpyAsync(&n_over, base + 8, 8, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    buf.release();
-    if (rc != HJR_OK) return rc;
-    if (e != hipSuccess) { set_error(std::string("hjr_trace_rays: ") + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
+    hs.down(out, base + 64 + 2 * rays, rays);
+    hs.down(&n_over, base + 8, 8);
+    if (const int rc = hs.finish("hjr_trace_rays")) return rc;
     if (c->event_pending) { hjr_stats prev; memset(&prev, 0, sizeof(prev)); prev.struct_size = (uint32_t)sizeof(prev); (void)hjr_get_stats(c, &prev); } // counters of an earlier render land first
     c->stats.lds_mode = (uint32_t)lds_mode; c->stats.stack_need = c->frame.stack_need; c->stats.stack_lds_entries = pl.kp.stack_lds_entries;
     c->stats.stack_overflow_pushes = n_over;

@@ -1,7 +1,7 @@
 // Temporal accumulation with reprojection for the Denoise modes: the temporal half of SVGF (Schied et al., HPG 2017) in front of the
 // variance-guided a-trous filter (hjr_denoise.hip.h).  Two kernels, both outside the render kernels (no render kernel knows about them):
-//   hjr_gbuffer_kernel<WIDTH>   first-hit record of every pixel's centre ray, by the stand-alone traversal the tile classifier uses;
-//   hjr_temporal_kernel         one lane per pixel: reprojects the pixel's surface point into the previous frame, gathers the previous
+//   hjr_gbuffer_kernel<WIDTH, COV>   first-hit record of every pixel's centre ray, by the stand-alone traversal the tile classifier uses;
+//   hjr_temporal_kernel<COV>    one lane per pixel: reprojects the pixel's surface point into the previous frame, gathers the previous
 //                               frame's accumulated colour / variance / history length with four validated bilinear taps and blends.
 // Included by hjr_device.hip only: correctly rounded divide, no contraction, denormals on.  Specified to the bit, so that the test suite's
 // CPU checker (tests/native/temporal_ref.cpp) restates it independently.  fp32 throughout, every operation as written, left to right:
@@ -46,7 +46,7 @@
 // Hostile input: every table index (instance of the current record and of each tap) is range-checked before it is used, no tap outside the
 // image is read, and float -> int conversion happens only after the float range check; nothing else indexes memory.
 //
-// COVERAGE G-BUFFER (hjr_gbuffer_cov_kernel<WIDTH>, side n = 2, 3 or 4).  The centre ray and its record are exactly the
+// COVERAGE G-BUFFER (hjr_gbuffer_kernel<WIDTH, true>, side n = 2, 3 or 4).  The centre ray and its record are exactly the
 //   G-BUFFER's above; only `pad` differs.  After the centre ray, n * n sub-pixel rays, no RNG: sub-ray (i, j), i, j = 0..n-1, j the outer
 //   loop:  ox = ((float)i + 0.5f) / (float)n,  oy = ((float)j + 0.5f) / (float)n,  u = (2 (px + ox) - W) / H,  v = (2 (py + oy) - H) / H,
 //   direction, origin, tmin and tmax by the centre ray's expression.  A sub-ray is ON THE CENTRE'S SURFACE iff
@@ -56,10 +56,10 @@
 //       D = pos_sub - G.pos  (pos_sub by the record's own `pos` expression),  nd = dot(G.ng, D),  nn = dot(G.ng, G.ng),
 //       view = G.pos - cam.pos,  vv = dot(view, view),  fh = cam.f * H,  fp2 = (vv * 4) / (fh * fh)   (dot as above; a NaN fails).
 //   pad = same | (n * n) << 8, `same` the number of sub-rays on the centre's surface.  A miss record carries its counts too (a sky pixel
-//   that partly covers geometry is known); every other field of a miss record stays 0.  hjr_gbuffer_kernel writes pad = 0.
+//   that partly covers geometry is known); every other field of a miss record stays 0.  hjr_gbuffer_kernel<WIDTH, false> writes pad = 0.
 //
-// COVERAGE-AWARE ACCUMULATION (hjr_temporal_cov_kernel: the ACCUMULATION above with two more inputs, prev.coverage and cur.coverage, the
-//   `coverage` fields of the two hjr_temporal_frame; with both 0 it is the rule above bit for bit, and that case runs hjr_temporal_kernel).
+// COVERAGE-AWARE ACCUMULATION (hjr_temporal_kernel<true>: the ACCUMULATION above with two more inputs, prev.coverage and cur.coverage, the
+//   `coverage` fields of the two hjr_temporal_frame; with both 0 it is the rule above bit for bit, and that case runs hjr_temporal_kernel<false>).
 //   A record R of a side whose coverage != 0 is MIXED iff  total = (R.pad >> 8) & 0xff  is above 0 and  (R.pad & 0xff) < total;  a record of a
 //   side whose coverage == 0 is never mixed and its pad is not looked at.  pad is only ever compared, never used as an index.
 //   3'. G not mixed: a tap whose record T (of prev) is mixed is INVALID; everything else is unchanged.
@@ -71,7 +71,7 @@
 //   In words: a mixed pixel keeps its history only from the pixel it coincides with, and otherwise restarts; a full pixel never taps a mixed
 //   one.  A static sequence still accumulates everywhere: the reprojection lands on the centre up to rounding.
 #pragma once
-#include "hjr_kernel.hip.h"
+#include "hjr_aux.hip.h" // TileStack: the classifier's stacks
 
 #define HJR_TEMPORAL_K_PLANE 1.0f
 #define HJR_TEMPORAL_K_DIST 3.0f
@@ -81,69 +81,23 @@ struct GbufArgs {
     const float4* nodes;
     const float4* tri_geom;
     const uint32_t* tri_inst;
+    const uint32_t* tri_shade; // COV: the shading rows as words: word 15 of a row is the material id
     uint32_t n_tris, width, height, tiles_x, n_tiles;
+    uint32_t side;             // COV: 2, 3 or 4
     hjr_camera cam;
     hjr_gbuffer_px* out;
 };
 
-// one wave per 8 x 8 tile, grid-stride over the tiles; 64 * stack_depth * 4 bytes of dynamic LDS (the classifier's stacks)
-template <int WIDTH>
-__global__ void __launch_bounds__(64) hjr_gbuffer_kernel(const GbufArgs A)
-{
-    typedef LaneStack<uint32_t, 64, false> ST;
-    ST stack;
-    stack.lds = reinterpret_cast<uint32_t*>(hjr_smem) + threadIdx.x;
-    stack.spill = nullptr; stack.spill_stride = 0; stack.lds_n = 0; stack.n_over = 0; stack.top = nullptr; stack.n_top = 0u;
-    for (uint32_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
-        uint32_t tx, ty;
-        hjr_tile_xy(tile, A.tiles_x, &tx, &ty);
-        const uint32_t px = tx * HJR_TILE + (threadIdx.x & 7u), py = ty * HJR_TILE + (threadIdx.x >> 3);
-        if (px >= A.width || py >= A.height) continue;
-        const float W = (float)A.width, H = (float)A.height;
-        const float u = (2.0f * ((float)px + 0.5f) - W) / H, v = (2.0f * ((float)py + 0.5f) - H) / H;
-        const f3 cd = V(A.cam.dir[0], A.cam.dir[1], A.cam.dir[2]), cu = V(A.cam.up[0], A.cam.up[1], A.cam.up[2]);
-        const f3 cr = V(A.cam.right[0], A.cam.right[1], A.cam.right[2]);
-        const f3 d = normalize(cd * A.cam.f + cr * u + cu * v);
-        Hit h;
-        Counters cnt; cnt.box = cnt.tri = 0;
-        hjr_gbuffer_px r;
-        r.prim = 0xffffffffu; r.inst = 0u; r.t = r.b1 = r.b2 = 0.0f; r.pad = 0u;
-        for (int k = 0; k < 3; k++) r.pos[k] = r.ng[k] = 0.0f;
-        if (traverse<false, false, WIDTH, 64, ST>(A.nodes, A.tri_geom, V(A.cam.pos[0], A.cam.pos[1], A.cam.pos[2]), d, 0.001f, 1e16f, h, stack, cnt) && h.prim < A.n_tris) {
-            const float4* g = A.tri_geom + (size_t)h.k * HJR_TRI_F4;
-            const float4 g0 = g[0], g1 = g[1], g2 = g[2];
-            const f3 v0 = V(g0.x, g0.y, g0.z), v1 = V(g0.w, g1.x, g1.y), v2 = V(g1.z, g1.w, g2.x);
-            const float w0 = 1.0f - h.b1 - h.b2;
-            const f3 pos = v0 * w0 + v1 * h.b1 + v2 * h.b2;
-            const f3 ng = cross(v1 - v0, v2 - v0);
-            r.prim = h.prim; r.inst = A.tri_inst[h.prim];
-            r.t = h.t; r.b1 = h.b1; r.b2 = h.b2;
-            r.pos[0] = pos.x; r.pos[1] = pos.y; r.pos[2] = pos.z;
-            r.ng[0] = ng.x; r.ng[1] = ng.y; r.ng[2] = ng.z;
-        }
-        A.out[(size_t)py * A.width + px] = r;
-    }
-}
-
 HD float t_dot(f3 a, f3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
-// The coverage pass: the G-buffer kernel's launch shape and stacks; per pixel the centre ray (iteration 0) and the n * n sub-pixel rays
-// (iterations 1 .. n * n) go through one traversal call site, every lane of a wave runs all n * n + 1 iterations, and what is carried from
-// the centre to the sub-rays are scalars (no per-lane array).
-struct GbufCovArgs {
-    GbufArgs g;
-    const uint32_t* tri_shade; // the shading rows as words: word 15 of a row is the material id
-    uint32_t side;             // 2, 3 or 4
-};
-template <int WIDTH>
-__global__ void __launch_bounds__(64) hjr_gbuffer_cov_kernel(const GbufCovArgs B)
+// One wave per 8 x 8 tile, grid-stride over the tiles; 64 * stack_depth * 4 bytes of dynamic LDS (the classifier's stacks).  Per pixel the
+// centre ray (iteration 0) and, COV, the n * n sub-pixel rays (iterations 1 .. n * n) go through one traversal call site, every lane of a
+// wave runs all iterations, and what is carried from the centre to the sub-rays are scalars (no per-lane array).
+template <int WIDTH, bool COV>
+__global__ void __launch_bounds__(64) hjr_gbuffer_kernel(const GbufArgs A)
 {
-    typedef LaneStack<uint32_t, 64, false> ST;
-    const GbufArgs& A = B.g;
-    ST stack;
-    stack.lds = reinterpret_cast<uint32_t*>(hjr_smem) + threadIdx.x;
-    stack.spill = nullptr; stack.spill_stride = 0; stack.lds_n = 0; stack.n_over = 0; stack.top = nullptr; stack.n_top = 0u;
-    const uint32_t n = B.side, n_rays = n * n;
+    TileStack stack = hjr_tile_stack();
+    const uint32_t n = COV ? A.side : 1u, n_rays = COV ? n * n : 0u;
     for (uint32_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
         uint32_t tx, ty;
         hjr_tile_xy(tile, A.tiles_x, &tx, &ty);
@@ -164,7 +118,7 @@ __global__ void __launch_bounds__(64) hjr_gbuffer_cov_kernel(const GbufCovArgs B
             const f3 d = normalize(cd * A.cam.f + cr * u + cu * v);
             Hit h;
             Counters cnt; cnt.box = cnt.tri = 0;
-            const bool hit = traverse<false, false, WIDTH, 64, ST>(A.nodes, A.tri_geom, cp, d, 0.001f, 1e16f, h, stack, cnt) && h.prim < A.n_tris;
+            const bool hit = traverse<false, false, WIDTH, 64, TileStack>(A.nodes, A.tri_geom, cp, d, 0.001f, 1e16f, h, stack, cnt) && h.prim < A.n_tris;
             f3 pos = V1(0.0f), ng = V1(0.0f);
             uint32_t inst = 0u, mat = 0u;
             if (hit) {
@@ -175,7 +129,7 @@ __global__ void __launch_bounds__(64) hjr_gbuffer_cov_kernel(const GbufCovArgs B
                 pos = v0 * w0 + v1 * h.b1 + v2 * h.b2;
                 ng = cross(v1 - v0, v2 - v0);
                 inst = A.tri_inst[h.prim];
-                mat = B.tri_shade[(size_t)h.prim * (HJR_SHADE_F4 * 4) + 15u];
+                if constexpr (COV) mat = A.tri_shade[(size_t)h.prim * (HJR_SHADE_F4 * 4) + 15u];
             }
             if (it == 0u) {
                 if (hit) {
@@ -183,11 +137,13 @@ __global__ void __launch_bounds__(64) hjr_gbuffer_cov_kernel(const GbufCovArgs B
                     r.t = h.t; r.b1 = h.b1; r.b2 = h.b2;
                     r.pos[0] = pos.x; r.pos[1] = pos.y; r.pos[2] = pos.z;
                     r.ng[0] = ng.x; r.ng[1] = ng.y; r.ng[2] = ng.z;
-                    c_mat = mat;
-                    const f3 view = pos - cp;
-                    const float vv = t_dot(view, view), fh = A.cam.f * H;
-                    const float fp2 = (vv * 4.0f) / (fh * fh), nn = t_dot(ng, ng);
-                    lim = ((HJR_TEMPORAL_K_PLANE * HJR_TEMPORAL_K_PLANE) * fp2) * nn;
+                    if constexpr (COV) {
+                        c_mat = mat;
+                        const f3 view = pos - cp;
+                        const float vv = t_dot(view, view), fh = A.cam.f * H;
+                        const float fp2 = (vv * 4.0f) / (fh * fh), nn = t_dot(ng, ng);
+                        lim = ((HJR_TEMPORAL_K_PLANE * HJR_TEMPORAL_K_PLANE) * fp2) * nn;
+                    }
                 }
             } else if (r.prim == 0xffffffffu) {
                 same += hit ? 0u : 1u;
@@ -196,7 +152,7 @@ __global__ void __launch_bounds__(64) hjr_gbuffer_cov_kernel(const GbufCovArgs B
                 same += nd * nd <= lim ? 1u : 0u;
             }
         }
-        r.pad = same | (n_rays << 8);
+        if constexpr (COV) r.pad = same | (n_rays << 8);
         A.out[(size_t)py * A.width + px] = r;
     }
 }
@@ -217,6 +173,7 @@ struct TemporalArgs {
     float4* out_color;
     float* out_variance;
     float* out_history;
+    uint32_t prev_cov, cur_cov; // COV: the two sides' hjr_temporal_frame.coverage
 };
 
 HD f3 t_xf(const float* __restrict__ m, f3 p)
@@ -228,7 +185,11 @@ HD f3 t_lin(const float* __restrict__ m, f3 d)
     return V((m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z, (m[8] * d.x + m[9] * d.y) + m[10] * d.z);
 }
 HD bool t_finite(float x) { return fabsf(x) <= HJ_FLT_MAX; }
+HD bool t_mixed(uint32_t pad) { const uint32_t total = (pad >> 8) & 0xffu; return total > 0u && (pad & 0xffu) < total; }
 
+// COV: the coverage-aware accumulation (rules 2' and 3' of the header comment), launched only when a side carries coverage.  Its four
+// expressions (g_mixed, the snap tap, n_taps, the pad test of a tap) are constants in the plain instantiation and fold away there.
+template <bool COV>
 __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
 {
     const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
@@ -253,91 +214,12 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
         const float u = su / s, v = sv / s;
         const float xp = (u * H + W) * 0.5f - 0.5f, yp = (v * H + H) * 0.5f - 0.5f;
         if (det != 0.0f && s > 0.0f && t_finite(s) && t_finite(u) && t_finite(v) && xp >= -1.0f && xp < W && yp >= -1.0f && yp < H) {
+            const bool g_mixed = COV && A.cur_cov != 0u && t_mixed(G.pad);
             const float fx = floorf(xp), fy = floorf(yp);
-            const int x0 = (int)fx, y0 = (int)fy;
-            const float tx = xp - fx, ty = yp - fy;
-            const float wk[4] = { (1.0f - tx) * (1.0f - ty), tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty };
-            const f3 view = gpos - V(A.cur.cam.pos[0], A.cur.cam.pos[1], A.cur.cam.pos[2]), ng = V(G.ng[0], G.ng[1], G.ng[2]);
-            const float vv = t_dot(view, view), fh = A.cur.cam.f * H;
-            const float fp2 = (vv * 4.0f) / (fh * fh), nn = t_dot(ng, ng), nv = t_dot(ng, view);
-            const float lim_plane = ((HJR_TEMPORAL_K_PLANE * HJR_TEMPORAL_K_PLANE) * fp2) * nn;
-            const float lim_dist = (((HJR_TEMPORAL_K_DIST * HJR_TEMPORAL_K_DIST) * fp2) * nn) * vv;
-            const float* const m_cur = A.cur.m + (size_t)G.inst * 12u;
-            float S = 0.0f, Cx = 0.0f, Cy = 0.0f, Cz = 0.0f, Vs = 0.0f, Hs = 0.0f;
-            bool unknown = false;
-            for (int k = 0; k < 4; k++) {
-                const int xt = x0 + (k & 1), yt = y0 + (k >> 1);
-                if (xt < 0 || yt < 0 || xt >= (int)A.width || yt >= (int)A.height) continue;
-                const size_t tap = (size_t)yt * A.width + (size_t)xt;
-                const hjr_gbuffer_px T = A.prev.gbuf[tap];
-                if (T.prim == 0xffffffffu || T.prim >= A.n_tris || T.inst != G.inst) continue; // (G.inst < n_instances: so is T.inst)
-                const f3 e = t_xf(A.prev.inv + (size_t)T.inst * 12u, V(T.pos[0], T.pos[1], T.pos[2])) - p_obj;
-                const f3 D = t_lin(m_cur, e);
-                const float nd = t_dot(ng, D);
-                if (!(nd * nd <= lim_plane) || !(t_dot(D, D) * (nv * nv) <= lim_dist)) continue;
-                const float4 pc = A.prev.color[tap];
-                const float pv = A.prev.variance[tap];
-                S = S + wk[k];
-                Cx = Cx + pc.x * wk[k]; Cy = Cy + pc.y * wk[k]; Cz = Cz + pc.z * wk[k];
-                unknown = unknown || !(pv < HJR_VARIANCE_UNKNOWN);
-                Vs = Vs + fmaxf(pv, 0.0f) * wk[k];
-                Hs = Hs + A.prev.history[tap] * wk[k];
-            }
-            if (S > 0.0f) {
-                const float px_ = Cx / S, py_ = Cy / S, pz_ = Cz / S, v_prev = Vs / S, h_prev = Hs / S;
-                hist = fminf(fmaxf(h_prev + 1.0f, 1.0f), HJR_TEMPORAL_H_MAX);
-                const float al = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA);
-                out.x = px_ + (cc.x - px_) * al; out.y = py_ + (cc.y - py_) * al; out.z = pz_ + (cc.z - pz_) * al;
-                unknown = unknown || !(cv < HJR_VARIANCE_UNKNOWN);
-                const float om = 1.0f - al;
-                var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0.0f);
-            }
-        }
-    }
-    A.out_color[pix] = out;
-    A.out_variance[pix] = var;
-    A.out_history[pix] = hist;
-}
-
-// The coverage-aware accumulation (rules 2' and 3' of the header comment).  A kernel of its own, launched only when a side carries coverage,
-// so that hjr_temporal_kernel keeps its code and its registers.
-struct TemporalCovArgs {
-    TemporalArgs a;
-    uint32_t prev_cov, cur_cov; // the two sides' hjr_temporal_frame.coverage
-};
-HD bool t_mixed(uint32_t pad) { const uint32_t total = (pad >> 8) & 0xffu; return total > 0u && (pad & 0xffu) < total; }
-
-__global__ void __launch_bounds__(256) hjr_temporal_cov_kernel(const TemporalCovArgs B)
-{
-    const TemporalArgs& A = B.a;
-    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
-    if (x >= A.width || y >= A.height) return;
-    const size_t pix = (size_t)y * A.width + x;
-    const float4 cc = A.cur.color[pix];
-    const float cv = A.cur.variance[pix];
-    float4 out = cc;
-    float var = cv, hist = 1.0f;
-    const hjr_gbuffer_px G = A.cur.gbuf[pix];
-    if (A.have_prev && G.prim != 0xffffffffu && G.prim < A.n_tris && G.inst < A.n_instances) {
-        const float W = (float)A.width, H = (float)A.height;
-        const f3 gpos = V(G.pos[0], G.pos[1], G.pos[2]);
-        const f3 p_obj = t_xf(A.cur.inv + (size_t)G.inst * 12u, gpos);
-        const f3 p_prev = t_xf(A.prev.m + (size_t)G.inst * 12u, p_obj);
-        const f3 w = p_prev - V(A.prev.cam.pos[0], A.prev.cam.pos[1], A.prev.cam.pos[2]);
-        const f3 a = V(A.prev.cam.dir[0] * A.prev.cam.f, A.prev.cam.dir[1] * A.prev.cam.f, A.prev.cam.dir[2] * A.prev.cam.f);
-        const f3 b = V(A.prev.cam.right[0], A.prev.cam.right[1], A.prev.cam.right[2]), c = V(A.prev.cam.up[0], A.prev.cam.up[1], A.prev.cam.up[2]);
-        const f3 bc = cross(b, c);
-        const float det = t_dot(a, bc);
-        const float s = t_dot(w, bc) / det, su = t_dot(a, cross(w, c)) / det, sv = t_dot(a, cross(b, w)) / det;
-        const float u = su / s, v = sv / s;
-        const float xp = (u * H + W) * 0.5f - 0.5f, yp = (v * H + H) * 0.5f - 0.5f;
-        if (det != 0.0f && s > 0.0f && t_finite(s) && t_finite(u) && t_finite(v) && xp >= -1.0f && xp < W && yp >= -1.0f && yp < H) {
-            const bool g_mixed = B.cur_cov != 0u && t_mixed(G.pad);
-            const float fx = floorf(xp), fy = floorf(yp);
-            const float tx = xp - fx, ty = yp - fy;
             const float xr = floorf(xp + 0.5f), yr = floorf(yp + 0.5f); // within [-1, W] x [-1, H] by the range test above
             const bool snap = fabsf(xp - xr) <= HJR_TEMPORAL_SNAP && fabsf(yp - yr) <= HJR_TEMPORAL_SNAP;
             const int x0 = (int)(g_mixed ? xr : fx), y0 = (int)(g_mixed ? yr : fy);
+            const float tx = xp - fx, ty = yp - fy;
             const int n_taps = g_mixed ? (snap ? 1 : 0) : 4;
             const float wk[4] = { g_mixed ? 1.0f : (1.0f - tx) * (1.0f - ty), tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty };
             const f3 view = gpos - V(A.cur.cam.pos[0], A.cur.cam.pos[1], A.cur.cam.pos[2]), ng = V(G.ng[0], G.ng[1], G.ng[2]);
@@ -348,7 +230,8 @@ __global__ void __launch_bounds__(256) hjr_temporal_cov_kernel(const TemporalCov
             const float* const m_cur = A.cur.m + (size_t)G.inst * 12u;
             float S = 0.0f, Cx = 0.0f, Cy = 0.0f, Cz = 0.0f, Vs = 0.0f, Hs = 0.0f;
             bool unknown = false;
-#pragma unroll
+            constexpr int kUnroll = COV ? 4 : 1; // the loop shapes each instantiation was measured with: the coverage rules unrolled, the plain loop rolled
+#pragma unroll kUnroll
             for (int k = 0; k < 4; k++) {
                 if (k >= n_taps) continue;
                 const int xt = x0 + (k & 1), yt = y0 + (k >> 1);
@@ -356,7 +239,7 @@ __global__ void __launch_bounds__(256) hjr_temporal_cov_kernel(const TemporalCov
                 const size_t tap = (size_t)yt * A.width + (size_t)xt;
                 const hjr_gbuffer_px T = A.prev.gbuf[tap];
                 if (T.prim == 0xffffffffu || T.prim >= A.n_tris || T.inst != G.inst) continue; // (G.inst < n_instances: so is T.inst)
-                if (B.prev_cov != 0u && (g_mixed ? T.pad != G.pad : t_mixed(T.pad))) continue; // rules 2' and 3'
+                if (COV && A.prev_cov != 0u && (g_mixed ? T.pad != G.pad : t_mixed(T.pad))) continue; // rules 2' and 3'
                 const f3 e = t_xf(A.prev.inv + (size_t)T.inst * 12u, V(T.pos[0], T.pos[1], T.pos[2])) - p_obj;
                 const f3 D = t_lin(m_cur, e);
                 const float nd = t_dot(ng, D);

@@ -114,6 +114,25 @@ def test_records_equal_the_checker(cornell, options, w, h):
         d.close()
 
 
+def test_both_passes_share_one_centre_ray(cornell):
+    """43 x 29 (partial tiles in both directions), the default layout and "bvh_width" 4, sides 2 and 4: with pad zeroed the coverage pass's
+    records are hjr_render_gbuffer's byte for byte, and the plain record's pad is 0 everywhere."""
+    w, h = 43, 29
+    p = hjr.make_params(w, h, 1, camera_at(cornell, x=3.5))
+    for options in (dict(), dict(bvh_width=4)):
+        d = cornell.device(options)
+        try:
+            plain = d.gbuffer(p)
+            assert plain.shape == (h, w) and (plain["pad"] == 0).all() and (plain["prim"] != MISS).any()
+            for side in (2, 4):
+                g = d.gbuffer(p, coverage=side).copy()
+                assert ((g["pad"] >> 8) == side * side).all()
+                g["pad"] = 0
+                assert g.tobytes() == plain.tobytes(), "%s, side %d" % (options, side)
+        finally:
+            d.close()
+
+
 def test_entry_point_refusals(cornell, dev):
     L = hjr.lib()
     out = np.zeros((8, 8), hjr.GBUFFER_DTYPE)

@@ -262,6 +262,53 @@ def test_render_denoised_refusals(cornell):
         d.close()
 
 
+def test_a_refused_output_size_does_not_advance_a_progressive_frame(cornell):
+    """hjr_render_denoised in DenoiseUpScale2X as the second sample pass of a frame, with an output size that breaks the size rule: the
+    refusal's code and text, nothing written, and the frame has not moved: the same pass with the right size gives the one-shot image."""
+    L = hjr.lib()
+    w, h, ow, oh, spp = 24, 16, 48, 32, 16
+    g = hjr.sample_granule(spp)
+    assert 0 < g < spp
+    d = cornell.device()
+    try:
+        p = cornell.hjr_params(w, h, spp)
+        want = d.render_denoised(p, UP, ow, oh)
+        d.render_denoised(with_range(p, 0, g), UP, ow, oh)
+        second = with_range(p, g, spp)
+        out = np.full((oh, ow + 2, 4), -7.0, f32)
+        rc = L.hjr_render_denoised(d._h, C.byref(second), UP, out.ctypes.data, ow + 2, oh)
+        assert rc == ERR_ARG and L.hjr_last_error().decode() == "hjr_denoise: DenoiseUpScale2X renders at (out_w / 2, out_h / 2)"
+        assert (out == -7.0).all()
+        assert_bits(d.render_denoised(second, UP, ow, oh), want, "the pass after the refusal")
+    finally:
+        d.close()
+
+
+def test_the_renders_own_refusals_keep_their_text_in_render_denoised(cornell):
+    """What the render itself refuses (no frame data, a frame above its size limit) is refused in its words by hjr_render_denoised too,
+    whatever the post stage would have said about the same call: with "denoise_temporal" on, and in Default mode."""
+    L = hjr.lib()
+    out = np.full((1, 16400, 4), -7.0, f32)
+
+    def call(d, p, mode, ow, oh):
+        rc = L.hjr_render_denoised(d._h, C.byref(p), mode, out.ctypes.data, ow, oh)
+        return rc, L.hjr_last_error().decode()
+
+    d = hjr.Device(0)
+    try:
+        d.upload_scene(cornell.scene.view)  # no transforms yet: no frame data
+        d.set_option("denoise_temporal", 1)
+        assert call(d, cornell.hjr_params(24, 16, 8), hjr.MODE_DENOISE, 24, 16) == (ERR_STATE, "hjr_render: upload a scene and set transforms first")
+        d.set_transforms(cornell.arrays["transforms"], cornell.arrays["inv_transforms"])
+        too_large = "hjr_render: frames larger than 8192 x 8192 are not supported"
+        assert call(d, cornell.hjr_params(8200, 1, 8), hjr.MODE_DENOISE, 8200, 1) == (ERR_ARG, too_large)
+        d.set_option("denoise_temporal", 0)
+        assert call(d, cornell.hjr_params(16400, 1, 8), hjr.MODE_DEFAULT, 16400, 1) == (ERR_ARG, too_large)
+        assert (out == -7.0).all()
+    finally:
+        d.close()
+
+
 # ------------------------------------------------------------------------------------------------------------------ 3. shards
 @pytest.mark.parametrize("filt", [None, "denoise_temporal"], ids=["plain", "temporal"])
 def test_shards_of_three_ranks_equal_the_one_rank_image(cornell, filt):
