@@ -31,7 +31,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/henjou_hip.h"
+#include "../host/render_job.hpp"
 
 #define HIPX(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fprintf(stderr, "henjou_cli[%d]: %s: %s\n", rank, #call, hipGetErrorString(e_)); return 1; } } while (0)
 #define NCCLX(call) do { ncclResult_t e_ = (call); if (e_ != ncclSuccess) { fprintf(stderr, "henjou_cli[%d]: %s: %s\n", rank, #call, ncclGetErrorString(e_)); return 1; } } while (0)
@@ -55,31 +55,15 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     hjr_render_option opt;
     HJR_INIT(opt);
     HJRX(hjr_load_render_option(json, &opt));
-    if (opt.render_mode != HJR_MODE_DEFAULT && opt.render_mode != HJR_MODE_DENOISE && opt.render_mode != HJR_MODE_DENOISE_UPSCALE2X) {
-        fprintf(stderr, "henjou_cli: Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)\n");
-        return 1;
-    }
     // Denoise modes (DESIGN.md §7 "Denoise modes"): every rank renders its tiles with the guide AOVs, and the variance AOV when the filter
     // options ask for it, into ONE per-rank buffer colour | albedo | normal | variance; the frame's one gather moves that buffer, and rank 0
     // assembles, accumulates and filters (hjr_denoise_shards_device).  The filter needs the whole frame, so it is not distributed.
-    const bool denoise = opt.render_mode != HJR_MODE_DEFAULT;
-    const bool with_var = denoise && opt.denoise_variance != 0;   // "denoise_variance" / "denoise_temporal" (stored as 2)
-    const bool temporal = denoise && opt.denoise_variance == 2;
-    if (temporal && opt.noise_threshold > 0.0f) {
-        fprintf(stderr, "henjou_cli: \"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history\n");
-        return 1;
-    }
-    // "firefly_clamp" (stored in bits 16..22 of device_bvh_opt) acts on whole-frame renders only, as in hjr_render_file; every rank clamps
-    // its own pixels (the rule is per pixel), so the gathered frame is the single-GPU one
-    const int firefly = (opt.device_bvh_opt >> 16) & 0x7f;
-    if (firefly && (opt.passes > 1 || opt.noise_threshold > 0.0f)) {
-        fprintf(stderr, "henjou_cli: \"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only\n");
-        return 1;
-    }
-    // Image Scale Setting (renderer.h:1089-1099): DenoiseUpScale2X renders at half the output size, as hjr_render_file does
-    const uint32_t W = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_width / 2u : opt.image_width;
-    const uint32_t H = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_height / 2u : opt.image_height;
-    if (W == 0 || H == 0) { fprintf(stderr, "henjou_cli: image too small for DenoiseUpScale2X\n"); return 1; }
+    // The refusals and the sizes are hjr_render_file's (host/render_job.hpp); "firefly_clamp" is per pixel, so every rank clamps its own
+    hjr::Job job;
+    std::string refusal;
+    if (!hjr::job_check(opt, job, refusal)) { fprintf(stderr, "henjou_cli: %s\n", refusal.c_str()); return 1; }
+    const bool denoise = job.denoise, with_var = job.with_var;
+    const uint32_t W = job.w, H = job.h, OW = job.out_w, OH = job.out_h; // the render size; the PNG's size
     hjr_scene* scene = nullptr;
     HJRX(hjr_scene_load_gltf(opt.gltf_path, opt.gltf_name, &opt, &scene));
     hjr_scene_view view;
@@ -87,36 +71,14 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     HJRX(hjr_scene_get_view(scene, &view));
     hjr_ctx* ctx = nullptr;
     HJRX(hjr_create(rank, &ctx));
-    if (opt.force_rebuild & 2) HJRX(hjr_set_option(ctx, "verbose", 1)); // key "verbose": stored as bit 1 of force_rebuild
-    if (opt.device_bvh) HJRX(hjr_set_option(ctx, "device_bvh", 1));
-    if (opt.device_bvh > 1) HJRX(hjr_set_option(ctx, "device_bvh_refit", opt.device_bvh - 1)); // key "device_bvh_refit": stored as 1 + N
-    if (opt.device_bvh_opt & 0xff) HJRX(hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt & 0xff));
-    if (opt.device_bvh_opt & 0x100) HJRX(hjr_set_option(ctx, "device_bvh_instances", 1)); // key "device_bvh_instances": bit 8 of the field
-    if (opt.device_bvh_opt & 0x200) HJRX(hjr_set_option(ctx, "device_bvh_graft", 1)); // key "device_bvh_graft": bit 9
-    if (rank == 0 && with_var) HJRX(hjr_set_option(ctx, "denoise_variance", 1)); // rank 0 filters
-    if (rank == 0 && temporal) HJRX(hjr_set_option(ctx, "denoise_temporal", 1));
-    if (rank == 0 && (opt.device_bvh_opt & 0x400)) HJRX(hjr_set_option(ctx, "denoise_variance_spatial", 1)); // key "denoise_variance_spatial": bit 10 of the field
-    if (rank == 0 && (opt.device_bvh_opt & 0x800)) HJRX(hjr_set_option(ctx, "upscale_guided", 1)); // key "upscale_guided": bit 11; rank 0 upscales, and has the frame data: it renders its own tiles
-    if (rank == 0 && ((opt.device_bvh_opt >> 12) & 7)) HJRX(hjr_set_option(ctx, "denoise_temporal_coverage", (opt.device_bvh_opt >> 12) & 7)); // key "denoise_temporal_coverage": bits 12..14; rank 0 accumulates
-    if (firefly) HJRX(hjr_set_option(ctx, "firefly_clamp", firefly));
+    // every rank builds and renders; rank 0 also filters, accumulates and upscales, and has the frame data for it: it renders its own tiles
+    HJRX(hjr::for_each_option(opt, hjr::rank_of_world(rank), [&](const char* key, int value) { return hjr_set_option(ctx, key, value); }));
     HJRX(hjr_upload_scene(ctx, &view));
     // "noise_threshold": each rank stops its own converged tiles between the sample passes (the rule does not depend on the rank); the one
     // gather per frame is unchanged.  A rank without tiles has nothing to adapt.
-    const bool adaptive = opt.noise_threshold > 0.0f && hjr_owned_tiles(W, H, (uint32_t)rank, (uint32_t)world) > 0;
-    if (adaptive) {
-        hjr_adaptive ad;
-        HJR_INIT(ad);
-        ad.noise_threshold = opt.noise_threshold; ad.min_samples = opt.min_samples;
-        HJRX(hjr_set_adaptive(ctx, &ad));
-    }
-    {
-        uint8_t* lut = nullptr; int lw = 0, lh = 0;
-        if (hjr_load_png_rgba8(opt.LUT_path, &lut, &lw, &lh) == HJR_OK) { HJRX(hjr_set_lut(ctx, lut, lw, lh)); hjr_free(lut); }
-        if (opt.use_IBL) {
-            float* sky = nullptr; int sw = 0, sh = 0;
-            if (hjr_load_hdr_rgba32f(opt.IBL_path, &sky, &sw, &sh) == HJR_OK) { HJRX(hjr_set_sky(ctx, sky, sw, sh)); hjr_free(sky); }
-        }
-    }
+    const bool adaptive = job.adaptive && hjr_owned_tiles(W, H, (uint32_t)rank, (uint32_t)world) > 0;
+    if (adaptive) HJRX(hjr::set_adaptive(ctx, opt));
+    HJRX(hjr::upload_assets(ctx, opt, view, rank == 0));
     // RCCL communicator: rank 0 creates the id and writes it to its pipe; the launcher passes it on to the pipes of the other ranks
     // (a world of one needs no hand-over).  Everything fallible that does not need the peers has happened above.
     HIPX(hipSetDevice(rank));
@@ -131,7 +93,6 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     hipStream_t st;
     HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 
-    const uint32_t OW = opt.image_width, OH = opt.image_height; // the PNG's size; W x H is the render size
     const size_t block = (size_t)hjr_owned_tiles(W, H, 0, (uint32_t)world) * 64; // slots per rank and AOV (rank 0 owns the most tiles; others pad)
     const size_t rank_floats = block * (denoise ? (with_var ? 13u : 12u) : 4u);  // the per-rank buffer: three float4 AOVs and one float, or the colour alone
     float *d_packed = nullptr, *d_all = nullptr, *d_frame = nullptr;
@@ -151,21 +112,14 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
         HJRX(hjr_scene_eval_transforms(scene, time, m.data(), inv.data()));
         HJRX(hjr_set_transforms(ctx, m.data(), inv.data(), view.n_instances));
         hjr_params p;
-        HJR_INIT(p);
-        p.width = W; p.height = H; p.spp = opt.max_spp; p.frame = f; p.seed = opt.seed; p.integrator = (uint32_t)opt.integrator;
-        HJRX(hjr_scene_eval_camera(scene, &opt, time, &p.camera));
-        for (int k = 0; k < 3; k++) p.sky[k] = opt.scene_sky_default[k];
-        p.ibl_intensity = opt.IBL_intensity;
-        p.rank = (uint32_t)rank; p.world_size = (uint32_t)world; p.flags = HJR_FLAG_PACKED | (opt.fast_math ? HJR_FLAG_FAST_MATH : 0u);
+        HJRX(hjr::frame_params(opt, scene, f, W, H, p));
+        p.rank = (uint32_t)rank; p.world_size = (uint32_t)world; p.flags |= HJR_FLAG_PACKED;
         const auto t0 = std::chrono::steady_clock::now();
-        // "passes": the frame in sample passes split as hjr_render_file splits it (k * spp / passes rounded down to the granule, empty
-        // passes dropped); the last pass leaves the frame's tiles in d_packed
-        const uint32_t n_pass = opt.passes ? opt.passes : 1u, g = hjr_sample_granule(p.spp);
-        uint32_t n_done = 0;
-        for (uint32_t k = 1, begin = 0; k <= n_pass; k++) {
-            const uint32_t end = k == n_pass ? p.spp : (g ? (uint32_t)((uint64_t)k * p.spp / n_pass) / g * g : 0u);
-            if (end <= begin) continue;
-            if (n_pass > 1) { p.sample_begin = begin; p.sample_end = end; }
+        // "passes": the frame in sample passes, split as hjr_render_file splits it; the last pass leaves the frame's tiles in d_packed
+        uint32_t n_done = 0, begin = 0;
+        for (const uint32_t end : hjr::pass_ends(p.spp, opt.passes ? opt.passes : 1u)) {
+            if (end <= begin) continue; // (a frame of no samples has no pass)
+            if (opt.passes > 1) { p.sample_begin = begin; p.sample_end = end; }
             HJRX(hjr_render_device_var(ctx, &p, d_packed, d_albedo, d_normal, d_var, st)); // (Default: the colour alone, hjr_render_device's launch)
             begin = end;
             n_done++;
@@ -204,9 +158,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
         if (rank == 0) {
             std::vector<uint8_t> rgba8((size_t)OW * OH * 4);
             HJRX(hjr_float4_to_srgb8(frame.data(), rgba8.data(), OW * OH));
-            std::string n = std::to_string(f); // renderer.h:1291-1302
-            while (n.size() < 3) n = "0" + n;
-            HJRX(hjr_write_png((std::string(opt.image_name) + "_" + n + ".png").c_str(), rgba8.data(), OW, OH, 1));
+            HJRX(hjr_write_png(hjr::frame_png_name(opt, f).c_str(), rgba8.data(), OW, OH, 1));
         }
     }
     ncclCommDestroy(comm);

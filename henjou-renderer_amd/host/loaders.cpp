@@ -10,6 +10,8 @@
 #include <sstream>
 
 #include "json.hpp"
+#include "options.hpp"
+#include "render_job.hpp"
 #include "scene.hpp"
 
 namespace hjr {
@@ -44,6 +46,32 @@ static bool fps_loader(unsigned int& fps, const std::string& path)
         while (std::getline(ifs, str)) { fps = (unsigned int)std::stoi(str); any = true; }
     } catch (std::exception&) { return false; }
     return any;
+}
+
+// The readers of the "Henjou_HIP" section.  A lenient flag: a bool, or a number with non-zero true; absent is false
+static bool flag(const Json* v) { return v ? (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) : false; }
+// An integer in [lo, hi] that context option `holes` (-1: none) does not refuse inside its range; the message gives the range, or with holes the values
+static int int_in(const Json& v, const std::string& name, int lo, int hi, int holes = -1)
+{
+    const double n = v.is_number() ? v.as_number() : lo - 1.0;
+    if (n >= lo && n <= hi && n == (double)(int)n && !(holes >= 0 && opt_hole(holes, (int)n))) return (int)n;
+    std::string want = holes < 0 ? "an integer in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]" : "";
+    for (int k = hi, after = 0; holes >= 0 && k >= lo; k--) // "0, 2, 3 or 4", built from its end
+        if (!opt_hole(holes, k)) want = std::to_string(k) + (after == 0 ? "" : after == 1 ? " or " : ", ") + want, after++;
+    throw JsonError(name + " must be " + want);
+}
+// One key of render_job.hpp's table: its value as the row says it is read (the context option of the same name has the range), the key it
+// needs, then its place in the struct
+static void parse_key(const Json& h, const KeyRow& r, hjr_render_option& o)
+{
+    const Json* v = h.find(r.key);
+    if (!v) return;
+    const std::string name = std::string("Henjou_HIP.") + r.key;
+    const int oi = opt_find(r.key);
+    if (r.read == READ_BOOL && !v->is_bool() && !(v->is_number() && (v->as_number() == 0.0 || v->as_number() == 1.0))) throw JsonError(name + " must be true, false, 0 or 1");
+    const int val = r.read == READ_FLAG || r.read == READ_BOOL ? (int)flag(v) : int_in(*v, name, opt_table()[oi].lo, opt_table()[oi].hi, r.read == READ_SET ? oi : -1);
+    if (r.needs && !key_get(o, key_row(r.needs))) throw JsonError(name + " needs \"" + r.needs + "\": true");
+    key_put(o, r, val);
 }
 
 bool load_render_option(const std::string& path, hjr_render_option& o, std::string& err)
@@ -128,74 +156,15 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             o.tile = 8;
             // serial_io: hjr_render_file without the overlap of the output stage / the next frame's host preparation with the render;
             // fast_math: the approximate-arithmetic kernels (HJR_FLAG_FAST_MATH; pictures within the metric's RMSE tolerance, not bit-exact)
-            auto flag = [&](const char* k) { const Json* v = h->find(k); return v ? (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) : false; };
-            o.serial_io = flag("serial_io") ? 1 : 0;
-            o.fast_math = flag("fast_math") ? 1 : 0;
-            o.force_rebuild = flag("force_rebuild") ? 1 : 0;
-            if (flag("verbose")) o.force_rebuild |= 2; // option "verbose" (one stderr line per frame-data build); the struct does not grow for it
-            o.device_bvh = flag("device_bvh") ? 1 : 0; // the frame data built on the device (option "device_bvh")
-            // device_bvh_refit: consecutive refits between two device builds (option "device_bvh_refit"), stored as device_bvh = 1 + N:
-            // the struct does not grow for it and every reader takes non-zero as "device build"
-            if (const Json* v = h->find("device_bvh_refit")) {
-                const double n = v->is_number() ? v->as_number() : -1.0;
-                if (!(n >= 0 && n <= 1000) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.device_bvh_refit must be an integer in [0, 1000]");
-                if (!o.device_bvh) throw JsonError("Henjou_HIP.device_bvh_refit needs \"device_bvh\": true");
-                o.device_bvh = 1 + (int32_t)n;
-            }
-            o.denoise_variance = flag("denoise_variance") ? 1 : 0; // the variance-guided filter in the Denoise modes (option "denoise_variance")
-            if (flag("denoise_temporal")) o.denoise_variance = 2; // ... plus temporal accumulation (option "denoise_temporal"); the struct does not grow for it
-            // device_bvh_opt: treelet-restructuring rounds of the device build (option "device_bvh_opt")
-            if (const Json* v = h->find("device_bvh_opt")) {
-                const double r = v->is_number() ? v->as_number() : -1.0;
-                if (!(r >= 0 && r <= 3) || r != (double)(uint32_t)r) throw JsonError("Henjou_HIP.device_bvh_opt must be an integer in [0, 3]");
-                o.device_bvh_opt = (int32_t)r;
-            }
-            // device_bvh_instances: per-instance trees under a per-commit top tree (option "device_bvh_instances"), stored as bit 8 of
-            // device_bvh_opt: the struct does not grow for it and the low bits stay the rounds
-            if (const Json* v = h->find("device_bvh_instances")) {
-                const bool ok = v->is_bool() || (v->is_number() && (v->as_number() == 0.0 || v->as_number() == 1.0));
-                if (!ok) throw JsonError("Henjou_HIP.device_bvh_instances must be true, false, 0 or 1");
-                if (!o.device_bvh) throw JsonError("Henjou_HIP.device_bvh_instances needs \"device_bvh\": true");
-                if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x100;
-            }
-            // device_bvh_graft: the instances' BVH4s collapsed once and grafted under a BVH4 top tree (option "device_bvh_graft"), bit 9 of
-            // the same field; it acts only on instance trees, so it is refused without them
-            if (const Json* v = h->find("device_bvh_graft")) {
-                const bool ok = v->is_bool() || (v->is_number() && (v->as_number() == 0.0 || v->as_number() == 1.0));
-                if (!ok) throw JsonError("Henjou_HIP.device_bvh_graft must be true, false, 0 or 1");
-                if (!(o.device_bvh_opt & 0x100)) throw JsonError("Henjou_HIP.device_bvh_graft needs \"device_bvh_instances\": true");
-                if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x200;
-            }
-            // firefly_clamp: kappa of the firefly clamp on whole-frame renders (option "firefly_clamp"), bits 16..22 of device_bvh_opt, the
-            // section's spare bits: the struct does not grow for it and the readers of the BVH bits mask the field
-            if (const Json* v = h->find("firefly_clamp")) {
-                const double n = v->is_number() ? v->as_number() : -1.0;
-                if (!(n >= 0 && n <= 64) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.firefly_clamp must be an integer in [0, 64]");
-                o.device_bvh_opt |= (int32_t)n << 16;
-            }
-            // denoise_variance_spatial: the 3 x 3 estimate for pixels of unknown variance (option "denoise_variance_spatial"), bit 10 of the same
-            // spare bits; it acts only where "denoise_variance" / "denoise_temporal" put a variance in play and is accepted without them
-            if (flag("denoise_variance_spatial")) o.device_bvh_opt |= 0x400;
-            // upscale_guided: the guided 2x upscale of DenoiseUpScale2X (option "upscale_guided"), bit 11 of the same spare bits; the other
-            // render modes accept it and ignore it
-            if (const Json* v = h->find("upscale_guided")) {
-                const bool ok = v->is_bool() || (v->is_number() && (v->as_number() == 0.0 || v->as_number() == 1.0));
-                if (!ok) throw JsonError("Henjou_HIP.upscale_guided must be true, false, 0 or 1");
-                if (v->is_bool() ? v->as_bool() : v->as_number() != 0.0) o.device_bvh_opt |= 0x800;
-            }
-            // denoise_temporal_coverage: the coverage side of the temporal stage (option "denoise_temporal_coverage"), bits 12..14 of the same
-            // spare bits; accepted and without effect without "denoise_temporal"
-            if (const Json* v = h->find("denoise_temporal_coverage")) {
-                const double n = v->is_number() ? v->as_number() : -1.0;
-                if (!(n == 0.0 || n == 2.0 || n == 3.0 || n == 4.0)) throw JsonError("Henjou_HIP.denoise_temporal_coverage must be 0, 2, 3 or 4");
-                o.device_bvh_opt |= (int32_t)n << 12;
-            }
+            o.serial_io = flag(h->find("serial_io")) ? 1 : 0;
+            o.fast_math = flag(h->find("fast_math")) ? 1 : 0;
+            // the keys that share a field of the struct: one row each in render_job.hpp's table, read in the order the format grew in
+            std::vector<const KeyRow*> rows;
+            for (const KeyRow& r : key_table()) rows.push_back(&r);
+            std::sort(rows.begin(), rows.end(), [](const KeyRow* a, const KeyRow* b) { return a->parse < b->parse; });
+            for (const KeyRow* r : rows) parse_key(*h, *r, o);
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it
-            if (const Json* v = h->find("passes")) {
-                const double n = v->is_number() ? v->as_number() : -1.0;
-                if (!(n >= 1 && n <= 64) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.passes must be an integer in [1, 64]");
-                o.passes = (uint32_t)n;
-            }
+            if (const Json* v = h->find("passes")) o.passes = (uint32_t)int_in(*v, "Henjou_HIP.passes", 1, 64);
             // noise_threshold / min_samples: adaptive sampling of the frame's sample passes (hjr_set_adaptive); a threshold without a
             // "passes" key splits the frame into 8 passes
             if (const Json* v = h->find("noise_threshold")) {
@@ -204,11 +173,7 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 o.noise_threshold = (float)t;
                 if (o.noise_threshold > 0.0f && !h->find("passes")) o.passes = 8;
             }
-            if (const Json* v = h->find("min_samples")) {
-                const double n = v->is_number() ? v->as_number() : -1.0;
-                if (!(n >= 0 && n <= 1048576.0) || n != (double)(uint32_t)n) throw JsonError("Henjou_HIP.min_samples must be an integer in [0, 1048576]");
-                o.min_samples = (uint32_t)n;
-            }
+            if (const Json* v = h->find("min_samples")) o.min_samples = (uint32_t)int_in(*v, "Henjou_HIP.min_samples", 0, 1048576);
         }
     } catch (std::exception& e) { // :222-225
         err = std::string("Caught exception: ") + e.what();

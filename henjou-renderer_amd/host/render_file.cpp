@@ -10,7 +10,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/henjou_hip.h"
+#include "render_job.hpp"
 
 namespace hjr {
 void set_error(const std::string& s);
@@ -18,20 +18,6 @@ bool write_png(const std::string& path, const uint8_t* rgba, uint32_t w, uint32_
 void float4_to_srgb8(const float* rgba, uint8_t* out, uint32_t n);
 } // namespace hjr
 using hjr::set_error;
-
-// sample-pass ends of a frame of spp samples in n passes ("Henjou_HIP": {"passes": n}): k * spp / n rounded down to the granule, the last one
-// spp; passes that come out empty are dropped, so a frame never has more passes than chunks.  henjou_cli's rank path splits the same way.
-static std::vector<uint32_t> pass_ends(uint32_t spp, uint32_t n)
-{
-    const uint32_t g = hjr_sample_granule(spp);
-    std::vector<uint32_t> ends;
-    for (uint32_t k = 1; k < n && g; k++) {
-        const uint32_t e = (uint32_t)((uint64_t)k * spp / n) / g * g;
-        if (e > (ends.empty() ? 0u : ends.back())) ends.push_back(e);
-    }
-    ends.push_back(spp);
-    return ends;
-}
 
 // Renderer::initializeAndRender — renderer/renderer.h:1053-1317.  Render_mode "Default" is the pass-through of the reference
 // (its denoiser runs with blendFactor 1); "Denoise" / "DenoiseUpScale2X" keep the reference's data flow with the HIP a-trous
@@ -43,22 +29,9 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     HJR_INIT(opt);
     int rc = hjr_load_render_option(render_option_json, &opt);
     if (rc != HJR_OK) return rc;
-    if (opt.render_mode != HJR_MODE_DEFAULT && opt.render_mode != HJR_MODE_DENOISE && opt.render_mode != HJR_MODE_DENOISE_UPSCALE2X) {
-        set_error("hjr_render_file: Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)");
-        return HJR_ERR_ARG;
-    }
-    // "denoise_temporal" (stored as denoise_variance == 2) in a Denoise mode; Default mode ignores the field as before
-    const bool temporal = opt.denoise_variance == 2 && opt.render_mode != HJR_MODE_DEFAULT;
-    if (temporal && opt.noise_threshold > 0.0f) {
-        set_error("hjr_render_file: \"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history");
-        return HJR_ERR_ARG;
-    }
-    // "firefly_clamp" (stored in bits 16..22 of device_bvh_opt) acts on whole-frame renders only
-    const int firefly = (opt.device_bvh_opt >> 16) & 0x7f;
-    if (firefly && (opt.passes > 1 || opt.noise_threshold > 0.0f)) {
-        set_error("hjr_render_file: \"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only");
-        return HJR_ERR_ARG;
-    }
+    hjr::Job job; // the refusals come before the scene and the device (host/render_job.hpp)
+    std::string refusal;
+    if (!hjr::job_check(opt, job, refusal)) { set_error("hjr_render_file: " + refusal); return HJR_ERR_ARG; }
     hjr_scene* scene = nullptr;
     rc = hjr_scene_load_gltf(opt.gltf_path, opt.gltf_name, &opt, &scene);
     if (rc != HJR_OK) return rc;
@@ -68,52 +41,12 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     hjr_scene_view view;
     HJR_INIT(view);
     hjr_scene_get_view(scene, &view);
-    if (opt.force_rebuild & 1) (void)hjr_set_option(ctx, "force_rebuild", 1);
-    if (opt.force_rebuild & 2) (void)hjr_set_option(ctx, "verbose", 1); // key "verbose": stored as bit 1
-    if (opt.device_bvh) (void)hjr_set_option(ctx, "device_bvh", 1);
-    if (opt.device_bvh > 1) (void)hjr_set_option(ctx, "device_bvh_refit", opt.device_bvh - 1); // key "device_bvh_refit": stored as 1 + N
-    if (opt.device_bvh_opt & 0xff) (void)hjr_set_option(ctx, "device_bvh_opt", opt.device_bvh_opt & 0xff);
-    if (opt.device_bvh_opt & 0x100) (void)hjr_set_option(ctx, "device_bvh_instances", 1); // key "device_bvh_instances": bit 8 of the field
-    if (opt.device_bvh_opt & 0x200) (void)hjr_set_option(ctx, "device_bvh_graft", 1); // key "device_bvh_graft": bit 9
-    if (opt.denoise_variance && opt.render_mode != HJR_MODE_DEFAULT) (void)hjr_set_option(ctx, "denoise_variance", 1); // (Default mode has no filter)
-    if (temporal) (void)hjr_set_option(ctx, "denoise_temporal", 1);
-    if (opt.device_bvh_opt & 0x400) (void)hjr_set_option(ctx, "denoise_variance_spatial", 1); // key "denoise_variance_spatial": bit 10
-    if (opt.device_bvh_opt & 0x800) (void)hjr_set_option(ctx, "upscale_guided", 1); // key "upscale_guided": bit 11 (acts in DenoiseUpScale2X only)
-    if ((opt.device_bvh_opt >> 12) & 7) (void)hjr_set_option(ctx, "denoise_temporal_coverage", (opt.device_bvh_opt >> 12) & 7); // key "denoise_temporal_coverage": bits 12..14
-    if (firefly) (void)hjr_set_option(ctx, "firefly_clamp", firefly);
-    const bool adaptive = opt.noise_threshold > 0.0f; // "noise_threshold": converged tiles stop between the sample passes
-    rc = hjr_upload_scene(ctx, &view);
-    if (rc == HJR_OK && adaptive) {
-        hjr_adaptive ad;
-        HJR_INIT(ad);
-        ad.noise_threshold = opt.noise_threshold; ad.min_samples = opt.min_samples;
-        rc = hjr_set_adaptive(ctx, &ad);
-    }
-    if (rc == HJR_OK) { // setLUT (renderer.h:854-898); a missing LUT file only matters if a material uses it
-        uint8_t* lut = nullptr;
-        int lw = 0, lh = 0;
-        if (hjr_load_png_rgba8(opt.LUT_path, &lut, &lw, &lh) == HJR_OK) {
-            rc = hjr_set_lut(ctx, lut, lw, lh);
-            hjr_free(lut);
-        } else {
-            bool needs = false;
-            for (uint32_t i = 0; i < view.n_materials; i++) needs = needs || view.materials[i].is_thinfilm;
-            if (needs) rc = HJR_ERR_IO; // hjr_last_error() already holds the PNG error
-        }
-    }
-    if (rc == HJR_OK && opt.use_IBL) { // setSky (renderer.h:802-851): a missing / undecodable HDR falls back to the 1x1 scene_sky_default texel (texture.h:89-98)
-        float* sky = nullptr;
-        int sw = 0, sh = 0;
-        if (hjr_load_hdr_rgba32f(opt.IBL_path, &sky, &sw, &sh) == HJR_OK) {
-            rc = hjr_set_sky(ctx, sky, sw, sh);
-            hjr_free(sky);
-        } else fprintf(stderr, "[henjou] %s NOT FOUND: using scene_sky_default\n", opt.IBL_path);
-    }
+    rc = hjr::for_each_option(opt, hjr::single_process(), [&](const char* key, int value) { return hjr_set_option(ctx, key, value); });
+    const bool adaptive = job.adaptive; // "noise_threshold": converged tiles stop between the sample passes
+    if (rc == HJR_OK) rc = hjr_upload_scene(ctx, &view);
+    if (rc == HJR_OK && adaptive) rc = hjr::set_adaptive(ctx, opt);
+    if (rc == HJR_OK) rc = hjr::upload_assets(ctx, opt, view, true);
     std::vector<float> m((size_t)view.n_instances * 12), inv((size_t)view.n_instances * 12);
-    // Image Scale Setting (renderer.h:1089-1099): DenoiseUpScale2X renders at half the output size
-    const uint32_t in_w = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_width / 2u : opt.image_width;
-    const uint32_t in_h = opt.render_mode == HJR_MODE_DENOISE_UPSCALE2X ? opt.image_height / 2u : opt.image_height;
-    if (in_w == 0 || in_h == 0) { set_error("hjr_render_file: image too small for DenoiseUpScale2X"); hjr_destroy(ctx); hjr_scene_free(scene); return HJR_ERR_ARG; }
     const size_t npx = (size_t)opt.image_width * opt.image_height;
     // Output stage off the critical path: float4 -> sRGB8 -> PNG -> file runs on a writer thread while the main thread
     // already builds and renders the next frame (two frame buffers in rotation).  The reference's loop is serial
@@ -175,21 +108,14 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     };
     if (opt.start_frame < opt.end_frame) prepare(opt.start_frame);
     for (uint32_t frame = opt.start_frame; rc == HJR_OK && frame < opt.end_frame; frame++) {
-        float time = frame / float(opt.fps); // renderer.h:1128
         if (prep.joinable()) prep.join();
         if (prep_rc != HJR_OK) { rc = prep_rc; set_error(prep_err); break; }
         rc = hjr_commit_transforms(ctx);
         if (rc != HJR_OK) break;
         if (frame + 1 < opt.end_frame && !serial_io) prep = std::thread(prepare, frame + 1);
         hjr_params p;
-        HJR_INIT(p);
-        p.width = in_w; p.height = in_h;
-        p.spp = opt.max_spp; p.frame = frame; p.seed = opt.seed; p.integrator = (uint32_t)opt.integrator;
-        hjr_scene_eval_camera(scene, &opt, time, &p.camera);
-        for (int k = 0; k < 3; k++) p.sky[k] = opt.scene_sky_default[k];
-        p.ibl_intensity = opt.IBL_intensity;
-        p.rank = 0; p.world_size = 1;
-        if (opt.fast_math) p.flags |= HJR_FLAG_FAST_MATH; // "Henjou_HIP": {"fast_math": true}
+        rc = hjr::frame_params(opt, scene, frame, job.w, job.h, p);
+        if (rc != HJR_OK) break;
         Slot& sl = slots[cur];
         if (!serial_io) { // the slot may still be with the writer (two frames behind)
             std::unique_lock<std::mutex> lk(mu);
@@ -197,7 +123,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
             if (write_rc != HJR_OK) { rc = write_rc; break; }
         }
         // "passes": the frame in sample passes; each pass overwrites the slot with the running mean, the last one with the frame
-        const std::vector<uint32_t> ends = pass_ends(p.spp, opt.passes ? opt.passes : 1u);
+        const std::vector<uint32_t> ends = hjr::pass_ends(p.spp, opt.passes ? opt.passes : 1u);
         // "noise_threshold": the frame ends with the first pass that leaves no tile active; the slot then holds the frame
         float kernel_ms = 0.0f;
         size_t n_done = 0;
@@ -223,10 +149,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
                     std::to_string(as.samples_rendered) + " samples rendered";
         fprintf(stderr, "[henjou] frame %u: %ux%u, %u spp, kernel %.3f ms (%.2f Msamples/s)%s\n", frame, p.width, p.height, p.spp,
                 kernel_ms, kernel_ms > 0 ? (double)p.width * p.height * p.spp / (kernel_ms * 1e3) : 0.0, note.c_str());
-        std::string str_frame = std::to_string(frame); // renderer.h:1291-1302
-        if (str_frame.size() < 2) str_frame = "00" + str_frame;
-        else if (str_frame.size() < 3) str_frame = "0" + str_frame;
-        sl.name = std::string(opt.image_name) + "_" + str_frame + ".png";
+        sl.name = hjr::frame_png_name(opt, frame);
         n_frames++;
         if (serial_io) { rc = write_slot(sl); if (rc != HJR_OK) set_error(write_err); if (rc == HJR_OK && frame + 1 < opt.end_frame) prepare(frame + 1); }
         else {

@@ -1,0 +1,198 @@
+// Job setup shared by the two drivers of a render_option.json (hjr_render_file in host/render_file.cpp, the rank path of cli/henjou_cli.cpp)
+// and by its parser (host/loaders.cpp): the table of the "Henjou_HIP" keys that live in a packed or shared field of hjr_render_option, the
+// refusals, the pass split, the per-frame parameters, the PNG name and the LUT / sky upload.  Header-only on include/henjou_hip.h and the
+// standard library.  No other file masks or shifts a hjr_render_option field: a new stored key is one row here.
+#pragma once
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/henjou_hip.h"
+
+namespace hjr {
+
+enum KeyEnc : uint8_t {
+    ENC_BITS,    // `width` bits at `shift` of the field
+    ENC_NONZERO, // the whole field: 0 / 1 when written, any non-zero value reads as 1 (a later row of the field may raise it)
+    ENC_PLUS1,   // "device_bvh_refit": device_bvh = 1 + N
+    ENC_IS2,     // "denoise_temporal": denoise_variance == 2
+};
+enum KeyRead : uint8_t {
+    READ_FLAG,  // lenient: a bool, or a number (non-zero is true)
+    READ_BOOL,  // strict: true, false, 0 or 1
+    READ_RANGE, // an integer in the range of the context option of the same name (opt_table(), host/options.hpp)
+    READ_SET,   // ... minus the values that option refuses (opt_hole())
+};
+enum KeyWho : uint8_t {
+    WHO_EVERY,          // every process of the job
+    WHO_FILTER,         // the process that filters and upscales: the single one, rank 0 of a world
+    WHO_FILTER_DENOISE, // ... and in Render_mode Denoise / DenoiseUpScale2X only (Default mode has no filter)
+    WHO_SINGLE,         // hjr_render_file only
+};
+struct KeyRow {
+    const char* key;   // the key of the section AND the context option it sets (hjr_set_option): they share their names
+    uint8_t parse;     // the parser's turn: the order the file format grew in, which decides what a file with two bad keys reports
+    int32_t hjr_render_option::*field;
+    KeyEnc enc;
+    uint8_t shift, width;
+    KeyRead read;
+    const char* needs; // the key that must be on for this one to be accepted at all, or nullptr
+    KeyWho who;
+};
+
+// in the order the drivers set the options
+inline const std::vector<KeyRow>& key_table()
+{
+    using O = hjr_render_option;
+    static const std::vector<KeyRow> t = {
+        { "force_rebuild", 0, &O::force_rebuild, ENC_BITS, 0, 1, READ_FLAG, nullptr, WHO_SINGLE },
+        { "verbose", 1, &O::force_rebuild, ENC_BITS, 1, 1, READ_FLAG, nullptr, WHO_EVERY },
+        { "device_bvh", 2, &O::device_bvh, ENC_NONZERO, 0, 31, READ_FLAG, nullptr, WHO_EVERY },
+        { "device_bvh_refit", 3, &O::device_bvh, ENC_PLUS1, 0, 31, READ_RANGE, "device_bvh", WHO_EVERY },
+        { "device_bvh_opt", 6, &O::device_bvh_opt, ENC_BITS, 0, 8, READ_RANGE, nullptr, WHO_EVERY },
+        { "device_bvh_instances", 7, &O::device_bvh_opt, ENC_BITS, 8, 1, READ_BOOL, "device_bvh", WHO_EVERY },
+        { "device_bvh_graft", 8, &O::device_bvh_opt, ENC_BITS, 9, 1, READ_BOOL, "device_bvh_instances", WHO_EVERY },
+        { "denoise_variance", 4, &O::denoise_variance, ENC_NONZERO, 0, 31, READ_FLAG, nullptr, WHO_FILTER_DENOISE },
+        { "denoise_temporal", 5, &O::denoise_variance, ENC_IS2, 0, 31, READ_FLAG, nullptr, WHO_FILTER_DENOISE },
+        { "denoise_variance_spatial", 10, &O::device_bvh_opt, ENC_BITS, 10, 1, READ_FLAG, nullptr, WHO_FILTER },
+        { "upscale_guided", 11, &O::device_bvh_opt, ENC_BITS, 11, 1, READ_BOOL, nullptr, WHO_FILTER },
+        { "denoise_temporal_coverage", 12, &O::device_bvh_opt, ENC_BITS, 12, 3, READ_SET, nullptr, WHO_FILTER },
+        { "firefly_clamp", 9, &O::device_bvh_opt, ENC_BITS, 16, 7, READ_RANGE, nullptr, WHO_EVERY }, // (per pixel: every rank clamps its own)
+    };
+    return t;
+}
+inline const KeyRow& key_row(const char* key)
+{
+    for (const KeyRow& r : key_table()) if (strcmp(r.key, key) == 0) return r;
+    return key_table().front(); // (not reached: the callers name rows of the table)
+}
+inline int key_get(const hjr_render_option& o, const KeyRow& r)
+{
+    const int32_t f = o.*r.field;
+    switch (r.enc) {
+    case ENC_BITS: return (f >> r.shift) & ((1 << r.width) - 1);
+    case ENC_NONZERO: return f != 0;
+    case ENC_PLUS1: return f > 1 ? f - 1 : 0;
+    default: return f == 2;
+    }
+}
+// the parser's side; the rows of a field are stored in their parse order
+inline void key_put(hjr_render_option& o, const KeyRow& r, int v)
+{
+    int32_t& f = o.*r.field;
+    switch (r.enc) {
+    case ENC_BITS: f |= v << r.shift; break;
+    case ENC_NONZERO: f = v ? 1 : 0; break;
+    case ENC_PLUS1: f = 1 + v; break;
+    default: if (v) f = 2;
+    }
+}
+
+struct JobScope { bool single; int rank; };
+inline JobScope single_process() { return { true, 0 }; }
+inline JobScope rank_of_world(int rank) { return { false, rank }; }
+
+// fn(option key, value) for every option the job sets in this process, in table order; stops at the first non-zero result and returns it
+template <typename Fn> int for_each_option(const hjr_render_option& o, JobScope s, Fn fn)
+{
+    for (const KeyRow& r : key_table()) {
+        const bool mine = r.who == WHO_EVERY || (r.who == WHO_SINGLE && s.single) || (r.who == WHO_FILTER && s.rank == 0) ||
+                          (r.who == WHO_FILTER_DENOISE && s.rank == 0 && o.render_mode != HJR_MODE_DEFAULT);
+        const int v = mine ? key_get(o, r) : 0;
+        if (v) { const int rc = fn(r.key, v); if (rc) return rc; }
+    }
+    return 0;
+}
+
+// what both drivers derive from the option
+struct Job {
+    bool denoise, with_var, temporal, adaptive; // a Denoise mode; ... with the variance AOV; ... with temporal accumulation; "noise_threshold" asked for
+    int firefly;                                // kappa of "firefly_clamp"
+    uint32_t w, h, out_w, out_h;                // render size (half the output in DenoiseUpScale2X, renderer.h:1089-1099); the PNG's size
+};
+// fills `job`; false with the refusal in `text` (the caller puts its own name in front), all before a scene or a device is touched
+inline bool job_check(const hjr_render_option& o, Job& job, std::string& text)
+{
+    job.denoise = o.render_mode != HJR_MODE_DEFAULT;
+    job.with_var = job.denoise && key_get(o, key_row("denoise_variance"));
+    job.temporal = job.denoise && key_get(o, key_row("denoise_temporal"));
+    job.adaptive = o.noise_threshold > 0.0f;
+    job.firefly = key_get(o, key_row("firefly_clamp"));
+    const bool half = o.render_mode == HJR_MODE_DENOISE_UPSCALE2X;
+    job.out_w = o.image_width; job.out_h = o.image_height;
+    job.w = half ? job.out_w / 2u : job.out_w; job.h = half ? job.out_h / 2u : job.out_h;
+    if (o.render_mode != HJR_MODE_DEFAULT && o.render_mode != HJR_MODE_DENOISE && o.render_mode != HJR_MODE_DENOISE_UPSCALE2X)
+        text = "Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)";
+    else if (job.temporal && job.adaptive)
+        text = "\"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history";
+    else if (job.firefly && (o.passes > 1 || job.adaptive)) // every rank clamps its own pixels, so the rule is the same on both paths
+        text = "\"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only";
+    else if (job.w == 0 || job.h == 0)
+        text = "image too small for DenoiseUpScale2X";
+    else return true;
+    return false;
+}
+
+// sample-pass ends of a frame of spp samples in n passes ("Henjou_HIP": {"passes": n}): k * spp / n rounded down to the granule, the last one
+// spp; passes that come out empty are dropped, so a frame never has more passes than chunks
+inline std::vector<uint32_t> pass_ends(uint32_t spp, uint32_t n)
+{
+    const uint32_t g = hjr_sample_granule(spp);
+    std::vector<uint32_t> ends;
+    for (uint32_t k = 1; k < n && g; k++) {
+        const uint32_t e = (uint32_t)((uint64_t)k * spp / n) / g * g;
+        if (e > (ends.empty() ? 0u : ends.back())) ends.push_back(e);
+    }
+    ends.push_back(spp);
+    return ends;
+}
+
+// the launch parameters of a whole frame on one process (rank 0 of 1) at render size w x h; the rank path adds its rank and HJR_FLAG_PACKED
+inline int frame_params(const hjr_render_option& o, const hjr_scene* scene, uint32_t frame, uint32_t w, uint32_t h, hjr_params& p)
+{
+    HJR_INIT(p);
+    p.width = w; p.height = h;
+    p.spp = o.max_spp; p.frame = frame; p.seed = o.seed; p.integrator = (uint32_t)o.integrator;
+    for (int k = 0; k < 3; k++) p.sky[k] = o.scene_sky_default[k];
+    p.ibl_intensity = o.IBL_intensity;
+    p.rank = 0; p.world_size = 1;
+    if (o.fast_math) p.flags |= HJR_FLAG_FAST_MATH; // "Henjou_HIP": {"fast_math": true}
+    return hjr_scene_eval_camera(scene, &o, frame / float(o.fps), &p.camera); // renderer.h:1128
+}
+
+// <image_name>_<fff>.png (renderer.h:1291-1302: at least three digits)
+inline std::string frame_png_name(const hjr_render_option& o, uint32_t frame)
+{
+    std::string n = std::to_string(frame);
+    if (n.size() < 3) n.insert(0, 3 - n.size(), '0');
+    return std::string(o.image_name) + "_" + n + ".png";
+}
+
+// setLUT (renderer.h:854-898): a missing LUT file only matters if a material uses it, and then ends the job with the PNG loader's error;
+// setSky (renderer.h:802-851): a missing / undecodable HDR falls back to the 1x1 scene_sky_default texel (texture.h:89-98), noted on stderr
+inline int upload_assets(hjr_ctx* ctx, const hjr_render_option& o, const hjr_scene_view& view, bool note)
+{
+    uint8_t* lut = nullptr;
+    float* sky = nullptr;
+    int w = 0, h = 0, rc = HJR_OK;
+    if (hjr_load_png_rgba8(o.LUT_path, &lut, &w, &h) == HJR_OK) rc = hjr_set_lut(ctx, lut, w, h);
+    else for (uint32_t i = 0; i < view.n_materials; i++) if (view.materials[i].is_thinfilm) rc = HJR_ERR_IO; // hjr_last_error() holds the PNG error
+    hjr_free(lut);
+    if (rc != HJR_OK || !o.use_IBL) return rc;
+    if (hjr_load_hdr_rgba32f(o.IBL_path, &sky, &w, &h) == HJR_OK) rc = hjr_set_sky(ctx, sky, w, h);
+    else if (note) fprintf(stderr, "[henjou] %s NOT FOUND: using scene_sky_default\n", o.IBL_path);
+    hjr_free(sky);
+    return rc;
+}
+
+// "noise_threshold" / "min_samples": converged tiles stop between the sample passes (hjr_set_adaptive)
+inline int set_adaptive(hjr_ctx* ctx, const hjr_render_option& o)
+{
+    hjr_adaptive ad;
+    HJR_INIT(ad);
+    ad.noise_threshold = o.noise_threshold; ad.min_samples = o.min_samples;
+    return hjr_set_adaptive(ctx, &ad);
+}
+
+} // namespace hjr

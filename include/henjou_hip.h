@@ -136,24 +136,26 @@ typedef struct hjr_render_option {
     uint32_t tile;               /* shard granularity in pixels; 8 is the only supported value */
     int32_t serial_io;           /* default 0; 1: hjr_render_file renders, writes and prepares the next frame one after the other (no overlap) */
     int32_t fast_math;           /* default 0; 1: hjr_render_file / henjou_cli launch with HJR_FLAG_FAST_MATH */
-    int32_t force_rebuild;       /* default 0; bit 0: hjr_render_file rebuilds the frame data every frame even when nothing moved (benchmarking);
-                                  * bit 1: hjr_render_file / henjou_cli set the context option "verbose" (key "verbose": true; the struct does not grow for it) */
-    int32_t device_bvh;          /* default 0; 1: hjr_render_file / henjou_cli build the frame data on the device (option "device_bvh");
-                                  * 1 + N: that and option "device_bvh_refit" N (key "device_bvh_refit": N; the struct does not grow for it) */
-    int32_t device_bvh_opt;      /* default 0; low 8 bits: 0..3 treelet-restructuring rounds of that device build (option "device_bvh_opt");
-                                  * bit 8: key "device_bvh_instances", bit 9: key "device_bvh_graft" (options of the same names; the
-                                  * struct does not grow for them); bit 10: key "denoise_variance_spatial"; bit 11: key "upscale_guided"; bits 16..22: key "firefly_clamp"
-                                  * 0..64 (options of the same names; the field is the section's spare bits, the keys have nothing to do
-                                  * with the BVH) */
+    /* The next three fields and denoise_variance hold thirteen keys of the section between them.  This is the whole layout; the table
+     * in henjou-renderer_amd/host/render_job.hpp is its code, the one place that packs and unpacks it.  A key sets the context option of
+     * its name (hjr_set_option) in hjr_render_file and henjou_cli, on the processes listed at the end of the hjr_set_option comment. */
+    int32_t force_rebuild;       /* default 0; bit 0: key "force_rebuild" (the frame data is rebuilt every frame even when nothing moved;
+                                  * hjr_render_file only); bit 1: key "verbose" */
+    int32_t device_bvh;          /* default 0; 1: key "device_bvh" (the frame data built on the device); 1 + N: that and key
+                                  * "device_bvh_refit": N, 0..1000 */
+    int32_t device_bvh_opt;      /* default 0; bits 0..7: key "device_bvh_opt", 0..3 treelet-restructuring rounds of that device build;
+                                  * bit 8: key "device_bvh_instances"; bit 9: key "device_bvh_graft"; bit 10: key "denoise_variance_spatial";
+                                  * bit 11: key "upscale_guided"; bits 12..14: key "denoise_temporal_coverage", 0, 2, 3 or 4; bits 16..22: key
+                                  * "firefly_clamp", 0..64 (bits 10 and up are the section's spare bits: those keys have nothing to do with
+                                  * the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
     float noise_threshold;       /* default 0 (off); > 0: hjr_render_file / henjou_cli set hjr_adaptive.noise_threshold, render each frame in
                                   * `passes` sample passes (8 when the file has no "passes" key), stop when no tile is active and write the
                                   * PNG from the last pass ("noise_threshold") */
     uint32_t min_samples;        /* default 0 = two granules: hjr_adaptive.min_samples ("min_samples") */
-    int32_t denoise_variance;    /* default 0; 1: hjr_render_file / henjou_cli set the context option "denoise_variance" (the variance-guided
-                                  * filter in Render_mode Denoise / DenoiseUpScale2X; ignored in Default); 2: that and the option
-                                  * "denoise_temporal" (key "denoise_temporal": true; the struct does not grow for it) */
+    int32_t denoise_variance;    /* default 0; 1: key "denoise_variance" (the variance-guided filter in Render_mode Denoise /
+                                  * DenoiseUpScale2X; ignored in Default); 2: that and key "denoise_temporal" */
 } hjr_render_option;
 
 typedef struct hjr_camera {      /* Params.camera_* (renderer/renderer.h:1187-1191) */
@@ -643,23 +645,18 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
- * "device_bvh_refit": N (integer 0..1000, only together with "device_bvh": true) of that section is stored as hjr_render_option.device_bvh
- * = 1 + N (the struct does not grow for it): hjr_render_file and henjou_cli set "device_bvh" 1 and "device_bvh_refit" N.
- * "device_bvh_instances": true (only together with "device_bvh": true) is stored as bit 8 of hjr_render_option.device_bvh_opt, whose low
- * 8 bits stay the treelet rounds: hjr_render_file and henjou_cli mask the field and set both options.
- * "device_bvh_graft": true (only together with "device_bvh_instances": true) is bit 9 of the same field and sets the option of that name.
- * "denoise_variance" of that section (hjr_render_option.denoise_variance) sets the context option of the same name; "denoise_temporal": true
- * of that section is stored as hjr_render_option.denoise_variance = 2 and sets both options (refused together with "noise_threshold" > 0:
- * an adaptive frame that stops early never reaches the pass that advances the history).
- * "firefly_clamp": N (integer 0..64) of that section is stored in bits 16..22 of hjr_render_option.device_bvh_opt (the struct does not grow
- * for it; readers of the BVH bits mask the field as before) and sets the option of that name, single-GPU and --devices N; refused together
- * with "passes" > 1 or "noise_threshold" > 0: the rule needs every chunk sum of a pixel and a frame in sample passes keeps running sums only.
- * "denoise_variance_spatial": true of that section is stored as bit 10 of hjr_render_option.device_bvh_opt (the struct does not grow for it; the
- * key has nothing to do with the BVH) and sets the option of that name, single-GPU and on rank 0 of --devices N.
- * "upscale_guided": true (or false, 0, 1; anything else is a parse error) of that section is stored as bit 11 of the same field and sets the
- * option of that name, single-GPU and on rank 0 of --devices N (the PNG is the single-GPU run's); Default and Denoise accept and ignore it.
- * "denoise_temporal_coverage": N (0, 2, 3 or 4; anything else is a parse error) of that section is stored in bits 12..14 of the same field and
- * sets the option of that name, single-GPU and on rank 0 of --devices N; accepted and without effect without "denoise_temporal".
+ * Thirteen more keys of that section set the context option of their name; where each is stored is in the comment on hjr_render_option.
+ * "force_rebuild" is set by hjr_render_file only.  "verbose", "device_bvh", "device_bvh_refit": N (integer 0..1000), "device_bvh_opt",
+ * "device_bvh_instances", "device_bvh_graft" and "firefly_clamp": N (integer 0..64) are set single-GPU and on every rank of --devices N.
+ * "denoise_variance", "denoise_temporal" (both in the two Denoise modes only), "denoise_variance_spatial", "upscale_guided" and
+ * "denoise_temporal_coverage": N (0, 2, 3 or 4) are set single-GPU and on rank 0 of --devices N, which filters, accumulates and upscales (the
+ * PNG is the single-GPU run's).  "device_bvh_refit" and "device_bvh_instances" are a parse error without "device_bvh": true, and
+ * "device_bvh_graft" without "device_bvh_instances": true; "device_bvh_instances", "device_bvh_graft" and "upscale_guided" take true, false, 0
+ * or 1 only.  "denoise_variance_spatial" and "denoise_temporal_coverage" are accepted and without effect without "denoise_variance" /
+ * "denoise_temporal", "upscale_guided" outside DenoiseUpScale2X.  Both drivers refuse, before they load the scene or touch a device:
+ * "denoise_temporal" together with "noise_threshold" > 0 (an adaptive frame that stops early never reaches the pass that advances the
+ * history), and "firefly_clamp" together with "passes" > 1 or "noise_threshold" > 0 (the rule needs every chunk sum of a pixel and a frame in
+ * sample passes keeps running sums only).  An option call that fails ends the job.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);

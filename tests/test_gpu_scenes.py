@@ -257,6 +257,7 @@ def test_preview_buffer_on_the_device():
     try:
         w, h = 200, 120
         fb = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # torch fills on its own stream, the context works on another
         d.render_device(s.hjr_params(w, h, 16), fb.data_ptr())
         d.synchronize()
         host_in = fb.cpu().numpy()
@@ -265,6 +266,7 @@ def test_preview_buffer_on_the_device():
         for img, name in ((fb, "frame"), (fb2, "ramp")):
             for mode in (hjr.TONEMAP_NONE, hjr.TONEMAP_UCHIMURA, hjr.TONEMAP_ACES):
                 out = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()  # (as above: the zeros must have landed before the preview writes)
                 d.preview_device(img.data_ptr(), w, h, mode, out.data_ptr())
                 d.synchronize()
                 got = out.cpu().numpy()
