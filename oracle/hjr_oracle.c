@@ -19,6 +19,58 @@
 typedef struct { float x, y, z; } f3;
 typedef struct { float x, y; } f2;
 
+/* ------------------------------------------------------------------ named branch counters (test infrastructure)
+ * HJO_HIT(name) marks one branch of the shading layer.  It is nothing unless the file is compiled with -DHJO_BRANCH_COUNTERS
+ * (tests/oracle_binding.py builds that variant into a temporary directory); then it is one relaxed atomic increment of a
+ * process-wide table, so the counts are exact at any thread count and the arithmetic around it is untouched. */
+#define HJO_BRANCH_LIST(X) \
+    X(sincos_q0) X(sincos_q1) X(sincos_q2) X(sincos_q3) \
+    X(acos_hi) X(acos_lo) X(acos_mid) \
+    X(exp_rescale) X(exp_underflow) X(exp_normal) \
+    X(pow_y_zero) X(pow_x_one) X(pow_nan_arg) X(pow_neg_base) X(pow_zero_base_pos_y) X(pow_zero_base_neg_y) X(pow_inf_base) \
+    X(pow_denormal_base) X(pow_normal_base) X(pow_t_nan) X(pow_overflow) X(pow_zero_result) X(pow_exp) \
+    X(atan_big) X(atan_mid) X(atan_small) \
+    X(atan2_nan_arg) X(atan2_y_zero) X(atan2_x_zero) X(atan2_x_neg) X(atan2_x_pos) \
+    X(refract_tir) X(refract_ok) \
+    X(basis_z_pos) X(basis_z_neg) \
+    X(cosine_sampling) X(visible_normal) \
+    X(lut_unbound) X(lut_bound) \
+    X(disney_eval_thinfilm) X(disney_eval_plain) \
+    X(disney_wo_below) X(disney_wo_above) X(disney_lobe_diffuse) X(disney_lobe_specular) X(disney_lobe_clearcoat) X(disney_wi_below) X(disney_wi_above) \
+    X(glass_from_inside) X(glass_from_outside) X(glass_reflect) X(glass_refract) X(glass_tir) \
+    X(lambda_up_exit) X(lambda_down_exit) X(lambda_general_up) X(lambda_general_down) \
+    X(g1_up_exit) X(g1_below) X(g1_general) \
+    X(height_up_exit) X(height_down_start) X(height_graze) X(height_escape) X(height_hit) \
+    X(walk_wo_below) X(walk_wo_above) X(walk_escape) X(walk_order_gt5) X(walk_nan_exit) X(walk_bounce) \
+    X(msggx_order_gt5) X(msggx_wi_below) X(msggx_ok) \
+    X(bsdf_is_ggx) X(bsdf_not_ggx) \
+    X(light_none) X(light_index_clamp) X(light_pick) \
+    X(nee_contrib_zero) X(nee_contrib_partial) X(nee_contrib_full) \
+    X(mis_contrib_zero) X(mis_contrib_partial) X(mis_contrib_full) \
+    X(mis_hit_light) X(mis_hit_other) X(mis_miss) X(mis_lightpdf_specular) X(mis_lightpdf_area) \
+    X(sample_nan_guard) X(sample_finite)
+#ifdef HJO_BRANCH_COUNTERS
+#define HJO_BRANCH_ENUM(n) HJO_B_##n,
+enum { HJO_BRANCH_LIST(HJO_BRANCH_ENUM) HJO_B_COUNT };
+static uint64_t g_branch[HJO_B_COUNT];
+#define HJO_HIT(n) ((void)__atomic_fetch_add(&g_branch[HJO_B_##n], 1, __ATOMIC_RELAXED))
+#define HJO_BRANCH_NAME(n) #n "\n"
+const char* hjo_branch_names(void) { return HJO_BRANCH_LIST(HJO_BRANCH_NAME); }
+int hjo_branch_counts(uint64_t* out)
+{
+    if (out) for (int i = 0; i < HJO_B_COUNT; i++) out[i] = __atomic_load_n(&g_branch[i], __ATOMIC_RELAXED);
+    return HJO_B_COUNT;
+}
+void hjo_branch_reset(void) { for (int i = 0; i < HJO_B_COUNT; i++) __atomic_store_n(&g_branch[i], 0, __ATOMIC_RELAXED); }
+#else
+#define HJO_HIT(n) ((void)0)
+#endif
+/* which of "all components zero / some / none" a light contribution is: the shadow-ray decision of NEE and MIS sees only the first */
+#define HJO_HIT_CONTRIB(pre, c) do { \
+    int nz_ = ((c).x == 0.0f) + ((c).y == 0.0f) + ((c).z == 0.0f); \
+    if (nz_ == 3) HJO_HIT(pre##_contrib_zero); else if (nz_ > 0) HJO_HIT(pre##_contrib_partial); else HJO_HIT(pre##_contrib_full); \
+    (void)nz_; } while (0)
+
 /* ------------------------------------------------------------------ sutil/vec_math.h restated */
 static inline f3 V(float x, float y, float z) { f3 r = { x, y, z }; return r; }
 static inline f3 V1(float s) { return V(s, s, s); }
@@ -61,10 +113,10 @@ static inline void p_sincos(float x, float* s, float* c)
     float cp = fmaf(fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f),
                     z * z, fmaf(-0.5f, z, 1.0f));
     switch (j & 3) {
-    case 0: *s = sp; *c = cp; break;
-    case 1: *s = cp; *c = -sp; break;
-    case 2: *s = -sp; *c = -cp; break;
-    default: *s = -cp; *c = sp; break;
+    case 0: HJO_HIT(sincos_q0); *s = sp; *c = cp; break;
+    case 1: HJO_HIT(sincos_q1); *s = cp; *c = -sp; break;
+    case 2: HJO_HIT(sincos_q2); *s = -sp; *c = -cp; break;
+    default: HJO_HIT(sincos_q3); *s = -cp; *c = sp; break;
     }
 }
 float hjo_p_sin(float x) { float s, c; p_sincos(x, &s, &c); return s; }
@@ -79,15 +131,18 @@ static inline float p_asin_poly(float x, float z)
 float hjo_p_acos(float x)
 {
     if (x > 0.5f) {
+        HJO_HIT(acos_hi);
         float z = 0.5f * (1.0f - x);
         float s = sqrtf(z);
         return 2.0f * p_asin_poly(s, z);
     }
     if (x < -0.5f) {
+        HJO_HIT(acos_lo);
         float z = 0.5f * (1.0f + x);
         float s = sqrtf(z);
         return HJ_PI - 2.0f * p_asin_poly(s, z);
     }
+    HJO_HIT(acos_mid);
     return 1.57079632679489661923f - p_asin_poly(x, x * x);
 }
 
@@ -126,23 +181,30 @@ static inline float p_exp(float x) /* -87 <= x <= 88.7 */
     p = fmaf(p, r, 1.6666665459e-1f);
     p = fmaf(p, r, 5.0000001201e-1f);
     p = fmaf(p, z, r) + 1.0f;
-    if (n > 127) { p = p * 1.70141183460469231732e38f; n -= 127; }
-    if (n < -126) return 0.0f;
+    if (n > 127) { HJO_HIT(exp_rescale); p = p * 1.70141183460469231732e38f; n -= 127; }
+    if (n < -126) { HJO_HIT(exp_underflow); return 0.0f; }
+    HJO_HIT(exp_normal);
     return p * bits2f((uint32_t)(n + 127) << 23);
 }
 float hjo_p_pow(float x, float y)
 {
-    if (y == 0.0f) return 1.0f;
-    if (x == 1.0f) return 1.0f;
-    if (x != x || y != y) return x + y;
-    if (x < 0.0f) return bits2f(0x7fc00000u);
-    if (x == 0.0f) return (y > 0.0f) ? 0.0f : bits2f(0x7f800000u);
-    if (x > FLT_MAX) return (y > 0.0f) ? x : 0.0f;
-    float lx = (x < FLT_MIN) ? p_log(x * 16777216.0f) - 16.6355323334f : p_log(x); /* denormal base: rescale by 2^24 */
+    if (y == 0.0f) { HJO_HIT(pow_y_zero); return 1.0f; }
+    if (x == 1.0f) { HJO_HIT(pow_x_one); return 1.0f; }
+    if (x != x || y != y) { HJO_HIT(pow_nan_arg); return x + y; }
+    if (x < 0.0f) { HJO_HIT(pow_neg_base); return bits2f(0x7fc00000u); }
+    if (x == 0.0f) {
+        if (y > 0.0f) { HJO_HIT(pow_zero_base_pos_y); return 0.0f; }
+        HJO_HIT(pow_zero_base_neg_y); return bits2f(0x7f800000u);
+    }
+    if (x > FLT_MAX) { HJO_HIT(pow_inf_base); return (y > 0.0f) ? x : 0.0f; }
+    float lx;
+    if (x < FLT_MIN) { HJO_HIT(pow_denormal_base); lx = p_log(x * 16777216.0f) - 16.6355323334f; } /* denormal base: rescale by 2^24 */
+    else { HJO_HIT(pow_normal_base); lx = p_log(x); }
     float t = y * lx;
-    if (t != t) return t;
-    if (t > 88.7f) return bits2f(0x7f800000u);
-    if (t < -87.0f) return 0.0f;
+    if (t != t) { HJO_HIT(pow_t_nan); return t; }
+    if (t > 88.7f) { HJO_HIT(pow_overflow); return bits2f(0x7f800000u); }
+    if (t < -87.0f) { HJO_HIT(pow_zero_result); return 0.0f; }
+    HJO_HIT(pow_exp);
     return p_exp(t);
 }
 float hjo_p_pow5(float x) { float x2 = x * x; float x4 = x2 * x2; return x4 * x; }
@@ -150,20 +212,20 @@ float hjo_p_pow5(float x) { float x2 = x * x; float x4 = x2 * x2; return x4 * x;
 static inline float p_atan_pos(float x)
 {
     float y0;
-    if (x > 2.414213562373095f) { y0 = 1.57079632679489661923f; x = -(1.0f / x); }
-    else if (x > 0.4142135623730950f) { y0 = 0.78539816339744830962f; x = (x - 1.0f) / (x + 1.0f); }
-    else y0 = 0.0f;
+    if (x > 2.414213562373095f) { HJO_HIT(atan_big); y0 = 1.57079632679489661923f; x = -(1.0f / x); }
+    else if (x > 0.4142135623730950f) { HJO_HIT(atan_mid); y0 = 0.78539816339744830962f; x = (x - 1.0f) / (x + 1.0f); }
+    else { HJO_HIT(atan_small); y0 = 0.0f; }
     float z = x * x;
     float p = fmaf(fmaf(fmaf(8.05374449538e-2f, z, -1.38776856032e-1f), z, 1.99777106478e-1f), z, -3.33329491539e-1f);
     return y0 + fmaf(p * z, x, x);
 }
 float hjo_p_atan2(float y, float x)
 {
-    if (x != x || y != y) return x + y;
-    if (y == 0.0f) return (x >= 0.0f && !(f2bits(x) >> 31)) ? y : copysignf(HJ_PI, y);
-    if (x == 0.0f) return copysignf(1.57079632679489661923f, y);
+    if (x != x || y != y) { HJO_HIT(atan2_nan_arg); return x + y; }
+    if (y == 0.0f) { HJO_HIT(atan2_y_zero); return (x >= 0.0f && !(f2bits(x) >> 31)) ? y : copysignf(HJ_PI, y); }
+    if (x == 0.0f) { HJO_HIT(atan2_x_zero); return copysignf(1.57079632679489661923f, y); }
     float a = p_atan_pos(fabsf(y / x));
-    if (x < 0.0f) a = HJ_PI - a;
+    if (x < 0.0f) { HJO_HIT(atan2_x_neg); a = HJ_PI - a; } else HJO_HIT(atan2_x_pos);
     return copysignf(a, y);
 }
 
@@ -275,6 +337,7 @@ static inline cmj_state state_from5(const uint32_t* s5)
 /* ------------------------------------------------------------------ kernel/math.h */
 static inline f3 cosine_sampling(int mm, float u, float v, float* pdf) /* math.h:7-15 */
 {
+    HJO_HIT(cosine_sampling);
     float phi = 2.0f * HJ_PI * v;
     float theta = m_half_acos(mm, 1.0f - 2.0f * u);
     float cosTheta = m_cos(mm, theta);
@@ -305,6 +368,7 @@ float hjo_schlick_ior(int mm, float no, float ni, const float* w, const float* n
 static inline void orthonormal_basis(f3 n, f3* t, f3* b) /* math.h:43-51 */
 {
     float sign = copysignf(1.0f, n.z);
+    if (sign > 0.0f) HJO_HIT(basis_z_pos); else HJO_HIT(basis_z_neg);
     const float a = -1.0f / (sign + n.z);
     const float bb = n.x * n.y * a;
     *t = V(1.0f + sign * n.x * n.x * a, sign * bb, -sign * n.x);
@@ -337,7 +401,8 @@ static inline float norm2(f3 v) { return v.x * v.x + v.y * v.y + v.z * v.z; } /*
 static inline int refract3(f3 v, f3 n, float ior1, float ior2, f3* r) /* math.h:92-103 */
 {
     const f3 t_h = muls(sub(v, muls(n, dot(v, n))), -ior1 / ior2);
-    if (norm2(t_h) > 1.0f) return 0;
+    if (norm2(t_h) > 1.0f) { HJO_HIT(refract_tir); return 0; }
+    HJO_HIT(refract_ok);
     const f3 t_p = muls(n, -sqrtf(fmaxf(1.0f - norm2(t_h), 0.0f)));
     *r = add(t_h, t_p);
     return 1;
@@ -374,7 +439,8 @@ static inline void payload_init(payload* p)
  * weights in 1.8 fixed point); the exact hardware rounding is unobservable here => build-defined. */
 void hjo_lut_fetch(const uint8_t* rgba, int w, int h, float u, float v, float* out)
 {
-    if (!rgba || w <= 0 || h <= 0) { out[0] = out[1] = out[2] = 0.0f; return; }
+    if (!rgba || w <= 0 || h <= 0) { HJO_HIT(lut_unbound); out[0] = out[1] = out[2] = 0.0f; return; }
+    HJO_HIT(lut_bound);
     float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
     float fx = floorf(x), fy = floorf(y);
     float ax = floorf((x - fx) * 256.0f + 0.5f) * (1.0f / 256.0f);
@@ -495,6 +561,7 @@ static inline f3 d_sampleDiffuse(const disney* d, f2 uv, float* pdf) /* :30-38 *
 /* spherical-cap VNDF sampling, shared by Disney (:64-80) and msGGX (BSDFs.h:616-632) */
 static inline f3 sample_visible_normal(int mm, float alpha, f2 uv, f3 wo)
 {
+    HJO_HIT(visible_normal);
     f3 strech_wo = normalize(V(wo.x * alpha, wo.y, wo.z * alpha));
     float phi = 2.0f * HJ_PI * uv.x;
     float z = m_fma(mm, (1.0f - uv.y), (1.0f + strech_wo.y), -strech_wo.y);
@@ -569,7 +636,9 @@ static inline f3 disney_eval(const disney* d, f3 wo, f3 wi) /* :179-235 */
     float deltacos = 1.0f / (dot_wi_n + dot_wo_n) - 0.5f;
     f3 f_subsurface = muls(muls(muls(d->basecolor, HJ_INV_PI), 1.25f), (f_tsi * f_tso * deltacos + 0.5f));
     f3 F0 = lerp3(V1(0.08f), d->basecolor, d->metallic);
+    if (!d->is_thinfilm) HJO_HIT(disney_eval_plain);
     if (d->is_thinfilm) {
+        HJO_HIT(disney_eval_thinfilm);
         float thickness = d->basecolor.x;
         float cosine = absdot(wi, wm);
         float l[3]; hjo_lut_fetch(d->lut, d->lut_w, d->lut_h, thickness, cosine, l);
@@ -591,28 +660,33 @@ static inline f3 disney_sample(const disney* d, f3 wo, f3* wi, float* pdf, cmj_s
     float dw = diffuseWeight / sumWeight;
     float sw = specularWeight / sumWeight;
     float cw = clearcoatWeight / sumWeight;
+    if (wo.y < 0.0f) HJO_HIT(disney_wo_below); else HJO_HIT(disney_wo_above);
     float select_p = cmj_1d(st);
     float pdf_diffuse = 1.0f, pdf_specular = 1.0f, pdf_clearcoat = 1.0f;
     f2 xi = cmj_2d(st);
     if (select_p < dw) {
+        HJO_HIT(disney_lobe_diffuse);
         *wi = d_sampleDiffuse(d, xi, &pdf_diffuse);
         f3 wm = normalize(add(*wi, wo));
         pdf_specular = d_getPDFSpecular(d, wm, wo);
         pdf_clearcoat = d_getPDFClearcoat(d, wm, wo);
     } else if (select_p < dw + sw) {
+        HJO_HIT(disney_lobe_specular);
         f3 wm = sample_visible_normal(d->mm, d->alpha, xi, wo);
         pdf_specular = d_getPDFSpecular(d, wm, wo);
         *wi = reflect3(neg(wo), wm);
         pdf_diffuse = d_getPDFDiffuse(*wi);
         pdf_clearcoat = d_getPDFClearcoat(d, wm, wo);
     } else {
+        HJO_HIT(disney_lobe_clearcoat);
         f3 wm = d_sampleClearcoat(d, xi, wo, &pdf_clearcoat);
         *wi = reflect3(neg(wo), wm);
         pdf_diffuse = d_getPDFDiffuse(*wi);
         pdf_specular = d_getPDFSpecular(d, wm, wo);
     }
     *pdf = dw * pdf_diffuse + sw * pdf_specular + cw * pdf_clearcoat;
-    if (wi->y < 0.0f) { *pdf = 1.0f; return V1(0.0f); }
+    if (wi->y < 0.0f) { HJO_HIT(disney_wi_below); *pdf = 1.0f; return V1(0.0f); }
+    HJO_HIT(disney_wi_above);
     return disney_eval(d, wo, *wi);
 }
 static inline float disney_pdf(const disney* d, f3 wo, f3 wi) /* :309-326 */
@@ -631,19 +705,23 @@ static inline f3 metaglass_sample(int mm, f3 rho, float ior, f3 wo, f3* wi, floa
     float ior_o = 1.0f, ior_i = ior, sign = 1.0f;
     f3 lwo = wo, lwi = V1(0.0f);
     f3 n = V(0, 1, 0);
-    if (wo.y < 0.0f) { ior_o = ior; ior_i = 1.0f; lwo.y = -lwo.y; sign = -1.0f; }
+    if (wo.y < 0.0f) { HJO_HIT(glass_from_inside); ior_o = ior; ior_i = 1.0f; lwo.y = -lwo.y; sign = -1.0f; }
+    else HJO_HIT(glass_from_outside);
     const float fr = schlick_ior(mm, ior_o, ior_i, lwo, n);
     f3 evalbsdf;
     float p = cmj_1d(st);
     if (p < fr) {
+        HJO_HIT(glass_reflect);
         lwi = reflect3(neg(lwo), n);
         *pdf = 1; evalbsdf = divs(rho, fabsf(lwi.y));
     } else {
         f3 t;
         if (refract3(lwo, n, ior_o, ior_i, &t)) {
+            HJO_HIT(glass_refract);
             lwi = reflect3(neg(t), V(0, -1, 0)); /* negative refractive index: tangential flip (:454) */
             *pdf = 1; evalbsdf = divs(rho, fabsf(lwi.y));
         } else {
+            HJO_HIT(glass_tir);
             lwi = reflect3(neg(lwo), n);
             *pdf = 1; evalbsdf = divs(rho, fabsf(lwi.y));
         }
@@ -659,8 +737,9 @@ static inline float ms_C1(float h) { return fminf(1.0f, fmaxf(0.0f, 0.5f * (h + 
 static inline float ms_invC1(float U) { return fmaxf(-1.0f, fminf(1.0f, 2.0f * U - 1.0f)); } /* :502-505 */
 static inline float ms_Lambda(const msggx* g, f3 v) /* :525-532 */
 {
-    if (v.y > 0.9999f) return 0.0f;
-    if (v.y < -0.9999f) return -1.0f;
+    if (v.y > 0.9999f) { HJO_HIT(lambda_up_exit); return 0.0f; }
+    if (v.y < -0.9999f) { HJO_HIT(lambda_down_exit); return -1.0f; }
+    if (v.y > 0.0f) HJO_HIT(lambda_general_up); else HJO_HIT(lambda_general_down);
     float a = g->alpha;
     float delta = 1.0f + (a * a * v.x * v.x + a * a * v.z * v.z) / (v.y * v.y);
     float sg = (v.y > 0.0f) ? 1.0f : -1.0f;
@@ -668,19 +747,21 @@ static inline float ms_Lambda(const msggx* g, f3 v) /* :525-532 */
 }
 static inline float ms_G1_Height(const msggx* g, f3 wi, float h0) /* :551-563 */
 {
-    if (wi.y > 0.9999f) return 1.0f;
-    if (wi.y <= 0.0f) return 0.0f;
+    if (wi.y > 0.9999f) { HJO_HIT(g1_up_exit); return 1.0f; }
+    if (wi.y <= 0.0f) { HJO_HIT(g1_below); return 0.0f; }
+    HJO_HIT(g1_general);
     const float C1_h0 = ms_C1(h0);
     const float Lambda = ms_Lambda(g, wi);
     return m_powf(g->mm, C1_h0, Lambda);
 }
 static inline float ms_sampleHeight(const msggx* g, f3 wr, float hr, float U) /* :566-586 */
 {
-    if (wr.y > 0.9999f) return FLT_MAX;
-    if (wr.y < -0.9999f) return ms_invC1(U * ms_C1(hr));
-    if (fabsf(wr.y) < 0.0001f) return hr;
+    if (wr.y > 0.9999f) { HJO_HIT(height_up_exit); return FLT_MAX; }
+    if (wr.y < -0.9999f) { HJO_HIT(height_down_start); return ms_invC1(U * ms_C1(hr)); }
+    if (fabsf(wr.y) < 0.0001f) { HJO_HIT(height_graze); return hr; }
     const float G_1_ = ms_G1_Height(g, wr, hr);
-    if (U > 1.0f - G_1_) return FLT_MAX;
+    if (U > 1.0f - G_1_) { HJO_HIT(height_escape); return FLT_MAX; }
+    HJO_HIT(height_hit);
     return ms_invC1(ms_C1(hr) / m_powf(g->mm, (1.0f - U), 1.0f / ms_Lambda(g, wr)));
 }
 static inline f3 ms_samplePhase(const msggx* g, f3 wi, cmj_state* st, f3* weight) /* :737-746 */
@@ -693,6 +774,7 @@ static inline f3 ms_samplePhase(const msggx* g, f3 wi, cmj_state* st, f3* weight
 }
 static inline f3 ms_sample(const msggx* g, f3 wi, f3* wo, int* order, cmj_state* st) /* :784-819 */
 {
+    if (wi.y < 0.0f) HJO_HIT(walk_wo_below); else HJO_HIT(walk_wo_above); /* wi: the view direction here */
     f3 wr = neg(wi);
     float hr = 1.0f + ms_invC1(0.999f);
     *order = 0;
@@ -700,13 +782,14 @@ static inline f3 ms_sample(const msggx* g, f3 wi, f3* wo, int* order, cmj_state*
     for (;;) {
         float U = cmj_1d(st);
         hr = ms_sampleHeight(g, wr, hr, U);
-        if (hr == FLT_MAX) break;
+        if (hr == FLT_MAX) { HJO_HIT(walk_escape); break; }
         else (*order)++;
-        if (*order > 5) { *wo = V(0, 0, 1); return V(0, 0, 0); }
+        if (*order > 5) { HJO_HIT(walk_order_gt5); *wo = V(0, 0, 1); return V(0, 0, 0); }
         f3 weight_1;
         wr = ms_samplePhase(g, neg(wr), st, &weight_1);
         weight = mul(weight, weight_1);
-        if ((hr != hr) || (wr.z != wr.z)) return V(0, 0, 1);
+        if ((hr != hr) || (wr.z != wr.z)) { HJO_HIT(walk_nan_exit); return V(0, 0, 1); }
+        HJO_HIT(walk_bounce);
     }
     *wo = wr;
     return weight;
@@ -715,7 +798,11 @@ static inline f3 msggx_sampleBSDF(const msggx* g, f3 wo, f3* wi, cmj_state* st, 
 {
     int order;
     f3 bsdf = ms_sample(g, wo, wi, &order, st);
-    if (wi->y < 0.0f || order > 5) return V1(0.0f); /* pdf left as the caller initialised it */
+    if (wi->y < 0.0f || order > 5) { /* pdf left as the caller initialised it */
+        if (order > 5) HJO_HIT(msggx_order_gt5); else HJO_HIT(msggx_wi_below);
+        return V1(0.0f);
+    }
+    HJO_HIT(msggx_ok);
     *pdf = fabsf(wi->y);
     return bsdf;
 }
@@ -731,6 +818,7 @@ static inline void bsdf_init(bsdf_t* b, const payload* p, int mm, const uint8_t*
     b->eggx.alpha = clampf(p->roughness * p->roughness, 0.0001f, 1.0f);
     b->eggx.mm = mm;
     b->is_ggx = p->metallic > 0.5f;
+    if (b->is_ggx) HJO_HIT(bsdf_is_ggx); else HJO_HIT(bsdf_not_ggx);
     b->mm = mm;
 }
 static inline f3 bsdf_eval(const bsdf_t* b, f3 wo, f3 wi)
@@ -1121,11 +1209,11 @@ static int TraceOcclusion(tctx* T, f3 o, f3 d, float tmin, float tmax)
 static f3 light_sample(tctx* T, cmj_state* st, float* pdf, f3* normal, f3* emission, int* valid)
 {
     const hjo_scene* s = &T->c->sc;
-    if (s->n_lights < 1) { *pdf = -1.0f; *normal = V1(0.0f); *emission = V1(0.0f); *valid = 0; return V1(0.0f); }
+    if (s->n_lights < 1) { HJO_HIT(light_none); *pdf = -1.0f; *normal = V1(0.0f); *emission = V1(0.0f); *valid = 0; return V1(0.0f); }
     *valid = 1;
     float p = cmj_1d(st);
     int index = (int)(p * s->n_lights);
-    if (index == (int)s->n_lights) index--;
+    if (index == (int)s->n_lights) { HJO_HIT(light_index_clamp); index--; } else HJO_HIT(light_pick);
     uint32_t prim_index = s->light_prim_ids[index];
     uint32_t left = 0U, right = s->n_instances - 1, middle = (left + right) / 2U;
     while (left <= right) {
@@ -1220,6 +1308,7 @@ static f3 NEE(tctx* T, f3 o, f3 d, cmj_state state, f3* aov_albedo, f3* aov_norm
                 float G = cosine2 / (light_distance * light_distance);
                 f3 contrib = mul(mul(throughput, divs(muls(muls(bsdf, G), cosine1), light_pdf)), light_color);
                 TR("   nee: wi_local %g %g %g bsdf_eval %g %g %g G %g cos1 %g light_pdf %g contrib %g %g %g\n", local_wi.x, local_wi.y, local_wi.z, bsdf.x, bsdf.y, bsdf.z, G, cosine1, light_pdf, contrib.x, contrib.y, contrib.z);
+                HJO_HIT_CONTRIB(nee, contrib);
                 if (!(contrib.x == 0.0f && contrib.y == 0.0f && contrib.z == 0.0f) &&
                     !TraceOcclusion(T, so, sd, 0.001f, light_distance - ipsiron_distance))
                     LTE = add(LTE, contrib);
@@ -1299,6 +1388,7 @@ static f3 MIS(tctx* T, f3 o, f3 d, cmj_state* statep, f3* aov_albedo, f3* aov_no
                 float pt_pdf = bsdf_pdf(&bs, local_wo, local_wi) * G;
                 float mis_weight = light_pdf / (light_pdf + pt_pdf);
                 f3 contrib = mul(muls(mul(throughput, divs(muls(muls(bsdf, G), cosine1), light_pdf)), mis_weight), light_emission);
+                HJO_HIT_CONTRIB(mis, contrib);
                 if (!(contrib.x == 0.0f && contrib.y == 0.0f && contrib.z == 0.0f) &&
                     !TraceOcclusion(T, prd.position, light_direction, 0.001f, light_distance - 0.001f))
                     LTE = add(LTE, contrib);
@@ -1312,7 +1402,10 @@ static f3 MIS(tctx* T, f3 o, f3 d, cmj_state* statep, f3* aov_albedo, f3* aov_no
             payload lh;
             RayTrace(T, prd.position, wi, 0.001f, 1e16f, &lh);
             if (lh.is_hit) {
+                if (!lh.is_light) HJO_HIT(mis_hit_other);
                 if (lh.is_light) {
+                    HJO_HIT(mis_hit_light);
+                    if (prd.is_specular) HJO_HIT(mis_lightpdf_specular); else HJO_HIT(mis_lightpdf_area);
                     float cosine2 = absdot(neg(wi), lh.normal);
                     float light_distance = length3(sub(lh.position, prd.position));
                     float invG = light_distance * light_distance / cosine2;
@@ -1321,6 +1414,7 @@ static f3 MIS(tctx* T, f3 o, f3 d, cmj_state* statep, f3* aov_albedo, f3* aov_no
                     LTE = add(LTE, divs(mul(mul(muls(muls(throughput, mis_weight), cosine1), lh.emission), brdf), pt_pdf));
                 }
             } else {
+                HJO_HIT(mis_miss);
                 LTE = add(LTE, divs(mul(muls(mul(throughput, brdf), cosine1), lh.emission), pt_pdf));
             }
         }
@@ -1358,7 +1452,8 @@ static void sample_one(tctx* T, uint32_t x, uint32_t y, uint32_t s, f3* L, f3* A
     else *L = NEE(T, cp, d, st, A, N);
     T->st.samples++;
     float sum = L->x + L->y + L->z;
-    if (!(sum - sum == 0.0f)) { *L = V1(0.0f); T->st.nan_samples++; } /* NaN/Inf guard (build-defined) */
+    if (!(sum - sum == 0.0f)) { HJO_HIT(sample_nan_guard); *L = V1(0.0f); T->st.nan_samples++; } /* NaN/Inf guard (build-defined) */
+    else HJO_HIT(sample_finite);
 }
 
 int hjo_sample(hjo_ctx* c, const hjo_params* P, uint32_t x, uint32_t y, uint32_t s, float* rad, float* alb, float* nor)

@@ -145,6 +145,14 @@ int hjo_denoise(int mode, uint32_t in_w, uint32_t in_h, const float* color, cons
                 uint32_t out_w, uint32_t out_h);
 float hjo_tonemap(float x, int mode);
 
+#ifdef HJO_BRANCH_COUNTERS
+/* Named branch counters of the shading layer (tests/test_shading_branches_host.py).  Only a build with -DHJO_BRANCH_COUNTERS has
+ * them; the default build compiles every HJO_HIT() to nothing.  Counts are relaxed atomics: exact at any thread count. */
+const char* hjo_branch_names(void);            /* the names, each followed by '\n', in counter order */
+int         hjo_branch_counts(uint64_t* out);  /* copies the counters (out may be NULL); returns how many there are */
+void        hjo_branch_reset(void);
+#endif
+
 #ifdef __cplusplus
 }
 #endif

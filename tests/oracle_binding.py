@@ -80,12 +80,13 @@ def build():
     subprocess.check_call(["make", "-s", "-C", ORACLE_DIR])
 
 
-def lib():
+def lib(path=None):
+    """the oracle library, loaded once; path: another build of it, loaded on every call and not kept"""
     global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
+    if _lib is None or path:
+        if not path and not os.path.exists(LIB_PATH):
             build()
-        L = C.CDLL(LIB_PATH)
+        L = C.CDLL(path or LIB_PATH)
         L.hjo_xxhash32_u4.restype = C.c_uint32
         L.hjo_xxhash32_u4.argtypes = [C.c_uint32] * 4
         L.hjo_cmj_permute.restype = C.c_uint32
@@ -134,8 +135,65 @@ def lib():
         L.hjo_trace_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p]
         L.hjo_trace_any.restype = C.c_int
         L.hjo_trace_any.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int]
+        if path:
+            return L
         _lib = L
     return _lib
+
+
+_counting = None
+
+
+class counting_oracle:
+    """with counting_oracle() as names: ...  — inside the block OracleScene and every other call of this module go to a build of the
+    oracle with -DHJO_BRANCH_COUNTERS (named branch counters of the shading layer, oracle/hjr_oracle.h).  The variant is compiled
+    once per process into a temporary directory, with the flags of oracle/Makefile; the default library is not touched.  Read the
+    counters with branch_counts() / branch_reset() inside the block."""
+
+    def __enter__(self):
+        global _lib, _counting
+        self.default = _lib
+        if _counting is None:
+            import atexit
+            import shutil
+            import tempfile
+            tmp = tempfile.mkdtemp(prefix="hjo_counting_")
+            atexit.register(shutil.rmtree, tmp, True)
+            out = os.path.join(tmp, "libhjr_oracle_counting.so")
+            import re
+            with open(os.path.join(ORACLE_DIR, "Makefile")) as f:  # the flags of the default build, from its Makefile
+                flags = re.search(r"^CFLAGS \?= (.*)$", f.read(), re.M).group(1)
+            subprocess.check_call([os.environ.get("CC", "gcc")] + flags.split() +
+                                  ["-DHJO_BRANCH_COUNTERS", "-shared", "-o", out, os.path.join(ORACLE_DIR, "hjr_oracle.c"),
+                                   "-lm", "-lpthread"])
+            L = lib(out)
+            L.hjo_branch_names.restype = C.c_char_p
+            L.hjo_branch_counts.restype = C.c_int
+            L.hjo_branch_counts.argtypes = [C.c_void_p]
+            _counting = L
+        _lib = _counting
+        return branch_names()
+
+    def __exit__(self, *a):
+        global _lib
+        _lib = self.default
+        return False
+
+
+def branch_names():
+    return _counting.hjo_branch_names().decode().split()
+
+
+def branch_counts():
+    """{name: count} of the counting oracle since the last branch_reset()"""
+    n = _counting.hjo_branch_counts(None)
+    out = (C.c_uint64 * n)()
+    _counting.hjo_branch_counts(out)
+    return dict(zip(branch_names(), [int(v) for v in out]))
+
+
+def branch_reset():
+    _counting.hjo_branch_reset()
 
 
 def _ptr(a):
@@ -189,11 +247,12 @@ class OracleScene:
             s.sky_h, s.sky_w = a["sky_rgba"].shape[:2]
         self.scene = s
         self.math_mode = math_mode
-        self.ctx = lib().hjo_create(C.byref(s), math_mode)
+        self.lib = lib()  # the library that owns the context (the default one, or the counting variant)
+        self.ctx = self.lib.hjo_create(C.byref(s), math_mode)
 
     def close(self):
         if self.ctx:
-            lib().hjo_destroy(self.ctx)
+            self.lib.hjo_destroy(self.ctx)
             self.ctx = None
 
     def __del__(self):
@@ -210,7 +269,7 @@ class OracleScene:
         albedo = np.zeros(n, dtype=np.float32) if want_aovs else None
         normal = np.zeros(n, dtype=np.float32) if want_aovs else None
         st = Stats()
-        rc = lib().hjo_render(self.ctx, C.byref(params), _ptr(color), _ptr(albedo), _ptr(normal), nthreads, C.byref(st))
+        rc = self.lib.hjo_render(self.ctx, C.byref(params), _ptr(color), _ptr(albedo), _ptr(normal), nthreads, C.byref(st))
         assert rc == 0
         shp = (params.height, params.width, 4)
         return (color.reshape(shp), None if albedo is None else albedo.reshape(shp),
@@ -218,21 +277,21 @@ class OracleScene:
 
     def sample(self, params, x, y, s):
         r, a, n = F3(), F3(), F3()
-        lib().hjo_sample(self.ctx, C.byref(params), x, y, s, r, a, n)
+        self.lib.hjo_sample(self.ctx, C.byref(params), x, y, s, r, a, n)
         return np.array(r, dtype=np.float32), np.array(a, dtype=np.float32), np.array(n, dtype=np.float32)
 
     def sample_is_nan(self, params, x, y, s):
         """True when sample s of pixel (x, y) is NaN / Inf on the oracle (zeroed and counted by the guard, like the product's)."""
         r, a, n = F3(), F3(), F3()
-        return lib().hjo_sample(self.ctx, C.byref(params), x, y, s, r, a, n) != 0
+        return self.lib.hjo_sample(self.ctx, C.byref(params), x, y, s, r, a, n) != 0
 
     def trace_closest(self, o, d, tmin=0.001, tmax=1e16, use_bvh=1):
         out = F3()
-        p = lib().hjo_trace_closest(self.ctx, F3(*o), F3(*d), tmin, tmax, use_bvh, out)
+        p = self.lib.hjo_trace_closest(self.ctx, F3(*o), F3(*d), tmin, tmax, use_bvh, out)
         return p, np.array(out, dtype=np.float32)
 
     def trace_any(self, o, d, tmin, tmax, use_bvh=1):
-        return lib().hjo_trace_any(self.ctx, F3(*o), F3(*d), tmin, tmax, use_bvh)
+        return self.lib.hjo_trace_any(self.ctx, F3(*o), F3(*d), tmin, tmax, use_bvh)
 
 
 def make_params(width, height, spp, cam, frame=1, seed=1, integrator=INTEGRATOR_NEE, sky=(0.8, 0.8, 0.8),

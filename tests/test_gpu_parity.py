@@ -56,6 +56,7 @@ def test_other_integrators_bitexact(cornell, dev, oracle, integrator):
     color, albedo, normal = dev.render(cornell.hjr_params(96, 64, 4, integrator=integrator))
     oc, oa, on, _ = oracle.render(cornell.oracle_params(96, 64, 4, integrator=integrator))
     assert_bitexact(color, oc, "aov_color")
+    assert_bitexact(albedo, oa, "aov_albedo")
     assert_bitexact(normal, on, "aov_normal")
 
 

@@ -101,6 +101,7 @@ def test_equirect_sky(tmp_path):
     arrays = dict(s.arrays, sky_rgba=sky)
     oc, oa, on, st = ob.OracleScene(arrays, ob.MATH_PORTABLE).render(s.oracle_params(96, 64, 6, ibl_intensity=0.7))
     assert_bitexact(color, oc, "aov_color")
+    assert_bitexact(albedo, oa, "aov_albedo")
     assert_bitexact(normal, on, "aov_normal")
     assert not np.array_equal(color, plain)
 
@@ -148,6 +149,7 @@ def test_random_materials_and_cameras():
         assert same_nan.all()
         assert_bitexact(color, oc, "trial %d colour" % trial)
         assert_bitexact(albedo, oa, "trial %d albedo" % trial)
+        assert_bitexact(normal, on, "trial %d normal" % trial)
 
 
 def test_no_lights_and_black_sky():
