@@ -714,7 +714,10 @@ class Device:
                                         C.c_void_p(stream) if stream else None), "hjr_preview_device")
 
     def set_option(self, key, value):
-        """hjr_set_option: tuning / test option of this context (-1 restores the default); layout options act at the next set_transforms."""
+        """hjr_set_option: tuning / test option of this context (-1 restores the default); layout options act at the next set_transforms.
+        "firefly_clamp" (kappa, 0..64) clamps whole-frame renders; with "firefly_clamp_passes" 1 next to it sample passes and adaptive
+        frames are accepted and clamped too (the colour chunk sums of the whole progressive frame are kept; include/henjou_hip.h "Firefly
+        clamp on sample passes").  Setting "firefly_clamp_passes", or "firefly_clamp" while it is 1, ends an unfinished progressive frame."""
         _check(lib().hjr_set_option(self._h, key.encode(), int(value)), "hjr_set_option")
 
     def get_option(self, key):

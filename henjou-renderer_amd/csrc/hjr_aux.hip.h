@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P, floa
     }
 }
 
-// ---- firefly clamp (option "firefly_clamp", DESIGN.md §4 rule 9; the rule is stated in include/henjou_hip.h).  Runs BEHIND
+// ---- firefly clamp (option "firefly_clamp", DESIGN.md §4 rules 9 and 10; the rules are stated in include/henjou_hip.h).  Runs BEHIND
 // hjr_finalize_kernel<false, false, VAR> on a one-shot frame of m = spp / chunk_spp >= 4 full chunks: the plain frame, its albedo, normal and
 // variance stand as that kernel wrote them (the summation stays written once, there), and this kernel rewrites the COLOUR of exactly the pixels
 // that have a scaled chunk, so every other pixel keeps the plain frame's bits by construction.  What it adds is a different sum: every chunk
@@ -242,18 +242,38 @@ __global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P, floa
 // waves with a lane over its limit, reads the colour sums again (the pixel's 16 m bytes were read a moment ago: L2) and adds them scaled, in
 // chunk order from +0.0f.  The scaled (pixel, chunk) pairs are counted per lane, added over the wave, one integer atomic per wave.
 // fp32 as written, correctly rounded divide, no contraction (this translation unit's flags): numpy float32 restates it bit for bit.
-template <uint32_t BLOCK>
+// The flags select what surrounds that, at compile time, as in hjr_finalize_kernel; the one-shot instantiation holds none of it:
+//   PASS      option "firefly_clamp_passes" (rule 10): behind hjr_finalize_kernel<true, ADAPTIVE, VAR> on a sample pass that ends at
+//             n = sample_end with m_n = n / chunk_spp >= 4.  P.part_color is the base of the colour chunk sums the context keeps for the whole
+//             progressive frame; chunks [0, m_n) are streamed, and the partial chunk m_n when n = spp (r_n > 0 only then).  The mean is over n.
+//   ADAPTIVE  (implies PASS) the pass of an adaptive frame.  A STOPPED tile (ad_state = n_tile, as the finalize kernel left it) is clamped
+//             over its own chunks [0, n_tile / chunk_spp) with n = n_tile, or left alone when those are fewer than 4: the slots behind them
+//             are stale and never read.  With P.ad_decide (the finalize kernel ran with 0) every ACTIVE tile takes rule 6's decision here,
+//             from the statistic of the CLAMPED sums, y' = (c.x s + c.y s) + c.z s with the products of the colour sum: a lane over its limit
+//             adds them in stream 2, any other lane has s = 1 throughout and adds its LDS column (y' = y to the bit).  All 64 lanes of the
+//             wave reach the butterfly, out-of-image lanes with e = 0; a tile that stops gets ad_state = n and leaves the active count.
+template <uint32_t BLOCK, bool PASS, bool ADAPTIVE>
 __global__ void __launch_bounds__(BLOCK) hjr_firefly_kernel(const KParams P, const float kappa, unsigned long long* __restrict__ n_clamped)
 {
+    static_assert(PASS || !ADAPTIVE, "adaptive sampling acts on sample passes");
     float* const ys = reinterpret_cast<float*>(hjr_smem) + threadIdx.x;
     const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
-    const uint32_t g = P.chunk_spp, m = P.spp / g, r = P.spp - m * g; // full chunks, samples of the partial last chunk (chunk m, if r > 0)
-    const uint32_t want = (m - 1u) / 2u;                              // rank of the lower median
-    const float inv = 1.0f / (float)P.spp;
+    const uint32_t g = P.chunk_spp, n_pass = PASS ? P.sample_end : P.spp;
+    uint32_t n = n_pass, m = n / g, r = n - m * g; // samples of the mean, full chunks, samples of the partial last chunk (chunk m, if r > 0)
+    uint32_t want = (m - 1u) / 2u;                 // rank of the lower median
+    float inv = 1.0f / (float)n;
     uint32_t n_scaled = 0u;
     for (size_t sl = (size_t)blockIdx.x * BLOCK + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * BLOCK) {
         uint32_t x, y;
         const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y);
+        bool deciding = false; // (wave-uniform)
+        if constexpr (ADAPTIVE) {
+            const uint32_t n_tile = P.ad_state[sl >> 6];
+            n = n_tile ? n_tile : n_pass; m = n / g; r = n - m * g;
+            if (m < 4u) continue; // the rule does not act on this tile
+            want = (m - 1u) / 2u; inv = 1.0f / (float)n;
+            deciding = P.ad_decide != 0u && n_tile == 0u;
+        }
         float lim = 0.0f, lim_r = 0.0f;
         bool over = false;
         if (inside) {
@@ -279,18 +299,35 @@ __global__ void __launch_bounds__(BLOCK) hjr_firefly_kernel(const KParams P, con
                 over = over || (v.x + v.y) + v.z > lim_r;
             }
         }
-        if (!__any(over)) continue; // (wave-uniform)
+        if (!deciding && !__any(over)) continue; // (wave-uniform)
+        float S1 = 0.0f, S2 = 0.0f; // ADAPTIVE: the statistic of the clamped sums over the full chunks
         if (over) {
             float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            for (uint32_t k = 0; k < P.n_chunks; k++) {
+            const uint32_t k_end = PASS ? m + (r ? 1u : 0u) : P.n_chunks;
+            for (uint32_t k = 0; k < k_end; k++) {
                 const float4 v = P.part_color[(size_t)k * n_slots + sl];
                 const float yk = (v.x + v.y) + v.z, L = k < m ? lim : lim_r;
                 const bool scale = yk > L;
                 const float s = scale ? L / yk : 1.0f;
                 a.x = a.x + v.x * s; a.y = a.y + v.y * s; a.z = a.z + v.z * s;
                 n_scaled += scale ? 1u : 0u;
+                if constexpr (ADAPTIVE) if (k < m) { const float yc = (v.x * s + v.y * s) + v.z * s; S1 = S1 + yc; S2 = S2 + yc * yc; } // (the three products above)
             }
             P.aov_color[P.packed ? sl : (size_t)y * P.width + x] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
+        }
+        if constexpr (ADAPTIVE) {
+            if (!deciding) continue;
+            if (inside && !over)
+                for (uint32_t k = 0; k < m; k++) { const float yk = ys[k * BLOCK]; S1 = S1 + yk; S2 = S2 + yk * yk; }
+            const float nf = (float)n, mf = (float)m;
+            const float q = fmaxf(mf * S2 - S1 * S1, 0.0f);
+            const float e = sqrtf(q / (mf - 1.0f)) / (S1 + HJR_ADAPTIVE_EPS * nf);
+            float v = inside ? e : 0.0f;
+            for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
+            if (v <= P.ad_threshold * 64.0f && (threadIdx.x & 63u) == 0u) {
+                P.ad_state[sl >> 6] = n;
+                atomicSub(&P.ad_state[P.n_owned_tiles], 1u); // (the finalize kernel counted the tile as active)
+            }
         }
     }
     for (int k = 32; k >= 1; k >>= 1) n_scaled += (uint32_t)__shfl_xor((int)n_scaled, k, 64);

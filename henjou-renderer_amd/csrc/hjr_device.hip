@@ -85,6 +85,9 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
         return HJR_ERR_ARG;
     }
     c->opt.v[i] = value;
+    // rule 10 keeps chunk sums from a frame's first pass on: an unfinished progressive frame cannot change its rule half way (as hjr_set_adaptive).
+    // "firefly_clamp" alone with "firefly_clamp_passes" off keeps what it always did: the next pass is refused by check_pass
+    if (i == hjr::OPT_FIREFLY_CLAMP_PASSES || (i == hjr::OPT_FIREFLY_CLAMP && c->opt.get(hjr::OPT_FIREFLY_CLAMP_PASSES, 0) == 1)) { c->pass.active = false; c->ad.frame = false; }
     if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL || i == hjr::OPT_DENOISE_TEMPORAL_COVERAGE) c->tmp.have_prev = false; // setting any of these options drops the history
     if (i == hjr::OPT_HOST_THREADS) hjr::set_host_threads(value);
     return HJR_OK;
@@ -478,6 +481,8 @@ struct PassRange {
     uint32_t aovs = 0;         // AOVs requested: bit 0 colour, 1 albedo, 2 normal, 3 variance
 };
 static const uint32_t PASS_FLAGS = HJR_FLAG_PACKED | HJR_FLAG_ZERO_UNOWNED | HJR_FLAG_FAST_MATH; // the flags that change pixels
+// options "firefly_clamp" > 0 and "firefly_clamp_passes" 1 (DESIGN.md §4 rule 10): a progressive frame keeps the colour chunk sums of all its passes
+static bool firefly_keeps_chunks(const hjr_ctx* c) { return c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0) > 0 && c->opt.get(hjr::OPT_FIREFLY_CLAMP_PASSES, 0) == 1; }
 
 // The pass rules, checked before a call enqueues or writes anything: HJR_ERR_ARG for a bad range, HJR_ERR_STATE for a pass that does not
 // continue the context's progressive frame.  Changes nothing; end_pass records a launch once it is enqueued.
@@ -491,7 +496,7 @@ static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, Pass
     }
     if (p->spp == 0) { set_error("hjr_render: width, height and spp must be positive"); return HJR_ERR_ARG; }
     if (p->sample_begin == 0 && p->sample_end == p->spp) return HJR_OK; // the whole frame, through the same path
-    if (c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0) > 0) { // the rule needs every chunk sum of a pixel; a progressive frame keeps running sums only
+    if (c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0) > 0 && !firefly_keeps_chunks(c)) { // the rule needs every chunk sum of a pixel; a progressive frame keeps running sums only
         set_error("hjr_render: option \"firefly_clamp\" takes whole-frame renders only: sample pass [" + std::to_string(p->sample_begin) + ", " + std::to_string(p->sample_end) +
                   ") of " + std::to_string(p->spp) + " spp refused");
         return HJR_ERR_ARG;
@@ -610,19 +615,22 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
     if (g.n_chunks > 1) {
         // chunk sums of THIS rank's tiles and this launch's chunks only: [chunk - chunk0][owned tile][64] float4 (1/world of the frame;
         // a sample pass needs its own chunks only; allocated once per size)
+        // Rule 10 (firefly_keeps_chunks) reads every colour chunk sum of the progressive frame at every pass: the colour buffer then holds all
+        // n_chunks, sized by the frame's first pass and not moved by the later ones (the same size), and is addressed from its base.
+        const bool keep = g.pr.pass && firefly_keeps_chunks(c);
         const size_t part_bytes = (size_t)g.owned * 64u * 16u * g.pass_chunks;
         DevBuf* pb[3] = { &c->d_part_color, &c->d_part_albedo, &c->d_part_normal };
         DevBuf* rb[3] = { &c->d_run_color, &c->d_run_albedo, &c->d_run_normal };
         void* want[3] = { d_color, d_albedo, d_normal };
         for (int i = 0; i < 3; i++) {
-            if (want[i] && !pb[i]->reserve(part_bytes)) { set_error("hjr_render: chunk-sum buffer allocation failed"); return HJR_ERR_DEVICE; }
+            if (want[i] && !pb[i]->reserve(i == 0 && keep ? (size_t)g.owned * 64u * 16u * g.n_chunks : part_bytes)) { set_error("hjr_render: chunk-sum buffer allocation failed"); return HJR_ERR_DEVICE; }
             // running sums of a progressive frame, [owned tile][64] float4; the same size for every pass of one frame, so kept across them
             if (want[i] && g.pr.pass && !rb[i]->reserve((size_t)g.owned * 64u * 16u)) { set_error("hjr_render: running-sum buffer allocation failed"); return HJR_ERR_DEVICE; }
         }
         // the render kernels address chunk k at k * owned * 64: a sample pass's buffers start at its first chunk, so the pointers are
         // moved back by chunk0 chunks (no chunk below chunk0 is stored or read; 0 for a one-shot frame)
         const size_t back = (size_t)g.chunk0 * g.owned * 64u;
-        kp.part_color = (float4*)c->d_part_color.p - back;
+        kp.part_color = (float4*)c->d_part_color.p - (keep ? 0u : back);
         kp.part_albedo = d_albedo ? (float4*)c->d_part_albedo.p - back : nullptr;
         kp.part_normal = d_normal ? (float4*)c->d_part_normal.p - back : nullptr;
         if (g.pr.pass) {
@@ -807,7 +815,15 @@ static int adaptive_filter(hjr_ctx* c, KParams& kp, hipStream_t st)
 // ... after the render kernel, for every launch: sums of the sample chunks -> pixel means (a sample pass: -> running sums and running means;
 // an adaptive one: statistic and stop decisions too, then the count of tiles still active goes to the host).  d_var: the variance AOV was
 // requested (hjr_render_var); a frame of a single chunk has no chunk sums and gets the fill.
-static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, KParams& kp, bool adaptive, float* d_var, hipStream_t st)
+// the count of tiles still active goes to the host, behind the kernel that took the pass's stop decisions
+static int adaptive_count(hjr_ctx* c, const FrameGeom& g, hipStream_t st)
+{
+    HIPCHK(hipMemcpyAsync(c->ad.h_active, (uint32_t*)c->ad.state.p + g.owned, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(c->ad.ready, st));
+    return HJR_OK;
+}
+// count_later: hjr_firefly_kernel decides behind this kernel (rule 10) and the caller sends the count after it
+static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, KParams& kp, bool adaptive, bool count_later, float* d_var, hipStream_t st)
 {
     using Kernel = void (*)(KParams, float*);
     static const Kernel kernels[2][2][2] = { // [pass][adaptive][variance]
@@ -827,10 +843,7 @@ static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, KParams& kp, bool ada
     const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
     hipLaunchKernelGGL(kern, dim3(fb), dim3(256), 0, st, kp, d_var);
     HIPCHK(hipGetLastError());
-    if (adaptive) {
-        HIPCHK(hipMemcpyAsync(c->ad.h_active, d_count, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(c->ad.ready, st));
-    }
+    if (adaptive && !count_later) return adaptive_count(c, g, st);
     return HJR_OK;
 }
 
@@ -844,8 +857,31 @@ static int firefly_clamp(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
     const size_t n_slots = (size_t)g.owned * 64u;
     if (kappa <= 0 || g.pr.pass || g.n_chunks < 2 || m < 4 || n_slots == 0) return HJR_OK;
     const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + FB - 1) / FB, (size_t)c->n_cus * 16));
-    hipLaunchKernelGGL(hjr_firefly_kernel<FB>, dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kp, (float)kappa,
+    hipLaunchKernelGGL((hjr_firefly_kernel<FB, false, false>), dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kp, (float)kappa,
                        (unsigned long long*)((char*)c->d_work.p + WorkArea::FIREFLY));
+    HIPCHK(hipGetLastError());
+    return HJR_OK;
+}
+// Option "firefly_clamp_passes" (DESIGN.md §4 rule 10), behind finalize_chunks on a sample pass of a frame that keeps its colour chunk sums
+// (firefly_keeps_chunks) and has received m_n = sample_end / granule >= 4 full chunks: the colour of the pixels with a chunk over their limit
+// is rewritten from chunks [0, m_n) (a stopped tile of an adaptive frame: from its own), and with `decide` the kernel takes the adaptive
+// pass's stop decisions from the clamped sums (finalize_chunks ran with ad_decide 0).  Earlier passes launch nothing: the parent's sequence.
+static bool firefly_pass_acts(const hjr_ctx* c, const FrameGeom& g)
+{
+    return g.pr.pass && g.n_chunks > 1 && g.owned > 0 && firefly_keeps_chunks(c) && g.pr.end / g.chunk_spp >= 4u;
+}
+static int firefly_clamp_pass(hjr_ctx* c, const FrameGeom& g, const KParams& kp, bool adaptive, bool decide, hipStream_t st)
+{
+    constexpr uint32_t FB = 128;
+    if (!firefly_pass_acts(c, g)) return HJR_OK;
+    const uint32_t m = g.pr.end / g.chunk_spp; // <= 64 full chunks (hjr_layout.h): at most 32 KiB of LDS
+    const size_t n_slots = (size_t)g.owned * 64u;
+    KParams kf = kp;
+    kf.ad_decide = decide ? 1u : 0u;
+    const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + FB - 1) / FB, (size_t)c->n_cus * 16));
+    unsigned long long* const d_n = (unsigned long long*)((char*)c->d_work.p + WorkArea::FIREFLY);
+    if (adaptive) hipLaunchKernelGGL((hjr_firefly_kernel<FB, true, true>), dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kf, (float)c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0), d_n);
+    else hipLaunchKernelGGL((hjr_firefly_kernel<FB, true, false>), dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kf, (float)c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0), d_n);
     HIPCHK(hipGetLastError());
     return HJR_OK;
 }
@@ -871,8 +907,13 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, voi
         if (adaptive && active < g.owned && (rc = adaptive_filter(c, kp, st)) != HJR_OK) return rc;
         if ((rc = launch_render(c, p, g, kp, st)) != HJR_OK) return rc;
     }
-    if ((rc = finalize_chunks(c, g, kp, adaptive, (float*)d_var, st)) != HJR_OK) return rc;
+    // rule 10: on a deciding pass of >= 4 full chunks the decision is hjr_firefly_kernel's, from the clamped sums
+    const bool decide = adaptive && kp.ad_decide != 0u, ff_decides = decide && firefly_pass_acts(c, g);
+    if (ff_decides) kp.ad_decide = 0u;
+    if ((rc = finalize_chunks(c, g, kp, adaptive, ff_decides, (float*)d_var, st)) != HJR_OK) return rc;
     if ((rc = firefly_clamp(c, p, g, kp, st)) != HJR_OK) return rc;
+    if ((rc = firefly_clamp_pass(c, g, kp, adaptive, ff_decides, st)) != HJR_OK) return rc;
+    if (ff_decides && (rc = adaptive_count(c, g, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
     if (pr.pass && c->opt.get(hjr::OPT_VERBOSE, 0))
@@ -884,7 +925,7 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, voi
         ad.samples = (pr.begin ? ad.samples : 0ull) + (uint64_t)active * (pr.end - pr.begin) * 64ull;
         if (c->opt.get(hjr::OPT_VERBOSE, 0))
             fprintf(stderr, "[hjr] frame %u: adaptive pass [%u, %u): %u of %u tiles active, %llu samples rendered so far%s\n", p->frame, pr.begin, pr.end, active, ad.owned,
-                    (unsigned long long)ad.samples, kp.ad_decide ? ", stop decision after it" : "");
+                    (unsigned long long)ad.samples, decide ? ", stop decision after it" : "");
     }
     end_pass(c, p, pr);
     return HJR_OK;

@@ -67,7 +67,7 @@ struct hjr_ctx {
     uint32_t n_textures = 0;
     int lut_w = 0, lut_h = 0;
     DevBuf d_color, d_albedo, d_normal; // staging for hjr_render (host buffers)
-    DevBuf d_part_color, d_part_albedo, d_part_normal; // chunk sums [pass_chunks][owned tile][64] float4
+    DevBuf d_part_color, d_part_albedo, d_part_normal; // chunk sums [pass_chunks][owned tile][64] float4 (colour under rule 10: [n_chunks], kept across the passes of a frame)
     DevBuf d_run_color, d_run_albedo, d_run_normal; // running sums of a frame rendered in sample passes, [owned tile][64] float4
     DevBuf d_stat; // per owned pixel (S1, S2) of such a frame, [owned tile][64] float2; allocated at the first adaptive pass or pass with a variance
     DevBuf d_spill; // overflow of the short traversal stacks (memory-path kernels)

@@ -160,7 +160,7 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
             o.fast_math = flag(h->find("fast_math")) ? 1 : 0;
             // the keys that share a field of the struct: one row each in render_job.hpp's table, read in the order the format grew in
             std::vector<const KeyRow*> rows;
-            for (const KeyRow& r : key_table()) rows.push_back(&r);
+            for (const KeyRow& r : key_rows()) rows.push_back(&r);
             std::sort(rows.begin(), rows.end(), [](const KeyRow* a, const KeyRow* b) { return a->parse < b->parse; });
             for (const KeyRow* r : rows) parse_key(*h, *r, o);
             // passes: sample passes per frame (hjr_params.sample_begin / sample_end); the frame's bytes do not depend on it

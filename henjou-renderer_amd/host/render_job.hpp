@@ -62,10 +62,30 @@ inline const std::vector<KeyRow>& key_table()
     };
     return t;
 }
+// key_table() holds the thirteen keys the hand-written parser had; tests/native/render_job_test.cpp pins that set, their bits and the lists
+// they give.  A key added since is a row here, of the same form, and the parser, key_row and for_each_option walk key_rows(): the two in
+// this order.  Its parse turns go on from key_table()'s.
+inline const std::vector<KeyRow>& key_table_since()
+{
+    using O = hjr_render_option;
+    static const std::vector<KeyRow> t = {
+        { "firefly_clamp_passes", 13, &O::device_bvh_opt, ENC_BITS, 23, 1, READ_BOOL, "firefly_clamp", WHO_EVERY }, // (every rank keeps its own chunk sums)
+    };
+    return t;
+}
+inline const std::vector<KeyRow>& key_rows()
+{
+    static const std::vector<KeyRow> all = [] {
+        std::vector<KeyRow> v = key_table();
+        v.insert(v.end(), key_table_since().begin(), key_table_since().end());
+        return v;
+    }();
+    return all;
+}
 inline const KeyRow& key_row(const char* key)
 {
-    for (const KeyRow& r : key_table()) if (strcmp(r.key, key) == 0) return r;
-    return key_table().front(); // (not reached: the callers name rows of the table)
+    for (const KeyRow& r : key_rows()) if (strcmp(r.key, key) == 0) return r;
+    return key_rows().front(); // (not reached: the callers name rows of the tables)
 }
 inline int key_get(const hjr_render_option& o, const KeyRow& r)
 {
@@ -96,7 +116,7 @@ inline JobScope rank_of_world(int rank) { return { false, rank }; }
 // fn(option key, value) for every option the job sets in this process, in table order; stops at the first non-zero result and returns it
 template <typename Fn> int for_each_option(const hjr_render_option& o, JobScope s, Fn fn)
 {
-    for (const KeyRow& r : key_table()) {
+    for (const KeyRow& r : key_rows()) {
         const bool mine = r.who == WHO_EVERY || (r.who == WHO_SINGLE && s.single) || (r.who == WHO_FILTER && s.rank == 0) ||
                           (r.who == WHO_FILTER_DENOISE && s.rank == 0 && o.render_mode != HJR_MODE_DEFAULT);
         const int v = mine ? key_get(o, r) : 0;
@@ -126,7 +146,7 @@ inline bool job_check(const hjr_render_option& o, Job& job, std::string& text)
         text = "Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)";
     else if (job.temporal && job.adaptive)
         text = "\"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history";
-    else if (job.firefly && (o.passes > 1 || job.adaptive)) // every rank clamps its own pixels, so the rule is the same on both paths
+    else if (job.firefly && !key_get(o, key_row("firefly_clamp_passes")) && (o.passes > 1 || job.adaptive)) // every rank clamps its own pixels, so the rule is the same on both paths
         text = "\"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only";
     else if (job.w == 0 || job.h == 0)
         text = "image too small for DenoiseUpScale2X";

@@ -146,8 +146,8 @@ typedef struct hjr_render_option {
     int32_t device_bvh_opt;      /* default 0; bits 0..7: key "device_bvh_opt", 0..3 treelet-restructuring rounds of that device build;
                                   * bit 8: key "device_bvh_instances"; bit 9: key "device_bvh_graft"; bit 10: key "denoise_variance_spatial";
                                   * bit 11: key "upscale_guided"; bits 12..14: key "denoise_temporal_coverage", 0, 2, 3 or 4; bits 16..22: key
-                                  * "firefly_clamp", 0..64 (bits 10 and up are the section's spare bits: those keys have nothing to do with
-                                  * the BVH) */
+                                  * "firefly_clamp", 0..64; bit 23: key "firefly_clamp_passes" (bits 10 and up are the section's spare bits:
+                                  * those keys have nothing to do with the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
     float noise_threshold;       /* default 0 (off); > 0: hjr_render_file / henjou_cli set hjr_adaptive.noise_threshold, render each frame in
@@ -282,7 +282,36 @@ typedef struct hjr_adaptive_state {
  * HJR_FLAG_PACKED, HJR_FLAG_ZERO_UNOWNED and sharded launches behave as for the plain frame, and N ranks give the one-rank frame.
  * hjr_stats.firefly_clamped counts the scaled (pixel, chunk) pairs of the launch.
  * The rule needs all chunk sums of a pixel and a progressive frame keeps running sums only: on a context with the option on, a sample
- * pass that is not the whole range [0, spp) is HJR_ERR_ARG (the error names the option); nothing is enqueued or written. */
+ * pass that is not the whole range [0, spp) is HJR_ERR_ARG (the error names the option); nothing is enqueued or written -- unless option
+ * "firefly_clamp_passes" is on:
+ *
+ * ---- Firefly clamp on sample passes (option "firefly_clamp_passes" = 1 next to "firefly_clamp" = kappa > 0; DESIGN.md §4 rule 10) ---------
+ * Off (0, the default), or with "firefly_clamp" 0, every call, refusal, kernel and launch is what the paragraph above says.  With both on
+ * a whole-frame render is still that paragraph's, bit for bit, and sample passes are accepted: the context keeps the COLOUR chunk sums of
+ * this rank's tiles for the whole progressive frame ([n_chunks][owned tile][64] float4: 16 bytes x n_chunks per owned pixel, where a
+ * plain pass keeps those of the pass only; albedo and normal stay per pass with their running sums).  A pass that ends at n = sample_end
+ * writes, per owned pixel, with g, c_k, y_k as above, m_n = n / g (integer division: the full chunks received) and r_n = n - m_n * g
+ * (non-zero only when n = spp), fp32 in the written order, no contraction, correctly rounded divide and sqrt:
+ *  1. the rule ACTS iff m_n >= 4; otherwise the colour has the plain pass's bits;
+ *  2. steps 2 - 6 above with m_n, r_n, n in place of m, r, spp: the lower median over y_0 .. y_{m_n-1}, lim = (float)kappa * med +
+ *     HJR_FIREFLY_EPS * (float)g, lim_r = lim * ((float)r_n / (float)g), s_k = (y_k > L) ? L / y_k : 1.0f, a.c = a.c + c_k.c * s_k in
+ *     chunk order from +0.0f, out = a * (1.0f / (float)n), alpha 1.  The pass that ends at spp therefore writes the one-shot clamped
+ *     frame, bit for bit, and a pixel with no scaled chunk keeps the plain pass's bits;
+ *  3. albedo, normal and the variance AOV have the bits of the same pass with "firefly_clamp" 0; the variance stays the raw statistic;
+ *  4. adaptive frames (hjr_set_adaptive): a pass decides under the conditions stated there, unchanged (n < spp, n >= min_samples,
+ *     m_n >= 2).  With m_n < 4 the decision is that rule as it is.  With m_n >= 4 the statistic is that of the CLAMPED sums, recomputed
+ *     from the kept chunk sums with this pass's limit:  y'_k = (c_k.x * s_k + c_k.y * s_k) + c_k.z * s_k  (the three products of step 2),
+ *     S1' = S1' + y'_k and S2' = S2' + y'_k * y'_k in chunk order from +0.0f over the m_n full chunks; then q, e, the xor butterfly and
+ *     v <= noise_threshold * 64.0f as there, with S1', S2'.  A stopped tile holds n_tile: its colour is step 2 over its chunks
+ *     [0, n_tile / g) with n = n_tile (the plain mean when those are fewer than 4), the bits it had when it stopped; the chunk slots the
+ *     render kernels left stale are never read.  hjr_get_adaptive_state and hjr_copy_tile_samples keep their meaning;
+ *  5. hjr_stats.firefly_clamped counts the scaled (pixel, chunk) pairs in the colours the pass wrote, over all in-image owned pixels (a
+ *     stopped tile over its own chunks); 0 when the rule did not act;
+ *  6. the rule is per pixel and per tile: HJR_FLAG_PACKED, HJR_FLAG_ZERO_UNOWNED, shards, kernel family, layout and integrator do not
+ *     enter, and N ranks give the one-rank frame.
+ * hjr_render_denoised filters the clamped running mean.  Setting either option (any value) while "firefly_clamp_passes" is on, or that
+ * option itself, ends an unfinished progressive frame as hjr_set_adaptive does: a continuing pass after it is HJR_ERR_STATE, with nothing
+ * enqueued or written. */
 #define HJR_FIREFLY_EPS 1e-3f    /* keeps the limit of a pixel whose median chunk is black above 0 */
 
 typedef struct hjr_stats {
@@ -313,7 +342,7 @@ typedef struct hjr_stats {
                                   * 0 = an ordinary build or host-built data */
     float    bvh_topology_ms;    /* HIP-event time of the last per-instance topology build of that option; the commits that reuse the
                                   * topology leave it as it is */
-    uint64_t firefly_clamped;    /* option "firefly_clamp": (pixel, chunk) pairs the last whole-frame launch scaled down; 0 when the rule did not act */
+    uint64_t firefly_clamped;    /* option "firefly_clamp": (pixel, chunk) pairs the last whole-frame launch scaled down (with "firefly_clamp_passes": those in the colours the last sample pass wrote); 0 when the rule did not act */
     uint32_t item_chunks;        /* chunks of a pixel per work item of the last render launch (option "item_chunks" as the launch resolved it; 1 for the wavefront kernels) */
     uint32_t _pad1;
 } hjr_stats;
@@ -612,8 +641,15 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  frame goes through hjr_denoise_shards_device, which honours both options); HJR_MODE_DEFAULT ignores it.  Setting it (any value) drops the history.  0 (default): today's call, bit for bit
    "firefly_clamp"  0..64        kappa of the firefly clamp (above, "Firefly clamp"): whole-frame renders scale every chunk sum of a pixel that
                                  exceeds kappa x the lower median of the pixel's full chunks down to that limit.  Biased, opt-in; 4 is the
-                                 recommended value.  Sample passes other than [0, spp) are HJR_ERR_ARG with it.  0 (default): today's call,
-                                 bit for bit, the same kernels
+                                 recommended value.  Sample passes other than [0, spp) are HJR_ERR_ARG with it unless "firefly_clamp_passes"
+                                 is on.  0 (default): today's call, bit for bit, the same kernels
+   "firefly_clamp_passes" 0 1    1: with "firefly_clamp" > 0 sample passes and adaptive frames are accepted (above, "Firefly clamp on sample
+                                 passes"): the context keeps the colour chunk sums of the whole progressive frame (16 bytes x chunks of the
+                                 frame per owned pixel: 1.06 GB at 1080p x 256 spp on one GPU), every pass of at least 4 full chunks writes
+                                 the clamped running mean, and an adaptive frame stops on the statistic of the clamped sums.  Whole-frame
+                                 renders are unchanged.  Without effect while "firefly_clamp" is 0.  Setting it (any value), or
+                                 "firefly_clamp" while it is 1, ends an unfinished progressive frame.  0 (default): today's calls and
+                                 refusals, bit for bit, the same launches
    "item_chunks"    1 2 4 8      megakernel: consecutive sample chunks of one pixel that form a work item of the queue.  A launch uses the
                                  largest power of two that is no larger than this and divides the number of chunks it renders (possibly 1).
                                  Scheduling only: every chunk is still summed on its own, frames are the same bits.  Default: 1 for launches
@@ -645,9 +681,10 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
- * Thirteen more keys of that section set the context option of their name; where each is stored is in the comment on hjr_render_option.
+ * Fourteen more keys of that section set the context option of their name; where each is stored is in the comment on hjr_render_option.
  * "force_rebuild" is set by hjr_render_file only.  "verbose", "device_bvh", "device_bvh_refit": N (integer 0..1000), "device_bvh_opt",
- * "device_bvh_instances", "device_bvh_graft" and "firefly_clamp": N (integer 0..64) are set single-GPU and on every rank of --devices N.
+ * "device_bvh_instances", "device_bvh_graft", "firefly_clamp": N (integer 0..64) and "firefly_clamp_passes" (true, false, 0 or 1; a parse
+ * error without "firefly_clamp") are set single-GPU and on every rank of --devices N.
  * "denoise_variance", "denoise_temporal" (both in the two Denoise modes only), "denoise_variance_spatial", "upscale_guided" and
  * "denoise_temporal_coverage": N (0, 2, 3 or 4) are set single-GPU and on rank 0 of --devices N, which filters, accumulates and upscales (the
  * PNG is the single-GPU run's).  "device_bvh_refit" and "device_bvh_instances" are a parse error without "device_bvh": true, and
@@ -655,8 +692,8 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
  * or 1 only.  "denoise_variance_spatial" and "denoise_temporal_coverage" are accepted and without effect without "denoise_variance" /
  * "denoise_temporal", "upscale_guided" outside DenoiseUpScale2X.  Both drivers refuse, before they load the scene or touch a device:
  * "denoise_temporal" together with "noise_threshold" > 0 (an adaptive frame that stops early never reaches the pass that advances the
- * history), and "firefly_clamp" together with "passes" > 1 or "noise_threshold" > 0 (the rule needs every chunk sum of a pixel and a frame in
- * sample passes keeps running sums only).  An option call that fails ends the job.
+ * history), and "firefly_clamp" together with "passes" > 1 or "noise_threshold" > 0 unless "firefly_clamp_passes" is true (the rule needs
+ * every chunk sum of a pixel and a frame in sample passes keeps running sums only).  An option call that fails ends the job.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
 int hjr_get_option(hjr_ctx*, const char* key, int* value);
