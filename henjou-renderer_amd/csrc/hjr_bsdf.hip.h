@@ -13,10 +13,14 @@ struct Surface { // kernel/Payload.h:12-42
 // ------------------------------------------------------------------ thin-film LUT: tex2D<float4>(params.lut_texture, u, v), disneyBRDF.h:11-14
 // Sampler state from renderer.h:854-898 (uchar4 -> normalised float, linear, wrap, normalised coords); filtering per the
 // CUDA programming guide: texel-centre offset, 1.8 fixed-point weights.
+// MEGA (here and in the functions below that pass it on): the megakernel's form.  It reads the table's size here, like the cold parameters of
+// hjr_params.hip.h: taken from P, the conversions and the reciprocals of the two `%` below are hoisted out of its render loop and hold,
+// or spill, registers through every round for the thin-film hits' sake.  (The wavefront kernel measured slower with it: MIS 181 -> 182.5 ms.)
+template <bool MEGA = false>
 HD f3 lut_fetch(const KParams& P, float u, float v)
 {
-    if (!P.lut || P.lut_w <= 0 || P.lut_h <= 0) return V1(0.0f);
-    int w = P.lut_w, h = P.lut_h;
+    const int w = MEGA ? HJR_COLD(lut_w) : P.lut_w, h = MEGA ? HJR_COLD(lut_h) : P.lut_h;
+    if (!P.lut || w <= 0 || h <= 0) return V1(0.0f);
     float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
     float fx = floorf(x), fy = floorf(y);
     float ax = floorf((x - fx) * 256.0f + 0.5f) * (1.0f / 256.0f);
@@ -172,6 +176,7 @@ HD bool disney_plain(const Disney& d, f3 wo, f3 wi)
     const bool plain = __float_as_uint(d.sheen) == 0u && __float_as_uint(d.clearcoat) == 0u && fminf(fabsf(wo.y), fabsf(wi.y)) > 1e-15f;
     return __ballot(!plain) == 0ull;
 }
+template <bool MEGA = false>
 HD f3 disney_eval(const KParams& P, const Disney& d, f3 wo, f3 wi) // :179-235
 {
     f3 wm = normalize(wo + wi);
@@ -187,7 +192,7 @@ HD f3 disney_eval(const KParams& P, const Disney& d, f3 wo, f3 wi) // :179-235
     if (d.is_thinfilm) { // :213-217
         float thickness = d.basecolor.x;
         float cosine = absdot(wi, wm);
-        F0 = lut_fetch(P, thickness, cosine);
+        F0 = lut_fetch<MEGA>(P, thickness, cosine);
     }
     // specular(), :112-120
     f3 f_specular;
@@ -231,13 +236,17 @@ HD void disney_weights(const Disney& d, float& dw, float& sw, float& cw)
     sw = specularWeight / sumWeight;
     cw = clearcoatWeight / sumWeight;
 }
-HD f3 disney_sample(const KParams& P, const Disney& d, f3 wo, f3& wi, float& pdf, CMJState& st) // :237-307
+// PRE (here and in the two samplers below; megakernel only, so it stands for MEGA too): the first cmj_1d / cmj_2d pair of the call was drawn
+// ahead by the caller (hjr_kernel.hip.h: bounce_post_trace, AHEAD): x_pre, xy_pre
+template <bool PRE = false>
+HD f3 disney_sample(const KParams& P, const Disney& d, f3 wo, f3& wi, float& pdf, CMJState& st, const float x_pre = 0.0f, const f2 xy_pre = f2()) // :237-307
 {
     float dw, sw, cw;
     disney_weights(d, dw, sw, cw);
-    float select_p = cmj_1d(st);
+    if (PRE) st.depth += 2u;
+    float select_p = PRE ? x_pre : cmj_1d(st);
     float pdf_diffuse = 1.0f, pdf_specular = 1.0f, pdf_clearcoat = 1.0f;
-    f2 xi = cmj_2d(st);
+    f2 xi = PRE ? xy_pre : cmj_2d(st);
     // The reference's three branches (:262-291) repeat most of their work: the azimuth sin / cos, the normalisation of the half
     // vector (diffuse and specular lobe) and the three lobe pdfs are the same operations on the lane's own (xi, wi, wm) whichever lobe
     // was chosen.  A wave that holds lanes of both the diffuse and the specular lobe (two thirds / one third for a dielectric) runs
@@ -278,7 +287,7 @@ HD f3 disney_sample(const KParams& P, const Disney& d, f3 wo, f3& wi, float& pdf
         pdf = dw * pdf_diffuse + sw * pdf_specular + cw * pdf_clearcoat;
     }
     if (wi.y < 0.0f) { pdf = 1.0f; return V1(0.0f); }
-    return disney_eval(P, d, wo, wi);
+    return disney_eval<PRE>(P, d, wo, wi);
 }
 HD float disney_pdf(const Disney& d, f3 wo, f3 wi) // :309-326
 {
@@ -289,7 +298,8 @@ HD float disney_pdf(const Disney& d, f3 wo, f3 wi) // :309-326
 }
 
 // ------------------------------------------------------------------ MetaMaterialGlass (kernel/BSDFs.h:404-479): negative refractive index
-HD f3 metaglass_sample(float ior, f3 wo, f3& wi, float& pdf, CMJState& st)
+template <bool PRE = false>
+HD f3 metaglass_sample(float ior, f3 wo, f3& wi, float& pdf, CMJState& st, const float x_pre = 0.0f)
 {
     const f3 rho = V1(1.0f); // BSDFs.h:998
     float ior_o = 1.0f, ior_i = ior, sign = 1.0f;
@@ -297,7 +307,8 @@ HD f3 metaglass_sample(float ior, f3 wo, f3& wi, float& pdf, CMJState& st)
     f3 n = V(0, 1, 0);
     if (wo.y < 0.0f) { ior_o = ior; ior_i = 1.0f; lwo.y = -lwo.y; sign = -1.0f; }
     const float fr = schlick_ior(ior_o, ior_i, lwo, n);
-    float p = cmj_1d(st);
+    if (PRE) st.depth += 1u;
+    float p = PRE ? x_pre : cmj_1d(st);
     f3 t;
     if (p < fr) lwi = reflect3(-lwo, n);
     else if (refract3(lwo, n, ior_o, ior_i, t)) lwi = reflect3(-t, V(0, -1, 0)); // tangential flip (:454)
@@ -337,53 +348,67 @@ HD float ms_sampleHeight(float a, f3 wr, float hr, float U) // :566-586
     if (U > 1.0f - G_1_) return HJ_FLT_MAX;
     return ms_invC1(ms_C1(hr) / p_pow((1.0f - U), 1.0f / ms_Lambda(a, wr)));
 }
-HD f3 msggx_sampleBSDF(f3 F0, float alpha, f3 wo_in, f3& wi_out, CMJState& st, float& pdf) // :784-819 + :843-851
+// one step of the walk (the loop body of :790-817); false: the walk is over.  PRE: the step's two draws were made ahead (x_pre, xy_pre)
+struct MsWalk { f3 wr; float hr; int order; f3 weight; bool early; f3 early_ret; };
+template <bool PRE>
+HD bool ms_walk_step(MsWalk& w, f3 F0, float alpha, f3& wi_out, CMJState& st, const float x_pre, const f2 xy_pre)
 {
-    f3 wr = -wo_in;
-    float hr = 1.0f + ms_invC1(0.999f);
-    int order = 0;
-    f3 weight = V1(1.0f);
-    bool early = false;
-    f3 early_ret = V1(0.0f);
-    for (;;) {
-        float U = cmj_1d(st);
-        hr = ms_sampleHeight(alpha, wr, hr, U);
-        if (hr == HJ_FLT_MAX) break;
-        else order++;
-        if (order > 5) { wi_out = V(0, 0, 1); early = true; early_ret = V(0, 0, 0); break; }
-        // samplePhaseFunction(-wr, state, weight_1), :737-746
-        f3 wi = -wr;
-        const f2 uv = cmj_2d(st);
-        f3 wm = sample_visible_normal(alpha, uv, wi);
-        wr = (-wi) + (wm * 2.0f) * dot(wi, wm);
-        f3 weight_1 = schlick3(F0, wi, wm);
-        weight = weight * weight_1;
-        if ((hr != hr) || (wr.z != wr.z)) { early = true; early_ret = V(0, 0, 1); break; } // wi_out untouched (:813-814)
-    }
+    float U;
+    if (PRE) { U = x_pre; st.depth += 1u; } else U = cmj_1d(st);
+    w.hr = ms_sampleHeight(alpha, w.wr, w.hr, U);
+    if (w.hr == HJ_FLT_MAX) return false;
+    w.order++;
+    if (w.order > 5) { wi_out = V(0, 0, 1); w.early = true; w.early_ret = V(0, 0, 0); return false; }
+    // samplePhaseFunction(-wr, state, weight_1), :737-746
+    f3 wi = -w.wr;
+    f2 uv;
+    if (PRE) { uv = xy_pre; st.depth += 1u; } else uv = cmj_2d(st);
+    f3 wm = sample_visible_normal(alpha, uv, wi);
+    w.wr = (-wi) + (wm * 2.0f) * dot(wi, wm);
+    f3 weight_1 = schlick3(F0, wi, wm);
+    w.weight = w.weight * weight_1;
+    if ((w.hr != w.hr) || (w.wr.z != w.wr.z)) { w.early = true; w.early_ret = V(0, 0, 1); return false; } // wi_out untouched (:813-814)
+    return true;
+}
+template <bool PRE = false>
+HD f3 msggx_sampleBSDF(f3 F0, float alpha, f3 wo_in, f3& wi_out, CMJState& st, float& pdf, const float x_pre = 0.0f, const f2 xy_pre = f2()) // :784-819 + :843-851
+{
+    MsWalk w;
+    w.wr = -wo_in;
+    w.hr = 1.0f + ms_invC1(0.999f);
+    w.order = 0;
+    w.weight = V1(1.0f);
+    w.early = false;
+    w.early_ret = V1(0.0f);
+    // (PRE: the step that takes the pair drawn ahead stands in front of the loop, so the pair is not carried through it)
+    if (!PRE || ms_walk_step<true>(w, F0, alpha, wi_out, st, x_pre, xy_pre))
+        while (ms_walk_step<false>(w, F0, alpha, wi_out, st, 0.0f, f2())) {}
     f3 bsdf;
-    if (early) bsdf = early_ret;
-    else { wi_out = wr; bsdf = weight; }
-    if (wi_out.y < 0.0f || order > 5) return V1(0.0f); // pdf stays as the caller initialised it (:846-848)
+    if (w.early) bsdf = w.early_ret;
+    else { wi_out = w.wr; bsdf = w.weight; }
+    if (wi_out.y < 0.0f || w.order > 5) return V1(0.0f); // pdf stays as the caller initialised it (:846-848)
     pdf = fabsf(wi_out.y);
     return bsdf;
 }
 
 // ------------------------------------------------------------------ BSDF dispatch (kernel/BSDFs.h:979-1038)
 // lambda_wo = disney_lambda_wo(s, wo), computed once by the caller for all the calls of one shaded hit
+template <bool MEGA = false>
 HD f3 bsdf_eval(const KParams& P, const Surface& s, f3 wo, f3 wi, float lambda_wo)
 {
     if (s.is_specular) return V1(0.0f);
     Disney d = disney_init(s, lambda_wo);
-    return disney_eval(P, d, wo, wi);
+    return disney_eval<MEGA>(P, d, wo, wi);
 }
-HD f3 bsdf_sample(const KParams& P, const Surface& s, f3 wo, f3& wi, float& pdf, CMJState& st, float lambda_wo)
+template <bool PRE = false>
+HD f3 bsdf_sample(const KParams& P, const Surface& s, f3 wo, f3& wi, float& pdf, CMJState& st, float lambda_wo, const float x_pre = 0.0f, const f2 xy_pre = f2())
 {
-    if (s.is_specular) return metaglass_sample(s.ior, wo, wi, pdf, st);
+    if (s.is_specular) return metaglass_sample<PRE>(s.ior, wo, wi, pdf, st, x_pre);
     if (!(s.metallic > 0.5f)) {
         Disney d = disney_init(s, lambda_wo);
-        return disney_sample(P, d, wo, wi, pdf, st);
+        return disney_sample<PRE>(P, d, wo, wi, pdf, st, x_pre, xy_pre);
     }
-    return msggx_sampleBSDF(s.basecolor, clampf(s.roughness * s.roughness, 0.0001f, 1.0f), wo, wi, st, pdf);
+    return msggx_sampleBSDF<PRE>(s.basecolor, clampf(s.roughness * s.roughness, 0.0001f, 1.0f), wo, wi, st, pdf, x_pre, xy_pre);
 }
 HD float bsdf_pdf(const Surface& s, f3 wo, f3 wi, float lambda_wo)
 {

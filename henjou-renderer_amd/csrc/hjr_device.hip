@@ -1030,7 +1030,7 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
 #endif
 #ifdef HJR_TIMING
     { // diagnostic build only: wave-clock shares of the megakernel's loop phases and lane occupancies
-        unsigned long long tk[18];
+        unsigned long long tk[25];
         HIPCHK(hipMemcpy(tk, (char*)c->d_work.p + WorkArea::DIAG, sizeof(tk), hipMemcpyDeviceToHost));
         const double tot = (double)tk[0] + (double)tk[1] + (double)tk[2];
         if (tot > 0) fprintf(stderr, "[hjr timing] roulette/refill/regeneration %.1f%%  fused trace %.1f%%  resolve + hit program + shading %.1f%%  (%.3g wave-clocks)\n",
@@ -1041,6 +1041,8 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
                                    "leaf parts in %.0f%% of the passes x %.1f lanes; triangle tests %.2f wave-iterations per pass x %.1f lanes\n",
                            tk[3] ? (double)td[0] / tk[3] : 0.0, (double)td[1] / td[0], (double)td[8] / td[0], (double)td[2] / td[0], td[2] ? (double)td[3] / td[2] : 0.0,
                            100.0 * td[4] / td[0], td[4] ? (double)td[5] / td[4] : 0.0, (double)td[6] / td[0], td[6] ? (double)td[7] / td[6] : 0.0);
+        const unsigned long long* ls = tk + 17; // (rounds that reach the site, rounds of those with at most 32 drawing lanes) x (light sample, Disney / glass sample, first walk step, roulette)
+        if (tk[3]) fprintf(stderr, "[hjr timing] draw sites: rounds %llu light %llu %llu bsdf %llu %llu walk %llu %llu roulette %llu %llu\n", tk[3], ls[0], ls[1], ls[2], ls[3], ls[4], ls[5], ls[6], ls[7]);
     }
 #endif
     return HJR_OK;

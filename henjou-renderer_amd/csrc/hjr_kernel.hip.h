@@ -300,19 +300,6 @@ HD bool shared_claim(const KParams& P, SharedRange* S, uint32_t n, uint32_t& a0,
     return dry;
 }
 
-// Launch parameters that only the start and the end of a work item need (tile list, queue head, output and chunk-sum pointers, shard
-// geometry) are read from the kernel-argument segment WHERE they are used instead of living in SGPRs for the whole kernel: the render
-// loop keeps ~100 scalar values alive, and every one of these that stays resident pushes another into a VGPR lane (v_writelane at entry,
-// v_readlane at each use: VALU instructions inside the round loop).  The empty asm makes the base pointer opaque, so the compiler can
-// neither hoist the load out of the loop nor merge it with the by-value copy of P.
-template <typename T> HD T cold_param(size_t offset)
-{
-    const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *reinterpret_cast<const T __attribute__((address_space(4)))*>(ka + offset);
-}
-#define HJR_COLD(field) cold_param<decltype(KParams::field)>(offsetof(KParams, field))
-
 // NaN/Inf guard + ordered accumulation of one finished sample
 template <bool STATS> HD void finish_sample(const KParams& P, LaneCtx& c, f3 L, unsigned long long* lc, const uint32_t s_back = 0u) // s_back = 1: the sample before c.s (its bookkeeping was closed while the shadow ray was pending)
 {
@@ -513,7 +500,9 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
 
 // ---- second half of a bounce, for a lane whose rays of this round are resolved: `occluded` answers the pending shadow ray
 // (if c.sh_valid), `h` the closest-hit ray (if tracing).  Lane-private: no cross-lane operation inside.
-template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST, bool ONEWRITE = false, bool GROUPS = false>
+// AHEAD (megakernel): the lanes of a wave have hit surfaces of every material class, and the first draws of the BSDF sample are made in
+// front of the material branch (below).  The wavefront kernel shades batches of one class: its samplers draw for themselves.
+template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST, bool ONEWRITE = false, bool GROUPS = false, bool AHEAD = false>
 HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* tris, const float4* mats, const float4* lights, LaneCtx& c,
                           const bool tracing, const bool occluded, const Hit& h, ST& stack, unsigned long long* lc)
 {
@@ -579,7 +568,7 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
         const float cosine1 = absdot(n, sd);
         const float cosine2 = absdot(light_normal, -sd);
         const f3 local_wi = world_to_local(sd, t, n, b);
-        const f3 bsdf = bsdf_eval(P, sf, local_wo, local_wi, lambda_wo);
+        const f3 bsdf = bsdf_eval<AHEAD>(P, sf, local_wo, local_wi, lambda_wo);
         const float G = cosine2 / (light_distance * light_distance);
         if (INTEGRATOR == HJR_INTEGRATOR_NEE_) {
             c.sh_contrib = (ps.thr * ((bsdf * G * cosine1) * inv_light_pdf)) * light_color; // rt.h:258: float3 / light_pdf
@@ -643,7 +632,14 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
     float pdf = 1.0f;
     f3 local_wi = V(0.0f, 1.0f, 0.0f);
     if (INTEGRATOR != HJR_INTEGRATOR_PT_) (void)cmj_2d(st); // drawn and discarded by the reference (rt.h:266, 426)
-    const f3 bsdf = bsdf_sample(P, sf, local_wo, local_wi, pdf, st, lambda_wo);
+    // Every material class starts its sample with the same two draws — a 1-D number, then a 2-D one (glass: the first only) — and each
+    // draws them inside its own branch: a wave whose lanes hit Disney, metallic and glass surfaces runs the ~225 hash instructions of the
+    // pair up to three times, each time with a part of its shading lanes.  AHEAD: drawn here, by all of them together, it runs them once;
+    // the samplers take the values and move the stream on as they do.  (A lane's unused second draw costs the wave nothing.)
+    float pre_x = 0.0f;
+    f2 pre_xy = f2();
+    if (AHEAD) { CMJState ahead = st; pre_x = cmj_1d(ahead); pre_xy = cmj_2d(ahead); }
+    const f3 bsdf = bsdf_sample<AHEAD>(P, sf, local_wo, local_wi, pdf, st, lambda_wo, pre_x, pre_xy);
     const f3 wi = local_to_world(local_wi, t, n, b);
     ps.thr = ps.thr * ((bsdf * fabsf(dot(wi, n))) / pdf); // rt.h:274
     ps.ro = prd.position;
@@ -727,6 +723,9 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
     // diagnostic build: wave-clock shares of the loop's phases, summed per wave into P.stats[HJR_NSTAT..] (never in the shipped build)
     unsigned long long tk[3] = { 0, 0, 0 }, oc[4] = { 0, 0, 0, 0 }; // rounds, lanes tracing closest, lanes with a shadow ray, lanes serviced
     unsigned long long td[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }; // traversal lane occupancy (hjr_traverse.hip.h): per-lane sums, added up at the end
+    // the four places where a lane draws a 1-D and a 2-D number back to back (light sample, Disney / glass sample, first step of the walk, roulette +
+    // regeneration): rounds that reach the place, and those of them in which the lanes that draw are at most half of the wave
+    unsigned long long ls[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     unsigned long long tstamp = __builtin_amdgcn_s_memtime();
 #define HJR_TICK(i) { __builtin_amdgcn_sched_barrier(0); unsigned long long now_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); tk[i] += now_ - tstamp; tstamp = now_; }
 #else
@@ -736,6 +735,9 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
     constexpr bool HOLD = LDSBVH; // (LDS-resident scenes only: on the 1 M-triangle scene the two extra live registers cost 3 % and the hold gains nothing)
     uint32_t hold = 0u; // > 0: this lane holds a resolved hit of a rare material class back (rounds held so far), see below
     for (;;) {
+#ifdef HJR_TIMING
+        const bool w_roulette = !inflight && (!HOLD || hold == 0u) && c.has_item && c.path_live;
+#endif
         bounce_pre_trace<STATS, AOVS, false, !SINGLE>(P, c, wr, !inflight && (!HOLD || hold == 0u), tracing, lc);
         if (__ballot(!c.dead) == 0ull) break; // a lane only dies with nothing pending
         HJR_TICK(0)
@@ -780,15 +782,34 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
                 if (rare && !run) { hold++; shade = false; tc.phase = 2; tc.cur = HJR_TRAV_DONE; tc.sp = 0; }
             }
         }
+#ifdef HJR_TIMING
+        {
+            bool w_light = false, w_bsdf = false, w_walk = false; // (material classes as the hold-back reads them: the untextured material)
+            if (shade && tracing && h.prim != 0xffffffffu) {
+                const float4* m = mats + f2bits(tris[h.k * HJR_TRI_F4 + 2].z) * HJR_MAT_F4;
+                const float4 m0 = m[0], m3 = m[3];
+                const bool lit = f2bits(m3.x) != 0, glass = f2bits(m3.y) != 0, metal = m0.w > 0.5f;
+                w_light = !lit && INTEGRATOR != HJR_INTEGRATOR_PT_ && P.n_lights >= 1u;
+                w_bsdf = !lit && (glass || !metal);
+                w_walk = !lit && !glass && metal;
+            }
+            const bool w[4] = { w_light, w_bsdf, w_walk, w_roulette };
+            for (int i = 0; i < 4; i++) {
+                const uint32_t n = (uint32_t)__popcll(__ballot(w[i]));
+                if (n) { ls[2 * i] += 1; if (n <= 32u) ls[2 * i + 1] += 1; }
+            }
+        }
+#endif
         if (shade) {
             if (HOLD) hold = 0u;
-            bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, false, !SINGLE>(P, nodes, tris, mats, lights, c, tracing, occluded, h, stack, lc);
+            bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, false, !SINGLE, true>(P, nodes, tris, mats, lights, c, tracing, occluded, h, stack, lc);
         }
         HJR_TICK(2)
     }
 #ifdef HJR_TIMING
     if (lane == 0) for (int i = 0; i < 3; i++) atomicAdd(&P.stats[HJR_NSTAT + i], tk[i]);
     if (__ffsll((long long)__ballot(true)) - 1 == (int)lane) for (int i = 0; i < 4; i++) atomicAdd(&P.stats[HJR_NSTAT + 3 + i], oc[i]);
+    if (lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&P.stats[HJR_NSTAT + 17 + i], ls[i]);
     for (int i = 0; i < 10; i++) {
         unsigned long long v = td[i];
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);

@@ -26,8 +26,8 @@ using hjr::set_error;
 struct WorkArea {
     static constexpr size_t QUEUE_HEAD = 0;                      // uint32 work-queue head (16 bytes)
     static constexpr size_t STATS = 16;                          // HJR_NSTAT uint64 counters (hjr_stats)
-    static constexpr size_t DIAG = STATS + HJR_NSTAT * 8;        // 20 uint64: phase clocks / lane-occupancy sums / watchdog record
-    static constexpr size_t TILE_COUNT = DIAG + 20 * 8;          // 8 uint32 tile-class counters (hjr_aux.hip.h)
+    static constexpr size_t DIAG = STATS + HJR_NSTAT * 8;        // 26 uint64: phase clocks / lane-occupancy sums / draw-site counts / watchdog record
+    static constexpr size_t TILE_COUNT = DIAG + 26 * 8;          // 8 uint32 tile-class counters (hjr_aux.hip.h)
     static constexpr size_t COST_HIST = TILE_COUNT + 32;         // 128 uint32: cost histogram and bucket cursors (hjr_aux.hip.h)
     static constexpr size_t NAN_LIST = COST_HIST + 512;          // uint64 count, then HJR_NAN_LIST located samples
     static constexpr size_t FIREFLY = NAN_LIST + (1 + HJR_NAN_LIST) * 8; // uint64: (pixel, chunk) pairs scaled by hjr_firefly_kernel (hjr_aux.hip.h)

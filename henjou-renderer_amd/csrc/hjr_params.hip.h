@@ -84,3 +84,16 @@ struct KParams {
     float ad_threshold;              // noise_threshold
     uint32_t ad_decide;              // 1: a stop decision is taken after this pass (sample_end < spp, >= min_samples, >= 2 chunks)
 };
+
+// Launch parameters that only the start and the end of a work item need (tile list, queue head, output and chunk-sum pointers, shard
+// geometry) are read from the kernel-argument segment WHERE they are used instead of living in SGPRs for the whole kernel: the render
+// loop keeps ~100 scalar values alive, and every one of these that stays resident pushes another into a VGPR lane (v_writelane at entry,
+// v_readlane at each use: VALU instructions inside the round loop).  The empty asm makes the base pointer opaque, so the compiler can
+// neither hoist the load out of the loop nor merge it with the by-value copy of P.
+template <typename T> HD T cold_param(size_t offset)
+{
+    const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return *reinterpret_cast<const T __attribute__((address_space(4)))*>(ka + offset);
+}
+#define HJR_COLD(field) cold_param<decltype(KParams::field)>(offsetof(KParams, field))
