@@ -35,6 +35,8 @@ typedef struct { float x, y; } f2;
     X(basis_z_pos) X(basis_z_neg) \
     X(cosine_sampling) X(visible_normal) \
     X(lut_unbound) X(lut_bound) \
+    X(lut_u_lo) X(lut_u_hi) X(lut_u_in) X(lut_v_lo) X(lut_v_hi) X(lut_v_in) \
+    X(sky_u_lo) X(sky_u_hi) X(sky_u_in) X(sky_v_lo) X(sky_v_hi) X(sky_v_in) \
     X(disney_eval_thinfilm) X(disney_eval_plain) \
     X(disney_wo_below) X(disney_wo_above) X(disney_lobe_diffuse) X(disney_lobe_specular) X(disney_lobe_clearcoat) X(disney_wi_below) X(disney_wi_above) \
     X(glass_from_inside) X(glass_from_outside) X(glass_reflect) X(glass_refract) X(glass_tir) \
@@ -65,6 +67,11 @@ void hjo_branch_reset(void) { for (int i = 0; i < HJO_B_COUNT; i++) __atomic_sto
 #else
 #define HJO_HIT(n) ((void)0)
 #endif
+/* which edge of a wrapped bilinear lookup a fetch takes, per axis: the first tap wrapped from -1 to the last column / row, the second
+ * tap wrapped to column / row 0, or neither */
+#define HJO_HIT_WRAP(pre, f, i1) do { \
+    if ((f) < 0.0f) HJO_HIT(pre##_lo); else if ((i1) == 0) HJO_HIT(pre##_hi); else HJO_HIT(pre##_in); \
+} while (0)
 /* which of "all components zero / some / none" a light contribution is: the shadow-ray decision of NEE and MIS sees only the first */
 #define HJO_HIT_CONTRIB(pre, c) do { \
     int nz_ = ((c).x == 0.0f) + ((c).y == 0.0f) + ((c).z == 0.0f); \
@@ -448,6 +455,7 @@ void hjo_lut_fetch(const uint8_t* rgba, int w, int h, float u, float v, float* o
     int i0 = (int)fx % w; if (i0 < 0) i0 += w;
     int j0 = (int)fy % h; if (j0 < 0) j0 += h;
     int i1 = (i0 + 1) % w, j1 = (j0 + 1) % h;
+    HJO_HIT_WRAP(lut_u, fx, i1); HJO_HIT_WRAP(lut_v, fy, j1);
     for (int c = 0; c < 3; c++) {
         float t00 = (float)rgba[4 * (j0 * w + i0) + c] * (1.0f / 255.0f);
         float t10 = (float)rgba[4 * (j0 * w + i1) + c] * (1.0f / 255.0f);
@@ -505,6 +513,7 @@ void hjo_sky_fetch(int mm, const float* rgba, int w, int h, const float* d, floa
     int i0 = (int)fx % w; if (i0 < 0) i0 += w;
     int j0 = (int)fy % h; if (j0 < 0) j0 += h;
     int i1 = (i0 + 1) % w, j1 = (j0 + 1) % h;
+    HJO_HIT_WRAP(sky_u, fx, i1); HJO_HIT_WRAP(sky_v, fy, j1);
     float w00 = (1.0f - ax) * (1.0f - ay), w10 = ax * (1.0f - ay), w01 = (1.0f - ax) * ay, w11 = ax * ay;
     for (int c = 0; c < 3; c++)
         out[c] = w00 * rgba[4 * (j0 * w + i0) + c] + w10 * rgba[4 * (j0 * w + i1) + c] + w01 * rgba[4 * (j1 * w + i0) + c] + w11 * rgba[4 * (j1 * w + i1) + c];

@@ -1,6 +1,8 @@
 """Small scenes built to drive the guarded special cases of the shading layer (the multiple-scattering GGX walk, the negative-index
 glass, Disney sampling, p_pow's special returns, the light pick, the zero-contribution test of NEE / MIS).  A handful of triangles
 each, assembled in numpy in the style of tests/table_util.py; frames of at most 32 x 32 at 4 to 32 spp.
+The film_* and sky_* cases bind generated thin-film tables and equirect skies of unlike, odd, one-row and one-column shapes and look
+where the lookups wrap (the counters lut_* / sky_* of the oracle).
 tests/test_shading_branches_host.py proves on the CPU, with the oracle's named branch counters, which branch each case takes;
 tests/test_gpu_shading_branches.py renders the same frames on the GPU against the default oracle."""
 import numpy as np
@@ -110,35 +112,55 @@ class Mesh:
 
 
 class Case:
-    """One frame: scene arrays, camera, size, sample stream, sky and whether the thin-film LUT / an equirect sky is bound."""
+    """One frame: scene arrays, camera, size, sample stream, sky and whether the thin-film LUT / an equirect sky is bound.
+    lut: True binds the bundled table, a uint8 [h, w, 4] array binds that table."""
 
-    def __init__(self, name, arrays, camera, w, h, spp, frame=1, seed=1, sky=(0.05, 0.06, 0.08), lut=False, sky_rgba=None, targets=""):
+    def __init__(self, name, arrays, camera, w, h, spp, frame=1, seed=1, sky=(0.05, 0.06, 0.08), lut=False, sky_rgba=None, targets="",
+                 ibl_intensity=1.0):
         assert w <= 32 and h <= 32 and 4 <= spp <= 32
         self.name, self.arrays, self.camera, self.w, self.h, self.spp = name, arrays, camera, w, h, spp
         self.frame, self.seed, self.sky, self.lut, self.sky_rgba, self.targets = frame, seed, sky, lut, sky_rgba, targets
+        self.ibl_intensity = ibl_intensity
+
+    def variant(self, **kw):
+        """a copy with the given attributes replaced (the scene arrays are shared)"""
+        import copy
+        c = copy.copy(self)
+        for k, v in kw.items():
+            assert hasattr(c, k), k
+            setattr(c, k, v)
+        assert c.w <= 32 and c.h <= 32 and 4 <= c.spp <= 32
+        return c
+
+    def lut_rgba(self):
+        """the table oracle and device get, or None"""
+        if isinstance(self.lut, np.ndarray):
+            return self.lut
+        return load_lut() if self.lut else None
 
     def oracle_arrays(self):
         a = dict(self.arrays)
-        if self.lut:
-            a["lut_rgba"] = load_lut()
+        if self.lut_rgba() is not None:
+            a["lut_rgba"] = self.lut_rgba()
         if self.sky_rgba is not None:
             a["sky_rgba"] = self.sky_rgba
         return a
 
     def oracle_params(self, integrator):
-        return ob.make_params(self.w, self.h, self.spp, self.camera, frame=self.frame, seed=self.seed, integrator=integrator, sky=self.sky)
+        return ob.make_params(self.w, self.h, self.spp, self.camera, frame=self.frame, seed=self.seed, integrator=integrator, sky=self.sky,
+                              ibl_intensity=self.ibl_intensity)
 
     def hjr_params(self, integrator, **kw):
         return hjr.make_params(self.w, self.h, self.spp, self.camera, frame=self.frame, seed=self.seed, integrator=integrator,
-                               sky=self.sky, **kw)
+                               sky=self.sky, ibl_intensity=self.ibl_intensity, **kw)
 
-    def device(self):
-        d = new_device()
+    def device(self, options=None):
+        d = new_device(options)
         try:
             d.upload_arrays(self.arrays)
             d.set_transforms(self.arrays["transforms"], self.arrays["inv_transforms"])
-            if self.lut:
-                d.set_lut(load_lut())
+            if self.lut_rgba() is not None:
+                d.set_lut(self.lut_rgba())
             if self.sky_rgba is not None:
                 d.set_sky(self.sky_rgba)
         except Exception:
@@ -314,6 +336,120 @@ def no_lights():
                 sky=(0.8, 0.7, 0.6), targets="light_none")
 
 
+# ------------------------------------------------------------------ thin-film tables and skies of unlike shapes, at their wrap edges
+FILM_SHAPES = [(1, 1), (1, 7), (7, 1), (3, 5), (5, 3), (2, 64)]  # [h, w]
+SKY_SHAPES = [(3, 7), (7, 3), (1, 1), (1, 5), (5, 1), (32, 64)]
+
+
+def _all_differ(a):
+    """no two rows and no two columns of [h, w, c] are equal"""
+    h, w = a.shape[:2]
+    return len({a[j].tobytes() for j in range(h)}) == h and len({a[:, i].tobytes() for i in range(w)}) == w
+
+
+def film_table(h, w):
+    """A generated thin-film table, uint8 [h, w, 4]: seeded random bytes, R, G and B unlike in every texel, no two rows or columns
+    equal, so that a wrong stride, a swapped size or a swapped channel changes the values fetched."""
+    rng = np.random.default_rng([5, h, w])
+    t = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    t[..., 1] = np.where(t[..., 1] == t[..., 0], t[..., 0] ^ 0x55, t[..., 1])
+    t[..., 2] = np.where((t[..., 2] == t[..., 0]) | (t[..., 2] == t[..., 1]), t[..., 0] ^ t[..., 1] ^ 0xff, t[..., 2])
+    t[..., 3] = 255
+    assert _all_differ(t[..., :3]) and (t[..., 0] != t[..., 1]).all() and (t[..., 1] != t[..., 2]).all() and (t[..., 0] != t[..., 2]).all()
+    return t
+
+
+def sky_table(h, w):
+    """A generated equirect sky, float32 [h, w, 4]: texels drawn from [0, 3), up to three of them 1e4 (a sun), all finite; channels,
+    rows and columns unlike."""
+    rng = np.random.default_rng([6, h, w])
+    t = np.zeros((h, w, 4), F32)
+    t[..., :3] = rng.uniform(0.0, 3.0, (h, w, 3)).astype(F32)
+    for k in rng.choice(h * w, min(3, h * w // 4), replace=False):
+        t[k // w, k % w, int(rng.integers(0, 3))] = 1e4
+    assert np.isfinite(t).all() and _all_differ(t[..., :3])
+    return t
+
+
+# (metallic, roughness) of the eight film strips: Disney (metallic <= 0.5) and, at 0.51, the material the walk samples and Disney evaluates
+FILM_STRIPS = [(0.0, 0.3), (0.51, 0.2), (0.3, 0.5), (0.5, 0.3), (0.51, 0.4), (0.2, 0.25), (0.5, 0.6), (0.0, 0.35)]
+
+
+def film_thickness(w):
+    """basecolor.x (the thickness: the table's u coordinate) of the eight strips for a table of w columns: both ends of [0, 1], the first
+    and the last texel centre, a hair inside each end, and two inner values"""
+    return [F32(x) for x in (0.0, 1.0, 0.5 / w, 1.0 - 0.5 / w, 1e-3, 0.999, 0.37, 0.71)]
+
+
+def film_mesh(m, mat0=0):
+    """eight floor strips of 2 x 16 along z, materials mat0 .. mat0 + 7"""
+    for i in range(8):
+        m.floor(-8 + 2 * i, -8, -6 + 2 * i, 8, mat0 + i)
+
+
+def film_lights(m, mat):
+    """an emitter over the strips, and a low one across their far end that faces the camera: lit from there a strip seen at a grazing
+    angle has its half vector near the normal and the light direction near the plane (cosines near 0: the table's first row)"""
+    m.ceiling(-3, -2, 3, 2, mat, y=5.0)
+    m.quad((-8, 0.05, 8.2), (-8, 0.8, 8.2), (8, 0.8, 8.2), (8, 0.05, 8.2), mat)
+
+
+def film_materials(w):
+    return [material((t, 0.55 + 0.05 * (i % 3), 0.9 - 0.1 * (i % 4)), metallic=mt, roughness=r, thinfilm=True)
+            for i, (t, (mt, r)) in enumerate(zip(film_thickness(w), FILM_STRIPS))]
+
+
+def film(h, w):
+    """Thin-film strips under an emitter, seen from low over the floor so that grazing and near-normal cosines (the table's v coordinate)
+    both occur, with a generated table of shape [h, w] bound."""
+    m = Mesh()
+    film_mesh(m)
+    film_lights(m, 8)
+    return Case("film_%dx%d" % (h, w), m.arrays(film_materials(w) + [LIGHT]), look_at((0, 1.0, -9), (0, 0, 0), 1.2), 32, 24, 8,
+                lut=film_table(h, w), targets="lut_u_* lut_v_*")
+
+
+def sky_mesh(m, mat0=0):
+    """a small diffuse floor with a metallic and a glass patch on it and an emitter over it: materials mat0 .. mat0 + 3"""
+    m.floor(-2, -2, 2, 2, mat0)
+    m.floor(-1.5, -1.5, -0.2, 1.5, mat0 + 1, y=0.01)
+    m.box((0.3, 0.01, -1.2), (1.5, 0.5, 1.2), mat0 + 2)
+    m.ceiling(-0.6, -0.6, 0.6, 0.6, mat0 + 3, y=3.0)
+
+
+SKY_MATERIALS = [material((0.7, 0.6, 0.5), roughness=0.8), material((0.9, 0.85, 0.7), metallic=1.0, roughness=0.25),
+                 material(glass=True, roughness=0.0, ior=1.5), LIGHT]
+# views of the sky scene: most of each frame is open sky
+SKY_VIEWS = {
+    "seam": ((4, 1, 0.3), (-4, 1.2, 0), 1.0, UP),            # along -x: the azimuth seam (u = 0 | 1) runs down the frame
+    "zenith": ((0.05, 0.1, -1.0), (0.05, 30, -0.9), 0.5, (0, 0, 1)),  # up from the floor, the glass box at one side: the rows at v = 0
+    "nadir": ((3.4, 2, 0.2), (3.4, -30, 0.25), 1.0, (0, 0, 1)),   # straight down past the floor's edge: the rows at v = 1
+    "nadir_long": ((2.6, 2, 0.2), (2.6, -30, 0.25), 3.0, (0, 0, 1)),  # the same through a longer lens: within 3 degrees of straight down
+    "side": ((0.5, 1.5, -6), (0, 0.8, 0), 1.5, UP),
+}
+
+
+def sky(h, w, view):
+    """The sky scene under a generated equirect sky of shape [h, w], ibl_intensity 0.75, in one of SKY_VIEWS."""
+    m = Mesh()
+    sky_mesh(m)
+    pos, target, f, up = SKY_VIEWS[view]
+    return Case("sky_%dx%d_%s" % (h, w, view), m.arrays(SKY_MATERIALS), look_at(pos, target, f, up_hint=up), 32, 24, 4,
+                sky_rgba=sky_table(h, w), ibl_intensity=0.75, targets="sky_u_* sky_v_*")
+
+
+def film_under_sky():
+    """The film strips (5 x 3 table) under an open 3 x 7 sky instead of a dark constant one, seen along -x over the strips so that the
+    azimuth seam crosses the frame: both lookups in one frame.  tests/test_gpu_lookups.py renders it on every kernel layout."""
+    m = Mesh()
+    film_mesh(m)
+    film_lights(m, 8)
+    return Case("film_under_sky", m.arrays(film_materials(3) + [LIGHT]), look_at((7, 1.2, -7), (-6, 0.3, 0), 1.2), 32, 24, 4,
+                lut=film_table(5, 3), sky_rgba=sky_table(3, 7), ibl_intensity=0.75, targets="lut_u_* lut_v_* sky_u_*")
+
+
+SKY_CASES = [(3, 7, "seam"), (7, 3, "zenith"), (1, 1, "side"), (1, 5, "seam"), (5, 1, "nadir"), (32, 64, "nadir_long")]
+
 _cases = None
 
 
@@ -323,6 +459,7 @@ def cases():
     if _cases is None:
         lst = [head_on_mirror(), grazing_lens(), rough_metal_pit(), glass(), shading_normals(), coloured_lights(), many_lights(),
                thin_film(True), thin_film(False), no_lights(), nan_normal()] + [unit_draw(*sd) for sd in UNIT_DRAWS]
+        lst += [film(h, w) for h, w in FILM_SHAPES] + [sky(*hwv) for hwv in SKY_CASES] + [film_under_sky()]
         _cases = {c.name: c for c in lst}
     return _cases
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+import shading_cases as sc
 from scene_util import Cornell, hjr
 
 L = ob.lib()
@@ -147,3 +148,54 @@ def test_oracle_normal_map(tmp_path):
     changed = np.any(a_nrm[..., :3] != b_nrm[..., :3], axis=-1)
     assert 0.05 < changed.mean() < 0.95
     assert np.allclose(np.linalg.norm(a_nrm[changed][:, :3], axis=-1), 1.0, atol=1e-5)
+
+
+# ------------------------------------------------------------------ the sky lookup against a float64 restatement, at unlike shapes
+F32 = np.float32
+
+
+def sky_uv(d):
+    """(u, v) of the direction as hjo_sky_fetch computes them in its PORTABLE mode: the same float32 operations on the oracle's own
+    exported p_atan2 / p_acos, so that the trigonometry cannot move a point across a texel boundary"""
+    d = [F32(x) for x in d]
+    u = F32(F32(F32(L.hjo_p_atan2(float(d[2]), float(d[0]))) * F32(0.15915494309189533577)) + F32(0.5))
+    v = F32(F32(L.hjo_p_acos(float(min(max(d[1], F32(-1.0)), F32(1.0))))) * F32(0.31830988618379067154))
+    return u, v
+
+
+def sky_directions(h, w, seed):
+    """the azimuth seam from both sides, zenith and nadir, the axes, and 300 seeded random unit vectors (float32)"""
+    from test_oracle_lut import clear_of_weight_steps
+    fixed = [(-1, 0, 1e-7), (-1, 0, -1e-7), (0, 1, 0), (0, -1, 0), (1, 0, 0), (-1, 0, 0), (0, 0, 1), (0, 0, -1)]
+    assert all(clear_of_weight_steps(*sky_uv(d), w, h) for d in fixed)
+    rng = np.random.default_rng([seed, h, w])
+    rand = []
+    while len(rand) < 300:
+        d = rng.normal(size=3)
+        d = (d / np.linalg.norm(d)).astype(F32)
+        if clear_of_weight_steps(*sky_uv(d), w, h):
+            rand.append(tuple(d))
+    return fixed + rand
+
+
+@pytest.mark.parametrize("shape", sc.SKY_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_sky_fetch_equals_float64_rule_at_unlike_shapes(shape):
+    """hjo_sky_fetch (PORTABLE) on the generated skies of tests/shading_cases.py (3 x 7, 7 x 3: taller than wide, 1 x 1, one row, one
+    column, 32 x 64; texels in [0, 3) and a few of 1e4) against test_oracle_lut.bilinear_f64 at the (u, v) of sky_uv.
+
+    Tolerance, from the float32 expression: texels are float32 and the weights multiples of 2^-16, both exact; the four weight * texel
+    products round once each, and as the weights sum to 1 their errors sum to at most one rounding of the largest tap; three additions
+    of partial sums that never exceed the largest tap.  1 + 3 = 4 roundings of 2^-24 relative to the largest tap of the fetch."""
+    from test_oracle_lut import bilinear_f64
+    h, w = shape
+    sky = sc.sky_table(h, w)
+    seam = set()
+    for d in sky_directions(h, w, 22):
+        u, v = sky_uv(d)
+        want, tmax = bilinear_f64(sky, 1.0, u, v)
+        o = ob.F3()
+        L.hjo_sky_fetch(ob.MATH_PORTABLE, sky.ctypes.data, w, h, ob.F3(*[float(x) for x in d]), o)
+        got = np.array(o, np.float64)
+        assert np.abs(got - want).max() <= 4 * 2.0 ** -24 * tmax, (shape, d, got, want)
+        seam.add(int(np.floor(float(u) * w - 0.5)) // max(w, 1))
+    assert {-1, 0} <= seam  # the first tap of some direction wrapped from column -1, that of others did not
