@@ -35,6 +35,15 @@ struct HitInfo { // the Payload fields the integrators read (kernel/Payload.h:12
     uint32_t k; // row of the hit triangle in tri_geom (leaf order)
 };
 
+// Material class of the hit on triangle row k, read off the UNTEXTURED material: 0 light, 1 Disney, 2 metallic (multiple-scattering GGX), 3 glass.
+// A scheduling hint (wavefront SHADE queues, the megakernel's hold-back, the HJR_TIMING draw-site counts): never an input of shading.
+HD uint32_t material_class(const float4* tris, const float4* mats, uint32_t k)
+{
+    const float4* m = mats + f2bits(tris[k * HJR_TRI_F4 + 2].z) * HJR_MAT_F4;
+    const float4 m0 = m[0], m3 = m[3];
+    return f2bits(m3.x) != 0 ? 0u : (f2bits(m3.y) != 0 ? 3u : (m0.w > 0.5f ? 2u : 1u));
+}
+
 // __closesthit__ch / __miss__ms for a finished closest-hit traversal
 template <bool STATS, bool FULL>
 HD void hit_program(const KParams& P, const float4* tris, const float4* mats, const Hit& h, const f3 rd, HitInfo& prd, unsigned long long* lc)
@@ -675,6 +684,38 @@ HD void stage_scene_in_lds(const KParams& P, float4* base, const float4*& nodes,
     nodes = l_nodes; tris = l_tris; mats = l_mats; lights = l_lights;
 }
 
+// first float4 behind the lanes' LDS stack columns of `entries` entries each (the dynamic LDS starts with the stacks)
+template <typename SE, int BLOCK> HD float4* lds_behind_stacks(const uint32_t entries) { return hjr_smem + (BLOCK * entries * (uint32_t)sizeof(SE) + 15u) / 16u; }
+
+// What every kernel that traverses under a launch plan does first (the two render kernels and the ray-batch test hook, hjr_trace_hook.hip.h):
+// the lane's stack — its LDS column at the start of the dynamic LDS, its column of the overflow buffer — and, at `behind` (lds_behind_stacks
+// of the layout's column length), the scene tables of an LDS-resident layout or (TOP: memory layout, BVH4) the copy of the top of the tree.
+// All threads of the workgroup; a barrier inside when anything is staged.
+template <int BLOCK, bool LDSBVH, bool TOP, typename ST>
+HD void kernel_prologue(const KParams& P, ST& stack, float4* behind, const float4*& nodes, const float4*& tris, const float4*& mats, const float4*& lights)
+{
+    typedef typename std::remove_pointer<decltype(stack.lds)>::type SE;
+    stack.n_over = 0;
+    stack.lds = reinterpret_cast<SE*>(hjr_smem) + threadIdx.x;
+    stack.spill = P.stack_spill + (blockIdx.x * BLOCK + threadIdx.x);
+    stack.spill_stride = P.spill_stride;
+    stack.lds_n = (int)P.stack_lds_entries;
+    stack.top = nullptr; stack.n_top = 0u;
+    nodes = P.nodes; tris = P.tri_geom; mats = P.materials; lights = P.lights;
+    if (LDSBVH) stage_scene_in_lds<SE, BLOCK>(P, behind, nodes, tris, mats, lights);
+    else if (TOP && P.n_top_nodes) {
+        for (uint32_t i = threadIdx.x; i < P.n_top_nodes * HJR_NODE4_F4; i += BLOCK) behind[i] = P.nodes[i];
+        __syncthreads();
+        stack.top = behind; stack.n_top = P.n_top_nodes;
+    }
+}
+
+// the wave's sum of v, in its lane 0 (the ray-batch hook's overflow count, the HJR_TIMING sums)
+HD unsigned long long wave_sum(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
 // ------------------------------------------------------------------ the megakernel
 // VAR: 0 = lean (colour only, untextured scene, constant sky), 1 = + albedo / normal AOV sums, 2 = + material textures, normal maps
 // and the equirect sky texture.  Each step costs registers (NEE, LDS layout: 20 / 25 / 48 VGPR spills), so a launch gets the
@@ -689,25 +730,11 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
     constexpr bool AOVS = VAR >= 1, TEX = VAR == 2;
     typedef typename std::conditional<STACK16, uint16_t, uint32_t>::type SE; // stack entry type
     typedef LaneStack<SE, BLOCK, !LDSBVH, STATS, LDSBVH> ST;
-    ST stack; // (this set-up, down to the `top` copy, is restated in hjr_trace_hook.hip.h::TraceLayout::setup for the ray-batch test hook: change both)
-    stack.n_over = 0;
-    stack.lds = reinterpret_cast<SE*>(hjr_smem) + threadIdx.x;
-    stack.spill = P.stack_spill + (blockIdx.x * BLOCK + threadIdx.x);
-    stack.spill_stride = P.spill_stride;
-    stack.lds_n = (int)P.stack_lds_entries;
-    stack.top = nullptr; stack.n_top = 0u;
+    ST stack;
+    const float4 *nodes, *tris, *mats, *lights;
+    // LDS layouts: whole stacks, then the scene tables; memory layouts: the short stacks, then (BVH4) the top of the breadth-first tree
+    kernel_prologue<BLOCK, LDSBVH, WIDTH == 4>(P, stack, lds_behind_stacks<SE, BLOCK>(LDSBVH ? P.stack_depth : P.stack_lds_entries), nodes, tris, mats, lights);
     const uint32_t lane = threadIdx.x & 63u;
-    const float4* nodes = P.nodes;
-    const float4* tris = P.tri_geom;
-    const float4* mats = P.materials;
-    const float4* lights = P.lights;
-    if (LDSBVH) stage_scene_in_lds<SE, BLOCK>(P, hjr_smem + (BLOCK * P.stack_depth * (uint32_t)sizeof(SE) + 15u) / 16u, nodes, tris, mats, lights);
-    else if (WIDTH == 4 && P.n_top_nodes) { // memory layout: the top of the (breadth-first) BVH4 behind the short stacks
-        float4* top = hjr_smem + (BLOCK * P.stack_lds_entries * (uint32_t)sizeof(SE) + 15u) / 16u;
-        for (uint32_t i = threadIdx.x; i < P.n_top_nodes * HJR_NODE4_F4; i += BLOCK) top[i] = P.nodes[i];
-        __syncthreads();
-        stack.top = top; stack.n_top = P.n_top_nodes;
-    }
 
     unsigned long long lc[HJR_NSTAT];
     if (STATS) for (int i = 0; i < HJR_NSTAT; i++) lc[i] = 0;
@@ -770,12 +797,7 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
         // the same way was measured too: 127.4 vs 126.4 ms, its sampling code is short.)
         bool shade = !inflight;
         if (HOLD && P.hold_min) {
-            bool rare = false;
-            if (shade && tracing && h.prim != 0xffffffffu) {
-                const float4* m = mats + f2bits(tris[h.k * HJR_TRI_F4 + 2].z) * HJR_MAT_F4;
-                const float4 m0 = m[0], m3 = m[3];
-                rare = f2bits(m3.x) == 0 && f2bits(m3.y) == 0 && m0.w > 0.5f; // not a light, not glass, metallic
-            }
+            const bool rare = shade && tracing && h.prim != 0xffffffffu && material_class(tris, mats, h.k) == 2u; // not a light, not glass, metallic
             const uint32_t n_rare = (uint32_t)__popcll(__ballot(rare));
             if (n_rare) {
                 const bool run = n_rare >= P.hold_min || __ballot(rare && hold >= P.hold_age) != 0ull || __ballot(shade && !rare) == 0ull;
@@ -786,12 +808,10 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
         {
             bool w_light = false, w_bsdf = false, w_walk = false; // (material classes as the hold-back reads them: the untextured material)
             if (shade && tracing && h.prim != 0xffffffffu) {
-                const float4* m = mats + f2bits(tris[h.k * HJR_TRI_F4 + 2].z) * HJR_MAT_F4;
-                const float4 m0 = m[0], m3 = m[3];
-                const bool lit = f2bits(m3.x) != 0, glass = f2bits(m3.y) != 0, metal = m0.w > 0.5f;
-                w_light = !lit && INTEGRATOR != HJR_INTEGRATOR_PT_ && P.n_lights >= 1u;
-                w_bsdf = !lit && (glass || !metal);
-                w_walk = !lit && !glass && metal;
+                const uint32_t cls = material_class(tris, mats, h.k);
+                w_light = cls != 0u && INTEGRATOR != HJR_INTEGRATOR_PT_ && P.n_lights >= 1u;
+                w_bsdf = cls == 1u || cls == 3u;
+                w_walk = cls == 2u;
             }
             const bool w[4] = { w_light, w_bsdf, w_walk, w_roulette };
             for (int i = 0; i < 4; i++) {
@@ -811,13 +831,12 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
     if (__ffsll((long long)__ballot(true)) - 1 == (int)lane) for (int i = 0; i < 4; i++) atomicAdd(&P.stats[HJR_NSTAT + 3 + i], oc[i]);
     if (lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&P.stats[HJR_NSTAT + 17 + i], ls[i]);
     for (int i = 0; i < 10; i++) {
-        unsigned long long v = td[i];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        const unsigned long long v = wave_sum(td[i]);
         if (lane == 0 && v) atomicAdd(&P.stats[HJR_NSTAT + 7 + i], v);
     }
 #endif
 
-    if (STATS) {
+    if (STATS) { // (written out in both render kernels: with the sum in a helper, wave_sum included, every counting kernel came out rescheduled)
         lc[10] = stack.n_over;
         for (int i = 0; i < HJR_NSTAT; i++) {
             unsigned long long v = lc[i];

@@ -1,6 +1,6 @@
 // Ray-batch test hook (hjr_trace_rays, include/henjou_hip.h): kernels that hand caller-chosen rays to the traversal of the render kernels.
-// Nothing of the traversal is restated here: the kernels build the LaneStack of the layout, stage the scene as hjr_render_kernel does
-// (stage_scene_in_lds, the BVH4 `top` copy) and call traverse<> / traverse_fused<> of hjr_traverse.hip.h as they are.  Two translation units
+// Nothing of the traversal or of a kernel's set-up is restated here: the kernels run hjr_render_kernel's prologue (hjr_kernel.hip.h::kernel_prologue:
+// the LaneStack of the layout, the scene staging, the BVH4 `top` copy) and call traverse<> / traverse_fused<> of hjr_traverse.hip.h as they are.  Two translation units
 // instantiate them: hjr_launch_trace.hip with the exact flags and hjr_launch_fast_trace.hip with the Makefile's FASTFLAGS (HJR_TRACE_FAST_BUILD),
 // which is how "the traversal and the triangle test are the same operations in every build" is checked ray by ray.
 // Included by those two units and by hjr_device.hip only: no render kernel sees this header.
@@ -18,35 +18,18 @@ struct TraceArgs {
     unsigned long long* n_over;  // stack pushes that went to the HBM overflow, summed over the grid
 };
 
-// the lane's stack and scene pointers, set up exactly as hjr_render_kernel does for the layout (COUNT = true: overflow pushes are counted)
-// (restated from hjr_kernel.hip.h::hjr_render_kernel, which carries a note to change both: sharing one function between the two was tried and
-// changed the render units' objects, which this hook must not do)
+// the lane's stack and scene pointers: hjr_render_kernel's own prologue, called as that kernel calls it (COUNT = true: overflow pushes are counted)
 template <int BLOCK, bool LDSBVH, bool STACK16, int WIDTH> struct TraceLayout {
     typedef typename std::conditional<STACK16, uint16_t, uint32_t>::type SE;
     typedef LaneStack<SE, BLOCK, !LDSBVH, true, LDSBVH> ST;
     static HD void setup(const KParams& P, ST& stack, const float4*& nodes, const float4*& tris)
     {
-        stack.n_over = 0;
-        stack.lds = reinterpret_cast<SE*>(hjr_smem) + threadIdx.x;
-        stack.spill = P.stack_spill + (blockIdx.x * BLOCK + threadIdx.x);
-        stack.spill_stride = P.spill_stride;
-        stack.lds_n = (int)P.stack_lds_entries;
-        stack.top = nullptr; stack.n_top = 0u;
-        nodes = P.nodes; tris = P.tri_geom;
-        const float4* mats = P.materials;
-        const float4* lights = P.lights;
-        if (LDSBVH) stage_scene_in_lds<SE, BLOCK>(P, hjr_smem + (BLOCK * P.stack_depth * (uint32_t)sizeof(SE) + 15u) / 16u, nodes, tris, mats, lights);
-        else if (WIDTH == 4 && P.n_top_nodes) {
-            float4* top = hjr_smem + (BLOCK * P.stack_lds_entries * (uint32_t)sizeof(SE) + 15u) / 16u;
-            for (uint32_t i = threadIdx.x; i < P.n_top_nodes * HJR_NODE4_F4; i += BLOCK) top[i] = P.nodes[i];
-            __syncthreads();
-            stack.top = top; stack.n_top = P.n_top_nodes;
-        }
+        const float4 *mats, *lights;
+        kernel_prologue<BLOCK, LDSBVH, WIDTH == 4>(P, stack, lds_behind_stacks<SE, BLOCK>(LDSBVH ? P.stack_depth : P.stack_lds_entries), nodes, tris, mats, lights);
     }
     static HD void flush_overflow(const ST& stack, unsigned long long* n_over)
     {
-        unsigned long long v = stack.n_over;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        const unsigned long long v = wave_sum(stack.n_over);
         if ((threadIdx.x & 63u) == 0u && v) atomicAdd(n_over, v);
     }
 };

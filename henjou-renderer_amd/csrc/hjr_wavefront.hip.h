@@ -22,6 +22,9 @@
 // What it buys (profiles/r02_experiments.md): 50 % active lanes and 20 % fewer VALU instructions than the megakernel, paid back in waits
 // at the stage boundaries.  It wins where the shading pass is long — MIS: 187 vs 222 ms on the bundled scene, 417 vs 635 ms on 1 M
 // triangles — and hjr_launch() selects it there; NEE and Pathtrace run faster on the megakernel.
+// Shared with the megakernel besides the bounce code: the kernel's set-up (hjr_kernel.hip.h::kernel_prologue) and the class test of the SHADE
+// queues (material_class).  The trace stage keeps its own copy of the traversal pass of hjr_traverse.hip.h::traverse_fused: the two agree line
+// for line, and as one function they cost registers and 1 % of MIS; tests/test_gpu_traversal_counters.py holds them together.
 #pragma once
 #include "hjr_kernel.hip.h"
 
@@ -284,12 +287,7 @@ HD void wf_trace_stage(const KParams& P, WfShared* Q, wf_ring_ptr rings, const f
     // a lane's rays are done: hit record -> slot 7 of the context record (.x of the slot belongs to the SHADE stage), context noted for the hand-over
     auto finish = [&]() {
         uint32_t kk = WF_MISS, cls = 0u;
-        if (hit.prim != 0xffffffffu) {
-            kk = hit.k;
-            const float4* m = mats + f2bits(tris[hit.k * HJR_TRI_F4 + 2].z) * HJR_MAT_F4;
-            const float4 m0 = m[0], m3 = m[3];
-            cls = f2bits(m3.x) != 0 ? 0u : (f2bits(m3.y) != 0 ? 3u : (m0.w > 0.5f ? 2u : 1u)); // light | glass | metallic (msGGX) | Disney
-        }
+        if (hit.prim != 0xffffffffu) { kk = hit.k; cls = material_class(tris, mats, hit.k); }
         float* hp = reinterpret_cast<float*>(ctx + (size_t)id * CTXF4 + 7) + 1;
         hp[0] = hit.b1; hp[1] = hit.b2; hp[2] = bits2f(kk | (occluded ? 0x80000000u : 0u));
         const uint32_t e = (id + 1u) | (cls << 16);
@@ -442,18 +440,9 @@ __global__ void __launch_bounds__(BLOCK, 1) hjr_wavefront_kernel(const KParams P
     typedef uint32_t SE;
     typedef LaneStack<SE, BLOCK, SPILL, STATS, LDSBVH, false> ST; // (last: the branch-free shape of the triangle test)
     ST stack;
-    stack.n_over = 0;
-    stack.lds = reinterpret_cast<SE*>(hjr_smem) + threadIdx.x;
-    stack.spill = P.stack_spill + (blockIdx.x * BLOCK + threadIdx.x);
-    stack.spill_stride = P.spill_stride;
-    stack.lds_n = (int)P.stack_lds_entries;
-    stack.top = nullptr; stack.n_top = 0u;
+    const float4 *nodes, *tris, *mats, *lights;
     const uint32_t lane = threadIdx.x & 63u;
-    const float4* nodes = P.nodes;
-    const float4* tris = P.tri_geom;
-    const float4* mats = P.materials;
-    const float4* lights = P.lights;
-    float4* after_stacks = hjr_smem + (BLOCK * P.stack_lds_entries * (uint32_t)sizeof(SE) + 15u) / 16u;
+    float4* after_stacks = lds_behind_stacks<SE, BLOCK>(P.stack_lds_entries);
     const uint32_t scene_f4 = LDSBVH ? (P.n_node_f4 + P.n_tri_f4 + P.n_mat_f4 + P.n_light_f4) : 0u;
     WfShared* Q = reinterpret_cast<WfShared*>(after_stacks + scene_f4);
     wf_ring_ptr rings = (wf_ring_ptr)(after_stacks + scene_f4 + 6); // the header takes 96 bytes
@@ -473,7 +462,9 @@ __global__ void __launch_bounds__(BLOCK, 1) hjr_wavefront_kernel(const KParams P
     float4* ctx = P.wf_ctx + (size_t)blockIdx.x * cap * CTXF4;
     for (uint32_t i = threadIdx.x; i < cap * CTXF4; i += BLOCK) // every context starts with all flags clear but `fresh`
         ctx[i] = (i % CTXF4 == 1u) ? make_float4(0.0f, 0.0f, 0.0f, bits2f(WF_FRESH)) : ((i % CTXF4 == 7u) ? make_float4(0.0f, 0.0f, 0.0f, bits2f(WF_MISS)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    if (LDSBVH) stage_scene_in_lds<SE, BLOCK>(P, after_stacks, nodes, tris, mats, lights); // ends with a barrier
+    // the shared prologue, without a `top` copy (behind the stacks and the scene tables lie the queues).  It stands where the staging always
+    // stood, behind the queue and context set-up: at the top of the kernel the whole kernel was scheduled differently and MIS ran 1 % slower
+    kernel_prologue<BLOCK, LDSBVH, false>(P, stack, after_stacks, nodes, tris, mats, lights);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -540,7 +531,7 @@ __global__ void __launch_bounds__(BLOCK, 1) hjr_wavefront_kernel(const KParams P
     if (lane == 0u) for (int i = 0; i < 19; i++) atomicAdd(&wf_diag[i], tdiag[i]);
 #endif
 
-    if (STATS) {
+    if (STATS) { // (written out in both render kernels: with the sum in a helper, wave_sum included, every counting kernel came out rescheduled)
         lc[10] = stack.n_over;
         for (int i = 0; i < HJR_NSTAT; i++) {
             unsigned long long v = lc[i];
