@@ -7,9 +7,17 @@
 #include <string>
 #include <utility>
 
+// Owns its allocation.  The one condition: a DevBuf is destroyed (or released, or moved onto) with its device current, which every entry
+// point and hjr_destroy see to before they touch a context.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { release(); swap(o); return *this; }
+    ~DevBuf() { release(); }
     template <class T> T* as() const { return static_cast<T*>(p); }
     // grow without copying to exactly `bytes` (the old contents are lost); *grown tells whether the buffer was reallocated
     bool reserve(size_t bytes, bool* grown = nullptr)
@@ -69,9 +77,9 @@ struct DeviceBvh {
         uint32_t tag = 0, k = 0;      // build tag it was built under, non-empty instances
         float ms = 0.0f;              // HIP-event time of its build
     } topo;
-    void drop_topology();
+    void drop_topology() { topo = Topology(); }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    void release();
+    void release(); // what is not a DevBuf: the events (the buffers go with the struct)
 };
 
 struct DeviceBvhResult {

@@ -1520,24 +1520,10 @@ namespace hjr {
 
 void DeviceBvh::release()
 {
-    for (DevBuf* x : { &stage, &vert, &norm, &uv, &idx, &mat, &prim_off, &xf, &wv, &box, &cent, &keys[0], &keys[1], &vals[0], &vals[1], &hist, &part, &leaf_box,
-                       &inner_box, &inner_child, &inner_range, &parent, &counter, &frontier[0], &frontier[1], &wide, &hdr, &node_count, &node_cost, &leaf_pos,
-                       &nodes, &tri_geom, &tri_shade, &tri_inst, &lights })
-        x->release();
-    drop_topology();
     have_scene = false;
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     ev0 = ev1 = nullptr;
-}
-
-void DeviceBvh::drop_topology()
-{
-    for (DevBuf* x : { &topo.child, &topo.range, &topo.parent, &topo.pos, &topo.order, &topo.top, &topo.top_ids, &topo.root, &topo.list, &topo.bounds,
-                       &topo.skel_refs, &topo.skel_parent, &topo.inst_ref, &topo.inst_stat, &topo.top_box })
-        x->release();
-    topo.valid = topo.graft = topo.skel_deep = false;
-    topo.k = topo.n_skel = 0;
 }
 
 #define DCHK(call)                                                                                           \

@@ -33,6 +33,45 @@
         }                                                                                                       \
     } while (0)
 
+// behind the last launch of a function: the runtime's verdict on what was enqueued
+static int launched() { HIPCHK(hipGetLastError()); return HJR_OK; }
+// the stream an entry point enqueues on: the caller's, or the context's own
+static hipStream_t stream_of(const hjr_ctx* c, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : c->stream; }
+// grid of the image kernels: 256 threads take 64 x 4 pixels
+static dim3 image_grid(uint32_t w, uint32_t h) { return dim3((w + 63) / 64, (h + 3) / 4); }
+// the sized hjr_params of entry point `who`, whose name the refusals carry; false: HJR_ERR_ARG
+static bool take_params(const hjr_ctx* c, const hjr_params* p_user, hjr_params& p, const char* who)
+{
+    if (!c) { set_error(std::string(who) + ": null context"); return false; }
+    return hjr::abi_take(p_user, p, who);
+}
+// LaunchPlan::lds_mode of frame data: the builder's 0 BVH4 in memory, 1 / 2 BVH2 staged in LDS, and 3 for a BVH2 it left in memory
+static int launch_layout(const hjr::FrameData& f) { return f.lds_mode == 0 && f.width == 2 ? 3 : f.lds_mode; }
+
+// Host buffers through device buffers on the context's stream: every entry point that takes host image pointers.  Uploads, the caller's
+// launch (into `rc`) and downloads each happen only while everything before them succeeded; finish() drains the stream on every path, so no
+// such entry point returns while a copy it enqueued is in flight, and folds the first error.  `buf` is the temporary buffer of the entry
+// points that stage through no context-owned one (empty for the others), released only after the stream has drained.
+struct HostStage {
+    hjr_ctx* c;
+    DevBuf buf;
+    int rc = HJR_OK;           // of the launch
+    hipError_t e = hipSuccess; // the first failed runtime call
+    explicit HostStage(hjr_ctx* c_) : c(c_) {}
+    bool ok() const { return rc == HJR_OK && e == hipSuccess; }
+    void up(void* dst, const void* src, size_t n) { if (ok() && n) e = hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream); }
+    void down(void* dst, const void* src, size_t n) { if (ok() && n) e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream); }
+    int finish(const char* who)
+    {
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        buf.release(); // explicitly, behind the drain
+        if (rc != HJR_OK) return rc;
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) { set_error(std::string(who) + ": " + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
+        return HJR_OK;
+    }
+};
+
 extern "C" int hjr_create(int device, hjr_ctx** out)
 {
     if (!out) { set_error("hjr_create: null out pointer"); return HJR_ERR_ARG; }
@@ -106,11 +145,13 @@ extern "C" void hjr_destroy(hjr_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    c->release_buffers();
+    if (c->ad.h_active) (void)hipHostFree(c->ad.h_active);
+    if (c->ad.ready) (void)hipEventDestroy(c->ad.ready);
+    c->dbvh.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c; // every DevBuf of the context, with its device still current
 }
 
 extern "C" int hjr_upload_scene(hjr_ctx* c, const hjr_scene_view* v)
@@ -156,8 +197,8 @@ extern "C" int hjr_upload_scene(hjr_ctx* c, const hjr_scene_view* v)
 
 // updateIASMatrix + buildIAS (renderer.h:257-291, 398-490) in two halves, so that a frame loop can prepare frame f + 1 on the
 // host (worker threads, no device access, no access to what a running render reads) while frame f renders:
-//   hjr_prepare_transforms: flatten + BVH build into the context's PENDING frame data;
-//   hjr_commit_transforms:  upload the pending data (after the previous render has finished) and make it current.
+//   hjr_prepare_transforms: flatten + BVH build into the context's prepared frame (hjr_ctx::prep);
+//   hjr_commit_transforms:  upload the prepared data (after the previous render has finished) and make it current (hjr_ctx::built).
 // hjr_set_transforms = prepare + commit.
 extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* inv, uint32_t n)
 {
@@ -176,34 +217,36 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
         set_error("hjr_set_transforms: \"device_bvh\" builds the BVH4 memory layout only; it cannot be combined with \"bvh_width\" 2 or \"lds_bvh\" 1");
         return HJR_ERR_ARG;
     }
-    const uint32_t build_tag = (bo.allow_lds ? 1u : 0u) | (bo.prefer_stack16 ? 2u : 0u) | ((uint32_t)(bo.bvh_width + 1) << 2) | ((uint32_t)(bo.leaf_max + 1) << 6) | ((uint32_t)(bo.refine + 1) << 10) | (device ? 1u << 16 : 0u) |
-                               (device ? (uint32_t)c->opt.get(hjr::OPT_DEVICE_BVH_OPT, 0) << 17 : 0u) |
-                               (device && c->opt.get(hjr::OPT_DEVICE_BVH_INSTANCES, 0) ? 1u << 19 : 0u) |
-                               (device && c->opt.get(hjr::OPT_DEVICE_BVH_INSTANCES, 0) && c->opt.get(hjr::OPT_DEVICE_BVH_GRAFT, 0) ? 1u << 20 : 0u);
-    c->pending_valid = false;
-    c->pending_same = false;
+    BuildKey key;
+    key.allow_lds = bo.allow_lds; key.prefer_stack16 = bo.prefer_stack16; key.bvh_width = bo.bvh_width; key.leaf_max = bo.leaf_max; key.refine = bo.refine;
+    key.device = device;
+    key.opt_rounds = device ? (uint32_t)c->opt.get(hjr::OPT_DEVICE_BVH_OPT, 0) : 0u;
+    key.instances = device && c->opt.get(hjr::OPT_DEVICE_BVH_INSTANCES, 0) != 0;
+    key.graft = key.instances && c->opt.get(hjr::OPT_DEVICE_BVH_GRAFT, 0) != 0;
+    hjr_ctx::Prepared& pp = c->prep;
+    pp.valid = false;
+    pp.same = false;
     // unchanged instance transforms (static geometry, e.g. a camera-only animation): the world-space arrays and the BVH of the
     // previous frame are still right; the reference re-uploads its IAS every frame (renderer.h:257-291), which costs it nothing
     const bool force_rebuild = c->opt.get(hjr::OPT_FORCE_REBUILD, 0) != 0; // benchmarking option
-    if (!force_rebuild && c->have_frame && c->last_build_tag == build_tag && c->last_m.size() == (size_t)n * 12 && n == c->scene.n_instances &&
-        (n == 0 || (memcmp(c->last_m.data(), m, (size_t)n * 48) == 0 && memcmp(c->last_inv.data(), inv, (size_t)n * 48) == 0))) {
-        c->pending_same = true;
-        c->pending_valid = true;
+    if (!force_rebuild && c->have_frame && c->built.key == key && c->built.m.size() == (size_t)n * 12 && n == c->scene.n_instances &&
+        (n == 0 || (memcmp(c->built.m.data(), m, (size_t)n * 48) == 0 && memcmp(c->built.inv.data(), inv, (size_t)n * 48) == 0))) {
+        pp.same = true;
+        pp.valid = true;
         return HJR_OK;
     }
     const auto t_build0 = std::chrono::steady_clock::now();
     if (device) { // validation and the light table here; flatten + BVH at the commit, on the device
         if (n != c->scene.n_instances) { set_error("hjr_set_transforms: instance count does not match the uploaded scene"); return HJR_ERR_ARG; }
-        c->pending = hjr::FrameData();
-        c->pending.n_tris = c->scene.n_triangles;
-        c->pending.width = 4;
-        c->pending.lds_mode = 0;
-        hjr::build_lights(c->scene, m, inv, c->pending);
-    } else if (!hjr::build_frame(c->scene, m, inv, n, bo, c->pending, err)) { set_error("hjr_set_transforms: " + err); return HJR_ERR_ARG; }
-    c->pending_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-    c->pending_device = device;
-    c->pending_m.assign(m, m + (size_t)n * 12); c->pending_inv.assign(inv, inv + (size_t)n * 12); c->pending_build_tag = build_tag;
-    c->pending_valid = true;
+        pp.frame = hjr::FrameData();
+        pp.frame.n_tris = c->scene.n_triangles;
+        pp.frame.width = 4;
+        pp.frame.lds_mode = 0;
+        hjr::build_lights(c->scene, m, inv, pp.frame);
+    } else if (!hjr::build_frame(c->scene, m, inv, n, bo, pp.frame, err)) { set_error("hjr_set_transforms: " + err); return HJR_ERR_ARG; }
+    pp.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
+    pp.m.assign(m, m + (size_t)n * 12); pp.inv.assign(inv, inv + (size_t)n * 12); pp.key = key;
+    pp.valid = true;
     return HJR_OK;
 }
 
@@ -212,27 +255,28 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
 // failed build leaves the previous frame current.
 // Option "device_bvh_refit": up to that many consecutive commits after a full build keep its topology and refit the boxes
 // (hjr::device_bvh_refit), while the current data is a device build of this scene with these build options and the cost guard holds.
-static int commit_device(hjr_ctx* c)
+// `instances`: the instance subtrees the build made (0: an ordinary build or a refit), for hjr_stats and the verbose line.
+static int commit_device(hjr_ctx* c, uint32_t& instances)
 {
     const int leaf_max = c->opt.get(hjr::OPT_LEAF_MAX, (int)HJR_LEAF_DEFAULT);
     const int opt_rounds = c->opt.get(hjr::OPT_DEVICE_BVH_OPT, 0); // option "device_bvh_opt": treelet-restructuring rounds
     const uint32_t limit = (uint32_t)c->opt.get(hjr::OPT_DEVICE_BVH_REFIT, 0);
-    const uint32_t n_inst = (uint32_t)(c->pending_m.size() / 12);
+    hjr_ctx::Prepared& pp = c->prep;
+    const uint32_t n_inst = (uint32_t)(pp.m.size() / 12), tag = pp.key.pack();
     hjr_ctx::Refit& rf = c->refit;
-    // Option "device_bvh_instances" (the tag's bit 19): per-instance trees kept in dbvh.topo, a top tree per commit; no refits with it
-    // Option "device_bvh_graft" (bit 20, only ever set with bit 19): the instances' BVH4s collapsed once, grafted under a BVH4 top tree
-    const bool instances = (c->pending_build_tag >> 19) & 1u, graft = (c->pending_build_tag >> 20) & 1u;
-    if (!instances) c->dbvh.drop_topology();
-    const bool refit = !instances && c->have_frame && rf.device && c->dbvh.have_scene && !rf.rebuild && rf.count < limit && rf.tag == c->pending_build_tag &&
-                       c->last_m.size() == c->pending_m.size() && c->scene.n_triangles >= 2 && c->frame.n_tris == c->scene.n_triangles;
+    // key.instances: per-instance trees kept in dbvh.topo, a top tree per commit; no refits with it
+    // key.graft (only ever set with it): the instances' BVH4s collapsed once, grafted under a BVH4 top tree
+    if (!pp.key.instances) c->dbvh.drop_topology();
+    const bool refit = !pp.key.instances && c->have_frame && rf.device && c->dbvh.have_scene && !rf.rebuild && rf.count < limit && rf.tag == tag &&
+                       c->built.m.size() == pp.m.size() && c->scene.n_triangles >= 2 && c->frame.n_tris == c->scene.n_triangles;
     hjr::DeviceBvhResult r;
     std::string err;
-    hjr::FrameData& f = c->pending;
-    const int rc = instances ? hjr::device_bvh_instances(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds,
-                                                         c->pending_build_tag, graft, f.lights.data(), f.lights.size(), c->stream, r, err)
-                   : refit ? hjr::device_bvh_refit(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, c->d_nodes, c->d_tri_geom, c->frame.n_nodes,
+    hjr::FrameData& f = pp.frame;
+    const int rc = pp.key.instances ? hjr::device_bvh_instances(c->dbvh, c->scene, pp.m.data(), pp.inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds, tag, pp.key.graft,
+                                                                f.lights.data(), f.lights.size(), c->stream, r, err)
+                   : refit ? hjr::device_bvh_refit(c->dbvh, c->scene, pp.m.data(), pp.inv.data(), n_inst, c->d_nodes, c->d_tri_geom, c->frame.n_nodes,
                                                  f.lights.data(), f.lights.size(), c->stream, r, err)
-                         : hjr::device_bvh_build(c->dbvh, c->scene, c->pending_m.data(), c->pending_inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds,
+                         : hjr::device_bvh_build(c->dbvh, c->scene, pp.m.data(), pp.inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds,
                                                  f.lights.data(), f.lights.size(), c->stream, r, err);
     if (rc != HJR_OK) { set_error("hjr_set_transforms: " + err); return rc; }
     c->d_nodes.swap(c->dbvh.nodes); c->d_tri_geom.swap(c->dbvh.tri_geom); c->d_tri_shade.swap(c->dbvh.tri_shade);
@@ -244,34 +288,33 @@ static int commit_device(hjr_ctx* c)
         rf.rebuild = (double)r.sah > (double)rf.sah_full * (1.0 + c->opt.get(hjr::OPT_DEVICE_BVH_REFIT_GROWTH, 10) / 100.0);
     } else {
         f.n_nodes = r.n_nodes; f.stack_need = r.stack_need; f.depth = r.depth;
-        rf.device = true; rf.rebuild = false; rf.count = 0; rf.tag = c->pending_build_tag; rf.sah_full = r.sah;
+        rf.device = true; rf.rebuild = false; rf.count = 0; rf.tag = tag; rf.sah_full = r.sah;
     }
     rf.sah = r.sah;
-    c->pending_instances = r.instances;
-    c->pending_grafted = graft && r.instances > 0;
-    c->pending_build_ms = r.build_ms;
+    instances = r.instances;
+    pp.build_ms = r.build_ms;
     return HJR_OK;
 }
 
 extern "C" int hjr_commit_transforms(hjr_ctx* c)
 {
     if (!c) { set_error("hjr_commit_transforms: null context"); return HJR_ERR_ARG; }
-    if (!c->pending_valid) { set_error("hjr_commit_transforms: nothing prepared"); return HJR_ERR_STATE; }
-    c->pending_valid = false;
-    if (c->pending_same) {
+    hjr_ctx::Prepared& pp = c->prep;
+    if (!pp.valid) { set_error("hjr_commit_transforms: nothing prepared"); return HJR_ERR_STATE; }
+    pp.valid = false;
+    if (pp.same) {
         if (c->opt.get(hjr::OPT_VERBOSE, 0)) fprintf(stderr, "[hjr] transforms unchanged: frame data reused\n");
         return HJR_OK;
     }
     HIPCHK(hipSetDevice(c->device));
     c->frame_gen++; // the frame data is replaced (a progressive frame cannot continue on it, even if the build below fails)
-    if (c->pending_device) {
-        if (const int rc = commit_device(c)) return rc;
-        std::swap(c->frame, c->pending);
+    uint32_t instances = 0; // option "device_bvh_instances": instance subtrees of this commit (0: an ordinary build)
+    if (pp.key.device) {
+        if (const int rc = commit_device(c, instances)) return rc;
+        std::swap(c->frame, pp.frame);
     } else {
-        std::swap(c->frame, c->pending);
+        std::swap(c->frame, pp.frame);
         c->refit = hjr_ctx::Refit(); // host-built data: nothing to refit
-        c->pending_instances = 0;
-        c->pending_grafted = false;
         c->dbvh.drop_topology();
         const hjr::FrameData& f = c->frame;
         bool ok = c->d_nodes.upload(f.nodes.data(), f.nodes.size() * 4, c->stream) &&
@@ -284,20 +327,20 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
     }
     const hjr::FrameData& f = c->frame;
     c->have_frame = true;
-    c->last_m.swap(c->pending_m); c->last_inv.swap(c->pending_inv); c->last_build_tag = c->pending_build_tag;
+    c->built.m.swap(pp.m); c->built.inv.swap(pp.inv); c->built.key = pp.key;
     c->stats.bvh_nodes = f.n_nodes;
     c->stats.bvh_depth = f.depth;
-    c->stats.bvh_builder = c->pending_device ? 1u : 0u;
-    c->stats.frame_build_ms = (float)c->pending_build_ms;
+    c->stats.bvh_builder = pp.key.device ? 1u : 0u;
+    c->stats.frame_build_ms = (float)pp.build_ms;
     c->stats.bvh_refits = c->refit.count;
     c->stats.bvh_sah = c->refit.sah;
-    c->stats.bvh_instances = c->pending_instances;
-    if (c->pending_instances) c->stats.bvh_topology_ms = c->dbvh.topo.ms;
-    const bool refitted = c->pending_device && c->refit.count > 0;
+    c->stats.bvh_instances = instances;
+    if (instances) c->stats.bvh_topology_ms = c->dbvh.topo.ms;
+    const bool refitted = pp.key.device && c->refit.count > 0;
     if (c->opt.get(hjr::OPT_VERBOSE, 0))
         fprintf(stderr, "[hjr] BVH%u (lds_mode %d): %u nodes (%zu KB), %u triangles (%zu KB), stack %u entries/lane, %s %s %.1f ms\n", f.width, f.lds_mode, f.n_nodes,
                 (size_t)f.n_nodes * (f.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4) * 16 / 1024, f.n_tris, (size_t)std::max(f.n_tris, 1u) * HJR_TRI_F4 * 16 / 1024,
-                f.stack_need, c->pending_device ? "device" : "host", refitted ? "refit" : (c->pending_instances ? (c->pending_grafted ? "grafted instance build" : "instance build") : "build"), c->pending_build_ms);
+                f.stack_need, pp.key.device ? "device" : "host", refitted ? "refit" : (instances ? (pp.key.graft ? "grafted instance build" : "instance build") : "build"), pp.build_ms);
     c->stats.n_triangles = f.n_tris;
     return HJR_OK;
 }
@@ -332,30 +375,27 @@ extern "C" int hjr_set_transforms(hjr_ctx* c, const float* m, const float* inv, 
     return rc != HJR_OK ? rc : hjr_commit_transforms(c);
 }
 
+// hjr_set_lut / hjr_set_sky: an image of `texel` bytes per pixel into `buf`, its size into (cw, ch); a null or empty image switches it off
+static int set_image(hjr_ctx* c, const char* who, DevBuf& buf, const void* rgba, int w, int h, size_t texel, int& cw, int& ch)
+{
+    HIPCHK(hipSetDevice(c->device));
+    c->frame_gen++;
+    c->tmp.have_prev = false; // temporal history: the shading / the lighting changes
+    if (!rgba || w <= 0 || h <= 0) { cw = ch = 0; return HJR_OK; }
+    if (!buf.upload(rgba, (size_t)w * (size_t)h * texel, c->stream)) { set_error(std::string(who) + ": upload failed"); return HJR_ERR_DEVICE; }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    cw = w; ch = h;
+    return HJR_OK;
+}
 extern "C" int hjr_set_lut(hjr_ctx* c, const uint8_t* rgba, int w, int h)
 {
     if (!c) { set_error("hjr_set_lut: null context"); return HJR_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-    c->frame_gen++;
-    c->tmp.have_prev = false; // temporal history: the shading changes
-    if (!rgba || w <= 0 || h <= 0) { c->lut_w = c->lut_h = 0; return HJR_OK; }
-    if (!c->d_lut.upload(rgba, (size_t)w * (size_t)h * 4, c->stream)) { set_error("hjr_set_lut: upload failed"); return HJR_ERR_DEVICE; }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->lut_w = w; c->lut_h = h;
-    return HJR_OK;
+    return set_image(c, "hjr_set_lut", c->d_lut, rgba, w, h, 4, c->lut_w, c->lut_h);
 }
-
 extern "C" int hjr_set_sky(hjr_ctx* c, const float* rgba, int w, int h)
 {
     if (!c) { set_error("hjr_set_sky: null context"); return HJR_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-    c->frame_gen++;
-    c->tmp.have_prev = false; // temporal history: the lighting changes
-    if (!rgba || w <= 0 || h <= 0) { c->sky_w = c->sky_h = 0; return HJR_OK; }
-    if (!c->d_sky.upload(rgba, (size_t)w * (size_t)h * 16, c->stream)) { set_error("hjr_set_sky: upload failed"); return HJR_ERR_DEVICE; }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->sky_w = w; c->sky_h = h;
-    return HJR_OK;
+    return set_image(c, "hjr_set_sky", c->d_sky, rgba, w, h, 16, c->sky_w, c->sky_h);
 }
 
 // the render kernels live in their own translation units (hjr_launch.hip.h)
@@ -572,8 +612,7 @@ static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_c
     // has seen the queue dry, hjr_kernel.hip.h); 2^24 covers 262 144 waves, far more than any resident grid
     if (g.n_items >= 0xffffffffull - (1ull << 24)) { set_error("hjr_render: image too large (more than 2^32 - 2^24 work items per launch)"); return HJR_ERR_ARG; }
     // node format / LDS staging were decided by the host builder for this frame (host/frame.cpp)
-    g.lds_mode = c->frame.lds_mode;
-    if (g.lds_mode == 0 && c->frame.width == 2) g.lds_mode = 3;
+    g.lds_mode = launch_layout(c->frame);
     return HJR_OK;
 }
 
@@ -768,8 +807,7 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
 #endif
 #endif
     if (const int rc = fn(c, pl, n_items, st)) return rc;
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return launched();
 }
 
 // An adaptive sample pass (hjr_set_adaptive), before bind_params: the tiles still active size the launch.  A continuing
@@ -847,20 +885,27 @@ static int finalize_chunks(hjr_ctx* c, const FrameGeom& g, KParams& kp, bool ada
     return HJR_OK;
 }
 
+// the launch of both rules: hjr_firefly_kernel over the owned pixels' first m (<= 64, hjr_layout.h) colour chunk sums, in the instantiation
+// of a one-shot frame, a sample pass or an adaptive sample pass
+static int firefly_launch(hjr_ctx* c, const FrameGeom& g, const KParams& kp, uint32_t m, bool pass, bool adaptive, hipStream_t st)
+{
+    constexpr uint32_t FB = 128; // lanes per workgroup: 64 chunks x 128 lanes x 4 bytes = 32 KiB of LDS at most
+    using Kernel = void (*)(const KParams, const float, unsigned long long*);
+    // (instantiated in the order they always were: it is their order in the code object)
+    static const Kernel kernels[3] = { hjr_firefly_kernel<FB, false, false>, hjr_firefly_kernel<FB, true, true>, hjr_firefly_kernel<FB, true, false> };
+    const size_t n_slots = (size_t)g.owned * 64u;
+    const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + FB - 1) / FB, (size_t)c->n_cus * 16));
+    hipLaunchKernelGGL(kernels[pass ? (adaptive ? 1 : 2) : 0], dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kp, (float)c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0),
+                       (unsigned long long*)((char*)c->d_work.p + WorkArea::FIREFLY));
+    return launched();
+}
 // Option "firefly_clamp" (hjr_firefly_kernel, DESIGN.md §4 rule 9), behind finalize_chunks on a one-shot frame: the colour of the pixels with a
 // chunk over their limit is rewritten.  With the option off, or a frame of fewer than 4 full chunks, nothing is launched.
 static int firefly_clamp(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, const KParams& kp, hipStream_t st)
 {
-    constexpr uint32_t FB = 128; // lanes per workgroup: 64 chunks x 128 lanes x 4 bytes = 32 KiB of LDS at most
-    const int kappa = c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0);
     const uint32_t m = p->spp / g.chunk_spp;
-    const size_t n_slots = (size_t)g.owned * 64u;
-    if (kappa <= 0 || g.pr.pass || g.n_chunks < 2 || m < 4 || n_slots == 0) return HJR_OK;
-    const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + FB - 1) / FB, (size_t)c->n_cus * 16));
-    hipLaunchKernelGGL((hjr_firefly_kernel<FB, false, false>), dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kp, (float)kappa,
-                       (unsigned long long*)((char*)c->d_work.p + WorkArea::FIREFLY));
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    if (c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0) <= 0 || g.pr.pass || g.n_chunks < 2 || m < 4 || g.owned == 0) return HJR_OK;
+    return firefly_launch(c, g, kp, m, false, false, st);
 }
 // Option "firefly_clamp_passes" (DESIGN.md §4 rule 10), behind finalize_chunks on a sample pass of a frame that keeps its colour chunk sums
 // (firefly_keeps_chunks) and has received m_n = sample_end / granule >= 4 full chunks: the colour of the pixels with a chunk over their limit
@@ -872,18 +917,10 @@ static bool firefly_pass_acts(const hjr_ctx* c, const FrameGeom& g)
 }
 static int firefly_clamp_pass(hjr_ctx* c, const FrameGeom& g, const KParams& kp, bool adaptive, bool decide, hipStream_t st)
 {
-    constexpr uint32_t FB = 128;
     if (!firefly_pass_acts(c, g)) return HJR_OK;
-    const uint32_t m = g.pr.end / g.chunk_spp; // <= 64 full chunks (hjr_layout.h): at most 32 KiB of LDS
-    const size_t n_slots = (size_t)g.owned * 64u;
     KParams kf = kp;
     kf.ad_decide = decide ? 1u : 0u;
-    const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + FB - 1) / FB, (size_t)c->n_cus * 16));
-    unsigned long long* const d_n = (unsigned long long*)((char*)c->d_work.p + WorkArea::FIREFLY);
-    if (adaptive) hipLaunchKernelGGL((hjr_firefly_kernel<FB, true, true>), dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kf, (float)c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0), d_n);
-    else hipLaunchKernelGGL((hjr_firefly_kernel<FB, true, false>), dim3(fb), dim3(FB), (size_t)m * FB * sizeof(float), st, kf, (float)c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0), d_n);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return firefly_launch(c, g, kf, g.pr.end / g.chunk_spp, true, adaptive, st);
 }
 
 // pr: check_pass of this call, made before the caller enqueued anything
@@ -1051,12 +1088,11 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
 extern "C" int hjr_render_device_var(hjr_ctx* c, const hjr_params* p_user, void* d_color, void* d_albedo, void* d_normal, void* d_variance, void* stream)
 {
     hjr_params params; // sized struct
-    if (!c || !hjr::abi_take(p_user, params, "hjr_render_device")) { if (!c) set_error("hjr_render_device: null context"); return HJR_ERR_ARG; }
+    if (!take_params(c, p_user, params, "hjr_render_device")) return HJR_ERR_ARG;
     const hjr_params* p = &params;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     PassRange pr;
     if (const int rc = check_pass(c, p, (d_color ? 1u : 0u) | (d_albedo ? 2u : 0u) | (d_normal ? 4u : 0u) | (d_variance ? 8u : 0u), pr)) return rc;
-    return render_impl(c, p, pr, d_color, d_albedo, d_normal, d_variance, st);
+    return render_impl(c, p, pr, d_color, d_albedo, d_normal, d_variance, stream_of(c, stream));
 }
 extern "C" int hjr_render_device(hjr_ctx* c, const hjr_params* p_user, void* d_color, void* d_albedo, void* d_normal, void* stream)
 {
@@ -1085,7 +1121,7 @@ static int denoise_device_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint3
     if (render_mode != HJR_MODE_DEFAULT && (!d_albedo || !d_normal)) { set_error("hjr_denoise: the albedo and normal guide AOVs are required"); return HJR_ERR_ARG; }
     if (render_mode != HJR_MODE_DEFAULT && with_var && !d_variance) { set_error("hjr_denoise_var: the variance AOV is required"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    hipStream_t st = stream_of(c, hip_stream);
     const size_t in_bytes = (size_t)in_w * in_h * 16;
     if (render_mode == HJR_MODE_DEFAULT) { // blendFactor 1: the output is the input (denoiser.h:94-97)
         if (d_out != d_color) HIPCHK(hipMemcpyAsync(d_out, d_color, in_bytes, hipMemcpyDeviceToDevice, st));
@@ -1093,7 +1129,7 @@ static int denoise_device_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint3
     }
     if (!c->d_dn_a.reserve(in_bytes) || !c->d_dn_b.reserve(in_bytes)) { set_error("hjr_denoise: allocation failed"); return HJR_ERR_DEVICE; }
     if (with_var && (!c->d_dnv_a.reserve(in_bytes / 4) || !c->d_dnv_b.reserve(in_bytes / 4))) { set_error("hjr_denoise_var: allocation failed"); return HJR_ERR_DEVICE; }
-    const dim3 block(256), grid((in_w + 63) / 64, (in_h + 3) / 4);
+    const dim3 block(256), grid = image_grid(in_w, in_h);
     const float4* src = (const float4*)d_color;
     float4* pp[2] = { (float4*)c->d_dn_a.p, (float4*)c->d_dn_b.p };
     const float* vsrc = (const float*)d_variance;
@@ -1107,12 +1143,8 @@ static int denoise_device_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint3
         if (with_var) vsrc = vp[it & 1];
         src = dst;
     }
-    if (up) {
-        const dim3 g2((out_w + 63) / 64, (out_h + 3) / 4);
-        hipLaunchKernelGGL(hjr_upscale2x_kernel, g2, block, 0, st, src, (float4*)d_out, (int)in_w, (int)in_h, (int)out_w, (int)out_h);
-    }
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    if (up) hipLaunchKernelGGL(hjr_upscale2x_kernel, image_grid(out_w, out_h), block, 0, st, src, (float4*)d_out, (int)in_w, (int)in_h, (int)out_w, (int)out_h);
+    return launched();
 }
 
 extern "C" int hjr_denoise_device(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const void* d_color, const void* d_albedo,
@@ -1138,19 +1170,18 @@ static int denoise_host_impl(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_
         set_error("hjr_denoise: allocation failed");
         return HJR_ERR_DEVICE;
     }
-    HIPCHK(hipMemcpyAsync(c->d_color.p, color, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (albedo) HIPCHK(hipMemcpyAsync(c->d_albedo.p, albedo, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (normal) HIPCHK(hipMemcpyAsync(c->d_normal.p, normal, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (with_var && variance) {
-        if (!c->d_variance.reserve(in_bytes / 4)) { set_error("hjr_denoise_var: allocation failed"); return HJR_ERR_DEVICE; }
-        HIPCHK(hipMemcpyAsync(c->d_variance.p, variance, in_bytes / 4, hipMemcpyHostToDevice, c->stream));
-    }
-    const int rc = denoise_device_impl(c, render_mode, in_w, in_h, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr,
-                                       with_var, with_var && variance ? c->d_variance.p : nullptr, c->d_dn_out.p, out_w, out_h, c->stream);
-    if (rc != HJR_OK) return rc;
-    HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return HJR_OK;
+    const bool var_in = with_var && variance;
+    if (var_in && !c->d_variance.reserve(in_bytes / 4)) { set_error("hjr_denoise_var: allocation failed"); return HJR_ERR_DEVICE; }
+    HostStage hs(c);
+    hs.up(c->d_color.p, color, in_bytes);
+    if (albedo) hs.up(c->d_albedo.p, albedo, in_bytes);
+    if (normal) hs.up(c->d_normal.p, normal, in_bytes);
+    if (var_in) hs.up(c->d_variance.p, variance, in_bytes / 4);
+    // (the filter's own refusals come here, where they always did: finish() drains the uploads before it hands them on)
+    if (hs.ok()) hs.rc = denoise_device_impl(c, render_mode, in_w, in_h, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr,
+                                             with_var, var_in ? c->d_variance.p : nullptr, c->d_dn_out.p, out_w, out_h, c->stream);
+    hs.down(out, c->d_dn_out.p, out_bytes);
+    return hs.finish(with_var ? "hjr_denoise_var" : "hjr_denoise");
 }
 extern "C" int hjr_denoise(hjr_ctx* c, int render_mode, uint32_t in_w, uint32_t in_h, const float* color, const float* albedo, const float* normal,
                            float* out, uint32_t out_w, uint32_t out_h)
@@ -1174,17 +1205,16 @@ static int estimate_variance_check(const hjr_ctx* c, uint32_t w, uint32_t h, con
 // the kernel on device memory; the callers checked the arguments.  d_vin NULL = every pixel unknown; d_vout may be d_vin
 static int estimate_variance_launch(uint32_t w, uint32_t h, const void* d_color, const void* d_albedo, const void* d_normal, const void* d_vin, void* d_vout, hipStream_t st)
 {
-    hipLaunchKernelGGL(hjr_spatial_var_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, (const float4*)d_color, (const float4*)d_normal, (const float4*)d_albedo,
+    hipLaunchKernelGGL(hjr_spatial_var_kernel, image_grid(w, h), dim3(256), 0, st, (const float4*)d_color, (const float4*)d_normal, (const float4*)d_albedo,
                        (const float*)d_vin, (float*)d_vout, (int)w, (int)h);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return launched();
 }
 extern "C" int hjr_estimate_variance_device(hjr_ctx* c, uint32_t w, uint32_t h, const void* d_color, const void* d_albedo, const void* d_normal, const void* d_variance_in,
                                             void* d_variance_out, void* hip_stream)
 {
     if (const int rc = estimate_variance_check(c, w, h, d_color, d_albedo, d_normal, d_variance_out)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    return estimate_variance_launch(w, h, d_color, d_albedo, d_normal, d_variance_in, d_variance_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+    return estimate_variance_launch(w, h, d_color, d_albedo, d_normal, d_variance_in, d_variance_out, stream_of(c, hip_stream));
 }
 extern "C" int hjr_estimate_variance(hjr_ctx* c, uint32_t w, uint32_t h, const float* color, const float* albedo, const float* normal, const float* variance_in,
                                      float* variance_out)
@@ -1196,38 +1226,15 @@ extern "C" int hjr_estimate_variance(hjr_ctx* c, uint32_t w, uint32_t h, const f
         set_error("hjr_estimate_variance: allocation failed");
         return HJR_ERR_DEVICE;
     }
-    HIPCHK(hipMemcpyAsync(c->d_color.p, color, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_albedo.p, albedo, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_normal.p, normal, bytes, hipMemcpyHostToDevice, c->stream));
-    if (variance_in) HIPCHK(hipMemcpyAsync(c->d_variance.p, variance_in, bytes / 4, hipMemcpyHostToDevice, c->stream));
-    if (const int rc = estimate_variance_launch(w, h, c->d_color.p, c->d_albedo.p, c->d_normal.p, variance_in ? c->d_variance.p : nullptr, c->d_variance.p, c->stream)) return rc;
-    HIPCHK(hipMemcpyAsync(variance_out, c->d_variance.p, bytes / 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return HJR_OK;
+    HostStage hs(c);
+    hs.up(c->d_color.p, color, bytes);
+    hs.up(c->d_albedo.p, albedo, bytes);
+    hs.up(c->d_normal.p, normal, bytes);
+    if (variance_in) hs.up(c->d_variance.p, variance_in, bytes / 4);
+    if (hs.ok()) hs.rc = estimate_variance_launch(w, h, c->d_color.p, c->d_albedo.p, c->d_normal.p, variance_in ? c->d_variance.p : nullptr, c->d_variance.p, c->stream);
+    hs.down(variance_out, c->d_variance.p, bytes / 4);
+    return hs.finish("hjr_estimate_variance");
 }
-
-// Host buffers through one temporary device buffer on the context's stream: what the host-buffer entry points do that stage through no
-// context-owned buffer.  Uploads, the caller's launch (into `rc`) and downloads each happen only while everything before them succeeded;
-// finish() drains the stream, releases the buffer (on every path, and only after the stream has drained) and folds the first error.
-struct HostStage {
-    hjr_ctx* c;
-    DevBuf buf;
-    int rc = HJR_OK;           // of the launch
-    hipError_t e = hipSuccess; // the first failed runtime call
-    explicit HostStage(hjr_ctx* c_) : c(c_) {}
-    bool ok() const { return rc == HJR_OK && e == hipSuccess; }
-    void up(void* dst, const void* src, size_t n) { if (ok() && n) e = hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream); }
-    void down(void* dst, const void* src, size_t n) { if (ok() && n) e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream); }
-    int finish(const char* who)
-    {
-        const hipError_t es = hipStreamSynchronize(c->stream);
-        buf.release();
-        if (rc != HJR_OK) return rc;
-        if (e == hipSuccess) e = es;
-        if (e != hipSuccess) { set_error(std::string(who) + ": " + hipGetErrorString(e)); return HJR_ERR_DEVICE; }
-        return HJR_OK;
-    }
-};
 
 // ---- temporal accumulation with reprojection (csrc/hjr_temporal.hip.h; include/henjou_hip.h)
 // The G-buffer pass's rules for the frame p describes, refused in the caller's words: `who` is the entry point, `t` what follows its name in
@@ -1277,8 +1284,7 @@ static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hip
         { hjr_gbuffer_kernel<4, false>, hjr_gbuffer_kernel<4, true> },
     };
     hipLaunchKernelGGL(kernels[c->frame.width != 2][side != 0], dim3(grid), dim3(64), smem, st, a);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return launched();
 }
 static bool coverage_side_ok(uint32_t side)
 {
@@ -1289,20 +1295,20 @@ static bool coverage_side_ok(uint32_t side)
 extern "C" int hjr_render_gbuffer_device(hjr_ctx* c, const hjr_params* p_user, void* d_out, void* hip_stream)
 {
     hjr_params params; // sized struct
-    if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
-    return gbuffer_device_impl(c, &params, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream, 0);
+    if (!take_params(c, p_user, params, "hjr_render_gbuffer")) return HJR_ERR_ARG;
+    return gbuffer_device_impl(c, &params, d_out, stream_of(c, hip_stream), 0);
 }
 extern "C" int hjr_render_gbuffer_cov_device(hjr_ctx* c, const hjr_params* p_user, uint32_t side, void* d_out, void* hip_stream)
 {
     hjr_params params; // sized struct
     if (!coverage_side_ok(side)) return HJR_ERR_ARG;
-    if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer_cov")) { if (!c) set_error("hjr_render_gbuffer_cov: null context"); return HJR_ERR_ARG; }
-    return gbuffer_device_impl(c, &params, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream, side);
+    if (!take_params(c, p_user, params, "hjr_render_gbuffer_cov")) return HJR_ERR_ARG;
+    return gbuffer_device_impl(c, &params, d_out, stream_of(c, hip_stream), side);
 }
 static int gbuffer_host_impl(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out, uint32_t side)
 {
     hjr_params params; // sized struct
-    if (!c || !hjr::abi_take(p_user, params, "hjr_render_gbuffer")) { if (!c) set_error("hjr_render_gbuffer: null context"); return HJR_ERR_ARG; }
+    if (!take_params(c, p_user, params, "hjr_render_gbuffer")) return HJR_ERR_ARG;
     if (!out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
     const size_t bytes = (size_t)params.width * params.height * sizeof(hjr_gbuffer_px);
     HostStage hs(c);
@@ -1332,9 +1338,8 @@ static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalS
     a.out_color = (float4*)d_color; a.out_variance = (float*)d_var; a.out_history = (float*)d_hist;
     using Kernel = void (*)(TemporalArgs);
     static const Kernel kernels[2] = { hjr_temporal_kernel<false>, hjr_temporal_kernel<true> }; // [a side carries coverage]
-    hipLaunchKernelGGL(kernels[a.prev_cov || a.cur_cov], dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, st, a);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    hipLaunchKernelGGL(kernels[a.prev_cov || a.cur_cov], image_grid(w, h), dim3(256), 0, st, a);
+    return launched();
 }
 // argument checks of hjr_temporal_accumulate[_device]: the sized structs, sizes that agree, every pointer the kernel reads
 static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, hjr_temporal_frame& prev, hjr_temporal_frame& cur, bool& have_prev)
@@ -1365,7 +1370,7 @@ extern "C" int hjr_temporal_accumulate_device(hjr_ctx* c, const hjr_temporal_fra
     if (const int rc = temporal_take(prev_user, cur_user, prev, cur, have_prev)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const TemporalSide ps = have_prev ? temporal_side(prev) : TemporalSide(), cs = temporal_side(cur);
-    return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, hip_stream ? (hipStream_t)hip_stream : c->stream,
+    return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, stream_of(c, hip_stream),
                            have_prev ? prev.coverage : 0u, cur.coverage);
 }
 extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist)
@@ -1410,14 +1415,14 @@ extern "C" int hjr_temporal_reset(hjr_ctx* c)
 }
 
 // Option "denoise_temporal", between the render (or the assembly of gathered shards) and the filter, all on `st`: G-buffer of this frame,
-// a device copy of the transforms the current frame data was built from (last_m / last_inv: what hjr_commit_transforms made current, so a
+// a device copy of the transforms the current frame data was built from (`built`: what hjr_commit_transforms made current, so a
 // frame loop that already prepares the next frame on another thread cannot be seen here), accumulation against the previous slot.
 // `commit`: this call ends the frame (a whole-frame render, or the sample pass that ends at spp): the slots rotate.
 // the current slot's buffers (no enqueue: post_plan calls it ahead of the first launch, temporal_stage again to no effect)
 static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
 {
     hjr_ctx::Temporal& t = c->tmp;
-    const size_t npx = (size_t)p->width * p->height, nx = c->last_m.size() * 4;
+    const size_t npx = (size_t)p->width * p->height, nx = c->built.m.size() * 4;
     const int k = t.cur;
     if (!t.color[k].reserve(npx * 16) || !t.variance[k].reserve(npx * 4) || !t.history[k].reserve(npx * 4) || !t.gbuf[k].reserve(npx * sizeof(hjr_gbuffer_px)) ||
         !t.xf[k].reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
@@ -1426,7 +1431,7 @@ static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
 static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
 {
     hjr_ctx::Temporal& t = c->tmp;
-    const uint32_t n_inst = (uint32_t)(c->last_m.size() / 12);
+    const uint32_t n_inst = (uint32_t)(c->built.m.size() / 12);
     if (t.have_prev && (t.width != p->width || t.height != p->height || t.mode != render_mode || t.n_instances != n_inst)) t.have_prev = false;
     const size_t nx = (size_t)n_inst * 48;
     const int k = t.cur;
@@ -1434,8 +1439,8 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
     const uint32_t cov = (uint32_t)c->opt.get(hjr::OPT_DENOISE_TEMPORAL_COVERAGE, 0); // option "denoise_temporal_coverage": the coverage pass and rules 2' / 3' (setting it drops the history, so both slots agree)
     if (const int rc = gbuffer_device_impl(c, p, t.gbuf[k].p, st, cov)) return rc;
     if (nx) {
-        HIPCHK(hipMemcpyAsync(t.xf[k].p, c->last_m.data(), nx, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((char*)t.xf[k].p + nx, c->last_inv.data(), nx, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t.xf[k].p, c->built.m.data(), nx, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((char*)t.xf[k].p + nx, c->built.inv.data(), nx, hipMemcpyHostToDevice, st));
     }
     t.cam[k] = p->camera;
     TemporalSide s[2];
@@ -1465,17 +1470,16 @@ static int upscale_guided_check(const hjr_ctx* c, uint32_t in_w, uint32_t in_h, 
 static int upscale_guided_launch(uint32_t in_w, uint32_t in_h, const void* d_color_lo, const void* d_gbuffer_lo, const hjr_camera& cam, const void* d_gbuffer_hi, void* d_out,
                                  uint32_t out_w, uint32_t out_h, hipStream_t st)
 {
-    hipLaunchKernelGGL(hjr_upscale_guided_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(256), 0, st, (const float4*)d_color_lo, (const hjr_gbuffer_px*)d_gbuffer_lo,
+    hipLaunchKernelGGL(hjr_upscale_guided_kernel, image_grid(out_w, out_h), dim3(256), 0, st, (const float4*)d_color_lo, (const hjr_gbuffer_px*)d_gbuffer_lo,
                        (const hjr_gbuffer_px*)d_gbuffer_hi, (float4*)d_out, cam, (int)in_w, (int)in_h, (int)out_w, (int)out_h);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return launched();
 }
 extern "C" int hjr_upscale_guided_device(hjr_ctx* c, uint32_t in_w, uint32_t in_h, const void* d_color_lo, const void* d_gbuffer_lo, const hjr_camera* cam,
                                          const void* d_gbuffer_hi, void* d_out, uint32_t out_w, uint32_t out_h, void* hip_stream)
 {
     if (const int rc = upscale_guided_check(c, in_w, in_h, d_color_lo, d_gbuffer_lo, cam, d_gbuffer_hi, d_out, out_w, out_h)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    return upscale_guided_launch(in_w, in_h, d_color_lo, d_gbuffer_lo, *cam, d_gbuffer_hi, d_out, out_w, out_h, hip_stream ? (hipStream_t)hip_stream : c->stream);
+    return upscale_guided_launch(in_w, in_h, d_color_lo, d_gbuffer_lo, *cam, d_gbuffer_hi, d_out, out_w, out_h, stream_of(c, hip_stream));
 }
 extern "C" int hjr_upscale_guided(hjr_ctx* c, uint32_t in_w, uint32_t in_h, const float* color_lo, const hjr_gbuffer_px* gbuffer_lo, const hjr_camera* cam,
                                   const hjr_gbuffer_px* gbuffer_hi, float* out, uint32_t out_w, uint32_t out_h)
@@ -1580,7 +1584,7 @@ static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, const PostPlan& p
 extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int render_mode, float* out, uint32_t out_w, uint32_t out_h)
 {
     hjr_params params; // sized struct
-    if (!c || !hjr::abi_take(p_user, params, "hjr_render_denoised")) { if (!c) set_error("hjr_render_denoised: null context"); return HJR_ERR_ARG; }
+    if (!take_params(c, p_user, params, "hjr_render_denoised")) return HJR_ERR_ARG;
     const hjr_params* p = &params;
     if (!out) { set_error("hjr_render_denoised: null argument"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
@@ -1593,13 +1597,11 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     if (pl.with_var) HIPCHK(hipMemsetAsync(c->d_variance.p, 0, in_bytes / 4, c->stream));
     HIPCHK(hipMemsetAsync(c->d_color.p, 0, in_bytes, c->stream));
     if (pl.guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
-    int rc = render_impl(c, p, pr, c->d_color.p, pl.guides ? c->d_albedo.p : nullptr, pl.guides ? c->d_normal.p : nullptr, pl.with_var ? c->d_variance.p : nullptr, c->stream);
-    if (rc != HJR_OK) return rc;
-    rc = denoise_post_stage(c, p, pl, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
-    if (rc != HJR_OK) return rc;
-    HIPCHK(hipMemcpyAsync(out, c->d_dn_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return HJR_OK;
+    HostStage hs(c);
+    hs.rc = render_impl(c, p, pr, c->d_color.p, pl.guides ? c->d_albedo.p : nullptr, pl.guides ? c->d_normal.p : nullptr, pl.with_var ? c->d_variance.p : nullptr, c->stream);
+    if (hs.ok()) hs.rc = denoise_post_stage(c, p, pl, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
+    hs.down(out, c->d_dn_out.p, out_bytes);
+    return hs.finish("hjr_render_denoised");
 }
 
 // ---- gathered shards of a multi-GPU frame (include/henjou_hip.h; kernel: csrc/hjr_aux.hip.h)
@@ -1612,8 +1614,7 @@ static int assemble_launch(const hjr_shards& s, uint32_t w, uint32_t h, void* d_
     a.rank_stride = s.rank_stride; a.width = w; a.height = h; a.world = s.world_size;
     a.tiles_x = (w + HJR_TILE - 1) / HJR_TILE;
     hipLaunchKernelGGL(hjr_assemble_shards_kernel, dim3((a.tiles_x + 3u) / 4u, (h + HJR_TILE - 1) / HJR_TILE), dim3(256), 0, st, a);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return launched();
 }
 extern "C" int hjr_assemble_shards_device(hjr_ctx* c, const hjr_shards* shards, uint32_t w, uint32_t h, void* d_color, void* d_albedo, void* d_normal, void* d_variance,
                                           void* hip_stream)
@@ -1624,7 +1625,7 @@ extern "C" int hjr_assemble_shards_device(hjr_ctx* c, const hjr_shards* shards, 
     if (!hjr::abi_take(shards, s, "hjr_assemble_shards_device")) return HJR_ERR_ARG;
     if (const int rc = hjr::check_shards(s, w, h, out, "hjr_assemble_shards_device")) return rc;
     HIPCHK(hipSetDevice(c->device));
-    return assemble_launch(s, w, h, d_color, d_albedo, d_normal, d_variance, hip_stream ? (hipStream_t)hip_stream : c->stream);
+    return assemble_launch(s, w, h, d_color, d_albedo, d_normal, d_variance, stream_of(c, hip_stream));
 }
 // Rank 0's half of a multi-GPU frame in a Denoise mode: the gathered blocks -> the context's AOV buffers -> the post stage of hjr_render_denoised.
 // Every argument and state check comes before the first enqueue.
@@ -1632,7 +1633,7 @@ extern "C" int hjr_denoise_shards_device(hjr_ctx* c, const hjr_params* p_user, i
                                          void* hip_stream)
 {
     hjr_params params; // sized struct
-    if (!c || !hjr::abi_take(p_user, params, "hjr_denoise_shards_device")) { if (!c) set_error("hjr_denoise_shards_device: null context"); return HJR_ERR_ARG; }
+    if (!take_params(c, p_user, params, "hjr_denoise_shards_device")) return HJR_ERR_ARG;
     if (!d_out) { set_error("hjr_denoise_shards_device: null argument"); return HJR_ERR_ARG; }
     if (render_mode == HJR_MODE_DEFAULT) { set_error("hjr_denoise_shards_device: Render_mode Default has no filter (hjr_assemble_shards_device assembles the frame)"); return HJR_ERR_ARG; }
     params.rank = 0; params.world_size = 1; params.flags &= ~HJR_FLAG_PACKED; // `frame` describes the whole frame; gathered->world_size is how it was rendered
@@ -1650,7 +1651,7 @@ extern "C" int hjr_denoise_shards_device(hjr_ctx* c, const hjr_params* p_user, i
     if (const int rc = post_plan(c, p, pl, out_w, out_h, "hjr_denoise_shards_device", nullptr)) return rc;
     const void* const out[4] = { c->d_color.p, c->d_albedo.p, c->d_normal.p, pl.with_var ? c->d_variance.p : nullptr };
     if (const int rc = hjr::check_shards(s, p->width, p->height, out, "hjr_denoise_shards_device")) return rc;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    hipStream_t st = stream_of(c, hip_stream);
     if (const int rc = assemble_launch(s, p->width, p->height, c->d_color.p, c->d_albedo.p, c->d_normal.p, pl.with_var ? c->d_variance.p : nullptr, st)) return rc;
     return denoise_post_stage(c, p, pl, whole || p->sample_end == p->spp, d_out, out_w, out_h, st);
 }
@@ -1696,8 +1697,7 @@ extern "C" int hjr_trace_rays(hjr_ctx* c, int path, uint32_t n, const hjr_ray* s
     KParams kp;
     memset(&kp, 0, sizeof(kp));
     bind_scene_tables(c, kp);
-    int lds_mode = c->frame.lds_mode;
-    if (lds_mode == 0 && c->frame.width == 2) lds_mode = 3;
+    const int lds_mode = launch_layout(c->frame);
     // (`fast` of plan_launch = "megakernel family whatever option pipeline says": the hook has no wavefront path)
     const LaunchPlan pl = plan_launch(c, kp, n, lds_mode, HJR_INTEGRATOR_NEE, true);
     const size_t rays = (size_t)n * sizeof(hjr_ray);
@@ -1735,38 +1735,34 @@ extern "C" int hjr_trace_rays(hjr_ctx* c, int path, uint32_t n, const hjr_ray* s
 #endif
 }
 
-extern "C" int hjr_pack_tiles_device(hjr_ctx* c, const void* d_frame, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, void* d_packed, void* hip_stream)
+// hjr_pack_tiles_device / hjr_unpack_tiles_device: the two kernels take (source, destination) and are otherwise one launch
+static int tiles_device(hjr_ctx* c, bool pack, const void* d_frame, const void* d_packed, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, void* hip_stream)
 {
-    if (!c || !d_frame || !d_packed || w == 0 || h == 0 || world == 0 || rank >= world) { set_error("hjr_pack_tiles_device: bad argument"); return HJR_ERR_ARG; }
+    if (!c || !d_frame || !d_packed || w == 0 || h == 0 || world == 0 || rank >= world) { set_error(std::string(pack ? "hjr_pack_tiles_device" : "hjr_unpack_tiles_device") + ": bad argument"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     const uint32_t n = hjr_owned_tiles(w, h, rank, world);
     if (n == 0) return HJR_OK;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    hipLaunchKernelGGL(hjr_pack_tiles_kernel, dim3((unsigned)(((size_t)n * 64 + 255) / 256)), dim3(256), 0, st, (const float4*)d_frame, (float4*)d_packed, w, h, (w + HJR_TILE - 1) / HJR_TILE, n, rank, world);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    hipLaunchKernelGGL(pack ? hjr_pack_tiles_kernel : hjr_unpack_tiles_kernel, dim3((unsigned)(((size_t)n * 64 + 255) / 256)), dim3(256), 0, stream_of(c, hip_stream),
+                       (const float4*)(pack ? d_frame : d_packed), (float4*)(pack ? d_packed : d_frame), w, h, (w + HJR_TILE - 1) / HJR_TILE, n, rank, world);
+    return launched();
+}
+extern "C" int hjr_pack_tiles_device(hjr_ctx* c, const void* d_frame, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, void* d_packed, void* hip_stream)
+{
+    return tiles_device(c, true, d_frame, d_packed, w, h, rank, world, hip_stream);
 }
 extern "C" int hjr_unpack_tiles_device(hjr_ctx* c, const void* d_packed, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, void* d_frame, void* hip_stream)
 {
-    if (!c || !d_frame || !d_packed || w == 0 || h == 0 || world == 0 || rank >= world) { set_error("hjr_unpack_tiles_device: bad argument"); return HJR_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-    const uint32_t n = hjr_owned_tiles(w, h, rank, world);
-    if (n == 0) return HJR_OK;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    hipLaunchKernelGGL(hjr_unpack_tiles_kernel, dim3((unsigned)(((size_t)n * 64 + 255) / 256)), dim3(256), 0, st, (const float4*)d_packed, (float4*)d_frame, w, h, (w + HJR_TILE - 1) / HJR_TILE, n, rank, world);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return tiles_device(c, false, d_frame, d_packed, w, h, rank, world, hip_stream);
 }
 
 extern "C" int hjr_preview_device(hjr_ctx* c, const void* d_color, uint32_t w, uint32_t h, int tonemap, void* d_rgba8, void* hip_stream)
 {
     if (!c || !d_color || !d_rgba8 || w == 0 || h == 0 || tonemap < HJR_TONEMAP_NONE || tonemap > HJR_TONEMAP_ACES) { set_error("hjr_preview_device: bad argument"); return HJR_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    hipStream_t st = stream_of(c, hip_stream);
     const size_t n = (size_t)w * h;
     hipLaunchKernelGGL(hjr_preview_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4*)d_color, (uchar4*)d_rgba8, n, tonemap);
-    HIPCHK(hipGetLastError());
-    return HJR_OK;
+    return launched();
 }
 
 extern "C" int hjr_synchronize(hjr_ctx* c)
@@ -1809,24 +1805,19 @@ extern "C" int hjr_render_var(hjr_ctx* c, const hjr_params* p_user, float* color
     PassRange pr;
     if (const int rc = check_pass(c, p, 1u | (albedo ? 2u : 0u) | (normal ? 4u : 0u) | (variance ? 8u : 0u), pr)) return rc;
     if (bytes == 0) { end_pass(c, p, pr); return HJR_OK; } // a rank without tiles
-    DevBuf* bufs[3] = { &c->d_color, &c->d_albedo, &c->d_normal };
-    float* host[3] = { color, albedo, normal };
-    for (int i = 0; i < 3; i++) {
+    DevBuf* bufs[4] = { &c->d_color, &c->d_albedo, &c->d_normal, &c->d_variance };
+    float* host[4] = { color, albedo, normal, variance };
+    const size_t len[4] = { bytes, bytes, bytes, bytes / 4 }; // (the variance is one float per pixel: a quarter of an AOV's bytes)
+    for (int i = 0; i < 4; i++) {
         if (!host[i]) continue;
-        if (!bufs[i]->reserve(bytes)) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
-        if (!packed_out) HIPCHK(hipMemsetAsync(bufs[i]->p, 0, bytes, c->stream));
+        if (!bufs[i]->reserve(len[i])) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
+        if (!packed_out) HIPCHK(hipMemsetAsync(bufs[i]->p, 0, len[i], c->stream));
     }
-    if (variance) { // one float per pixel: a quarter of an AOV's bytes
-        if (!c->d_variance.reserve(bytes / 4)) { set_error("hjr_render: AOV allocation failed"); return HJR_ERR_DEVICE; }
-        if (!packed_out) HIPCHK(hipMemsetAsync(c->d_variance.p, 0, bytes / 4, c->stream));
-    }
-    int rc = render_impl(c, p, pr, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr, variance ? c->d_variance.p : nullptr, c->stream);
-    if (rc != HJR_OK) return rc;
-    for (int i = 0; i < 3; i++)
-        if (host[i]) HIPCHK(hipMemcpyAsync(host[i], bufs[i]->p, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (variance) HIPCHK(hipMemcpyAsync(variance, c->d_variance.p, bytes / 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream)); // CUDA_SYNC_CHECK (renderer.h:1242)
-    return HJR_OK;
+    HostStage hs(c);
+    hs.rc = render_impl(c, p, pr, c->d_color.p, albedo ? c->d_albedo.p : nullptr, normal ? c->d_normal.p : nullptr, variance ? c->d_variance.p : nullptr, c->stream);
+    for (int i = 0; i < 4; i++)
+        if (host[i]) hs.down(host[i], bufs[i]->p, len[i]);
+    return hs.finish("hjr_render"); // drains the stream: CUDA_SYNC_CHECK (renderer.h:1242)
 }
 extern "C" int hjr_render(hjr_ctx* c, const hjr_params* p_user, float* color, float* albedo, float* normal)
 {

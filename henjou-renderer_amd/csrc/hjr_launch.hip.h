@@ -34,6 +34,24 @@ struct WorkArea {
     static constexpr size_t BYTES = FIREFLY + 8;
 };
 
+// The build options frame data depends on, as hjr_prepare_transforms read them: frame data is reused for unchanged transforms, refitted, or
+// its instance topology kept, only under an equal key.
+struct BuildKey {
+    bool allow_lds = true, prefer_stack16 = false;  // options "lds_bvh", "lds_stack16"
+    int bvh_width = -1, leaf_max = -1, refine = -1; // "bvh_width", "leaf_max", "bvh_refine" as set (-1: the builder's default)
+    bool device = false;                            // "device_bvh": hjr_commit_transforms runs the build; without it the three below stay 0
+    uint32_t opt_rounds = 0;                        // "device_bvh_opt"
+    bool instances = false, graft = false;          // "device_bvh_instances", and under it "device_bvh_graft"
+    // One word per key, one-to-one over the options' ranges: what Refit::tag and the builder's topology cache compare.  Composed here only;
+    // nothing takes it apart.
+    uint32_t pack() const
+    {
+        return (uint32_t)allow_lds | ((uint32_t)prefer_stack16 << 1) | ((uint32_t)(bvh_width + 1) << 2) | ((uint32_t)(leaf_max + 1) << 6) | ((uint32_t)(refine + 1) << 10) |
+               ((uint32_t)device << 16) | (opt_rounds << 17) | ((uint32_t)instances << 19) | ((uint32_t)graft << 20);
+    }
+    bool operator==(const BuildKey& o) const { return pack() == o.pack(); }
+};
+
 struct hjr_ctx {
     int device = 0;
     int n_cus = 0;
@@ -41,16 +59,20 @@ struct hjr_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hjr::SceneCopy scene;
     bool have_scene = false, have_frame = false;
-    std::vector<float> last_m, last_inv; // instance transforms of the frame data currently on the device
-    uint32_t last_build_tag = 0; // the build options the current frame data was built with
-    hjr::FrameData pending; // built by hjr_prepare_transforms, made current by hjr_commit_transforms
-    std::vector<float> pending_m, pending_inv;
-    bool pending_valid = false, pending_same = false;
-    uint32_t pending_build_tag = 0;
-    double pending_build_ms = 0.0;
-    bool pending_grafted = false;   // ... and they were grafted under a BVH4 top tree (option "device_bvh_graft")
-    uint32_t pending_instances = 0; // option "device_bvh_instances": instance subtrees of the commit being made (0: an ordinary build)
-    bool pending_device = false; // option "device_bvh": hjr_commit_transforms runs the build (pending.lights is the host-built light table)
+    // what the frame data currently on the device was built from
+    struct Built {
+        std::vector<float> m, inv; // instance transforms
+        BuildKey key;
+    } built;
+    // what hjr_prepare_transforms hands to hjr_commit_transforms, which makes it current
+    struct Prepared {
+        bool valid = false;   // a prepare succeeded and no commit has taken it yet
+        bool same = false;    // transforms and key equal `built`: the commit keeps the frame data, nothing below was written
+        hjr::FrameData frame; // host build: the frame data.  key.device: the counts and the host-built light table; the commit runs the build
+        std::vector<float> m, inv;
+        BuildKey key;
+        double build_ms = 0.0; // host wall time of the prepare (a device build: replaced by its HIP-event time)
+    } prep;
     hjr::FrameData frame; // device-built frame data: the counts, format and lights only (the arrays live in d_nodes, d_tri_*)
     hjr::DeviceBvh dbvh;  // the device builder's scene copy, scratch and pending output buffers
     // option "device_bvh_refit": what the next commit needs to know about the current frame data
@@ -117,19 +139,6 @@ struct hjr_ctx {
         DevBuf color[2], variance[2], history[2], gbuf[2], xf[2]; // accumulated unfiltered colour | its variance | h | G-buffer | [M | M^-1] of that render
     } tmp;
     hjr::Options opt; // hjr_set_option (host/options.hpp): the library reads no environment variable
-
-    void release_buffers()
-    {
-        for (DevBuf* b : { &d_nodes, &d_tri_geom, &d_tri_shade, &d_tri_inst, &d_materials, &d_lights, &d_lut, &d_work, &d_texels, &d_tex_desc, &d_srgb_lut, &d_sky, &d_color,
-                           &d_albedo, &d_normal, &d_part_color, &d_part_albedo, &d_part_normal, &d_run_color, &d_run_albedo, &d_run_normal, &d_stat, &d_spill, &d_wf_ctx, &d_tiles, &d_tile_cost, &d_dn_a, &d_dn_b, &d_dn_out, &d_variance, &d_dnv_a, &d_dnv_b, &d_ug_lo, &d_ug_hi, &ad.state, &ad.list })
-            b->release();
-        for (int i = 0; i < 2; i++)
-            for (DevBuf* b : { &tmp.color[i], &tmp.variance[i], &tmp.history[i], &tmp.gbuf[i], &tmp.xf[i] }) b->release();
-        if (ad.h_active) (void)hipHostFree(ad.h_active);
-        if (ad.ready) (void)hipEventDestroy(ad.ready);
-        ad.h_active = nullptr; ad.ready = nullptr;
-        dbvh.release();
-    }
 };
 
 // One render launch as hjr_device.hip::plan_launch decided it: all but the occupancy query and the buffers sized by the grid
