@@ -20,7 +20,7 @@ HD f3 crossf(f3 a, f3 b)
     return V(fmaf(a.y, b.z, -(a.z * b.y)), fmaf(a.z, b.x, -(a.x * b.z)), fmaf(a.x, b.y, -(a.y * b.x)));
 }
 // canonical ray/triangle test — the same operation sequence as the oracle's ray_tri().  Two shapes of the same arithmetic:
-// with early returns (EARLY; the megakernel on LDS-resident scenes: whole waves leave at the first two tests often enough, 2.5 % faster there) and
+// with early exits (EARLY; the megakernel on LDS-resident scenes: whole waves leave at the first two tests often enough, 2.5 % faster there) and
 // with all seven conditions evaluated and combined at the end (scenes read from memory and the wavefront kernels: the fewer branches the better,
 // 1.2 % / 0.8 % faster there).  A zero
 // determinant makes inv infinite and u infinite or NaN; `det != 0` keeps the result explicit.  (profiles/r03_experiments.md)
@@ -30,18 +30,35 @@ HD bool ray_tri(f3 v0, f3 v1, f3 v2, f3 o, f3 d, float tmin, float tmax, float& 
     f3 e1 = v1 - v0, e2 = v2 - v0;
     f3 p = crossf(d, e2);
     float det = dotf(e1, p);
-    if (EARLY && det == 0.0f) return false;
-    float inv = exact_div(1.0f, det); // == 1.0f / det, whatever the division flags of the translation unit
-    f3 tv = o - v0;
-    float u = dotf(tv, p) * inv;
-    if (EARLY && !(u >= 0.0f && u <= 1.0f)) return false;
-    f3 q = crossf(tv, e1);
-    float v = dotf(d, q) * inv;
-    if (EARLY && !(v >= 0.0f && u + v <= 1.0f)) return false;
-    float tt = dotf(e2, q) * inv;
-    const bool ok = (det != 0.0f) & (u >= 0.0f) & (u <= 1.0f) & (v >= 0.0f) & (u + v <= 1.0f) & (tt > tmin) & (tt < tmax);
-    if (ok) { t = tt; b1 = u; b2 = v; }
-    return ok;
+    if constexpr (EARLY) {
+        // the exits are wave-uniform — the wave leaves when NO lane is left after a stage (one scalar branch on the ballot, no exec
+        // bookkeeping); a lane that failed a stage computes on next to the others and its verdict is the predicate `ok`.  (SIMT runs a
+        // block while any lane is in it, so divergent returns issue the same vector instructions.)
+        bool ok = det != 0.0f;
+        if (__ballot(ok) == 0ull) return false;
+        float inv = exact_div(1.0f, det);
+        f3 tv = o - v0;
+        float u = dotf(tv, p) * inv;
+        ok &= (u >= 0.0f) & (u <= 1.0f);
+        if (__ballot(ok) == 0ull) return false;
+        f3 q = crossf(tv, e1);
+        float v = dotf(d, q) * inv;
+        ok &= (v >= 0.0f) & (u + v <= 1.0f);
+        if (__ballot(ok) == 0ull) return false;
+        float tt = dotf(e2, q) * inv;
+        t = tt; b1 = u; b2 = v; // (every lane that is still here writes: the caller reads them under the verdict only, or selects with it)
+        return ok & (tt > tmin) & (tt < tmax);
+    } else {
+        float inv = exact_div(1.0f, det); // == 1.0f / det, whatever the division flags of the translation unit
+        f3 tv = o - v0;
+        float u = dotf(tv, p) * inv;
+        f3 q = crossf(tv, e1);
+        float v = dotf(d, q) * inv;
+        float tt = dotf(e2, q) * inv;
+        const bool ok = (det != 0.0f) & (u >= 0.0f) & (u <= 1.0f) & (v >= 0.0f) & (u + v <= 1.0f) & (tt > tmin) & (tt < tmax);
+        if (ok) { t = tt; b1 = u; b2 = v; }
+        return ok;
+    }
 }
 
 // ---- per-lane traversal stack in LDS, element i of this lane at stack[i * BLOCK] (conflict-free columns).  Small scenes that
@@ -363,14 +380,15 @@ HD bool traverse_fused(const float4* nodes, const float4* tris, const bool a_val
                 if (STATS) { if (phase == 0) ca.box += nb; else cb.box += nb; }
             }
             const uint32_t n_inner = (uint32_t)__popcll(__ballot(!(cur & HJR_LEAF_FLAG)));
-            if (n_inner == 0u || n_inner < node_min) break;
+            if (n_inner < node_min) break; // (node_min >= 1, hjr_params.hip.h: this is also "no lane holds an inner node")
         }
         // ... then all lanes that hold a leaf test its triangles together
         bool done = (cur == HJR_TRAV_DONE);
         if (!done && (cur & HJR_LEAF_FLAG)) {
             HJR_TD_WAVE(4)
             HJR_TD_LANE(5)
-            const uint32_t first = cur & 0x07ffffffu, count = (cur >> 27) & 15u;
+            const uint32_t first = cur & 0x07ffffffu;
+            uint32_t count = (cur >> 27) & 15u;
             const float tri_tmax = (phase == 0) ? a_tmax : 1e16f;
             for (uint32_t i = 0; i < count; i++) {
                 HJR_TD_WAVE(6)
@@ -379,7 +397,24 @@ HD bool traverse_fused(const float4* nodes, const float4* tris, const bool a_val
                 const float4 g0 = g[0], g1 = g[1], g2 = g[2];
                 float t, b1, b2;
                 if (STATS) { if (phase == 0) ca.tri++; else cb.tri++; }
-                if (ray_tri<ST::kTriEarly>(V(g0.x, g0.y, g0.z), V(g0.w, g1.x, g1.y), V(g1.z, g1.w, g2.x), o, d, tmin, tri_tmax, t, b1, b2)) {
+                const bool ok = ray_tri<ST::kTriEarly>(V(g0.x, g0.y, g0.z), V(g0.w, g1.x, g1.y), V(g1.z, g1.w, g2.x), o, d, tmin, tri_tmax, t, b1, b2);
+                if constexpr (ST::kTriEarly) {
+                    // LDS-resident megakernel: everything behind the test sits behind ONE wave-uniform branch — an iteration in which no lane
+                    // hits pays that branch and nothing else — and is written as selects.  An occluded shadow lane ends its part in the loop
+                    // by zeroing its own count: no `break`, so the loop goes on under the one compare i < count; the lane's later triangles
+                    // are neither tested nor counted.  `occluded` is set from `done` behind the loop (a lane enters the loop with done ==
+                    // false): every flag carried through the loop costs a mask merge (andn2 / and / or) in every iteration.
+                    if (__ballot(ok) != 0ull) {
+                        const bool shadow_hit = ok & (phase == 0);
+                        const uint32_t prim = f2bits(g2.y);
+                        // order-independent closest-hit rule: smaller t wins; equal t -> smaller global prim id
+                        const bool closer = ok & (phase != 0) & ((hit.prim == 0xffffffffu) | (t < hit.t) | ((t == hit.t) & (prim < hit.prim)));
+                        hit.t = closer ? t : hit.t; hit.b1 = closer ? b1 : hit.b1; hit.b2 = closer ? b2 : hit.b2;
+                        hit.k = closer ? first + i : hit.k; hit.prim = closer ? prim : hit.prim;
+                        done |= shadow_hit;
+                        count = shadow_hit ? 0u : count;
+                    }
+                } else if (ok) {
                     if (phase == 0) { occluded = true; done = true; break; }
                     const uint32_t prim = f2bits(g2.y);
                     // order-independent closest-hit rule: smaller t wins; equal t -> smaller global prim id
@@ -388,6 +423,7 @@ HD bool traverse_fused(const float4* nodes, const float4* tris, const bool a_val
                     }
                 }
             }
+            if constexpr (ST::kTriEarly) { if (done) occluded = true; }
             if (!done) {
                 if (sp > 0) { sp--; cur = stack.get(sp); }
                 else done = true;
