@@ -173,6 +173,7 @@ GBUFFER_DTYPE = np.dtype([("prim", "<u4"), ("inst", "<u4"), ("t", "<f4"), ("b1",
 GBUFFER_MISS = 0xffffffff
 TEMPORAL_ALPHA = np.float32(0.2)  # HJR_TEMPORAL_ALPHA
 TEMPORAL_SNAP = np.float32(0.125)  # HJR_TEMPORAL_SNAP
+TEMPORAL_MOMENTS_MIN = np.float32(4.0)  # HJR_TEMPORAL_MOMENTS_MIN
 
 
 class TemporalFrame(_Sized):
@@ -260,6 +261,8 @@ def lib():
             "hjr_render_gbuffer_cov_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_temporal_accumulate_moments": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_temporal_accumulate_moments_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_reset": [C.c_void_p],
             "hjr_upscale_guided": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
             "hjr_upscale_guided_device": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -663,9 +666,11 @@ class Device:
         keep.append(arrs)
         return f
 
-    def temporal_accumulate(self, prev, cur):
+    def temporal_accumulate(self, prev, cur, moments=False):
         """hjr_temporal_accumulate on dicts of arrays (keys: camera, transforms, inv_transforms, gbuffer, color, variance, optionally coverage; prev also
-        history; prev None = no previous frame): returns (color [h, w, 4], variance [h, w], history [h, w])."""
+        history; prev None = no previous frame): returns (color [h, w, 4], variance [h, w], history [h, w]).  moments=True:
+        hjr_temporal_accumulate_moments, which reads prev["moments"] ([h, w, 2], passed as its prev_moments argument) and returns a fourth
+        array, the moments [h, w, 2]."""
         keep = []
         fc = self._temporal_frame(cur, keep)
         fp = None if prev is None else self._temporal_frame(prev, keep)
@@ -673,6 +678,17 @@ class Device:
         color = np.zeros((h, w, 4), dtype=np.float32)
         variance = np.zeros((h, w), dtype=np.float32)
         history = np.zeros((h, w), dtype=np.float32)
+        if moments:
+            mom = np.zeros((h, w, 2), dtype=np.float32)
+            pm = None
+            if prev is not None and prev.get("moments") is not None:
+                pm = np.ascontiguousarray(prev["moments"], dtype=np.float32)
+                if pm.shape != (h, w, 2):
+                    raise ValueError("temporal frame: moments must be [height, width, 2]")
+            _check(lib().hjr_temporal_accumulate_moments(self._h, None if fp is None else C.byref(fp), C.byref(fc), color.ctypes.data, variance.ctypes.data,
+                                                         history.ctypes.data, None if pm is None else pm.ctypes.data, mom.ctypes.data),
+                   "hjr_temporal_accumulate_moments")
+            return color, variance, history, mom
         _check(lib().hjr_temporal_accumulate(self._h, None if fp is None else C.byref(fp), C.byref(fc), color.ctypes.data, variance.ctypes.data,
                                              history.ctypes.data), "hjr_temporal_accumulate")
         return color, variance, history

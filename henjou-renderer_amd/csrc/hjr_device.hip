@@ -127,7 +127,7 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
     // rule 10 keeps chunk sums from a frame's first pass on: an unfinished progressive frame cannot change its rule half way (as hjr_set_adaptive).
     // "firefly_clamp" alone with "firefly_clamp_passes" off keeps what it always did: the next pass is refused by check_pass
     if (i == hjr::OPT_FIREFLY_CLAMP_PASSES || (i == hjr::OPT_FIREFLY_CLAMP && c->opt.get(hjr::OPT_FIREFLY_CLAMP_PASSES, 0) == 1)) { c->pass.active = false; c->ad.frame = false; }
-    if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL || i == hjr::OPT_DENOISE_TEMPORAL_COVERAGE) c->tmp.have_prev = false; // setting any of these options drops the history
+    if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL || i == hjr::OPT_DENOISE_TEMPORAL_COVERAGE || i == hjr::OPT_DENOISE_TEMPORAL_MOMENTS) c->tmp.have_prev = false; // setting any of these options drops the history
     if (i == hjr::OPT_HOST_THREADS) hjr::set_host_threads(value);
     return HJR_OK;
 }
@@ -1325,8 +1325,9 @@ extern "C" int hjr_render_gbuffer_cov(hjr_ctx* c, const hjr_params* p_user, uint
 
 // the accumulation kernel on device memory; the two frames were checked by the callers
 // prev_cov / cur_cov: the two sides' `coverage`; with both 0 the launch is the plain instantiation's, as before the coverage rules existed
+// d_out_mom != nullptr: the temporal moments (d_prev_mom: prev's, checked by the callers); nullptr: the launch as before they existed
 static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_color, void* d_var, void* d_hist, hipStream_t st,
-                           uint32_t prev_cov, uint32_t cur_cov)
+                           uint32_t prev_cov, uint32_t cur_cov, const void* d_prev_mom = nullptr, void* d_out_mom = nullptr)
 {
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
@@ -1336,13 +1337,17 @@ static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalS
     a.n_tris = c->have_scene ? c->scene.n_triangles : 0xffffffffu; // prim ids are checked against the uploaded scene
     a.prev_cov = prev ? prev_cov : 0u; a.cur_cov = cur_cov;
     a.out_color = (float4*)d_color; a.out_variance = (float*)d_var; a.out_history = (float*)d_hist;
+    a.prev_moments = prev ? (const float2*)d_prev_mom : nullptr; a.out_moments = (float2*)d_out_mom;
     using Kernel = void (*)(TemporalArgs);
-    static const Kernel kernels[2] = { hjr_temporal_kernel<false>, hjr_temporal_kernel<true> }; // [a side carries coverage]
-    hipLaunchKernelGGL(kernels[a.prev_cov || a.cur_cov], image_grid(w, h), dim3(256), 0, st, a);
+    static const Kernel kernels[2][2] = { // [a side carries coverage][moments]
+        { hjr_temporal_kernel<false, false>, hjr_temporal_kernel<false, true> },
+        { hjr_temporal_kernel<true, false>, hjr_temporal_kernel<true, true> },
+    };
+    hipLaunchKernelGGL(kernels[a.prev_cov || a.cur_cov][d_out_mom != nullptr], image_grid(w, h), dim3(256), 0, st, a);
     return launched();
 }
 // argument checks of hjr_temporal_accumulate[_device]: the sized structs, sizes that agree, every pointer the kernel reads
-static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, hjr_temporal_frame& prev, hjr_temporal_frame& cur, bool& have_prev)
+static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, hjr_temporal_frame& prev, hjr_temporal_frame& cur, bool& have_prev, bool moments = false, const void* prev_moments = nullptr)
 {
     if (!hjr::abi_take(cur_user, cur, "hjr_temporal_accumulate")) return HJR_ERR_ARG;
     have_prev = prev_user != nullptr;
@@ -1352,6 +1357,7 @@ static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal
     if (have_prev) {
         if (prev.width != cur.width || prev.height != cur.height || prev.n_instances != cur.n_instances) { set_error("hjr_temporal_accumulate: width, height and n_instances of the two frames must agree"); return HJR_ERR_ARG; }
         if (!prev.gbuffer || !prev.color || !prev.variance || !prev.history || (prev.n_instances && (!prev.transforms12 || !prev.inv_transforms12))) { set_error("hjr_temporal_accumulate: null pointer in the previous frame"); return HJR_ERR_ARG; }
+        if (moments && !prev_moments) { set_error("hjr_temporal_accumulate_moments: the previous frame has no moments"); return HJR_ERR_ARG; }
     }
     return HJR_OK;
 }
@@ -1362,27 +1368,36 @@ static TemporalSide temporal_side(const hjr_temporal_frame& f)
     s.color = (const float4*)f.color; s.variance = f.variance; s.history = f.history;
     return s;
 }
-extern "C" int hjr_temporal_accumulate_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist, void* hip_stream)
+// d_mom == nullptr: hjr_temporal_accumulate_device, and d_prev_mom is not looked at
+extern "C" int hjr_temporal_accumulate_moments_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist,
+                                                      const void* d_prev_mom, void* d_mom, void* hip_stream)
 {
     if (!c || !d_color || !d_var || !d_hist) { set_error("hjr_temporal_accumulate: null argument"); return HJR_ERR_ARG; }
     hjr_temporal_frame prev, cur;
     bool have_prev;
-    if (const int rc = temporal_take(prev_user, cur_user, prev, cur, have_prev)) return rc;
+    if (const int rc = temporal_take(prev_user, cur_user, prev, cur, have_prev, d_mom != nullptr, d_prev_mom)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const TemporalSide ps = have_prev ? temporal_side(prev) : TemporalSide(), cs = temporal_side(cur);
     return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, stream_of(c, hip_stream),
-                           have_prev ? prev.coverage : 0u, cur.coverage);
+                           have_prev ? prev.coverage : 0u, cur.coverage, have_prev && d_mom ? d_prev_mom : nullptr, d_mom);
 }
-extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist)
+extern "C" int hjr_temporal_accumulate_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist, void* hip_stream)
+{
+    return hjr_temporal_accumulate_moments_device(c, prev_user, cur_user, d_color, d_var, d_hist, nullptr, nullptr, hip_stream);
+}
+// out_mom == nullptr: hjr_temporal_accumulate, and prev_mom is not looked at
+extern "C" int hjr_temporal_accumulate_moments(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist,
+                                               const float* prev_mom, float* out_mom)
 {
     if (!c || !out_color || !out_var || !out_hist) { set_error("hjr_temporal_accumulate: null argument"); return HJR_ERR_ARG; }
     hjr_temporal_frame f[2]; // [0] prev, [1] cur
     bool have_prev;
-    if (const int rc = temporal_take(prev_user, cur_user, f[0], f[1], have_prev)) return rc;
+    if (const int rc = temporal_take(prev_user, cur_user, f[0], f[1], have_prev, out_mom != nullptr, prev_mom)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t npx = (size_t)f[1].width * f[1].height, nx = (size_t)f[1].n_instances * 48;
-    // one temporary buffer: per side [M | M^-1 | gbuffer | colour | variance | history], then the three outputs
-    const size_t side = (2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4) + 255) & ~(size_t)255, outs = npx * (16 + 4 + 4); // (float4 images stay 16-byte aligned)
+    const size_t mom = out_mom ? npx * 8 : 0; // the moments: prev's behind its side's images, the output behind the three outputs
+    // one temporary buffer: per side [M | M^-1 | gbuffer | colour | variance | history | (moments)], then the three outputs (and the moments)
+    const size_t side = (2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4) + mom + 255) & ~(size_t)255, outs = npx * (16 + 4 + 4) + mom; // (float4 images stay 16-byte aligned)
     HostStage hs(c);
     if (!hs.buf.reserve(2 * side + outs)) { set_error("hjr_temporal_accumulate: device allocation failed"); return HJR_ERR_DEVICE; }
     TemporalSide s[2];
@@ -1398,14 +1413,21 @@ extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* pre
         }
         s[i].cam = f[i].camera; s[i].m = (const float*)dst[0]; s[i].inv = (const float*)dst[1]; s[i].gbuf = (const hjr_gbuffer_px*)dst[2];
         s[i].color = (const float4*)dst[3]; s[i].variance = (const float*)dst[4]; s[i].history = (const float*)dst[5];
+        if (i == 0 && mom) hs.up(b, prev_mom, mom); // (b: behind the history, 96 n + 72 npx bytes into the side: float2 stays 8-byte aligned)
     }
     char* const o = (char*)hs.buf.p + 2 * side;
+    const char* const pm = (const char*)hs.buf.p + 2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4);
     if (hs.ok()) hs.rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream,
-                                         have_prev ? f[0].coverage : 0u, f[1].coverage);
+                                         have_prev ? f[0].coverage : 0u, f[1].coverage, have_prev && mom ? pm : nullptr, mom ? o + npx * 24 : nullptr);
     hs.down(out_color, o, npx * 16);
     hs.down(out_var, o + npx * 16, npx * 4);
     hs.down(out_hist, o + npx * 20, npx * 4);
+    if (mom) hs.down(out_mom, o + npx * 24, mom);
     return hs.finish("hjr_temporal_accumulate");
+}
+extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist)
+{
+    return hjr_temporal_accumulate_moments(c, prev_user, cur_user, out_color, out_var, out_hist, nullptr, nullptr);
 }
 extern "C" int hjr_temporal_reset(hjr_ctx* c)
 {
@@ -1426,6 +1448,7 @@ static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
     const int k = t.cur;
     if (!t.color[k].reserve(npx * 16) || !t.variance[k].reserve(npx * 4) || !t.history[k].reserve(npx * 4) || !t.gbuf[k].reserve(npx * sizeof(hjr_gbuffer_px)) ||
         !t.xf[k].reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
+    if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) && !t.moments[k].reserve(npx * 8)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     return HJR_OK;
 }
 static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
@@ -1450,7 +1473,9 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
         s[i].color = (const float4*)t.color[q].p; s[i].variance = (const float*)t.variance[q].p; s[i].history = (const float*)t.history[q].p;
     }
     s[1].color = (const float4*)d_color; s[1].variance = (const float*)d_var; s[1].history = nullptr;
-    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, st, cov, cov)) return rc;
+    const bool mom = c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) != 0; // option "denoise_temporal_moments": both slots carry (m1, m2) (setting it drops the history, so the previous slot has them)
+    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, st, cov, cov,
+                                       mom && t.have_prev ? t.moments[k ^ 1].p : nullptr, mom ? t.moments[k].p : nullptr)) return rc;
     d_color = t.color[k].p; d_var = t.variance[k].p;
     if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur = k ^ 1; }
     return HJR_OK;

@@ -1,7 +1,7 @@
 // Temporal accumulation with reprojection for the Denoise modes: the temporal half of SVGF (Schied et al., HPG 2017) in front of the
 // variance-guided a-trous filter (hjr_denoise.hip.h).  Two kernels, both outside the render kernels (no render kernel knows about them):
 //   hjr_gbuffer_kernel<WIDTH, COV>   first-hit record of every pixel's centre ray, by the stand-alone traversal the tile classifier uses;
-//   hjr_temporal_kernel<COV>    one lane per pixel: reprojects the pixel's surface point into the previous frame, gathers the previous
+//   hjr_temporal_kernel<COV, MOM>  one lane per pixel: reprojects the pixel's surface point into the previous frame, gathers the previous
 //                               frame's accumulated colour / variance / history length with four validated bilinear taps and blends.
 // Included by hjr_device.hip only: correctly rounded divide, no contraction, denormals on.  Specified to the bit, so that the test suite's
 // CPU checker (tests/native/temporal_ref.cpp) restates it independently.  fp32 throughout, every operation as written, left to right:
@@ -41,7 +41,8 @@
 //      cv = cur.variance;  unknown |= !(cv < HJR_VARIANCE_UNKNOWN);  om = 1 - al;
 //      var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0)     (fmaxf(NaN, 0) = 0 never reaches the sum).
 //   The variance is that of a convex combination of independent estimates (frames are independent: the RNG index is frame * spp + s), which
-//   is why it is propagated and not estimated from temporal moments.  K_PLANE = 1, K_DIST = 3: "a tap is at most one pixel from the exact
+//   is why it is propagated and not estimated from temporal moments (section TEMPORAL MOMENTS below adds that estimate, opt-in, for frames
+//   whose own variance is unknown).  K_PLANE = 1, K_DIST = 3: "a tap is at most one pixel from the exact
 //   point" (DESIGN.md §11 has what was measured).
 // Hostile input: every table index (instance of the current record and of each tap) is range-checked before it is used, no tap outside the
 // image is read, and float -> int conversion happens only after the float range check; nothing else indexes memory.
@@ -70,6 +71,23 @@
 //       T.pad == G.pad (all 32 bits).  Step 4 proceeds with that one tap: S = 1, and the divides are still performed.
 //   In words: a mixed pixel keeps its history only from the pixel it coincides with, and otherwise restarts; a full pixel never taps a mixed
 //   one.  A static sequence still accumulates everywhere: the reprojection lands on the centre up to rounding.
+//
+// TEMPORAL MOMENTS (hjr_temporal_kernel<COV, true>: the ACCUMULATION above, with or without the coverage rules, with one more input,
+//   prev.moments (the entry points' prev_moments argument, not a field of hjr_temporal_frame), and one more output, both float2 (m1, m2) per pixel: the accumulated first and second moment of the luminance
+//     l = (cur.r + cur.g) + cur.b     of the current frame's colour as the kernel reads it.   DESIGN.md §11.7.)
+//   RESTART (every case above): additionally  m1 = l,  m2 = l * l.   Colour, variance and h are the ones above.
+//   4. per valid tap, in tap order, both sums from +0.0f, pm = prev.moments[tap]:   M1 = M1 + pm.x * w_k;   M2 = M2 + pm.y * w_k.
+//      After S > 0:   m1p = M1 / S,  m2p = M2 / S  (one divide each);   m1 = m1p + (l - m1p) * al,   m2 = m2p + (l * l - m2p) * al
+//      (al the colour's blend factor).   If  h >= HJR_TEMPORAL_MOMENTS_MIN  the variance of step 4 is replaced by
+//        k = fmaxf(1 / h, HJR_TEMPORAL_ALPHA / (2 - HJR_TEMPORAL_ALPHA));   d = m2 - m1 * m1;
+//        var = finite(d) ? fmaxf(d, 0) * (k / (1 - k)) : HJR_VARIANCE_UNKNOWN;   a var that is not below HJR_VARIANCE_UNKNOWN is written as
+//        HJR_VARIANCE_UNKNOWN.   Otherwise (h < HJR_TEMPORAL_MOMENTS_MIN) the variance is step 4's, "unknown" included.
+//   k is the sum of the squared blend weights of the frames in the accumulated colour: 1 / h while the blend is a plain mean, with limit
+//   alpha / (2 - alpha) once al stays at alpha.  1 / (1 - k) unbiases the weighted sample variance m2 - m1 * m1 of one frame's luminance, and
+//   the factor k turns the variance of one frame's value into that of the accumulated colour, which is what rule 7 and the filter expect.
+//   With a fractional h after bilinear mixing the weights are not exactly those, so k is approximate there.
+//   Rules 2' / 3' choose the taps as above; the moments ride on whichever taps are chosen.  Moments are only ever multiplied, added and
+//   compared: NaN, Inf and values whose square overflows end in HJR_VARIANCE_UNKNOWN or a finite variance, and index nothing.
 #pragma once
 #include "hjr_aux.hip.h" // TileStack: the classifier's stacks
 
@@ -174,6 +192,8 @@ struct TemporalArgs {
     float* out_variance;
     float* out_history;
     uint32_t prev_cov, cur_cov; // COV: the two sides' hjr_temporal_frame.coverage
+    const float2* prev_moments; // MOM: the previous frame's moments (at the end: the other fields keep their places in the argument block)
+    float2* out_moments;        // MOM
 };
 
 HD f3 t_xf(const float* __restrict__ m, f3 p)
@@ -189,7 +209,9 @@ HD bool t_mixed(uint32_t pad) { const uint32_t total = (pad >> 8) & 0xffu; retur
 
 // COV: the coverage-aware accumulation (rules 2' and 3' of the header comment), launched only when a side carries coverage.  Its four
 // expressions (g_mixed, the snap tap, n_taps, the pad test of a tap) are constants in the plain instantiation and fold away there.
-template <bool COV>
+// MOM: the temporal luminance moments (section TEMPORAL MOMENTS of the header comment): one float2 load per valid tap, one float2 store
+// per pixel; every line of it sits under `if constexpr (MOM)`, so the MOM = false instantiations are the code they were without it.
+template <bool COV, bool MOM>
 __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
 {
     const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
@@ -199,6 +221,8 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
     const float cv = A.cur.variance[pix];
     float4 out = cc;
     float var = cv, hist = 1.0f;
+    [[maybe_unused]] float lum = 0.0f, m1 = 0.0f, m2 = 0.0f;
+    if constexpr (MOM) { lum = (cc.x + cc.y) + cc.z; m1 = lum; m2 = lum * lum; }
     const hjr_gbuffer_px G = A.cur.gbuf[pix];
     if (A.have_prev && G.prim != 0xffffffffu && G.prim < A.n_tris && G.inst < A.n_instances) {
         const float W = (float)A.width, H = (float)A.height;
@@ -230,6 +254,7 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
             const float* const m_cur = A.cur.m + (size_t)G.inst * 12u;
             float S = 0.0f, Cx = 0.0f, Cy = 0.0f, Cz = 0.0f, Vs = 0.0f, Hs = 0.0f;
             bool unknown = false;
+            [[maybe_unused]] float M1 = 0.0f, M2 = 0.0f;
             constexpr int kUnroll = COV ? 4 : 1; // the loop shapes each instantiation was measured with: the coverage rules unrolled, the plain loop rolled
 #pragma unroll kUnroll
             for (int k = 0; k < 4; k++) {
@@ -251,6 +276,10 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
                 unknown = unknown || !(pv < HJR_VARIANCE_UNKNOWN);
                 Vs = Vs + fmaxf(pv, 0.0f) * wk[k];
                 Hs = Hs + A.prev.history[tap] * wk[k];
+                if constexpr (MOM) {
+                    const float2 pm = A.prev_moments[tap];
+                    M1 = M1 + pm.x * wk[k]; M2 = M2 + pm.y * wk[k];
+                }
             }
             if (S > 0.0f) {
                 const float px_ = Cx / S, py_ = Cy / S, pz_ = Cz / S, v_prev = Vs / S, h_prev = Hs / S;
@@ -260,10 +289,21 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
                 unknown = unknown || !(cv < HJR_VARIANCE_UNKNOWN);
                 const float om = 1.0f - al;
                 var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0.0f);
+                if constexpr (MOM) {
+                    const float m1p = M1 / S, m2p = M2 / S;
+                    m1 = m1p + (lum - m1p) * al; m2 = m2p + (lum * lum - m2p) * al;
+                    if (hist >= HJR_TEMPORAL_MOMENTS_MIN) {
+                        const float kk = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA / (2.0f - HJR_TEMPORAL_ALPHA));
+                        const float d = m2 - m1 * m1;
+                        const float mv = t_finite(d) ? fmaxf(d, 0.0f) * (kk / (1.0f - kk)) : HJR_VARIANCE_UNKNOWN;
+                        var = mv < HJR_VARIANCE_UNKNOWN ? mv : HJR_VARIANCE_UNKNOWN;
+                    }
+                }
             }
         }
     }
     A.out_color[pix] = out;
     A.out_variance[pix] = var;
     A.out_history[pix] = hist;
+    if constexpr (MOM) A.out_moments[pix] = make_float2(m1, m2);
 }

@@ -70,6 +70,7 @@ inline const std::vector<KeyRow>& key_table_since()
     using O = hjr_render_option;
     static const std::vector<KeyRow> t = {
         { "firefly_clamp_passes", 13, &O::device_bvh_opt, ENC_BITS, 23, 1, READ_BOOL, "firefly_clamp", WHO_EVERY }, // (every rank keeps its own chunk sums)
+        { "denoise_temporal_moments", 14, &O::device_bvh_opt, ENC_BITS, 15, 1, READ_BOOL, nullptr, WHO_FILTER },
     };
     return t;
 }

@@ -146,7 +146,7 @@ typedef struct hjr_render_option {
     int32_t device_bvh_opt;      /* default 0; bits 0..7: key "device_bvh_opt", 0..3 treelet-restructuring rounds of that device build;
                                   * bit 8: key "device_bvh_instances"; bit 9: key "device_bvh_graft"; bit 10: key "denoise_variance_spatial";
                                   * bit 11: key "upscale_guided"; bits 12..14: key "denoise_temporal_coverage", 0, 2, 3 or 4; bits 16..22: key
-                                  * "firefly_clamp", 0..64; bit 23: key "firefly_clamp_passes" (bits 10 and up are the section's spare bits:
+                                  * "firefly_clamp", 0..64; bit 23: key "firefly_clamp_passes"; bit 15: key "denoise_temporal_moments" (bits 10 and up are the section's spare bits:
                                   * those keys have nothing to do with the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
@@ -535,9 +535,24 @@ int hjr_render_gbuffer_cov_device(hjr_ctx*, const hjr_params*, uint32_t side, vo
  * mixed.  A current pixel that is mixed keeps its history only from the previous pixel it coincides with: the reprojected position must lie
  * within HJR_TEMPORAL_SNAP of a pixel centre in x and in y, that pixel is the only tap (weight 1, the usual validity tests) and, if the
  * previous side carries coverage, its pad word must equal the current one; otherwise the pixel restarts.  pad is only compared, never an
- * index. */
+ * index.
+ * Temporal moments (hjr_temporal_accumulate_moments[_device] with out_moments != NULL): SVGF's temporal variance estimate.
+ * Every pixel also carries the accumulated first and second moment (m1, m2: float2, width x height) of the luminance l = (r + g) + b of the
+ * current frame's colour.  A restarting pixel starts them at (l, l * l); otherwise the taps that carry the colour carry the previous
+ * moments with the same weights, and l and l * l are blended in with the colour's alpha.  Once the pixel's history length h has reached
+ * HJR_TEMPORAL_MOMENTS_MIN the output variance is not the propagated one but
+ *   max(m2 - m1 * m1, 0) * k / (1 - k),  k = max(1 / h, HJR_TEMPORAL_ALPHA / (2 - HJR_TEMPORAL_ALPHA)):
+ * the unbiased weighted sample variance of one frame's luminance, scaled by the sum of the squared blend weights to the variance of the
+ * accumulated colour (approximate where bilinear mixing made h fractional).  A difference that is not finite, or a product that is not
+ * below HJR_VARIANCE_UNKNOWN, is HJR_VARIANCE_UNKNOWN.  Below the threshold the variance is the propagated one, "unknown" included.  The
+ * coverage rules choose the taps as without moments.  Moments are only multiplied, added and compared: NaN, Inf or huge caller-made values
+ * cannot fault.  The previous frame's moments are the argument prev_moments (hjr_temporal_frame itself is unchanged: its size and its last
+ * field, `coverage`, are part of the ABI callers were built against); out_moments == NULL is hjr_temporal_accumulate[_device], bit for bit
+ * and the same launch, and prev_moments is then ignored; out_moments != NULL with a prev != NULL and prev_moments == NULL is HJR_ERR_ARG
+ * and nothing is enqueued; with prev == NULL prev_moments is ignored. */
 #define HJR_TEMPORAL_ALPHA 0.2f  /* the published value */
 #define HJR_TEMPORAL_SNAP 0.125f /* a mixed pixel's reprojection may lie this many pixels off a pixel centre, per axis */
+#define HJR_TEMPORAL_MOMENTS_MIN 4.0f /* history length from which the variance comes from the moments (the published switch) */
 typedef struct hjr_temporal_frame {
     uint32_t struct_size, width, height, n_instances;
     hjr_camera camera;
@@ -550,6 +565,12 @@ int hjr_temporal_accumulate(hjr_ctx*, const hjr_temporal_frame* prev /* NULL = n
                             float* out_variance, float* out_history);
 int hjr_temporal_accumulate_device(hjr_ctx*, const hjr_temporal_frame* prev, const hjr_temporal_frame* cur, void* d_out_color, void* d_out_variance,
                                    void* d_out_history, void* hip_stream);
+int hjr_temporal_accumulate_moments(hjr_ctx*, const hjr_temporal_frame* prev /* NULL = none */, const hjr_temporal_frame* cur, float* out_color,
+                                    float* out_variance, float* out_history, const float* prev_moments /* float2, of prev */,
+                                    float* out_moments /* float2; NULL = hjr_temporal_accumulate */);
+int hjr_temporal_accumulate_moments_device(hjr_ctx*, const hjr_temporal_frame* prev, const hjr_temporal_frame* cur, void* d_out_color,
+                                           void* d_out_variance, void* d_out_history, const void* d_prev_moments, void* d_out_moments,
+                                           void* hip_stream);
 /* The guided 2x upscale (csrc/hjr_denoise.hip.h has the arithmetic to the bit, DESIGN.md §11.4 what was measured): a joint-bilateral stand-in
  * for the bilinear upscale of HJR_MODE_DENOISE_UPSCALE2X.  Every pixel of the out_w x out_h output takes the four bilinear taps (weights 0.75 /
  * 0.25, clamped indices) of the in_w x in_h colour image and keeps those whose low-resolution G-buffer record shows the surface of the output
@@ -677,19 +698,26 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  records in the history slots and accumulate with `coverage` set on both sides (rules 2' and 3' of
                                  csrc/hjr_temporal.hip.h).  1 and values above 4 are HJR_ERR_ARG.  No effect unless "denoise_temporal" is on.
                                  Setting it (any value) drops the temporal history.  0 (default): today's call, bit for bit, the same launches
+   "denoise_temporal_moments" 0 1  1: with "denoise_temporal" on, hjr_render_denoised and hjr_denoise_shards_device keep a moments buffer in each of
+                                 the two history slots and accumulate with hjr_temporal_accumulate_moments_device: from a history length of
+                                 HJR_TEMPORAL_MOMENTS_MIN on a pixel's variance comes from its own luminance history.  Meant for frames of at
+                                 most 8 spp together with "denoise_variance_spatial", which supplies the variance of shorter histories (without
+                                 it those stay "unknown").  A sample pass that does not end the frame computes the moments and discards them.
+                                 No effect unless "denoise_temporal" is on.  Setting it (any value) drops the temporal history.  0 (default):
+                                 today's call, bit for bit, the same launches
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
- * Fourteen more keys of that section set the context option of their name; where each is stored is in the comment on hjr_render_option.
+ * Fifteen more keys of that section set the context option of their name; where each is stored is in the comment on hjr_render_option.
  * "force_rebuild" is set by hjr_render_file only.  "verbose", "device_bvh", "device_bvh_refit": N (integer 0..1000), "device_bvh_opt",
  * "device_bvh_instances", "device_bvh_graft", "firefly_clamp": N (integer 0..64) and "firefly_clamp_passes" (true, false, 0 or 1; a parse
  * error without "firefly_clamp") are set single-GPU and on every rank of --devices N.
- * "denoise_variance", "denoise_temporal" (both in the two Denoise modes only), "denoise_variance_spatial", "upscale_guided" and
- * "denoise_temporal_coverage": N (0, 2, 3 or 4) are set single-GPU and on rank 0 of --devices N, which filters, accumulates and upscales (the
+ * "denoise_variance", "denoise_temporal" (both in the two Denoise modes only), "denoise_variance_spatial", "upscale_guided",
+ * "denoise_temporal_moments" (true, false, 0 or 1) and "denoise_temporal_coverage": N (0, 2, 3 or 4) are set single-GPU and on rank 0 of --devices N, which filters, accumulates and upscales (the
  * PNG is the single-GPU run's).  "device_bvh_refit" and "device_bvh_instances" are a parse error without "device_bvh": true, and
  * "device_bvh_graft" without "device_bvh_instances": true; "device_bvh_instances", "device_bvh_graft" and "upscale_guided" take true, false, 0
- * or 1 only.  "denoise_variance_spatial" and "denoise_temporal_coverage" are accepted and without effect without "denoise_variance" /
+ * or 1 only.  "denoise_variance_spatial", "denoise_temporal_coverage" and "denoise_temporal_moments" are accepted and without effect without "denoise_variance" /
  * "denoise_temporal", "upscale_guided" outside DenoiseUpScale2X.  Both drivers refuse, before they load the scene or touch a device:
  * "denoise_temporal" together with "noise_threshold" > 0 (an adaptive frame that stops early never reaches the pass that advances the
  * history), and "firefly_clamp" together with "passes" > 1 or "noise_threshold" > 0 unless "firefly_clamp_passes" is true (the rule needs
