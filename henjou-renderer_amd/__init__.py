@@ -174,6 +174,7 @@ GBUFFER_MISS = 0xffffffff
 TEMPORAL_ALPHA = np.float32(0.2)  # HJR_TEMPORAL_ALPHA
 TEMPORAL_SNAP = np.float32(0.125)  # HJR_TEMPORAL_SNAP
 TEMPORAL_MOMENTS_MIN = np.float32(4.0)  # HJR_TEMPORAL_MOMENTS_MIN
+TEMPORAL_RESP = {"R": 2, "T0": np.float32(3.0), "T1": np.float32(6.0), "NMIN": 5, "EPS": np.float32(1e-3)}  # HJR_TEMPORAL_RESP_*
 
 
 class TemporalFrame(_Sized):
@@ -263,6 +264,8 @@ def lib():
             "hjr_temporal_accumulate_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate_moments": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate_moments_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "hjr_temporal_accumulate_response": [C.c_void_p] * 9,
+            "hjr_temporal_accumulate_response_device": [C.c_void_p] * 10,
             "hjr_temporal_reset": [C.c_void_p],
             "hjr_upscale_guided": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
             "hjr_upscale_guided_device": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -666,11 +669,12 @@ class Device:
         keep.append(arrs)
         return f
 
-    def temporal_accumulate(self, prev, cur, moments=False):
+    def temporal_accumulate(self, prev, cur, moments=False, response=False):
         """hjr_temporal_accumulate on dicts of arrays (keys: camera, transforms, inv_transforms, gbuffer, color, variance, optionally coverage; prev also
         history; prev None = no previous frame): returns (color [h, w, 4], variance [h, w], history [h, w]).  moments=True:
         hjr_temporal_accumulate_moments, which reads prev["moments"] ([h, w, 2], passed as its prev_moments argument) and returns a fourth
-        array, the moments [h, w, 2]."""
+        array, the moments [h, w, 2].  response=True: hjr_temporal_accumulate_response, with or without the moments, which returns lambda
+        [h, w] as a further array (the last one)."""
         keep = []
         fc = self._temporal_frame(cur, keep)
         fp = None if prev is None else self._temporal_frame(prev, keep)
@@ -678,13 +682,19 @@ class Device:
         color = np.zeros((h, w, 4), dtype=np.float32)
         variance = np.zeros((h, w), dtype=np.float32)
         history = np.zeros((h, w), dtype=np.float32)
-        if moments:
-            mom = np.zeros((h, w, 2), dtype=np.float32)
+        if moments or response:
+            mom = np.zeros((h, w, 2), dtype=np.float32) if moments else None
             pm = None
-            if prev is not None and prev.get("moments") is not None:
+            if moments and prev is not None and prev.get("moments") is not None:
                 pm = np.ascontiguousarray(prev["moments"], dtype=np.float32)
                 if pm.shape != (h, w, 2):
                     raise ValueError("temporal frame: moments must be [height, width, 2]")
+            if response:
+                lam = np.zeros((h, w), dtype=np.float32)
+                _check(lib().hjr_temporal_accumulate_response(self._h, None if fp is None else C.byref(fp), C.byref(fc), color.ctypes.data, variance.ctypes.data,
+                                                              history.ctypes.data, None if pm is None else pm.ctypes.data, None if mom is None else mom.ctypes.data,
+                                                              lam.ctypes.data), "hjr_temporal_accumulate_response")
+                return (color, variance, history, mom, lam) if moments else (color, variance, history, lam)
             _check(lib().hjr_temporal_accumulate_moments(self._h, None if fp is None else C.byref(fp), C.byref(fc), color.ctypes.data, variance.ctypes.data,
                                                          history.ctypes.data, None if pm is None else pm.ctypes.data, mom.ctypes.data),
                    "hjr_temporal_accumulate_moments")

@@ -127,7 +127,7 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
     // rule 10 keeps chunk sums from a frame's first pass on: an unfinished progressive frame cannot change its rule half way (as hjr_set_adaptive).
     // "firefly_clamp" alone with "firefly_clamp_passes" off keeps what it always did: the next pass is refused by check_pass
     if (i == hjr::OPT_FIREFLY_CLAMP_PASSES || (i == hjr::OPT_FIREFLY_CLAMP && c->opt.get(hjr::OPT_FIREFLY_CLAMP_PASSES, 0) == 1)) { c->pass.active = false; c->ad.frame = false; }
-    if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL || i == hjr::OPT_DENOISE_TEMPORAL_COVERAGE || i == hjr::OPT_DENOISE_TEMPORAL_MOMENTS) c->tmp.have_prev = false; // setting any of these options drops the history
+    if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL || i == hjr::OPT_DENOISE_TEMPORAL_COVERAGE || i == hjr::OPT_DENOISE_TEMPORAL_MOMENTS || i == hjr::OPT_DENOISE_TEMPORAL_RESPONSE) c->tmp.have_prev = false; // setting any of these options drops the history
     if (i == hjr::OPT_HOST_THREADS) hjr::set_host_threads(value);
     return HJR_OK;
 }
@@ -1326,8 +1326,9 @@ extern "C" int hjr_render_gbuffer_cov(hjr_ctx* c, const hjr_params* p_user, uint
 // the accumulation kernel on device memory; the two frames were checked by the callers
 // prev_cov / cur_cov: the two sides' `coverage`; with both 0 the launch is the plain instantiation's, as before the coverage rules existed
 // d_out_mom != nullptr: the temporal moments (d_prev_mom: prev's, checked by the callers); nullptr: the launch as before they existed
+// d_out_resp != nullptr: the windowed change test (hjr_temporal_resp_kernel, one workgroup per 16 x 16 pixels); nullptr: the launch as before it existed
 static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_color, void* d_var, void* d_hist, hipStream_t st,
-                           uint32_t prev_cov, uint32_t cur_cov, const void* d_prev_mom = nullptr, void* d_out_mom = nullptr)
+                           uint32_t prev_cov, uint32_t cur_cov, const void* d_prev_mom = nullptr, void* d_out_mom = nullptr, void* d_out_resp = nullptr)
 {
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
@@ -1343,6 +1344,16 @@ static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalS
         { hjr_temporal_kernel<false, false>, hjr_temporal_kernel<false, true> },
         { hjr_temporal_kernel<true, false>, hjr_temporal_kernel<true, true> },
     };
+    if (d_out_resp) {
+        using RespKernel = void (*)(TemporalArgs, float*);
+        static const RespKernel resp_kernels[2][2] = {
+            { hjr_temporal_resp_kernel<false, false>, hjr_temporal_resp_kernel<false, true> },
+            { hjr_temporal_resp_kernel<true, false>, hjr_temporal_resp_kernel<true, true> },
+        };
+        hipLaunchKernelGGL(resp_kernels[a.prev_cov || a.cur_cov][d_out_mom != nullptr], dim3((w + RESP_TILE - 1) / RESP_TILE, (h + RESP_TILE - 1) / RESP_TILE), dim3(256), 0, st, a,
+                           (float*)d_out_resp);
+        return launched();
+    }
     hipLaunchKernelGGL(kernels[a.prev_cov || a.cur_cov][d_out_mom != nullptr], image_grid(w, h), dim3(256), 0, st, a);
     return launched();
 }
@@ -1368,9 +1379,9 @@ static TemporalSide temporal_side(const hjr_temporal_frame& f)
     s.color = (const float4*)f.color; s.variance = f.variance; s.history = f.history;
     return s;
 }
-// d_mom == nullptr: hjr_temporal_accumulate_device, and d_prev_mom is not looked at
-extern "C" int hjr_temporal_accumulate_moments_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist,
-                                                      const void* d_prev_mom, void* d_mom, void* hip_stream)
+// d_mom == nullptr: without moments, and d_prev_mom is not looked at; d_resp == nullptr: hjr_temporal_accumulate_moments_device
+extern "C" int hjr_temporal_accumulate_response_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist,
+                                                       const void* d_prev_mom, void* d_mom, void* d_resp, void* hip_stream)
 {
     if (!c || !d_color || !d_var || !d_hist) { set_error("hjr_temporal_accumulate: null argument"); return HJR_ERR_ARG; }
     hjr_temporal_frame prev, cur;
@@ -1379,15 +1390,20 @@ extern "C" int hjr_temporal_accumulate_moments_device(hjr_ctx* c, const hjr_temp
     HIPCHK(hipSetDevice(c->device));
     const TemporalSide ps = have_prev ? temporal_side(prev) : TemporalSide(), cs = temporal_side(cur);
     return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, stream_of(c, hip_stream),
-                           have_prev ? prev.coverage : 0u, cur.coverage, have_prev && d_mom ? d_prev_mom : nullptr, d_mom);
+                           have_prev ? prev.coverage : 0u, cur.coverage, have_prev && d_mom ? d_prev_mom : nullptr, d_mom, d_resp);
+}
+extern "C" int hjr_temporal_accumulate_moments_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist,
+                                                      const void* d_prev_mom, void* d_mom, void* hip_stream)
+{
+    return hjr_temporal_accumulate_response_device(c, prev_user, cur_user, d_color, d_var, d_hist, d_prev_mom, d_mom, nullptr, hip_stream);
 }
 extern "C" int hjr_temporal_accumulate_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist, void* hip_stream)
 {
     return hjr_temporal_accumulate_moments_device(c, prev_user, cur_user, d_color, d_var, d_hist, nullptr, nullptr, hip_stream);
 }
-// out_mom == nullptr: hjr_temporal_accumulate, and prev_mom is not looked at
-extern "C" int hjr_temporal_accumulate_moments(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist,
-                                               const float* prev_mom, float* out_mom)
+// out_mom == nullptr: without moments, and prev_mom is not looked at; out_resp == nullptr: hjr_temporal_accumulate_moments
+extern "C" int hjr_temporal_accumulate_response(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist,
+                                                const float* prev_mom, float* out_mom, float* out_resp)
 {
     if (!c || !out_color || !out_var || !out_hist) { set_error("hjr_temporal_accumulate: null argument"); return HJR_ERR_ARG; }
     hjr_temporal_frame f[2]; // [0] prev, [1] cur
@@ -1397,7 +1413,8 @@ extern "C" int hjr_temporal_accumulate_moments(hjr_ctx* c, const hjr_temporal_fr
     const size_t npx = (size_t)f[1].width * f[1].height, nx = (size_t)f[1].n_instances * 48;
     const size_t mom = out_mom ? npx * 8 : 0; // the moments: prev's behind its side's images, the output behind the three outputs
     // one temporary buffer: per side [M | M^-1 | gbuffer | colour | variance | history | (moments)], then the three outputs (and the moments)
-    const size_t side = (2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4) + mom + 255) & ~(size_t)255, outs = npx * (16 + 4 + 4) + mom; // (float4 images stay 16-byte aligned)
+    const size_t resp = out_resp ? npx * 4 : 0; // lambda: the last output
+    const size_t side = (2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4) + mom + 255) & ~(size_t)255, outs = npx * (16 + 4 + 4) + mom + resp; // (float4 images stay 16-byte aligned)
     HostStage hs(c);
     if (!hs.buf.reserve(2 * side + outs)) { set_error("hjr_temporal_accumulate: device allocation failed"); return HJR_ERR_DEVICE; }
     TemporalSide s[2];
@@ -1418,12 +1435,19 @@ extern "C" int hjr_temporal_accumulate_moments(hjr_ctx* c, const hjr_temporal_fr
     char* const o = (char*)hs.buf.p + 2 * side;
     const char* const pm = (const char*)hs.buf.p + 2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4);
     if (hs.ok()) hs.rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream,
-                                         have_prev ? f[0].coverage : 0u, f[1].coverage, have_prev && mom ? pm : nullptr, mom ? o + npx * 24 : nullptr);
+                                         have_prev ? f[0].coverage : 0u, f[1].coverage, have_prev && mom ? pm : nullptr, mom ? o + npx * 24 : nullptr,
+                                         resp ? o + npx * 24 + mom : nullptr);
     hs.down(out_color, o, npx * 16);
     hs.down(out_var, o + npx * 16, npx * 4);
     hs.down(out_hist, o + npx * 20, npx * 4);
     if (mom) hs.down(out_mom, o + npx * 24, mom);
+    if (resp) hs.down(out_resp, o + npx * 24 + mom, resp);
     return hs.finish("hjr_temporal_accumulate");
+}
+extern "C" int hjr_temporal_accumulate_moments(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist,
+                                               const float* prev_mom, float* out_mom)
+{
+    return hjr_temporal_accumulate_response(c, prev_user, cur_user, out_color, out_var, out_hist, prev_mom, out_mom, nullptr);
 }
 extern "C" int hjr_temporal_accumulate(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist)
 {
@@ -1449,6 +1473,7 @@ static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
     if (!t.color[k].reserve(npx * 16) || !t.variance[k].reserve(npx * 4) || !t.history[k].reserve(npx * 4) || !t.gbuf[k].reserve(npx * sizeof(hjr_gbuffer_px)) ||
         !t.xf[k].reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) && !t.moments[k].reserve(npx * 8)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
+    if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_RESPONSE, 0) && !t.response.reserve(npx * 4)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     return HJR_OK;
 }
 static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
@@ -1474,8 +1499,9 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
     }
     s[1].color = (const float4*)d_color; s[1].variance = (const float*)d_var; s[1].history = nullptr;
     const bool mom = c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) != 0; // option "denoise_temporal_moments": both slots carry (m1, m2) (setting it drops the history, so the previous slot has them)
+    const bool resp = c->opt.get(hjr::OPT_DENOISE_TEMPORAL_RESPONSE, 0) != 0; // option "denoise_temporal_response": the windowed change test; its lambda image is written and not read again
     if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, st, cov, cov,
-                                       mom && t.have_prev ? t.moments[k ^ 1].p : nullptr, mom ? t.moments[k].p : nullptr)) return rc;
+                                       mom && t.have_prev ? t.moments[k ^ 1].p : nullptr, mom ? t.moments[k].p : nullptr, resp ? t.response.p : nullptr)) return rc;
     d_color = t.color[k].p; d_var = t.variance[k].p;
     if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur = k ^ 1; }
     return HJR_OK;

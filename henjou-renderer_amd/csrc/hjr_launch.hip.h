@@ -138,6 +138,7 @@ struct hjr_ctx {
         hjr_camera cam[2];
         DevBuf color[2], variance[2], history[2], gbuf[2], xf[2]; // accumulated unfiltered colour | its variance | h | G-buffer | [M | M^-1] of that render
         DevBuf moments[2];                                        // option "denoise_temporal_moments": float2 (m1, m2) per pixel
+        DevBuf response;                                          // option "denoise_temporal_response": lambda per pixel of the last accumulation
     } tmp;
     hjr::Options opt; // hjr_set_option (host/options.hpp): the library reads no environment variable
 };

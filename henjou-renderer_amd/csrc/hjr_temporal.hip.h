@@ -3,6 +3,7 @@
 //   hjr_gbuffer_kernel<WIDTH, COV>   first-hit record of every pixel's centre ray, by the stand-alone traversal the tile classifier uses;
 //   hjr_temporal_kernel<COV, MOM>  one lane per pixel: reprojects the pixel's surface point into the previous frame, gathers the previous
 //                               frame's accumulated colour / variance / history length with four validated bilinear taps and blends.
+//   hjr_temporal_resp_kernel<COV, MOM>  the same with the windowed change test of section RESPONSE: a workgroup per 16 x 16 pixels.
 // Included by hjr_device.hip only: correctly rounded divide, no contraction, denormals on.  Specified to the bit, so that the test suite's
 // CPU checker (tests/native/temporal_ref.cpp) restates it independently.  fp32 throughout, every operation as written, left to right:
 //   dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z ;   cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x) ;
@@ -88,6 +89,29 @@
 //   With a fractional h after bilinear mixing the weights are not exactly those, so k is approximate there.
 //   Rules 2' / 3' choose the taps as above; the moments ride on whichever taps are chosen.  Moments are only ever multiplied, added and
 //   compared: NaN, Inf and values whose square overflows end in HJR_VARIANCE_UNKNOWN or a finite variance, and index nothing.
+//
+// RESPONSE (hjr_temporal_resp_kernel<COV, MOM>: the ACCUMULATION above, with or without the coverage rules and the moments, with one more
+//   output, lambda per pixel (float, [H][W]).  DESIGN.md §11.8.)  Reprojection follows surfaces, not illumination; this section lets the
+//   history give way where the window mean of the current luminance has left that of the reprojected history.
+//   Steps 1 to 4 are unchanged up to c_prev, v_prev, h_prev (with 2' / 3', and the moments' m1p, m2p).  A pixel is CARRIED iff it did not
+//   RESTART.  For a pixel q:   lc_q = (cur.r + cur.g) + cur.b  of q's current colour;   for a carried q,  lp_q = (c_prev.r + c_prev.g) + c_prev.b
+//   of q's own c_prev.
+//   For a carried pixel p with record G_p the window is the (2 R + 1)^2 pixels (x + dx, y + dy), dy the outer loop and dx the inner one, both
+//   from -R to R.  A pixel q of it is a MEMBER iff it lies in the image, G_q.prim != 0xffffffff and G_q.prim < n_triangles,
+//   G_q.inst == G_p.inst, and q is carried (p is a member of its own window).  In window order over the members, all sums from +0.0f, n the
+//   number of members:   Sd = Sd + (lc_q - lp_q);   Sc = Sc + lc_q;   Sc2 = Sc2 + lc_q * lc_q.   Then
+//     nf = (float)n;  mu_d = Sd / nf;  mu_c = Sc / nf;  var_c = fmaxf(Sc2 / nf - mu_c * mu_c, 0);  se = sqrtf(var_c / nf) + EPS;
+//     t = fabsf(mu_d) / se;   lambda = (n >= NMIN) ? fminf(fmaxf((t - T0) / (T1 - T0), 0), 1) : 0      (a NaN t gives 0 through fmaxf).
+//   The blend of step 4 and of the moments uses  al' = fmaxf(al, lambda)  wherever they use al: the colour, om = 1 - al', the propagated
+//   variance, m1 and m2.  The history length becomes  h = (lambda > 0) ? fminf(h, 1 / al') : h  (after al was taken from the unchanged h),
+//   and that h is the one written and the one the moments' test  h >= HJR_TEMPORAL_MOMENTS_MIN  and their k see.
+//   RESTART pixels write lambda = 0 and everything else as above.
+//   R, T0, T1, NMIN, EPS are HJR_TEMPORAL_RESP_R (2), _T0 (3), _T1 (6), _NMIN (5), _EPS (1e-3f) of include/henjou_hip.h.
+//   The difference of the means is judged against the spread of the current frame alone: sqrt(var_c / n) is the standard error of the
+//   window mean of one frame, so t counts standard errors, and the history's own (smaller) noise is left out.  With lambda = 0 in a pixel
+//   its outputs are the bits of the kernel without this section: fmaxf(al, 0) = al exactly, and h is untouched.
+//   Luminances are only added, multiplied, divided and compared, and the window is addressed by integer pixel offsets inside the image:
+//   NaN, Inf and overflowing squares end in a lambda in [0, 1] and index nothing.
 #pragma once
 #include "hjr_aux.hip.h" // TileStack: the classifier's stacks
 
@@ -211,18 +235,23 @@ HD bool t_mixed(uint32_t pad) { const uint32_t total = (pad >> 8) & 0xffu; retur
 // expressions (g_mixed, the snap tap, n_taps, the pad test of a tap) are constants in the plain instantiation and fold away there.
 // MOM: the temporal luminance moments (section TEMPORAL MOMENTS of the header comment): one float2 load per valid tap, one float2 store
 // per pixel; every line of it sits under `if constexpr (MOM)`, so the MOM = false instantiations are the code they were without it.
-template <bool COV, bool MOM>
-__global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
+
+// what steps 1 to 4 gather of the previous frame for one pixel: c_prev, v_prev, h_prev (and m1p, m2p) and the taps' "unknown"
+struct TemporalPrev {
+    float cx, cy, cz, v, h;
+    bool unknown;
+    float m1, m2;  // MOM
+    uint32_t inst; // the pixel's instance, < n_instances
+};
+
+// Steps 1 to 4 of ACCUMULATION (with 2' / 3' and the moments' sums) for the pixel whose record is G, up to the divides by S: a carried
+// pixel calls carried(P) at the place step 4 blends, a RESTART calls nothing.  Shared by hjr_temporal_kernel and hjr_temporal_resp_kernel.
+// A callback and the argument block by value, not a returned flag and a reference, and hjr_temporal_kernel's body in a function that takes
+// the block by value as well: of the forms tried, the one in which the four hjr_temporal_kernel instantiations keep the instructions
+// they had as one body (the same opcodes the same number of times; a few commuted operands and reordered neighbours).
+template <bool COV, bool MOM, typename Carried>
+__device__ __forceinline__ void hjr_temporal_gather(const TemporalArgs A, const size_t pix, Carried carried)
 {
-    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
-    if (x >= A.width || y >= A.height) return;
-    const size_t pix = (size_t)y * A.width + x;
-    const float4 cc = A.cur.color[pix];
-    const float cv = A.cur.variance[pix];
-    float4 out = cc;
-    float var = cv, hist = 1.0f;
-    [[maybe_unused]] float lum = 0.0f, m1 = 0.0f, m2 = 0.0f;
-    if constexpr (MOM) { lum = (cc.x + cc.y) + cc.z; m1 = lum; m2 = lum * lum; }
     const hjr_gbuffer_px G = A.cur.gbuf[pix];
     if (A.have_prev && G.prim != 0xffffffffu && G.prim < A.n_tris && G.inst < A.n_instances) {
         const float W = (float)A.width, H = (float)A.height;
@@ -282,28 +311,177 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
                 }
             }
             if (S > 0.0f) {
-                const float px_ = Cx / S, py_ = Cy / S, pz_ = Cz / S, v_prev = Vs / S, h_prev = Hs / S;
-                hist = fminf(fmaxf(h_prev + 1.0f, 1.0f), HJR_TEMPORAL_H_MAX);
-                const float al = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA);
-                out.x = px_ + (cc.x - px_) * al; out.y = py_ + (cc.y - py_) * al; out.z = pz_ + (cc.z - pz_) * al;
-                unknown = unknown || !(cv < HJR_VARIANCE_UNKNOWN);
-                const float om = 1.0f - al;
-                var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0.0f);
-                if constexpr (MOM) {
-                    const float m1p = M1 / S, m2p = M2 / S;
-                    m1 = m1p + (lum - m1p) * al; m2 = m2p + (lum * lum - m2p) * al;
-                    if (hist >= HJR_TEMPORAL_MOMENTS_MIN) {
-                        const float kk = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA / (2.0f - HJR_TEMPORAL_ALPHA));
-                        const float d = m2 - m1 * m1;
-                        const float mv = t_finite(d) ? fmaxf(d, 0.0f) * (kk / (1.0f - kk)) : HJR_VARIANCE_UNKNOWN;
-                        var = mv < HJR_VARIANCE_UNKNOWN ? mv : HJR_VARIANCE_UNKNOWN;
-                    }
-                }
+                TemporalPrev P;
+                P.cx = Cx / S; P.cy = Cy / S; P.cz = Cz / S; P.v = Vs / S; P.h = Hs / S;
+                P.unknown = unknown; P.inst = G.inst;
+                if constexpr (MOM) { P.m1 = M1 / S; P.m2 = M2 / S; } else P.m1 = P.m2 = 0.0f;
+                carried(P);
             }
         }
     }
+}
+
+// Step 4's blend as section RESPONSE has it, for hjr_temporal_resp_kernel: al and h answer to lambda first.  (RESP = false is the blend
+// written out in hjr_temporal_pixel, which keeps its own text: called from there, this function changes that kernel's code.)
+template <bool MOM, bool RESP>
+__device__ __forceinline__ void hjr_temporal_blend(const TemporalPrev& P, float4 cc, float cv, [[maybe_unused]] float lum, [[maybe_unused]] float lambda, float4& out, float& var,
+                                                   float& hist, [[maybe_unused]] float& m1, [[maybe_unused]] float& m2)
+{
+    hist = fminf(fmaxf(P.h + 1.0f, 1.0f), HJR_TEMPORAL_H_MAX);
+    float al = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA);
+    if constexpr (RESP) {
+        al = fmaxf(al, lambda);
+        hist = lambda > 0.0f ? fminf(hist, 1.0f / al) : hist;
+    }
+    out.x = P.cx + (cc.x - P.cx) * al; out.y = P.cy + (cc.y - P.cy) * al; out.z = P.cz + (cc.z - P.cz) * al;
+    const bool unknown = P.unknown || !(cv < HJR_VARIANCE_UNKNOWN);
+    const float om = 1.0f - al;
+    var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * P.v + (al * al) * fmaxf(cv, 0.0f);
+    if constexpr (MOM) {
+        m1 = P.m1 + (lum - P.m1) * al; m2 = P.m2 + (lum * lum - P.m2) * al;
+        if (hist >= HJR_TEMPORAL_MOMENTS_MIN) {
+            const float kk = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA / (2.0f - HJR_TEMPORAL_ALPHA));
+            const float d = m2 - m1 * m1;
+            const float mv = t_finite(d) ? fmaxf(d, 0.0f) * (kk / (1.0f - kk)) : HJR_VARIANCE_UNKNOWN;
+            var = mv < HJR_VARIANCE_UNKNOWN ? mv : HJR_VARIANCE_UNKNOWN;
+        }
+    }
+}
+
+// hjr_temporal_kernel's body (by value: see hjr_temporal_gather)
+template <bool COV, bool MOM>
+__device__ __forceinline__ void hjr_temporal_pixel(const TemporalArgs A)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= A.width || y >= A.height) return;
+    const size_t pix = (size_t)y * A.width + x;
+    const float4 cc = A.cur.color[pix];
+    const float cv = A.cur.variance[pix];
+    float4 out = cc;
+    float var = cv, hist = 1.0f;
+    [[maybe_unused]] float lum = 0.0f, m1 = 0.0f, m2 = 0.0f;
+    if constexpr (MOM) { lum = (cc.x + cc.y) + cc.z; m1 = lum; m2 = lum * lum; }
+    // (step 4's blend stays written out here, as it always was)
+    hjr_temporal_gather<COV, MOM>(A, pix, [&](const TemporalPrev& P) {
+        const float px_ = P.cx, py_ = P.cy, pz_ = P.cz, v_prev = P.v, h_prev = P.h;
+        bool unknown = P.unknown;
+        hist = fminf(fmaxf(h_prev + 1.0f, 1.0f), HJR_TEMPORAL_H_MAX);
+        const float al = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA);
+        out.x = px_ + (cc.x - px_) * al; out.y = py_ + (cc.y - py_) * al; out.z = pz_ + (cc.z - pz_) * al;
+        unknown = unknown || !(cv < HJR_VARIANCE_UNKNOWN);
+        const float om = 1.0f - al;
+        var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0.0f);
+        if constexpr (MOM) {
+            const float m1p = P.m1, m2p = P.m2;
+            m1 = m1p + (lum - m1p) * al; m2 = m2p + (lum * lum - m2p) * al;
+            if (hist >= HJR_TEMPORAL_MOMENTS_MIN) {
+                const float kk = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA / (2.0f - HJR_TEMPORAL_ALPHA));
+                const float d = m2 - m1 * m1;
+                const float mv = t_finite(d) ? fmaxf(d, 0.0f) * (kk / (1.0f - kk)) : HJR_VARIANCE_UNKNOWN;
+                var = mv < HJR_VARIANCE_UNKNOWN ? mv : HJR_VARIANCE_UNKNOWN;
+            }
+        }
+    });
     A.out_color[pix] = out;
     A.out_variance[pix] = var;
     A.out_history[pix] = hist;
     if constexpr (MOM) A.out_moments[pix] = make_float2(m1, m2);
+}
+
+template <bool COV, bool MOM>
+__global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
+{
+    hjr_temporal_pixel<COV, MOM>(A);
+}
+
+// RESPONSE (section RESPONSE of the header comment).  A 256-thread workgroup owns a 16 x 16 pixel tile and stages the tile and a halo of
+// HJR_TEMPORAL_RESP_R pixels in LDS: per cell lc, lc - lp and a member key (the instance of a carried pixel, RESP_NO_KEY for every other
+// cell: restarted, outside the image), so that "q is a member of p's window" is one compare with G_p.inst.  Every thread gathers its own
+// pixel (round 0, kept in registers for the blend) and the first RESP_HALO threads one halo cell each (round 1); after the one barrier every
+// carried pixel takes its window sums from LDS in window order.  Three planes of RESP_ROWS rows with a row stride of RESP_STRIDE = 48
+// floats: a wave's lanes are 4 rows of 16 pixels, ds_read_b32 conflicts within a 32-lane half (2 rows) over 32 banks, and 48 = 16 mod 32
+// puts the second row's 16 banks beside the first's at every window offset (the row length 20 would be a 2-way conflict on 12 of 16 banks).
+#define RESP_TILE 16
+#define RESP_SIDE (RESP_TILE + 2 * HJR_TEMPORAL_RESP_R)                                  // 20 (22 with R = 3)
+#define RESP_HALO (RESP_SIDE * RESP_SIDE - RESP_TILE * RESP_TILE)                        // 144 (228): at most one round of 256 threads
+#define RESP_STRIDE 48
+#define RESP_NO_KEY 0xffffffffu // (no carried pixel has it: G.inst < n_instances <= 0xffffffff)
+static_assert(RESP_HALO <= 256 && RESP_SIDE <= RESP_STRIDE && RESP_STRIDE % 32 == 16, "one halo round, rows that fit, rows of a half on unlike banks");
+
+template <bool COV, bool MOM>
+__global__ void __launch_bounds__(256) hjr_temporal_resp_kernel(const TemporalArgs A, float* __restrict__ out_response)
+{
+    __shared__ float s_lc[RESP_SIDE * RESP_STRIDE], s_d[RESP_SIDE * RESP_STRIDE];
+    __shared__ uint32_t s_key[RESP_SIDE * RESP_STRIDE];
+    constexpr int R = HJR_TEMPORAL_RESP_R;
+    const int tid = (int)threadIdx.x, lx = tid & (RESP_TILE - 1), ly = tid >> 4;
+    // the thread's own pixel: what the blend needs stays in registers
+    float4 own_cc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float own_cv = 0.0f, own_lc = 0.0f;
+    bool own_carried = false, own_inside = false;
+    TemporalPrev own;
+    own.cx = own.cy = own.cz = own.v = own.h = own.m1 = own.m2 = 0.0f; own.unknown = false; own.inst = 0u;
+#pragma unroll 1
+    for (int round = 0; round < 2; round++) {
+        int cx, cy; // the cell in the staged square
+        if (round == 0) { cx = lx + R; cy = ly + R; }
+        else {
+            if (tid >= RESP_HALO) break;
+            constexpr int kBand = R * RESP_SIDE; // cells of the rows above the tile, and of those below
+            if (tid < 2 * kBand) { const int b = tid < kBand ? tid : tid - kBand; cy = b / RESP_SIDE + (tid < kBand ? 0 : RESP_TILE + R); cx = b % RESP_SIDE; }
+            else { const int b = tid - 2 * kBand; cy = R + b / (2 * R); const int k = b % (2 * R); cx = k < R ? k : RESP_TILE + k; }
+        }
+        const int px = (int)(blockIdx.x * RESP_TILE) + cx - R, py = (int)(blockIdx.y * RESP_TILE) + cy - R;
+        const bool inside = px >= 0 && py >= 0 && px < (int)A.width && py < (int)A.height;
+        float lc = 0.0f, d = 0.0f;
+        uint32_t key = RESP_NO_KEY;
+        if (inside) {
+            const size_t pix = (size_t)py * A.width + (size_t)px;
+            const float4 cc = A.cur.color[pix];
+            lc = (cc.x + cc.y) + cc.z;
+            bool carried = false;
+            hjr_temporal_gather<COV, MOM>(A, pix, [&](const TemporalPrev& P) {
+                carried = true; d = lc - ((P.cx + P.cy) + P.cz); key = P.inst;
+                if (round == 0) own = P;
+            });
+            if (round == 0) { own_cc = cc; own_cv = A.cur.variance[pix]; own_lc = lc; own_carried = carried; own_inside = true; }
+        }
+        const int cell = cy * RESP_STRIDE + cx;
+        s_lc[cell] = lc; s_d[cell] = d; s_key[cell] = key;
+    }
+    __syncthreads();
+    if (!own_inside) return;
+    float4 out = own_cc;
+    float var = own_cv, hist = 1.0f, lambda = 0.0f;
+    [[maybe_unused]] float m1 = own_lc, m2 = own_lc * own_lc;
+    if (own_carried) {
+        float Sd = 0.0f, Sc = 0.0f, Sc2 = 0.0f;
+        int n = 0;
+#pragma unroll
+        for (int dy = -R; dy <= R; dy++) {
+#pragma unroll
+            for (int dx = -R; dx <= R; dx++) {
+                const int cell = (ly + R + dy) * RESP_STRIDE + (lx + R + dx);
+                const bool member = s_key[cell] == own.inst;
+                const float qc = s_lc[cell], qd = s_d[cell];
+                n += member ? 1 : 0;
+                Sd = member ? Sd + qd : Sd;
+                Sc = member ? Sc + qc : Sc;
+                Sc2 = member ? Sc2 + qc * qc : Sc2;
+            }
+        }
+        const float nf = (float)n;
+        const float mu_d = Sd / nf, mu_c = Sc / nf;
+        const float var_c = fmaxf(Sc2 / nf - mu_c * mu_c, 0.0f);
+        const float se = sqrtf(var_c / nf) + HJR_TEMPORAL_RESP_EPS;
+        const float t = fabsf(mu_d) / se;
+        lambda = n >= HJR_TEMPORAL_RESP_NMIN ? fminf(fmaxf((t - HJR_TEMPORAL_RESP_T0) / (HJR_TEMPORAL_RESP_T1 - HJR_TEMPORAL_RESP_T0), 0.0f), 1.0f) : 0.0f;
+        hjr_temporal_blend<MOM, true>(own, own_cc, own_cv, own_lc, lambda, out, var, hist, m1, m2);
+    }
+    const size_t pix = (size_t)(blockIdx.y * RESP_TILE + ly) * A.width + (blockIdx.x * RESP_TILE + lx);
+    A.out_color[pix] = out;
+    A.out_variance[pix] = var;
+    A.out_history[pix] = hist;
+    if constexpr (MOM) A.out_moments[pix] = make_float2(m1, m2);
+    out_response[pix] = lambda;
 }

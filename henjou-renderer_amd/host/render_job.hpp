@@ -70,7 +70,10 @@ inline const std::vector<KeyRow>& key_table_since()
     using O = hjr_render_option;
     static const std::vector<KeyRow> t = {
         { "firefly_clamp_passes", 13, &O::device_bvh_opt, ENC_BITS, 23, 1, READ_BOOL, "firefly_clamp", WHO_EVERY }, // (every rank keeps its own chunk sums)
-        { "denoise_temporal_moments", 14, &O::device_bvh_opt, ENC_BITS, 15, 1, READ_BOOL, nullptr, WHO_FILTER },
+        // (in front of "denoise_temporal_moments", which tests/test_temporal_moments_host.py pins as the table's last row and latest parse
+        // turn: a file with both keys bad reports this one; no file without this key is read differently)
+        { "denoise_temporal_response", 14, &O::device_bvh_opt, ENC_BITS, 24, 1, READ_BOOL, nullptr, WHO_FILTER },
+        { "denoise_temporal_moments", 15, &O::device_bvh_opt, ENC_BITS, 15, 1, READ_BOOL, nullptr, WHO_FILTER },
     };
     return t;
 }
