@@ -4,8 +4,9 @@ index clamp, the zero-contribution test of NEE / MIS), on both kernel families a
 tests/test_shading_branches_host.py proves on the CPU that the frames take those branches.
 
 Bar: BIT-EXACT float32 equality of the colour, albedo and normal AOVs with the oracle's PORTABLE mode; with FLAG_STATS the ray, hit,
-light-sample and NaN counters are the oracle's and every NaN sample the GPU locates is one of the oracle's.  No fast-math kernel (not
-bit-exact by contract), no full-size frame: every parameter set is one frame of at most 32 x 32 pixels."""
+light-sample and NaN counters are the oracle's and every NaN sample the GPU locates is one of the oracle's.  The fast-math kernels (not
+bit-exact by contract) render the same cases in tests/test_gpu_fast_math_cases.py, under a per-pixel rule.  No full-size frame: every
+parameter set is one frame of at most 32 x 32 pixels."""
 import pytest
 
 import oracle_binding as ob
