@@ -1323,38 +1323,25 @@ extern "C" int hjr_render_gbuffer_cov(hjr_ctx* c, const hjr_params* p_user, uint
     return coverage_side_ok(side) ? gbuffer_host_impl(c, p_user, out, side) : HJR_ERR_ARG;
 }
 
-// the accumulation kernel on device memory; the two frames were checked by the callers
-// prev_cov / cur_cov: the two sides' `coverage`; with both 0 the launch is the plain instantiation's, as before the coverage rules existed
-// d_out_mom != nullptr: the temporal moments (d_prev_mom: prev's, checked by the callers); nullptr: the launch as before they existed
-// d_out_resp != nullptr: the windowed change test (hjr_temporal_resp_kernel, one workgroup per 16 x 16 pixels); nullptr: the launch as before it existed
-static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_color, void* d_var, void* d_hist, hipStream_t st,
-                           uint32_t prev_cov, uint32_t cur_cov, const void* d_prev_mom = nullptr, void* d_out_mom = nullptr, void* d_out_resp = nullptr)
+// The accumulation kernel on device memory; the two frames were checked by the callers.  prev == nullptr: no previous frame (this is the
+// one place that zeroes the missing side).  The records choose the kernel: out.response the windowed change test (a workgroup per
+// 16 x 16 pixels), out.moments the temporal moments, a side's coverage rules 2' / 3'.
+static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, const TemporalOut& out, hipStream_t st)
 {
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
-    a.cur = cur;
+    a.cur = cur; a.out = out;
     if (prev) { a.prev = *prev; a.have_prev = 1u; }
     a.width = w; a.height = h; a.n_instances = n_inst;
     a.n_tris = c->have_scene ? c->scene.n_triangles : 0xffffffffu; // prim ids are checked against the uploaded scene
-    a.prev_cov = prev ? prev_cov : 0u; a.cur_cov = cur_cov;
-    a.out_color = (float4*)d_color; a.out_variance = (float*)d_var; a.out_history = (float*)d_hist;
-    a.prev_moments = prev ? (const float2*)d_prev_mom : nullptr; a.out_moments = (float2*)d_out_mom;
     using Kernel = void (*)(TemporalArgs);
-    static const Kernel kernels[2][2] = { // [a side carries coverage][moments]
-        { hjr_temporal_kernel<false, false>, hjr_temporal_kernel<false, true> },
-        { hjr_temporal_kernel<true, false>, hjr_temporal_kernel<true, true> },
+    static const Kernel kernels[2][2][2] = { // [response][a side carries coverage][moments]
+        { { hjr_temporal_kernel<false, false>, hjr_temporal_kernel<false, true> }, { hjr_temporal_kernel<true, false>, hjr_temporal_kernel<true, true> } },
+        { { hjr_temporal_resp_kernel<false, false>, hjr_temporal_resp_kernel<false, true> }, { hjr_temporal_resp_kernel<true, false>, hjr_temporal_resp_kernel<true, true> } },
     };
-    if (d_out_resp) {
-        using RespKernel = void (*)(TemporalArgs, float*);
-        static const RespKernel resp_kernels[2][2] = {
-            { hjr_temporal_resp_kernel<false, false>, hjr_temporal_resp_kernel<false, true> },
-            { hjr_temporal_resp_kernel<true, false>, hjr_temporal_resp_kernel<true, true> },
-        };
-        hipLaunchKernelGGL(resp_kernels[a.prev_cov || a.cur_cov][d_out_mom != nullptr], dim3((w + RESP_TILE - 1) / RESP_TILE, (h + RESP_TILE - 1) / RESP_TILE), dim3(256), 0, st, a,
-                           (float*)d_out_resp);
-        return launched();
-    }
-    hipLaunchKernelGGL(kernels[a.prev_cov || a.cur_cov][d_out_mom != nullptr], image_grid(w, h), dim3(256), 0, st, a);
+    const bool resp = out.response != nullptr;
+    const dim3 grid = resp ? dim3((w + RESP_TILE - 1) / RESP_TILE, (h + RESP_TILE - 1) / RESP_TILE) : image_grid(w, h);
+    hipLaunchKernelGGL(kernels[resp][a.prev.coverage || a.cur.coverage][out.moments != nullptr], grid, dim3(256), 0, st, a);
     return launched();
 }
 // argument checks of hjr_temporal_accumulate[_device]: the sized structs, sizes that agree, every pointer the kernel reads
@@ -1372,11 +1359,13 @@ static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal
     }
     return HJR_OK;
 }
-static TemporalSide temporal_side(const hjr_temporal_frame& f)
+// the kernel's view of a frame whose pointers are device pointers; d_moments: the frame's moments (read of a previous frame only)
+static TemporalSide temporal_side(const hjr_temporal_frame& f, const void* d_moments)
 {
     TemporalSide s;
     s.cam = f.camera; s.m = f.transforms12; s.inv = f.inv_transforms12; s.gbuf = f.gbuffer;
     s.color = (const float4*)f.color; s.variance = f.variance; s.history = f.history;
+    s.moments = (const float2*)d_moments; s.coverage = f.coverage;
     return s;
 }
 // d_mom == nullptr: without moments, and d_prev_mom is not looked at; d_resp == nullptr: hjr_temporal_accumulate_moments_device
@@ -1388,9 +1377,9 @@ extern "C" int hjr_temporal_accumulate_response_device(hjr_ctx* c, const hjr_tem
     bool have_prev;
     if (const int rc = temporal_take(prev_user, cur_user, prev, cur, have_prev, d_mom != nullptr, d_prev_mom)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    const TemporalSide ps = have_prev ? temporal_side(prev) : TemporalSide(), cs = temporal_side(cur);
-    return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_color, d_var, d_hist, stream_of(c, hip_stream),
-                           have_prev ? prev.coverage : 0u, cur.coverage, have_prev && d_mom ? d_prev_mom : nullptr, d_mom, d_resp);
+    const TemporalSide ps = have_prev ? temporal_side(prev, d_prev_mom) : TemporalSide(), cs = temporal_side(cur, nullptr);
+    const TemporalOut out = { (float4*)d_color, (float*)d_var, (float*)d_hist, (float2*)d_mom, (float*)d_resp };
+    return temporal_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, out, stream_of(c, hip_stream));
 }
 extern "C" int hjr_temporal_accumulate_moments_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_color, void* d_var, void* d_hist,
                                                       const void* d_prev_mom, void* d_mom, void* hip_stream)
@@ -1411,37 +1400,46 @@ extern "C" int hjr_temporal_accumulate_response(hjr_ctx* c, const hjr_temporal_f
     if (const int rc = temporal_take(prev_user, cur_user, f[0], f[1], have_prev, out_mom != nullptr, prev_mom)) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t npx = (size_t)f[1].width * f[1].height, nx = (size_t)f[1].n_instances * 48;
-    const size_t mom = out_mom ? npx * 8 : 0; // the moments: prev's behind its side's images, the output behind the three outputs
-    // one temporary buffer: per side [M | M^-1 | gbuffer | colour | variance | history | (moments)], then the three outputs (and the moments)
-    const size_t resp = out_resp ? npx * 4 : 0; // lambda: the last output
-    const size_t side = (2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4) + mom + 255) & ~(size_t)255, outs = npx * (16 + 4 + 4) + mom + resp; // (float4 images stay 16-byte aligned)
-    HostStage hs(c);
-    if (!hs.buf.reserve(2 * side + outs)) { set_error("hjr_temporal_accumulate: device allocation failed"); return HJR_ERR_DEVICE; }
-    TemporalSide s[2];
-    for (int i = have_prev ? 0 : 1; i < 2; i++) {
-        char* b = (char*)hs.buf.p + (size_t)i * side;
-        const void* src[6] = { f[i].transforms12, f[i].inv_transforms12, f[i].gbuffer, f[i].color, f[i].variance, i == 0 ? f[i].history : nullptr };
-        const size_t len[6] = { nx, nx, npx * sizeof(hjr_gbuffer_px), npx * 16, npx * 4, npx * 4 };
-        const void* dst[6];
-        for (int k = 0; k < 6; k++) {
-            dst[k] = b;
-            if (src[k]) hs.up(b, src[k], len[k]);
-            b += len[k];
+    const size_t mom = out_mom ? npx * 8 : 0, resp = out_resp ? npx * 4 : 0;
+    // One temporary buffer behind one cursor: per side M, M^-1, the G-buffer, colour, variance (prev: history, moments), then the outputs.
+    // Alignment: every image starts at a multiple of its element's (16 bytes for float4 and the records, 8 for float2, 4 for float).
+    hjr_temporal_frame d[2]; // the staged copies: f[i] with device pointers
+    const void* d_prev_mom = nullptr;
+    TemporalOut out;
+    const auto layout = [&](uintptr_t base) { // places every image from `base` on; returns the bytes that takes
+        size_t at = 0;
+        const auto take = [&](size_t bytes, size_t align) { const size_t o = (at + align - 1) & ~(align - 1); at = o + bytes; return (void*)(base + o); };
+        for (int i = have_prev ? 0 : 1; i < 2; i++) {
+            d[i] = f[i];
+            d[i].transforms12 = (const float*)take(nx, 4); d[i].inv_transforms12 = (const float*)take(nx, 4);
+            d[i].gbuffer = (const hjr_gbuffer_px*)take(npx * sizeof(hjr_gbuffer_px), 16);
+            d[i].color = (const float*)take(npx * 16, 16); d[i].variance = (const float*)take(npx * 4, 4);
+            d[i].history = i == 0 ? (const float*)take(npx * 4, 4) : nullptr;
+            if (i == 0 && mom) d_prev_mom = take(mom, 8);
         }
-        s[i].cam = f[i].camera; s[i].m = (const float*)dst[0]; s[i].inv = (const float*)dst[1]; s[i].gbuf = (const hjr_gbuffer_px*)dst[2];
-        s[i].color = (const float4*)dst[3]; s[i].variance = (const float*)dst[4]; s[i].history = (const float*)dst[5];
-        if (i == 0 && mom) hs.up(b, prev_mom, mom); // (b: behind the history, 96 n + 72 npx bytes into the side: float2 stays 8-byte aligned)
+        out.color = (float4*)take(npx * 16, 16); out.variance = (float*)take(npx * 4, 4); out.history = (float*)take(npx * 4, 4);
+        out.moments = mom ? (float2*)take(mom, 8) : nullptr; out.response = resp ? (float*)take(resp, 4) : nullptr;
+        return at;
+    };
+    HostStage hs(c);
+    if (!hs.buf.reserve(layout(0))) { set_error("hjr_temporal_accumulate: device allocation failed"); return HJR_ERR_DEVICE; }
+    layout((uintptr_t)hs.buf.p);
+    for (int i = have_prev ? 0 : 1; i < 2; i++) {
+        hs.up((void*)d[i].transforms12, f[i].transforms12, nx);
+        hs.up((void*)d[i].inv_transforms12, f[i].inv_transforms12, nx);
+        hs.up((void*)d[i].gbuffer, f[i].gbuffer, npx * sizeof(hjr_gbuffer_px));
+        hs.up((void*)d[i].color, f[i].color, npx * 16);
+        hs.up((void*)d[i].variance, f[i].variance, npx * 4);
+        if (i == 0) hs.up((void*)d[i].history, f[i].history, npx * 4);
     }
-    char* const o = (char*)hs.buf.p + 2 * side;
-    const char* const pm = (const char*)hs.buf.p + 2 * nx + npx * (sizeof(hjr_gbuffer_px) + 16 + 4 + 4);
-    if (hs.ok()) hs.rc = temporal_launch(c, have_prev ? &s[0] : nullptr, s[1], f[1].width, f[1].height, f[1].n_instances, o, o + npx * 16, o + npx * 20, c->stream,
-                                         have_prev ? f[0].coverage : 0u, f[1].coverage, have_prev && mom ? pm : nullptr, mom ? o + npx * 24 : nullptr,
-                                         resp ? o + npx * 24 + mom : nullptr);
-    hs.down(out_color, o, npx * 16);
-    hs.down(out_var, o + npx * 16, npx * 4);
-    hs.down(out_hist, o + npx * 20, npx * 4);
-    if (mom) hs.down(out_mom, o + npx * 24, mom);
-    if (resp) hs.down(out_resp, o + npx * 24 + mom, resp);
+    if (d_prev_mom) hs.up((void*)d_prev_mom, prev_mom, mom);
+    const TemporalSide ps = have_prev ? temporal_side(d[0], d_prev_mom) : TemporalSide(), cs = temporal_side(d[1], nullptr);
+    if (hs.ok()) hs.rc = temporal_launch(c, have_prev ? &ps : nullptr, cs, f[1].width, f[1].height, f[1].n_instances, out, c->stream);
+    hs.down(out_color, out.color, npx * 16);
+    hs.down(out_var, out.variance, npx * 4);
+    hs.down(out_hist, out.history, npx * 4);
+    hs.down(out_mom, out.moments, mom);
+    hs.down(out_resp, out.response, resp);
     return hs.finish("hjr_temporal_accumulate");
 }
 extern "C" int hjr_temporal_accumulate_moments(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_color, float* out_var, float* out_hist,
@@ -1469,10 +1467,10 @@ static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
 {
     hjr_ctx::Temporal& t = c->tmp;
     const size_t npx = (size_t)p->width * p->height, nx = c->built.m.size() * 4;
-    const int k = t.cur;
-    if (!t.color[k].reserve(npx * 16) || !t.variance[k].reserve(npx * 4) || !t.history[k].reserve(npx * 4) || !t.gbuf[k].reserve(npx * sizeof(hjr_gbuffer_px)) ||
-        !t.xf[k].reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
-    if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) && !t.moments[k].reserve(npx * 8)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
+    hjr_ctx::Temporal::Slot& s = t.slot[t.cur];
+    if (!s.color.reserve(npx * 16) || !s.variance.reserve(npx * 4) || !s.history.reserve(npx * 4) || !s.gbuf.reserve(npx * sizeof(hjr_gbuffer_px)) ||
+        !s.xf.reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
+    if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) && !s.moments.reserve(npx * 8)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_RESPONSE, 0) && !t.response.reserve(npx * 4)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     return HJR_OK;
 }
@@ -1482,28 +1480,30 @@ static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool
     const uint32_t n_inst = (uint32_t)(c->built.m.size() / 12);
     if (t.have_prev && (t.width != p->width || t.height != p->height || t.mode != render_mode || t.n_instances != n_inst)) t.have_prev = false;
     const size_t nx = (size_t)n_inst * 48;
-    const int k = t.cur;
     if (const int rc = temporal_reserve(c, p)) return rc;
+    hjr_ctx::Temporal::Slot &now = t.slot[t.cur], &before = t.slot[t.cur ^ 1];
     const uint32_t cov = (uint32_t)c->opt.get(hjr::OPT_DENOISE_TEMPORAL_COVERAGE, 0); // option "denoise_temporal_coverage": the coverage pass and rules 2' / 3' (setting it drops the history, so both slots agree)
-    if (const int rc = gbuffer_device_impl(c, p, t.gbuf[k].p, st, cov)) return rc;
+    if (const int rc = gbuffer_device_impl(c, p, now.gbuf.p, st, cov)) return rc;
     if (nx) {
-        HIPCHK(hipMemcpyAsync(t.xf[k].p, c->built.m.data(), nx, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((char*)t.xf[k].p + nx, c->built.inv.data(), nx, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(now.xf.p, c->built.m.data(), nx, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((char*)now.xf.p + nx, c->built.inv.data(), nx, hipMemcpyHostToDevice, st));
     }
-    t.cam[k] = p->camera;
-    TemporalSide s[2];
-    for (int i = 0; i < 2; i++) {
-        const int q = i == 0 ? (k ^ 1) : k;
-        s[i].cam = t.cam[q]; s[i].m = (const float*)t.xf[q].p; s[i].inv = (const float*)((const char*)t.xf[q].p + nx); s[i].gbuf = (const hjr_gbuffer_px*)t.gbuf[q].p;
-        s[i].color = (const float4*)t.color[q].p; s[i].variance = (const float*)t.variance[q].p; s[i].history = (const float*)t.history[q].p;
-    }
-    s[1].color = (const float4*)d_color; s[1].variance = (const float*)d_var; s[1].history = nullptr;
+    now.cam = p->camera;
     const bool mom = c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) != 0; // option "denoise_temporal_moments": both slots carry (m1, m2) (setting it drops the history, so the previous slot has them)
     const bool resp = c->opt.get(hjr::OPT_DENOISE_TEMPORAL_RESPONSE, 0) != 0; // option "denoise_temporal_response": the windowed change test; its lambda image is written and not read again
-    if (const int rc = temporal_launch(c, t.have_prev ? &s[0] : nullptr, s[1], p->width, p->height, n_inst, t.color[k].p, t.variance[k].p, t.history[k].p, st, cov, cov,
-                                       mom && t.have_prev ? t.moments[k ^ 1].p : nullptr, mom ? t.moments[k].p : nullptr, resp ? t.response.p : nullptr)) return rc;
-    d_color = t.color[k].p; d_var = t.variance[k].p;
-    if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur = k ^ 1; }
+    const auto frame_of = [&](const hjr_ctx::Temporal::Slot& s) { // a slot as a frame of device pointers
+        hjr_temporal_frame f = {};
+        f.camera = s.cam; f.transforms12 = (const float*)s.xf.p; f.inv_transforms12 = (const float*)((const char*)s.xf.p + nx); f.gbuffer = (const hjr_gbuffer_px*)s.gbuf.p;
+        f.color = (const float*)s.color.p; f.variance = (const float*)s.variance.p; f.history = (const float*)s.history.p; f.coverage = cov;
+        return f;
+    };
+    hjr_temporal_frame cur = frame_of(now);
+    cur.color = (const float*)d_color; cur.variance = (const float*)d_var; cur.history = nullptr; // what was rendered: the slot's own images are the outputs
+    const TemporalSide ps = temporal_side(frame_of(before), mom ? before.moments.p : nullptr), cs = temporal_side(cur, nullptr);
+    const TemporalOut out = { (float4*)now.color.p, (float*)now.variance.p, (float*)now.history.p, mom ? (float2*)now.moments.p : nullptr, resp ? (float*)t.response.p : nullptr };
+    if (const int rc = temporal_launch(c, t.have_prev ? &ps : nullptr, cs, p->width, p->height, n_inst, out, st)) return rc;
+    d_color = now.color.p; d_var = now.variance.p;
+    if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur ^= 1; }
     return HJR_OK;
 }
 
@@ -1621,7 +1621,7 @@ static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, const PostPlan& p
                                    out_w, out_h, st);
     void* const filtered = c->d_dn_a.p; // the last pass reads d_dn_b: the bilinear path's buffers
     if (const int rc = denoise_device_impl(c, HJR_MODE_DENOISE, p->width, p->height, f_color, c->d_albedo.p, c->d_normal.p, pl.with_var, f_var, filtered, p->width, p->height, st)) return rc;
-    const void* g_lo = pl.temporal ? c->tmp.gbuf[slot].p : c->d_ug_lo.p;
+    const void* g_lo = pl.temporal ? c->tmp.slot[slot].gbuf.p : c->d_ug_lo.p;
     if (!pl.temporal)
         if (const int rc = gbuffer_device_impl(c, p, c->d_ug_lo.p, st, 0)) return rc;
     hjr_params hi = *p;

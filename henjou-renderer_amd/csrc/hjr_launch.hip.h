@@ -129,16 +129,18 @@ struct hjr_ctx {
         hipEvent_t ready = nullptr;
     } ad;
     // Temporal accumulation (option "denoise_temporal", csrc/hjr_temporal.hip.h).  Nothing here is allocated before the first render with the
-    // option on.  Two slots in rotation: `cur` receives the frame being rendered, cur ^ 1 holds the committed previous frame (if have_prev).
+    // option on.  Two slots in rotation: slot[cur] receives the frame being rendered, slot[cur ^ 1] holds the committed previous frame (if have_prev).
     struct Temporal {
+        struct Slot {
+            hjr_camera cam;
+            DevBuf color, variance, history, gbuf, xf; // accumulated unfiltered colour | its variance | h | G-buffer | [M | M^-1] of that render
+            DevBuf moments;                            // option "denoise_temporal_moments": float2 (m1, m2) per pixel
+        } slot[2];
+        DevBuf response;                               // option "denoise_temporal_response": lambda per pixel of the last accumulation
         bool have_prev = false;
         int cur = 0;
         uint32_t width = 0, height = 0, n_instances = 0; // of the previous frame
         int mode = 0;
-        hjr_camera cam[2];
-        DevBuf color[2], variance[2], history[2], gbuf[2], xf[2]; // accumulated unfiltered colour | its variance | h | G-buffer | [M | M^-1] of that render
-        DevBuf moments[2];                                        // option "denoise_temporal_moments": float2 (m1, m2) per pixel
-        DevBuf response;                                          // option "denoise_temporal_response": lambda per pixel of the last accumulation
     } tmp;
     hjr::Options opt; // hjr_set_option (host/options.hpp): the library reads no environment variable
 };

@@ -61,7 +61,8 @@
 //   that partly covers geometry is known); every other field of a miss record stays 0.  hjr_gbuffer_kernel<WIDTH, false> writes pad = 0.
 //
 // COVERAGE-AWARE ACCUMULATION (hjr_temporal_kernel<true>: the ACCUMULATION above with two more inputs, prev.coverage and cur.coverage, the
-//   `coverage` fields of the two hjr_temporal_frame; with both 0 it is the rule above bit for bit, and that case runs hjr_temporal_kernel<false>).
+//   `coverage` fields of the two hjr_temporal_frame (and of the two TemporalSide); with both 0 it is the rule above bit for bit, and that
+//   case runs hjr_temporal_kernel<false>).
 //   A record R of a side whose coverage != 0 is MIXED iff  total = (R.pad >> 8) & 0xff  is above 0 and  (R.pad & 0xff) < total;  a record of a
 //   side whose coverage == 0 is never mixed and its pad is not looked at.  pad is only ever compared, never used as an index.
 //   3'. G not mixed: a tap whose record T (of prev) is mixed is INVALID; everything else is unchanged.
@@ -74,7 +75,8 @@
 //   one.  A static sequence still accumulates everywhere: the reprojection lands on the centre up to rounding.
 //
 // TEMPORAL MOMENTS (hjr_temporal_kernel<COV, true>: the ACCUMULATION above, with or without the coverage rules, with one more input,
-//   prev.moments (the entry points' prev_moments argument, not a field of hjr_temporal_frame), and one more output, both float2 (m1, m2) per pixel: the accumulated first and second moment of the luminance
+//   prev.moments (a field of the device-side TemporalSide; the public entry points take it as their prev_moments argument, it is no field
+//   of hjr_temporal_frame), and one more output, both float2 (m1, m2) per pixel: the accumulated first and second moment of the luminance
 //     l = (cur.r + cur.g) + cur.b     of the current frame's colour as the kernel reads it.   DESIGN.md §11.7.)
 //   RESTART (every case above): additionally  m1 = l,  m2 = l * l.   Colour, variance and h are the ones above.
 //   4. per valid tap, in tap order, both sums from +0.0f, pm = prev.moments[tap]:   M1 = M1 + pm.x * w_k;   M2 = M2 + pm.y * w_k.
@@ -199,7 +201,7 @@ __global__ void __launch_bounds__(64) hjr_gbuffer_kernel(const GbufArgs A)
     }
 }
 
-// device view of one hjr_temporal_frame
+// device view of one frame: a hjr_temporal_frame and, for prev, the entry points' prev_moments
 struct TemporalSide {
     hjr_camera cam;
     const float* m;             // n_instances x 12
@@ -208,16 +210,22 @@ struct TemporalSide {
     const float4* color;
     const float* variance;
     const float* history;       // prev only
+    const float2* moments;      // MOM, prev only
+    uint32_t coverage;          // COV: hjr_temporal_frame.coverage
+};
+// what a launch writes; the two optional images choose the kernel (hjr_device.hip: temporal_launch)
+struct TemporalOut {
+    float4* color;
+    float* variance;
+    float* history;
+    float2* moments;            // MOM
+    float* response;            // hjr_temporal_resp_kernel: lambda
 };
 struct TemporalArgs {
-    TemporalSide prev, cur;
+    TemporalSide cur, prev;     // prev is all zero unless have_prev (cur first: with prev first hjr_temporal_resp_kernel<false, true> keeps
+                                // 10 SGPRs in VGPR lanes for 8)
+    TemporalOut out;
     uint32_t have_prev, width, height, n_instances, n_tris;
-    float4* out_color;
-    float* out_variance;
-    float* out_history;
-    uint32_t prev_cov, cur_cov; // COV: the two sides' hjr_temporal_frame.coverage
-    const float2* prev_moments; // MOM: the previous frame's moments (at the end: the other fields keep their places in the argument block)
-    float2* out_moments;        // MOM
 };
 
 HD f3 t_xf(const float* __restrict__ m, f3 p)
@@ -246,9 +254,8 @@ struct TemporalPrev {
 
 // Steps 1 to 4 of ACCUMULATION (with 2' / 3' and the moments' sums) for the pixel whose record is G, up to the divides by S: a carried
 // pixel calls carried(P) at the place step 4 blends, a RESTART calls nothing.  Shared by hjr_temporal_kernel and hjr_temporal_resp_kernel.
-// A callback and the argument block by value, not a returned flag and a reference, and hjr_temporal_kernel's body in a function that takes
-// the block by value as well: of the forms tried, the one in which the four hjr_temporal_kernel instantiations keep the instructions
-// they had as one body (the same opcodes the same number of times; a few commuted operands and reordered neighbours).
+// A callback and the argument block by value, not a returned flag and a reference: by reference the plain-G-buffer response kernels keep
+// 12 and 10 SGPRs in VGPR lanes for 4 and 8, and every kernel is 6 to 48 instructions longer (profiles/temporal_fold_kernel_resources.txt).
 template <bool COV, bool MOM, typename Carried>
 __device__ __forceinline__ void hjr_temporal_gather(const TemporalArgs A, const size_t pix, Carried carried)
 {
@@ -267,7 +274,7 @@ __device__ __forceinline__ void hjr_temporal_gather(const TemporalArgs A, const 
         const float u = su / s, v = sv / s;
         const float xp = (u * H + W) * 0.5f - 0.5f, yp = (v * H + H) * 0.5f - 0.5f;
         if (det != 0.0f && s > 0.0f && t_finite(s) && t_finite(u) && t_finite(v) && xp >= -1.0f && xp < W && yp >= -1.0f && yp < H) {
-            const bool g_mixed = COV && A.cur_cov != 0u && t_mixed(G.pad);
+            const bool g_mixed = COV && A.cur.coverage != 0u && t_mixed(G.pad);
             const float fx = floorf(xp), fy = floorf(yp);
             const float xr = floorf(xp + 0.5f), yr = floorf(yp + 0.5f); // within [-1, W] x [-1, H] by the range test above
             const bool snap = fabsf(xp - xr) <= HJR_TEMPORAL_SNAP && fabsf(yp - yr) <= HJR_TEMPORAL_SNAP;
@@ -293,7 +300,7 @@ __device__ __forceinline__ void hjr_temporal_gather(const TemporalArgs A, const 
                 const size_t tap = (size_t)yt * A.width + (size_t)xt;
                 const hjr_gbuffer_px T = A.prev.gbuf[tap];
                 if (T.prim == 0xffffffffu || T.prim >= A.n_tris || T.inst != G.inst) continue; // (G.inst < n_instances: so is T.inst)
-                if (COV && A.prev_cov != 0u && (g_mixed ? T.pad != G.pad : t_mixed(T.pad))) continue; // rules 2' and 3'
+                if (COV && A.prev.coverage != 0u && (g_mixed ? T.pad != G.pad : t_mixed(T.pad))) continue; // rules 2' and 3'
                 const f3 e = t_xf(A.prev.inv + (size_t)T.inst * 12u, V(T.pos[0], T.pos[1], T.pos[2])) - p_obj;
                 const f3 D = t_lin(m_cur, e);
                 const float nd = t_dot(ng, D);
@@ -306,7 +313,7 @@ __device__ __forceinline__ void hjr_temporal_gather(const TemporalArgs A, const 
                 Vs = Vs + fmaxf(pv, 0.0f) * wk[k];
                 Hs = Hs + A.prev.history[tap] * wk[k];
                 if constexpr (MOM) {
-                    const float2 pm = A.prev_moments[tap];
+                    const float2 pm = A.prev.moments[tap];
                     M1 = M1 + pm.x * wk[k]; M2 = M2 + pm.y * wk[k];
                 }
             }
@@ -321,8 +328,7 @@ __device__ __forceinline__ void hjr_temporal_gather(const TemporalArgs A, const 
     }
 }
 
-// Step 4's blend as section RESPONSE has it, for hjr_temporal_resp_kernel: al and h answer to lambda first.  (RESP = false is the blend
-// written out in hjr_temporal_pixel, which keeps its own text: called from there, this function changes that kernel's code.)
+// Step 4's blend (with the moments' part); RESP: as section RESPONSE has it, al and h answer to lambda first.
 template <bool MOM, bool RESP>
 __device__ __forceinline__ void hjr_temporal_blend(const TemporalPrev& P, float4 cc, float cv, [[maybe_unused]] float lum, [[maybe_unused]] float lambda, float4& out, float& var,
                                                    float& hist, [[maybe_unused]] float& m1, [[maybe_unused]] float& m2)
@@ -348,9 +354,8 @@ __device__ __forceinline__ void hjr_temporal_blend(const TemporalPrev& P, float4
     }
 }
 
-// hjr_temporal_kernel's body (by value: see hjr_temporal_gather)
 template <bool COV, bool MOM>
-__device__ __forceinline__ void hjr_temporal_pixel(const TemporalArgs A)
+__global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
 {
     const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
     if (x >= A.width || y >= A.height) return;
@@ -361,37 +366,11 @@ __device__ __forceinline__ void hjr_temporal_pixel(const TemporalArgs A)
     float var = cv, hist = 1.0f;
     [[maybe_unused]] float lum = 0.0f, m1 = 0.0f, m2 = 0.0f;
     if constexpr (MOM) { lum = (cc.x + cc.y) + cc.z; m1 = lum; m2 = lum * lum; }
-    // (step 4's blend stays written out here, as it always was)
-    hjr_temporal_gather<COV, MOM>(A, pix, [&](const TemporalPrev& P) {
-        const float px_ = P.cx, py_ = P.cy, pz_ = P.cz, v_prev = P.v, h_prev = P.h;
-        bool unknown = P.unknown;
-        hist = fminf(fmaxf(h_prev + 1.0f, 1.0f), HJR_TEMPORAL_H_MAX);
-        const float al = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA);
-        out.x = px_ + (cc.x - px_) * al; out.y = py_ + (cc.y - py_) * al; out.z = pz_ + (cc.z - pz_) * al;
-        unknown = unknown || !(cv < HJR_VARIANCE_UNKNOWN);
-        const float om = 1.0f - al;
-        var = unknown ? HJR_VARIANCE_UNKNOWN : (om * om) * v_prev + (al * al) * fmaxf(cv, 0.0f);
-        if constexpr (MOM) {
-            const float m1p = P.m1, m2p = P.m2;
-            m1 = m1p + (lum - m1p) * al; m2 = m2p + (lum * lum - m2p) * al;
-            if (hist >= HJR_TEMPORAL_MOMENTS_MIN) {
-                const float kk = fmaxf(1.0f / hist, HJR_TEMPORAL_ALPHA / (2.0f - HJR_TEMPORAL_ALPHA));
-                const float d = m2 - m1 * m1;
-                const float mv = t_finite(d) ? fmaxf(d, 0.0f) * (kk / (1.0f - kk)) : HJR_VARIANCE_UNKNOWN;
-                var = mv < HJR_VARIANCE_UNKNOWN ? mv : HJR_VARIANCE_UNKNOWN;
-            }
-        }
-    });
-    A.out_color[pix] = out;
-    A.out_variance[pix] = var;
-    A.out_history[pix] = hist;
-    if constexpr (MOM) A.out_moments[pix] = make_float2(m1, m2);
-}
-
-template <bool COV, bool MOM>
-__global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
-{
-    hjr_temporal_pixel<COV, MOM>(A);
+    hjr_temporal_gather<COV, MOM>(A, pix, [&](const TemporalPrev& P) { hjr_temporal_blend<MOM, false>(P, cc, cv, lum, 0.0f, out, var, hist, m1, m2); });
+    A.out.color[pix] = out;
+    A.out.variance[pix] = var;
+    A.out.history[pix] = hist;
+    if constexpr (MOM) A.out.moments[pix] = make_float2(m1, m2);
 }
 
 // RESPONSE (section RESPONSE of the header comment).  A 256-thread workgroup owns a 16 x 16 pixel tile and stages the tile and a halo of
@@ -409,7 +388,7 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
 static_assert(RESP_HALO <= 256 && RESP_SIDE <= RESP_STRIDE && RESP_STRIDE % 32 == 16, "one halo round, rows that fit, rows of a half on unlike banks");
 
 template <bool COV, bool MOM>
-__global__ void __launch_bounds__(256) hjr_temporal_resp_kernel(const TemporalArgs A, float* __restrict__ out_response)
+__global__ void __launch_bounds__(256) hjr_temporal_resp_kernel(const TemporalArgs A)
 {
     __shared__ float s_lc[RESP_SIDE * RESP_STRIDE], s_d[RESP_SIDE * RESP_STRIDE];
     __shared__ uint32_t s_key[RESP_SIDE * RESP_STRIDE];
@@ -479,9 +458,9 @@ __global__ void __launch_bounds__(256) hjr_temporal_resp_kernel(const TemporalAr
         hjr_temporal_blend<MOM, true>(own, own_cc, own_cv, own_lc, lambda, out, var, hist, m1, m2);
     }
     const size_t pix = (size_t)(blockIdx.y * RESP_TILE + ly) * A.width + (blockIdx.x * RESP_TILE + lx);
-    A.out_color[pix] = out;
-    A.out_variance[pix] = var;
-    A.out_history[pix] = hist;
-    if constexpr (MOM) A.out_moments[pix] = make_float2(m1, m2);
-    out_response[pix] = lambda;
+    A.out.color[pix] = out;
+    A.out.variance[pix] = var;
+    A.out.history[pix] = hist;
+    if constexpr (MOM) A.out.moments[pix] = make_float2(m1, m2);
+    A.out.response[pix] = lambda;
 }

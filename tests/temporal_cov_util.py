@@ -4,30 +4,15 @@
 2' and 3'), the inputs it takes, and the cameras and sequences the GPU tests, tools/temporal_rehearsal.py and tools/temporal_bench.py use."""
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 
 import trace_util
-from scene_util import ROOT, hjr
-from temporal_util import _side_bytes, cam_floats, camera_at, moved_consistent, ref_mask, rmse
+from scene_util import hjr
+from temporal_util import _side_bytes, build_checker, cam_floats, camera_at, moved_consistent, ref_mask, rmse
 
 f32 = np.float32
 SNAP = f32(0.125)
-
-_exe = None
-_dir = None
-
-
-def checker():
-    global _exe, _dir
-    if _exe is None:
-        _dir = tempfile.TemporaryDirectory(prefix="hjr_tcov_")
-        exe = os.path.join(_dir.name, "temporal_cov_ref")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "native", "temporal_cov_ref.cpp"), "-o", exe])
-        _exe = exe
-    return _exe
-
 
 def pad_word(same, total):
     return np.uint32(same | (total << 8))
@@ -66,8 +51,8 @@ def rows_from_device(dev, arrays):
 
 def gbuffer_cov_ref(rows, tri_inst, tri_mat, w, h, cam, side):
     """The native checker's coverage pass (side 0: the plain G-buffer): GBUFFER_DTYPE [h, w]."""
-    exe = checker()
-    src, dst = os.path.join(_dir.name, "g_in.bin"), os.path.join(_dir.name, "g_out.bin")
+    exe, tmp = build_checker("temporal_cov_ref")
+    src, dst = os.path.join(tmp, "g_in.bin"), os.path.join(tmp, "g_out.bin")
     rows = np.ascontiguousarray(rows, f32).reshape(-1, 12)
     with open(src, "wb") as f:
         f.write(cam_floats(cam).tobytes() + rows.tobytes() + np.ascontiguousarray(tri_inst, np.uint32).tobytes() + np.ascontiguousarray(tri_mat, np.uint32).tobytes())
@@ -79,10 +64,10 @@ def gbuffer_cov_ref(rows, tri_inst, tri_mat, w, h, cam, side):
 def temporal_cov_ref(prev, cur, n_tris, snap=None):
     """The native checker's accumulation on dicts as Device.temporal_accumulate takes them (key "coverage" per side, absent = 0):
     (color [h, w, 4], variance [h, w], history [h, w])."""
-    exe = checker()
+    exe, tmp = build_checker("temporal_cov_ref")
     h, w = np.asarray(cur["gbuffer"]).shape
     n_inst = np.asarray(cur["transforms"], f32).size // 12
-    src, dst = os.path.join(_dir.name, "a_in.bin"), os.path.join(_dir.name, "a_out.bin")
+    src, dst = os.path.join(tmp, "a_in.bin"), os.path.join(tmp, "a_out.bin")
     with open(src, "wb") as f:
         if prev is not None:
             f.write(_side_bytes(prev, True))

@@ -5,39 +5,23 @@ the header comment of csrc/hjr_temporal.hip.h), the chain of stateless stages th
 comparison of §11.7."""
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 
-from scene_util import ROOT, hjr
-from temporal_util import _side_bytes, ref_mask, rmse
+from temporal_util import _side_bytes, build_checker, ref_mask, rmse
 
 f32 = np.float32
 UNKNOWN = f32(1e30)
 MOMENTS_MIN = f32(4.0)
 K_LIMIT = f32(0.2) / (f32(2.0) - f32(0.2))  # HJR_TEMPORAL_ALPHA / (2 - HJR_TEMPORAL_ALPHA)
 
-_exe = None
-_dir = None
-
-
-def checker():
-    global _exe, _dir
-    if _exe is None:
-        _dir = tempfile.TemporaryDirectory(prefix="hjr_tmom_")
-        exe = os.path.join(_dir.name, "temporal_moments_ref")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "native", "temporal_moments_ref.cpp"), "-o", exe])
-        _exe = exe
-    return _exe
-
-
 def temporal_moments_ref(prev, cur, n_tris, moments=True, moments_min=None):
     """The native checker on dicts as Device.temporal_accumulate takes them (key "coverage" per side, absent = 0; prev["moments"] [h, w, 2]
     when moments): (color [h, w, 4], variance [h, w], history [h, w], moments [h, w, 2]); without moments the first three."""
-    exe = checker()
+    exe, tmp = build_checker("temporal_moments_ref")
     h, w = np.asarray(cur["gbuffer"]).shape
     n_inst = np.asarray(cur["transforms"], f32).size // 12
-    src, dst = os.path.join(_dir.name, "in.bin"), os.path.join(_dir.name, "out.bin")
+    src, dst = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     with open(src, "wb") as f:
         if prev is not None:
             f.write(_side_bytes(prev, True))
@@ -54,29 +38,6 @@ def temporal_moments_ref(prev, cur, n_tris, moments=True, moments_min=None):
     assert raw.size == n * (8 if moments else 6)
     out = (raw[:n * 4].reshape(h, w, 4), raw[n * 4:n * 5].reshape(h, w), raw[n * 5:n * 6].reshape(h, w))
     return out + (raw[n * 6:].reshape(h, w, 2),) if moments else out
-
-
-def same_bits(a, b):
-    """Bit equality of two float32 arrays (NaN payloads included)."""
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def assert_same(got, want, what):
-    names = ("colour", "variance", "history", "moments")
-    assert len(got) == len(want)
-    for name, g, w in zip(names, got, want):
-        assert same_bits(g, w), "%s: %s differs in %d values" % (what, name, int(np.sum(np.ascontiguousarray(g, f32).view(np.uint32) != np.ascontiguousarray(w, f32).view(np.uint32))))
-
-
-def luminance(color):
-    c = np.asarray(color, f32)
-    return (c[..., 0] + c[..., 1]) + c[..., 2]
-
-
-def next_prev(cur, out):
-    """The next call's previous frame from this call's current one and its four outputs."""
-    return dict(cur, color=out[0], variance=out[1], history=out[2], moments=out[3])
 
 
 # ---- the quality comparison of §11.7: per-frame RMSE of filter(temporal path) against the frame's reference, four ways

@@ -5,39 +5,24 @@ COVERAGE-AWARE ACCUMULATION, TEMPORAL MOMENTS and RESPONSE of the header comment
 section RESPONSE alone, the three test sequences S, L and M, and the quality comparison of §11.8."""
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 
-from scene_util import ROOT, hjr
-from temporal_util import MISS, _side_bytes, moved_consistent, ref_mask, rmse, translated
+from scene_util import hjr
+from temporal_util import MISS, _side_bytes, build_checker, luminance, moved_consistent, next_prev, ref_mask, rmse, translated
 
 f32 = np.float32
 UNKNOWN = f32(1e30)
 ALPHA = f32(0.2)
 RESP_R, RESP_T0, RESP_T1, RESP_NMIN, RESP_EPS = 2, f32(3.0), f32(6.0), 5, f32(1e-3)
 
-_exe = None
-_dir = None
-
-
-def checker():
-    global _exe, _dir
-    if _exe is None:
-        _dir = tempfile.TemporaryDirectory(prefix="hjr_tresp_")
-        exe = os.path.join(_dir.name, "temporal_response_ref")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "native", "temporal_response_ref.cpp"), "-o", exe])
-        _exe = exe
-    return _exe
-
-
 def temporal_response_ref(prev, cur, n_tris, moments=False, response=True, radius=None):
     """The native checker on dicts as Device.temporal_accumulate takes them (key "coverage" per side, absent = 0; prev["moments"] [h, w, 2]
     when moments): (color [h, w, 4], variance [h, w], history [h, w], moments [h, w, 2] if moments, lambda [h, w] if response)."""
-    exe = checker()
+    exe, tmp = build_checker("temporal_response_ref")
     h, w = np.asarray(cur["gbuffer"]).shape
     n_inst = np.asarray(cur["transforms"], f32).size // 12
-    src, dst = os.path.join(_dir.name, "in.bin"), os.path.join(_dir.name, "out.bin")
+    src, dst = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     with open(src, "wb") as f:
         if prev is not None:
             f.write(_side_bytes(prev, True))
@@ -60,32 +45,6 @@ def temporal_response_ref(prev, cur, n_tris, moments=False, response=True, radiu
     if response:
         out.append(raw[at:].reshape(h, w))
     return tuple(out)
-
-
-def same_bits(a, b):
-    """Bit equality of two float32 arrays (NaN payloads included)."""
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def assert_same(got, want, what, moments=False):
-    names = ("colour", "variance", "history") + (("moments",) if moments else ()) + ("lambda",)
-    assert len(got) == len(want), (len(got), len(want))
-    for name, g, w in zip(names, got, want):
-        assert same_bits(g, w), "%s: %s differs in %d values" % (what, name, int(np.sum(np.ascontiguousarray(g, f32).view(np.uint32) != np.ascontiguousarray(w, f32).view(np.uint32))))
-
-
-def luminance(color):
-    c = np.asarray(color, f32)
-    return (c[..., 0] + c[..., 1]) + c[..., 2]
-
-
-def next_prev(cur, out, moments=False):
-    """The next call's previous frame from this call's current one and its outputs."""
-    d = dict(cur, color=out[0], variance=out[1], history=out[2])
-    if moments:
-        d["moments"] = out[3]
-    return d
 
 
 # ---- section RESPONSE alone, in numpy float32: every operation as written, the window in its order, one pixel image per window offset

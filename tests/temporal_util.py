@@ -1,6 +1,7 @@
-"""Shared by the temporal-accumulation tests: the native checker of the accumulation rule (tests/native/temporal_ref.cpp, built once per
-process with g++ -O2 -ffp-contract=off; it restates the header comment of csrc/hjr_temporal.hip.h), the numpy float32 restatement of the
-pixel-centre ray, and small builders of frames (dicts of arrays as Device.temporal_accumulate takes them)."""
+"""Shared by the temporal-accumulation tests: the native checker of the accumulation rule (tests/native/temporal_ref.cpp; it restates the
+header comment of csrc/hjr_temporal.hip.h), the numpy float32 restatement of the pixel-centre ray, and small builders of frames (dicts of
+arrays as Device.temporal_accumulate takes them).  And what the coverage, moments and response utilities beside it share: build_checker
+(every native checker, built once per process with g++ -O2 -ffp-contract=off), same_bits, assert_same, luminance, next_prev."""
 import ctypes as C
 import os
 import subprocess
@@ -14,18 +15,47 @@ f32 = np.float32
 UNKNOWN = f32(1e30)
 MISS = 0xffffffff
 
-_exe = None
-_dir = None
+_built = {}  # checker name -> (its temporary directory, the executable in it)
 
 
-def checker():
-    global _exe, _dir
-    if _exe is None:
-        _dir = tempfile.TemporaryDirectory(prefix="hjr_tmp_")
-        exe = os.path.join(_dir.name, "temporal_ref")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "native", "temporal_ref.cpp"), "-o", exe])
-        _exe = exe
-    return _exe
+def build_checker(name):
+    """tests/native/<name>.cpp, built once per process into a temporary directory of its own: (executable, that directory, where the
+    caller keeps the checker's input and output files)."""
+    if name not in _built:
+        tmp = tempfile.TemporaryDirectory(prefix="hjr_%s_" % name)
+        exe = os.path.join(tmp.name, name)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", exe])
+        _built[name] = (tmp, exe)
+    tmp, exe = _built[name]
+    return exe, tmp.name
+
+
+def same_bits(a, b):
+    """Bit equality of two float32 arrays (NaN payloads included)."""
+    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def assert_same(got, want, what, moments=False):
+    """Two tuples of outputs of the accumulation agree bit for bit: colour, variance, history, then (moments) the moments, then lambda."""
+    names = ("colour", "variance", "history") + (("moments",) if moments or (len(got) > 3 and np.ndim(got[3]) == 3) else ()) + ("lambda",)
+    assert len(got) == len(want), (len(got), len(want))
+    for name, g, w in zip(names, got, want):
+        assert same_bits(g, w), "%s: %s differs in %d values" % (what, name, int(np.sum(np.ascontiguousarray(g, f32).view(np.uint32) != np.ascontiguousarray(w, f32).view(np.uint32))))
+
+
+def luminance(color):
+    c = np.asarray(color, f32)
+    return (c[..., 0] + c[..., 1]) + c[..., 2]
+
+
+def next_prev(cur, out, moments=False):
+    """The next call's previous frame from this call's current one and its outputs (moments: out[3] holds them; a fourth output of shape
+    [h, w, 2] is taken for them as well, so the callers that always accumulate moments need not say so)."""
+    d = dict(cur, color=out[0], variance=out[1], history=out[2])
+    if moments or (len(out) > 3 and np.ndim(out[3]) == 3):
+        d["moments"] = out[3]
+    return d
 
 
 def cam_floats(cam):
@@ -47,10 +77,10 @@ def _side_bytes(d, with_history):
 
 def temporal_ref(prev, cur, n_tris, k=None):
     """The native checker: (color [h, w, 4], variance [h, w], history [h, w]).  k = (k_plane, k_dist) overrides the constants."""
-    exe = checker()
+    exe, tmp = build_checker("temporal_ref")
     h, w = np.asarray(cur["gbuffer"]).shape
     n_inst = np.asarray(cur["transforms"], f32).size // 12
-    src, dst = os.path.join(_dir.name, "in.bin"), os.path.join(_dir.name, "out.bin")
+    src, dst = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     with open(src, "wb") as f:
         if prev is not None:
             f.write(_side_bytes(prev, True))

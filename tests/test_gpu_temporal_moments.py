@@ -18,9 +18,8 @@ from denoise_var_util import denoise_var_ref
 from scene_util import ROOT, Cornell, f32_time, hjr
 from spatial_var_util import spatial_var_ref
 from temporal_cov_util import mixed, reprojection
-from temporal_moments_util import (MOMENTS_MIN, UNKNOWN, assert_same, format_tables, luminance, next_prev, quality_chain, quality_conditions, same_bits,
-                                   temporal_moments_ref)
-from temporal_util import MISS, camera_at, identity_xf, moved_consistent, plane_gbuffer, wall_camera
+from temporal_moments_util import MOMENTS_MIN, UNKNOWN, format_tables, quality_chain, quality_conditions, temporal_moments_ref
+from temporal_util import MISS, assert_same, camera_at, identity_xf, luminance, moved_consistent, next_prev, plane_gbuffer, same_bits, wall_camera
 from test_gpu_denoise_shards import render_shards
 from test_gpu_progressive import with_range
 from test_temporal_moments_host import hostile_moments

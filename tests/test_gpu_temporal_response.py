@@ -5,7 +5,8 @@ the ABI rules, the context option against the stateless pieces chained by hand, 
 option is for.
 
 Shapes: the kernel's workgroup owns 16 x 16 pixels and stages a halo of 2, so 37 x 19 has ragged tiles on both axes and windows that span
-four workgroups; the rendered chains run at 48 x 32, 16 spp (two chunks: the rendered variance is known)."""
+four workgroups; the rendered chains run at 48 x 32, 16 spp (two chunks: the rendered variance is known); section 5b runs every form of
+the kernel through both entries at 43 x 29, 4 spp."""
 import ctypes as C
 import json
 import os
@@ -18,9 +19,9 @@ import pytest
 from denoise_var_util import denoise_var_ref
 from scene_util import ROOT, Cornell, f32_time, hjr
 from temporal_cov_util import mixed
-from temporal_response_util import (P_TRIS, PH, PW, QFRAMES, assert_same, check_planes_lambda, format_tables, geometry_changes, next_prev, planes_case,
-                                    quality_chain, quality_conditions, same_bits, sequence_transforms, temporal_response_ref, worst_pixels)
-from temporal_util import MISS, camera_at, moved_consistent, ref_mask
+from temporal_response_util import (P_TRIS, PH, PW, QFRAMES, check_planes_lambda, format_tables, geometry_changes, planes_case, quality_chain, quality_conditions,
+                                    sequence_transforms, temporal_response_ref, worst_pixels)
+from temporal_util import MISS, assert_same, camera_at, moved_consistent, next_prev, ref_mask, same_bits
 from test_gpu_denoise_shards import render_shards
 from test_gpu_progressive import with_range
 
@@ -272,6 +273,73 @@ def test_abi_rules(torch, dev):
     assert L.hjr_temporal_accumulate_response_device(dev._h, C.byref(dp), C.byref(dc), ptr(d_out[0]), ptr(d_out[1]), None, None, None, ptr(d_out[4]), None) == ERR_ARG
     dev.synchronize()
     assert (d_out[4].cpu().numpy() == 7).all(), "nothing was enqueued"
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5b. every form, both entries
+FW, FH = 43, 29  # odd on both axes, no multiple of the response kernel's 16 x 16 tile or of the 64 x 4 grid cell, and an odd pixel count
+
+
+@pytest.fixture(scope="module")
+def form_frames(cornell, dev):
+    """{coverage: (prev, cur)} at 43 x 29 x 4 spp: frame 1 with a history of 5 everywhere and random moments, and frame 2 with every
+    instance moved one step, so the taps are bilinear and the window test has something to answer to.  Rendered once for the eight cases."""
+    cam, frames = camera_at(cornell), {}
+    try:
+        for coverage in (0, 2):
+            prev = rendered(cornell, dev, FW, FH, cam, 1, moved_consistent(cornell.arrays, 0), coverage=coverage, spp=4)
+            prev = with_moments(dict(prev, history=np.full((FH, FW), 5.0, f32)))
+            frames[coverage] = (prev, rendered(cornell, dev, FW, FH, cam, 2, moved_consistent(cornell.arrays, 1), coverage=coverage, spp=4))
+    finally:
+        dev.set_transforms(cornell.arrays["transforms"], cornell.arrays["inv_transforms"])
+    return frames
+
+
+@pytest.mark.parametrize("response", [False, True])
+@pytest.mark.parametrize("moments", [False, True])
+@pytest.mark.parametrize("coverage", [0, 2])
+def test_every_form_host_and_device_entry(torch, cornell, dev, form_frames, coverage, moments, response):
+    """All eight kernels (coverage x moments x response) at 43 x 29: the host entry, whose staging buffer then holds images of an odd
+    number of pixels back to back, equals the checker bit for bit in every returned array, and the matching _device entry on torch buffers
+    equals the host entry."""
+    prev, cur = form_frames[coverage]
+    hit = cur["gbuffer"]["prim"] != MISS
+    assert hit.any() and not hit.all() and (not coverage or mixed(cur["gbuffer"]).any())
+    got = dev.temporal_accumulate(prev, cur, moments=moments, response=response)
+    want = temporal_response_ref(prev, cur, n_tris(cornell), moments=moments, response=response)
+    assert len(got) == 3 + moments + response
+    assert_same(got, want, "host entry against the checker", moments)
+    assert (got[2] > 1).sum() >= 100 and (got[2] == 1).any() and (not response or (got[-1] > 0).any()), "carried pixels, restarts, a lambda above 0"
+    # the device entry of the same form
+    keep, t = [], {}
+    for name, d in (("p", prev), ("c", cur)):
+        for key in ("transforms", "inv_transforms", "color", "variance", "history", "moments"):
+            if d.get(key) is not None:
+                t[name + key] = torch.from_numpy(np.ascontiguousarray(d[key], f32)).cuda()
+        t[name + "gbuffer"] = torch.from_numpy(np.ascontiguousarray(d["gbuffer"]).view(np.uint8).reshape(-1).copy()).cuda()
+    frames = []
+    for name, d in (("p", prev), ("c", cur)):
+        f = hjr.Device._temporal_frame(d, keep)
+        f.transforms12, f.inv_transforms12, f.gbuffer = t[name + "transforms"].data_ptr(), t[name + "inv_transforms"].data_ptr(), t[name + "gbuffer"].data_ptr()
+        f.color, f.variance = t[name + "color"].data_ptr(), t[name + "variance"].data_ptr()
+        f.history = t[name + "history"].data_ptr() if name == "p" else None
+        frames.append(f)
+    shapes = [(FH, FW, 4), (FH, FW), (FH, FW)] + ([(FH, FW, 2)] if moments else []) + ([(FH, FW)] if response else [])
+    d_out = [torch.full(s, 7.0, dtype=torch.float32, device="cuda") for s in shapes]
+    torch.cuda.synchronize()
+    L = hjr.lib()
+    ptr = lambda a: C.c_void_p(a.data_ptr())
+    head = (dev._h, C.byref(frames[0]), C.byref(frames[1]), ptr(d_out[0]), ptr(d_out[1]), ptr(d_out[2]))
+    mom_args = (ptr(t["pmoments"]), ptr(d_out[3])) if moments else (None, None)
+    if response:
+        rc = L.hjr_temporal_accumulate_response_device(*head, *mom_args, ptr(d_out[-1]), None)
+    elif moments:
+        rc = L.hjr_temporal_accumulate_moments_device(*head, *mom_args, None)
+    else:
+        rc = L.hjr_temporal_accumulate_device(*head, None)
+    assert rc == 0, L.hjr_last_error()
+    dev.synchronize()
+    on_device = tuple(a.cpu().numpy() for a in d_out)
+    assert_same(on_device, got, "device entry against the host entry", moments)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 6. the context option

@@ -12,8 +12,8 @@ import pytest
 
 from scene_util import ROOT, Cornell, hjr
 from temporal_cov_util import pad_word, temporal_cov_ref
-from temporal_moments_util import K_LIMIT, MOMENTS_MIN, UNKNOWN, assert_same, luminance, next_prev, same_bits, temporal_moments_ref
-from temporal_util import identity_xf, temporal_ref, translated, wall_camera
+from temporal_moments_util import K_LIMIT, MOMENTS_MIN, UNKNOWN, temporal_moments_ref
+from temporal_util import assert_same, identity_xf, luminance, next_prev, same_bits, temporal_ref, translated, wall_camera
 from test_device_bvh import _option_json
 from test_temporal_host import H, W, WALL, frame
 

@@ -14,9 +14,9 @@ import pytest
 from scene_util import ROOT, Cornell, hjr
 from temporal_cov_util import pad_word
 from temporal_moments_util import temporal_moments_ref
-from temporal_response_util import (P_SPLIT, P_TRIS, PH, PW, RESP_EPS, RESP_NMIN, RESP_R, RESP_T0, RESP_T1, assert_same, blend_numpy, check_planes_lambda,
-                                    light_instance, planes_case, response_numpy, same_bits, sequence_transforms, temporal_response_ref)
-from temporal_util import MISS, temporal_ref
+from temporal_response_util import (P_SPLIT, P_TRIS, PH, PW, RESP_EPS, RESP_NMIN, RESP_R, RESP_T0, RESP_T1, blend_numpy, check_planes_lambda, light_instance,
+                                    planes_case, response_numpy, sequence_transforms, temporal_response_ref)
+from temporal_util import MISS, assert_same, same_bits, temporal_ref
 from test_device_bvh import _option_json
 
 f32 = np.float32
