@@ -266,6 +266,8 @@ def lib():
             "hjr_temporal_accumulate_moments_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_temporal_accumulate_response": [C.c_void_p] * 9,
             "hjr_temporal_accumulate_response_device": [C.c_void_p] * 10,
+            "hjr_temporal_prior": [C.c_void_p] * 4,
+            "hjr_temporal_prior_device": [C.c_void_p] * 5,
             "hjr_temporal_reset": [C.c_void_p],
             "hjr_upscale_guided": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
             "hjr_upscale_guided_device": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -640,7 +642,7 @@ class Device:
         return out
 
     @staticmethod
-    def _temporal_frame(d, keep):
+    def _temporal_frame(d, keep, images=True):
         """dict -> TemporalFrame: camera (Camera or dict), transforms / inv_transforms [n, 12], gbuffer (GBUFFER_DTYPE [h, w]), color
         [h, w, 4], variance [h, w] and, for the previous frame, history [h, w]; optional coverage (non-zero: the G-buffer's pad words are
         coverage counts)."""
@@ -648,9 +650,9 @@ class Device:
         h, w = g.shape
         m = np.ascontiguousarray(d["transforms"], dtype=np.float32).reshape(-1, 12)
         inv = np.ascontiguousarray(d["inv_transforms"], dtype=np.float32).reshape(-1, 12)
-        col = np.ascontiguousarray(d["color"], dtype=np.float32)
-        var = np.ascontiguousarray(d["variance"], dtype=np.float32)
-        if m.shape != inv.shape or col.shape != (h, w, 4) or var.shape != (h, w):
+        col = np.ascontiguousarray(d["color"], dtype=np.float32) if images else None
+        var = np.ascontiguousarray(d["variance"], dtype=np.float32) if images else None
+        if m.shape != inv.shape or (images and (col.shape != (h, w, 4) or var.shape != (h, w))):
             raise ValueError("temporal frame: array shapes do not agree")
         f = TemporalFrame()
         f.width, f.height, f.n_instances = w, h, m.shape[0]
@@ -658,7 +660,7 @@ class Device:
         f.camera = cam if isinstance(cam, Camera) else make_params(w, h, 1, cam).camera
         arrs = [m, inv, g, col, var]
         f.transforms12, f.inv_transforms12 = m.ctypes.data if m.size else None, inv.ctypes.data if inv.size else None
-        f.gbuffer, f.color, f.variance = g.ctypes.data, col.ctypes.data, var.ctypes.data
+        f.gbuffer, f.color, f.variance = g.ctypes.data, col.ctypes.data if images else None, var.ctypes.data if images else None
         f.coverage = int(d.get("coverage") or 0)
         if d.get("history") is not None:
             hist = np.ascontiguousarray(d["history"], dtype=np.float32)
@@ -703,6 +705,17 @@ class Device:
                                              history.ctypes.data), "hjr_temporal_accumulate")
         return color, variance, history
 
+    def temporal_prior(self, prev, cur):
+        """hjr_temporal_prior on dicts of arrays as temporal_accumulate takes them (prev None = no previous frame); cur needs camera,
+        transforms, inv_transforms, gbuffer and optionally coverage only: its colour and variance are not read.  Returns the prior
+        [h, w, 4]: (lp, vp, al, 0) per pixel, (0, 0, 1, 0) where the history contributes nothing (adaptive sampling's rule 11)."""
+        keep = []
+        fc = self._temporal_frame(cur, keep, images=False)
+        fp = None if prev is None else self._temporal_frame(prev, keep)
+        prior = np.zeros((fc.height, fc.width, 4), dtype=np.float32)
+        _check(lib().hjr_temporal_prior(self._h, None if fp is None else C.byref(fp), C.byref(fc), prior.ctypes.data), "hjr_temporal_prior")
+        return prior
+
     def upscale_guided(self, color_lo, gbuffer_lo, cam, gbuffer_hi):
         """hjr_upscale_guided on host arrays: color_lo float32 [h, w, 4] (the filtered half-size image), gbuffer_lo GBUFFER_DTYPE [h, w],
         gbuffer_hi GBUFFER_DTYPE [oh, ow] with ow // 2 == w and oh // 2 == h (Device.gbuffer at both sizes from `cam`, a Camera or dict).
@@ -743,7 +756,10 @@ class Device:
         """hjr_set_option: tuning / test option of this context (-1 restores the default); layout options act at the next set_transforms.
         "firefly_clamp" (kappa, 0..64) clamps whole-frame renders; with "firefly_clamp_passes" 1 next to it sample passes and adaptive
         frames are accepted and clamped too (the colour chunk sums of the whole progressive frame are kept; include/henjou_hip.h "Firefly
-        clamp on sample passes").  Setting "firefly_clamp_passes", or "firefly_clamp" while it is 1, ends an unfinished progressive frame."""
+        clamp on sample passes").  Setting "firefly_clamp_passes", or "firefly_clamp" while it is 1, ends an unfinished progressive frame.
+        "adaptive_temporal" 1 lets the sample passes of render_denoised on an adaptive frame with "denoise_temporal" on stop a tile on the
+        error of the accumulated pixel (rule 11) and commits the history when the last tile stops; setting it ends an unfinished
+        progressive frame too."""
         _check(lib().hjr_set_option(self._h, key.encode(), int(value)), "hjr_set_option")
 
     def get_option(self, key):

@@ -62,6 +62,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     hjr::Job job;
     std::string refusal;
     if (!hjr::job_check(opt, job, refusal)) { fprintf(stderr, "henjou_cli: %s\n", refusal.c_str()); return 1; }
+    if (world > 1 && hjr::multi_gpu_refusal(opt, refusal)) { fprintf(stderr, "henjou_cli: %s\n", refusal.c_str()); return 1; }
     const bool denoise = job.denoise, with_var = job.with_var;
     const uint32_t W = job.w, H = job.h, OW = job.out_w, OH = job.out_h; // the render size; the PNG's size
     hjr_scene* scene = nullptr;
@@ -183,12 +184,15 @@ int main(int argc, char** argv)
     }
     // a rank process of a multi-GPU render (world 1: the same code path on one GPU, no id hand-over)
     if (rank >= 0) return (world >= 1 && rank < world && (world == 1 || id_fd >= 0)) ? run_rank(path, rank, world, id_fd) : 2;
-    if (devices == 0) { // the JSON decides (host-only parse: no GPU is touched here)
-        hjr_render_option opt;
-        HJR_INIT(opt);
-        if (hjr_load_render_option(path, &opt) != HJR_OK) { fprintf(stderr, "henjou_cli: error: %s\n", hjr_last_error()); return 1; }
+    hjr_render_option opt;
+    HJR_INIT(opt);
+    const bool parsed = hjr_load_render_option(path, &opt) == HJR_OK; // (host-only parse: no GPU is touched here)
+    if (devices == 0) { // the JSON decides
+        if (!parsed) { fprintf(stderr, "henjou_cli: error: %s\n", hjr_last_error()); return 1; }
         devices = (int)opt.devices;
     }
+    std::string refusal; // what no world of several ranks renders: said once, before a rank is started (a file that does not parse is the ranks' to report)
+    if (devices > 1 && parsed && hjr::multi_gpu_refusal(opt, refusal)) { fprintf(stderr, "henjou_cli: %s\n", refusal.c_str()); return 1; }
     if (devices <= 1) {
         int rc = hjr_render_file(path, device);
         if (rc != HJR_OK) { fprintf(stderr, "henjou_cli: error %d: %s\n", rc, hjr_last_error()); return 1; }

@@ -334,6 +334,54 @@ __global__ void __launch_bounds__(BLOCK) hjr_firefly_kernel(const KParams P, con
     if ((threadIdx.x & 63u) == 0u && n_scaled) atomicAdd(n_clamped, (unsigned long long)n_scaled);
 }
 
+// ---- adaptive sampling that counts the temporal history (option "adaptive_temporal", DESIGN.md §4 rule 11; stated in include/henjou_hip.h).
+// Runs BEHIND hjr_finalize_kernel<true, true, VAR> on a deciding pass of an adaptive frame that has a prior (hjr_temporal_prior_kernel,
+// csrc/hjr_temporal.hip.h: (lp, vp, al, 0) per pixel in frame layout); the finalize kernel ran with ad_decide 0, so every tile that was
+// active stands as active (ad_state 0, counted), its raw statistic (S1, S2) is in P.stat and every AOV is written.  One wave per owned tile
+// (n_slots and the grid stride are multiples of 64); a stopped tile's wave leaves at once.  Per pixel of an active tile, n = sample_end,
+// g = chunk_spp, m = n / g, fp32 as written (correctly rounded divide and sqrt, no contraction: this translation unit's flags):
+//     e6 = sqrtf(fmaxf(m S2 - S1 S1, 0) / (m - 1)) / (S1 + HJR_ADAPTIVE_EPS n)                       (rule 6's e: the expression of hjr_finalize_kernel)
+//     if al < 1:   lc = S1 / n;   vc = hjr_variance_of_mean(S1, S2, m, g, n);   om = 1 - al;   va = (om om) vp + (al al) vc;
+//                  la = lp + (lc - lp) al;   ea = sqrtf(va) / (fmaxf(la, 0) + HJR_ADAPTIVE_EPS);   e = fminf(ea, e6)     (a NaN ea gives e6)
+//     else         e = e6
+// Out-of-image lanes of an edge tile carry e = 0 into rule 6's xor butterfly; the tile stops iff the sum <= noise_threshold x 64, and lane 0
+// then writes ad_state = n and takes the tile out of the active count.  e <= e6 per pixel and float addition is monotone, so a tile that
+// rule 6 stops on this statistic stops here too.  The prior is an argument of its own: KParams does not grow.
+__global__ void __launch_bounds__(256) hjr_adaptive_temporal_kernel(const KParams P, const float4* __restrict__ prior)
+{
+    const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
+    const uint32_t n = P.sample_end, g = P.chunk_spp, m = n / g;
+    const float nf = (float)n, mf = (float)m;
+    for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
+        if (P.ad_state[sl >> 6] != 0u) continue; // (wave-uniform) stopped before this pass
+        uint32_t x, y;
+        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y);
+        float e = 0.0f;
+        if (inside) {
+            const float2 s = P.stat[sl];
+            const float q = fmaxf(mf * s.y - s.x * s.x, 0.0f);
+            const float e6 = sqrtf(q / (mf - 1.0f)) / (s.x + HJR_ADAPTIVE_EPS * nf);
+            const float4 pr = prior[(size_t)y * P.width + x]; // (lp, vp, al, 0)
+            e = e6;
+            if (pr.z < 1.0f) {
+                const float lc = s.x / nf;
+                const float vc = hjr_variance_of_mean(s.x, s.y, m, g, n);
+                const float om = 1.0f - pr.z;
+                const float va = (om * om) * pr.y + (pr.z * pr.z) * vc;
+                const float la = pr.x + (lc - pr.x) * pr.z;
+                const float ea = sqrtf(va) / (fmaxf(la, 0.0f) + HJR_ADAPTIVE_EPS);
+                e = fminf(ea, e6);
+            }
+        }
+        float v = e;
+        for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
+        if (v <= P.ad_threshold * 64.0f && (threadIdx.x & 63u) == 0u) {
+            P.ad_state[sl >> 6] = n;
+            atomicSub(&P.ad_state[P.n_owned_tiles], 1u); // (the finalize kernel counted the tile as active)
+        }
+    }
+}
+
 // The launch's tile list without the stopped tiles: a STABLE compaction of ad_src (the cost order hjr_order_tiles_kernel /
 // hjr_cost_scatter_kernel just produced, or the plain round-robin order when there is none), so the expensive-first order survives and the
 // result is the same for the same input.  At most 129 600 tiles (4K): one workgroup walks the list in steps of 1024 with a ballot per wave

@@ -127,6 +127,7 @@ extern "C" int hjr_set_option(hjr_ctx* c, const char* key, int value)
     // rule 10 keeps chunk sums from a frame's first pass on: an unfinished progressive frame cannot change its rule half way (as hjr_set_adaptive).
     // "firefly_clamp" alone with "firefly_clamp_passes" off keeps what it always did: the next pass is refused by check_pass
     if (i == hjr::OPT_FIREFLY_CLAMP_PASSES || (i == hjr::OPT_FIREFLY_CLAMP && c->opt.get(hjr::OPT_FIREFLY_CLAMP_PASSES, 0) == 1)) { c->pass.active = false; c->ad.frame = false; }
+    if (i == hjr::OPT_ADAPTIVE_TEMPORAL) { c->pass.active = false; c->ad.frame = false; c->tmp.have_prior = false; } // rule 11: an unfinished progressive frame cannot change its rule half way (as hjr_set_adaptive); the history stays
     if (i == hjr::OPT_DENOISE_TEMPORAL || i == hjr::OPT_DENOISE_VARIANCE_SPATIAL || i == hjr::OPT_DENOISE_TEMPORAL_COVERAGE || i == hjr::OPT_DENOISE_TEMPORAL_MOMENTS || i == hjr::OPT_DENOISE_TEMPORAL_RESPONSE) c->tmp.have_prev = false; // setting any of these options drops the history
     if (i == hjr::OPT_HOST_THREADS) hjr::set_host_threads(value);
     return HJR_OK;
@@ -555,7 +556,8 @@ static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, Pass
     if (r.begin == 0) return HJR_OK; // starts a progressive frame (replacing an unfinished one)
     const hjr_ctx::PassSession& s = c->pass;
     std::string bad;
-    if (!s.active) bad = "no progressive frame is open (its first pass starts at sample 0)";
+    if (!s.active) bad = s.committed ? "the frame ended when its last active tile stopped and option \"adaptive_temporal\" committed its history (the next pass starts a new frame at sample 0)"
+                                     : "no progressive frame is open (its first pass starts at sample 0)";
     else if (r.begin != s.next) bad = "sample_begin " + std::to_string(r.begin) + " does not continue the previous pass, which ended at " + std::to_string(s.next);
     else if (p->width != s.p.width || p->height != s.p.height) bad = "width / height differ from the frame's first pass";
     else if (p->spp != s.p.spp) bad = "spp differs from the frame's first pass";
@@ -575,6 +577,7 @@ static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, Pass
 static void end_pass(hjr_ctx* c, const hjr_params* p, const PassRange& r)
 {
     hjr_ctx::PassSession& s = c->pass;
+    s.committed = false;
     if (!r.pass || r.end == p->spp) { s.active = false; return; }
     if (r.begin == 0) { s.p = *p; s.aovs = r.aovs; s.gen = c->frame_gen; }
     s.active = true;
@@ -923,9 +926,20 @@ static int firefly_clamp_pass(hjr_ctx* c, const FrameGeom& g, const KParams& kp,
     return firefly_launch(c, g, kf, g.pr.end / g.chunk_spp, true, adaptive, st);
 }
 
+// Option "adaptive_temporal" (DESIGN.md §4 rule 11), behind finalize_chunks on a deciding pass of an adaptive frame with a prior: one wave per
+// owned tile, the finalize dispatch's shape.  finalize_chunks ran with ad_decide 0 and left the statistic in kp.stat.
+static int adaptive_temporal_launch(hjr_ctx* c, const FrameGeom& g, const KParams& kp, const void* d_prior, hipStream_t st)
+{
+    const size_t n_slots = (size_t)g.owned * 64u;
+    const unsigned fb = (unsigned)std::max<size_t>(1, std::min<size_t>((n_slots + 255) / 256, (size_t)c->n_cus * 8));
+    hipLaunchKernelGGL(hjr_adaptive_temporal_kernel, dim3(fb), dim3(256), 0, st, kp, (const float4*)d_prior);
+    return launched();
+}
+
 // pr: check_pass of this call, made before the caller enqueued anything
 // d_var: the variance AOV (one float per pixel) or null
-static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st)
+// d_prior: option "adaptive_temporal" in effect and the frame has a prior (hjr_render_denoised): rule 11 takes an adaptive pass's decisions
+static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st, const void* d_prior = nullptr)
 {
     FrameGeom g;
     KParams kp;
@@ -946,11 +960,14 @@ static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, voi
     }
     // rule 10: on a deciding pass of >= 4 full chunks the decision is hjr_firefly_kernel's, from the clamped sums
     const bool decide = adaptive && kp.ad_decide != 0u, ff_decides = decide && firefly_pass_acts(c, g);
-    if (ff_decides) kp.ad_decide = 0u;
-    if ((rc = finalize_chunks(c, g, kp, adaptive, ff_decides, (float*)d_var, st)) != HJR_OK) return rc;
+    // rule 11: with a prior the decision is hjr_adaptive_temporal_kernel's (the caller refused the pair with rule 10)
+    const bool at_decides = decide && !ff_decides && d_prior != nullptr;
+    if (ff_decides || at_decides) kp.ad_decide = 0u;
+    if ((rc = finalize_chunks(c, g, kp, adaptive, ff_decides || at_decides, (float*)d_var, st)) != HJR_OK) return rc;
     if ((rc = firefly_clamp(c, p, g, kp, st)) != HJR_OK) return rc;
     if ((rc = firefly_clamp_pass(c, g, kp, adaptive, ff_decides, st)) != HJR_OK) return rc;
-    if (ff_decides && (rc = adaptive_count(c, g, st)) != HJR_OK) return rc;
+    if (at_decides && (rc = adaptive_temporal_launch(c, g, kp, d_prior, st)) != HJR_OK) return rc;
+    if ((ff_decides || at_decides) && (rc = adaptive_count(c, g, st)) != HJR_OK) return rc;
     HIPCHK(hipEventRecord(c->ev1, st));
     c->event_pending = true;
     if (pr.pass && c->opt.get(hjr::OPT_VERBOSE, 0))
@@ -1345,13 +1362,15 @@ static int temporal_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalS
     return launched();
 }
 // argument checks of hjr_temporal_accumulate[_device]: the sized structs, sizes that agree, every pointer the kernel reads
-static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, hjr_temporal_frame& prev, hjr_temporal_frame& cur, bool& have_prev, bool moments = false, const void* prev_moments = nullptr)
+// `prior`: hjr_temporal_prior[_device], which reads no colour or variance of the current frame: those two may be NULL
+static int temporal_take(const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, hjr_temporal_frame& prev, hjr_temporal_frame& cur, bool& have_prev, bool moments = false, const void* prev_moments = nullptr,
+                         bool prior = false)
 {
     if (!hjr::abi_take(cur_user, cur, "hjr_temporal_accumulate")) return HJR_ERR_ARG;
     have_prev = prev_user != nullptr;
     if (have_prev && !hjr::abi_take(prev_user, prev, "hjr_temporal_accumulate")) return HJR_ERR_ARG;
     if (cur.width == 0 || cur.height == 0 || cur.width > 16384 || cur.height > 16384) { set_error("hjr_temporal_accumulate: bad image size"); return HJR_ERR_ARG; }
-    if (!cur.gbuffer || !cur.color || !cur.variance || (cur.n_instances && (!cur.transforms12 || !cur.inv_transforms12))) { set_error("hjr_temporal_accumulate: null pointer in the current frame"); return HJR_ERR_ARG; }
+    if (!cur.gbuffer || (!prior && (!cur.color || !cur.variance)) || (cur.n_instances && (!cur.transforms12 || !cur.inv_transforms12))) { set_error("hjr_temporal_accumulate: null pointer in the current frame"); return HJR_ERR_ARG; }
     if (have_prev) {
         if (prev.width != cur.width || prev.height != cur.height || prev.n_instances != cur.n_instances) { set_error("hjr_temporal_accumulate: width, height and n_instances of the two frames must agree"); return HJR_ERR_ARG; }
         if (!prev.gbuffer || !prev.color || !prev.variance || !prev.history || (prev.n_instances && (!prev.transforms12 || !prev.inv_transforms12))) { set_error("hjr_temporal_accumulate: null pointer in the previous frame"); return HJR_ERR_ARG; }
@@ -1458,6 +1477,77 @@ extern "C" int hjr_temporal_reset(hjr_ctx* c)
     return HJR_OK;
 }
 
+// ---- the prior of adaptive sampling's rule 11 (csrc/hjr_temporal.hip.h section PRIOR; include/henjou_hip.h: hjr_temporal_prior)
+// The kernel on device memory; prev == nullptr: no previous frame, every pixel (0, 0, 1, 0).  A side's coverage chooses rules 2' / 3'.
+static int temporal_prior_launch(hjr_ctx* c, const TemporalSide* prev, const TemporalSide& cur, uint32_t w, uint32_t h, uint32_t n_inst, void* d_prior, hipStream_t st)
+{
+    TemporalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cur = cur;
+    if (prev) { a.prev = *prev; a.have_prev = 1u; }
+    a.width = w; a.height = h; a.n_instances = n_inst;
+    a.n_tris = c->have_scene ? c->scene.n_triangles : 0xffffffffu; // as temporal_launch
+    if (a.prev.coverage || a.cur.coverage) hipLaunchKernelGGL(hjr_temporal_prior_kernel<true>, image_grid(w, h), dim3(256), 0, st, a, (float4*)d_prior);
+    else hipLaunchKernelGGL(hjr_temporal_prior_kernel<false>, image_grid(w, h), dim3(256), 0, st, a, (float4*)d_prior);
+    return launched();
+}
+extern "C" int hjr_temporal_prior_device(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, void* d_prior, void* hip_stream)
+{
+    if (!c || !d_prior) { set_error("hjr_temporal_prior: null argument"); return HJR_ERR_ARG; }
+    hjr_temporal_frame prev, cur;
+    bool have_prev;
+    if (const int rc = temporal_take(prev_user, cur_user, prev, cur, have_prev, false, nullptr, true)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const TemporalSide ps = have_prev ? temporal_side(prev, nullptr) : TemporalSide(), cs = temporal_side(cur, nullptr);
+    return temporal_prior_launch(c, have_prev ? &ps : nullptr, cs, cur.width, cur.height, cur.n_instances, d_prior, stream_of(c, hip_stream));
+}
+extern "C" int hjr_temporal_prior(hjr_ctx* c, const hjr_temporal_frame* prev_user, const hjr_temporal_frame* cur_user, float* out_prior)
+{
+    if (!c || !out_prior) { set_error("hjr_temporal_prior: null argument"); return HJR_ERR_ARG; }
+    hjr_temporal_frame f[2]; // [0] prev, [1] cur
+    bool have_prev;
+    if (const int rc = temporal_take(prev_user, cur_user, f[0], f[1], have_prev, false, nullptr, true)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t npx = (size_t)f[1].width * f[1].height, nx = (size_t)f[1].n_instances * 48;
+    // one temporary buffer, 16-byte images first: the prior, per side the G-buffer (prev: and its colour), then the floats: per side M, M^-1 (prev: variance, history)
+    hjr_temporal_frame d[2];
+    char* d_prior = nullptr;
+    const auto layout = [&](uintptr_t base) {
+        size_t at = 0;
+        const auto take = [&](size_t bytes) { char* const q = (char*)(base + at); at += bytes; return q; };
+        d_prior = take(npx * 16);
+        for (int i = have_prev ? 0 : 1; i < 2; i++) {
+            d[i] = f[i];
+            d[i].gbuffer = (const hjr_gbuffer_px*)take(npx * sizeof(hjr_gbuffer_px));
+            d[i].color = i == 0 ? (const float*)take(npx * 16) : nullptr;
+        }
+        for (int i = have_prev ? 0 : 1; i < 2; i++) {
+            d[i].transforms12 = (const float*)take(nx); d[i].inv_transforms12 = (const float*)take(nx);
+            d[i].variance = i == 0 ? (const float*)take(npx * 4) : nullptr;
+            d[i].history = i == 0 ? (const float*)take(npx * 4) : nullptr;
+        }
+        return at;
+    };
+    static_assert(sizeof(hjr_gbuffer_px) % 16 == 0, "the records keep the images behind them 16-byte aligned");
+    HostStage hs(c);
+    if (!hs.buf.reserve(layout(0))) { set_error("hjr_temporal_prior: device allocation failed"); return HJR_ERR_DEVICE; }
+    layout((uintptr_t)hs.buf.p);
+    for (int i = have_prev ? 0 : 1; i < 2; i++) {
+        hs.up((void*)d[i].transforms12, f[i].transforms12, nx);
+        hs.up((void*)d[i].inv_transforms12, f[i].inv_transforms12, nx);
+        hs.up((void*)d[i].gbuffer, f[i].gbuffer, npx * sizeof(hjr_gbuffer_px));
+        if (i == 0) {
+            hs.up((void*)d[i].color, f[i].color, npx * 16);
+            hs.up((void*)d[i].variance, f[i].variance, npx * 4);
+            hs.up((void*)d[i].history, f[i].history, npx * 4);
+        }
+    }
+    const TemporalSide ps = have_prev ? temporal_side(d[0], nullptr) : TemporalSide(), cs = temporal_side(d[1], nullptr);
+    if (hs.ok()) hs.rc = temporal_prior_launch(c, have_prev ? &ps : nullptr, cs, f[1].width, f[1].height, f[1].n_instances, d_prior, c->stream);
+    hs.down(out_prior, d_prior, npx * 16);
+    return hs.finish("hjr_temporal_prior");
+}
+
 // Option "denoise_temporal", between the render (or the assembly of gathered shards) and the filter, all on `st`: G-buffer of this frame,
 // a device copy of the transforms the current frame data was built from (`built`: what hjr_commit_transforms made current, so a
 // frame loop that already prepares the next frame on another thread cannot be seen here), accumulation against the previous slot.
@@ -1472,38 +1562,80 @@ static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
         !s.xf.reserve(2 * nx + 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) && !s.moments.reserve(npx * 8)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     if (c->opt.get(hjr::OPT_DENOISE_TEMPORAL_RESPONSE, 0) && !t.response.reserve(npx * 4)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
+    if (c->opt.get(hjr::OPT_ADAPTIVE_TEMPORAL, 0) && !t.prior.reserve(npx * 16)) { set_error("hjr_render_denoised: temporal history allocation failed"); return HJR_ERR_DEVICE; }
     return HJR_OK;
 }
-static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
+// the history belongs to frames of this size, mode and instance count: anything else restarts
+static void temporal_match(hjr_ctx* c, const hjr_params* p, int render_mode, uint32_t n_inst)
 {
     hjr_ctx::Temporal& t = c->tmp;
-    const uint32_t n_inst = (uint32_t)(c->built.m.size() / 12);
     if (t.have_prev && (t.width != p->width || t.height != p->height || t.mode != render_mode || t.n_instances != n_inst)) t.have_prev = false;
+}
+// the current slot's G-buffer, transforms and camera of the frame p describes
+static int temporal_trace(hjr_ctx* c, const hjr_params* p, uint32_t n_inst, uint32_t cov, hipStream_t st)
+{
+    hjr_ctx::Temporal::Slot& now = c->tmp.slot[c->tmp.cur];
     const size_t nx = (size_t)n_inst * 48;
-    if (const int rc = temporal_reserve(c, p)) return rc;
-    hjr_ctx::Temporal::Slot &now = t.slot[t.cur], &before = t.slot[t.cur ^ 1];
-    const uint32_t cov = (uint32_t)c->opt.get(hjr::OPT_DENOISE_TEMPORAL_COVERAGE, 0); // option "denoise_temporal_coverage": the coverage pass and rules 2' / 3' (setting it drops the history, so both slots agree)
     if (const int rc = gbuffer_device_impl(c, p, now.gbuf.p, st, cov)) return rc;
     if (nx) {
         HIPCHK(hipMemcpyAsync(now.xf.p, c->built.m.data(), nx, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync((char*)now.xf.p + nx, c->built.inv.data(), nx, hipMemcpyHostToDevice, st));
     }
     now.cam = p->camera;
+    return HJR_OK;
+}
+// a slot as a frame of device pointers
+static hjr_temporal_frame temporal_slot_frame(const hjr_ctx::Temporal::Slot& s, size_t nx, uint32_t cov)
+{
+    hjr_temporal_frame f = {};
+    f.camera = s.cam; f.transforms12 = (const float*)s.xf.p; f.inv_transforms12 = (const float*)((const char*)s.xf.p + nx); f.gbuffer = (const hjr_gbuffer_px*)s.gbuf.p;
+    f.color = (const float*)s.color.p; f.variance = (const float*)s.variance.p; f.history = (const float*)s.history.p; f.coverage = cov;
+    return f;
+}
+// Option "adaptive_temporal", ahead of the render of a frame's first sample pass (the buffers stand: post_plan): the frame's G-buffer into the
+// current slot and the prior against the committed history, for every pass of the frame.  Without a history there is no prior, and the frame
+// is rule 6's.
+static int temporal_prior_stage(hjr_ctx* c, const hjr_params* p, int render_mode, hipStream_t st)
+{
+    hjr_ctx::Temporal& t = c->tmp;
+    const uint32_t n_inst = (uint32_t)(c->built.m.size() / 12);
+    const size_t nx = (size_t)n_inst * 48;
+    temporal_match(c, p, render_mode, n_inst);
+    t.have_prior = false;
+    if (!t.have_prev) return HJR_OK;
+    const uint32_t cov = (uint32_t)c->opt.get(hjr::OPT_DENOISE_TEMPORAL_COVERAGE, 0);
+    if (const int rc = temporal_trace(c, p, n_inst, cov, st)) return rc;
+    const TemporalSide ps = temporal_side(temporal_slot_frame(t.slot[t.cur ^ 1], nx, cov), nullptr), cs = temporal_side(temporal_slot_frame(t.slot[t.cur], nx, cov), nullptr);
+    if (const int rc = temporal_prior_launch(c, &ps, cs, p->width, p->height, n_inst, t.prior.p, st)) return rc;
+    t.have_prior = true; t.prior_cur = t.cur;
+    return HJR_OK;
+}
+// `commit` of temporal_stage: the frame in the current slot becomes the history, the slots rotate
+static void temporal_commit(hjr_ctx* c, const hjr_params* p, int render_mode, uint32_t n_inst)
+{
+    hjr_ctx::Temporal& t = c->tmp;
+    t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur ^= 1;
+}
+static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
+{
+    hjr_ctx::Temporal& t = c->tmp;
+    const uint32_t n_inst = (uint32_t)(c->built.m.size() / 12);
+    temporal_match(c, p, render_mode, n_inst);
+    const size_t nx = (size_t)n_inst * 48;
+    if (const int rc = temporal_reserve(c, p)) return rc;
+    hjr_ctx::Temporal::Slot &now = t.slot[t.cur], &before = t.slot[t.cur ^ 1];
+    const uint32_t cov = (uint32_t)c->opt.get(hjr::OPT_DENOISE_TEMPORAL_COVERAGE, 0); // option "denoise_temporal_coverage": the coverage pass and rules 2' / 3' (setting it drops the history, so both slots agree)
+    if (const int rc = temporal_trace(c, p, n_inst, cov, st)) return rc;
     const bool mom = c->opt.get(hjr::OPT_DENOISE_TEMPORAL_MOMENTS, 0) != 0; // option "denoise_temporal_moments": both slots carry (m1, m2) (setting it drops the history, so the previous slot has them)
     const bool resp = c->opt.get(hjr::OPT_DENOISE_TEMPORAL_RESPONSE, 0) != 0; // option "denoise_temporal_response": the windowed change test; its lambda image is written and not read again
-    const auto frame_of = [&](const hjr_ctx::Temporal::Slot& s) { // a slot as a frame of device pointers
-        hjr_temporal_frame f = {};
-        f.camera = s.cam; f.transforms12 = (const float*)s.xf.p; f.inv_transforms12 = (const float*)((const char*)s.xf.p + nx); f.gbuffer = (const hjr_gbuffer_px*)s.gbuf.p;
-        f.color = (const float*)s.color.p; f.variance = (const float*)s.variance.p; f.history = (const float*)s.history.p; f.coverage = cov;
-        return f;
-    };
+    const auto frame_of = [&](const hjr_ctx::Temporal::Slot& s) { return temporal_slot_frame(s, nx, cov); };
     hjr_temporal_frame cur = frame_of(now);
     cur.color = (const float*)d_color; cur.variance = (const float*)d_var; cur.history = nullptr; // what was rendered: the slot's own images are the outputs
     const TemporalSide ps = temporal_side(frame_of(before), mom ? before.moments.p : nullptr), cs = temporal_side(cur, nullptr);
     const TemporalOut out = { (float4*)now.color.p, (float*)now.variance.p, (float*)now.history.p, mom ? (float2*)now.moments.p : nullptr, resp ? (float*)t.response.p : nullptr };
     if (const int rc = temporal_launch(c, t.have_prev ? &ps : nullptr, cs, p->width, p->height, n_inst, out, st)) return rc;
     d_color = now.color.p; d_var = now.variance.p;
-    if (commit) { t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur ^= 1; }
+    if (commit) temporal_commit(c, p, render_mode, n_inst);
     return HJR_OK;
 }
 
@@ -1644,15 +1776,33 @@ extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int ren
     const PostPlan pl = post_options(c, render_mode);
     PassRange pr; // a sample pass: the running mean is filtered (a denoised preview; the last pass gives the one-shot call's image)
     if (const int rc = post_plan(c, p, pl, out_w, out_h, "hjr_render_denoised", &pr)) return rc;
+    // Option "adaptive_temporal" is in effect on a sample pass of an adaptive frame in a Denoise mode with "denoise_temporal" on (DESIGN.md §4
+    // rule 11): the frame's first pass computes the prior, rule 11 decides wherever there is one, and the pass that leaves no active tile
+    // commits the history as the pass that ends at spp does.  Everywhere else nothing below differs from the call without the option.
+    const bool at = pl.temporal && pr.pass && c->ad.threshold > 0.0f && c->opt.get(hjr::OPT_ADAPTIVE_TEMPORAL, 0) != 0;
+    if (at && firefly_keeps_chunks(c)) {
+        set_error("hjr_render_denoised: option \"adaptive_temporal\" cannot be combined with options \"firefly_clamp\" > 0 and \"firefly_clamp_passes\" 1: rule 10 and rule 11 would both take the stop decision");
+        return HJR_ERR_ARG;
+    }
     if (!c->d_dn_out.reserve(out_bytes)) { set_error("hjr_render_denoised: allocation failed"); return HJR_ERR_DEVICE; }
     if (pl.with_var) HIPCHK(hipMemsetAsync(c->d_variance.p, 0, in_bytes / 4, c->stream));
     HIPCHK(hipMemsetAsync(c->d_color.p, 0, in_bytes, c->stream));
     if (pl.guides) { HIPCHK(hipMemsetAsync(c->d_albedo.p, 0, in_bytes, c->stream)); HIPCHK(hipMemsetAsync(c->d_normal.p, 0, in_bytes, c->stream)); }
     HostStage hs(c);
-    hs.rc = render_impl(c, p, pr, c->d_color.p, pl.guides ? c->d_albedo.p : nullptr, pl.guides ? c->d_normal.p : nullptr, pl.with_var ? c->d_variance.p : nullptr, c->stream);
-    if (hs.ok()) hs.rc = denoise_post_stage(c, p, pl, !pr.pass || pr.end == p->spp, c->d_dn_out.p, out_w, out_h, c->stream);
+    if (at && pr.begin == 0) hs.rc = temporal_prior_stage(c, p, render_mode, c->stream);
+    // a continuing pass reuses its frame's prior while the history it was gathered from stands
+    const void* const d_prior = at && c->tmp.have_prior && c->tmp.have_prev && c->tmp.prior_cur == c->tmp.cur ? c->tmp.prior.p : nullptr;
+    const bool last = !pr.pass || pr.end == p->spp;
+    if (hs.ok()) hs.rc = render_impl(c, p, pr, c->d_color.p, pl.guides ? c->d_albedo.p : nullptr, pl.guides ? c->d_normal.p : nullptr, pl.with_var ? c->d_variance.p : nullptr, c->stream, d_prior);
+    if (hs.ok()) hs.rc = denoise_post_stage(c, p, pl, last, c->d_dn_out.p, out_w, out_h, c->stream);
     hs.down(out, c->d_dn_out.p, out_bytes);
-    return hs.finish("hjr_render_denoised");
+    const int rc = hs.finish("hjr_render_denoised");
+    // (the stream is drained: the count the pass read back is at hand)  No tile is left: the frame is over, its accumulation is the history
+    if (rc == HJR_OK && at && !last && c->ad.frame && *c->ad.h_active == 0u) {
+        temporal_commit(c, p, render_mode, (uint32_t)(c->built.m.size() / 12));
+        c->pass.active = false; c->pass.committed = true;
+    }
+    return rc;
 }
 
 // ---- gathered shards of a multi-GPU frame (include/henjou_hip.h; kernel: csrc/hjr_aux.hip.h)

@@ -116,6 +116,7 @@ struct hjr_ctx {
         hjr_params p;
         uint32_t next = 0, aovs = 0;
         uint64_t gen = 0;
+        bool committed = false; // option "adaptive_temporal": the frame ended when its last tile stopped and its history was committed (cleared by the next pass that is enqueued)
     } pass;
     // Adaptive sampling (hjr_set_adaptive).  Nothing below is allocated or created before the first adaptive sample pass.
     struct Adaptive {
@@ -137,6 +138,9 @@ struct hjr_ctx {
             DevBuf moments;                            // option "denoise_temporal_moments": float2 (m1, m2) per pixel
         } slot[2];
         DevBuf response;                               // option "denoise_temporal_response": lambda per pixel of the last accumulation
+        DevBuf prior;                                  // option "adaptive_temporal": float4 (lp, vp, al, 0) per pixel of the frame being rendered in sample passes
+        bool have_prior = false;                       // ... written at that frame's first pass against slot[prior_cur ^ 1]
+        int prior_cur = 0;
         bool have_prev = false;
         int cur = 0;
         uint32_t width = 0, height = 0, n_instances = 0; // of the previous frame

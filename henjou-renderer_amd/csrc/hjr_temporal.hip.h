@@ -4,6 +4,7 @@
 //   hjr_temporal_kernel<COV, MOM>  one lane per pixel: reprojects the pixel's surface point into the previous frame, gathers the previous
 //                               frame's accumulated colour / variance / history length with four validated bilinear taps and blends.
 //   hjr_temporal_resp_kernel<COV, MOM>  the same with the windowed change test of section RESPONSE: a workgroup per 16 x 16 pixels.
+//   hjr_temporal_prior_kernel<COV>      the gather alone, ahead of the frame's render: section PRIOR.
 // Included by hjr_device.hip only: correctly rounded divide, no contraction, denormals on.  Specified to the bit, so that the test suite's
 // CPU checker (tests/native/temporal_ref.cpp) restates it independently.  fp32 throughout, every operation as written, left to right:
 //   dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z ;   cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x) ;
@@ -114,6 +115,20 @@
 //   its outputs are the bits of the kernel without this section: fmaxf(al, 0) = al exactly, and h is untouched.
 //   Luminances are only added, multiplied, divided and compared, and the window is addressed by integer pixel offsets inside the image:
 //   NaN, Inf and overflowing squares end in a lambda in [0, 1] and index nothing.
+//
+// PRIOR (hjr_temporal_prior_kernel<COV>: what the history will contribute to a pixel of the frame that is about to be rendered, before any
+//   of its colour exists; adaptive sampling's rule 11 reads it, csrc/hjr_aux.hip.h and DESIGN.md §4 rule 11.)  One float4 (lp, vp, al, 0) per
+//   pixel, [H][W].  Steps 1 to 4 of ACCUMULATION (with 2' / 3' when a side carries coverage) run unchanged up to c_prev, v_prev, h_prev and
+//   the taps' `unknown`; cur.color and cur.variance are never read (cur is the G-buffer, camera and transforms of the coming frame).
+//   A CARRIED pixel (one that did not RESTART) whose taps' `unknown` is false writes
+//     h = fminf(fmaxf(h_prev + 1, 1), 64);   al = fmaxf(1 / h, HJR_TEMPORAL_ALPHA);   lp = (c_prev.r + c_prev.g) + c_prev.b;   vp = v_prev
+//   (h and al are step 4's, so al is the factor the accumulation will blend this pixel's colour with).  Every other pixel (a RESTART of any
+//   kind, no previous frame, an unknown variance in a tap) writes (0, 0, 1, 0): al = 1 says "the current frame stands alone".
+//   Neither section RESPONSE's lambda nor the TEMPORAL MOMENTS enter: both need the current frame's colour, which does not exist yet.  With
+//   those options on the accumulation still applies them, and the prior is then the blend they would leave with lambda = 0 and the
+//   propagated variance: a limit of the prior, not of the accumulation.
+//   c_prev, v_prev and h_prev are only added, divided and compared: a NaN h_prev gives al = 1 through fmaxf, a NaN lp or vp is written as it is
+//   (rule 11 falls back to rule 6 on a NaN) and nothing indexes memory.
 #pragma once
 #include "hjr_aux.hip.h" // TileStack: the classifier's stacks
 
@@ -371,6 +386,23 @@ __global__ void __launch_bounds__(256) hjr_temporal_kernel(const TemporalArgs A)
     A.out.variance[pix] = var;
     A.out.history[pix] = hist;
     if constexpr (MOM) A.out.moments[pix] = make_float2(m1, m2);
+}
+
+// PRIOR (section PRIOR of the header comment): hjr_temporal_kernel's launch shape and gather, no colour of the current frame.  A.out and
+// the current side's colour and variance are not looked at; the prior is an argument of its own, so TemporalArgs stays what it was.
+template <bool COV>
+__global__ void __launch_bounds__(256) hjr_temporal_prior_kernel(const TemporalArgs A, float4* __restrict__ prior)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= A.width || y >= A.height) return;
+    const size_t pix = (size_t)y * A.width + x;
+    float4 out = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    hjr_temporal_gather<COV, false>(A, pix, [&](const TemporalPrev& P) {
+        if (P.unknown) return;
+        const float h = fminf(fmaxf(P.h + 1.0f, 1.0f), HJR_TEMPORAL_H_MAX);
+        out = make_float4((P.cx + P.cy) + P.cz, P.v, fmaxf(1.0f / h, HJR_TEMPORAL_ALPHA), 0.0f);
+    });
+    prior[pix] = out;
 }
 
 // RESPONSE (section RESPONSE of the header comment).  A 256-thread workgroup owns a 16 x 16 pixel tile and stages the tile and a halo of

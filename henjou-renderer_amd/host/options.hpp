@@ -13,7 +13,7 @@ enum Opt {
     OPT_FORCE_REBUILD, OPT_TOP_NODES, OPT_BVH_REFINE, OPT_DEVICE_BVH, OPT_DEVICE_BVH_OPT, OPT_DENOISE_VARIANCE, OPT_DENOISE_TEMPORAL, OPT_DEVICE_BVH_REFIT,
     OPT_DEVICE_BVH_REFIT_GROWTH, OPT_DEVICE_BVH_INSTANCES, OPT_DEVICE_BVH_GRAFT, OPT_FIREFLY_CLAMP, OPT_ITEM_CHUNKS, OPT_DENOISE_VARIANCE_SPATIAL,
     OPT_UPSCALE_GUIDED, OPT_DENOISE_TEMPORAL_COVERAGE, OPT_FIREFLY_CLAMP_PASSES, OPT_DENOISE_TEMPORAL_MOMENTS,
-    OPT_DENOISE_TEMPORAL_RESPONSE,
+    OPT_DENOISE_TEMPORAL_RESPONSE, OPT_ADAPTIVE_TEMPORAL,
     OPT_COUNT
 };
 struct OptDesc { const char* key; int lo, hi; };
@@ -57,6 +57,7 @@ inline const OptDesc* opt_table()
         { "firefly_clamp_passes", 0, 1 },        // "firefly_clamp" on: 1 accepts sample passes and adaptive frames, keeps the colour chunk sums of the whole progressive frame and clamps every pass of >= 4 full chunks; an adaptive frame stops on the clamped statistic (default 0: passes refused; no effect with "firefly_clamp" 0)
         { "denoise_temporal_moments", 0, 1 },    // "denoise_temporal" on: 1 keeps the luminance moments (m1, m2) per pixel in the history and takes the variance from them once a pixel's history length reaches HJR_TEMPORAL_MOMENTS_MIN (default 0; no effect otherwise)
         { "denoise_temporal_response", 0, 1 },   // "denoise_temporal" on: 1 accumulates with the windowed change test (hjr_temporal_accumulate_response_device): where the current frame's window mean of the luminance leaves the reprojected history's, the history gives way (default 0; no effect otherwise)
+        { "adaptive_temporal", 0, 1 },           // "denoise_temporal" on and hjr_set_adaptive: 1 lets the sample passes of hjr_render_denoised stop a tile on the error of the ACCUMULATED pixel (DESIGN.md §4 rule 11) and commits the history when the last tile stops (default 0; no effect otherwise; refused with an acting "firefly_clamp_passes")
     };
     return t;
 }

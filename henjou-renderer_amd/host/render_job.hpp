@@ -73,7 +73,9 @@ inline const std::vector<KeyRow>& key_table_since()
         // (in front of "denoise_temporal_moments", which tests/test_temporal_moments_host.py pins as the table's last row and latest parse
         // turn: a file with both keys bad reports this one; no file without this key is read differently)
         { "denoise_temporal_response", 14, &O::device_bvh_opt, ENC_BITS, 24, 1, READ_BOOL, nullptr, WHO_FILTER },
-        { "denoise_temporal_moments", 15, &O::device_bvh_opt, ENC_BITS, 15, 1, READ_BOOL, nullptr, WHO_FILTER },
+        // (likewise in front of the moments row, which moves up a turn to stay the latest; its turn number is pinned by nobody, its rank is)
+        { "adaptive_temporal", 15, &O::device_bvh_opt, ENC_BITS, 25, 1, READ_BOOL, "denoise_temporal", WHO_FILTER },
+        { "denoise_temporal_moments", 16, &O::device_bvh_opt, ENC_BITS, 15, 1, READ_BOOL, nullptr, WHO_FILTER },
     };
     return t;
 }
@@ -148,7 +150,7 @@ inline bool job_check(const hjr_render_option& o, Job& job, std::string& text)
     job.w = half ? job.out_w / 2u : job.out_w; job.h = half ? job.out_h / 2u : job.out_h;
     if (o.render_mode != HJR_MODE_DEFAULT && o.render_mode != HJR_MODE_DENOISE && o.render_mode != HJR_MODE_DENOISE_UPSCALE2X)
         text = "Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)";
-    else if (job.temporal && job.adaptive)
+    else if (job.temporal && job.adaptive && !key_get(o, key_row("adaptive_temporal"))) // with the key the pass that stops the last tile commits the history (rule 11)
         text = "\"denoise_temporal\" cannot be combined with \"noise_threshold\": an adaptive frame that stops early never reaches the sample pass that advances the history";
     else if (job.firefly && !key_get(o, key_row("firefly_clamp_passes")) && (o.passes > 1 || job.adaptive)) // every rank clamps its own pixels, so the rule is the same on both paths
         text = "\"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only";
@@ -156,6 +158,14 @@ inline bool job_check(const hjr_render_option& o, Job& job, std::string& text)
         text = "image too small for DenoiseUpScale2X";
     else return true;
     return false;
+}
+
+// what a job of several ranks (henjou_cli --devices N > 1) cannot do and one process can; true with the refusal in `text`
+inline bool multi_gpu_refusal(const hjr_render_option& o, std::string& text)
+{
+    if (!key_get(o, key_row("adaptive_temporal"))) return false;
+    text = "\"adaptive_temporal\" cannot be combined with \"devices\" > 1: every rank takes the stop decisions of its own shard without the temporal history, which only rank 0 keeps";
+    return true;
 }
 
 // sample-pass ends of a frame of spp samples in n passes ("Henjou_HIP": {"passes": n}): k * spp / n rounded down to the granule, the last one

@@ -146,7 +146,7 @@ typedef struct hjr_render_option {
     int32_t device_bvh_opt;      /* default 0; bits 0..7: key "device_bvh_opt", 0..3 treelet-restructuring rounds of that device build;
                                   * bit 8: key "device_bvh_instances"; bit 9: key "device_bvh_graft"; bit 10: key "denoise_variance_spatial";
                                   * bit 11: key "upscale_guided"; bits 12..14: key "denoise_temporal_coverage", 0, 2, 3 or 4; bits 16..22: key
-                                  * "firefly_clamp", 0..64; bit 23: key "firefly_clamp_passes"; bit 15: key "denoise_temporal_moments"; bit 24: key "denoise_temporal_response" (bits 10 and up are the section's spare bits:
+                                  * "firefly_clamp", 0..64; bit 23: key "firefly_clamp_passes"; bit 15: key "denoise_temporal_moments"; bit 24: key "denoise_temporal_response"; bit 25: key "adaptive_temporal" (bits 10 and up are the section's spare bits:
                                   * those keys have nothing to do with the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
@@ -594,6 +594,18 @@ int hjr_temporal_accumulate_response(hjr_ctx*, const hjr_temporal_frame* prev /*
 int hjr_temporal_accumulate_response_device(hjr_ctx*, const hjr_temporal_frame* prev, const hjr_temporal_frame* cur, void* d_out_color,
                                             void* d_out_variance, void* d_out_history, const void* d_prev_moments, void* d_out_moments,
                                             void* d_out_response, void* hip_stream);
+/* The prior (csrc/hjr_temporal.hip.h section PRIOR; adaptive sampling's rule 11 below reads it): what the history will contribute to each
+ * pixel of a frame that has not been rendered yet.  out_prior is float4 (lp, vp, al, 0), width x height.  The reprojection, the taps and
+ * their validity tests (and the coverage rules when a side's `coverage` is set) are hjr_temporal_accumulate's, bit for bit, up to the
+ * gathered c_prev, v_prev, h_prev.  A pixel that keeps its history, with no tap of unknown variance, gets
+ *   h = min(max(h_prev + 1, 1), 64),  al = max(1 / h, HJR_TEMPORAL_ALPHA),  lp = (c_prev.r + c_prev.g) + c_prev.b,  vp = v_prev;
+ * every other pixel (a restart, prev == NULL, an unknown variance in a tap) gets (0, 0, 1, 0).  al is the factor the accumulation will blend
+ * the pixel's colour with.  The response's lambda and the temporal moments do not enter: they need the current frame's colour.  The
+ * arguments and their checks are hjr_temporal_accumulate's, except that cur->color and cur->variance are not read and may be NULL (cur
+ * needs its G-buffer, camera and transforms).  hjr_temporal_prior: host pointers, synchronous; hjr_temporal_prior_device: device pointers,
+ * asynchronous on `hip_stream`. */
+int hjr_temporal_prior(hjr_ctx*, const hjr_temporal_frame* prev /* NULL = none */, const hjr_temporal_frame* cur, float* out_prior /* float4 */);
+int hjr_temporal_prior_device(hjr_ctx*, const hjr_temporal_frame* prev, const hjr_temporal_frame* cur, void* d_out_prior, void* hip_stream);
 /* The guided 2x upscale (csrc/hjr_denoise.hip.h has the arithmetic to the bit, DESIGN.md §11.4 what was measured): a joint-bilateral stand-in
  * for the bilinear upscale of HJR_MODE_DENOISE_UPSCALE2X.  Every pixel of the out_w x out_h output takes the four bilinear taps (weights 0.75 /
  * 0.25, clamped indices) of the in_w x in_h colour image and keeps those whose low-resolution G-buffer record shows the surface of the output
@@ -735,22 +747,40 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  "denoise_temporal_moments", "denoise_variance_spatial", sample passes and "firefly_clamp".  No effect unless
                                  "denoise_temporal" is on.  Setting it (any value) drops the temporal history.  0 (default): today's call, bit
                                  for bit, the same launches
+   "adaptive_temporal" 0 1       1: adaptive sampling counts the temporal history (rule 11).  In effect only on a sample pass of an
+                                 adaptive frame (hjr_set_adaptive, threshold > 0) rendered by hjr_render_denoised in a Denoise mode with
+                                 "denoise_temporal" on; every other call is today's, bit for bit and the same launches.  At the frame's first
+                                 pass the G-buffer is traced and hjr_temporal_prior_device gathers (lp, vp, al) per pixel from the history; a
+                                 frame without history has no prior and is rule 6's frame, bit for bit.  With a prior, on a deciding pass
+                                 (rule 6's conditions) hjr_finalize_kernel decides nothing and hjr_adaptive_temporal_kernel decides behind it,
+                                 per pixel of an active tile, fp32 as written, n = sample_end, g the granule, m = n / g, (S1, S2) the raw statistic:
+                                   e6 = rule 6's e;   if al < 1:   lc = S1 / n,   vc = rule 7's variance of the mean (S1, S2, m, g, n),
+                                   om = 1 - al,   va = (om om) vp + (al al) vc,   la = lp + (lc - lp) al,
+                                   ea = sqrt(va) / (max(la, 0) + HJR_ADAPTIVE_EPS),   e = min(ea, e6)  (a NaN ea gives e6);   else e = e6;
+                                 the tile sum is rule 6's butterfly and the tile stops iff sum <= noise_threshold x 64.  e <= e6, so a tile
+                                 never receives more samples than under rule 6 on the same frame, history and passes.  The prior leaves
+                                 out "denoise_temporal_response"'s lambda and "denoise_temporal_moments"; the accumulation still applies
+                                 them.  A pass that leaves no active tile commits the temporal history as the pass that ends at spp does;
+                                 a pass that continues such a frame is HJR_ERR_STATE with nothing enqueued (the next pass starts a new frame).
+                                 Together with "firefly_clamp" > 0 and "firefly_clamp_passes" 1 the call is HJR_ERR_ARG before anything is
+                                 enqueued (rules 10 and 11 would both decide).  Setting it ends an unfinished progressive frame, as
+                                 hjr_set_adaptive does, and keeps the history.  hjr_denoise_shards_device ignores it
    [*] takes effect at the next hjr_set_transforms / hjr_prepare_transforms.
  * Not a context option: "passes" (1..64, default 1) is a key of the file's "Henjou_HIP" section (hjr_render_option.passes): hjr_render_file
  * and henjou_cli render each frame in that many sample passes (hjr_params.sample_begin / sample_end) and write the same PNG.  Nor are
  * "noise_threshold" / "min_samples" of the same section (hjr_render_option.noise_threshold / min_samples -> hjr_set_adaptive).
- * Sixteen more keys of that section set the context option of their name; where each is stored is in the comment on hjr_render_option.
+ * Seventeen more keys of that section set the context option of their name; where each is stored is in the comment on hjr_render_option.
  * "force_rebuild" is set by hjr_render_file only.  "verbose", "device_bvh", "device_bvh_refit": N (integer 0..1000), "device_bvh_opt",
  * "device_bvh_instances", "device_bvh_graft", "firefly_clamp": N (integer 0..64) and "firefly_clamp_passes" (true, false, 0 or 1; a parse
  * error without "firefly_clamp") are set single-GPU and on every rank of --devices N.
  * "denoise_variance", "denoise_temporal" (both in the two Denoise modes only), "denoise_variance_spatial", "upscale_guided",
- * "denoise_temporal_moments", "denoise_temporal_response" (both true, false, 0 or 1) and "denoise_temporal_coverage": N (0, 2, 3 or 4) are set single-GPU and on rank 0 of --devices N, which filters, accumulates and upscales (the
+ * "denoise_temporal_moments", "denoise_temporal_response", "adaptive_temporal" (all three true, false, 0 or 1; "adaptive_temporal" is a parse error without "denoise_temporal": true, and henjou_cli --devices N > 1 refuses it: the ranks decide per shard without a history) and "denoise_temporal_coverage": N (0, 2, 3 or 4) are set single-GPU and on rank 0 of --devices N, which filters, accumulates and upscales (the
  * PNG is the single-GPU run's).  "device_bvh_refit" and "device_bvh_instances" are a parse error without "device_bvh": true, and
  * "device_bvh_graft" without "device_bvh_instances": true; "device_bvh_instances", "device_bvh_graft" and "upscale_guided" take true, false, 0
  * or 1 only.  "denoise_variance_spatial", "denoise_temporal_coverage", "denoise_temporal_moments" and "denoise_temporal_response" are accepted and without effect without "denoise_variance" /
  * "denoise_temporal", "upscale_guided" outside DenoiseUpScale2X.  Both drivers refuse, before they load the scene or touch a device:
- * "denoise_temporal" together with "noise_threshold" > 0 (an adaptive frame that stops early never reaches the pass that advances the
- * history), and "firefly_clamp" together with "passes" > 1 or "noise_threshold" > 0 unless "firefly_clamp_passes" is true (the rule needs
+ * "denoise_temporal" together with "noise_threshold" > 0 unless "adaptive_temporal" is true (an adaptive frame that stops early never
+ * reaches the pass that advances the history; with the key the pass that stops the last tile commits it), and "firefly_clamp" together with "passes" > 1 or "noise_threshold" > 0 unless "firefly_clamp_passes" is true (the rule needs
  * every chunk sum of a pixel and a frame in sample passes keeps running sums only).  An option call that fails ends the job.
  * No reference counterpart (OptiX owns these decisions); tests use them to force every kernel layout. */
 int hjr_set_option(hjr_ctx*, const char* key, int value);
