@@ -83,6 +83,13 @@ class RenderOption(_Sized):
                 ("noise_threshold", C.c_float), ("min_samples", C.c_uint32), ("denoise_variance", C.c_int32)]
 
 
+class RenderOptionV2(RenderOption):
+    """hjr_render_option_window: hjr_render_option (`RenderOption`, the layout up to denoise_variance) with the "Henjou_HIP" keys "window"
+    [x0, y0, x1, y1] and "bucket" [bw, bh] (include/henjou_hip.h).  Both are valid callers under the sized-struct rule; load_render_option
+    returns this one."""
+    _fields_ = [("window", C.c_uint32 * 4), ("bucket", C.c_uint32 * 2)]
+
+
 class Camera(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("dir", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3),
                 ("f", C.c_float)]
@@ -103,6 +110,13 @@ class ParamsV2(Params):
     """hjr_params with the fields appended after `Params` (the layout up to flags): the sample pass of a progressive frame
     (include/henjou_hip.h; sample_end 0 = the whole frame).  Both are valid callers under the sized-struct rule; make_params returns this one."""
     _fields_ = [("sample_begin", C.c_uint32), ("sample_end", C.c_uint32)]
+
+
+class ParamsV3(ParamsV2):
+    """hjr_params_window: hjr_params with the render window behind it (include/henjou_hip.h: x0, y0, x1, y1 in full-frame pixels; x1 == 0 =
+    the whole frame).
+    A shorter caller (Params, ParamsV2) renders the whole frame; make_params returns this one when it is given a window."""
+    _fields_ = [("window", C.c_uint32 * 4)]
 
 
 class Stats(_Sized):
@@ -212,6 +226,7 @@ def lib():
         L.hjr_last_error.restype = C.c_char_p
         for name, args in {
             "hjr_load_render_option": [C.c_char_p, C.c_void_p],
+            "hjr_load_render_option_window": [C.c_char_p, C.c_void_p],
             "hjr_scene_load_gltf": [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p],
             "hjr_scene_get_view": [C.c_void_p, C.c_void_p],
             "hjr_scene_eval_transforms": [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p],
@@ -275,12 +290,17 @@ def lib():
             "hjr_assemble_shards": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_assemble_shards_device": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_denoise_shards_device": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+            "hjr_bucket_window": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
+            "hjr_blit_window": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
+            "hjr_blit_window_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
         }.items():
             fn = getattr(L, name)
             fn.restype = C.c_int
             fn.argtypes = args
         L.hjr_owned_tiles.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.hjr_owned_tiles.restype = C.c_uint32
+        L.hjr_bucket_count.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.hjr_bucket_count.restype = C.c_uint32
         L.hjr_sample_granule.argtypes = [C.c_uint32]
         L.hjr_sample_granule.restype = C.c_uint32
         L.hjr_scene_free.argtypes = [C.c_void_p]
@@ -307,8 +327,8 @@ def _np(ptr, count, dtype):
 
 def load_render_option(path):
     """load_json (loader/render_json_loader.h:78-228)."""
-    opt = RenderOption()
-    _check(lib().hjr_load_render_option(os.fsencode(path), C.byref(opt)), "hjr_load_render_option")
+    opt = RenderOptionV2()
+    _check(lib().hjr_load_render_option_window(os.fsencode(path), C.byref(opt)), "hjr_load_render_option_window")
     return opt
 
 
@@ -496,8 +516,8 @@ class Device:
 
     def render(self, params, want_aovs=True, want_variance=False):
         """Synchronous render into host arrays (hjr_render); want_variance: hjr_render_var, and the variance AOV (float32 [h, w]) is
-        returned as a fourth array."""
-        shp = (params.height, params.width, 4)
+        returned as a fourth array.  With a render window (params.window) the arrays have the window's shape."""
+        shp = window_shape(params) + (4,)
         color = np.zeros(shp, dtype=np.float32)
         albedo = np.zeros(shp, dtype=np.float32) if want_aovs else None
         normal = np.zeros(shp, dtype=np.float32) if want_aovs else None
@@ -515,7 +535,7 @@ class Device:
         (sample_end, color, albedo, normal) after each: the running mean over samples [0, sample_end).  The last one is the one-shot frame,
         bit for bit.  `params` itself is not modified.  want_variance: the variance AOV of each pass is yielded as a fifth item."""
         for begin, end in pass_bounds(params.spp, passes):
-            p = ParamsV2()
+            p = ParamsV3()
             C.memmove(C.addressof(p), C.addressof(params), min(C.sizeof(params), C.sizeof(p)))
             p.struct_size = C.sizeof(p)
             p.sample_begin, p.sample_end = begin, end
@@ -559,6 +579,13 @@ class Device:
         _check(lib().hjr_render_device(self._h, C.byref(params), C.c_void_p(d_color),
                                        C.c_void_p(d_albedo) if d_albedo else None, C.c_void_p(d_normal) if d_normal else None,
                                        C.c_void_p(stream) if stream else None), "hjr_render_device")
+
+    def blit_window_device(self, d_window, window, d_frame, width, height, stream=None):
+        """hjr_blit_window_device: the float4 image of a window launch (device pointer, ints as in render_device) into rows y0 .. y1 - 1,
+        columns x0 .. x1 - 1 of a width x height float4 frame on the device; asynchronous on `stream`."""
+        w = (C.c_uint32 * 4)(*window)
+        _check(lib().hjr_blit_window_device(self._h, C.c_void_p(d_window), w, C.c_void_p(d_frame), width, height,
+                                            C.c_void_p(stream) if stream else None), "hjr_blit_window_device")
 
     def denoise(self, mode, color, albedo=None, normal=None, variance=None):
         """OptixDenoiserManager::denoise() replacement on host float4 images (hjr_denoise); returns AOV_Output.  With `variance`
@@ -796,8 +823,10 @@ class Device:
 
 
 def make_params(width, height, spp, camera, frame=1, seed=1, integrator=INTEGRATOR_NEE, sky=(0.8, 0.8, 0.8),
-                ibl_intensity=1.0, rank=0, world_size=1, flags=0, sample_begin=0, sample_end=0):
-    p = ParamsV2()
+                ibl_intensity=1.0, rank=0, world_size=1, flags=0, sample_begin=0, sample_end=0, window=None):
+    """hjr_params.  window: (x0, y0, x1, y1), the render window in full-frame pixels: a ParamsV3.  None = the whole frame, as the ParamsV2
+    this function always returned (the shorter caller of the sized-struct rule)."""
+    p = ParamsV2() if window is None else ParamsV3()
     p.width, p.height, p.spp, p.frame, p.seed, p.integrator = width, height, spp, frame, seed, integrator
     if isinstance(camera, Camera):
         p.camera = camera
@@ -811,7 +840,43 @@ def make_params(width, height, spp, camera, frame=1, seed=1, integrator=INTEGRAT
     p.ibl_intensity = ibl_intensity
     p.rank, p.world_size, p.flags = rank, world_size, flags
     p.sample_begin, p.sample_end = sample_begin, sample_end
+    if window is not None:
+        p.window = (C.c_uint32 * 4)(*window)
     return p
+
+
+def window_shape(params):
+    """(rows, columns) of the outputs of a launch with `params`: the window's, or else the frame's (a caller without the field: the frame's)."""
+    win = getattr(params, "window", None)
+    if win is not None and win[2] != 0:
+        return (int(win[3]) - int(win[1]), int(win[2]) - int(win[0]))
+    return (params.height, params.width)
+
+
+def bucket_windows(width, height, bw, bh):
+    """The buckets of a width x height frame as windows [(x0, y0, x1, y1), ...]: bw x bh rectangles (multiples of 8), row-major from (0, 0),
+    edge buckets clipped to the frame (hjr_bucket_count / hjr_bucket_window)."""
+    n = int(lib().hjr_bucket_count(width, height, bw, bh))
+    if n == 0:
+        raise HjrError("bucket_windows: the frame must not be empty and the bucket sides must be positive multiples of 8")
+    out = []
+    for i in range(n):
+        w = (C.c_uint32 * 4)()
+        _check(lib().hjr_bucket_window(width, height, bw, bh, i, w), "hjr_bucket_window")
+        out.append(tuple(int(v) for v in w))
+    return out
+
+
+def blit_window(window_rgba, window, frame):
+    """hjr_blit_window: writes the float4 image of a window launch into its rectangle of `frame` (row-major float4, modified in place)."""
+    a = np.ascontiguousarray(window_rgba, dtype=np.float32)
+    h, w = frame.shape[:2]
+    assert frame.dtype == np.float32 and frame.flags["C_CONTIGUOUS"]
+    x0, y0, x1, y1 = window
+    if a.shape != (y1 - y0, x1 - x0, 4):
+        raise HjrError("blit_window: the image must have the window's shape")
+    _check(lib().hjr_blit_window(a.ctypes.data, (C.c_uint32 * 4)(*window), frame.ctypes.data, w, h), "hjr_blit_window")
+    return frame
 
 
 def owned_tile_mask(width, height, rank, world_size, tile=8):

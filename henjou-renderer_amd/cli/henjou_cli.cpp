@@ -52,9 +52,10 @@ static bool io_all(int fd, void* buf, size_t n, bool write_it)
 // one rank of a multi-GPU render (its own process; GPU `rank` of the node)
 static int run_rank(const char* json, int rank, int world, int id_fd)
 {
-    hjr_render_option opt;
-    HJR_INIT(opt);
-    HJRX(hjr_load_render_option(json, &opt));
+    hjr::RenderOptionW opt; // (the long form: "window" and "bucket" behind hjr_render_option)
+    memset(static_cast<void*>(&opt), 0, sizeof(opt));
+    opt.struct_size = (uint32_t)sizeof(opt);
+    HJRX(hjr_load_render_option_window(json, &opt));
     // Denoise modes (DESIGN.md §7 "Denoise modes"): every rank renders its tiles with the guide AOVs, and the variance AOV when the filter
     // options ask for it, into ONE per-rank buffer colour | albedo | normal | variance; the frame's one gather moves that buffer, and rank 0
     // assembles, accumulates and filters (hjr_denoise_shards_device).  The filter needs the whole frame, so it is not distributed.
@@ -112,8 +113,12 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
         const float time = f / float(opt.fps); // renderer.h:1128
         HJRX(hjr_scene_eval_transforms(scene, time, m.data(), inv.data()));
         HJRX(hjr_set_transforms(ctx, m.data(), inv.data(), view.n_instances));
-        hjr_params p;
-        HJRX(hjr::frame_params(opt, scene, f, W, H, p));
+        hjr_params_window pw; // (the longer caller: the render window behind hjr_params)
+        memset(&pw, 0, sizeof(pw));
+        hjr_params& p = pw.p;
+        HJRX(hjr::frame_params(opt, scene, f, job.frame_w, job.frame_h, p));
+        p.struct_size = (uint32_t)sizeof(pw);
+        if (job.win) memcpy(pw.window, opt.window, sizeof(pw.window)); // "window": W x H is the window's size; the ranks shard the window's tiles
         p.rank = (uint32_t)rank; p.world_size = (uint32_t)world; p.flags |= HJR_FLAG_PACKED;
         const auto t0 = std::chrono::steady_clock::now();
         // "passes": the frame in sample passes, split as hjr_render_file splits it; the last pass leaves the frame's tiles in d_packed
@@ -142,6 +147,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
             sh.color = d_all; sh.albedo = d_all + block * 4; sh.normal = d_all + block * 8;
             sh.variance = with_var ? d_all + block * 12 : nullptr;
             hjr_params whole = p; // the gather follows the frame's last pass: rank 0 ends the frame (the history advances once per frame)
+            whole.struct_size = (uint32_t)sizeof(whole); // (a plain hjr_params: the Denoise modes take no window)
             whole.sample_begin = whole.sample_end = 0;
             HJRX(hjr_denoise_shards_device(ctx, &whole, opt.render_mode, &sh, d_frame, OW, OH, st));
             HIPX(hipMemcpyAsync(frame.data(), d_frame, frame.size() * 4, hipMemcpyDeviceToHost, st));
@@ -184,9 +190,10 @@ int main(int argc, char** argv)
     }
     // a rank process of a multi-GPU render (world 1: the same code path on one GPU, no id hand-over)
     if (rank >= 0) return (world >= 1 && rank < world && (world == 1 || id_fd >= 0)) ? run_rank(path, rank, world, id_fd) : 2;
-    hjr_render_option opt;
-    HJR_INIT(opt);
-    const bool parsed = hjr_load_render_option(path, &opt) == HJR_OK; // (host-only parse: no GPU is touched here)
+    hjr::RenderOptionW opt;
+    memset(static_cast<void*>(&opt), 0, sizeof(opt));
+    opt.struct_size = (uint32_t)sizeof(opt);
+    const bool parsed = hjr_load_render_option_window(path, &opt) == HJR_OK; // (host-only parse: no GPU is touched here)
     if (devices == 0) { // the JSON decides
         if (!parsed) { fprintf(stderr, "henjou_cli: error: %s\n", hjr_last_error()); return 1; }
         devices = (int)opt.devices;

@@ -30,9 +30,10 @@ __global__ void __launch_bounds__(64) hjr_classify_tiles_kernel(const KParams P)
         const uint32_t tile = idx * P.world + P.rank;
         uint32_t tx, ty;
         hjr_tile_xy(tile, P.tiles_x, &tx, &ty);
-        const uint32_t px = tx * HJR_TILE + (threadIdx.x & 7u), py = ty * HJR_TILE + (threadIdx.x >> 3);
+        const uint32_t wx = tx * HJR_TILE + (threadIdx.x & 7u), wy = ty * HJR_TILE + (threadIdx.x >> 3); // in the work rectangle (the window's tile grid)
+        const uint32_t px = wx + (P.win_word & 0x1fffu), py = wy + (P.win_word >> 13);                     // in the frame: the centre ray is the frame's
         uint32_t cls = 0;
-        if (px < P.width && py < P.height) {
+        if (wx < P.work_w && wy < P.work_h) {
             const float W = (float)P.width, H = (float)P.height;
             const float u = (2.0f * ((float)px + 0.5f) - W) / H, v = (2.0f * ((float)py + 0.5f) - H) / H;
             const f3 cd = V(P.cam_dir[0], P.cam_dir[1], P.cam_dir[2]), cu = V(P.cam_up[0], P.cam_up[1], P.cam_up[2]);
@@ -141,8 +142,8 @@ __global__ void __launch_bounds__(256) hjr_fill_var_kernel(const KParams P, floa
     const size_t n_slots = (size_t)P.n_owned_tiles * 64u;
     for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
         uint32_t x, y;
-        if (!hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y)) continue;
-        aov_var[P.packed ? sl : (size_t)y * P.width + x] = HJR_VARIANCE_UNKNOWN;
+        if (!hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.work_w, P.work_h, &x, &y)) continue;
+        aov_var[P.packed ? sl : (size_t)y * P.work_w + x] = HJR_VARIANCE_UNKNOWN;
     }
 }
 
@@ -177,7 +178,7 @@ __global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P, floa
     const bool run_load = PASS && P.run_load, run_store = PASS && P.run_store;
     for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
         uint32_t x, y;
-        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y);
+        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.work_w, P.work_h, &x, &y);
         if constexpr (!ADAPTIVE) { if (!inside) continue; }
         uint32_t n_tile = 0u; // (wave-uniform) 0: the tile is active
         if constexpr (ADAPTIVE) n_tile = run_load ? P.ad_state[sl >> 6] : 0u;
@@ -223,7 +224,7 @@ __global__ void __launch_bounds__(256) hjr_finalize_kernel(const KParams P, floa
         if constexpr (ADAPTIVE) { if (!inside) continue; } // (after the butterfly)
         const uint32_t n_mean = n_tile ? n_tile : n_frame; // the samples the written mean is over
         const float inv = 1.0f / (float)n_mean;
-        const size_t pix = P.packed ? sl : (size_t)y * P.width + x;
+        const size_t pix = P.packed ? sl : (size_t)y * P.work_w + x;
         P.aov_color[pix] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
         if (P.aov_albedo) P.aov_albedo[pix] = make_float4(b.x * inv, b.y * inv, b.z * inv, 1.0f);
         if (P.aov_normal) P.aov_normal[pix] = make_float4(c.x * inv, c.y * inv, c.z * inv, 1.0f);
@@ -265,7 +266,7 @@ __global__ void __launch_bounds__(BLOCK) hjr_firefly_kernel(const KParams P, con
     uint32_t n_scaled = 0u;
     for (size_t sl = (size_t)blockIdx.x * BLOCK + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * BLOCK) {
         uint32_t x, y;
-        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y);
+        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.work_w, P.work_h, &x, &y);
         bool deciding = false; // (wave-uniform)
         if constexpr (ADAPTIVE) {
             const uint32_t n_tile = P.ad_state[sl >> 6];
@@ -313,7 +314,7 @@ __global__ void __launch_bounds__(BLOCK) hjr_firefly_kernel(const KParams P, con
                 n_scaled += scale ? 1u : 0u;
                 if constexpr (ADAPTIVE) if (k < m) { const float yc = (v.x * s + v.y * s) + v.z * s; S1 = S1 + yc; S2 = S2 + yc * yc; } // (the three products above)
             }
-            P.aov_color[P.packed ? sl : (size_t)y * P.width + x] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
+            P.aov_color[P.packed ? sl : (size_t)y * P.work_w + x] = make_float4(a.x * inv, a.y * inv, a.z * inv, 1.0f);
         }
         if constexpr (ADAPTIVE) {
             if (!deciding) continue;
@@ -355,13 +356,13 @@ __global__ void __launch_bounds__(256) hjr_adaptive_temporal_kernel(const KParam
     for (size_t sl = (size_t)blockIdx.x * blockDim.x + threadIdx.x; sl < n_slots; sl += (size_t)gridDim.x * blockDim.x) {
         if (P.ad_state[sl >> 6] != 0u) continue; // (wave-uniform) stopped before this pass
         uint32_t x, y;
-        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.width, P.height, &x, &y);
+        const bool inside = hjr_slot_xy(sl, P.rank, P.world, P.tiles_x, P.work_w, P.work_h, &x, &y);
         float e = 0.0f;
         if (inside) {
             const float2 s = P.stat[sl];
             const float q = fmaxf(mf * s.y - s.x * s.x, 0.0f);
             const float e6 = sqrtf(q / (mf - 1.0f)) / (s.x + HJR_ADAPTIVE_EPS * nf);
-            const float4 pr = prior[(size_t)y * P.width + x]; // (lp, vp, al, 0)
+            const float4 pr = prior[(size_t)y * P.work_w + x]; // (lp, vp, al, 0)
             e = e6;
             if (pr.z < 1.0f) {
                 const float lc = s.x / nf;
@@ -422,6 +423,15 @@ __global__ void __launch_bounds__(256) hjr_unpack_tiles_kernel(const float4* pac
     if (sl >= (size_t)n_owned * 64u) return;
     uint32_t x, y;
     if (hjr_slot_xy(sl, rank, world, tiles_x, width, height, &x, &y)) frame[(size_t)y * width + x] = packed[sl];
+}
+
+// ---- window pixels -> frame (hjr_blit_window_device): the float4 image of a render window, (y1 - y0) x (x1 - x0) row-major, goes into its
+// rectangle of a full-size frame.  256 threads take 64 x 4 window pixels (image_grid); the frame's other pixels are not touched.
+__global__ void __launch_bounds__(256) hjr_blit_window_kernel(const float4* __restrict__ win, float4* __restrict__ frame, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t frame_w)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    frame[(size_t)(y0 + y) * frame_w + (x0 + x)] = win[(size_t)y * w + x];
 }
 
 // ---- gathered shards -> frames (hjr_assemble_shards_device; DESIGN.md §7 "Denoise modes").  After the one gather of a multi-GPU frame rank 0

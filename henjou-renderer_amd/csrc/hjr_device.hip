@@ -40,13 +40,50 @@ static hipStream_t stream_of(const hjr_ctx* c, void* hip_stream) { return hip_st
 // grid of the image kernels: 256 threads take 64 x 4 pixels
 static dim3 image_grid(uint32_t w, uint32_t h) { return dim3((w + 63) / 64, (h + 3) / 4); }
 // the sized hjr_params of entry point `who`, whose name the refusals carry; false: HJR_ERR_ARG
-static bool take_params(const hjr_ctx* c, const hjr_params* p_user, hjr_params& p, const char* who)
+static bool take_params(const hjr_ctx* c, const hjr_params* p_user, ParamsW& p, const char* who)
 {
     if (!c) { set_error(std::string(who) + ": null context"); return false; }
-    return hjr::abi_take(p_user, p, who);
+    // (abi_take for a caller's hjr_params or hjr_params_window: the window is read iff the caller's struct_size covers it, else it is 0)
+    uint32_t n;
+    if (!hjr::abi_size(p_user, n, who)) return false;
+    memset(static_cast<void*>(&p), 0, sizeof(p));
+    memcpy(static_cast<void*>(&p), p_user, std::min<size_t>(n, sizeof(p)));
+    p.struct_size = (uint32_t)sizeof(p);
+    return true;
 }
 // LaunchPlan::lds_mode of frame data: the builder's 0 BVH4 in memory, 1 / 2 BVH2 staged in LDS, and 3 for a BVH2 it left in memory
 static int launch_layout(const hjr::FrameData& f) { return f.lds_mode == 0 && f.width == 2 ? 3 : f.lds_mode; }
+
+// The work rectangle of a render call: the window (hjr_params_window.window, include/henjou_hip.h), or else the frame.  The one place that reads the
+// window: the tile grid, the owned tiles, the items and every buffer size follow from w x h; x0, y0 reach the kernels as the origin of the
+// full-frame coordinates (KParams::win_word).  p->width and p->height are positive (the callers check).
+struct WorkRect {
+    uint32_t x0 = 0, y0 = 0, w = 0, h = 0;
+    bool window = false;
+    uint64_t key() const { return window ? ((uint64_t)x0 << 39) ^ ((uint64_t)y0 << 26) ^ ((uint64_t)w << 13) ^ (uint64_t)h ^ (1ull << 52) : 0ull; } // 0 = no window; one-to-one below 8192
+};
+static bool has_window(const ParamsW* p) { return p->window[2] != 0u; }
+static int work_rect(const ParamsW* p, const char* who, WorkRect& r)
+{
+    r = WorkRect();
+    r.w = p->width; r.h = p->height;
+    if (!has_window(p)) return HJR_OK;
+    const uint32_t x0 = p->window[0], y0 = p->window[1], x1 = p->window[2], y1 = p->window[3];
+    const std::string text = std::string(who) + ": window [" + std::to_string(x0) + ", " + std::to_string(x1) + ") x [" + std::to_string(y0) + ", " + std::to_string(y1) + ") of a " +
+                             std::to_string(p->width) + " x " + std::to_string(p->height) + " frame: ";
+    if (x0 >= x1 || y0 >= y1) { set_error(text + "window needs x0 < x1 and y0 < y1"); return HJR_ERR_ARG; }
+    if (x1 > p->width || y1 > p->height) { set_error(text + "window needs x1 <= width and y1 <= height"); return HJR_ERR_ARG; }
+    if (x0 % HJR_TILE || y0 % HJR_TILE) { set_error(text + "window needs x0 and y0 to be multiples of " + std::to_string(HJR_TILE)); return HJR_ERR_ARG; }
+    r.x0 = x0; r.y0 = y0; r.w = x1 - x0; r.h = y1 - y0; r.window = true;
+    return HJR_OK;
+}
+// the entry points whose filters need neighbours outside a window take whole frames only
+static int refuse_window(const ParamsW* p, const char* who)
+{
+    if (!has_window(p)) return HJR_OK;
+    set_error(std::string(who) + ": a render window (hjr_params_window.window) is not supported here (the filters and the G-buffer pass need the pixels around a window); render the whole frame");
+    return HJR_ERR_ARG;
+}
 
 // Host buffers through device buffers on the context's stream: every entry point that takes host image pointers.  Uploads, the caller's
 // launch (into `rc`) and downloads each happen only while everything before them succeeded; finish() drains the stream on every path, so no
@@ -527,7 +564,7 @@ static bool firefly_keeps_chunks(const hjr_ctx* c) { return c->opt.get(hjr::OPT_
 
 // The pass rules, checked before a call enqueues or writes anything: HJR_ERR_ARG for a bad range, HJR_ERR_STATE for a pass that does not
 // continue the context's progressive frame.  Changes nothing; end_pass records a launch once it is enqueued.
-static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, PassRange& r)
+static int check_pass(const hjr_ctx* c, const ParamsW* p, uint32_t aovs, PassRange& r)
 {
     r = PassRange();
     r.aovs = aovs;
@@ -560,6 +597,7 @@ static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, Pass
                                      : "no progressive frame is open (its first pass starts at sample 0)";
     else if (r.begin != s.next) bad = "sample_begin " + std::to_string(r.begin) + " does not continue the previous pass, which ended at " + std::to_string(s.next);
     else if (p->width != s.p.width || p->height != s.p.height) bad = "width / height differ from the frame's first pass";
+    else if (memcmp(p->window, s.p.window, sizeof(p->window)) != 0) bad = "window differs from the frame's first pass";
     else if (p->spp != s.p.spp) bad = "spp differs from the frame's first pass";
     else if (p->frame != s.p.frame) bad = "frame differs from the frame's first pass";
     else if (p->seed != s.p.seed) bad = "seed differs from the frame's first pass";
@@ -574,7 +612,7 @@ static int check_pass(const hjr_ctx* c, const hjr_params* p, uint32_t aovs, Pass
     return HJR_OK;
 }
 // after a launch was enqueued: the progressive frame goes on to r.end, or ends (last pass, or a whole-frame render)
-static void end_pass(hjr_ctx* c, const hjr_params* p, const PassRange& r)
+static void end_pass(hjr_ctx* c, const ParamsW* p, const PassRange& r)
 {
     hjr_ctx::PassSession& s = c->pass;
     s.committed = false;
@@ -586,6 +624,7 @@ static void end_pass(hjr_ctx* c, const hjr_params* p, const PassRange& r)
 
 // this rank's share of a frame
 struct FrameGeom {
+    WorkRect rect; // the window, or else the frame: the extent everything below is derived from
     uint32_t world, tiles_x, chunk_spp, n_chunks;
     uint32_t chunk0, pass_chunks; // the chunks this launch renders: [chunk0, chunk0 + pass_chunks) (all n_chunks for a whole frame)
     uint64_t owned, n_items;
@@ -594,7 +633,7 @@ struct FrameGeom {
 };
 
 // argument checks and tile geometry
-static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_color, const PassRange& pr, FrameGeom& g)
+static int frame_geometry(const hjr_ctx* c, const ParamsW* p, const void* d_color, const PassRange& pr, FrameGeom& g)
 {
     if (!c || !p || !d_color) { set_error("hjr_render: null argument"); return HJR_ERR_ARG; }
     if (!c->have_scene || !c->have_frame) { set_error("hjr_render: upload a scene and set transforms first"); return HJR_ERR_STATE; }
@@ -603,8 +642,10 @@ static int frame_geometry(const hjr_ctx* c, const hjr_params* p, const void* d_c
     if (p->integrator > HJR_INTEGRATOR_MIS) { set_error("hjr_render: unknown integrator"); return HJR_ERR_ARG; }
     g.world = p->world_size ? p->world_size : 1u;
     if (p->rank >= g.world) { set_error("hjr_render: rank >= world_size"); return HJR_ERR_ARG; }
-    g.tiles_x = (p->width + HJR_TILE - 1) / HJR_TILE;
-    const uint64_t n_tiles = (uint64_t)g.tiles_x * ((p->height + HJR_TILE - 1) / HJR_TILE);
+    if (const int rc = work_rect(p, "hjr_render", g.rect)) return rc;
+    if (g.rect.window && c->opt.get(hjr::OPT_ADAPTIVE_TEMPORAL, 0) != 0) { set_error("hjr_render: a render window (hjr_params_window.window) cannot be combined with option \"adaptive_temporal\" (its prior is a whole-frame gather)"); return HJR_ERR_ARG; }
+    g.tiles_x = (g.rect.w + HJR_TILE - 1) / HJR_TILE;
+    const uint64_t n_tiles = (uint64_t)g.tiles_x * ((g.rect.h + HJR_TILE - 1) / HJR_TILE);
     g.owned = (n_tiles > p->rank) ? (n_tiles - p->rank + g.world - 1) / g.world : 0;
     g.chunk_spp = hjr_chunk_spp(p->spp); g.n_chunks = hjr_n_chunks(p->spp);
     g.pr = pr;
@@ -636,14 +677,14 @@ static void bind_scene_tables(const hjr_ctx* c, KParams& kp)
 }
 
 // work area, output zeroing, chunk-sum buffers, and the kernel parameters of scene, frame and outputs
-static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st, KParams& kp)
+static int bind_params(hjr_ctx* c, const ParamsW* p, const FrameGeom& g, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st, KParams& kp)
 {
     if (c->d_work.cap < WorkArea::BYTES) {
         std::vector<unsigned char> z(WorkArea::BYTES, 0);
         if (!c->d_work.upload(z.data(), WorkArea::BYTES, st)) { set_error("hjr_render: work buffer allocation failed"); return HJR_ERR_DEVICE; }
     }
     HIPCHK(hipMemsetAsync(c->d_work.p, 0, WorkArea::BYTES, st));
-    const size_t img_bytes = (size_t)p->width * p->height * 16;
+    const size_t img_bytes = (size_t)g.rect.w * g.rect.h * 16;
     const bool packed = (p->flags & HJR_FLAG_PACKED) != 0;
     if (!packed && g.world > 1 && (p->flags & HJR_FLAG_ZERO_UNOWNED)) {
         HIPCHK(hipMemsetAsync(d_color, 0, img_bytes, st));
@@ -698,7 +739,8 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
     kp.stats = (unsigned long long*)(work + WorkArea::STATS);
     kp.nan_list = (unsigned long long*)(work + WorkArea::NAN_LIST);
     kp.n_lights = c->frame.n_lights;
-    kp.width = p->width; kp.height = p->height; kp.spp = p->spp; kp.frame = p->frame; kp.seed = p->seed; kp.integrator = p->integrator;
+    kp.width = p->width; kp.height = p->height; kp.work_w = g.rect.w; kp.work_h = g.rect.h; kp.win_word = g.rect.x0 | (g.rect.y0 << 13);
+    kp.spp = p->spp; kp.frame = p->frame; kp.seed = p->seed; kp.integrator = p->integrator;
     kp.tiles_x = g.tiles_x; kp.n_owned_items = (uint32_t)g.n_items;
     kp.rank = p->rank; kp.world = g.world;
     kp.packed = packed ? 1u : 0u;
@@ -714,7 +756,7 @@ static int bind_params(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, void
 }
 
 // cost-ordered tile list (hjr_classify_tiles_kernel): option "tile_order" = 0 keeps the plain round-robin order
-static int order_tiles(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KParams& kp, hipStream_t st)
+static int order_tiles(hjr_ctx* c, const ParamsW* p, const FrameGeom& g, KParams& kp, hipStream_t st)
 {
     const int order_knob = c->opt.get(hjr::OPT_TILE_ORDER, -1); // option "tile_order"
     if (order_knob == 0 || g.owned == 0) return HJR_OK;
@@ -738,9 +780,10 @@ static int order_tiles(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KPar
     if (cost_feedback) {
         if (!c->d_tile_cost.reserve(tb, &grown)) { set_error("hjr_render: tile cost allocation failed"); return HJR_ERR_DEVICE; }
         if (grown) c->cost_tag = 0;
-        have_cost = c->cost_tag == tag;
+        // (the costs and classes are per tile of the work rectangle's grid: those of another window are another configuration)
+        have_cost = c->cost_tag == tag && c->cost_rect == g.rect.key();
         if (!have_cost) HIPCHK(hipMemsetAsync(c->d_tile_cost.p, 0, tb, st));
-        c->cost_tag = tag;
+        c->cost_tag = tag; c->cost_rect = g.rect.key();
         kp.tile_cost = (uint32_t*)c->d_tile_cost.p;
         kp.cost_hist = (uint32_t*)(work + WorkArea::COST_HIST);
         // the costs were measured by the previous launch of this configuration: normalised by ITS samples (a whole frame, or the
@@ -766,7 +809,7 @@ static int order_tiles(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KPar
 }
 
 // the render kernel
-static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, const KParams& kp, hipStream_t st)
+static int launch_render(hjr_ctx* c, const ParamsW* p, const FrameGeom& g, const KParams& kp, hipStream_t st)
 {
     const bool stats = (p->flags & HJR_FLAG_STATS) != 0;
     bool fast = false;
@@ -776,6 +819,7 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
     fast = (p->flags & HJR_FLAG_FAST_MATH) && !stats && p->integrator != HJR_INTEGRATOR_MIS;
 #endif
     LaunchPlan pl = plan_launch(c, kp, g.n_items, g.lds_mode, p->integrator, fast);
+    pl.window = g.rect.window; // the kernels that carry the window's origin; every whole-frame launch runs the kernels it always ran
     // Megakernel: a work item is a pixel's group of r consecutive chunks (hjr_layout.h: hjr_item_range), r = the largest power of two <=
     // option "item_chunks" that divides the launch's chunk count.  The queue then holds 1 / r of the single-chunk items frame_geometry
     // counted, and its head still overshoots by at most 64 per wave, so the margin taken there covers every r.
@@ -792,7 +836,7 @@ static int launch_render(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, co
     if (!pl.wf && p->integrator != HJR_INTEGRATOR_MIS) { // (MIS runs the wavefront kernels; its megakernel, an option, keeps single chunks)
         const bool is_long = g.n_items >= (uint64_t)(c->n_cus > 0 ? c->n_cus : 1) * HJR_BLOCK_LDS * HJR_ITEM_GROUP_MIN;
         const int def = (g.world > 1 || stats || !is_long || g.chunk_spp > 8u) ? 1 : HJR_ITEM_CHUNKS;
-        pl.kp.item_chunks = hjr_item_chunks((uint32_t)c->opt.get(hjr::OPT_ITEM_CHUNKS, def), g.pass_chunks);
+        pl.kp.item_chunks = g.rect.window ? 1u : hjr_item_chunks((uint32_t)c->opt.get(hjr::OPT_ITEM_CHUNKS, def), g.pass_chunks); // (a window: single chunks, the only form its kernels have)
         n_items = hjr_item_count(g.n_items / ((uint64_t)g.pass_chunks * 64u), g.pass_chunks, pl.kp.item_chunks); // (g.n_items counts the active tiles of an adaptive pass)
         pl.kp.n_owned_items = (uint32_t)n_items;
     }
@@ -831,7 +875,7 @@ static int adaptive_items(hjr_ctx* c, FrameGeom& g, uint32_t& active)
     return HJR_OK;
 }
 // ... after bind_params: the tile states (+ the counter word) and the compacted list, kept across the passes of a frame
-static int adaptive_bind(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, KParams& kp)
+static int adaptive_bind(hjr_ctx* c, const ParamsW* p, const FrameGeom& g, KParams& kp)
 {
     hjr_ctx::Adaptive& ad = c->ad;
     if (!ad.state.reserve(((size_t)g.owned + 1u) * 4u) || !ad.list.reserve((size_t)g.owned * 4u)) {
@@ -904,7 +948,7 @@ static int firefly_launch(hjr_ctx* c, const FrameGeom& g, const KParams& kp, uin
 }
 // Option "firefly_clamp" (hjr_firefly_kernel, DESIGN.md §4 rule 9), behind finalize_chunks on a one-shot frame: the colour of the pixels with a
 // chunk over their limit is rewritten.  With the option off, or a frame of fewer than 4 full chunks, nothing is launched.
-static int firefly_clamp(hjr_ctx* c, const hjr_params* p, const FrameGeom& g, const KParams& kp, hipStream_t st)
+static int firefly_clamp(hjr_ctx* c, const ParamsW* p, const FrameGeom& g, const KParams& kp, hipStream_t st)
 {
     const uint32_t m = p->spp / g.chunk_spp;
     if (c->opt.get(hjr::OPT_FIREFLY_CLAMP, 0) <= 0 || g.pr.pass || g.n_chunks < 2 || m < 4 || g.owned == 0) return HJR_OK;
@@ -939,7 +983,7 @@ static int adaptive_temporal_launch(hjr_ctx* c, const FrameGeom& g, const KParam
 // pr: check_pass of this call, made before the caller enqueued anything
 // d_var: the variance AOV (one float per pixel) or null
 // d_prior: option "adaptive_temporal" in effect and the frame has a prior (hjr_render_denoised): rule 11 takes an adaptive pass's decisions
-static int render_impl(hjr_ctx* c, const hjr_params* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st, const void* d_prior = nullptr)
+static int render_impl(hjr_ctx* c, const ParamsW* p, const PassRange& pr, void* d_color, void* d_albedo, void* d_normal, void* d_var, hipStream_t st, const void* d_prior = nullptr)
 {
     FrameGeom g;
     KParams kp;
@@ -1104,9 +1148,11 @@ static int fetch_stats(hjr_ctx* c, hipStream_t st)
 
 extern "C" int hjr_render_device_var(hjr_ctx* c, const hjr_params* p_user, void* d_color, void* d_albedo, void* d_normal, void* d_variance, void* stream)
 {
-    hjr_params params; // sized struct
+    ParamsW params; // sized struct (the long form: the render window behind hjr_params)
     if (!take_params(c, p_user, params, "hjr_render_device")) return HJR_ERR_ARG;
-    const hjr_params* p = &params;
+    const ParamsW* p = &params;
+    WorkRect rect; // (a bad window is HJR_ERR_ARG ahead of the pass rules, as in hjr_render_var)
+    if (const int rc = work_rect(p, "hjr_render", rect)) return rc;
     PassRange pr;
     if (const int rc = check_pass(c, p, (d_color ? 1u : 0u) | (d_albedo ? 2u : 0u) | (d_normal ? 4u : 0u) | (d_variance ? 8u : 0u), pr)) return rc;
     return render_impl(c, p, pr, d_color, d_albedo, d_normal, d_variance, stream_of(c, stream));
@@ -1269,7 +1315,7 @@ static const GbufTexts GBUF_TEMPORAL = { ": option \"denoise_temporal\" needs th
 static const GbufTexts GBUF_GUIDED = { ": option \"upscale_guided\" needs the frame data of this frame (upload a scene and set transforms first)",
                                        ": option \"upscale_guided\" does not take world_size > 1 or HJR_FLAG_PACKED",
                                        ": option \"upscale_guided\" does not take outputs larger than " HJR_GBUFFER_MAX_TEXT };
-static int gbuffer_check(const hjr_ctx* c, const hjr_params* p, const std::string& who, const GbufTexts& t)
+static int gbuffer_check(const hjr_ctx* c, const ParamsW* p, const std::string& who, const GbufTexts& t)
 {
     if (!c->have_scene || !c->have_frame) { set_error(who + t.no_frame); return HJR_ERR_STATE; }
     if (p->world_size > 1 || (p->flags & HJR_FLAG_PACKED)) { set_error(who + t.sharded); return HJR_ERR_ARG; }
@@ -1279,9 +1325,10 @@ static int gbuffer_check(const hjr_ctx* c, const hjr_params* p, const std::strin
 }
 // G-buffer pass on device memory: the classifier's launch shape (one wave per tile, its stacks in dynamic LDS).  side 0: the plain pass;
 // 2, 3, 4: the coverage pass with side x side sub-pixel rays
-static int gbuffer_device_impl(hjr_ctx* c, const hjr_params* p, void* d_out, hipStream_t st, uint32_t side)
+static int gbuffer_device_impl(hjr_ctx* c, const ParamsW* p, void* d_out, hipStream_t st, uint32_t side)
 {
     if (!c || !p || !d_out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
+    if (const int rc = refuse_window(p, "hjr_render_gbuffer")) return rc;
     if (const int rc = gbuffer_check(c, p, "hjr_render_gbuffer", GBUF_OWN)) return rc;
     HIPCHK(hipSetDevice(c->device));
     GbufArgs a;
@@ -1311,20 +1358,20 @@ static bool coverage_side_ok(uint32_t side)
 }
 extern "C" int hjr_render_gbuffer_device(hjr_ctx* c, const hjr_params* p_user, void* d_out, void* hip_stream)
 {
-    hjr_params params; // sized struct
+    ParamsW params; // sized struct (the long form: the render window behind hjr_params)
     if (!take_params(c, p_user, params, "hjr_render_gbuffer")) return HJR_ERR_ARG;
     return gbuffer_device_impl(c, &params, d_out, stream_of(c, hip_stream), 0);
 }
 extern "C" int hjr_render_gbuffer_cov_device(hjr_ctx* c, const hjr_params* p_user, uint32_t side, void* d_out, void* hip_stream)
 {
-    hjr_params params; // sized struct
+    ParamsW params; // sized struct (the long form: the render window behind hjr_params)
     if (!coverage_side_ok(side)) return HJR_ERR_ARG;
     if (!take_params(c, p_user, params, "hjr_render_gbuffer_cov")) return HJR_ERR_ARG;
     return gbuffer_device_impl(c, &params, d_out, stream_of(c, hip_stream), side);
 }
 static int gbuffer_host_impl(hjr_ctx* c, const hjr_params* p_user, hjr_gbuffer_px* out, uint32_t side)
 {
-    hjr_params params; // sized struct
+    ParamsW params; // sized struct (the long form: the render window behind hjr_params)
     if (!take_params(c, p_user, params, "hjr_render_gbuffer")) return HJR_ERR_ARG;
     if (!out) { set_error("hjr_render_gbuffer: null argument"); return HJR_ERR_ARG; }
     const size_t bytes = (size_t)params.width * params.height * sizeof(hjr_gbuffer_px);
@@ -1553,7 +1600,7 @@ extern "C" int hjr_temporal_prior(hjr_ctx* c, const hjr_temporal_frame* prev_use
 // frame loop that already prepares the next frame on another thread cannot be seen here), accumulation against the previous slot.
 // `commit`: this call ends the frame (a whole-frame render, or the sample pass that ends at spp): the slots rotate.
 // the current slot's buffers (no enqueue: post_plan calls it ahead of the first launch, temporal_stage again to no effect)
-static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
+static int temporal_reserve(hjr_ctx* c, const ParamsW* p)
 {
     hjr_ctx::Temporal& t = c->tmp;
     const size_t npx = (size_t)p->width * p->height, nx = c->built.m.size() * 4;
@@ -1566,13 +1613,13 @@ static int temporal_reserve(hjr_ctx* c, const hjr_params* p)
     return HJR_OK;
 }
 // the history belongs to frames of this size, mode and instance count: anything else restarts
-static void temporal_match(hjr_ctx* c, const hjr_params* p, int render_mode, uint32_t n_inst)
+static void temporal_match(hjr_ctx* c, const ParamsW* p, int render_mode, uint32_t n_inst)
 {
     hjr_ctx::Temporal& t = c->tmp;
     if (t.have_prev && (t.width != p->width || t.height != p->height || t.mode != render_mode || t.n_instances != n_inst)) t.have_prev = false;
 }
 // the current slot's G-buffer, transforms and camera of the frame p describes
-static int temporal_trace(hjr_ctx* c, const hjr_params* p, uint32_t n_inst, uint32_t cov, hipStream_t st)
+static int temporal_trace(hjr_ctx* c, const ParamsW* p, uint32_t n_inst, uint32_t cov, hipStream_t st)
 {
     hjr_ctx::Temporal::Slot& now = c->tmp.slot[c->tmp.cur];
     const size_t nx = (size_t)n_inst * 48;
@@ -1595,7 +1642,7 @@ static hjr_temporal_frame temporal_slot_frame(const hjr_ctx::Temporal::Slot& s, 
 // Option "adaptive_temporal", ahead of the render of a frame's first sample pass (the buffers stand: post_plan): the frame's G-buffer into the
 // current slot and the prior against the committed history, for every pass of the frame.  Without a history there is no prior, and the frame
 // is rule 6's.
-static int temporal_prior_stage(hjr_ctx* c, const hjr_params* p, int render_mode, hipStream_t st)
+static int temporal_prior_stage(hjr_ctx* c, const ParamsW* p, int render_mode, hipStream_t st)
 {
     hjr_ctx::Temporal& t = c->tmp;
     const uint32_t n_inst = (uint32_t)(c->built.m.size() / 12);
@@ -1611,12 +1658,12 @@ static int temporal_prior_stage(hjr_ctx* c, const hjr_params* p, int render_mode
     return HJR_OK;
 }
 // `commit` of temporal_stage: the frame in the current slot becomes the history, the slots rotate
-static void temporal_commit(hjr_ctx* c, const hjr_params* p, int render_mode, uint32_t n_inst)
+static void temporal_commit(hjr_ctx* c, const ParamsW* p, int render_mode, uint32_t n_inst)
 {
     hjr_ctx::Temporal& t = c->tmp;
     t.have_prev = true; t.width = p->width; t.height = p->height; t.mode = render_mode; t.n_instances = n_inst; t.cur ^= 1;
 }
-static int temporal_stage(hjr_ctx* c, const hjr_params* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
+static int temporal_stage(hjr_ctx* c, const ParamsW* p, int render_mode, bool commit, const void*& d_color, const void*& d_var, hipStream_t st)
 {
     hjr_ctx::Temporal& t = c->tmp;
     const uint32_t n_inst = (uint32_t)(c->built.m.size() / 12);
@@ -1706,14 +1753,14 @@ static PostPlan post_options(const hjr_ctx* c, int render_mode)
 // temporal stage traces the render-size one itself).  Nothing of the stage can fail behind the first launch but the runtime.
 // `pr` non-null: the caller renders the frame itself (hjr_render_denoised), and the render's pass and argument rules speak where they
 // always did, behind the guided upscale's and ahead of the filter's: *pr is the pass the render will run.
-static int post_plan(hjr_ctx* c, const hjr_params* p, const PostPlan& pl, uint32_t out_w, uint32_t out_h, const char* who, PassRange* pr)
+static int post_plan(hjr_ctx* c, const ParamsW* p, const PostPlan& pl, uint32_t out_w, uint32_t out_h, const char* who, PassRange* pr)
 {
     const bool sharded = p->world_size > 1 || (p->flags & HJR_FLAG_PACKED);
     if (pl.temporal && sharded) { set_error(std::string(who) + GBUF_TEMPORAL.sharded); return HJR_ERR_ARG; }
     if (pl.guided && sharded) { set_error(std::string(who) + GBUF_GUIDED.sharded); return HJR_ERR_ARG; }
     if (pl.guided) {
         if (const int rc = denoise_check_sizes(pl.mode, p->width, p->height, out_w, out_h)) return rc;
-        hjr_params hi = *p; // the second G-buffer pass
+        ParamsW hi = *p; // the second G-buffer pass
         hi.width = out_w; hi.height = out_h;
         if (const int rc = gbuffer_check(c, &hi, who, GBUF_GUIDED)) return rc;
     }
@@ -1740,7 +1787,7 @@ static int post_plan(hjr_ctx* c, const hjr_params* p, const PostPlan& pl, uint32
 // Option "denoise_variance_spatial" with a variance in play: ahead of both, pixels of unknown variance get the spatial estimate, in place.
 // pl.guided: the filter as in Denoise mode with its last pass into the ping-pong buffer, the G-buffer at the render size (the temporal
 // stage's of this frame if there is one) and at the output size from the same camera, and the guided kernel in place of the bilinear one.
-static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, const PostPlan& pl, bool commit, void* d_out, uint32_t out_w, uint32_t out_h, hipStream_t st)
+static int denoise_post_stage(hjr_ctx* c, const ParamsW* p, const PostPlan& pl, bool commit, void* d_out, uint32_t out_w, uint32_t out_h, hipStream_t st)
 {
     const void *f_color = c->d_color.p, *f_var = pl.with_var ? c->d_variance.p : nullptr; // what the filter reads
     if (pl.with_var && c->opt.get(hjr::OPT_DENOISE_VARIANCE_SPATIAL, 0) != 0)
@@ -1756,7 +1803,7 @@ static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, const PostPlan& p
     const void* g_lo = pl.temporal ? c->tmp.slot[slot].gbuf.p : c->d_ug_lo.p;
     if (!pl.temporal)
         if (const int rc = gbuffer_device_impl(c, p, c->d_ug_lo.p, st, 0)) return rc;
-    hjr_params hi = *p;
+    ParamsW hi = *p;
     hi.width = out_w; hi.height = out_h;
     if (const int rc = gbuffer_device_impl(c, &hi, c->d_ug_hi.p, st, 0)) return rc;
     return upscale_guided_launch(p->width, p->height, filtered, g_lo, p->camera, c->d_ug_hi.p, d_out, out_w, out_h, st);
@@ -1766,10 +1813,11 @@ static int denoise_post_stage(hjr_ctx* c, const hjr_params* p, const PostPlan& p
 // (renderer.h:1229-1281).  p->width x p->height is the RENDER size (already halved by the caller for DenoiseUpScale2X).
 extern "C" int hjr_render_denoised(hjr_ctx* c, const hjr_params* p_user, int render_mode, float* out, uint32_t out_w, uint32_t out_h)
 {
-    hjr_params params; // sized struct
+    ParamsW params; // sized struct (the long form: the render window behind hjr_params)
     if (!take_params(c, p_user, params, "hjr_render_denoised")) return HJR_ERR_ARG;
-    const hjr_params* p = &params;
+    const ParamsW* p = &params;
     if (!out) { set_error("hjr_render_denoised: null argument"); return HJR_ERR_ARG; }
+    if (const int rc = refuse_window(p, "hjr_render_denoised")) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t in_bytes = (size_t)p->width * p->height * 16, out_bytes = (size_t)out_w * out_h * 16;
     if (in_bytes == 0 || out_bytes == 0) { set_error("hjr_render_denoised: empty image"); return HJR_ERR_ARG; }
@@ -1833,12 +1881,13 @@ extern "C" int hjr_assemble_shards_device(hjr_ctx* c, const hjr_shards* shards, 
 extern "C" int hjr_denoise_shards_device(hjr_ctx* c, const hjr_params* p_user, int render_mode, const hjr_shards* gathered, void* d_out, uint32_t out_w, uint32_t out_h,
                                          void* hip_stream)
 {
-    hjr_params params; // sized struct
+    ParamsW params; // sized struct (the long form: the render window behind hjr_params)
     if (!take_params(c, p_user, params, "hjr_denoise_shards_device")) return HJR_ERR_ARG;
     if (!d_out) { set_error("hjr_denoise_shards_device: null argument"); return HJR_ERR_ARG; }
+    if (const int rc = refuse_window(&params, "hjr_denoise_shards_device")) return rc;
     if (render_mode == HJR_MODE_DEFAULT) { set_error("hjr_denoise_shards_device: Render_mode Default has no filter (hjr_assemble_shards_device assembles the frame)"); return HJR_ERR_ARG; }
     params.rank = 0; params.world_size = 1; params.flags &= ~HJR_FLAG_PACKED; // `frame` describes the whole frame; gathered->world_size is how it was rendered
-    const hjr_params* p = &params;
+    const ParamsW* p = &params;
     if (const int rc = denoise_check_sizes(render_mode, p->width, p->height, out_w, out_h)) return rc;
     const bool whole = p->sample_end == 0 || (p->sample_begin == 0 && p->sample_end == p->spp);
     if (!whole && (p->sample_begin >= p->sample_end || p->sample_end > p->spp)) { set_error("hjr_denoise_shards_device: bad sample range"); return HJR_ERR_ARG; }
@@ -1956,6 +2005,37 @@ extern "C" int hjr_unpack_tiles_device(hjr_ctx* c, const void* d_packed, uint32_
     return tiles_device(c, false, d_frame, d_packed, w, h, rank, world, hip_stream);
 }
 
+// hjr_render_file's bucketed frames (host/render_file.cpp is plain host code): the context's two buffers, and the frame's one download
+namespace hjr {
+int bucket_buffer(hjr_ctx* c, int slot, size_t bytes, void** d_out)
+{
+    if (!c || !d_out || slot < 0 || slot > 1) { set_error("bucket_buffer: bad argument"); return HJR_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_bucket[slot].reserve(bytes)) { set_error("hjr_render_file: bucket buffer allocation failed"); return HJR_ERR_DEVICE; }
+    *d_out = c->d_bucket[slot].p;
+    return HJR_OK;
+}
+int bucket_download(hjr_ctx* c, float* host, const void* d_frame, size_t bytes)
+{
+    if (!c || !host || !d_frame) { set_error("bucket_download: null argument"); return HJR_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(host, d_frame, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return HJR_OK;
+}
+} // namespace hjr
+
+// hjr_blit_window_device: a window launch's float4 image into its rectangle of a full-size frame (csrc/hjr_aux.hip.h)
+extern "C" int hjr_blit_window_device(hjr_ctx* c, const void* d_window, const uint32_t window[4], void* d_frame, uint32_t w, uint32_t h, void* hip_stream)
+{
+    if (!c || !d_window || !window || !d_frame) { set_error("hjr_blit_window_device: null argument"); return HJR_ERR_ARG; }
+    if (const int rc = hjr::check_blit_window(window, w, h, "hjr_blit_window_device")) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const uint32_t ww = window[2] - window[0], wh = window[3] - window[1];
+    hipLaunchKernelGGL(hjr_blit_window_kernel, image_grid(ww, wh), dim3(256), 0, stream_of(c, hip_stream), (const float4*)d_window, (float4*)d_frame, window[0], window[1], ww, wh, w);
+    return launched();
+}
+
 extern "C" int hjr_preview_device(hjr_ctx* c, const void* d_color, uint32_t w, uint32_t h, int tonemap, void* d_rgba8, void* hip_stream)
 {
     if (!c || !d_color || !d_rgba8 || w == 0 || h == 0 || tonemap < HJR_TONEMAP_NONE || tonemap > HJR_TONEMAP_ACES) { set_error("hjr_preview_device: bad argument"); return HJR_ERR_ARG; }
@@ -1994,15 +2074,17 @@ extern "C" int hjr_get_stats(hjr_ctx* c, hjr_stats* out)
 extern "C" int hjr_render_var(hjr_ctx* c, const hjr_params* p_user, float* color, float* albedo, float* normal, float* variance)
 {
     if (!c || !p_user || !color) { set_error("hjr_render: null argument"); return HJR_ERR_ARG; }
-    hjr_params params; // sized struct
-    if (!hjr::abi_take(p_user, params, "hjr_render")) return HJR_ERR_ARG;
-    const hjr_params* p = &params;
+    ParamsW params; // sized struct (the long form: the render window behind hjr_params)
+    if (!take_params(c, p_user, params, "hjr_render")) return HJR_ERR_ARG;
+    const ParamsW* p = &params;
     HIPCHK(hipSetDevice(c->device));
     if ((size_t)p->width * p->height == 0) { set_error("hjr_render: empty image"); return HJR_ERR_ARG; }
     // HJR_FLAG_PACKED: the buffers hold this rank's tiles only (hjr_owned_tiles x 64 float4), as in hjr_render_device
     const bool packed_out = (p->flags & HJR_FLAG_PACKED) != 0;
     if (p->rank >= (p->world_size ? p->world_size : 1u)) { set_error("hjr_render: rank >= world_size"); return HJR_ERR_ARG; }
-    const size_t bytes = packed_out ? (size_t)hjr_owned_tiles(p->width, p->height, p->rank, p->world_size ? p->world_size : 1u) * 64u * 16u : (size_t)p->width * p->height * 16;
+    WorkRect rect; // the host buffers are the work rectangle's size: the window's, or else the frame's
+    if (const int rc = work_rect(p, "hjr_render", rect)) return rc;
+    const size_t bytes = packed_out ? (size_t)hjr_owned_tiles(rect.w, rect.h, p->rank, p->world_size ? p->world_size : 1u) * 64u * 16u : (size_t)rect.w * rect.h * 16;
     PassRange pr;
     if (const int rc = check_pass(c, p, 1u | (albedo ? 2u : 0u) | (normal ? 4u : 0u) | (variance ? 8u : 0u), pr)) return rc;
     if (bytes == 0) { end_pass(c, p, pr); return HJR_OK; } // a rank without tiles

@@ -169,7 +169,7 @@ struct PathState {
 // CMJState of the path that is running sample s of pixel (px, py) (build-defined seeding)
 HD CMJState path_rng(const KParams& P, uint32_t px, uint32_t py, uint32_t s, uint32_t depth)
 {
-    return cmj_state((unsigned long long)P.frame * (unsigned long long)P.spp + (unsigned long long)s, P.seed, px + py * P.width, depth);
+    return cmj_state((unsigned long long)P.frame * (unsigned long long)P.spp + (unsigned long long)s, P.seed, px + py * P.width, depth); // (px, py and P.width are the full frame's, also under a render window)
 }
 HD uint32_t path_head(const KParams& P, uint32_t px, uint32_t py, uint32_t s) { return path_rng(P, px, py, s, 0u).head; }
 // the same state from a stored head: index = (frame * spp + s) % 16 needs the low bits of the sum only
@@ -190,7 +190,7 @@ HD void start_path(const KParams& P, PathState& ps, uint32_t px, uint32_t py, ui
     ps.rng_head = st.head;
     f2 j = cmj_2d(st);
     ps.rng_depth = st.depth;
-    float W = (float)P.width, H = (float)P.height;
+    float W = (float)P.width, H = (float)P.height; // (the full frame's)
     float u = (2.0f * ((float)px + j.x) - W) / H;
     float v = (2.0f * ((float)py + j.y) - H) / H;
     f3 cd = V(P.cam_dir[0], P.cam_dir[1], P.cam_dir[2]);
@@ -335,13 +335,20 @@ template <bool GROUPS> HD void close_sample(const KParams& P, LaneCtx& c)
     // first one of the next chunk, like any other next sample (write_out moves the item word on once the sums are stored)
     if (c.s == HJR_S_END(c)) { c.write_pending = true; c.has_item = GROUPS && !hjr_item_last_chunk(HJR_CHUNK(c), P.chunk0, P.item_chunks); }
 }
-template <bool AOVS, bool GROUPS> HD void write_out(const KParams& P, LaneCtx& c)
+// WIN: the launch renders a window (KParams::win_word): the kernels of whole-frame launches do not carry the origin and are the code they were
+template <bool AOVS, bool GROUPS, bool WIN = false> HD void write_out(const KParams& P, LaneCtx& c)
 {
     const float inv_spp = 1.0f / (float)P.spp;
     const uint32_t tiles_x = HJR_COLD(tiles_x), world = HJR_COLD(world), n_chunks = HJR_COLD(n_chunks); // (cold parameters: see cold_param)
+    // WIN: the item word holds full-frame coordinates; the outputs and the tile grid are the window's.  Neither field of the origin word exceeds
+    // the item's, so one subtraction takes both back to window coordinates.  Without WIN every expression below is the one it was
+    [[maybe_unused]] uint32_t work_w = 0u, rel = 0u;
+    if constexpr (WIN) { work_w = HJR_COLD(work_w); rel = c.item - HJR_COLD(win_word); } // (read here, with the others: see KParams::win_word)
+#define HJR_WX(c) (WIN ? (rel & 0x1fffu) : HJR_PX(c))
+#define HJR_WY(c) (WIN ? ((rel >> 13) & 0x1fffu) : HJR_PY(c))
     // AOV element of the pixel: row-major frame, or (HJR_FLAG_PACKED) this rank's tiles back to back: (owned tile index) * 64 + pixel in tile
-    const size_t pix = HJR_COLD(packed) ? (size_t)(hjr_tile_id(HJR_PX(c) / HJR_TILE, HJR_PY(c) / HJR_TILE, tiles_x) / world) * 64u + ((HJR_PY(c) & 7u) * 8u + (HJR_PX(c) & 7u))
-                                        : (size_t)HJR_PX(c) + (size_t)HJR_PY(c) * P.width;
+    const size_t pix = HJR_COLD(packed) ? (size_t)(hjr_tile_id(HJR_WX(c) / HJR_TILE, HJR_WY(c) / HJR_TILE, tiles_x) / world) * 64u + ((HJR_WY(c) & 7u) * 8u + (HJR_WX(c) & 7u))
+                                        : (size_t)HJR_WX(c) + (size_t)HJR_WY(c) * (WIN ? work_w : P.width);
     f3 sumA = c.sumA, sumN = c.sumN;
     if (AOVS && c.aov) { const float4 a = c.aov[0], n = c.aov[1]; sumA = V(a.x, a.y, a.z); sumN = V(n.x, n.y, n.z); }
     if (n_chunks == 1u) { // the item is the whole pixel: mean = chunk sum * (1 / spp)
@@ -356,8 +363,8 @@ template <bool AOVS, bool GROUPS> HD void write_out(const KParams& P, LaneCtx& c
     } else { // chunk sum -> HBM; hjr_finalize_kernel adds the chunks of a pixel in chunk order.  The buffers hold this rank's
              // tiles only: slot = ((chunk * owned tiles) + owned tile index) * 64 + pixel in tile
         // (a sample pass, DESIGN.md §4.4, holds the sums of its own chunks only: the host offsets part_* by -chunk0 chunks)
-        const uint32_t otile = hjr_tile_id(HJR_PX(c) / HJR_TILE, HJR_PY(c) / HJR_TILE, tiles_x) / world;
-        const size_t slot = ((size_t)HJR_CHUNK(c) * HJR_COLD(n_owned_tiles) + otile) * 64u + ((HJR_PY(c) & 7u) * 8u + (HJR_PX(c) & 7u));
+        const uint32_t otile = hjr_tile_id(HJR_WX(c) / HJR_TILE, HJR_WY(c) / HJR_TILE, tiles_x) / world;
+        const size_t slot = ((size_t)HJR_CHUNK(c) * HJR_COLD(n_owned_tiles) + otile) * 64u + ((HJR_WY(c) & 7u) * 8u + (HJR_WX(c) & 7u));
         float4* const part_color = HJR_COLD(part_color);
         part_color[slot] = make_float4(c.sumL.x, c.sumL.y, c.sumL.z, 0.0f);
         if (AOVS) {
@@ -372,13 +379,15 @@ template <bool AOVS, bool GROUPS> HD void write_out(const KParams& P, LaneCtx& c
         c.sumL = V1(0.0f); c.sumA = V1(0.0f); c.sumN = V1(0.0f);
         c.item += 1u << 26;
     }
+#undef HJR_WX
+#undef HJR_WY
 }
 
 // ---- first half of a bounce.  ALL 64 lanes of the wave must call it together (ballots and shuffles inside); `active` is
 // false for lanes that sit this round out (megakernel: lanes whose traversal is carried over; wavefront: lanes without a
 // context).  On return `tracing` says whether the lane has a closest-hit ray to trace (origin: camera if c.fresh, else c.ps.ro;
 // direction c.ps.rd) and c.sh_valid whether a shadow ray (origin c.ps.ro, direction c.sh_d, tmax c.sh_tmax) goes with it.
-template <bool STATS, bool AOVS, bool ONEWRITE = false, bool GROUPS = false>
+template <bool STATS, bool AOVS, bool ONEWRITE = false, bool GROUPS = false, bool WIN = false>
 HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool active, bool& tracing, unsigned long long* lc)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -397,7 +406,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
                     finish_sample<STATS>(P, c, c.ps.L, lc);
                     c.ps.L = V1(0.0f);
                     close_sample<GROUPS>(P, c);
-                    if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
+                    if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS, WIN>(P, c);
                 }
             } else c.ps.thr = c.ps.thr / russian_p;
         }
@@ -408,7 +417,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
     //      bounce_post_trace), so the write-out code (two integer divisions, up to six stores) exists once instead of four times: MIS
     //      192.9 -> 188.2 ms.  Nothing is added to an item's sums after its last sample closed, and the refill below waits for the write.
     //      The megakernel keeps the four in-place writes: there this extra test in every round cost 0.4 - 1 %.
-    if (ONEWRITE && active && c.write_pending && !c.fin_pending) write_out<AOVS, GROUPS>(P, c);
+    if (ONEWRITE && active && c.write_pending && !c.fin_pending) write_out<AOVS, GROUPS, WIN>(P, c);
 
     // ---- ray-queue refill (ballot + mbcnt prefix): idle lanes take consecutive items from the wave's private range
     //      [wr.next, wr.end); when it runs dry the wave fetches the next 64 items with ONE atomic on the global head.
@@ -423,6 +432,10 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             // (item decode: hjr_layout.h::hjr_decode_range; with GROUPS, P.chunk0 / P.item_chunks are resident for close_sample anyway)
             const uint32_t* const tile_order = HJR_COLD(tile_order);
             uint32_t* const tile_cost = HJR_COLD(tile_cost);
+            // render window: the queue, the tile list, the ranges and the tile costs are those of the window's own tile grid; its origin word
+            // (KParams::win_word, wave-uniform) is added where a lane takes an item, so a lane's item word holds full-frame coordinates
+            [[maybe_unused]] uint32_t win_word = 0u, work_w = 0u, work_h = 0u; // (without WIN every expression below is the one it was)
+            if constexpr (WIN) { win_word = HJR_COLD(win_word); work_w = HJR_COLD(work_w); work_h = HJR_COLD(work_h); }
             uint32_t q;
             uint32_t r_item = 0u; // item word of pixel (0, 0) of the range this lane's item comes from
             bool again = false; // shared range only: unserved lanes ask again in their next pass instead of retiring
@@ -463,7 +476,9 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             // case) share one atomic.  All lanes are here (m is wave-uniform), so the shuffles below are well defined.
             if (wr.shared && need && q < n_owned_items) r_item = hjr_decode_range(q & ~63u, pass_chunks, HJR_COLD(chunk0), 1u, tiles_x, world, HJR_COLD(rank), tile_order); // (wavefront kernel: runs of the shared range, decoded per lane)
             if (tile_cost) {
-                const uint32_t old_tile = hjr_tile_id(HJR_PX(c) / HJR_TILE, HJR_PY(c) / HJR_TILE, tiles_x);
+                [[maybe_unused]] const uint32_t old_rel = c.item - win_word; // (a lane that never had an item never flushes)
+                const uint32_t old_tile = WIN ? hjr_tile_id((old_rel & 0x1fffu) / HJR_TILE, ((old_rel >> 13) & 0x1fffu) / HJR_TILE, tiles_x)
+                                              : hjr_tile_id(HJR_PX(c) / HJR_TILE, HJR_PY(c) / HJR_TILE, tiles_x);
                 const uint32_t new_tile = (need && q < n_owned_items) ? hjr_tile_id((r_item & 0x1fffu) / HJR_TILE, ((r_item >> 13) & 0x1fffu) / HJR_TILE, tiles_x) : 0xffffffffu;
                 bool flush = need && c.it_cost != 0u && new_tile != old_tile;
                 while (__ballot(flush)) {
@@ -481,9 +496,9 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
                     // the 64 lanes of a wave start on one tile and one group of sample chunks (coherent primary rays): the range's item word + the pixel in the tile
                     const uint32_t item = hjr_item_word(r_item, q);
                     const uint32_t px = item & 0x1fffu, py = (item >> 13) & 0x1fffu, chunk = item >> 26;
-                    if (px < P.width && py < P.height) {
+                    if (WIN ? (px < work_w && py < work_h) : (px < P.width && py < P.height)) { // inside the work rectangle: the window, or else the frame
                         c.has_item = true; c.path_live = false;
-                        c.item = item;
+                        c.item = WIN ? item + win_word : item;
                         c.s = chunk * P.chunk_spp;
                         c.sumL = V1(0.0f);
                         if (AOVS && c.aov) c.aov[0] = c.aov[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -511,7 +526,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
 // (if c.sh_valid), `h` the closest-hit ray (if tracing).  Lane-private: no cross-lane operation inside.
 // AHEAD (megakernel): the lanes of a wave have hit surfaces of every material class, and the first draws of the BSDF sample are made in
 // front of the material branch (below).  The wavefront kernel shades batches of one class: its samplers draw for themselves.
-template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST, bool ONEWRITE = false, bool GROUPS = false, bool AHEAD = false>
+template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST, bool ONEWRITE = false, bool GROUPS = false, bool AHEAD = false, bool WIN = false>
 HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* tris, const float4* mats, const float4* lights, LaneCtx& c,
                           const bool tracing, const bool occluded, const Hit& h, ST& stack, unsigned long long* lc)
 {
@@ -525,7 +540,7 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
         finish_sample<STATS>(P, c, ps.L, lc, 1u);
         ps.L = V1(0.0f); // from here on ps.L belongs to the path that was regenerated (or to nothing)
         c.fin_pending = false;
-        if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
+        if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS, WIN>(P, c);
     }
     if (!tracing) return;
 
@@ -545,7 +560,7 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
         if (INTEGRATOR == HJR_INTEGRATOR_PT_ || ps.depth == 0) ps.L = ps.L + ps.thr * prd.emission;
         finish_sample<STATS>(P, c, ps.L, lc);
         close_sample<GROUPS>(P, c);
-        if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
+        if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS, WIN>(P, c);
         return;
     }
     CMJState st = path_rng_from_head(P, ps.rng_head, c.s, ps.rng_depth);
@@ -662,7 +677,7 @@ HD void bounce_post_trace(const KParams& P, const float4* nodes, const float4* t
             finish_sample<STATS>(P, c, ps.L, lc);
             ps.L = V1(0.0f);
             close_sample<GROUPS>(P, c);
-            if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS>(P, c);
+            if (!ONEWRITE && c.write_pending) write_out<AOVS, GROUPS, WIN>(P, c);
         }
     }
 }
@@ -724,7 +739,7 @@ HD unsigned long long wave_sum(unsigned long long v)
 // power in the SHADING code, traversal and triangle test unchanged) instantiate FAST = true, the exact ones FAST = false.
 // SINGLE: a launch whose work items are single chunks (KParams::item_chunks == 1: shards, counting and short launches by default, MIS always):
 // the item rule is compiled away, the kernel is the one it was before items could be groups (close_sample).
-template <int INTEGRATOR, bool STATS, int BLOCK, bool LDSBVH, bool STACK16, int WIDTH, int VAR, bool FAST = false, bool SINGLE = false>
+template <int INTEGRATOR, bool STATS, int BLOCK, bool LDSBVH, bool STACK16, int WIDTH, int VAR, bool FAST = false, bool SINGLE = false, bool WIN = false>
 __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_render_kernel(const KParams P)
 {
     constexpr bool AOVS = VAR >= 1, TEX = VAR == 2;
@@ -765,7 +780,7 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
 #ifdef HJR_TIMING
         const bool w_roulette = !inflight && (!HOLD || hold == 0u) && c.has_item && c.path_live;
 #endif
-        bounce_pre_trace<STATS, AOVS, false, !SINGLE>(P, c, wr, !inflight && (!HOLD || hold == 0u), tracing, lc);
+        bounce_pre_trace<STATS, AOVS, false, !SINGLE, WIN>(P, c, wr, !inflight && (!HOLD || hold == 0u), tracing, lc);
         if (__ballot(!c.dead) == 0ull) break; // a lane only dies with nothing pending
         HJR_TICK(0)
 #ifdef HJR_TIMING
@@ -822,7 +837,7 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_rende
 #endif
         if (shade) {
             if (HOLD) hold = 0u;
-            bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, false, !SINGLE, true>(P, nodes, tris, mats, lights, c, tracing, occluded, h, stack, lc);
+            bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, false, !SINGLE, true, WIN>(P, nodes, tris, mats, lights, c, tracing, occluded, h, stack, lc);
         }
         HJR_TICK(2)
     }

@@ -52,6 +52,11 @@ struct BuildKey {
     bool operator==(const BuildKey& o) const { return pack() == o.pack(); }
 };
 
+// hjr_params as the library keeps it: the caller's hjr_params with the render window behind it, the layout of hjr_params_window
+// (include/henjou_hip.h); take_params (hjr_device.hip) fills it from either caller
+struct ParamsW : hjr_params { uint32_t window[4]; };
+static_assert(sizeof(ParamsW) == sizeof(hjr_params_window) && sizeof(hjr_params) % 4 == 0, "ParamsW must have the layout of hjr_params_window");
+
 struct hjr_ctx {
     int device = 0;
     int n_cus = 0;
@@ -89,6 +94,7 @@ struct hjr_ctx {
     uint32_t n_textures = 0;
     int lut_w = 0, lut_h = 0;
     DevBuf d_color, d_albedo, d_normal; // staging for hjr_render (host buffers)
+    DevBuf d_bucket[2]; // hjr_render_file, "bucket": the frame being composed | the bucket being rendered
     DevBuf d_part_color, d_part_albedo, d_part_normal; // chunk sums [pass_chunks][owned tile][64] float4 (colour under rule 10: [n_chunks], kept across the passes of a frame)
     DevBuf d_run_color, d_run_albedo, d_run_normal; // running sums of a frame rendered in sample passes, [owned tile][64] float4
     DevBuf d_stat; // per owned pixel (S1, S2) of such a frame, [owned tile][64] float2; allocated at the first adaptive pass or pass with a variance
@@ -97,6 +103,7 @@ struct hjr_ctx {
     DevBuf d_tiles; // [tile_order | tile_class] of the cost-ordered tile list
     DevBuf d_tile_cost; // measured per-tile cost of the previous frame
     uint64_t cost_tag = 0; // (width, height, spp, rank, world, integrator) the costs belong to; 0 = none
+    uint64_t cost_rect = 0; // ... and the work rectangle (WorkRect::key; 0 = the whole frame)
     uint32_t cost_samples = 0; // samples per pixel of the launch that measured them (a whole frame or a sample pass)
     DevBuf d_dn_a, d_dn_b, d_dn_out; // denoise ping-pong / host-entry staging
     // variance AOV (hjr_render_var) and variance-guided filter (hjr_denoise_var); nothing here is allocated before a call asks for a variance
@@ -113,7 +120,7 @@ struct hjr_ctx {
     // and the frame data generation it was started on
     struct PassSession {
         bool active = false;
-        hjr_params p;
+        ParamsW p;
         uint32_t next = 0, aovs = 0;
         uint64_t gen = 0;
         bool committed = false; // option "adaptive_temporal": the frame ended when its last tile stopped and its history was committed (cleared by the next pass that is enqueued)
@@ -161,6 +168,7 @@ struct LaunchPlan {
     size_t smem = 0;               // dynamic LDS bytes
     bool set_smem = true;          // raise the kernel's dynamic-LDS limit to smem
     bool spill_buf = true;         // reserve d_spill for the stack entries beyond kp.stack_lds_entries
+    bool window = false;           // the launch renders a window: the WIN instantiations, which carry its origin (kp.win_word); single chunks
 };
 
 #ifdef HJR_FAST_MATH
@@ -174,17 +182,17 @@ template <class F> static RenderKernel with_variant(int var, F f)
 {
     return var == 2 ? f(std::integral_constant<int, 2>()) : var == 1 ? f(std::integral_constant<int, 1>()) : f(std::integral_constant<int, 0>());
 }
-template <int I, bool S, bool LDS, int W, int A> static RenderKernel wf_kernel(bool spill)
+template <int I, bool S, bool LDS, int W, int A, bool WIN = false> static RenderKernel wf_kernel(bool spill)
 {
-    return spill ? hjr_wavefront_kernel<I, S, HJR_BLOCK_LDS, LDS, true, W, A> : hjr_wavefront_kernel<I, S, HJR_BLOCK_LDS, LDS, false, W, A>;
+    return spill ? hjr_wavefront_kernel<I, S, HJR_BLOCK_LDS, LDS, true, W, A, WIN> : hjr_wavefront_kernel<I, S, HJR_BLOCK_LDS, LDS, false, W, A, WIN>;
 }
-template <int I, bool S, int A, bool SINGLE> static RenderKernel mega_kernel(int lds_mode)
+template <int I, bool S, int A, bool SINGLE, bool WIN = false> static RenderKernel mega_kernel(int lds_mode)
 {
-    if (lds_mode == 1) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, false, 2, A, HJR_FAST_TAG, SINGLE>;
-    if (lds_mode == 0) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 4, A, HJR_FAST_TAG, SINGLE>;
+    if (lds_mode == 1) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, false, 2, A, HJR_FAST_TAG, SINGLE, WIN>;
+    if (lds_mode == 0) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 4, A, HJR_FAST_TAG, SINGLE, WIN>;
 #ifndef HJR_LEAN_VARIANT
-    if (lds_mode == 2) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, true, 2, A, HJR_FAST_TAG, SINGLE>;
-    if (lds_mode == 3) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 2, A, HJR_FAST_TAG, SINGLE>;
+    if (lds_mode == 2) return hjr_render_kernel<I, S, HJR_BLOCK_LDS, true, true, 2, A, HJR_FAST_TAG, SINGLE, WIN>;
+    if (lds_mode == 3) return hjr_render_kernel<I, S, HJR_BLOCK, false, false, 2, A, HJR_FAST_TAG, SINGLE, WIN>;
 #endif
     return nullptr;
 }
@@ -194,11 +202,20 @@ template <int I, bool S> static RenderKernel pick_kernel(const LaunchPlan& pl)
     return with_variant(pl.var, [&](auto var) -> RenderKernel {
         constexpr int A = decltype(var)::value;
 #if !defined(HJR_FAST_MATH) && !defined(HJR_LEAN_VARIANT)
+        if (pl.wf && pl.window) { // (window launches: the same choice among the WIN instantiations)
+            if (pl.lds_mode == 1 || pl.lds_mode == 2) return wf_kernel<I, S, true, 2, A, true>(pl.wf_spill);
+            if (pl.lds_mode == 3) return wf_kernel<I, S, false, 2, A, true>(pl.wf_spill);
+            return wf_kernel<I, S, false, 4, A, true>(pl.wf_spill);
+        }
         if (pl.wf) {
             if (pl.lds_mode == 1 || pl.lds_mode == 2) return wf_kernel<I, S, true, 2, A>(pl.wf_spill); // stack entries are always 32-bit here
             if (pl.lds_mode == 3) return wf_kernel<I, S, false, 2, A>(pl.wf_spill);
             return wf_kernel<I, S, false, 4, A>(pl.wf_spill);
         }
+#endif
+#ifndef HJR_LEAN_VARIANT
+        // a window launch runs single chunks (hjr_device.hip: launch_render), so the WIN megakernels exist in the SINGLE form only
+        if (pl.window) return mega_kernel<I, S, A, true, true>(pl.lds_mode);
 #endif
         // items of several chunks (kp.item_chunks > 1; NEE and Pathtrace) run the kernels that carry the item rule, every other launch the
         // SINGLE instantiations, which do not (hjr_kernel.hip.h: close_sample)

@@ -27,7 +27,7 @@ struct KParams {
     int lut_w, lut_h;
     int sky_w, sky_h;
     uint32_t n_lights;
-    uint32_t width, height, spp, frame, seed, integrator;
+    uint32_t width, height, spp, frame, seed, integrator; // width, height: the FULL frame's, also under a render window (work_w / work_h below)
     uint32_t tiles_x, n_owned_items; // items of the launch's queue: owned tiles * pass_chunks * 64 single chunks, fewer when the megakernel groups them (hjr_item_count)
     uint32_t rank, world;
     uint32_t packed;                 // HJR_FLAG_PACKED: the AOV buffers hold this rank's tiles only, [owned tile][64] float4
@@ -83,6 +83,12 @@ struct KParams {
     uint32_t* ad_list;               // ... and its stable compaction to the active tiles, which becomes tile_order
     float ad_threshold;              // noise_threshold
     uint32_t ad_decide;              // 1: a stop decision is taken after this pass (sample_end < spp, >= min_samples, >= 2 chunks)
+    // render window (DESIGN.md §4 rule 12; hjr_params_window.window): ray generation and the RNG key use the FULL frame's width / height (above) and
+    // full-frame pixel coordinates, so a window is the crop of the frame; everything else works on the work rectangle's own tile grid.  The render
+    // kernels of a window launch (template parameter WIN) read the three words below cold, next to the other cold parameters of an item's start and
+    // end; the kernels of whole-frame launches do not read them at all
+    uint32_t work_w, work_h;         // extent of the launch's work rectangle, the window or else the frame: the tile grid (tiles_x) and every output are this size
+    uint32_t win_word;               // x0 | y0 << 13, the window's origin (multiples of HJR_TILE) as a WIN kernel adds it to an item word; 0 without a window
 };
 
 // Launch parameters that only the start and the end of a work item need (tile list, queue head, output and chunk-sum pointers, shard

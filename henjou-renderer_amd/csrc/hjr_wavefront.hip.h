@@ -383,7 +383,7 @@ HD void wf_trace_stage(const KParams& P, WfShared* Q, wf_ring_ptr rings, const f
 }
 
 // ---- SHADE stage: up to 64 contexts of one class: second half of the bounce just traced, first half of the next one
-template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST>
+template <int INTEGRATOR, bool STATS, bool AOVS, bool TEX, int WIDTH, int BLOCK, typename ST, bool WIN>
 HD void wf_shade_stage(const KParams& P, WfShared* Q, wf_ring_ptr rings, int q, const float4* nodes, const float4* tris, const float4* mats, const float4* lights,
                        float4* ctx, WaveRange& wr, ST& stack, unsigned long long* lc, unsigned long long* tdiag)
 {
@@ -413,10 +413,10 @@ HD void wf_shade_stage(const KParams& P, WfShared* Q, wf_ring_ptr rings, int q, 
         Hit h;
         h.t = 0.0f; h.b1 = hr.y; h.b2 = hr.z; h.k = kk & 0x7fffffffu; // (the hit distance is not an input of the hit program)
         h.prim = (h.k == WF_MISS) ? 0xffffffffu : f2bits(tris[h.k * HJR_TRI_F4 + 2].y);
-        bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, true>(P, nodes, tris, mats, lights, c, tracing, (kk >> 31) != 0u, h, stack, lc);
+        bounce_post_trace<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, true, false, false, WIN>(P, nodes, tris, mats, lights, c, tracing, (kk >> 31) != 0u, h, stack, lc);
     }
     tracing = false;
-    bounce_pre_trace<STATS, AOVS, true>(P, c, wr, have, tracing, lc); // (ONEWRITE: one write-out site per pass)
+    bounce_pre_trace<STATS, AOVS, true, false, WIN>(P, c, wr, have, tracing, lc); // (ONEWRITE: one write-out site per pass)
     const bool again = have && (tracing || c.sh_valid);
     // no ray, not dead: the item it took lies outside a ragged frame edge; it takes the next one in another pass (class "path ends")
     const bool retry = have && !again && !c.dead;
@@ -433,7 +433,7 @@ HD void wf_shade_stage(const KParams& P, WfShared* Q, wf_ring_ptr rings, int q, 
 // Dynamic LDS: [traversal stacks: stack_lds_entries x BLOCK uint32][scene tables when LDSBVH][WfShared][rings: HJR_WF_QUEUES x wf_cap uint16]
 // SPILL: only the top stack_lds_entries of a lane's traversal stack are in LDS, deeper ones in the HBM overflow buffer (always for the
 // memory layouts; for the LDS-resident layout only when the whole stacks do not fit beside the scene tables and the queues)
-template <int INTEGRATOR, bool STATS, int BLOCK, bool LDSBVH, bool SPILL, int WIDTH, int VAR>
+template <int INTEGRATOR, bool STATS, int BLOCK, bool LDSBVH, bool SPILL, int WIDTH, int VAR, bool WIN = false> // (WIN: as in hjr_render_kernel)
 __global__ void __launch_bounds__(BLOCK, 1) hjr_wavefront_kernel(const KParams P)
 {
     constexpr bool AOVS = VAR >= 1, TEX = VAR == 2; // as in hjr_render_kernel
@@ -525,7 +525,7 @@ __global__ void __launch_bounds__(BLOCK, 1) hjr_wavefront_kernel(const KParams P
         [[maybe_unused]] const unsigned long long t_g0 = WF_NOW();
 
         if (pick == 0u) { wf_trace_stage<STATS, WIDTH, BLOCK, ST>(P, Q, rings, nodes, tris, mats, ctx, stack, lc, tdiag); WF_T(8, 1); WF_T(1, WF_NOW() - t_g0); }
-        else { wf_shade_stage<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST>(P, Q, rings, (int)pick, nodes, tris, mats, lights, ctx, wr, stack, lc, tdiag); WF_T(2, WF_NOW() - t_g0); }
+        else { wf_shade_stage<INTEGRATOR, STATS, AOVS, TEX, WIDTH, BLOCK, ST, WIN>(P, Q, rings, (int)pick, nodes, tris, mats, lights, ctx, wr, stack, lc, tdiag); WF_T(2, WF_NOW() - t_g0); }
     }
 #ifdef HJR_WF_TIMING
     if (lane == 0u) for (int i = 0; i < 19; i++) atomicAdd(&wf_diag[i], tdiag[i]);

@@ -15,6 +15,8 @@ void set_error(const std::string& s);
 // the argument rule of hjr_assemble_shards, hjr_assemble_shards_device and hjr_denoise_shards_device in one place (host/capi.cpp): sizes,
 // alignment, and per AOV "source block and output both or neither"; `s` has been through abi_take
 int check_shards(const hjr_shards& s, uint32_t w, uint32_t h, const void* const out[4], const char* who);
+// the argument rule of hjr_blit_window and hjr_blit_window_device (host/capi.cpp): x0 < x1 <= w and y0 < y1 <= h
+int check_blit_window(const uint32_t window[4], uint32_t w, uint32_t h, const char* who);
 
 inline bool abi_size(const void* user, uint32_t& n, const char* who)
 {

@@ -10,6 +10,7 @@
 #include "../csrc/hjr_layout.h"
 #include "abi.hpp"
 #include "scene.hpp"
+#include "render_job.hpp"
 
 namespace hjr {
 static thread_local std::string g_err;
@@ -43,6 +44,22 @@ extern "C" int hjr_load_render_option(const char* json_path, hjr_render_option* 
     }
     opt.struct_size = (uint32_t)sizeof(opt);
     return hjr::abi_give(out, opt, "hjr_load_render_option") ? HJR_OK : HJR_ERR_ARG; // sized struct: at most out->struct_size bytes are written
+}
+// the same for a caller with hjr_render_option_window (or any shorter struct): the keys "window" and "bucket" are handed out too
+extern "C" int hjr_load_render_option_window(const char* json_path, hjr_render_option* out)
+{
+    if (!json_path || !out) { set_error("hjr_load_render_option_window: null argument"); return HJR_ERR_ARG; }
+    uint32_t n;
+    if (!hjr::abi_size(out, n, "hjr_load_render_option_window")) return HJR_ERR_ARG;
+    std::string err;
+    hjr::RenderOptionW opt;
+    if (!hjr::load_render_option(json_path, opt, err)) {
+        set_error(err);
+        return err.rfind("File ", 0) == 0 ? HJR_ERR_IO : HJR_ERR_PARSE;
+    }
+    opt.struct_size = n; // (abi_give for the long struct: the caller's struct_size stays what it was)
+    memcpy(static_cast<void*>(out), &opt, std::min<size_t>(n, sizeof(opt)));
+    return HJR_OK;
 }
 
 extern "C" int hjr_scene_load_gltf(const char* dir, const char* file, hjr_render_option* opt, hjr_scene** out)
@@ -196,6 +213,44 @@ template <bool PACK> static int tiles_copy(const float* src, float* dst, uint32_
 }
 extern "C" int hjr_pack_tiles(const float* frame, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, float* packed) { return tiles_copy<true>(frame, packed, w, h, rank, world); }
 extern "C" int hjr_unpack_tiles(const float* packed, uint32_t w, uint32_t h, uint32_t rank, uint32_t world, float* frame) { return tiles_copy<false>(packed, frame, w, h, rank, world); }
+
+// ---- buckets and compositing of render windows (include/henjou_hip.h: hjr_params.window)
+static bool bucket_args_ok(uint32_t w, uint32_t h, uint32_t bw, uint32_t bh) { return w && h && bw && bh && bw % HJR_TILE == 0 && bh % HJR_TILE == 0; }
+extern "C" uint32_t hjr_bucket_count(uint32_t w, uint32_t h, uint32_t bw, uint32_t bh)
+{
+    if (!bucket_args_ok(w, h, bw, bh)) return 0;
+    const uint64_t n = (uint64_t)((w - 1u) / bw + 1u) * ((h - 1u) / bh + 1u);
+    return n > 0xffffffffull ? 0u : (uint32_t)n;
+}
+extern "C" int hjr_bucket_window(uint32_t w, uint32_t h, uint32_t bw, uint32_t bh, uint32_t index, uint32_t window[4])
+{
+    if (!window) { set_error("hjr_bucket_window: null argument"); return HJR_ERR_ARG; }
+    if (!bucket_args_ok(w, h, bw, bh)) { set_error("hjr_bucket_window: the frame must not be empty and the bucket sides must be positive multiples of 8"); return HJR_ERR_ARG; }
+    const uint32_t nx = (w - 1u) / bw + 1u, n = hjr_bucket_count(w, h, bw, bh);
+    if (index >= n) { set_error("hjr_bucket_window: bucket index " + std::to_string(index) + " of " + std::to_string(n)); return HJR_ERR_ARG; }
+    const uint32_t bx = index % nx, by = index / nx;
+    window[0] = bx * bw; window[1] = by * bh;
+    window[2] = w - window[0] > bw ? window[0] + bw : w; // (edge buckets are clipped to the frame)
+    window[3] = h - window[1] > bh ? window[1] + bh : h;
+    return HJR_OK;
+}
+namespace hjr {
+// the argument rule of hjr_blit_window and hjr_blit_window_device (csrc/hjr_device.hip)
+int check_blit_window(const uint32_t window[4], uint32_t w, uint32_t h, const char* who)
+{
+    if (window[0] < window[2] && window[2] <= w && window[1] < window[3] && window[3] <= h) return HJR_OK;
+    set_error(std::string(who) + ": window needs x0 < x1 <= width and y0 < y1 <= height");
+    return HJR_ERR_ARG;
+}
+} // namespace hjr
+extern "C" int hjr_blit_window(const float* win, const uint32_t window[4], float* frame, uint32_t w, uint32_t h)
+{
+    if (!win || !window || !frame) { set_error("hjr_blit_window: null argument"); return HJR_ERR_ARG; }
+    if (const int rc = hjr::check_blit_window(window, w, h, "hjr_blit_window")) return rc;
+    const uint32_t ww = window[2] - window[0], wh = window[3] - window[1];
+    for (uint32_t y = 0; y < wh; y++) memcpy(frame + ((size_t)(window[1] + y) * w + window[0]) * 4, win + (size_t)y * ww * 4, (size_t)ww * 16);
+    return HJR_OK;
+}
 
 // ---- gathered shards -> frames (include/henjou_hip.h, DESIGN.md §7 "Denoise modes").  The argument rule of hjr_assemble_shards and
 // hjr_assemble_shards_device (csrc/hjr_device.hip) in one place: sizes, alignment, and per AOV "source and output both or neither".

@@ -76,6 +76,13 @@ static void parse_key(const Json& h, const KeyRow& r, hjr_render_option& o)
 
 bool load_render_option(const std::string& path, hjr_render_option& o, std::string& err)
 {
+    RenderOptionW w; // (the two keys of the render window are checked and dropped: this caller's struct has no room for them)
+    const bool ok = load_render_option(path, w, err);
+    o = w;
+    return ok;
+}
+bool load_render_option(const std::string& path, RenderOptionW& o, std::string& err)
+{
     memset(&o, 0, sizeof(o));
     o.camera_animation_id = -1;
     o.seed = 1;
@@ -174,6 +181,27 @@ bool load_render_option(const std::string& path, hjr_render_option& o, std::stri
                 if (o.noise_threshold > 0.0f && !h->find("passes")) o.passes = 8;
             }
             if (const Json* v = h->find("min_samples")) o.min_samples = (uint32_t)int_in(*v, "Henjou_HIP.min_samples", 0, 1048576);
+            // window / bucket: the render window of every frame, and frames rendered bucket by bucket (hjr_params.window, hjr_bucket_window).
+            // Read behind every other key, so a file without them reports what it always did
+            if (const Json* v = h->find("window")) {
+                const char* want = "Henjou_HIP.window must be [x0, y0, x1, y1]: four integers in [0, 8192] with x0 < x1, y0 < y1 and x0, y0 multiples of 8";
+                if (!v->is_array() || v->size() != 4) throw JsonError(want);
+                for (size_t k = 0; k < 4; k++) {
+                    const double n = v->at(k).is_number() ? v->at(k).as_number() : -1.0;
+                    if (!(n >= 0.0 && n <= 8192.0) || n != (double)(uint32_t)n) throw JsonError(want);
+                    o.window[k] = (uint32_t)n;
+                }
+                if (o.window[0] >= o.window[2] || o.window[1] >= o.window[3] || o.window[0] % 8u || o.window[1] % 8u) throw JsonError(want);
+            }
+            if (const Json* v = h->find("bucket")) {
+                const char* want = "Henjou_HIP.bucket must be [bw, bh]: two positive multiples of 8, at most 8192";
+                if (!v->is_array() || v->size() != 2) throw JsonError(want);
+                for (size_t k = 0; k < 2; k++) {
+                    const double n = v->at(k).is_number() ? v->at(k).as_number() : -1.0;
+                    if (!(n >= 8.0 && n <= 8192.0) || n != (double)(uint32_t)n || (uint32_t)n % 8u) throw JsonError(want);
+                    o.bucket[k] = (uint32_t)n;
+                }
+            }
         }
     } catch (std::exception& e) { // :222-225
         err = std::string("Caught exception: ") + e.what();

@@ -16,6 +16,10 @@ namespace hjr {
 void set_error(const std::string& s);
 bool write_png(const std::string& path, const uint8_t* rgba, uint32_t w, uint32_t h, bool flip_y, std::string& err);
 void float4_to_srgb8(const float* rgba, uint8_t* out, uint32_t n);
+// "bucket" (csrc/hjr_device.hip): two buffers of the context for a bucketed frame, slot 0 the frame and slot 1 a bucket, and the frame's one
+// download on the context's stream (synchronous)
+int bucket_buffer(hjr_ctx* c, int slot, size_t bytes, void** d_out);
+int bucket_download(hjr_ctx* c, float* host, const void* d_frame, size_t bytes);
 } // namespace hjr
 using hjr::set_error;
 
@@ -25,9 +29,10 @@ using hjr::set_error;
 extern "C" int hjr_render_file(const char* render_option_json, int device)
 {
     if (!render_option_json) { set_error("hjr_render_file: null path"); return HJR_ERR_ARG; }
-    hjr_render_option opt;
-    HJR_INIT(opt);
-    int rc = hjr_load_render_option(render_option_json, &opt);
+    hjr::RenderOptionW opt; // (the long form: "window" and "bucket" behind hjr_render_option)
+    memset(static_cast<void*>(&opt), 0, sizeof(opt));
+    opt.struct_size = (uint32_t)sizeof(opt);
+    int rc = hjr_load_render_option_window(render_option_json, &opt);
     if (rc != HJR_OK) return rc;
     hjr::Job job; // the refusals come before the scene and the device (host/render_job.hpp)
     std::string refusal;
@@ -47,7 +52,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (rc == HJR_OK && adaptive) rc = hjr::set_adaptive(ctx, opt);
     if (rc == HJR_OK) rc = hjr::upload_assets(ctx, opt, view, true);
     std::vector<float> m((size_t)view.n_instances * 12), inv((size_t)view.n_instances * 12);
-    const size_t npx = (size_t)opt.image_width * opt.image_height;
+    const size_t npx = (size_t)job.out_w * job.out_h; // (the window's size with "window")
     // Output stage off the critical path: float4 -> sRGB8 -> PNG -> file runs on a writer thread while the main thread
     // already builds and renders the next frame (two frame buffers in rotation).  The reference's loop is serial
     // (renderer.h:1281-1302); the files are the same.  Only aov_color is produced: Default mode never reads the albedo /
@@ -65,7 +70,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
         std::vector<uint8_t> rgba8(npx * 4);
         hjr::float4_to_srgb8(sl.color.data(), rgba8.data(), (uint32_t)npx);
         std::string err;
-        if (!hjr::write_png(sl.name, rgba8.data(), opt.image_width, opt.image_height, true, err)) {
+        if (!hjr::write_png(sl.name, rgba8.data(), job.out_w, job.out_h, true, err)) {
             std::lock_guard<std::mutex> lk(mu);
             write_err = err;
             return HJR_ERR_IO;
@@ -113,9 +118,13 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
         rc = hjr_commit_transforms(ctx);
         if (rc != HJR_OK) break;
         if (frame + 1 < opt.end_frame && !serial_io) prep = std::thread(prepare, frame + 1);
-        hjr_params p;
-        rc = hjr::frame_params(opt, scene, frame, job.w, job.h, p);
+        hjr_params_window pw; // (the longer caller: the render window behind hjr_params)
+        memset(&pw, 0, sizeof(pw));
+        hjr_params& p = pw.p;
+        rc = hjr::frame_params(opt, scene, frame, job.frame_w, job.frame_h, p);
         if (rc != HJR_OK) break;
+        p.struct_size = (uint32_t)sizeof(pw);
+        if (job.win) memcpy(pw.window, opt.window, sizeof(pw.window)); // "window": every launch of the frame renders that rectangle
         Slot& sl = slots[cur];
         if (!serial_io) { // the slot may still be with the writer (two frames behind)
             std::unique_lock<std::mutex> lk(mu);
@@ -129,7 +138,41 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
         size_t n_done = 0;
         hjr_adaptive_state as;
         HJR_INIT(as);
-        for (size_t k = 0; rc == HJR_OK && k < ends.size(); k++) {
+        // "bucket": the frame (the window, when there is one) bucket by bucket.  A bucket goes through all its sample passes, adaptive stop
+        // included, into a bucket-sized device buffer and is then written into the frame on the device; the frame comes down once.  Every
+        // buffer the context keeps for a launch (chunk sums, running sums, adaptive state) has the bucket's size.
+        const uint32_t n_buckets = opt.bucket[0] ? hjr_bucket_count(job.w, job.h, opt.bucket[0], opt.bucket[1]) : 0u;
+        void *d_frame = nullptr, *d_bucket = nullptr;
+        if (n_buckets) rc = hjr::bucket_buffer(ctx, 0, npx * 16, &d_frame);
+        for (uint32_t b = 0; rc == HJR_OK && b < n_buckets; b++) {
+            uint32_t rel[4]; // the bucket inside the job's rectangle; + its origin: the launch's window
+            rc = hjr_bucket_window(job.w, job.h, opt.bucket[0], opt.bucket[1], b, rel);
+            if (rc != HJR_OK) break;
+            hjr_params_window pb = pw;
+            pb.window[0] = job.x0 + rel[0]; pb.window[1] = job.y0 + rel[1]; pb.window[2] = job.x0 + rel[2]; pb.window[3] = job.y0 + rel[3];
+            rc = hjr::bucket_buffer(ctx, 1, (size_t)(rel[2] - rel[0]) * (rel[3] - rel[1]) * 16, &d_bucket);
+            for (size_t k = 0; rc == HJR_OK && k < ends.size(); k++) {
+                if (ends.size() > 1) { pb.p.sample_begin = k ? ends[k - 1] : 0u; pb.p.sample_end = ends[k]; }
+                rc = hjr_render_device(ctx, &pb.p, d_bucket, nullptr, nullptr, nullptr);
+                if (rc != HJR_OK) break;
+                hjr_stats st;
+                HJR_INIT(st);
+                if (hjr_get_stats(ctx, &st) == HJR_OK) kernel_ms += st.last_kernel_ms;
+                if (k + 1 > n_done) n_done = k + 1; // (the note: the most passes any bucket of the frame took)
+                if (rc == HJR_OK && adaptive && ends.size() > 1) {
+                    hjr_adaptive_state ab;
+                    HJR_INIT(ab);
+                    rc = hjr_get_adaptive_state(ctx, &ab);
+                    if (rc != HJR_OK) break;
+                    const bool over = ab.active_tiles == 0 || k + 1 == ends.size();
+                    if (over) { as.owned_tiles += ab.owned_tiles; as.active_tiles += ab.active_tiles; as.samples_rendered += ab.samples_rendered; if (ab.sample_end > as.sample_end) as.sample_end = ab.sample_end; } // (tiles and samples of all buckets; the latest pass end of any)
+                    if (ab.active_tiles == 0) break;
+                }
+            }
+            if (rc == HJR_OK) rc = hjr_blit_window_device(ctx, d_bucket, rel, d_frame, job.w, job.h, nullptr);
+        }
+        if (rc == HJR_OK && n_buckets) rc = hjr::bucket_download(ctx, sl.color.data(), d_frame, npx * 16);
+        for (size_t k = 0; rc == HJR_OK && !n_buckets && k < ends.size(); k++) {
             if (ends.size() > 1) { p.sample_begin = k ? ends[k - 1] : 0u; p.sample_end = ends[k]; }
             if (opt.render_mode == HJR_MODE_DEFAULT) rc = hjr_render(ctx, &p, sl.color.data(), nullptr, nullptr);
             else rc = hjr_render_denoised(ctx, &p, opt.render_mode, sl.color.data(), opt.image_width, opt.image_height); // renderer.h:1258-1281
@@ -143,12 +186,13 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
             }
         }
         if (rc != HJR_OK) break;
-        std::string note = ends.size() > 1 ? ", " + std::to_string(n_done) + " sample passes" : "";
+        std::string note = ends.size() > 1 ? ", " + std::to_string(n_done) + " sample passes" + (n_buckets ? " at most per bucket" : "") : "";
         if (adaptive && ends.size() > 1)
             note += ", adaptive: " + std::to_string(as.active_tiles) + " of " + std::to_string(as.owned_tiles) + " tiles active at " + std::to_string(as.sample_end) + " spp, " +
                     std::to_string(as.samples_rendered) + " samples rendered";
-        fprintf(stderr, "[henjou] frame %u: %ux%u, %u spp, kernel %.3f ms (%.2f Msamples/s)%s\n", frame, p.width, p.height, p.spp,
-                kernel_ms, kernel_ms > 0 ? (double)p.width * p.height * p.spp / (kernel_ms * 1e3) : 0.0, note.c_str());
+        if (n_buckets) note += ", " + std::to_string(n_buckets) + " buckets";
+        fprintf(stderr, "[henjou] frame %u: %ux%u, %u spp, kernel %.3f ms (%.2f Msamples/s)%s\n", frame, job.w, job.h, p.spp,
+                kernel_ms, kernel_ms > 0 ? (double)job.w * job.h * p.spp / (kernel_ms * 1e3) : 0.0, note.c_str());
         sl.name = hjr::frame_png_name(opt, frame);
         n_frames++;
         if (serial_io) { rc = write_slot(sl); if (rc != HJR_OK) set_error(write_err); if (rc == HJR_OK && frame + 1 < opt.end_frame) prepare(frame + 1); }

@@ -12,6 +12,21 @@
 
 namespace hjr {
 
+// hjr_render_option as the drivers and the parser keep it: the caller's struct with the render window's two keys behind it, the layout of
+// hjr_render_option_window (include/henjou_hip.h).  hjr_load_render_option_window fills it; the functions below that take the short struct
+// see no window and no bucket.
+struct RenderOptionW : hjr_render_option { uint32_t window[4]; uint32_t bucket[2]; };
+static_assert(sizeof(RenderOptionW) == sizeof(hjr_render_option_window), "RenderOptionW must have the layout of hjr_render_option_window");
+inline RenderOptionW with_no_window(const hjr_render_option& o)
+{
+    RenderOptionW w;
+    memset(static_cast<void*>(&w), 0, sizeof(w));
+    static_cast<hjr_render_option&>(w) = o;
+    return w;
+}
+// the parser (host/loaders.cpp)
+bool load_render_option(const std::string& path, RenderOptionW& opt, std::string& err);
+
 enum KeyEnc : uint8_t {
     ENC_BITS,    // `width` bits at `shift` of the field
     ENC_NONZERO, // the whole field: 0 / 1 when written, any non-zero value reads as 1 (a later row of the field may raise it)
@@ -135,10 +150,13 @@ template <typename Fn> int for_each_option(const hjr_render_option& o, JobScope 
 struct Job {
     bool denoise, with_var, temporal, adaptive; // a Denoise mode; ... with the variance AOV; ... with temporal accumulation; "noise_threshold" asked for
     int firefly;                                // kappa of "firefly_clamp"
-    uint32_t w, h, out_w, out_h;                // render size (half the output in DenoiseUpScale2X, renderer.h:1089-1099); the PNG's size
+    uint32_t w, h, out_w, out_h;                // render size (half the output in DenoiseUpScale2X, renderer.h:1089-1099); the PNG's size.  With
+                                                // "window" both are the window's size ...
+    bool win;                                   // ... this is set and (x0, y0) is the window's origin in the frame of frame_w x frame_h pixels
+    uint32_t x0, y0, frame_w, frame_h;
 };
 // fills `job`; false with the refusal in `text` (the caller puts its own name in front), all before a scene or a device is touched
-inline bool job_check(const hjr_render_option& o, Job& job, std::string& text)
+inline bool job_check(const RenderOptionW& o, Job& job, std::string& text)
 {
     job.denoise = o.render_mode != HJR_MODE_DEFAULT;
     job.with_var = job.denoise && key_get(o, key_row("denoise_variance"));
@@ -148,6 +166,7 @@ inline bool job_check(const hjr_render_option& o, Job& job, std::string& text)
     const bool half = o.render_mode == HJR_MODE_DENOISE_UPSCALE2X;
     job.out_w = o.image_width; job.out_h = o.image_height;
     job.w = half ? job.out_w / 2u : job.out_w; job.h = half ? job.out_h / 2u : job.out_h;
+    job.frame_w = job.w; job.frame_h = job.h; job.win = false; job.x0 = job.y0 = 0u;
     if (o.render_mode != HJR_MODE_DEFAULT && o.render_mode != HJR_MODE_DENOISE && o.render_mode != HJR_MODE_DENOISE_UPSCALE2X)
         text = "Render_mode must be Default, Denoise or DenoiseUpScale2X (Debug is declared but unused by the reference)";
     else if (job.temporal && job.adaptive && !key_get(o, key_row("adaptive_temporal"))) // with the key the pass that stops the last tile commits the history (rule 11)
@@ -156,17 +175,37 @@ inline bool job_check(const hjr_render_option& o, Job& job, std::string& text)
         text = "\"firefly_clamp\" cannot be combined with \"passes\" > 1 or \"noise_threshold\": the clamp needs every chunk sum of a pixel, and a frame rendered in sample passes keeps running sums only";
     else if (job.w == 0 || job.h == 0)
         text = "image too small for DenoiseUpScale2X";
-    else return true;
+    else if (job.denoise && (o.window[2] || o.bucket[0])) // the filters read the pixels around a window
+        text = "\"window\" and \"bucket\" need Render_mode Default: the Denoise modes filter whole frames";
+    else if (key_get(o, key_row("adaptive_temporal")) && (o.window[2] || o.bucket[0]))
+        text = "\"adaptive_temporal\" cannot be combined with \"window\" or \"bucket\": its prior is gathered over the whole frame";
+    else if (o.window[2] > job.w || o.window[3] > job.h)
+        text = "\"window\" reaches outside the " + std::to_string(job.w) + " x " + std::to_string(job.h) + " image";
+    else {
+        // the rectangle the job renders and writes: the window, or else the frame
+        job.win = o.window[2] != 0u;
+        job.x0 = job.win ? o.window[0] : 0u; job.y0 = job.win ? o.window[1] : 0u;
+        if (job.win) { job.w = o.window[2] - o.window[0]; job.h = o.window[3] - o.window[1]; job.out_w = job.w; job.out_h = job.h; }
+        return true;
+    }
     return false;
 }
 
+inline bool job_check(const hjr_render_option& o, Job& job, std::string& text) { return job_check(with_no_window(o), job, text); }
+
 // what a job of several ranks (henjou_cli --devices N > 1) cannot do and one process can; true with the refusal in `text`
-inline bool multi_gpu_refusal(const hjr_render_option& o, std::string& text)
+inline bool multi_gpu_refusal(const RenderOptionW& o, std::string& text)
 {
+    if (o.bucket[0]) {
+        text = "\"bucket\" cannot be combined with \"devices\" > 1: buckets are composed on the one device that renders them";
+        return true;
+    }
     if (!key_get(o, key_row("adaptive_temporal"))) return false;
     text = "\"adaptive_temporal\" cannot be combined with \"devices\" > 1: every rank takes the stop decisions of its own shard without the temporal history, which only rank 0 keeps";
     return true;
 }
+
+inline bool multi_gpu_refusal(const hjr_render_option& o, std::string& text) { return multi_gpu_refusal(with_no_window(o), text); }
 
 // sample-pass ends of a frame of spp samples in n passes ("Henjou_HIP": {"passes": n}): k * spp / n rounded down to the granule, the last one
 // spp; passes that come out empty are dropped, so a frame never has more passes than chunks

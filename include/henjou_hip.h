@@ -157,6 +157,21 @@ typedef struct hjr_render_option {
     int32_t denoise_variance;    /* default 0; 1: key "denoise_variance" (the variance-guided filter in Render_mode Denoise /
                                   * DenoiseUpScale2X; ignored in Default); 2: that and key "denoise_temporal" */
 } hjr_render_option;
+/* hjr_render_option with the render window's keys behind it: the LONGER caller of the sized-struct rule.  hjr_render_option itself keeps its
+ * size (callers and tools were built against it); a caller that wants the two keys hands `&w.o` of this struct, with
+ * w.o.struct_size = sizeof(hjr_render_option_window) (HJR_INIT_WINDOW), to hjr_load_render_option_window. */
+typedef struct hjr_render_option_window {
+    hjr_render_option o;
+    uint32_t window[4];          /* default 0, 0, 0, 0 (x1 == 0: the whole frame); key "window": [x0, y0, x1, y1], the render window of every frame
+                                  * (hjr_params_window.window: full-frame pixels, row 0 at the bottom, x0 and y0 multiples of 8).  hjr_render_file /
+                                  * henjou_cli then write PNGs of the window's size: the window's rows and columns of the whole frame's PNG.
+                                  * Render_mode Default only */
+    uint32_t bucket[2];          /* default 0, 0 (off); key "bucket": [bw, bh], positive multiples of 8: hjr_render_file / henjou_cli render every
+                                  * frame (the window, when there is one) bucket by bucket (hjr_bucket_window), compose it on the device
+                                  * (hjr_blit_window_device) and download it once; the PNG is unchanged, per-frame chunk-sum memory follows the
+                                  * bucket.  Render_mode Default, one process ("devices" 1) */
+} hjr_render_option_window;
+#define HJR_INIT_WINDOW(s, head) do { memset(&(s), 0, sizeof(s)); (s).head.struct_size = (uint32_t)sizeof(s); } while (0) /* head: o or p */
 
 typedef struct hjr_camera {      /* Params.camera_* (renderer/renderer.h:1187-1191) */
     float pos[3], dir[3], up[3], right[3];
@@ -178,6 +193,29 @@ typedef struct hjr_params {
     uint32_t flags;              /* HJR_FLAG_* */
     uint32_t sample_begin, sample_end; /* sample pass of a progressive frame (below); sample_end 0 = the whole frame */
 } hjr_params;
+/* hjr_params with the render window behind sample_end: the LONGER caller of the sized-struct rule.  hjr_params itself keeps its size; a caller
+ * that renders a window hands `&w.p` of this struct, with w.p.struct_size = sizeof(hjr_params_window) (HJR_INIT_WINDOW(w, p)), to any entry
+ * point that takes a const hjr_params*.  The library reads the four words behind the hjr_params it knows iff struct_size covers them. */
+typedef struct hjr_params_window {
+    hjr_params p;
+    uint32_t window[4];          /* x0, y0, x1, y1: render window (below); x1 == 0 = the whole frame */
+} hjr_params_window;
+/* ---- Render window: the pixels of one rectangle of the frame (hjr_params_window.window; DESIGN.md §4 rule 12) ----------------------------
+ * window = { x0, y0, x1, y1 }, a half-open rectangle [x0, x1) x [y0, y1) in the kernel's pixel coordinates (row 0 at the bottom, as
+ * everywhere).  x1 == 0 (what a plain hjr_params reads as) is the whole frame: that launch is the launch it always was, bit for bit.
+ * width and height remain the FULL frame.  A pixel's value depends on its full-frame coordinates, the sample number, the seed and spp only,
+ * so a window launch writes the crop of the whole-frame launch, bit for bit, in every AOV.
+ * Conditions, else HJR_ERR_ARG with a text that names `window`, and nothing is enqueued or written: x0 < x1 <= width, y0 < y1 <= height, and
+ * x0 and y0 multiples of 8 (the window's 8x8 tiles are then tiles of the frame, which the adaptive rule needs); x1 and y1 are free.
+ * Every output of a window launch, host or device, is WINDOW-sized: (y1 - y0) x (x1 - x0) elements, row-major, window row 0 first; with
+ * HJR_FLAG_PACKED hjr_owned_tiles(x1 - x0, y1 - y0, rank, world_size) x 64 elements on the window's own tile grid.  rank / world_size shard
+ * the window's tiles; hjr_get_adaptive_state and hjr_copy_tile_samples speak of the window's tiles.
+ * hjr_render[_var] and hjr_render_device[_var] take a window: both kernel families, all integrators, every flag, sample passes, adaptive
+ * sampling and both firefly options.  The window is one of the things a continuing sample pass must repeat (else HJR_ERR_STATE).
+ * hjr_stats.samples counts window pixels x samples; nan_where stays in full-frame coordinates.  Nothing the context keeps between launches
+ * (measured tile costs, adaptive state, running sums, kept chunk sums) is used for another window: pixel bits never depend on what was
+ * rendered before.  The filters need neighbours outside the window: hjr_render_denoised, hjr_render_gbuffer*, hjr_denoise_shards_device and
+ * any render on a context with option "adaptive_temporal" on refuse a window with HJR_ERR_ARG. */
 /* ---- Rendering one frame in sample passes (progressive rendering) ------------------------------------------------
  * sample_end == 0 (what an older, shorter hjr_params reads as), or sample_begin == 0 with sample_end == spp: the whole frame in one launch.
  * Otherwise the call renders samples [sample_begin, sample_end) of the spp-sample frame and writes, to every AOV it is given, the running
@@ -356,6 +394,10 @@ const char* hjr_last_error(void);
 /* load_json(filepath, RenderOption&) — loader/render_json_loader.h:78-228 (incl. ./fps.txt override, :164-171).
  * `out` must carry its struct_size (HJR_INIT) before the call, like every sized struct. */
 int hjr_load_render_option(const char* json_path, hjr_render_option* out);
+/* the same with the keys "window" and "bucket" of the "Henjou_HIP" section: `out` is the `o` of a hjr_render_option_window whose struct_size
+ * covers the fields it wants (a shorter struct receives what fits, as ever).  hjr_load_render_option checks the two keys and hands out
+ * hjr_render_option only: it never writes behind sizeof(hjr_render_option). */
+int hjr_load_render_option_window(const char* json_path, hjr_render_option* out);
 /* gltfloader(filepath, filename, SceneData&, RenderOption&) — loader/gltfloader.h:1068-1601 */
 int hjr_scene_load_gltf(const char* dir, const char* file, hjr_render_option* opt_inout, hjr_scene** out);
 void hjr_scene_free(hjr_scene*);
@@ -428,7 +470,19 @@ int hjr_unpack_tiles(const float* packed_rgba, uint32_t width, uint32_t height, 
 /* the same on device pointers, asynchronous on `hip_stream` (NULL = the context's stream) */
 int hjr_pack_tiles_device(hjr_ctx*, const void* d_frame, uint32_t width, uint32_t height, uint32_t rank, uint32_t world_size, void* d_packed, void* hip_stream);
 int hjr_unpack_tiles_device(hjr_ctx*, const void* d_packed, uint32_t width, uint32_t height, uint32_t rank, uint32_t world_size, void* d_frame, void* hip_stream);
-/* ---- gathered shards -> frames (DESIGN.md §7 "Denoise modes").  What rank 0 holds after the one gather of a frame: world_size blocks, one per
+/* ---- buckets and compositing of render windows (hjr_params_window.window).  Buckets cut a width x height frame into bw x bh rectangles, row-major
+ * from (0, 0), the ones at the right and top edge clipped to the frame; bw and bh are positive multiples of 8, so every bucket is a valid
+ * window.  hjr_bucket_count: how many (0 for a bad argument).  hjr_bucket_window: bucket `index` as { x0, y0, x1, y1 }; HJR_ERR_ARG for an
+ * empty frame, a side that is not a positive multiple of 8, or an index past the end.  Host only, no GPU needed. */
+uint32_t hjr_bucket_count(uint32_t width, uint32_t height, uint32_t bw, uint32_t bh);
+int hjr_bucket_window(uint32_t width, uint32_t height, uint32_t bw, uint32_t bh, uint32_t index, uint32_t window[4]);
+/* window pixels -> frame: the (y1 - y0) x (x1 - x0) float4 image of a window launch is written into rows y0 .. y1 - 1, columns x0 .. x1 - 1 of
+ * a width x height float4 frame; the frame's other pixels are untouched.  HJR_ERR_ARG unless x0 < x1 <= width and y0 < y1 <= height (any
+ * alignment).  Host form: host pointers, needs no context.  Device form: device pointers, one kernel launch, asynchronous on `hip_stream`
+ * (NULL = the context's stream). */
+int hjr_blit_window(const float* window_rgba, const uint32_t window[4], float* frame_rgba, uint32_t width, uint32_t height);
+int hjr_blit_window_device(hjr_ctx*, const void* d_window, const uint32_t window[4], void* d_frame, uint32_t width, uint32_t height, void* hip_stream);
+/* ---- gathered shards -> frames (DESIGN.md §7 "Denoise modes"). What rank 0 holds after the one gather of a frame: world_size blocks, one per
  * rank, rank r's at byte offset r * rank_stride from each of up to four base pointers (rank 0's packed AOVs): colour, albedo and normal as
  * [owned tile][64] float4, the variance AOV as [owned tile][64] float; NULL = absent.  One gather of a per-rank buffer laid out
  * colour | albedo | normal | variance yields exactly this: the pointers are offsets into rank 0's block and rank_stride is the size of the
