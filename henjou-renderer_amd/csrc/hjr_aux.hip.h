@@ -1,18 +1,7 @@
-// The small kernels around the render kernels: cost-ordered tile list, chunk-sum finalisation, tile packing for the multi-GPU gather.
-// Included by hjr_device.hip only (non-template __global__ functions: one translation unit).
+// The small kernels around the render kernels: cost-ordered tile list, chunk-sum finalisation, firefly clamp, adaptive sampling's rule 11
+// and tile filter.  Included by hjr_render.hip only (non-template __global__ functions: one translation unit).
 #pragma once
-#include "hjr_kernel.hip.h"
-
-// the stack of a lane of a one-wave workgroup that traces pixel-centre rays against the frame data in memory (the tile classifier, the G-buffer
-// pass): the lane's whole column in dynamic LDS, no overflow buffer, no staged tree top
-typedef LaneStack<uint32_t, 64, false> TileStack;
-__device__ __forceinline__ TileStack hjr_tile_stack()
-{
-    TileStack stack;
-    stack.lds = reinterpret_cast<uint32_t*>(hjr_smem) + threadIdx.x;
-    stack.spill = nullptr; stack.spill_stride = 0; stack.lds_n = 0; stack.n_over = 0; stack.top = nullptr; stack.n_top = 0u;
-    return stack;
-}
+#include "hjr_traverse.hip.h"
 
 // ---- cost-ordered tile list.  The frame ends when the slowest work item ends, and an item (8 samples of one pixel, each up
 // to 10 bounces, strictly sequential) can run for milliseconds: with plain scanline order the tail of the launch is whatever
@@ -115,17 +104,6 @@ __global__ void __launch_bounds__(256) hjr_cost_scatter_kernel(const KParams P)
     }
     __syncthreads();
     if (live) P.tile_order_w[base[b] + rank_in_block] = idx * P.world + P.rank;
-}
-
-// ---- slot -> pixel.  Everything behind the render kernels is laid out [owned tile][64]: slot sl is pixel (sl & 7, (sl >> 3) & 7) of
-// this rank's owned tile sl >> 6.  Returns whether the pixel lies inside the image (edge tiles are partial).
-__device__ inline bool hjr_slot_xy(size_t sl, uint32_t rank, uint32_t world, uint32_t tiles_x, uint32_t width, uint32_t height, uint32_t* x, uint32_t* y)
-{
-    uint32_t tx, ty;
-    hjr_tile_xy((uint32_t)(sl >> 6) * world + rank, tiles_x, &tx, &ty);
-    *x = tx * HJR_TILE + ((uint32_t)sl & 7u);
-    *y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
-    return *x < width && *y < height;
 }
 
 // variance of a pixel's mean from the statistic of its chunk sums (DESIGN.md §4 rule 7)
@@ -407,98 +385,3 @@ __global__ void __launch_bounds__(1024) hjr_filter_tiles_kernel(const KParams P)
         __syncthreads(); // wave_n is rewritten by the next step
     }
 }
-
-// ---- tile pack / unpack: the multi-GPU exchange moves only owned tiles ([owned tile][64] float4)
-__global__ void __launch_bounds__(256) hjr_pack_tiles_kernel(const float4* frame, float4* packed, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_owned, uint32_t rank, uint32_t world)
-{
-    const size_t sl = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (sl >= (size_t)n_owned * 64u) return;
-    uint32_t x, y;
-    const bool inside = hjr_slot_xy(sl, rank, world, tiles_x, width, height, &x, &y);
-    packed[sl] = inside ? frame[(size_t)y * width + x] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-__global__ void __launch_bounds__(256) hjr_unpack_tiles_kernel(const float4* packed, float4* frame, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_owned, uint32_t rank, uint32_t world)
-{
-    const size_t sl = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (sl >= (size_t)n_owned * 64u) return;
-    uint32_t x, y;
-    if (hjr_slot_xy(sl, rank, world, tiles_x, width, height, &x, &y)) frame[(size_t)y * width + x] = packed[sl];
-}
-
-// ---- window pixels -> frame (hjr_blit_window_device): the float4 image of a render window, (y1 - y0) x (x1 - x0) row-major, goes into its
-// rectangle of a full-size frame.  256 threads take 64 x 4 window pixels (image_grid); the frame's other pixels are not touched.
-__global__ void __launch_bounds__(256) hjr_blit_window_kernel(const float4* __restrict__ win, float4* __restrict__ frame, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t frame_w)
-{
-    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    frame[(size_t)(y0 + y) * frame_w + (x0 + x)] = win[(size_t)y * w + x];
-}
-
-// ---- gathered shards -> frames (hjr_assemble_shards_device; DESIGN.md §7 "Denoise modes").  After the one gather of a multi-GPU frame rank 0
-// holds `world` blocks, rank r's at byte offset r * rank_stride from each base pointer: up to three float4 AOVs and the one-float variance AOV,
-// each [owned tile][64].  One launch scatters all of them: the inverse of hjr_slot_xy for every rank at once.  One lane per frame pixel, a wave
-// per 8 x 8 tile (lane = slot within the tile), so a wave reads 1 KiB (256 B of variance) contiguous and writes 8 rows of 128 B (32 B).  The
-// owner and the slot are arithmetic on the tile id (csrc/hjr_layout.h): tile t is rank t % world's (t / world)-th tile.  Lanes of an edge tile
-// outside the image have no pixel and read nothing; padding behind a rank's last tile is never addressed (t < n_tiles).  Null = absent AOV.
-struct ShardArgs {
-    const char *color, *albedo, *normal, *variance; // rank 0's blocks
-    float4 *out_color, *out_albedo, *out_normal;    // row-major frames
-    float* out_variance;
-    unsigned long long rank_stride;                 // bytes between the blocks of consecutive ranks
-    uint32_t width, height, tiles_x, world;
-};
-__global__ void __launch_bounds__(256) hjr_assemble_shards_kernel(const ShardArgs a)
-{
-    const uint32_t lane = threadIdx.x & 63u, tx = blockIdx.x * 4u + (threadIdx.x >> 6), ty = blockIdx.y;
-    const uint32_t x = tx * HJR_TILE + (lane & 7u), y = ty * HJR_TILE + (lane >> 3);
-    if (x >= a.width || y >= a.height) return; // (also the tiles of the last workgroup of a row behind tiles_x)
-    const uint32_t t = hjr_tile_id(tx, ty, a.tiles_x);
-    const size_t off = (size_t)(t % a.world) * a.rank_stride, slot = (size_t)(t / a.world) * 64u + lane, pix = (size_t)y * a.width + x;
-    if (a.color) a.out_color[pix] = reinterpret_cast<const float4*>(a.color + off)[slot];
-    if (a.albedo) a.out_albedo[pix] = reinterpret_cast<const float4*>(a.albedo + off)[slot];
-    if (a.normal) a.out_normal[pix] = reinterpret_cast<const float4*>(a.normal + off)[slot];
-    if (a.variance) a.out_variance[pix] = reinterpret_cast<const float*>(a.variance + off)[slot];
-}
-
-// ---- the 8-bit preview buffer of the raygen program (`uchar4* image` of Params, renderer/renderer.h:1102, 1175: written by the missing
-// __raygen__rg, never read back by the host — the PNG comes from AOV_Output).  Build-defined: the colour AOV through the tonemappers of
-// kernel/color.h (Tonemap_Uchimura :10-39, ACESFilm :55-63), then toSRGB + quantizeUnsignedChar as float4ConvertColor does on the host
-// (renderer.h:73-101).  The host form is hjr_tonemap_to_srgb8 (libm); this one uses the device's pow / exp, so single pixels may differ by
-// one code value at a quantisation boundary.
-__device__ inline float hjr_tm_uchimura(float x)
-{
-    const float P = 1.0f, a = 1.0f, m = 0.22f, l = 0.4f, c = 1.33f, b = 0.0f;
-    const float l0 = ((P - m) * l) / a, S0 = m + l0, S1 = m + a * l0, C2 = (a * P) / (P - S1), CP = -C2 / P;
-    const float sx = fmaxf(0.0f, fminf((x - 0.0f) / (m - 0.0f), 1.0f));
-    const float w0 = (float)(1.0 - (double)(sx * sx * (3.0f - 2.0f * sx)));
-    const float w2 = (float)((m + l0) < x);
-    const float w1 = (float)(1.0 - (double)w0 - (double)w2);
-    const float T = (float)((double)m * pow((double)(x / m), (double)c) + (double)b);
-    const float S = (float)((double)P - (double)(P - S1) * exp((double)(CP * (x - S0))));
-    const float L = m + a * (x - m);
-    return T * w0 + L * w1 + S * w2;
-}
-__device__ inline float hjr_tm_aces(float x)
-{
-    const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
-    return fmaxf(0.0f, fminf((x * (a * x + b)) / (x * (c * x + d) + e), 1.0f));
-}
-__global__ void __launch_bounds__(256) hjr_preview_kernel(const float4* color, uchar4* out, size_t n, int tonemap)
-{
-    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float4 v = color[i];
-    float ch[3] = { v.x, v.y, v.z };
-    unsigned char q8[3];
-    for (int k = 0; k < 3; k++) {
-        float col = ch[k];
-        col = tonemap == 1 ? hjr_tm_uchimura(col) : (tonemap == 2 ? hjr_tm_aces(col) : col);
-        const float powed = powf(col, 1.0f / 2.4f);
-        const float sr = col < 0.0031308f ? 12.92f * col : 1.055f * powed - 0.055f;
-        const float q = sr * 256.0f;
-        const uint32_t u = (q > 0.0f) ? ((q >= 4294967040.0f) ? 4294967040u : (uint32_t)q) : 0u;
-        q8[k] = (unsigned char)(u < 255u ? u : 255u);
-    }
-    out[i] = make_uchar4(q8[0], q8[1], q8[2], 255);
-}
-

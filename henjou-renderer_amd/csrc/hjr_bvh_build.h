@@ -42,7 +42,7 @@ namespace hjr {
 struct SceneCopy;
 
 // Traversal-stack entries a device-built tree may need: the tile classifier takes 64 * stack_need * 4 bytes of dynamic LDS without
-// raising the kernel's limit (hjr_device.hip::order_tiles), which stays at 32 KB with this cap.
+// raising the kernel's limit (hjr_render.hip::order_tiles), which stays at 32 KB with this cap.
 constexpr uint32_t DEVICE_BVH_MAX_STACK = 128;
 // Option "device_bvh_instances": instance subtrees one top tree takes (its clusters live in the LDS of one workgroup)
 constexpr uint32_t HJR_TOP_MAX = 1024;

@@ -152,7 +152,6 @@ HD f3 light_sample(const KParams& P, const float4* lights, CMJState& st, float& 
 }
 
 // ------------------------------------------------------------------ the megakernel
-#define HJR_BLOCK 256
 #define HJR_INTEGRATOR_NEE_ 0
 #define HJR_INTEGRATOR_PT_ 1
 #define HJR_INTEGRATOR_MIS_ 2
@@ -208,8 +207,8 @@ HD void start_path(const KParams& P, PathState& ps, uint32_t px, uint32_t py, ui
 // Dynamic LDS: [traversal stacks: stack_depth x BLOCK uint32][nodes][tri_geom]  (the last two only when LDSBVH).
 // LDSBVH: the whole BVH + leaf-order triangles are staged into LDS once per persistent workgroup (coalesced dwordx4 loads),
 // so every traversal step reads LDS (ds_read_b128, ~100-cycle latency) instead of L2 (~500+ cycles under load).  One
-// workgroup of BLOCK threads per CU shares the copy.  Chosen by the host when the scene fits (hjr_device.hip).
-extern __shared__ float4 hjr_smem[];
+// workgroup of BLOCK threads per CU shares the copy.  Chosen by the host when the scene fits (hjr_render.hip::plan_launch).
+// (hjr_smem, the array itself: hjr_traverse.hip.h)
 
 // ------------------------------------------------------------------ per-lane path context and the two halves of a bounce
 // Everything a lane carries from one bounce to the next.  The megakernel keeps it in registers for the lifetime of the lane;
@@ -452,7 +451,7 @@ HD void bounce_pre_trace(const KParams& P, LaneCtx& c, WaveRange& wr, const bool
             r_item = wr.base_item;
             if (n > have) {                         // not enough: lanes beyond `have` come from a fresh range
                 // once a wave has seen the queue run dry it never touches the head again (wave-uniform flag): the 32-bit head
-                // overshoots n_owned_items by at most 64 per wave of the grid and cannot wrap (hjr_device.hip keeps that margin)
+                // overshoots n_owned_items by at most 64 per wave of the grid and cannot wrap (hjr_render.hip::frame_geometry keeps that margin)
                 uint32_t base = 0xffffffffu;
                 if (!wr.exhausted) {
                     if (lane == 0) base = atomicAdd(HJR_COLD(queue_head), 64u);

@@ -1,6 +1,7 @@
 // Device data layout shared by the host-side frame builder and the HIP kernel.
 // Everything is 16-byte records so that each per-lane fetch is a global_load_dwordx4.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define HJR_TILE 8u                 /* 8x8 pixel tiles = one wavefront of pixels */
@@ -19,6 +20,16 @@ HJR_LAYOUT_FN void hjr_tile_xy(uint32_t t, uint32_t tiles_x, uint32_t* tx, uint3
     const uint32_t y = t / tiles_x, c = t - y * tiles_x, r = y % tiles_x;
     *ty = y;
     *tx = c >= r ? c - r : c + tiles_x - r;
+}
+/* slot -> pixel.  Everything behind the render kernels is laid out [owned tile][64]: slot sl is pixel (sl & 7, (sl >> 3) & 7) of
+ * this rank's owned tile sl >> 6.  Returns whether the pixel lies inside the image (edge tiles are partial). */
+HJR_LAYOUT_FN bool hjr_slot_xy(size_t sl, uint32_t rank, uint32_t world, uint32_t tiles_x, uint32_t width, uint32_t height, uint32_t* x, uint32_t* y)
+{
+    uint32_t tx, ty;
+    hjr_tile_xy((uint32_t)(sl >> 6) * world + rank, tiles_x, &tx, &ty);
+    *x = tx * HJR_TILE + ((uint32_t)sl & 7u);
+    *y = ty * HJR_TILE + (((uint32_t)sl >> 3) & 7u);
+    return *x < width && *y < height;
 }
 #define HJR_STACK_DEPTH 32          /* per-lane traversal stack entries (LDS); the builder caps tree depth at this */
 #define HJR_LEAF_FLAG 0x80000000u   /* child ref: bit31 = leaf, bits 27..30 = triangle count, bits 0..26 = first triangle */
@@ -49,7 +60,19 @@ HJR_LAYOUT_FN void hjr_tile_xy(uint32_t t, uint32_t tiles_x, uint32_t* tx, uint3
 #ifndef HJR_BLOCK_LDS
 #define HJR_BLOCK_LDS 1024          /* threads of the one-per-CU workgroup that shares an LDS copy of the BVH (16 waves = 4 per SIMD) */
 #endif
+#define HJR_BLOCK 256               /* threads of a megakernel workgroup of the memory layouts */
 #define HJR_LDS_BUDGET (159u * 1024u)
+/* wavefront kernel (hjr_wavefront.hip.h): tuning defaults the launch plan hands over, and the number of its queues */
+#ifndef HJR_WF_REFILL
+#define HJR_WF_REFILL 16 /* trace stage: lanes without a ray (nothing prefetched either) before the wave stops for a hand-over */
+#endif
+#ifndef HJR_WF_PREFETCH_MIN
+#define HJR_WF_PREFETCH_MIN 32 /* trace stage: lanes that have used up their prefetched context before the wave stops for a hand-over */
+#endif
+#ifndef HJR_WF_TRACE_MIN
+#define HJR_WF_TRACE_MIN 32 /* scheduler: a TRACE batch is preferred over a partial SHADE batch from this many queued rays on */
+#endif
+#define HJR_WF_QUEUES 5
 /* Triangle (leaf order), 48 B = 3 x float4: world-space vertices + global prim id.
  *   g0 = (v0.x v0.y v0.z v1.x)  g1 = (v1.y v1.z v2.x v2.y)  g2 = (v2.z, prim_id bits, material_id bits, 0) */
 #define HJR_TRI_F4 3

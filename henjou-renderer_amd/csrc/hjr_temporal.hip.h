@@ -5,7 +5,7 @@
 //                               frame's accumulated colour / variance / history length with four validated bilinear taps and blends.
 //   hjr_temporal_resp_kernel<COV, MOM>  the same with the windowed change test of section RESPONSE: a workgroup per 16 x 16 pixels.
 //   hjr_temporal_prior_kernel<COV>      the gather alone, ahead of the frame's render: section PRIOR.
-// Included by hjr_device.hip only: correctly rounded divide, no contraction, denormals on.  Specified to the bit, so that the test suite's
+// Included by hjr_post.hip only: correctly rounded divide, no contraction, denormals on.  Specified to the bit, so that the test suite's
 // CPU checker (tests/native/temporal_ref.cpp) restates it independently.  fp32 throughout, every operation as written, left to right:
 //   dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z ;   cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x) ;
 //   a 3 x 4 row-major transform M (12 floats, as hjr_set_transforms) applied to a point:  xf(M, p).i = ((M[4i] * p.x + M[4i+1] * p.y) + M[4i+2] * p.z) + M[4i+3],
@@ -130,7 +130,7 @@
 //   c_prev, v_prev and h_prev are only added, divided and compared: a NaN h_prev gives al = 1 through fmaxf, a NaN lp or vp is written as it is
 //   (rule 11 falls back to rule 6 on a NaN) and nothing indexes memory.
 #pragma once
-#include "hjr_aux.hip.h" // TileStack: the classifier's stacks
+#include "hjr_traverse.hip.h" // TileStack: the classifier's stacks
 
 #define HJR_TEMPORAL_K_PLANE 1.0f
 #define HJR_TEMPORAL_K_DIST 3.0f
@@ -228,7 +228,7 @@ struct TemporalSide {
     const float2* moments;      // MOM, prev only
     uint32_t coverage;          // COV: hjr_temporal_frame.coverage
 };
-// what a launch writes; the two optional images choose the kernel (hjr_device.hip: temporal_launch)
+// what a launch writes; the two optional images choose the kernel (hjr_post.hip: temporal_launch)
 struct TemporalOut {
     float4* color;
     float* variance;

@@ -3,7 +3,7 @@
 // the LaneStack of the layout, the scene staging, the BVH4 `top` copy) and call traverse<> / traverse_fused<> of hjr_traverse.hip.h as they are.  Two translation units
 // instantiate them: hjr_launch_trace.hip with the exact flags and hjr_launch_fast_trace.hip with the Makefile's FASTFLAGS (HJR_TRACE_FAST_BUILD),
 // which is how "the traversal and the triangle test are the same operations in every build" is checked ray by ray.
-// Included by those two units and by hjr_device.hip only: no render kernel sees this header.
+// Included by those two units and by hjr_util.hip (the entry point) only: no render kernel sees this header.
 #pragma once
 #include "hjr_launch.hip.h"
 
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(BLOCK, (LDSBVH ? 1 : HJR_MIN_WAVES)) hjr_trace
     L::flush_overflow(stack, A.n_over);
 }
 
-// hjr_device.hip::hjr_trace_rays calls these; each is launch_trace_batch of its unit
+// hjr_util.hip::hjr_trace_rays calls these; each is launch_trace_batch of its unit
 int hjr_launch_trace(hjr_ctx* c, const LaunchPlan& pl, bool fused, const TraceArgs& a, hipStream_t st);      // hjr_launch_trace.hip
 int hjr_launch_trace_fast(hjr_ctx* c, const LaunchPlan& pl, bool fused, const TraceArgs& a, hipStream_t st); // hjr_launch_fast_trace.hip
 

@@ -65,7 +65,7 @@ HD bool ray_tri(f3 v0, f3 v1, f3 v2, f3 o, f3 d, float tmin, float tmax, float& 
 // are staged into LDS use 16-bit entries (node index < 32768, or leaf: bit15 | count << 13 | first triangle < 8192), which
 // halves the stack's LDS footprint; everything else uses the 32-bit child refs as they are.
 // The 16-bit form holds leaves of at most HJR_STACK16_LEAF_MAX triangles (2-bit count): host/frame.cpp only selects it
-// for such trees, and hjr_selftest_stack16 (csrc/hjr_device.hip) round-trips every ref the builder can emit.
+// for such trees, and hjr_selftest_stack16 (csrc/hjr_util.hip) round-trips every ref the builder can emit.
 #define HJR_STACK16_LEAF_MAX 3u
 #define HJR_STACK16_MAX_TRIS 8192u
 #define HJR_STACK16_MAX_NODES 32768u
@@ -446,3 +446,16 @@ HD bool traverse_fused(const float4* nodes, const float4* tris, const bool a_val
 #ifdef HJR_FAST_MATH
 #pragma clang fp contract(fast)
 #endif
+
+// the one dynamic-LDS array of every kernel (the render kernels' layout of it: hjr_kernel.hip.h)
+extern __shared__ float4 hjr_smem[];
+// the stack of a lane of a one-wave workgroup that traces pixel-centre rays against the frame data in memory (the tile classifier, the G-buffer
+// pass): the lane's whole column in dynamic LDS, no overflow buffer, no staged tree top
+typedef LaneStack<uint32_t, 64, false> TileStack;
+__device__ __forceinline__ TileStack hjr_tile_stack()
+{
+    TileStack stack;
+    stack.lds = reinterpret_cast<uint32_t*>(hjr_smem) + threadIdx.x;
+    stack.spill = nullptr; stack.spill_stride = 0; stack.lds_n = 0; stack.n_over = 0; stack.top = nullptr; stack.n_top = 0u;
+    return stack;
+}

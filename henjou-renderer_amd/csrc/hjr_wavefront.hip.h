@@ -28,16 +28,7 @@
 #pragma once
 #include "hjr_kernel.hip.h"
 
-#ifndef HJR_WF_REFILL
-#define HJR_WF_REFILL 16 /* trace stage: lanes without a ray (nothing prefetched either) before the wave stops for a hand-over */
-#endif
-#ifndef HJR_WF_PREFETCH_MIN
-#define HJR_WF_PREFETCH_MIN 32 /* trace stage: lanes that have used up their prefetched context before the wave stops for a hand-over */
-#endif
-#ifndef HJR_WF_TRACE_MIN
-#define HJR_WF_TRACE_MIN 32 /* scheduler: a TRACE batch is preferred over a partial SHADE batch from this many queued rays on */
-#endif
-#define HJR_WF_QUEUES 5
+// (the trace stage's and the scheduler's tuning defaults HJR_WF_REFILL, HJR_WF_PREFETCH_MIN, HJR_WF_TRACE_MIN and HJR_WF_QUEUES: hjr_layout.h, where the host's launch plan reads them)
 
 // LDS-typed pointers: accesses through them are ds_* instructions (lgkmcnt only).  A generic pointer would make them flat_*
 // instructions, which also count in vmcnt and would make every queue operation wait for the trace stage's prefetch loads.
@@ -48,7 +39,7 @@ typedef WF_LDS volatile uint16_t* wf_ring_ptr;
 // four SHADE queues share two 64-bit words per counter kind: word 0 = queue 1 | queue 2 << 32, word 1 = queue 3 | queue 4 << 32, so
 // that a trace hand-over reserves (and publishes) its entries of two classes with ONE LDS atomic — "path ends" + Disney, which is all
 // most hand-overs carry.  The 32-bit fields are free-running ring positions; a carry from the low into the high field would need 2^32
-// pushes into one queue of one workgroup (hjr_device.hip keeps launches far below that).
+// pushes into one queue of one workgroup (hjr_render.hip::plan_launch keeps launches far below that).
 struct WfShared {
     uint32_t head[HJR_WF_QUEUES]; // next ring position to take
     uint32_t live;                // contexts not yet retired

@@ -235,7 +235,7 @@ extern "C" int hjr_bucket_window(uint32_t w, uint32_t h, uint32_t bw, uint32_t b
     return HJR_OK;
 }
 namespace hjr {
-// the argument rule of hjr_blit_window and hjr_blit_window_device (csrc/hjr_device.hip)
+// the argument rule of hjr_blit_window and hjr_blit_window_device (csrc/hjr_util.hip)
 int check_blit_window(const uint32_t window[4], uint32_t w, uint32_t h, const char* who)
 {
     if (window[0] < window[2] && window[2] <= w && window[1] < window[3] && window[3] <= h) return HJR_OK;
@@ -253,7 +253,7 @@ extern "C" int hjr_blit_window(const float* win, const uint32_t window[4], float
 }
 
 // ---- gathered shards -> frames (include/henjou_hip.h, DESIGN.md §7 "Denoise modes").  The argument rule of hjr_assemble_shards and
-// hjr_assemble_shards_device (csrc/hjr_device.hip) in one place: sizes, alignment, and per AOV "source and output both or neither".
+// hjr_assemble_shards_device (csrc/hjr_post.hip) in one place: sizes, alignment, and per AOV "source and output both or neither".
 namespace hjr {
 int check_shards(const hjr_shards& s, uint32_t w, uint32_t h, const void* const out[4], const char* who)
 {
@@ -276,7 +276,7 @@ int check_shards(const hjr_shards& s, uint32_t w, uint32_t h, const void* const 
     return HJR_OK;
 }
 } // namespace hjr
-// host form: per pixel the arithmetic of csrc/hjr_aux.hip.h::hjr_assemble_shards_kernel (tile id -> owner and slot; no table of owners)
+// host form: per pixel the arithmetic of csrc/hjr_shards.hip.h::hjr_assemble_shards_kernel (tile id -> owner and slot; no table of owners)
 extern "C" int hjr_assemble_shards(const hjr_shards* shards, uint32_t w, uint32_t h, float* color, float* albedo, float* normal, float* variance)
 {
     hjr_shards s;

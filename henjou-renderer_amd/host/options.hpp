@@ -50,7 +50,7 @@ inline const OptDesc* opt_table()
         { "device_bvh_instances", 0, 1 },        // device_bvh 1: per-instance trees built once per scene, a top tree over them per commit (default 0; host build ignores it; refits are off with it) [next hjr_set_transforms]
         { "device_bvh_graft", 0, 1 },            // device_bvh 1 and device_bvh_instances 1: every instance's BVH4 collapsed once and grafted under a BVH4 top tree per commit (default 0; ignored otherwise) [next hjr_set_transforms]
         { "firefly_clamp", 0, 64 },              // kappa of the firefly clamp on whole-frame renders: chunk sums above kappa x the pixel's median chunk are scaled down to it (default 0 = off; 4 recommended; biased)
-        { "item_chunks", 1, 8 },                 // megakernel: consecutive chunks of a pixel in one work item: 1, 2, 4 or 8; a launch uses the largest power of two <= this that divides its chunk count (default: measured per launch kind, hjr_device.hip)
+        { "item_chunks", 1, 8 },                 // megakernel: consecutive chunks of a pixel in one work item: 1, 2, 4 or 8; a launch uses the largest power of two <= this that divides its chunk count (default: measured per launch kind, hjr_render.hip: launch_render)
         { "denoise_variance_spatial", 0, 1 },    // "denoise_variance" / "denoise_temporal" on: 1 fills pixels whose variance is unknown (frames of at most 8 spp, a first one-granule pass) with a 3 x 3 guide-weighted estimate in front of the temporal stage and the filter (default 0; no effect otherwise)
         { "upscale_guided", 0, 1 },              // 1: DenoiseUpScale2X of hjr_render_denoised / hjr_denoise_shards_device traces G-buffers at the render and the output size and runs the guided upscale (hjr_upscale_guided) instead of the bilinear one (default 0; the other modes ignore it)
         { "denoise_temporal_coverage", 0, 4 },   // "denoise_temporal" on: 2, 3 or 4 run the coverage G-buffer pass with that many sub-pixel rays per side and the coverage-aware accumulation rules (default 0; 1 is rejected; no effect otherwise)

@@ -16,7 +16,7 @@ namespace hjr {
 void set_error(const std::string& s);
 bool write_png(const std::string& path, const uint8_t* rgba, uint32_t w, uint32_t h, bool flip_y, std::string& err);
 void float4_to_srgb8(const float* rgba, uint8_t* out, uint32_t n);
-// "bucket" (csrc/hjr_device.hip): two buffers of the context for a bucketed frame, slot 0 the frame and slot 1 a bucket, and the frame's one
+// "bucket" (csrc/hjr_util.hip): two buffers of the context for a bucketed frame, slot 0 the frame and slot 1 a bucket, and the frame's one
 // download on the context's stream (synchronous)
 int bucket_buffer(hjr_ctx* c, int slot, size_t bytes, void** d_out);
 int bucket_download(hjr_ctx* c, float* host, const void* d_frame, size_t bytes);

@@ -764,7 +764,7 @@ int hjr_get_stats(hjr_ctx*, hjr_stats* out);
                                  largest power of two that is no larger than this and divides the number of chunks it renders (possibly 1).
                                  Scheduling only: every chunk is still summed on its own, frames are the same bits.  Default: 1 for launches
                                  with world_size > 1 (short, tail-bound) and for counting launches (HJR_FLAG_STATS), else what was measured
-                                 fastest on one GPU (csrc/hjr_device.hip: HJR_ITEM_CHUNKS).  The wavefront kernels and MIS always run single chunks;
+                                 fastest on one GPU (csrc/hjr_render.hip: HJR_ITEM_CHUNKS).  The wavefront kernels and MIS always run single chunks;
                                  hjr_stats.item_chunks reports what the last launch used
    "denoise_variance_spatial" 0 1  1: with "denoise_variance" or "denoise_temporal" on, hjr_render_denoised and hjr_denoise_shards_device run
                                  hjr_estimate_variance_device in place on the frame's variance AOV before the temporal stage and the filter:

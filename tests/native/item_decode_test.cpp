@@ -4,7 +4,7 @@
 // For tile grids 1x1, 3x2, 5x3; world 1, 2, 3 (every rank); pass_chunks 1, 2, 3, 4, 6, 8 at chunk0 0 and 1; requested item_chunks 1, 2, 4, 8;
 // plain and permuted tile lists:
 //   * the effective r is a power of two, <= the request, divides pass_chunks, and no larger power of two does;
-//   * the item count is owned tiles * (pass_chunks / r) * 64, what hjr_device.hip sizes the queue for;
+//   * the item count is owned tiles * (pass_chunks / r) * 64, what hjr_render.hip sizes the queue for;
 //   * every (owned tile, chunk of the pass, pixel) is rendered exactly once, and nothing else is;
 //   * the chunks of an item are r consecutive chunks of one pixel, aligned to r from chunk0.
 // Build: g++ -O1 -std=c++17 tests/native/item_decode_test.cpp -o item_decode_test

@@ -143,6 +143,24 @@ def planes_case(seed=1):
     return prev, cur, c_prev
 
 
+# ---- the staging case of the host entry points (GPU tests of hjr_temporal_accumulate_response and hjr_temporal_prior)
+def staging_case(seed=11):
+    """7 x 5 pixels of three wall instances side by side, seen by two cameras a fifth of a unit apart: 35 pixels, so the one-float images
+    are an odd number of floats and the float2 and float4 images staged behind them start on their own alignment only if the host entry
+    point's layout puts them there; three instances, so M and M^-1 are 36 floats each.  Returns (prev with moments, cur)."""
+    from temporal_util import identity_xf, plane_gbuffer, wall_camera
+    w, h = 7, 5
+    planes = [(-4.0, 0, 1, -1e9, -0.6), (-4.0, 1, 2, -0.6, 0.6), (-4.0, 2, 3, 0.6, 1e9)]
+    rng = np.random.default_rng(seed)
+    side = lambda cam: {"camera": cam, "transforms": identity_xf(3), "inv_transforms": identity_xf(3), "gbuffer": plane_gbuffer(w, h, cam, planes),
+                        "color": rng.uniform(0.1, 0.9, (h, w, 4)).astype(f32), "variance": rng.uniform(0.01, 0.02, (h, w)).astype(f32)}
+    prev, cur = side(wall_camera()), side(wall_camera(x=0.2))
+    assert all((g["inst"] == k).any() for g in (prev["gbuffer"], cur["gbuffer"]) for k in range(3))
+    prev["history"] = rng.integers(1, 9, (h, w)).astype(f32)
+    prev["moments"] = rng.uniform(0.1, 0.9, (h, w, 2)).astype(f32)
+    return prev, cur
+
+
 def check_planes_lambda(lam, what):
     """The lambda image of planes_case: what the construction gives (docstring of planes_case)."""
     assert (lam[2:PH - 2, 2:P_SPLIT - 2] == 1).all(), what + ": the raised instance's interior"

@@ -158,6 +158,17 @@ def test_prior_equals_native_checker(cornell, aux, cam, w, h, case):
     assert_bits(out.cpu().numpy(), want, "%s %dx%d, device form" % (case, w, h))
 
 
+def test_prior_host_entry_staging_at_an_odd_pixel_count(aux):
+    """hjr_temporal_prior through its host entry point at 7 x 5 pixels and 3 instances (temporal_response_util.staging_case: one-float
+    images of an odd number of floats in the staging buffer) equals tests/native/temporal_prior_ref.cpp bit for bit."""
+    from temporal_response_util import P_TRIS, staging_case
+    prev, cur = staging_case()
+    prev = {k: v for k, v in prev.items() if k != "moments"}
+    want = atu.prior_ref(prev, geometry_of(cur), P_TRIS)
+    assert_bits(aux.temporal_prior(prev, geometry_of(cur)), want, "7 x 5, 3 instances, host form")
+    assert (want[..., 2] < 1).any(), "pixels are carried: the previous side's images were read"
+
+
 def test_prior_argument_checks(cornell, aux, cam):
     L = hjr.lib()
     prev = rendered(cornell, aux, 28, 20, 0, cam, 1)

@@ -181,7 +181,7 @@ def test_two_sample_passes(cornell, dev, item_chunks, split):
 
 
 def test_default_selection(cornell, dev):
-    """With the option unset the launch decides (hjr_device.hip::launch_render): pairs for a single-GPU launch of at least 192 single-chunk
+    """With the option unset the launch decides (hjr_render.hip::launch_render): pairs for a single-GPU launch of at least 192 single-chunk
     items per lane of the grid — the headline shape, 1080p x 256 spp —, single chunks for a short launch, a rank of a shard and a counting
     launch.  The headline frame with the default is the frame of single chunks, bit for bit."""
     w, h = 1920, 1080

@@ -20,7 +20,7 @@ from denoise_var_util import denoise_var_ref
 from scene_util import ROOT, Cornell, f32_time, hjr
 from temporal_cov_util import mixed
 from temporal_response_util import (P_TRIS, PH, PW, QFRAMES, check_planes_lambda, format_tables, geometry_changes, planes_case, quality_chain, quality_conditions,
-                                    sequence_transforms, temporal_response_ref, worst_pixels)
+                                    sequence_transforms, staging_case, temporal_response_ref, worst_pixels)
 from temporal_util import MISS, assert_same, camera_at, moved_consistent, next_prev, ref_mask, same_bits
 from test_gpu_denoise_shards import render_shards
 from test_gpu_progressive import with_range
@@ -125,6 +125,14 @@ def test_synthetic_planes(dev):
         assert not same_bits(got[0], plain[0]) and not same_bits(got[2], plain[2])
         zero = got[-1] == 0
         assert all(same_bits(a[zero], b[zero]) for a, b in zip(got[:-1], plain)), "where lambda = 0 the outputs are the plain call's"
+
+
+def test_host_entry_staging_at_an_odd_pixel_count(dev):
+    """hjr_temporal_accumulate_response through its host entry point at 7 x 5 pixels, 3 instances, a previous frame, moments and response on:
+    all five outputs equal tests/native/temporal_response_ref.cpp bit for bit."""
+    prev, cur = staging_case()
+    got = checked(dev, prev, cur, P_TRIS, "7 x 5, 3 instances", moments=True)
+    assert len(got) == 5 and (got[2] > 1).any(), "pixels are carried: the previous side's images were read"
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3. hostile input

@@ -1,6 +1,6 @@
 """Every shipped kernel layout of both kernel families under a bit-exact parity test (VERDICT r01 task 1).
 
-hjr_device.hip::plan_launch dispatches four layouts (hjr_stats.lds_mode): 0 = BVH4 read from memory, 1 = BVH2 staged in LDS with
+hjr_render.hip::plan_launch dispatches four layouts (hjr_stats.lds_mode): 0 = BVH4 read from memory, 1 = BVH2 staged in LDS with
 32-bit stack entries, 2 = BVH2 in LDS with 16-bit stack entries, 3 = BVH2 read from memory; the memory-path layouts keep the
 top of a lane's traversal stack in LDS and overflow into an HBM buffer.  The bundled scene only ever selects layout 1, so each
 other layout is forced here (hjr_set_option: layout options act when the frame data is built, the others at the launch) and checked,
@@ -227,7 +227,7 @@ def test_full_size_frames_agree_between_the_families(cornell):
 
 
 def test_pipeline_selection(cornell):
-    """Without HJR_PIPELINE the library picks the kernel family per launch (hjr_device.hip::plan_launch): the wavefront kernels for MIS
+    """Without HJR_PIPELINE the library picks the kernel family per launch (hjr_render.hip::plan_launch): the wavefront kernels for MIS
     (any layout), the megakernel otherwise.  Whatever it picks, the bits are the oracle's."""
     if True:
         d = cornell.device()

@@ -9,7 +9,7 @@ Per pass count, after one warm-up frame, R frames each of:
   kernel_ms        sum over the passes of hjr_stats.last_kernel_ms (HIP events around tile order + render + finalize / accumulate)
   wall_ms          host wall time of the frame: every pass enqueued with hjr_render_device into device tensors, one synchronize at the end
   chunk_bytes      peak chunk-sum bytes (owned tiles x 64 x 16 B x the largest pass's chunks x AOVs) and running-sum bytes (x AOVs when
-                   the frame has more than one pass), from the library's allocation rule (csrc/hjr_device.hip::bind_params)
+                   the frame has more than one pass), from the library's allocation rule (csrc/hjr_render.hip::bind_params)
 The last pass's colour is checked bit for bit against the one-pass frame.
 --variance: every render also writes the variance AOV (a fourth device tensor, one float per pixel; DESIGN.md §4 rule 7).
 """
