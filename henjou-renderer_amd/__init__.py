@@ -131,7 +131,7 @@ class Stats(_Sized):
     def as_dict(self):
         names = [n for k in reversed(type(self).__mro__) for n, _ in getattr(k, "_fields_", [])]
         d = {n: (float(getattr(self, n)) if n in ("last_kernel_ms", "frame_build_ms", "bvh_sah", "bvh_topology_ms") else int(getattr(self, n)))
-             for n in names if n not in ("struct_size", "_pad0", "_pad1", "nan_where")}
+             for n in names if n not in ("struct_size", "_pad0", "_pad1", "_pad2", "nan_where")}
         d["nan_where"] = [tuple(int(v) for v in self.nan_where[i]) for i in range(int(self.nan_located))]  # (x, y, sample)
         return d
 
@@ -158,8 +158,25 @@ class StatsV5(StatsV4):
 
 
 class StatsV6(StatsV5):
-    """hjr_stats with the work-item length of the last launch appended after `StatsV5` (option "item_chunks").  Device.stats() uses this one."""
+    """hjr_stats with the work-item length of the last launch appended after `StatsV5` (option "item_chunks")."""
     _fields_ = [("item_chunks", C.c_uint32), ("_pad1", C.c_uint32)]
+
+
+class StatsV7(StatsV6):
+    """hjr_stats with the deformation fields appended after `StatsV6` (hjr_set_morph, hjr_update_vertices).  Device.stats() uses this one."""
+    _fields_ = [("morph_vertices", C.c_uint32), ("_pad2", C.c_uint32), ("geometry_generation", C.c_uint64)]
+
+
+class MorphSet(C.Structure):
+    """hjr_morph_set: one deformed vertex range of hjr_set_morph."""
+    _fields_ = [("first_vertex", C.c_uint32), ("n_vertices", C.c_uint32), ("n_targets", C.c_uint32), ("first_weight", C.c_uint32),
+                ("position_deltas", C.c_void_p), ("normal_deltas", C.c_void_p)]
+
+
+class Morph(_Sized):
+    """hjr_morph: the morph sets of a scene and their default weights (hjr_set_morph, hjr_scene_get_morph)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_sets", C.c_uint32), ("n_weights", C.c_uint32), ("_pad0", C.c_uint32), ("sets", C.c_void_p),
+                ("default_weights", C.c_void_p)]
 
 
 class Adaptive(_Sized):
@@ -231,9 +248,14 @@ def lib():
             "hjr_scene_get_view": [C.c_void_p, C.c_void_p],
             "hjr_scene_eval_transforms": [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p],
             "hjr_scene_eval_camera": [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p],
+            "hjr_scene_get_morph": [C.c_void_p, C.c_void_p],
+            "hjr_scene_eval_morph_weights": [C.c_void_p, C.c_float, C.c_void_p, C.c_uint32],
             "hjr_load_png_rgba8": [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_load_hdr_rgba32f": [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p],
             "hjr_set_sky": [C.c_void_p, C.c_void_p, C.c_int, C.c_int],
+            "hjr_update_vertices": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
+            "hjr_set_morph": [C.c_void_p, C.c_void_p],
+            "hjr_set_morph_weights": [C.c_void_p, C.c_void_p, C.c_uint32],
             "hjr_create": [C.c_int, C.c_void_p],
             "hjr_upload_scene": [C.c_void_p, C.c_void_p],
             "hjr_set_transforms": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32],
@@ -418,6 +440,28 @@ class Scene:
         _check(lib().hjr_scene_eval_camera(self._h, C.byref(opt), C.c_float(time), C.byref(cam)), "hjr_scene_eval_camera")
         return cam
 
+    def morph(self):
+        """hjr_scene_get_morph: (sets, default_weights) in the form Device.set_morph takes (numpy copies), or ([], empty) for a file without
+        morph targets.  The scene view and arrays() stay the rest pose."""
+        m = Morph()
+        _check(lib().hjr_scene_get_morph(self._h, C.byref(m)), "hjr_scene_get_morph")
+        sets = []
+        if m.n_sets:
+            for s in (MorphSet * m.n_sets).from_address(m.sets):
+                shape = (s.n_targets, s.n_vertices, 3)
+                sets.append({"first_vertex": int(s.first_vertex), "first_weight": int(s.first_weight),
+                             "position_deltas": _np(s.position_deltas, s.n_targets * s.n_vertices * 3, np.float32).reshape(shape),
+                             "normal_deltas": _np(s.normal_deltas, s.n_targets * s.n_vertices * 3, np.float32).reshape(shape) if s.normal_deltas else None})
+        return sets, (_np(m.default_weights, m.n_weights, np.float32) if m.n_weights else np.zeros(0, np.float32))
+
+    def morph_weights(self, time):
+        """hjr_scene_eval_morph_weights: float32 [n_weights] at `time`."""
+        m = Morph()
+        _check(lib().hjr_scene_get_morph(self._h, C.byref(m)), "hjr_scene_get_morph")
+        w = np.zeros(m.n_weights, dtype=np.float32)
+        _check(lib().hjr_scene_eval_morph_weights(self._h, C.c_float(time), w.ctypes.data if w.size else None, m.n_weights), "hjr_scene_eval_morph_weights")
+        return w
+
     def arrays(self, time=None):
         """numpy copies of the SceneData columns (+ transforms at `time`) — the oracle's input in tests/bench."""
         v = self.view
@@ -513,6 +557,52 @@ class Device:
             return
         a = np.ascontiguousarray(rgba32f, dtype=np.float32)
         _check(lib().hjr_set_sky(self._h, a.ctypes.data, a.shape[1], a.shape[0]), "hjr_set_sky")
+
+    def update_vertices(self, first_vertex, positions, normals=None):
+        """hjr_update_vertices: overwrite base positions (float32 [n, 3]) from `first_vertex` on, and the normals unless None."""
+        p = np.ascontiguousarray(positions, dtype=np.float32)
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm is not None and nrm.size != p.size:
+            raise ValueError("update_vertices: positions and normals must have the same size")
+        _check(lib().hjr_update_vertices(self._h, int(first_vertex), p.size // 3, p.ctypes.data if p.size else None,
+                                         None if nrm is None else nrm.ctypes.data), "hjr_update_vertices")
+
+    def set_morph(self, sets, default_weights=None):
+        """hjr_set_morph.  sets: dicts with first_vertex, first_weight, position_deltas (float32 [K, n, 3], target-major) and optionally
+        normal_deltas (the same shape); None or an empty list removes the morph.  default_weights: float32 [n_weights] (None: zeros, as many as the
+        sets use)."""
+        if not sets:
+            _check(lib().hjr_set_morph(self._h, None), "hjr_set_morph")
+            return
+        keep, arr = [], (MorphSet * len(sets))()
+        need = 0
+        for i, s in enumerate(sets):
+            pd = np.ascontiguousarray(s["position_deltas"], dtype=np.float32)
+            if pd.ndim != 3 or pd.shape[2] != 3:
+                raise ValueError("set_morph: position_deltas must be [targets, vertices, 3]")
+            nd = s.get("normal_deltas")
+            if nd is not None:
+                nd = np.ascontiguousarray(nd, dtype=np.float32)
+                if nd.shape != pd.shape:
+                    raise ValueError("set_morph: normal_deltas must have the shape of position_deltas")
+            keep += [pd, nd]
+            arr[i].first_vertex, arr[i].n_vertices, arr[i].n_targets = int(s["first_vertex"]), pd.shape[1], pd.shape[0]
+            arr[i].first_weight = int(s.get("first_weight", 0))
+            arr[i].position_deltas = pd.ctypes.data
+            arr[i].normal_deltas = None if nd is None else nd.ctypes.data
+            need = max(need, arr[i].first_weight + pd.shape[0])
+        m = Morph()
+        m.n_sets = len(sets)
+        m.sets = C.addressof(arr)
+        w = None if default_weights is None else np.ascontiguousarray(default_weights, dtype=np.float32)
+        m.n_weights = w.size if w is not None else need
+        m.default_weights = None if w is None else w.ctypes.data
+        _check(lib().hjr_set_morph(self._h, C.byref(m)), "hjr_set_morph")
+
+    def set_morph_weights(self, weights):
+        """hjr_set_morph_weights: float32 [n_weights]."""
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        _check(lib().hjr_set_morph_weights(self._h, w.ctypes.data if w.size else None, w.size), "hjr_set_morph_weights")
 
     def render(self, params, want_aovs=True, want_variance=False):
         """Synchronous render into host arrays (hjr_render); want_variance: hjr_render_var, and the variance AOV (float32 [h, w]) is
@@ -817,7 +907,7 @@ class Device:
         return out
 
     def stats(self):
-        st = StatsV6()
+        st = StatsV7()
         _check(lib().hjr_get_stats(self._h, C.byref(st)), "hjr_get_stats")
         return st.as_dict()
 

@@ -81,6 +81,8 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     const bool adaptive = job.adaptive && hjr_owned_tiles(W, H, (uint32_t)rank, (uint32_t)world) > 0;
     if (adaptive) HJRX(hjr::set_adaptive(ctx, opt));
     HJRX(hjr::upload_assets(ctx, opt, view, rank == 0));
+    std::vector<float> morph_w; // "morph_targets": every rank blends the whole scene, so the PNGs are the single-GPU bytes
+    HJRX(hjr::set_morph(ctx, opt, scene, morph_w));
     // RCCL communicator: rank 0 creates the id and writes it to its pipe; the launcher passes it on to the pipes of the other ranks
     // (a world of one needs no hand-over).  Everything fallible that does not need the peers has happened above.
     HIPX(hipSetDevice(rank));
@@ -112,6 +114,7 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
     for (uint32_t f = opt.start_frame; f < opt.end_frame; f++) {
         const float time = f / float(opt.fps); // renderer.h:1128
         HJRX(hjr_scene_eval_transforms(scene, time, m.data(), inv.data()));
+        HJRX(hjr::set_morph_weights(ctx, scene, time, morph_w));
         HJRX(hjr_set_transforms(ctx, m.data(), inv.data(), view.n_instances));
         hjr_params_window pw; // (the longer caller: the render window behind hjr_params)
         memset(&pw, 0, sizeof(pw));

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <string>
 #include <utility>
+#include <vector>
 
 // Owns its allocation.  The one condition: a DevBuf is destroyed (or released, or moved onto) with its device current, which every entry
 // point and hjr_destroy see to before they touch a context.
@@ -82,6 +83,30 @@ struct DeviceBvh {
     void release(); // what is not a DevBuf: the events (the buffers go with the struct)
 };
 
+// hjr_set_morph on the device builder: the deltas and the set table go up once, the weights per commit, and
+// hjr_morph_kernel writes the working vertex / normal arrays that every flatten of the three paths below reads in place of b.vert / b.norm.
+// Nothing here is allocated without a morph.  The context keeps it beside the DeviceBvh and hands it to every build.
+struct Morph;
+struct DeviceMorph {
+    const Morph* host = nullptr;   // the context's morph (null or not active: the builds read the base arrays)
+    const float* w_next = nullptr; // the weights of this commit, host->weights' size
+    DevBuf vert, norm;             // working arrays, the base's size
+    DevBuf deltas, table, weights; // Morph::deltas | one record per set | the weights of the working arrays
+    bool uploaded = false;         // deltas and table are the host's
+    bool copied = false;           // the working arrays hold the base outside the sets (and what the last blend wrote inside them)
+    bool blended = false;          // ... and inside the sets the blend of the base under `w`
+    std::vector<float> w;
+    uint32_t launched = 0;         // vertices hjr_morph_kernel was launched over since the caller zeroed it
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; // around that launch on the build's stream (kernel_ms reads them after the build's host wait)
+    float kernel_ms() const { float ms = 0.0f; return launched && ev0 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess ? ms : 0.0f; }
+    void drop() // with the device current, like every DevBuf
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        *this = DeviceMorph();
+    }
+};
+
 struct DeviceBvhResult {
     uint32_t n_nodes = 0, stack_need = 0, depth = 0;
     float build_ms = 0.0f; // HIP-event time of the build's kernels
@@ -93,16 +118,17 @@ struct DeviceBvhResult {
 // Enqueues the whole build on `st` behind whatever is already there, waits for it and reads back its header.  HJR_ERR_ARG with `err`
 // set for a scene the host builder rejects too (non-finite vertex, tree deeper than the traversal stack allows), HJR_ERR_DEVICE for a
 // runtime failure.  The lights are the host's table (build_lights), copied into `b.lights`.
+// `dm` (all three builds; may be null): the morph of the scene, blended ahead of the flatten when its working arrays are not current.
 // `opt_rounds` (option "device_bvh_opt", 0..3) treelet-restructuring rounds run over the BVH2 before the collapse; 0 leaves the build as it was.
 int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
-                     const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+                     const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err, DeviceMorph* dm = nullptr);
 // Option "device_bvh_refit": the frame data for new transforms over the topology of the CURRENT frame data (`cur_nodes`, `cur_geom`: a
 // device build or refit of the same scene with n_nodes nodes; only the refs rows and the prim ids are read, nothing is written there).
 // Flatten in leaf order, node boxes bottom-up over the BVH4, tree cost; one host wait.  Writes b.nodes / tri_* / lights like the build;
 // r.stack_need and r.depth stay 0 (the topology's, which the caller has).  Errors as device_bvh_build; HJR_ERR_DEVICE when the current
 // data fails a bound.  At least 2 triangles.
 int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const DevBuf& cur_nodes, const DevBuf& cur_geom,
-                     uint32_t n_nodes, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+                     uint32_t n_nodes, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err, DeviceMorph* dm = nullptr);
 // Option "device_bvh_instances": the frame data for these transforms from per-instance trees.  The topology (a BVH2 over object-space
 // boxes whose subtrees are the instances: sort keys carry the instance id above the Morton code; `opt_rounds` treelet rounds that never
 // cross an instance) is built when b.topo is not valid for `tag`, and kept.  Every call flattens in its leaf order, computes the world
@@ -114,5 +140,6 @@ int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
 // workgroup and places the instance nodes behind the top nodes.  No per-level launches, one host wait; the BVH2 is freed after the
 // topology build.  The same fallbacks.
 int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
-                         uint32_t tag, bool graft, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err);
+                         uint32_t tag, bool graft, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err,
+                         DeviceMorph* dm = nullptr);
 } // namespace hjr

@@ -120,6 +120,44 @@ __global__ void __launch_bounds__(NT) scan_down_kernel(const uint32_t* in, uint3
     }
 }
 
+// ---- morph targets (hjr_set_morph): the working vertex / normal arrays every flatten below reads ---------------------
+// One record per set; block_begin: the first workgroup of the set (ascending, set 0 at 0).  pos / nrm: first float of the set's deltas in
+// MorphArgs::deltas, target-major (target k of vertex i at 3 * (k * n_vertices + i)), so every target's read is as coalesced as the base's.
+struct MorphSetDev { uint32_t first_vertex, n_vertices, n_targets, first_weight, block_begin, has_nrm; unsigned long long pos, nrm; };
+struct MorphArgs {
+    const float *base_v, *base_n, *deltas, *w;
+    const MorphSetDev* sets;
+    uint32_t n_sets;
+    float *out_v, *out_n;
+};
+// p = base; p = p + w[k] * d[k] for k = 0 .. K-1, per component: the product rounded, then the sum (this unit is built with -ffp-contract=off).
+// The loads of four targets are independent of the sums and issue together; the sums stay in target order.
+__device__ __forceinline__ void morph_vertex3(const float* base, const float* d, size_t stride, const float* w, uint32_t K, float* out)
+{
+    float p0 = base[0], p1 = base[1], p2 = base[2];
+#pragma unroll 4
+    for (uint32_t k = 0; k < K; k++) {
+        const float* dk = d + (size_t)k * stride;
+        const float wk = w[k], t0 = wk * dk[0], t1 = wk * dk[1], t2 = wk * dk[2];
+        p0 = p0 + t0; p1 = p1 + t1; p2 = p2 + t2;
+    }
+    out[0] = p0; out[1] = p1; out[2] = p2;
+}
+// One lane per vertex of a set; a workgroup lies inside one set.  Streaming: no LDS, no scratch, no atomics; every byte is read or written once.
+// Vertices outside the sets, and the normals of a set without normal deltas, are not touched: the working arrays hold the base there.
+__global__ void __launch_bounds__(NT) hjr_morph_kernel(MorphArgs a)
+{
+    uint32_t lo = 0, hi = a.n_sets; // the set of this workgroup: the last block_begin <= blockIdx.x (uniform)
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (a.sets[mid].block_begin <= blockIdx.x) lo = mid; else hi = mid; }
+    const MorphSetDev s = a.sets[lo];
+    const uint32_t i = (blockIdx.x - s.block_begin) * NT + threadIdx.x;
+    if (i >= s.n_vertices) return;
+    const size_t v = 3 * ((size_t)s.first_vertex + i), stride = 3 * (size_t)s.n_vertices;
+    const float* w = a.w + s.first_weight;
+    morph_vertex3(a.base_v + v, a.deltas + s.pos + 3 * (size_t)i, stride, w, s.n_targets, a.out_v + v);
+    if (s.has_nrm) morph_vertex3(a.base_n + v, a.deltas + s.nrm + 3 * (size_t)i, stride, w, s.n_targets, a.out_n + v);
+}
+
 // ---- flatten: frame.cpp:520-543 (world vertices, shading record, instance) and :586-600 (box, centroid, max |coordinate|) ----------
 __device__ __forceinline__ void xform_pos(const float* m, float px, float py, float pz, float* o)
 {
@@ -1551,6 +1589,53 @@ static bool upload_scene(DeviceBvh& b, const SceneCopy& sc, hipStream_t st)
     return true;
 }
 
+static bool morph_active(const DeviceMorph* dm) { return dm && dm->host && dm->host->active() && dm->w_next; }
+
+// The working arrays of a morphed scene for this commit's weights, on `st` ahead of the flatten; the object-space scene is on the device.
+// Once per hjr_set_morph: deltas and set table.  Once per change of the base: a device copy of the base arrays.  Per commit: the weights
+// and one hjr_morph_kernel over the sets' vertices, unless the working arrays already hold this blend.
+static int prepare_morph(DeviceBvh& b, const SceneCopy& sc, DeviceMorph* dm, hipStream_t st, std::string& err)
+{
+    if (!morph_active(dm)) return HJR_OK;
+    const Morph& mo = *dm->host;
+    const size_t base_bytes = sc.vertices.size() * 4, nw = mo.weights.size();
+    std::vector<MorphSetDev> table;
+    uint32_t blocks = 0;
+    for (const MorphSet& s : mo.sets) {
+        table.push_back({ s.first_vertex, s.n_vertices, s.n_targets, s.first_weight, blocks, s.nrm != Morph::NONE ? 1u : 0u, (unsigned long long)s.pos,
+                          s.nrm != Morph::NONE ? (unsigned long long)s.nrm : 0ull });
+        blocks += (s.n_vertices + NT - 1) / NT;
+    }
+    if (!dm->uploaded) {
+        if (!dm->deltas.upload(mo.deltas.data(), mo.deltas.size() * 4, st) || !dm->table.upload(table.data(), table.size() * sizeof(MorphSetDev), st) ||
+            !dm->vert.reserve(base_bytes) || !dm->norm.reserve(base_bytes) || !dm->weights.reserve(std::max<size_t>(nw, 1) * 4))
+            return fail_alloc(err);
+        DCHK(hipStreamSynchronize(st)); // `table` is a local
+        dm->uploaded = true;
+        dm->copied = false;
+    }
+    if (!dm->copied) {
+        DCHK(hipMemcpyAsync(dm->vert.p, b.vert.p, base_bytes, hipMemcpyDeviceToDevice, st));
+        DCHK(hipMemcpyAsync(dm->norm.p, b.norm.p, base_bytes, hipMemcpyDeviceToDevice, st));
+        dm->copied = true;
+        dm->blended = false;
+    }
+    if (dm->blended && dm->w.size() == nw && memcmp(dm->w.data(), dm->w_next, nw * 4) == 0) return HJR_OK;
+    dm->w.assign(dm->w_next, dm->w_next + nw); // kept: the source of the copy below
+    DCHK(hipMemcpyAsync(dm->weights.p, dm->w.data(), nw * 4, hipMemcpyHostToDevice, st));
+    MorphArgs a = { b.vert.as<float>(), b.norm.as<float>(), dm->deltas.as<float>(), dm->weights.as<float>(), dm->table.as<MorphSetDev>(), (uint32_t)table.size(),
+                    dm->vert.as<float>(), dm->norm.as<float>() };
+    if (!dm->ev0) DCHK(hipEventCreate(&dm->ev0));
+    if (!dm->ev1) DCHK(hipEventCreate(&dm->ev1));
+    DCHK(hipEventRecord(dm->ev0, st));
+    hipLaunchKernelGGL(hjr_morph_kernel, dim3(blocks), dim3(NT), 0, st, a);
+    DCHK(hipEventRecord(dm->ev1, st));
+    DCHK(hipGetLastError());
+    dm->blended = true;
+    dm->launched += mo.n_vertices;
+    return HJR_OK;
+}
+
 // what b.xf takes per instance: 12 floats of M, then 12 of Mi (the caller keeps it until its host wait)
 static std::vector<float> pack_transforms(const float* M, const float* Mi, uint32_t n_inst)
 {
@@ -1562,11 +1647,12 @@ static std::vector<float> pack_transforms(const float* M, const float* Mi, uint3
     return xf;
 }
 
-// the scene, the transforms and the builder's per-triangle buffers; a kernel reads only those its pass has reserved
-static FlattenArgs flatten_args(const DeviceBvh& b, uint32_t n, uint32_t n_inst)
+// the scene (under a morph: its working arrays), the transforms and the builder's per-triangle buffers; a kernel reads only those its pass has reserved
+static FlattenArgs flatten_args(const DeviceBvh& b, const DeviceMorph* dm, uint32_t n, uint32_t n_inst)
 {
     FlattenArgs fa;
-    fa.vert = b.vert.as<float>(); fa.norm = b.norm.as<float>(); fa.uv = b.uv.as<float>(); fa.xf = b.xf.as<float>();
+    const bool morphed = morph_active(dm); // the working arrays prepare_morph made current
+    fa.vert = (morphed ? dm->vert : b.vert).as<float>(); fa.norm = (morphed ? dm->norm : b.norm).as<float>(); fa.uv = b.uv.as<float>(); fa.xf = b.xf.as<float>();
     fa.idx = b.idx.as<uint32_t>(); fa.mat = b.mat.as<uint32_t>(); fa.prim_off = b.prim_off.as<uint32_t>();
     fa.n = n; fa.n_inst = n_inst;
     fa.wv = b.wv.as<float>(); fa.shade = b.tri_shade.as<float>(); fa.box = b.box.as<float>(); fa.cent = b.cent.as<float>();
@@ -1697,13 +1783,14 @@ static int collapse_and_cost(DeviceBvh& b, const CollapseArgs& ca, uint32_t n, s
 }
 
 int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
-                     const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+                     const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err, DeviceMorph* dm)
 {
     const uint32_t n = sc.n_triangles;
     r = DeviceBvhResult();
     if (!b.ev0) DCHK(hipEventCreate(&b.ev0));
     if (!b.ev1) DCHK(hipEventCreate(&b.ev1));
     if (!upload_scene(b, sc, st)) return fail_alloc(err);
+    if (const int rc = prepare_morph(b, sc, dm, st, err)) return rc;
     const std::vector<float> xf = pack_transforms(M, Mi, n_inst);
     const size_t nn = std::max<uint32_t>(n, 1u);            // node / frontier capacity: a wide node takes at least one BVH2 inner node
     const uint32_t nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
@@ -1734,7 +1821,7 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
     }
     uint2* child = b.inner_child.as<uint2>();
     uint32_t *parent = b.parent.as<uint32_t>(), *order = b.vals[0].as<uint32_t>();
-    hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, flatten_args(b, n, n_inst));
+    hipLaunchKernelGGL(flatten_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, flatten_args(b, dm, n, n_inst));
     hipLaunchKernelGGL(morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, b.box.as<float>(), b.cent.as<float>(), hdr, b.keys[0].as<uint64_t>(), order);
     if (const int rc = sort_pairs(b, n, nb, st, err)) return rc;
     // with a restructuring, tri_geom waits for the leaves' new positions
@@ -1760,7 +1847,7 @@ int device_bvh_build(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
 }
 
 int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const DevBuf& cur_nodes, const DevBuf& cur_geom,
-                     uint32_t n_nodes, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+                     uint32_t n_nodes, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err, DeviceMorph* dm)
 {
     const uint32_t n = sc.n_triangles;
     r = DeviceBvhResult();
@@ -1769,6 +1856,7 @@ int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         err = "device BVH refit: no device-built frame data of this scene";
         return HJR_ERR_DEVICE;
     }
+    if (const int rc = prepare_morph(b, sc, dm, st, err)) return rc;
     const std::vector<float> xf = pack_transforms(M, Mi, n_inst);
     if (!b.xf.upload(xf.data(), xf.size() * 4, st) || !b.lights.upload(lights, light_floats * 4, st) || !b.hdr.reserve(H_WORDS * 4) || !b.nodes.reserve(node_bytes) ||
         !b.tri_geom.reserve(geom_bytes) || !b.tri_shade.reserve((size_t)n * HJR_SHADE_F4 * 16) || !b.tri_inst.reserve((size_t)n * 4) ||
@@ -1776,7 +1864,7 @@ int device_bvh_refit(DeviceBvh& b, const SceneCopy& sc, const float* M, const fl
         return fail_alloc(err);
     uint32_t* hdr = b.hdr.as<uint32_t>();
     const float4* refs = cur_nodes.as<float4>() + 6; // only the refs rows and the prim ids of the current frame data are read
-    LeafFlattenArgs fa = { flatten_args(b, n, n_inst), cur_geom.as<float4>(), nullptr, nullptr, b.tri_geom.as<float4>(), nullptr };
+    LeafFlattenArgs fa = { flatten_args(b, dm, n, n_inst), cur_geom.as<float4>(), nullptr, nullptr, b.tri_geom.as<float4>(), nullptr };
     NodeBoxArgs na = { n, n_nodes, refs, HJR_NODE4_F4, false, b.tri_geom.as<float4>(), b.nodes.as<float4>(), b.parent.as<uint32_t>(), b.counter.as<uint32_t>(), hdr };
     DCHK(hipEventRecord(b.ev0, st));
     hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(64), 0, st, hdr);
@@ -1833,8 +1921,8 @@ static int build_skeleton(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t le
 
 // The topology of option "device_bvh_instances" into b.topo (kernel comment above); the object-space scene is on the device and the
 // build's scratch is reserved.  One host wait; b.topo.ms is its HIP-event time.
-static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds, bool graft, const std::vector<uint32_t>& list,
-                          hipStream_t st, std::string& err)
+static int build_topology(DeviceBvh& b, const DeviceMorph* dm, uint32_t n, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds, bool graft,
+                          const std::vector<uint32_t>& list, hipStream_t st, std::string& err)
 {
     DeviceBvh::Topology& T = b.topo;
     T.valid = false;
@@ -1858,7 +1946,7 @@ static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t le
     DCHK(hipMemsetAsync(bmin, 0xff, (size_t)n_inst * 12, st));
     DCHK(hipMemsetAsync(bmax, 0, (size_t)n_inst * 12, st));
     DCHK(hipMemsetAsync(T.root.p, 0xff, (size_t)n_inst * 4, st));
-    hipLaunchKernelGGL(obj_box_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, flatten_args(b, n, n_inst), bmin, bmax); // tri_inst: scratch until the commit's flatten
+    hipLaunchKernelGGL(obj_box_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, flatten_args(b, dm, n, n_inst), bmin, bmax); // tri_inst: scratch until the commit's flatten
     hipLaunchKernelGGL(obj_morton_kernel, dim3(blocks_for(n)), dim3(NT), 0, st, n, b.cent.as<float>(), b.tri_inst.as<uint32_t>(), bmin, bmax, bits, keys, vals);
     if (const int rc = sort_pairs(b, n, nb, st, err)) return rc;
     DCHK(hipMemcpyAsync(T.order.p, vals, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
@@ -1898,18 +1986,19 @@ static int build_topology(DeviceBvh& b, uint32_t n, uint32_t n_inst, uint32_t le
 }
 
 int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, uint32_t leaf_max, uint32_t opt_rounds,
-                         uint32_t tag, bool graft, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err)
+                         uint32_t tag, bool graft, const float* lights, size_t light_floats, hipStream_t st, DeviceBvhResult& r, std::string& err, DeviceMorph* dm)
 {
     const uint32_t n = sc.n_triangles;
     std::vector<uint32_t> list; // the non-empty instances
     for (uint32_t i = 0; i < n_inst && i < sc.prim_offset.size(); i++)
         if ((i + 1 < n_inst && i + 1 < sc.prim_offset.size() ? sc.prim_offset[i + 1] : n) > sc.prim_offset[i]) list.push_back(i);
-    auto ordinary = [&] { return device_bvh_build(b, sc, M, Mi, n_inst, leaf_max, opt_rounds, lights, light_floats, st, r, err); };
+    auto ordinary = [&] { return device_bvh_build(b, sc, M, Mi, n_inst, leaf_max, opt_rounds, lights, light_floats, st, r, err, dm); };
     if (n == 0 || list.empty() || list.size() > HJR_TOP_MAX) return ordinary();
     r = DeviceBvhResult();
     if (!b.ev0) DCHK(hipEventCreate(&b.ev0));
     if (!b.ev1) DCHK(hipEventCreate(&b.ev1));
     if (!upload_scene(b, sc, st)) return fail_alloc(err);
+    if (const int rc = prepare_morph(b, sc, dm, st, err)) return rc;
     const std::vector<float> xf = pack_transforms(M, Mi, n_inst);
     const size_t nn = n;
     const uint32_t nb = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
@@ -1923,14 +2012,14 @@ int device_bvh_instances(DeviceBvh& b, const SceneCopy& sc, const float* M, cons
         if (!b.box.reserve(nn * 32) || !b.cent.reserve(nn * 16) || !b.keys[0].reserve(nn * 8) || !b.keys[1].reserve(nn * 8) || !b.vals[0].reserve(nn * 4) ||
             !b.vals[1].reserve(nn * 4) || !b.hist.reserve(std::max<size_t>(1, (size_t)nb * 256 * 4)) || !b.node_count.reserve(nn * 4) || !b.node_cost.reserve(nn * 4))
             return fail_alloc(err);
-        if (const int rc = build_topology(b, n, n_inst, leaf_max, opt_rounds, graft, list, st, err)) return rc;
+        if (const int rc = build_topology(b, dm, n, n_inst, leaf_max, opt_rounds, graft, list, st, err)) return rc;
         T.tag = tag;
     }
     const uint32_t k = T.k;
     uint32_t* hdr = b.hdr.as<uint32_t>();
     if (graft && T.skel_deep) return ordinary(); // an instance tree deeper than the traversal stack
     // under device_bvh_graft no leaf boxes: the skeleton's boxes come from tri_geom
-    LeafFlattenArgs fa = { flatten_args(b, n, n_inst), nullptr, T.order.as<uint32_t>(), T.pos.as<uint32_t>(), b.tri_geom.as<float4>(),
+    LeafFlattenArgs fa = { flatten_args(b, dm, n, n_inst), nullptr, T.order.as<uint32_t>(), T.pos.as<uint32_t>(), b.tri_geom.as<float4>(),
                            graft ? nullptr : b.leaf_box.as<float4>() };
     if (graft) { // flatten, skeleton boxes, top tree, placement, cost: one host wait
         const uint32_t S = T.n_skel;

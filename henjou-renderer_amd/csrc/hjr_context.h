@@ -147,6 +147,18 @@ struct hjr_ctx {
         int mode = 0;
     } tmp;
     hjr::Options opt; // hjr_set_option (host/options.hpp): the library reads no environment variable
+    // Deforming meshes (hjr_update_vertices, hjr_set_morph, hjr_set_morph_weights).  Kept behind everything else, so that no
+    // field the render units read moves.  `gen` counts the geometry: frame data is "unchanged" only when it was built from the current one.
+    struct Deform {
+        hjr::Morph morph;              // hjr_set_morph's copy; morph.weights: as last set
+        uint64_t gen = 0;              // bumped by every call that changes the base, the sets or the weights
+        uint64_t built_gen = 0;        // of the current frame data
+        uint64_t prep_gen = 0;         // of the prepared frame
+        std::vector<float> prep_w;     // device builder: the weights the prepared frame's light table was blended with; its commit blends with them
+        uint32_t prep_vertices = 0;    // host builder: vertices the prepare blended
+        std::vector<float> vert, norm; // host builder: the working copy build_frame reads (empty without a morph)
+        hjr::DeviceMorph dev;          // device builder: deltas, weights and working arrays
+    } deform;
 };
 
 // One render launch as hjr_render.hip::plan_launch decided it: all but the occupancy query and the buffers sized by the grid

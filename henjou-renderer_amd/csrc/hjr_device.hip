@@ -85,6 +85,7 @@ extern "C" void hjr_destroy(hjr_ctx* c)
     if (c->ad.h_active) (void)hipHostFree(c->ad.h_active);
     if (c->ad.ready) (void)hipEventDestroy(c->ad.ready);
     c->dbvh.release();
+    c->deform.dev.drop();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -129,6 +130,71 @@ extern "C" int hjr_upload_scene(hjr_ctx* c, const hjr_scene_view* v)
     c->dbvh.have_scene = false; // the device builder uploads the new scene at its next build
     c->dbvh.topo.valid = false; // ... and "device_bvh_instances" builds its topology again
     c->refit = hjr_ctx::Refit(); // ... which is a full one
+    c->deform.morph = hjr::Morph(); // the morph belonged to the scene before
+    c->deform.dev.drop();
+    c->deform.vert = std::vector<float>(); c->deform.norm = std::vector<float>();
+    c->deform.gen++;
+    return HJR_OK;
+}
+
+// ---- deforming meshes (include/henjou_hip.h) ----
+// what the three calls share once their arguments are accepted: the geometry is another one
+static void geometry_changed(hjr_ctx* c)
+{
+    c->deform.gen++;            // the next prepare is not "unchanged"
+    c->frame_gen++;             // an unfinished progressive frame ends (as hjr_set_sky)
+    c->tmp.have_prev = false;   // temporal history: reprojection is rigid per instance and cannot follow a deforming surface
+    c->dbvh.topo.valid = false; // "device_bvh_instances": the topology is built again at the next commit
+}
+
+extern "C" int hjr_update_vertices(hjr_ctx* c, uint32_t first_vertex, uint32_t n_vertices, const float* positions, const float* normals)
+{
+    if (!c) { set_error("hjr_update_vertices: null context"); return HJR_ERR_ARG; }
+    if (!c->have_scene) { set_error("hjr_update_vertices: no scene uploaded"); return HJR_ERR_STATE; }
+    if (!positions) { set_error("hjr_update_vertices: null positions"); return HJR_ERR_ARG; }
+    const size_t nv = c->scene.vertices.size() / 3;
+    if (n_vertices == 0 || (uint64_t)first_vertex + n_vertices > nv) { set_error("hjr_update_vertices: vertex range outside the scene"); return HJR_ERR_ARG; }
+    const size_t off = 3 * (size_t)first_vertex, bytes = 12 * (size_t)n_vertices;
+    if (c->dbvh.have_scene) { // the device builder's copy of the base; nothing a render reads
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipMemcpyAsync(c->dbvh.vert.as<float>() + off, positions, bytes, hipMemcpyHostToDevice, c->stream));
+        if (normals) HIPCHK(hipMemcpyAsync(c->dbvh.norm.as<float>() + off, normals, bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream)); // the caller's arrays are free on return
+    }
+    memcpy(&c->scene.vertices[off], positions, bytes);
+    if (normals) memcpy(&c->scene.normals[off], normals, bytes);
+    c->deform.dev.copied = false; // the working arrays of a morph: from the new base
+    geometry_changed(c);
+    return HJR_OK;
+}
+
+extern "C" int hjr_set_morph(hjr_ctx* c, const hjr_morph* m)
+{
+    if (!c) { set_error("hjr_set_morph: null context"); return HJR_ERR_ARG; }
+    if (!c->have_scene) { set_error("hjr_set_morph: no scene uploaded"); return HJR_ERR_STATE; }
+    hjr_morph mm;
+    if (m) { if (!hjr::abi_take(m, mm, "hjr_set_morph")) return HJR_ERR_ARG; }
+    else { memset(&mm, 0, sizeof(mm)); }
+    std::string err;
+    if (!c->deform.morph.set(mm, (uint32_t)(c->scene.vertices.size() / 3), err)) { set_error("hjr_set_morph: " + err); return HJR_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    c->deform.dev.drop(); // deltas, table and working arrays: uploaded at the next device build (none without a morph)
+    if (!c->deform.morph.active()) { c->deform.vert = std::vector<float>(); c->deform.norm = std::vector<float>(); }
+    geometry_changed(c);
+    return HJR_OK;
+}
+
+extern "C" int hjr_set_morph_weights(hjr_ctx* c, const float* w, uint32_t n)
+{
+    if (!c) { set_error("hjr_set_morph_weights: null context"); return HJR_ERR_ARG; }
+    hjr::Morph& mo = c->deform.morph;
+    if (!mo.active()) { set_error("hjr_set_morph_weights: no morph set"); return HJR_ERR_STATE; }
+    if (n != mo.weights.size()) { set_error("hjr_set_morph_weights: weight count does not match the morph's n_weights"); return HJR_ERR_ARG; }
+    if (n && !w) { set_error("hjr_set_morph_weights: null weights"); return HJR_ERR_ARG; }
+    const bool equal = n == 0 || memcmp(mo.weights.data(), w, (size_t)n * 4) == 0;
+    if (n) memcpy(mo.weights.data(), w, (size_t)n * 4);
+    if (equal) { c->frame_gen++; c->tmp.have_prev = false; } // the same bits: the same geometry, so frame data and topology built from it stay current
+    else geometry_changed(c);
     return HJR_OK;
 }
 
@@ -166,7 +232,8 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
     // unchanged instance transforms (static geometry, e.g. a camera-only animation): the world-space arrays and the BVH of the
     // previous frame are still right; the reference re-uploads its IAS every frame (renderer.h:257-291), which costs it nothing
     const bool force_rebuild = c->opt.get(hjr::OPT_FORCE_REBUILD, 0) != 0; // benchmarking option
-    if (!force_rebuild && c->have_frame && c->built.key == key && c->built.m.size() == (size_t)n * 12 && n == c->scene.n_instances &&
+    hjr_ctx::Deform& df = c->deform;
+    if (!force_rebuild && c->have_frame && df.built_gen == df.gen && c->built.key == key && c->built.m.size() == (size_t)n * 12 && n == c->scene.n_instances &&
         (n == 0 || (memcmp(c->built.m.data(), m, (size_t)n * 48) == 0 && memcmp(c->built.inv.data(), inv, (size_t)n * 48) == 0))) {
         pp.same = true;
         pp.valid = true;
@@ -179,8 +246,18 @@ extern "C" int hjr_prepare_transforms(hjr_ctx* c, const float* m, const float* i
         pp.frame.n_tris = c->scene.n_triangles;
         pp.frame.width = 4;
         pp.frame.lds_mode = 0;
-        hjr::build_lights(c->scene, m, inv, pp.frame);
-    } else if (!hjr::build_frame(c->scene, m, inv, n, bo, pp.frame, err)) { set_error("hjr_set_transforms: " + err); return HJR_ERR_ARG; }
+        df.prep_w = df.morph.weights;
+        hjr::build_lights(c->scene, m, inv, pp.frame, nullptr, nullptr, &df.morph, df.prep_w.data()); // a morph: only the light triangles' vertices are blended here
+    } else {
+        const bool morphed = df.morph.active(); // the working copy, on the worker threads; without a morph no copy and no pass
+        if (morphed) hjr::morph_blend(c->scene, df.morph, df.morph.weights.data(), df.vert, df.norm);
+        df.prep_vertices = morphed ? df.morph.n_vertices : 0u;
+        if (!hjr::build_frame(c->scene, m, inv, n, bo, pp.frame, err, morphed ? df.vert.data() : nullptr, morphed ? df.norm.data() : nullptr)) {
+            set_error("hjr_set_transforms: " + err);
+            return HJR_ERR_ARG;
+        }
+    }
+    df.prep_gen = df.gen;
     pp.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
     pp.m.assign(m, m + (size_t)n * 12); pp.inv.assign(inv, inv + (size_t)n * 12); pp.key = key;
     pp.valid = true;
@@ -209,12 +286,14 @@ static int commit_device(hjr_ctx* c, uint32_t& instances)
     hjr::DeviceBvhResult r;
     std::string err;
     hjr::FrameData& f = pp.frame;
+    hjr::DeviceMorph* dm = &c->deform.dev; // hjr_set_morph: blended on the stream ahead of the flatten of whichever build runs
+    dm->host = &c->deform.morph; dm->w_next = c->deform.morph.active() ? c->deform.prep_w.data() : nullptr; dm->launched = 0;
     const int rc = pp.key.instances ? hjr::device_bvh_instances(c->dbvh, c->scene, pp.m.data(), pp.inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds, tag, pp.key.graft,
-                                                                f.lights.data(), f.lights.size(), c->stream, r, err)
+                                                                f.lights.data(), f.lights.size(), c->stream, r, err, dm)
                    : refit ? hjr::device_bvh_refit(c->dbvh, c->scene, pp.m.data(), pp.inv.data(), n_inst, c->d_nodes, c->d_tri_geom, c->frame.n_nodes,
-                                                 f.lights.data(), f.lights.size(), c->stream, r, err)
+                                                 f.lights.data(), f.lights.size(), c->stream, r, err, dm)
                          : hjr::device_bvh_build(c->dbvh, c->scene, pp.m.data(), pp.inv.data(), n_inst, (uint32_t)leaf_max, (uint32_t)opt_rounds,
-                                                 f.lights.data(), f.lights.size(), c->stream, r, err);
+                                                 f.lights.data(), f.lights.size(), c->stream, r, err, dm);
     if (rc != HJR_OK) { set_error("hjr_set_transforms: " + err); return rc; }
     c->d_nodes.swap(c->dbvh.nodes); c->d_tri_geom.swap(c->dbvh.tri_geom); c->d_tri_shade.swap(c->dbvh.tri_shade);
     c->d_tri_inst.swap(c->dbvh.tri_inst); c->d_lights.swap(c->dbvh.lights);
@@ -241,6 +320,7 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
     pp.valid = false;
     if (pp.same) {
         if (c->opt.get(hjr::OPT_VERBOSE, 0)) fprintf(stderr, "[hjr] transforms unchanged: frame data reused\n");
+        c->stats.morph_vertices = 0; // nothing was blended for this commit
         return HJR_OK;
     }
     HIPCHK(hipSetDevice(c->device));
@@ -265,6 +345,10 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
     const hjr::FrameData& f = c->frame;
     c->have_frame = true;
     c->built.m.swap(pp.m); c->built.inv.swap(pp.inv); c->built.key = pp.key;
+    if (c->deform.built_gen != c->deform.prep_gen) c->tmp.have_prev = false; // the geometry takes effect here: a render since the call has made a history of the old one
+    c->deform.built_gen = c->deform.prep_gen;
+    c->stats.morph_vertices = pp.key.device ? c->deform.dev.launched : c->deform.prep_vertices;
+    c->stats.geometry_generation = c->deform.built_gen;
     c->stats.bvh_nodes = f.n_nodes;
     c->stats.bvh_depth = f.depth;
     c->stats.bvh_builder = pp.key.device ? 1u : 0u;
@@ -278,6 +362,9 @@ extern "C" int hjr_commit_transforms(hjr_ctx* c)
         fprintf(stderr, "[hjr] BVH%u (lds_mode %d): %u nodes (%zu KB), %u triangles (%zu KB), stack %u entries/lane, %s %s %.1f ms\n", f.width, f.lds_mode, f.n_nodes,
                 (size_t)f.n_nodes * (f.width == 2 ? HJR_NODE2_F4 : HJR_NODE4_F4) * 16 / 1024, f.n_tris, (size_t)std::max(f.n_tris, 1u) * HJR_TRI_F4 * 16 / 1024,
                 f.stack_need, pp.key.device ? "device" : "host", refitted ? "refit" : (instances ? (pp.key.graft ? "grafted instance build" : "instance build") : "build"), pp.build_ms);
+    if (c->opt.get(hjr::OPT_VERBOSE, 0) && c->stats.morph_vertices)
+        fprintf(stderr, "[hjr] morph: %u vertices blended%s", c->stats.morph_vertices, pp.key.device ? "" : " on the host\n");
+    if (c->opt.get(hjr::OPT_VERBOSE, 0) && c->stats.morph_vertices && pp.key.device) fprintf(stderr, " on the device, kernel %.4f ms\n", c->deform.dev.kernel_ms());
     c->stats.n_triangles = f.n_tris;
     return HJR_OK;
 }

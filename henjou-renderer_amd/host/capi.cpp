@@ -115,6 +115,28 @@ extern "C" int hjr_scene_get_view(const hjr_scene* s, hjr_scene_view* v)
     return hjr::abi_give(user, full, "hjr_scene_get_view") ? HJR_OK : HJR_ERR_ARG;
 }
 
+extern "C" int hjr_scene_get_morph(const hjr_scene* s, hjr_morph* out)
+{
+    if (!s || !out) { set_error("hjr_scene_get_morph: null argument"); return HJR_ERR_ARG; }
+    const hjr::SceneData& d = s->data;
+    hjr_morph full; // sized struct: borrowed pointers, valid as long as the scene; n_sets == 0: the file has no morph targets
+    memset(&full, 0, sizeof(full));
+    full.struct_size = (uint32_t)sizeof(full);
+    full.n_sets = (uint32_t)d.morph_views.size();
+    full.n_weights = (uint32_t)d.morph_default_weights.size();
+    full.sets = d.morph_views.empty() ? nullptr : d.morph_views.data();
+    full.default_weights = d.morph_default_weights.empty() ? nullptr : d.morph_default_weights.data();
+    return hjr::abi_give(out, full, "hjr_scene_get_morph") ? HJR_OK : HJR_ERR_ARG;
+}
+
+extern "C" int hjr_scene_eval_morph_weights(const hjr_scene* s, float time, float* w, uint32_t n)
+{
+    if (!s || (n && !w)) { set_error("hjr_scene_eval_morph_weights: null argument"); return HJR_ERR_ARG; }
+    if (n != s->data.morph_default_weights.size()) { set_error("hjr_scene_eval_morph_weights: weight count does not match the scene's n_weights"); return HJR_ERR_ARG; }
+    hjr::eval_morph_weights(s->data, time, w);
+    return HJR_OK;
+}
+
 extern "C" int hjr_scene_eval_transforms(const hjr_scene* s, float time, float* m12, float* inv12)
 {
     if (!s || ((!m12 || !inv12) && !s->data.instances.empty())) { set_error("hjr_scene_eval_transforms: null argument"); return HJR_ERR_ARG; }

@@ -496,9 +496,75 @@ void emit_bvh4(const Builder& B, FrameData& out)
 
 } // namespace
 
-// light table (light_sample.h:22-58, 69-72); both builders use it (the device path keeps it on the host: O(lights), double arithmetic)
-void build_lights(const SceneCopy& sc, const float* M, const float* Mi, FrameData& out)
+bool Morph::set(const hjr_morph& m, uint32_t scene_vertices, std::string& err)
 {
+    if (m.n_sets == 0) { *this = Morph(); return true; }
+    if (!m.sets) { err = "null sets"; return false; }
+    Morph r;
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;
+    for (uint32_t s = 0; s < m.n_sets; s++) {
+        const hjr_morph_set& in = m.sets[s];
+        const std::string who = "set " + std::to_string(s);
+        if (in.n_vertices == 0 || in.n_targets == 0) { err = who + ": no vertices or no targets"; return false; }
+        if ((uint64_t)in.first_vertex + in.n_vertices > scene_vertices) { err = who + ": vertex range outside the scene"; return false; }
+        if ((uint64_t)in.first_weight + in.n_targets > m.n_weights) { err = who + ": weights outside n_weights"; return false; }
+        if (!in.position_deltas) { err = who + ": null position_deltas"; return false; }
+        ranges.push_back({ in.first_vertex, (uint64_t)in.first_vertex + in.n_vertices });
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); i++)
+        if (ranges[i].first < ranges[i - 1].second) { err = "overlapping sets"; return false; }
+    for (uint32_t s = 0; s < m.n_sets; s++) {
+        const hjr_morph_set& in = m.sets[s];
+        const size_t n = (size_t)3 * in.n_targets * in.n_vertices;
+        MorphSet o = { in.first_vertex, in.n_vertices, in.n_targets, in.first_weight, r.deltas.size(), NONE };
+        r.deltas.insert(r.deltas.end(), in.position_deltas, in.position_deltas + n);
+        if (in.normal_deltas) { o.nrm = r.deltas.size(); r.deltas.insert(r.deltas.end(), in.normal_deltas, in.normal_deltas + n); }
+        r.sets.push_back(o);
+        r.n_vertices += in.n_vertices;
+    }
+    if (m.default_weights) r.weights.assign(m.default_weights, m.default_weights + m.n_weights);
+    else r.weights.assign(m.n_weights, 0.0f);
+    *this = std::move(r);
+    return true;
+}
+
+void morph_vertex(const SceneCopy& sc, const Morph& mo, const float* w, uint32_t vertex, float* p, float* n)
+{
+    for (int a = 0; a < 3; a++) { p[a] = sc.vertices[3 * (size_t)vertex + a]; n[a] = sc.normals[3 * (size_t)vertex + a]; }
+    for (const MorphSet& s : mo.sets) {
+        if (vertex < s.first_vertex || vertex - s.first_vertex >= s.n_vertices) continue;
+        const size_t i = 3 * (size_t)(vertex - s.first_vertex), stride = 3 * (size_t)s.n_vertices;
+        for (int a = 0; a < 3; a++) {
+            p[a] = morph_component(p[a], &mo.deltas[s.pos + i + a], stride, w + s.first_weight, s.n_targets);
+            if (s.nrm != Morph::NONE) n[a] = morph_component(n[a], &mo.deltas[s.nrm + i + a], stride, w + s.first_weight, s.n_targets);
+        }
+        return; // sets do not overlap
+    }
+}
+
+void morph_blend(const SceneCopy& sc, const Morph& mo, const float* w, std::vector<float>& vert, std::vector<float>& norm)
+{
+    vert = sc.vertices;
+    norm = sc.normals;
+    for (const MorphSet& s : mo.sets) {
+        const size_t stride = 3 * (size_t)s.n_vertices, first = 3 * (size_t)s.first_vertex;
+        const float* ws = w + s.first_weight;
+        parallel_chunks(stride, 3 * 16384, [&](size_t b, size_t e, size_t) { // element-wise over the set's components
+            for (size_t i = b; i < e; i++) {
+                vert[first + i] = morph_component(sc.vertices[first + i], &mo.deltas[s.pos + i], stride, ws, s.n_targets);
+                if (s.nrm != Morph::NONE) norm[first + i] = morph_component(sc.normals[first + i], &mo.deltas[s.nrm + i], stride, ws, s.n_targets);
+            }
+        });
+    }
+}
+
+// light table (light_sample.h:22-58, 69-72); both builders use it (the device path keeps it on the host: O(lights), double arithmetic)
+void build_lights(const SceneCopy& sc, const float* M, const float* Mi, FrameData& out, const float* vert, const float* norm, const Morph* mo, const float* w)
+{
+    const float* const V = vert ? vert : sc.vertices.data();
+    const float* const N = norm ? norm : sc.normals.data();
+    const bool per_vertex = !vert && mo && mo->active() && w; // the device builder's prepare: no working copy on the host
     const uint32_t nl = (uint32_t)sc.light_prim_ids.size();
     out.n_lights = nl;
     out.lights.assign((size_t)nl * HJR_LIGHT_F4 * 4, 0.0f);
@@ -511,8 +577,10 @@ void build_lights(const SceneCopy& sc, const float* M, const float* Mi, FrameDat
         V3 v[3], nn[3];
         for (int k = 0; k < 3; k++) {
             uint32_t idx = sc.indices[3 * prim + k];
-            v[k] = transform_position(m, { sc.vertices[3 * idx], sc.vertices[3 * idx + 1], sc.vertices[3 * idx + 2] });
-            nn[k] = transform_normal(mi, { sc.normals[3 * idx], sc.normals[3 * idx + 1], sc.normals[3 * idx + 2] });
+            float p[3] = { V[3 * (size_t)idx], V[3 * (size_t)idx + 1], V[3 * (size_t)idx + 2] }, q[3] = { N[3 * (size_t)idx], N[3 * (size_t)idx + 1], N[3 * (size_t)idx + 2] };
+            if (per_vertex) morph_vertex(sc, *mo, w, idx, p, q);
+            v[k] = transform_position(m, { p[0], p[1], p[2] });
+            nn[k] = transform_normal(mi, { q[0], q[1], q[2] });
         }
         V3 c = cross(sub(v[1], v[0]), sub(v[2], v[0]));
         float area = sqrtf(dot(c, c)) * 0.5f;
@@ -533,8 +601,11 @@ void build_lights(const SceneCopy& sc, const float* M, const float* Mi, FrameDat
 
 void set_host_threads(int n) { g_host_threads.store(n > 0 ? n : 0, std::memory_order_relaxed); }
 
-bool build_frame(const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const BuildOptions& bo, FrameData& out, std::string& err)
+bool build_frame(const SceneCopy& sc, const float* M, const float* Mi, uint32_t n_inst, const BuildOptions& bo, FrameData& out, std::string& err,
+                 const float* vert, const float* norm)
 {
+    const float* const V = vert ? vert : sc.vertices.data();
+    const float* const N = norm ? norm : sc.normals.data();
     const bool allow_lds = bo.allow_lds;
     if (n_inst != sc.n_instances) { err = "instance count does not match the uploaded scene"; return false; }
     const uint32_t n = sc.n_triangles;
@@ -564,8 +635,8 @@ bool build_frame(const SceneCopy& sc, const float* M, const float* Mi, uint32_t 
             float uv[6];
             for (int k = 0; k < 3; k++) {
                 uint32_t idx = sc.indices[3 * t + k];
-                V3 v = transform_position(m, { sc.vertices[3 * idx], sc.vertices[3 * idx + 1], sc.vertices[3 * idx + 2] });
-                V3 nn = normalize(transform_normal(mi, { sc.normals[3 * idx], sc.normals[3 * idx + 1], sc.normals[3 * idx + 2] }));
+                V3 v = transform_position(m, { V[3 * (size_t)idx], V[3 * (size_t)idx + 1], V[3 * (size_t)idx + 2] });
+                V3 nn = normalize(transform_normal(mi, { N[3 * (size_t)idx], N[3 * (size_t)idx + 1], N[3 * (size_t)idx + 2] }));
                 wv[9 * t + 3 * k + 0] = v.x; wv[9 * t + 3 * k + 1] = v.y; wv[9 * t + 3 * k + 2] = v.z;
                 s[4 * k + 0] = nn.x; s[4 * k + 1] = nn.y; s[4 * k + 2] = nn.z;
                 uv[2 * k] = sc.texcoords[2 * idx]; uv[2 * k + 1] = sc.texcoords[2 * idx + 1];
@@ -578,7 +649,7 @@ bool build_frame(const SceneCopy& sc, const float* M, const float* Mi, uint32_t 
     });
 
     lap("flatten");
-    build_lights(sc, M, Mi, out);
+    build_lights(sc, M, Mi, out, V, N);
 
     // BVH over padded triangle boxes
     Builder B;

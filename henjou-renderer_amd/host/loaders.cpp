@@ -488,6 +488,7 @@ bool load_gltf(const std::string& dir, const std::string& file, SceneData& sc, h
                 sc.prim_offset.push_back(gas.index_offset / 3);
                 uint32_t prim_id = (uint32_t)(sc.vertices.size() / 3);
                 const Json& prims = meshj.at("primitives");
+                int morph_block = -1; // morph targets: the node's weight block, made by its first primitive with `targets`
                 for (size_t pi = 0; pi < prims.size(); pi++) {
                     const Json& prim = prims.at(pi);
                     int ind_acc = (int)prim.int_or("indices", -1);
@@ -517,6 +518,53 @@ bool load_gltf(const std::string& dir, const std::string& file, SceneData& sc, h
                     if (const Json* a = attrs.find("NORMAL")) m.span((int)a->as_int(), np, nstride, ncount, 12);
                     if (const Json* a = attrs.find("TEXCOORD_0")) m.span((int)a->as_int(), tp, tstride, tcount, 8);
                     if (!vp) throw JsonError("primitive without POSITION");
+                    // ---- morph targets: POSITION and optionally NORMAL deltas, de-indexed exactly as the vertices below
+                    const Json* targets = prim.find("targets");
+                    if (targets && targets->is_array() && targets->size()) {
+                        const size_t K = targets->size();
+                        if (morph_block < 0) {
+                            SceneData::MorphBlock blk;
+                            blk.node = (uint32_t)node_index; blk.first_weight = (uint32_t)sc.morph_default_weights.size(); blk.n_targets = (uint32_t)K;
+                            const Json* mw = meshj.find("weights");
+                            MorphWeights w0;
+                            for (size_t k = 0; k < K; k++) w0.w.push_back((float)arr_or(mw, k, 0.0));
+                            sc.morph_default_weights.insert(sc.morph_default_weights.end(), w0.w.begin(), w0.w.end());
+                            blk.track.push(0, w0);
+                            morph_block = (int)sc.morph_blocks.size();
+                            sc.morph_blocks.push_back(std::move(blk));
+                        } else if (sc.morph_blocks[(size_t)morph_block].n_targets != K)
+                            throw JsonError("the primitives of a mesh have different numbers of morph targets");
+                        SceneData::MorphSetData set;
+                        set.first_vertex = (uint32_t)sc.vertices.size(); set.n_vertices = (uint32_t)(icount / 3 * 3); set.n_targets = (uint32_t)K;
+                        set.first_weight = sc.morph_blocks[(size_t)morph_block].first_weight;
+                        auto deltas = [&](const Json& tgt, const char* name, std::vector<float>& out, size_t k) {
+                            const Json* a = tgt.find(name);
+                            if (!a) return;
+                            const int acc = (int)a->as_int();
+                            if (acc < 0 || (size_t)acc >= m.accessors.size()) throw JsonError("accessor index out of range");
+                            if (m.accessors[(size_t)acc].componentType != 5126 || m.accessors[(size_t)acc].type != "VEC3" || j.at("accessors").at((size_t)acc).find("sparse"))
+                                throw JsonError(std::string("morph target ") + name + " must be a non-sparse FLOAT VEC3 accessor");
+                            const unsigned char* dp; size_t dstride, dcount;
+                            m.span(acc, dp, dstride, dcount, 12);
+                            if (out.empty()) out.assign(3 * K * (size_t)set.n_vertices, 0.0f);
+                            for (size_t v = 0; v < set.n_vertices; v++) {
+                                const unsigned int ix = index_at(v);
+                                if (ix >= dcount) throw JsonError("Tried to access beyond the last element of an array adapter");
+                                const unsigned char* p = dp + ix * dstride;
+                                for (int c = 0; c < 3; c++) out[3 * (k * set.n_vertices + v) + (size_t)c] = rd<float>(p + 4 * c);
+                            }
+                        };
+                        for (size_t k = 0; k < K; k++) {
+                            const Json& tgt = targets->at(k);
+                            for (auto& kv : tgt.obj)
+                                if (kv.first != "POSITION" && kv.first != "NORMAL" && kv.first != "TANGENT") throw JsonError("unsupported morph target attribute " + kv.first);
+                            if (!tgt.find("POSITION")) throw JsonError("morph target without POSITION");
+                            deltas(tgt, "POSITION", set.position_deltas, k);
+                            deltas(tgt, "NORMAL", set.normal_deltas, k); // a target without it: zeros, once another target has it
+                        }
+                        if (set.n_vertices) sc.morph_sets.push_back(std::move(set));
+                    } else if (morph_block >= 0)
+                        throw JsonError("the primitives of a mesh have different numbers of morph targets");
                     for (size_t tri = 0; tri < icount / 3; tri++) {
                         unsigned int idx[3] = { index_at(tri * 3), index_at(tri * 3 + 1), index_at(tri * 3 + 2) };
                         float3_ vert[3], norm[3];
@@ -609,11 +657,25 @@ bool load_gltf(const std::string& dir, const std::string& file, SceneData& sc, h
                             const float4_ v = { rd<float>(p), rd<float>(p + 4), rd<float>(p + 8), rd<float>(p + 12) };
                             a.rotation.push(key_at(k), v);
                         }
+                    } else if (path == "weights") { // keyframes of K floats into the node's weight block
+                        SceneData::MorphBlock* blk = nullptr;
+                        for (auto& b : sc.morph_blocks) if (b.node == (uint32_t)target_node) blk = &b;
+                        if (!blk) throw JsonError("a weights channel targets a node without morph targets");
+                        m.span((int)sampler.at("output").as_int(), dp, dstride, dcount, 4);
+                        const size_t K = blk->n_targets;
+                        for (size_t k = 0; k < dcount / K; k++) {
+                            MorphWeights v;
+                            for (size_t t = 0; t < K; t++) v.w.push_back(rd<float>(dp + (k * K + t) * dstride));
+                            blk->track.push(key_at(k), v);
+                        }
                     }
                 }
             }
         }
         sc.animations = animation;
+        for (auto& s : sc.morph_sets)
+            sc.morph_views.push_back(hjr_morph_set{ s.first_vertex, s.n_vertices, s.n_targets, s.first_weight, s.position_deltas.data(),
+                                                    s.normal_deltas.empty() ? nullptr : s.normal_deltas.data() });
         for (auto& t : sc.textures) sc.texture_views.push_back(hjr_texture{ t.rgba.data(), t.width, t.height, t.srgb, 0 });
         for (size_t i = 0; i < sc.instances.size(); i++) {
             sc.geo_index_offset.push_back(sc.geometries[sc.instances[i].geometry_id].index_offset);
@@ -628,6 +690,14 @@ bool load_gltf(const std::string& dir, const std::string& file, SceneData& sc, h
 }
 
 // ---------------------------------------------------------------- per-frame evaluation
+void eval_morph_weights(const SceneData& sc, float time, float* w)
+{
+    for (const auto& b : sc.morph_blocks) {
+        const MorphWeights v = b.track.at(time);
+        for (uint32_t k = 0; k < b.n_targets; k++) w[b.first_weight + k] = v.w[k];
+    }
+}
+
 void affine_inverse_3x4(const float* m, float* inv)
 {
     // inverse of [A t; 0 1]: A^-1 by cofactors in double, t' = -A^-1 t; rounded once to float.

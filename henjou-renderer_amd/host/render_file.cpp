@@ -51,6 +51,8 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
     if (rc == HJR_OK) rc = hjr_upload_scene(ctx, &view);
     if (rc == HJR_OK && adaptive) rc = hjr::set_adaptive(ctx, opt);
     if (rc == HJR_OK) rc = hjr::upload_assets(ctx, opt, view, true);
+    std::vector<float> morph_w; // "morph_targets": the glTF's morph sets, once; the weights per frame below
+    if (rc == HJR_OK) rc = hjr::set_morph(ctx, opt, scene, morph_w);
     std::vector<float> m((size_t)view.n_instances * 12), inv((size_t)view.n_instances * 12);
     const size_t npx = (size_t)job.out_w * job.out_h; // (the window's size with "window")
     // Output stage off the critical path: float4 -> sRGB8 -> PNG -> file runs on a writer thread while the main thread
@@ -111,13 +113,21 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
         prep_rc = hjr_prepare_transforms(ctx, m.data(), inv.data(), view.n_instances);
         if (prep_rc != HJR_OK) prep_err = hjr_last_error(); // thread-local on the helper thread
     };
-    if (opt.start_frame < opt.end_frame) prepare(opt.start_frame);
+    // "morph_targets": the weights of a frame are set on this thread before its prepare is started (and the previous one has been joined):
+    // hjr_set_morph_weights must not run concurrently with hjr_prepare_transforms.  It ends no frame: frame f has not begun its passes
+    auto weights = [&](uint32_t frame) { return hjr::set_morph_weights(ctx, scene, frame / float(opt.fps), morph_w); };
+    if (rc == HJR_OK && opt.start_frame < opt.end_frame) rc = weights(opt.start_frame);
+    if (rc == HJR_OK && opt.start_frame < opt.end_frame) prepare(opt.start_frame);
     for (uint32_t frame = opt.start_frame; rc == HJR_OK && frame < opt.end_frame; frame++) {
         if (prep.joinable()) prep.join();
         if (prep_rc != HJR_OK) { rc = prep_rc; set_error(prep_err); break; }
         rc = hjr_commit_transforms(ctx);
         if (rc != HJR_OK) break;
-        if (frame + 1 < opt.end_frame && !serial_io) prep = std::thread(prepare, frame + 1);
+        if (frame + 1 < opt.end_frame && !serial_io) {
+            rc = weights(frame + 1);
+            if (rc != HJR_OK) break;
+            prep = std::thread(prepare, frame + 1);
+        }
         hjr_params_window pw; // (the longer caller: the render window behind hjr_params)
         memset(&pw, 0, sizeof(pw));
         hjr_params& p = pw.p;
@@ -195,7 +205,7 @@ extern "C" int hjr_render_file(const char* render_option_json, int device)
                 kernel_ms, kernel_ms > 0 ? (double)job.w * job.h * p.spp / (kernel_ms * 1e3) : 0.0, note.c_str());
         sl.name = hjr::frame_png_name(opt, frame);
         n_frames++;
-        if (serial_io) { rc = write_slot(sl); if (rc != HJR_OK) set_error(write_err); if (rc == HJR_OK && frame + 1 < opt.end_frame) prepare(frame + 1); }
+        if (serial_io) { rc = write_slot(sl); if (rc != HJR_OK) set_error(write_err); if (rc == HJR_OK && frame + 1 < opt.end_frame) rc = weights(frame + 1); if (rc == HJR_OK && frame + 1 < opt.end_frame) prepare(frame + 1); }
         else {
             { std::lock_guard<std::mutex> lk(mu); sl.full = true; }
             cv.notify_all();

@@ -44,6 +44,7 @@ enum KeyWho : uint8_t {
     WHO_FILTER,         // the process that filters and upscales: the single one, rank 0 of a world
     WHO_FILTER_DENOISE, // ... and in Render_mode Denoise / DenoiseUpScale2X only (Default mode has no filter)
     WHO_SINGLE,         // hjr_render_file only
+    WHO_DRIVER,         // no context option: the drivers read the key themselves (key_get)
 };
 struct KeyRow {
     const char* key;   // the key of the section AND the context option it sets (hjr_set_option): they share their names
@@ -90,7 +91,10 @@ inline const std::vector<KeyRow>& key_table_since()
         { "denoise_temporal_response", 14, &O::device_bvh_opt, ENC_BITS, 24, 1, READ_BOOL, nullptr, WHO_FILTER },
         // (likewise in front of the moments row, which moves up a turn to stay the latest; its turn number is pinned by nobody, its rank is)
         { "adaptive_temporal", 15, &O::device_bvh_opt, ENC_BITS, 25, 1, READ_BOOL, "denoise_temporal", WHO_FILTER },
-        { "denoise_temporal_moments", 16, &O::device_bvh_opt, ENC_BITS, 15, 1, READ_BOOL, nullptr, WHO_FILTER },
+        // (in front of the moments row, which moves up a turn once more.)  "morph_targets": the drivers hand the glTF's morph targets and, per
+        // frame, its evaluated weights to the context (set_morph, set_morph_weights below); the next spare bit of the packed section
+        { "morph_targets", 16, &O::device_bvh_opt, ENC_BITS, 26, 1, READ_BOOL, nullptr, WHO_DRIVER },
+        { "denoise_temporal_moments", 17, &O::device_bvh_opt, ENC_BITS, 15, 1, READ_BOOL, nullptr, WHO_FILTER },
     };
     return t;
 }
@@ -256,6 +260,34 @@ inline int upload_assets(hjr_ctx* ctx, const hjr_render_option& o, const hjr_sce
     if (hjr_load_hdr_rgba32f(o.IBL_path, &sky, &w, &h) == HJR_OK) rc = hjr_set_sky(ctx, sky, w, h);
     else if (note) fprintf(stderr, "[henjou] %s NOT FOUND: using scene_sky_default\n", o.IBL_path);
     hjr_free(sky);
+    return rc;
+}
+
+// "morph_targets": the scene's morph sets into the context, once after the upload; `weights` (those the context holds) stays empty without
+// the key or without targets in the file, and then nothing is set (the drop-in default: the reference ignores morph data and renders the
+// rest pose)
+inline int set_morph(hjr_ctx* ctx, const hjr_render_option& o, const hjr_scene* scene, std::vector<float>& weights)
+{
+    weights.clear();
+    if (!key_get(o, key_row("morph_targets"))) return HJR_OK;
+    hjr_morph mo;
+    HJR_INIT(mo);
+    int rc = hjr_scene_get_morph(scene, &mo);
+    if (rc != HJR_OK || mo.n_sets == 0) return rc;
+    rc = hjr_set_morph(ctx, &mo);
+    if (rc == HJR_OK) weights.assign(mo.default_weights, mo.default_weights + mo.n_weights);
+    return rc;
+}
+// ... and per frame the weights at the frame's time, BEFORE that frame's hjr_prepare_transforms is started and never while one runs.
+// Weights that did not change are not set again, so a stretch of the animation that does not deform keeps its temporal history
+inline int set_morph_weights(hjr_ctx* ctx, const hjr_scene* scene, float time, std::vector<float>& weights)
+{
+    if (weights.empty()) return HJR_OK;
+    std::vector<float> w(weights.size());
+    int rc = hjr_scene_eval_morph_weights(scene, time, w.data(), (uint32_t)w.size());
+    if (rc != HJR_OK || memcmp(w.data(), weights.data(), w.size() * sizeof(float)) == 0) return rc;
+    rc = hjr_set_morph_weights(ctx, w.data(), (uint32_t)w.size());
+    if (rc == HJR_OK) weights.swap(w);
     return rc;
 }
 

@@ -111,6 +111,12 @@ struct NodeMotion {
     void rotation3x3(float time, float r[3][3]) const { rotation_rows(rotation.empty() ? float4_{ 0, 0, 0, 0 } : rotation.at(time), r); }
 };
 
+// The weights of one morphed mesh node at a key: Track<MorphWeights> samples them like every other channel (linear, component-wise,
+// every product rounded, then the sum).  No reference counterpart: the reference ignores morph data.
+struct MorphWeights { std::vector<float> w; };
+inline MorphWeights operator*(const MorphWeights& a, float s) { MorphWeights r = a; for (float& x : r.w) x = x * s; return r; }
+inline MorphWeights operator+(const MorphWeights& a, const MorphWeights& b) { MorphWeights r = a; for (size_t i = 0; i < r.w.size() && i < b.w.size(); i++) r.w[i] = r.w[i] + b.w[i]; return r; }
+
 struct GeometryData { uint32_t index_offset, index_count; };   // scene.h:9-12
 struct InstanceData { uint32_t geometry_id, animation_id; };   // scene.h:14-17
 
@@ -134,6 +140,14 @@ struct SceneData { // scene.h:19-36
     std::vector<uint32_t> prim_offset;
     // flattened per-instance columns for the C view
     std::vector<uint32_t> geo_index_offset, geo_index_count, inst_animation_id;
+    // glTF morph targets (hjr_scene_get_morph, hjr_scene_eval_morph_weights).  One set per primitive with `targets`, de-indexed like its
+    // vertices, target-major; the primitives of one mesh node share the node's weight block.  `vertices` / `normals` stay the rest pose.
+    struct MorphSetData { uint32_t first_vertex = 0, n_vertices = 0, n_targets = 0, first_weight = 0; std::vector<float> position_deltas, normal_deltas; };
+    struct MorphBlock { uint32_t node = 0, first_weight = 0, n_targets = 0; Track<MorphWeights> track; }; // key 0: mesh.weights at time 0; "weights" channels behind it
+    std::vector<MorphSetData> morph_sets;
+    std::vector<MorphBlock> morph_blocks;
+    std::vector<float> morph_default_weights;
+    std::vector<hjr_morph_set> morph_views; // borrowed pointers into morph_sets
 };
 
 // 3x4 inverse of an affine matrix (replaces glm::inverse in renderer.h:274-283, whose exact rounding is not observable).
@@ -143,5 +157,6 @@ bool load_render_option(const std::string& path, hjr_render_option& opt, std::st
 bool load_gltf(const std::string& dir, const std::string& file, SceneData& scene, hjr_render_option& opt, std::string& err);
 void eval_transforms(const SceneData& scene, float time, float* m12, float* inv12);
 void eval_camera(const SceneData& scene, const hjr_render_option& opt, float time, hjr_camera& cam);
+void eval_morph_weights(const SceneData& scene, float time, float* w); // morph_default_weights.size() floats
 
 } // namespace hjr

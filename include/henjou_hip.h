@@ -29,7 +29,7 @@ extern "C" {
 #define HJR_ERR_STATE (-5)   /* call order violated (render before upload, ...) */
 
 /* ---- Sized structs (the rule that keeps callers and library binary-compatible across releases) --------------------------------
- * hjr_scene_view, hjr_render_option, hjr_params, hjr_stats, hjr_adaptive, hjr_adaptive_state and hjr_shards may GROW at their end in later releases.  Each starts with
+ * hjr_scene_view, hjr_render_option, hjr_params, hjr_stats, hjr_adaptive, hjr_adaptive_state, hjr_shards and hjr_morph may GROW at their end in later releases.  Each starts with
  * `struct_size`: the CALLER sets it to sizeof(its own struct) before handing the struct to ANY entry point, input or output
  * (HJR_INIT does it together with the zero fill).  The library copies min(struct_size, its own sizeof) bytes in either direction:
  *   - a field the caller's (older, shorter) struct does not have is never written and reads as 0, which selects the default;
@@ -146,7 +146,7 @@ typedef struct hjr_render_option {
     int32_t device_bvh_opt;      /* default 0; bits 0..7: key "device_bvh_opt", 0..3 treelet-restructuring rounds of that device build;
                                   * bit 8: key "device_bvh_instances"; bit 9: key "device_bvh_graft"; bit 10: key "denoise_variance_spatial";
                                   * bit 11: key "upscale_guided"; bits 12..14: key "denoise_temporal_coverage", 0, 2, 3 or 4; bits 16..22: key
-                                  * "firefly_clamp", 0..64; bit 23: key "firefly_clamp_passes"; bit 15: key "denoise_temporal_moments"; bit 24: key "denoise_temporal_response"; bit 25: key "adaptive_temporal" (bits 10 and up are the section's spare bits:
+                                  * "firefly_clamp", 0..64; bit 23: key "firefly_clamp_passes"; bit 15: key "denoise_temporal_moments"; bit 24: key "denoise_temporal_response"; bit 25: key "adaptive_temporal"; bit 26: key "morph_targets" (the drivers hand the glTF's morph targets and per-frame weights to the context; default false, as the reference ignores morph data) (bits 10 and up are the section's spare bits:
                                   * those keys have nothing to do with the BVH) */
     uint32_t passes;             /* default 1; 1..64: hjr_render_file / henjou_cli render each frame in this many sample passes, split at
                                   * boundaries rounded down to hjr_sample_granule (empty passes dropped); the PNG is unchanged ("passes") */
@@ -383,7 +383,30 @@ typedef struct hjr_stats {
     uint64_t firefly_clamped;    /* option "firefly_clamp": (pixel, chunk) pairs the last whole-frame launch scaled down (with "firefly_clamp_passes": those in the colours the last sample pass wrote); 0 when the rule did not act */
     uint32_t item_chunks;        /* chunks of a pixel per work item of the last render launch (option "item_chunks" as the launch resolved it; 1 for the wavefront kernels) */
     uint32_t _pad1;
+    uint32_t morph_vertices;     /* hjr_set_morph: vertices blended for the current frame data by the last commit; 0: no morph, or the blend was skipped
+                                  * (the commit reused the frame data, or the working arrays already held these weights over this base) */
+    uint32_t _pad2;
+    uint64_t geometry_generation; /* the geometry (hjr_update_vertices, hjr_set_morph, hjr_set_morph_weights) the current frame data was built from */
 } hjr_stats;
+
+/* ---------------- deforming meshes: per-frame vertex updates and morph targets ----------------
+ * A morph set deforms the vertex range [first_vertex, first_vertex + n_vertices) of the uploaded scene with n_targets targets under the
+ * weights w[first_weight .. first_weight + n_targets).  Per vertex and per component, in fp32, no contraction, in target order from the base:
+ *     p = base;  for k = 0 .. K-1:  p = p + w[k] * d[k]        (the product rounded, then the sum rounded; no target is skipped for a zero weight)
+ * Positions take position_deltas, normals normal_deltas (NULL: the set's normals stay at the base).  Normals are not renormalised here: the
+ * flatten normalises world normals.  Vertices outside every set keep the base bytes.  The base is what hjr_upload_scene supplied, as last
+ * overwritten by hjr_update_vertices.  Sets may share weights (the primitives of one glTF mesh do); sets must not overlap. */
+typedef struct hjr_morph_set {
+    uint32_t first_vertex, n_vertices, n_targets, first_weight;
+    const float* position_deltas; /* float3 x n_targets x n_vertices, target-major: target k of vertex i at 3 * (k * n_vertices + i) */
+    const float* normal_deltas;   /* the same shape, or NULL */
+} hjr_morph_set;                  /* 32 bytes, fixed layout */
+typedef struct hjr_morph {
+    uint32_t struct_size;         /* sizeof(hjr_morph) of the caller (HJR_INIT) */
+    uint32_t n_sets, n_weights, _pad0;
+    const hjr_morph_set* sets;    /* n_sets */
+    const float* default_weights; /* n_weights, or NULL: zeros */
+} hjr_morph;
 
 typedef struct hjr_scene hjr_scene; /* owning, host side (SceneData + animations) */
 typedef struct hjr_ctx hjr_ctx;     /* one per device */
@@ -404,6 +427,14 @@ void hjr_scene_free(hjr_scene*);
 int hjr_scene_get_view(const hjr_scene*, hjr_scene_view* out);
 /* Renderer::updateIASMatrix(time) — renderer/renderer.h:257-291: per instance Matrix4x3 + inverse, row-major 3x4 */
 int hjr_scene_eval_transforms(const hjr_scene*, float time, float* transforms12, float* inv_transforms12);
+/* glTF morph targets ("deforming meshes" above): one set per primitive with `targets` (POSITION and optionally NORMAL, non-sparse FLOAT
+ * VEC3; TANGENT is ignored, anything else is a parse error), de-indexed like the vertices; the primitives of a mesh node share the node's
+ * weights, whose defaults are mesh.weights.  The pointers are borrowed from the scene.  n_sets == 0: the file has none.  hjr_scene_view is
+ * the rest pose either way.  No reference counterpart: the reference ignores morph data. */
+int hjr_scene_get_morph(const hjr_scene*, hjr_morph* out);
+/* the weights at `time`: the defaults, or the keys of the node's animation channel with "path": "weights", sampled like every other channel
+ * (linear, "interpolation" not read, the sampler picked by channel index).  n must equal hjr_morph.n_weights. */
+int hjr_scene_eval_morph_weights(const hjr_scene*, float time, float* weights, uint32_t n);
 /* camera block of the frame loop — renderer/renderer.h:1145-1169 */
 int hjr_scene_eval_camera(const hjr_scene*, const hjr_render_option*, float time, hjr_camera* out);
 /* Texture(LUT_path, NonColor) — renderer/texture.h:16-39, loader/texture_load.h:7-20: 8-bit RGBA, caller frees with hjr_free */
@@ -432,6 +463,21 @@ int hjr_set_lut(hjr_ctx*, const uint8_t* rgba, int w, int h);
 /* setSky — renderer.h:802-851: equirect float4 IBL texture (wrap, linear, element read).  NULL restores the 1x1 texel
  * `hjr_params.sky` (scene_sky_default).  Direction -> (u, v): u = atan2(d.z, d.x) / 2pi + 0.5, v = acos(d.y) / pi (build-defined). */
 int hjr_set_sky(hjr_ctx*, const float* rgba32f, int w, int h);
+/* Deforming meshes (above).  The three calls below take effect at the next hjr_prepare_transforms (hjr_set_transforms), which then is not
+ * "unchanged" even with the transforms of the current frame data; they must NOT run concurrently with hjr_prepare_transforms, nor between it
+ * and its hjr_commit_transforms.  Like hjr_set_sky they end an unfinished progressive frame (a later pass with sample_begin > 0 is
+ * HJR_ERR_STATE), and they drop the temporal history: that stage reprojects rigidly through the instance transforms and cannot follow a
+ * deforming surface.  With "device_bvh_instances" they make the next commit build the topology again.  A commit that differs from the
+ * previous one only in geometry is a refit under the ordinary policy of "device_bvh_refit".  Errors are HJR_ERR_ARG with hjr_last_error
+ * naming the cause, and change nothing.  A vertex made non-finite is caught by the builders ("non-finite vertex after transform"); the
+ * previous frame data stays current.  hjr_upload_scene removes the morph.
+ * hjr_update_vertices: overwrites [first_vertex, first_vertex + n_vertices) of the base positions, and of the base normals unless `normals`
+ * is NULL (float3 each): the entry for deformation the caller computes (skinning, cloth).  The arrays are free on return. */
+int hjr_update_vertices(hjr_ctx*, uint32_t first_vertex, uint32_t n_vertices, const float* positions, const float* normals);
+/* hjr_set_morph: the morph sets and their default weights; everything is copied.  NULL or n_sets == 0 removes the morph. */
+int hjr_set_morph(hjr_ctx*, const hjr_morph*);
+/* hjr_set_morph_weights: n must equal hjr_morph.n_weights. */
+int hjr_set_morph_weights(hjr_ctx*, const float* weights, uint32_t n);
 /* Params fill + optixLaunch + CUDA_SYNC_CHECK + AOV D->H — renderer.h:1175-1242, 103-136.
  * Host buffers, width*height*4 floats each (albedo/normal may be NULL).  Synchronous. */
 int hjr_render(hjr_ctx*, const hjr_params*, float* aov_color, float* aov_albedo, float* aov_normal);
