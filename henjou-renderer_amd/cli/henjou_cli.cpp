@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "../host/frame_loop.hpp"
 #include "../host/render_job.hpp"
 
 #define HIPX(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fprintf(stderr, "henjou_cli[%d]: %s: %s\n", rank, #call, hipGetErrorString(e_)); return 1; } } while (0)
@@ -125,23 +126,18 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
         p.rank = (uint32_t)rank; p.world_size = (uint32_t)world; p.flags |= HJR_FLAG_PACKED;
         const auto t0 = std::chrono::steady_clock::now();
         // "passes": the frame in sample passes, split as hjr_render_file splits it; the last pass leaves the frame's tiles in d_packed
-        uint32_t n_done = 0, begin = 0;
-        for (const uint32_t end : hjr::pass_ends(p.spp, opt.passes ? opt.passes : 1u)) {
-            if (end <= begin) continue; // (a frame of no samples has no pass)
-            if (opt.passes > 1) { p.sample_begin = begin; p.sample_end = end; }
-            HJRX(hjr_render_device_var(ctx, &p, d_packed, d_albedo, d_normal, d_var, st)); // (Default: the colour alone, hjr_render_device's launch)
-            begin = end;
-            n_done++;
-            if (adaptive && p.sample_end && !(p.sample_begin == 0 && p.sample_end == p.spp)) { // (a frame of a single pass is a whole-frame render: not adaptive)
-                hjr_adaptive_state as;
-                HJR_INIT(as);
-                HJRX(hjr_get_adaptive_state(ctx, &as));
-                if (as.active_tiles == 0 || end == p.spp)
-                    fprintf(stderr, "[henjou %d/%d] frame %u: adaptive: %u of %u tiles active at %u spp, %llu samples rendered\n", rank, world, f, as.active_tiles, as.owned_tiles,
-                            as.sample_end, (unsigned long long)as.samples_rendered);
-                if (as.active_tiles == 0) break;
-            }
-        }
+        // (no after_pass hook: a per-pass hjr_get_stats would wait for the device; a frame of a single pass is a whole-frame render, not adaptive)
+        std::function<int(hjr_adaptive_state&)> adaptive_state;
+        if (adaptive) adaptive_state = [ctx](hjr_adaptive_state& as) { return hjr_get_adaptive_state(ctx, &as); };
+        hjr_params_window pass = pw; // (the passes' ranges go into this copy: `p` stays the whole frame, which rank 0 ends below)
+        const hjr::PassRun run = hjr::render_passes(hjr::pass_ends(p.spp, opt.passes ? opt.passes : 1u), pass.p, opt.passes > 1, [&](hjr_params& q) {
+            return hjr_render_device_var(ctx, &q, d_packed, d_albedo, d_normal, d_var, st); // (Default: the colour alone, hjr_render_device's launch)
+        }, nullptr, adaptive_state);
+        if (run.rc != HJR_OK) { fprintf(stderr, "henjou_cli[%d]: sample pass %u of frame %u -> %d: %s\n", rank, run.done + 1, f, run.rc, hjr_last_error()); return 1; }
+        const uint32_t n_done = run.done;
+        if (run.queried)
+            fprintf(stderr, "[henjou %d/%d] frame %u: adaptive: %u of %u tiles active at %u spp, %llu samples rendered\n", rank, world, f, run.state.active_tiles,
+                    run.state.owned_tiles, run.state.sample_end, (unsigned long long)run.state.samples_rendered);
         NCCLX(ncclGather(d_packed, d_all, rank_floats, ncclFloat, 0, comm, st)); // the one data-path collective of a frame
         if (rank == 0 && denoise) { // the gathered blocks -> frames -> (temporal accumulation) -> filter -> (upscale), all on st
             hjr_shards sh;
@@ -151,7 +147,6 @@ static int run_rank(const char* json, int rank, int world, int id_fd)
             sh.variance = with_var ? d_all + block * 12 : nullptr;
             hjr_params whole = p; // the gather follows the frame's last pass: rank 0 ends the frame (the history advances once per frame)
             whole.struct_size = (uint32_t)sizeof(whole); // (a plain hjr_params: the Denoise modes take no window)
-            whole.sample_begin = whole.sample_end = 0;
             HJRX(hjr_denoise_shards_device(ctx, &whole, opt.render_mode, &sh, d_frame, OW, OH, st));
             HIPX(hipMemcpyAsync(frame.data(), d_frame, frame.size() * 4, hipMemcpyDeviceToHost, st));
         } else if (rank == 0) {
